@@ -12,7 +12,12 @@ images (image i is a pure function of i) is cut into contiguous shards (parallel
 compare the gathered records with a 1-GPU pass over the same images.
 Metric: images/sec over all GPUs (weak scaling: `--batch` images per GPU).
 
-The JSON line also carries
+A plain run sets up, warms up (`--warmup` steps), times `--steps` steps, writes the outputs of the last timed step when
+`--dump-outputs DIR` is given (dump_outputs: the same arguments give the same inputs on every run) and prints one JSON line:
+`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (milliseconds per timed step), `steps`, `warmup`,
+`config`, and `verify` / the exchange timing where they apply.
+
+With `--full` it measures and checks everything else after the timed steps, and the JSON line also carries
   roofline     -- the dominant kernel family (most time per step).  YOLOv3: a conv family on FP32 MFMA --
                   `frac` = multiplies actually issued on the matrix pipe / the 157.3 TFLOP/s FP32-MFMA peak;
                   `algorithmic_frac` = direct-form FLOPs / peak (exceeds `frac` by 2.25x for the Winograd kernel,
@@ -26,6 +31,9 @@ The JSON line also carries
   parity_check -- the timed step's own records against the oracle (first images of the batch): NMS decisions exact, and --
                   with the CPU baseline's oracle forward at hand -- scores / boxes within 1e-4 and the detection sets equal
                   wherever no decision sits inside the observed round-off; a failure exits with code 4
+  power        -- board power and shader clock while the step keeps replaying (rocm-smi, when present)
+  other_configs, float32_mfma_only, summary -- for the default headline command: short runs of the other BASELINE
+                  configs, the same step on the float32 matrix instruction only, and a compact digest as the last key
 `--nms-worst` measures the isolated NMS worst cases of SURVEY 8d instead (512 boxes in 1 / in 80 classes).
 `--profile` is the command to put behind `rocprofv3 ... --`: nothing but warm-up and timed passes is launched.
 """
@@ -53,37 +61,61 @@ WORKLOADS = {
 }
 
 
+def positive_int(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f'must be >= 1, got {v}')
+    return v
+
+
+def non_negative_int(s):
+    v = int(s)
+    if v < 0:
+        raise argparse.ArgumentTypeError(f'must be >= 0, got {v}')
+    return v
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=10)
-    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--steps', type=positive_int, default=10, help='timed steps')
+    ap.add_argument('--warmup', type=non_negative_int, default=3, help='untimed steps before the timed ones')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: per-kernel stages and roofline (an eager pricing pass), the '
+                         'NMS p50 loop, board power, the CPU baseline, the parity check against the CPU oracle (exit code 4 '
+                         'when it fails) and, for the default headline, the other configs and the float32-MFMA-only step')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps: write what the last timed step returned (detection records and the '
+                         'candidates they were selected from) as float32 / float64 DIR/<name>.npy, at most 64 MB in all')
     ap.add_argument('--batch', type=int, default=None, help='images per GPU (default: the BASELINE batch of --config)')
     ap.add_argument('--size', type=int, default=640)
     ap.add_argument('--config', default='yolov3_80', help='yolov3_80 (headline) | efficientdet-d1 | d1_fcs2_atss')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--graph', action='store_true', help='(default) replay the step from a captured hipGraph')
     ap.add_argument('--eager', action='store_true', help='issue every launch of the step from the host instead of replaying a hipGraph')
     ap.add_argument('--verify', action='store_true',
                     help='after the timed region: the gathered records must equal a 1-GPU pass over the same global batch')
     ap.add_argument('--nms-worst', action='store_true', help='isolated NMS worst cases (512 boxes, 1 and 80 classes)')
-    ap.add_argument('--cpu-sample-batch', type=int, default=2)
-    ap.add_argument('--cpu-repeats', type=int, default=5)
+    ap.add_argument('--cpu-sample-batch', type=int, default=2, help='with --full: images of the CPU baseline')
+    ap.add_argument('--cpu-repeats', type=int, default=5, help='with --full: timed repeats of the CPU baseline')
     ap.add_argument('--cpu-threads', type=int, default=16)
     ap.add_argument('--parity-images', type=int, default=6,
-                    help='images of the timed batch the parity check compares with the CPU oracle forward (the CPU baseline sample '
-                         'covers the first --cpu-sample-batch of them; the rest cost one more oracle forward each)')
+                    help='with --full: images of the timed batch the parity check compares with the CPU oracle forward (the CPU '
+                         'baseline sample covers the first --cpu-sample-batch of them; the rest cost one more oracle forward each)')
     ap.add_argument('--dry-run-launch', action='store_true', help='with --gpus N > 1: print the launcher command as JSON and exit')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='headline run only: skip the short runs of the other single-GPU BASELINE configs (`other_configs`)')
-    ap.add_argument('--no-power-probe', action='store_true', help='skip the 1.5 s of extra replays under rocm-smi sampling (board power, shader clock)')
+                    help='with --full, headline run only: skip the short runs of the other single-GPU BASELINE configs (`other_configs`)')
+    ap.add_argument('--no-power-probe', action='store_true', help='with --full: skip the 3 s of extra replays under rocm-smi sampling (board power, shader clock)')
     ap.add_argument('--lanes', default=None,
                     help="batch lanes of the replayed graph: a number, 'auto' (capture with 1 and 2, keep the faster: rank 0 decides "
                          "for all ranks), default: MYDET_LANES or the model's batch_lanes_hint -- the rule api.Detector uses")
     ap.add_argument('--profile', action='store_true',
                     help='for rocprofv3: only capture warm-up + warm-up + timed replays run (no lane trial, no pricing pass, no NMS '
                          'p50 loop, no CPU baseline): every kernel count in the trace = launches per step x `passes` of the JSON line')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.profile and args.dump_outputs:
+        ap.error('--dump-outputs launches copies after the timed steps: not with --profile')
+    return args
 
 
 def launch_command(args, port, argv=None):
@@ -265,6 +297,53 @@ def parity_check(cand, rec, conf, nms, oracle_cand=None, images=2, extra_conf=()
     return out
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(path, rec, cand, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: what the timed path returned in its last step, as DIR/<name>.npy in float32 / float64 (integers as
+    float64, exact), so that two builds can be compared output for output on the same seeded inputs:
+      records_{count,bbox,score,class_idx,index} -- the detection records a caller receives (rows >= count are zero);
+                                                    with N > 1 GPUs the gathered records of the whole global batch
+      candidates_{bbox,score,class_idx}          -- the candidates they were selected from (this rank's shard), [B, N, ...]
+    At most `budget` bytes in all: when the candidates do not fit, a fixed sample of them (positions drawn with `seed` over
+    the flattened [B, N], in ascending order) is written instead, with its positions as candidates_position.npy.
+    Returns a description for the JSON line."""
+    import numpy as np
+    import torch
+    arrays = {'records_count': rec['count'].cpu().numpy().astype(np.float64),
+              'records_bbox': rec['bbox'].cpu().numpy().astype(np.float32),
+              'records_score': rec['score'].cpu().numpy().astype(np.float32),
+              'records_class_idx': rec['class_idx'].cpu().numpy().astype(np.float64),
+              'records_index': rec['index'].cpu().numpy().astype(np.float64)}
+    bb, ci, sc = cand
+    B, N = sc.shape
+    left = budget - sum(a.nbytes + 128 for a in arrays.values()) - 4 * 128        # 128: an .npy header
+    per_cand = 4 * 4 + 4 + 4                                                         # bbox, score, class id (float32)
+    if B * N * per_cand <= left:
+        sample = None
+        arrays.update({'candidates_bbox': bb.cpu().numpy().astype(np.float32),
+                       'candidates_score': sc.cpu().numpy().astype(np.float32),
+                       'candidates_class_idx': ci.cpu().numpy().astype(np.float32)})
+    else:
+        k = max(0, left // (per_cand + 8))                                             # + the float64 position
+        sample = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(B * N, size=k, replace=False))
+        pos = torch.from_numpy(sample).to(bb.device)
+        arrays.update({'candidates_bbox': bb.reshape(B * N, 4)[pos].cpu().numpy().astype(np.float32),
+                       'candidates_score': sc.reshape(B * N)[pos].cpu().numpy().astype(np.float32),
+                       'candidates_class_idx': ci.reshape(B * N)[pos].cpu().numpy().astype(np.float32),
+                       'candidates_position': sample.astype(np.float64)})
+    assert int(np.abs(arrays['candidates_class_idx']).max(initial=0)) < 1 << 24      # class ids exact in float32
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+        total += os.path.getsize(os.path.join(path, name + '.npy'))
+    assert total <= budget, total
+    return {'dir': path, 'files': sorted(n + '.npy' for n in arrays), 'bytes': total,
+            'candidates': 'all' if sample is None else f'{len(sample)} of {B * N} (seeded sample, positions over [B, N])'}
+
+
 def nms_worst_cases(dev, iters=200, warm=20):
     """exactly 512 boxes per image in 1 class and spread over 80 classes, B = 1 and B = 32; p50 / p95 of
     the post-process launch over `iters` stream-synchronised iterations (HIP events around each launch)."""
@@ -332,16 +411,17 @@ def main():
 
     ctx = {'dev': dev, 'world': world, 'rank': rank, 'dist_on': dist_on, 'rehearse': rehearse}
     out, code = measure(args, ctx)
-    # the other single-GPU BASELINE configs, briefly, inside the driver's default command (the headline fields above stay as
-    # they are): configs[2], configs[3] and the 512 x 512 batch north_star asks for -- value, roofline and parity gate each
-    if (out is not None and world == 1 and not dist_on and args.config == 'yolov3_80' and args.size == 640 and args.batch is None
-            and not args.eager and not args.no_other_configs and not args.verify):
+    # --full: the other single-GPU BASELINE configs, briefly, after the headline (the headline fields above stay as they
+    # are): configs[2], configs[3] and the 512 x 512 batch north_star asks for -- value, roofline and parity gate each
+    if (args.full and out is not None and world == 1 and not dist_on and args.config == 'yolov3_80' and args.size == 640
+            and args.batch is None and not args.eager and not args.no_other_configs and not args.verify):
         others = {}
         for name, key, bsz, size in OTHER_CONFIGS:
             a = argparse.Namespace(**vars(args))
             a.config, a.batch, a.size = name, bsz, size
             a.steps, a.warmup = min(args.steps, 10), min(args.warmup, 3)
             a.no_cpu_baseline, a.parity_images, a.lanes, a.no_power_probe = True, 2, None, True
+            a.dump_outputs = None                                # the dump is the headline's
             t0 = time.perf_counter()
             o, c = measure(a, ctx)
             code = code or c
@@ -353,6 +433,7 @@ def main():
         if ops.SPLIT_BF16:
             a = argparse.Namespace(**vars(args))
             a.steps, a.warmup, a.no_cpu_baseline, a.parity_images, a.no_power_probe = min(args.steps, 10), min(args.warmup, 3), True, 2, True
+            a.dump_outputs = None
             t0 = time.perf_counter()
             ops.SPLIT_BF16 = False
             try:
@@ -365,7 +446,8 @@ def main():
                                         'note': 'the same step with every direct conv on v_mfma_f32_32x32x2_f32 (no split-bf16 kernels)',
                                         'wall_s': round(time.perf_counter() - t0, 1)}
     if out is not None:
-        out['summary'] = summary_of(out)          # LAST key, < 1 500 characters: what a 2 000-character tail of this line still shows
+        if args.full:
+            out['summary'] = summary_of(out)      # LAST key, < 1 500 characters: what a 2 000-character tail of this line still shows
         print(json.dumps(out))
     if dist_on:
         torch.distributed.destroy_process_group()
@@ -506,6 +588,8 @@ def measure(args, ctx):
             graphed = GraphedPath(model, x, conf, nms, lanes=n_l)
         assert graphed.lanes == n_l
 
+    last_cand = []                         # eager timed steps: the candidates of the latest one (for --dump-outputs)
+
     def local_records(inp=None, pricing=False):
         if graphed is not None and inp is None:
             return graphed()
@@ -521,6 +605,8 @@ def measure(args, ctx):
                     out = batched_post_process(bb, ci, sc, conf, nms)
                 return out
             bb, ci, sc = model.forward_candidates(src)
+            if inp is None:
+                last_cand[:] = (bb, ci, sc)
             return batched_post_process(bb, ci, sc, conf, nms)
 
     exchange = []                          # (start, end) HIP events around the all-gather of every step, on the launch stream
@@ -558,8 +644,13 @@ def measure(args, ctx):
     barrier()
     elapsed = time.perf_counter() - t0
     timer, ops.TIMER = ops.TIMER, None
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything else runs: the static buffers of a replayed graph hold what the last timed step returned
+        dumped = dump_outputs(args.dump_outputs, rec, graphed.cand if graphed is not None else tuple(last_cand))
     power = None
-    if rank == 0 and world == 1 and not dist_on and not args.profile and not getattr(args, 'no_power_probe', False):
+    if (args.full and rank == 0 and world == 1 and not dist_on and not args.profile
+            and not getattr(args, 'no_power_probe', False)):
         power = power_probe(step)
 
     # launches of the step's kernels over the whole process: GraphedPath runs two eager warm-up passes before a capture
@@ -581,6 +672,77 @@ def measure(args, ctx):
                               'note': 'profile run: every kernel of the step appears launches-per-step x passes times in the trace'}))
         return None, 0
 
+    if dist_on:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        elapsed = float(t.item())
+
+    verify = None
+    if args.verify:
+        # rank 0 runs every shard's images through its own GPU, in the shard composition the ranks used, and the
+        # gathered records must equal that bit for bit (count, candidate indices, classes, scores, boxes)
+        ok, checked = True, 0
+        if rank == 0:
+            got = {k: v.clone() for k, v in rec.items() if k != 'records'}
+            for r in range(world):
+                rlo, rhi = parallel.shard_range(total, r, world)
+                xr = x if r == 0 else synth.make_image_set(rlo, rhi, args.size, cfg['general.input_format']).to(dev)
+                ref = local_records(xr)
+                for k in ('count', 'index', 'class_idx', 'score', 'bbox'):
+                    ok = ok and torch.equal(got[k][rlo:rhi], ref[k])
+                checked += rhi - rlo
+            ok = ok and got['count'].shape[0] == total and int(got['count'].sum()) > 0
+        verify = {'ok': bool(ok), 'images': checked, 'against': '1-GPU pass over the same global batch (rank 0)'}
+
+    # the headline figure: what a plain run reports
+    images = total * args.steps
+    headline = args.config == 'yolov3_80'
+    out = {
+        'metric': (f'images/sec at batch {batch}, {args.size}x{args.size}, YOLOv3-80 (backbone -> FPN -> head -> decode -> NMS)'
+                   if headline else f'images/sec at batch {batch}, {args.size}x{args.size}, {args.config} (backbone -> BiFPN -> head -> decode -> NMS)'),
+        'value': round(images / elapsed, 2),
+        'unit': 'images/sec',
+        'n_gpus': world,
+        'steps': args.steps,
+        'warmup': args.warmup,
+        'ms_per_step': round(elapsed / args.steps * 1e3, 3),
+        'higher_is_better': True,
+        'scaling': 'weak',
+        'vs_baseline': None,
+        'dtype': 'f32',
+        'arithmetic': ('float32 values and float32 accumulation throughout; ' +
+                       ('direct convs with Cin % 16 == 0 form their float32 products from exact three-piece bfloat16 splits of both '
+                        'operands (six v_mfma_f32_32x32x16_bf16 piece products per k-step; results equal the float32-instruction '
+                        "kernel's to float32 round-off; MYDET_CONV_SPLIT_BF16=0 turns it off)" if ops.SPLIT_BF16 else
+                        'every matrix product on v_mfma_f32_* (MYDET_CONV_SPLIT_BF16=0)')),
+        'data': 'synthetic',
+        'config': {'workload': f'{WORKLOADS.get(args.config, args.config)}, batch {batch}/GPU, {args.size}x{args.size}, '
+                               'random-init calibrated weights' + (f', hipGraph replay ({graphed.lanes} batch lane{"s" if graphed.lanes > 1 else ""} per GPU)' if args.graph else ', eager launches'),
+                   'global_batch': total, 'image_size': args.size, 'parallelism': f'dp{world}',
+                   'batch_lanes': graphed.lanes if graphed is not None else 1,
+                   'batch_lanes_rule': lanes_rule, 'batch_lanes_per_rank': lanes_per_rank if graphed is not None else [1] * world,
+                   'passes': passes,
+                   'exchange': f'one all-gather of {parallel.WORDS * 4} B detection records per image' if world > 1 else 'none'},
+    }
+    if dist_on:
+        out['rccl_ranks'] = torch.distributed.get_world_size()
+        out['exchange_backend'] = str(torch.distributed.get_backend())
+        # the line's n_gpus is a claim about what exchanged records: every rank of the RCCL group is one of the N GPUs
+        assert out['rccl_ranks'] == world == args.gpus, (out['rccl_ranks'], world, args.gpus)
+        assert out['exchange_backend'] == 'nccl', out['exchange_backend']
+        out['rccl_ranks_equal_n_gpus'] = True
+        out['exchange_ms_per_step'] = round(sum(a.elapsed_time(b) for a, b in exchange) / max(1, len(exchange)), 4)
+        out['exchange_note'] = ('HIP events on the launch stream around the one all_gather_into_tensor of the step (rank 0; it includes '
+                                'waiting for the slowest rank to arrive)')
+    if verify is not None:
+        out['verify'] = verify
+    if dumped is not None:
+        out['outputs'] = dumped
+    code = 3 if verify is not None and rank == 0 and not verify['ok'] else 0
+    if not args.full:
+        return (out if rank == 0 else None), code
+
+    # --full from here on: per-kernel stages and roofline, NMS latency, CPU baseline, parity check against the oracle
     # the parity check's GPU side: the candidates and records of the LAST TIMED STEP (first images of this rank's shard)
     n_pc = max(1, min(args.parity_images, batch))
     with torch.no_grad():
@@ -616,28 +778,6 @@ def measure(args, ctx):
     torch.cuda.synchronize()
     nms_spans = sorted(a.elapsed_time(b) for a, b in nms_spans)
     del cand
-
-    if dist_on:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        elapsed = float(t.item())
-
-    verify = None
-    if args.verify:
-        # rank 0 runs every shard's images through its own GPU, in the shard composition the ranks used, and the
-        # gathered records must equal that bit for bit (count, candidate indices, classes, scores, boxes)
-        ok, checked = True, 0
-        if rank == 0:
-            got = {k: v.clone() for k, v in rec.items() if k != 'records'}
-            for r in range(world):
-                rlo, rhi = parallel.shard_range(total, r, world)
-                xr = x if r == 0 else synth.make_image_set(rlo, rhi, args.size, cfg['general.input_format']).to(dev)
-                ref = local_records(xr)
-                for k in ('count', 'index', 'class_idx', 'score', 'bbox'):
-                    ok = ok and torch.equal(got[k][rlo:rhi], ref[k])
-                checked += rhi - rlo
-            ok = ok and got['count'].shape[0] == total and int(got['count'].sum()) > 0
-        verify = {'ok': bool(ok), 'images': checked, 'against': '1-GPU pass over the same global batch (rank 0)'}
 
     summ = timer.summary()
     stages = {k: {'launches_per_step': v[0] / args.steps, 'ms_per_step': round(v[1] / args.steps, 4)} for k, v in summ.items()}
@@ -761,60 +901,20 @@ def measure(args, ctx):
                      'algorithmic_bytes_per_launch': round(timer.bytes.get(dom, 0.0) / n_k) if n_k else None,
                      'launches_per_step': n_k / args.steps, 'avg_launch_ms': round(ms_k / n_k, 4)})
 
-    images = total * args.steps
-    headline = args.config == 'yolov3_80'
-    out = {
-        'metric': (f'images/sec at batch {batch}, {args.size}x{args.size}, YOLOv3-80 (backbone -> FPN -> head -> decode -> NMS)'
-                   if headline else f'images/sec at batch {batch}, {args.size}x{args.size}, {args.config} (backbone -> BiFPN -> head -> decode -> NMS)'),
-        'value': round(images / elapsed, 2),
-        'unit': 'images/sec',
-        'n_gpus': world,
-        'steps': args.steps,
-        'warmup': args.warmup,
-        'ms_per_step': round(elapsed / args.steps * 1e3, 3),
+    out.update({
         'kernel_ms_per_step': round(kernel_ms, 3),
         'timer': ('HIP events on the launch stream; eager runs chain them (the event closing one launch opens the next), so '
                   'per-kernel times include inter-launch gaps and kernel_ms_per_step ~ ms_per_step by construction'
                   if not args.graph else 'HIP events on the launch stream around each launch of an eager re-run after the replayed timed '
                   'region (the same kernels: with batch lanes the lanes\' launch sequences one after the other on one stream)'),
-        'higher_is_better': True,
-        'scaling': 'weak',
-        'vs_baseline': None,
-        'dtype': 'f32',
-        'arithmetic': ('float32 values and float32 accumulation throughout; ' +
-                       ('direct convs with Cin % 16 == 0 form their float32 products from exact three-piece bfloat16 splits of both '
-                        'operands (six v_mfma_f32_32x32x16_bf16 piece products per k-step; results equal the float32-instruction '
-                        "kernel's to float32 round-off; MYDET_CONV_SPLIT_BF16=0 turns it off)" if ops.SPLIT_BF16 else
-                        'every matrix product on v_mfma_f32_* (MYDET_CONV_SPLIT_BF16=0)')),
-        'data': 'synthetic',
-        'config': {'workload': f'{WORKLOADS.get(args.config, args.config)}, batch {batch}/GPU, {args.size}x{args.size}, '
-                               'random-init calibrated weights' + (f', hipGraph replay ({graphed.lanes} batch lane{"s" if graphed.lanes > 1 else ""} per GPU)' if args.graph else ', eager launches'),
-                   'global_batch': total, 'image_size': args.size, 'parallelism': f'dp{world}',
-                   'batch_lanes': graphed.lanes if graphed is not None else 1,
-                   'batch_lanes_rule': lanes_rule, 'batch_lanes_per_rank': lanes_per_rank if graphed is not None else [1] * world,
-                   'passes': passes,
-                   'exchange': f'one all-gather of {parallel.WORDS * 4} B detection records per image' if world > 1 else 'none'},
         'roofline': roofline,
         'stages': stages,
         'nms_p50_ms': stages['postprocess']['p50_ms'],
         'power': power,
-    }
+    })
     n_lanes = graphed.lanes if graphed is not None else 1
     out['launches_per_lane'] = round(sum(v[0] for v in summ.values()) / args.steps / n_lanes, 1)
-    if dist_on:
-        out['rccl_ranks'] = torch.distributed.get_world_size()
-        out['exchange_backend'] = str(torch.distributed.get_backend())
-        # the line's n_gpus is a claim about what exchanged records: every rank of the RCCL group is one of the N GPUs
-        assert out['rccl_ranks'] == world == args.gpus, (out['rccl_ranks'], world, args.gpus)
-        assert out['exchange_backend'] == 'nccl', out['exchange_backend']
-        out['rccl_ranks_equal_n_gpus'] = True
-        out['exchange_ms_per_step'] = round(sum(a.elapsed_time(b) for a, b in exchange) / max(1, len(exchange)), 4)
-        out['exchange_note'] = ('HIP events on the launch stream around the one all_gather_into_tensor of the step (rank 0; it includes '
-                                'waiting for the slowest rank to arrive)')
-    if verify is not None:
-        out['verify'] = verify
     oracle_cand = None
-    code = 0
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'], oracle_cand = cpu_baseline(args.config, cfg, args.size, args.cpu_sample_batch, args.cpu_repeats, args.cpu_threads)
         out['cpu_baseline']['gpu_over_cpu'] = round(out['value'] / out['cpu_baseline']['value'], 1)
@@ -832,8 +932,6 @@ def measure(args, ctx):
             oracle_cand = tuple(np.concatenate([p_[j] for p_ in parts]) for j in range(3))
         extra_conf = sorted({0.05, float(cfg.get('test.default_conf_thres', 0.5))} - {float(conf)})
         out['parity_check'] = parity_check(pc_cand, pc_rec, conf, nms, oracle_cand, images=n_pc, extra_conf=extra_conf)
-    if verify is not None and rank == 0 and not verify['ok']:
-        code = 3
     if rank == 0 and not out['parity_check']['ok']:
         code = code or 4
     return (out if rank == 0 else None), code

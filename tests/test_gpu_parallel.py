@@ -61,7 +61,7 @@ def test_bench_rehearsal_with_verify(monkeypatch, capsys):
     monkeypatch.setenv('MASTER_PORT', str(_free_port()))
     monkeypatch.setenv('MYDET_REHEARSE_RCCL', '1')
     monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '3',
-                                      '--size', '256', '--verify', '--no-cpu-baseline'])
+                                      '--size', '256', '--verify', '--no-cpu-baseline', '--full'])
     sys.path.insert(0, ROOT)
     import bench
     bench.main()

@@ -569,6 +569,65 @@ def test_bench_parity_check_logic():
         assert not bench.parity_check(cand, r2, conf, nms, oracle_cand=None, images=B)['ok'], tamper
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_options():
+    """A plain bench run is the headline only; --full turns on everything else; --steps is the number of timed steps and
+    must be at least one; --dump-outputs cannot go with --profile (which launches nothing but the steps)."""
+    bench = _bench_module()
+    a = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '0'])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 0)
+    a = bench.parse_args(['--full', '--dump-outputs', 'out'])
+    assert a.full and a.dump_outputs == 'out'
+    for bad in (['--steps', '0'], ['--warmup', '-1'], ['--profile', '--dump-outputs', 'out']):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the records and candidates of the last timed step as float32 / float64 .npy files, integers
+    exact, within the byte budget; a candidate set over the budget is replaced by the same seeded sample on every call."""
+    import numpy as np
+    bench = _bench_module()
+    rng = np.random.Generator(np.random.PCG64(11))
+    B, N, K = 3, 5000, 512
+    count = torch.tensor([4, 0, 512], dtype=torch.int32)
+    rec = {'count': count, 'bbox': torch.from_numpy(rng.random((B, K, 4), dtype=np.float32)),
+           'score': torch.from_numpy(rng.random((B, K), dtype=np.float32)),
+           'class_idx': torch.from_numpy(rng.integers(0, 80, (B, K))), 'index': torch.from_numpy(rng.integers(0, N, (B, K)).astype(np.int32))}
+    cand = (torch.from_numpy(rng.random((B, N, 4), dtype=np.float32)), torch.from_numpy(rng.integers(0, 80, (B, N))),
+            torch.from_numpy(rng.random((B, N), dtype=np.float32)))
+    d = bench.dump_outputs(str(tmp_path / 'all'), rec, cand)
+    assert d['candidates'] == 'all' and d['bytes'] <= bench.DUMP_BUDGET_BYTES
+    files = sorted(os.listdir(tmp_path / 'all'))
+    assert files == d['files'] and len(files) == 8
+    for f in files:
+        a = np.load(tmp_path / 'all' / f)
+        assert a.dtype in (np.float32, np.float64), f
+    np.testing.assert_array_equal(np.load(tmp_path / 'all' / 'records_count.npy'), count.numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / 'all' / 'records_class_idx.npy'), rec['class_idx'].numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / 'all' / 'records_index.npy'), rec['index'].numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / 'all' / 'candidates_bbox.npy'), cand[0].numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / 'all' / 'candidates_class_idx.npy'), cand[1].numpy())
+
+    budget = 200_000                                              # records ~55 kB: room for a few thousand candidates of 15 000
+    s1 = bench.dump_outputs(str(tmp_path / 's1'), rec, cand, budget=budget)
+    s2 = bench.dump_outputs(str(tmp_path / 's2'), rec, cand, budget=budget)
+    assert s1['candidates'] != 'all' and s1['bytes'] <= budget
+    pos = np.load(tmp_path / 's1' / 'candidates_position.npy')
+    assert 0 < len(pos) < B * N and (np.diff(pos) > 0).all()
+    np.testing.assert_array_equal(pos, np.load(tmp_path / 's2' / 'candidates_position.npy'))
+    flat = pos.astype(np.int64)
+    np.testing.assert_array_equal(np.load(tmp_path / 's1' / 'candidates_score.npy'), cand[2].numpy().reshape(-1)[flat])
+    np.testing.assert_array_equal(np.load(tmp_path / 's1' / 'candidates_bbox.npy'), cand[0].numpy().reshape(-1, 4)[flat])
+
+
 def test_bench_multi_gpu_launch_guard():
     """`python bench.py --gpus 8` on a machine without eight GPUs (this container has none): the launcher command is the
     driver's (`torch.distributed.run`, one rank per GPU, rendezvous on 127.0.0.1) and is built before anything touches a

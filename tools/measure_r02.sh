@@ -6,7 +6,7 @@ T=${MYDET_TOOL_TIMEOUT:-300}
 set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02; mkdir -p $O
 cd $R
-b() { name=$1; shift; timeout -k 5 $T python bench.py "$@" 2>$O/$name.err | tail -1 > $O/$name.json; python - <<PY
+b() { name=$1; shift; timeout -k 5 $T python bench.py --full "$@" 2>$O/$name.err | tail -1 > $O/$name.json; python - <<PY
 import json; d=json.load(open('$O/$name.json')); print('$name', d.get('value'), d.get('unit'), 'ms/step', d.get('ms_per_step'), 'frac', (d.get('roofline') or {}).get('frac'))
 PY
 }

@@ -6,7 +6,7 @@
 T=${MYDET_TOOL_TIMEOUT:-300}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04m; mkdir -p $O
 cd $R
-b() { name=$1; shift; timeout -k 5 $T python bench.py "$@" 2>$O/$name.err | tail -1 > $O/$name.json || echo "$name rc $?"; python - <<PY
+b() { name=$1; shift; timeout -k 5 $T python bench.py --full "$@" 2>$O/$name.err | tail -1 > $O/$name.json || echo "$name rc $?"; python - <<PY
 import json; d=json.load(open('$O/$name.json')); print('$name', d.get('value'), 'ms/step', d.get('ms_per_step'), 'frac', (d.get('roofline') or {}).get('frac'), 'parity', (d.get('parity_check') or {}).get('ok'))
 PY
 }

@@ -8,14 +8,14 @@ print('   parity_check', json.dumps(d.get('parity_check')))
 print('   roofline', json.dumps({k: v for k, v in (d.get('roofline') or {}).items() if k in ('bound','frac','achieved','kernel','traffic')})[:300])
 PY
 }
-timeout -k 5 400 python bench.py --steps 20 --warmup 5 > $O/bc_yolo.json 2>$O/bc_yolo.err || { echo "yolo rc $?"; tail -5 $O/bc_yolo.err; }
+timeout -k 5 400 python bench.py --full --steps 20 --warmup 5 > $O/bc_yolo.json 2>$O/bc_yolo.err || { echo "yolo rc $?"; tail -5 $O/bc_yolo.err; }
 show $O/bc_yolo.json
-timeout -k 5 400 python bench.py --steps 20 --warmup 5 --config efficientdet-d1 > $O/bc_d1.json 2>$O/bc_d1.err || { echo "d1 rc $?"; tail -5 $O/bc_d1.err; }
+timeout -k 5 400 python bench.py --full --steps 20 --warmup 5 --config efficientdet-d1 > $O/bc_d1.json 2>$O/bc_d1.err || { echo "d1 rc $?"; tail -5 $O/bc_d1.err; }
 show $O/bc_d1.json
-timeout -k 5 400 python bench.py --steps 20 --warmup 5 --config d1_fcs2_atss > $O/bc_fcos.json 2>$O/bc_fcos.err || { echo "fcos rc $?"; tail -5 $O/bc_fcos.err; }
+timeout -k 5 400 python bench.py --full --steps 20 --warmup 5 --config d1_fcs2_atss > $O/bc_fcos.json 2>$O/bc_fcos.err || { echo "fcos rc $?"; tail -5 $O/bc_fcos.err; }
 show $O/bc_fcos.json
 timeout -k 5 400 python bench.py --steps 10 --warmup 8 --profile > $O/bc_prof.json 2>$O/bc_prof.err || { echo "prof rc $?"; tail -5 $O/bc_prof.err; }
 cat $O/bc_prof.json
-timeout -k 5 400 python bench.py --steps 10 --warmup 3 --eager --no-cpu-baseline > $O/bc_eager.json 2>$O/bc_eager.err || { echo "eager rc $?"; tail -5 $O/bc_eager.err; }
+timeout -k 5 400 python bench.py --full --steps 10 --warmup 3 --eager --no-cpu-baseline > $O/bc_eager.json 2>$O/bc_eager.err || { echo "eager rc $?"; tail -5 $O/bc_eager.err; }
 show $O/bc_eager.json
 timeout -k 5 400 python -m pytest tests/test_gpu_parallel.py -q -x 2>&1 | tail -3

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r05; mkdir -p $O
 cd $R
 timeout -k 10 $T python -m pytest tests -m gpu -x -q > $O/first_pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/first_pytest.log
 tail -5 $O/first_pytest.log
-timeout -k 10 $T python bench.py --steps 20 --warmup 5 2>$O/first_bench.err | tail -1 > $O/first_bench.json; echo "bench rc=$?"
+timeout -k 10 $T python bench.py --full --steps 20 --warmup 5 2>$O/first_bench.err | tail -1 > $O/first_bench.json; echo "bench rc=$?"
 cut -c1-400 $O/first_bench.json
 timeout -k 10 60 python - > $O/first_occupancy.txt 2>&1 <<'PY'
 import ctypes, torch

@@ -9,7 +9,7 @@ for rep in 1 2; do
 for v in 1 0; do
   for spec in "efficientdet-d1 16" "d1_fcs2_atss 32"; do
     set -- $spec
-    MYDET_SE_IN_DW=$v timeout -k 10 120 python bench.py --config $1 --batch $2 --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs --parity-images 2 2>/dev/null | tail -1 | python -c "import sys,json; o=json.loads(sys.stdin.read()); print('se_in_dw=$v', '$1', o['value'], o['ms_per_step'], o['launches_per_lane'], o['parity_check']['ok'], {k: round(v['ms_per_step'],3) for k,v in o['stages'].items()})" | tee -a $O/se_ab.txt
+    MYDET_SE_IN_DW=$v timeout -k 10 120 python bench.py --full --config $1 --batch $2 --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs --parity-images 2 2>/dev/null | tail -1 | python -c "import sys,json; o=json.loads(sys.stdin.read()); print('se_in_dw=$v', '$1', o['value'], o['ms_per_step'], o['launches_per_lane'], o['parity_check']['ok'], {k: round(v['ms_per_step'],3) for k,v in o['stages'].items()})" | tee -a $O/se_ab.txt
   done
 done
 done

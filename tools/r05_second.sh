@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r05; mkdir -p $O
 cd $R
 timeout -k 10 $T python -m pytest tests -m gpu -q > $O/second_pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/second_pytest.log
 tail -8 $O/second_pytest.log
-timeout -k 10 $T python bench.py --steps 20 --warmup 5 2>$O/second_bench.err | tail -1 > $O/second_bench.json; echo "bench rc=$?"
+timeout -k 10 $T python bench.py --full --steps 20 --warmup 5 2>$O/second_bench.err | tail -1 > $O/second_bench.json; echo "bench rc=$?"
 cut -c1-300 $O/second_bench.json
 for per in 5 4; do
   for cfg in "efficientdet-d1" "d1_fcs2_atss" "yolov3_80"; do

@@ -6,7 +6,7 @@ timeout -k 5 120 tools/bin/hw_pk_probe 64 > $O/pk_probe_64.txt 2>&1; echo "probe
 timeout -k 5 120 tools/bin/hw_pk_probe 16 > $O/pk_probe_16.txt 2>&1; echo "probe16 rc $?"
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/gpu_tests.log 2>&1; echo "tests rc $?"; tail -3 $O/gpu_tests.log
 ab() { for rep in 1 2; do for lib in tmp_libs/libmydet_r05_pk.so mydetection_amd/lib/libmydet_hip.so; do
-  MYDET_LIB_PATH=$R/$lib timeout -k 5 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-power-probe "$@" 2>/dev/null | tail -1 | python -c "
+  MYDET_LIB_PATH=$R/$lib timeout -k 5 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-power-probe "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$lib', '$*', d['value'], d['ms_per_step'], (d.get('parity_check') or {}).get('ok'))"; done; done; }
 ab > $O/ab_yolo.txt 2>&1; cat $O/ab_yolo.txt
 ab --config efficientdet-d1 > $O/ab_d1.txt 2>&1; cat $O/ab_d1.txt

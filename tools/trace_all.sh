@@ -5,7 +5,7 @@ T=${MYDET_TOOL_TIMEOUT:-300}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; NAME=$1; shift
 D=$R/gpurun_out/trace_$NAME; rm -rf $D; mkdir -p $D
-timeout -k 5 $T rocprofv3 --kernel-trace --output-format csv -d $D -- python3 $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline "$@" > $D/log.txt 2>&1 || { tail -5 $D/log.txt; exit 1; }
+timeout -k 5 $T rocprofv3 --kernel-trace --output-format csv -d $D -- python3 $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline "$@" > $D/log.txt 2>&1 || { tail -5 $D/log.txt; exit 1; }
 python3 - > $R/gpurun_out/trace_$NAME.txt <<PY
 import csv, glob, collections
 f = glob.glob('$D/**/*kernel_trace.csv', recursive=True)[0]
