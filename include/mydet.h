@@ -461,6 +461,31 @@ int mydet_sepconv_decode_retina_f32(int n, const mydet_sepconv_decode_node *node
                                     int img_h, int img_w, float *bbox, int64_t *class_idx, float *score, int64_t N,
                                     void *stream);
 
+/* The lr_tb box layer of the EfficientDet + custom FCOS head (_LR_TB_last, models/rpns.py:208-229), every pyramid level
+ * of a batch in one launch:
+ *     dlr = depthwise3x3_pad1(x; W_lr0)   lr = conv(dlr; W_lr1 [2,C,1,3], pad (0,1)) + b_lr1
+ *     dtb = depthwise3x3_pad1(x; W_tb0)   tb = conv(dtb; W_tb1 [2,C,3,1], pad (1,0)) + b_tb1
+ *     y = (lr[0], tb[0], lr[1], tb[1]) per pixel
+ * (the second conv pads the depthwise OUTPUT with zeros).  x: logical [B,C,H,W] channels-last with pixel stride ldx >= C
+ * (4-byte aligned; 16-byte aligned with ldx % 4 == 0 takes vector loads).  y: [B,H,W,ldy], ldy % 4 == 0, 16-byte aligned:
+ * one 16-byte store of (l, t, r, b) per pixel.  w: the level's weights packed as (30 C + 4) floats, 16-byte aligned:
+ *     [0, 9C)    W_lr0 as [kh][kw][C]       [9C, 18C)  W_tb0 as [kh][kw][C]
+ *     [18C, 24C) W_lr1 as [o][kw][C]        [24C, 30C) W_tb1 as [o][kh][C]
+ *     [30C, 30C + 4) (b_lr1[0], b_tb1[0], b_lr1[1], b_tb1[1])
+ * `levels` is a HOST array of n (<= MYDET_LR_TB_MAX_LEVELS) descriptors sharing B and C; C % 4 == 0, C <= MYDET_LR_TB_MAX_C.
+ * Anything else returns MYDET_E_BADARG before any launch. */
+#define MYDET_LR_TB_MAX_LEVELS 8
+#define MYDET_LR_TB_MAX_C      128
+typedef struct {
+    const float *x;
+    int64_t ldx;
+    const float *w;
+    float *y;
+    int64_t ldy;
+    int H, W;
+} mydet_lr_tb_level;
+int mydet_lr_tb_levels_f32(int n, const mydet_lr_tb_level *levels, int B, int C, void *stream);
+
 /* Pairwise IoU [Na,Nb]; utils/bbox_ops.py:6-49 (xyxy != 0: corner format, else cxcywh). */
 int mydet_bboxes_iou_f32(const float *a, int Na, const float *b, int Nb, int xyxy,
                          float *iou, void *stream);

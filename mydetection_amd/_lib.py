@@ -60,6 +60,7 @@ SIGNATURES = {
     'mydet_sepconv_nodes_f32': [c_int, c_ptr, c_int, c_int, c_ptr],
     'mydet_stem_dw_f32': [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int,
                           c_int, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr],
+    'mydet_lr_tb_levels_f32': [c_int, c_ptr, c_int, c_int, c_ptr],
     'mydet_sepconv_decode_retina_f32': [c_int, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr],
     'mydet_bboxes_iou_f32': [c_ptr, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr],
     'mydet_bboxes_to_original_batched_f32': [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr],
@@ -112,6 +113,15 @@ class SepconvDecodeNode(ctypes.Structure):
 
 
 SEPCONV_MAX_NODES = 10
+
+
+class LrTbLevel(ctypes.Structure):
+    """mydet_lr_tb_level (include/mydet.h)."""
+    _fields_ = [('x', c_ptr), ('ldx', c_i64), ('w', c_ptr), ('y', c_ptr), ('ldy', c_i64), ('H', c_int), ('W', c_int)]
+
+
+LR_TB_MAX_LEVELS = 8                # MYDET_LR_TB_MAX_LEVELS of include/mydet.h
+LR_TB_MAX_C = 128                   # MYDET_LR_TB_MAX_C
 
 _lib = None
 

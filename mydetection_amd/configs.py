@@ -92,6 +92,15 @@ def _build():
     c.update(_test(640, 0.5))
     out['d1_fcs'] = c
 
+    # EfficientDet + custom FCOS: the box towers end in _LR_TB_last (configs/d1_fcs2s.json; d1_fcs2s_mos.json differs from
+    # it in training keys only)
+    for name in ('d1_fcs2s', 'd1_fcs2s_mos'):
+        c = _efficientnet_bifpn(128, True, 'conv')
+        c.update(_effrpn('effrpn', 1, True, **{'model.effrpn.bbox_last': 'lr_tb', 'model.effrpn.cls_last': 'spconv'}))
+        c.update({'model.pred_layer': 'FCOS2', 'model.fcos.anchors': _FCOS_RANGES, 'model.fcos2.ignored_threshold': 0.75})
+        c.update(_test(640, 0.45))
+        out[name] = c
+
     # registry composition on three pyramid levels (get_bifpn -> BiFPN3, models/fpns.py:302-303; the reference ships it
     # for its rotated-box model d1_rapid): d1_fcs2 with model.backbone.num_levels = 3
     c = _efficientnet_bifpn(32, False, None, levels=3)

@@ -5,7 +5,7 @@ from .. import ops
 import numpy as np
 import torch
 
-from .modules import prepare_wino, prepare_b3, FusedConvMixin, SeparableConv2d, SpconvBn, prepare_conv
+from .modules import prepare_wino, prepare_b3, FusedConvMixin, SeparableConv2d, SpconvBn, prepare_conv, _versions
 
 
 class RawPreds(dict):
@@ -97,12 +97,53 @@ class _LastConv(nn.Conv2d):
         return y[:, :cout]
 
 
+class _LR_TB_last(nn.Module):
+    '''
+    Box layer of the EfficientDet + custom FCOS head (reference: models/rpns.py:208-229): per side pair a depthwise 3x3
+    (no bias) followed by a (1,3) conv for (l, r) and a (3,1) conv for (t, b); the output stacks (l, t, r, b).  One
+    HIP launch (ops.lr_tb_levels) for any number of levels: EfDetHead passes all five at once.
+    '''
+    def __init__(self, in_ch):
+        super().__init__()
+        self._lr = nn.Sequential(
+            nn.Conv2d(in_ch, in_ch, 3, 1, padding=1, groups=in_ch, bias=False),
+            nn.Conv2d(in_ch, 2, (1, 3), stride=1, padding=(0, 1))
+        )
+        self._tb = nn.Sequential(
+            nn.Conv2d(in_ch, in_ch, 3, 1, padding=1, groups=in_ch, bias=False),
+            nn.Conv2d(in_ch, 2, (3, 1), stride=1, padding=(1, 0))
+        )
+
+    def prepared(self):
+        """The packed kernel weights (ops.pack_lr_tb), cached and rebuilt when any parameter is replaced or modified in
+        place (the version key of prepare_conv)."""
+        if self.training:
+            raise NotImplementedError('mydetection_amd implements the inference path only; call model.eval()')
+        tensors = (self._lr[0].weight, self._tb[0].weight, self._lr[1].weight, self._lr[1].bias, self._tb[1].weight,
+                   self._tb[1].bias)
+        key = _versions(*tensors)
+        cache = self.__dict__.setdefault('_prep_cache', {})
+        hit = cache.get('lr_tb')
+        if hit is None or hit[0] != key:
+            hit = (key, ops.pack_lr_tb(*tensors))
+            cache['lr_tb'] = hit
+        return hit[1]
+
+    @staticmethod
+    def levels(layers, xs):
+        """Every layer of `layers` on its map of `xs`, one launch."""
+        return ops.lr_tb_levels([(x, m.prepared()) for m, x in zip(layers, xs)])
+
+    def forward(self, x):
+        return ops.lr_tb_levels([(x, self.prepared())])[0]
+
+
 class EfDetHead(nn.Module):
     '''
-    Per-level class and box towers: repeat x (sepconv -> BN -> swish) then a last sepconv (or dense conv)
-    (reference: models/rpns.py:121-197).  Weights are not shared across levels.  Output dict per level:
-    'bbox' [B,A,H,W,4] (or [B,H,W,4] when A == 1), 'class' [...,n_cls], and 'conf' = class channel 0
-    when enable_conf.
+    Per-level class and box towers: repeat x (sepconv -> BN -> swish) then a last sepconv (or dense conv; the box
+    tower's may be _LR_TB_last, model.effrpn.bbox_last = 'lr_tb') (reference: models/rpns.py:121-197).  Weights are
+    not shared across levels.  Output dict per level: 'bbox' [B,A,H,W,4] (or [B,H,W,4] when A == 1), 'class'
+    [...,n_cls], and 'conf' = class channel 0 when enable_conf.
     '''
     def __init__(self, cfg: dict):
         super().__init__()
@@ -114,14 +155,18 @@ class EfDetHead(nn.Module):
         enable_conf = cfg['model.effrpn.enable_conf']
         bbox_last_type = cfg.get('model.effrpn.bbox_last', 'default')
         cls_last_type = cfg.get('model.effrpn.cls_last', 'spconv')
-        if bbox_last_type != 'default':
+        if bbox_last_type not in ('default', 'lr_tb'):
             raise NotImplementedError()
         self.class_nets = nn.ModuleList()
         self.bbox_nets = nn.ModuleList()
         cls_ch = n_anch * (1 + n_cls) if enable_conf else n_anch * n_cls
         for ch in feature_chs:
             bb_net = [spconv3x3_bn_swish(ch) for _ in range(repeat)]
-            bb_net.append(SeparableConv2d(ch, n_anch * bb_param, 3, 1, padding=1))
+            if bbox_last_type == 'default':
+                bb_net.append(SeparableConv2d(ch, n_anch * bb_param, 3, 1, padding=1))
+            else:                                   # 'lr_tb' (reference :137-145)
+                assert n_anch == 1 and bb_param == 4
+                bb_net.append(_LR_TB_last(ch))
             self.bbox_nets.append(nn.Sequential(*bb_net))
             cls_net = [spconv3x3_bn_swish(ch) for _ in range(repeat)]
             # final bias -log((1 - 0.01) / 0.01): initial confidences close to 0.01 (reference :150-158)
@@ -206,6 +251,11 @@ class EfDetHead(nn.Module):
             return list(zip(outs[:n], outs[n:]))
         if all(isinstance(m, SeparableConv2d) and m.fusable() for m in last):
             box = ops.sepconv_nodes([m.node([t]) for m, t in zip(last, box_t)])
+        elif all(isinstance(m, _LR_TB_last) for m in last) and n <= ops._lib.LR_TB_MAX_LEVELS:
+            box = _LR_TB_last.levels(last, box_t)                # the box layers of every level: one launch
+            if all(isinstance(m, SeparableConv2d) and m.fusable() for m in cls_last):
+                cls = ops.sepconv_nodes([m.node([t]) for m, t in zip(cls_last, cls_t)])
+                return list(zip(cls, box))
         else:
             box = [m(t) for m, t in zip(last, box_t)]
         return [(m(t), b) for m, t, b in zip(cls_last, cls_t, box)]

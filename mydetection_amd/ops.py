@@ -771,6 +771,47 @@ def sepconv_nodes(nodes):
     return outs
 
 
+def pack_lr_tb(w_lr0, w_tb0, w_lr1, b_lr1, w_tb1, b_tb1):
+    """Kernel-ready weights of one _LR_TB_last layer (mydet_lr_tb_levels_f32): (30 C + 4) floats, the two depthwise convs
+    [C,1,3,3] as [kh][kw][C], the (1,3) / (3,1) convs [2,C,1,3] / [2,C,3,1] as [o][k][C], then the biases in ltrb order."""
+    C = w_lr0.shape[0]
+    with torch.no_grad():
+        parts = [w_lr0.reshape(C, 9).t(), w_tb0.reshape(C, 9).t(), w_lr1[:, :, 0, :].permute(0, 2, 1),
+                 w_tb1[:, :, :, 0].permute(0, 2, 1), torch.stack([b_lr1[0], b_tb1[0], b_lr1[1], b_tb1[1]])]
+        return torch.cat([p.detach().float().reshape(-1) for p in parts]).contiguous()
+
+
+def lr_tb_levels(levels):
+    """The lr_tb box layer (models/rpns.py _LR_TB_last) of up to 8 pyramid levels in ONE launch.  levels: list of
+    (x [B,C,H,W], packed weights from pack_lr_tb); all share B and C.  Returns per level the box logits [B,4,H,W]
+    (l, t, r, b), stored pixel-major [B,H,W,4]."""
+    assert 1 <= len(levels) <= _lib.LR_TB_MAX_LEVELS
+    arr = (_lib.LrTbLevel * len(levels))()
+    outs, keep = [], []
+    B = C = None
+    nbytes = flops = 0.0
+    for i, (x, w) in enumerate(levels):
+        require_gpu(x, 'lr_tb_levels')
+        xt, ldx = to_nhwc(x)
+        b, c, H, W = xt.shape
+        B, C = (b, c) if B is None else (B, C)
+        assert (b, c) == (B, C), 'all levels of a launch share batch and channels'
+        assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.numel() == 30 * C + 4
+        out, ldy = empty_nhwc(B, 4, H, W, xt.device)
+        lv = arr[i]
+        lv.x, lv.ldx, lv.w, lv.y, lv.ldy, lv.H, lv.W = xt.data_ptr(), ldx, w.data_ptr(), out.data_ptr(), ldy, H, W
+        keep.append((xt, w, out))
+        outs.append(out)
+        nbytes += 4.0 * B * H * W * (C + 4)                       # the map read once, ltrb written once
+        flops += 2.0 * B * H * W * C * 30                             # 2 x depthwise 3x3, 2 x (2 outputs x 3 taps)
+    t0 = TIMER.start() if TIMER else None
+    code = _lib.lib().mydet_lr_tb_levels_f32(len(levels), ctypes.cast(arr, ctypes.c_void_p), B, C, _stream())
+    if t0:
+        TIMER.stop('lr_tb', t0, flops, nbytes)
+    _lib.check(code, 'mydet_lr_tb_levels_f32')
+    return outs
+
+
 # MYDET_FUSED_DECODE=0: the EfDetHead + RetinaLayer path writes its class logits and decodes them in a second launch
 FUSED_DECODE = os.environ.get('MYDET_FUSED_DECODE', '1') != '0'
 

@@ -129,9 +129,11 @@ _N_CLS = 80          # every configuration of the family has 80 classes (general
 
 def _efdet_last_kind(key):
     """'class' | 'bbox' | 'center' for the final layers of EfDetHead / EfDetHead_wCenter (models/rpns.py:139-160,
-    245-266): rpn.{class,bbox}_nets.{lvl}.3[.pointwise|.depthwise].*, rpn.bbox_lasts.{lvl}.*, rpn.center_nets.{lvl}.1.*;
-    None for every other key."""
+    245-266): rpn.{class,bbox}_nets.{lvl}.3[.pointwise|.depthwise|._lr.1|._tb.1].*, rpn.bbox_lasts.{lvl}.*,
+    rpn.center_nets.{lvl}.1.*; None for every other key."""
     parts = key.split('.')
+    if key.startswith('rpn.bbox_nets.') and ('._lr.0.' in key or '._tb.0.' in key):
+        return None             # _LR_TB_last's bias-free depthwise convs (models/rpns.py:208-229): plain conv weights
     if key.startswith(('rpn.class_nets.', 'rpn.bbox_nets.')) and len(parts) >= 5 and parts[3] == '3':
         return 'class' if parts[1] == 'class_nets' else 'bbox'
     if key.startswith('rpn.bbox_lasts.'):
@@ -164,7 +166,8 @@ def _efdet_row_targets(kind, rows, from_coarsest=0):
         # 4 channels: FCOS (models/detlayers/fcos2.py:222-251); 9 anchors: RetinaNet, cx = acx + tx * aw with anchors up
         # to 1 149 px (models/detlayers/retinanet.py:21-28,63-70) -- a centre offset of a few percent of the anchor keeps
         # float32 round-off of the box inside 1e-4 + 1e-4 |v|; otherwise the YOLO decode (models/detlayers/yolov3.py:41-47)
-        style = 'ltrb' if rows == 4 else None
+        # (2 channels: one of the two box convs of _LR_TB_last, (l, r) or (t, b), models/rpns.py:208-229)
+        style = 'ltrb' if rows in (2, 4) else None
         if style:
             std[:], bias[:] = _EFDET_TARGETS['ltrb']
         else:
@@ -252,10 +255,15 @@ def load_calibration(config_name, recipe='conditioned'):
     import os
     ck = config_name if recipe == 'conditioned' else f'{config_name}.{recipe}'
     if ck not in _CALIB_CACHE:
-        stem = {'d1_fcs2': 'd1_fcs2_atss'}.get(config_name, config_name)      # same network, same statistics
+        stem = {'d1_fcs2': 'd1_fcs2_atss', 'd1_fcs2s_mos': 'd1_fcs2s'}.get(config_name, config_name)      # same network, same statistics
         if recipe != 'conditioned':
             stem += '.' + recipe
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'calib', f'{stem}.npz')
+        if not os.path.exists(path):
+            # statistics measured on the reference for a configuration added later ship as a test fixture
+            # (tools/gen_golden_lr_tb.py): tests/golden/<stem>.calib.npz
+            path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden',
+                                f'{stem}.calib.npz')
         _CALIB_CACHE[ck] = dict(np.load(path)) if os.path.exists(path) else {}
     return _CALIB_CACHE[ck]
 
