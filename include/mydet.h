@@ -255,20 +255,26 @@ int mydet_spp_concat_f32(const float *x, int64_t ldx, float *y, int64_t ldy, int
  *   mode MYDET_DECODE_YOLO   YOLOLayer.forward        models/detlayers/yolov3.py:41-69
  *   mode MYDET_DECODE_RETINA RetinaLayer.forward      models/detlayers/retinanet.py:63-82
  *   mode MYDET_DECODE_FCOS   FCOS_ATSS_Layer.forward  models/detlayers/fcos2.py:222-251
- * box : [B,H,W,*] pixel stride ldbox; anchor a's 4 box logits at a*box_astride + box_c0
+ *   mode MYDET_DECODE_RAPID  RAPiDLayer.forward       models/detlayers/rapid.py:36-81 (inference branch)
+ * box : [B,H,W,*] pixel stride ldbox; anchor a's 4 box logits (5 for RAPID) at a*box_astride + box_c0
  * cls : [B,H,W,*] pixel stride ldcls; anchor a's C class logits at a*cls_astride + cls_c0,
  *       its objectness/centerness logit (YOLO, FCOS) at a*cls_astride + conf_c0.
- *       (YOLO head: box == cls, astride 5+C, box_c0 0, conf_c0 4, cls_c0 5.)
+ *       (YOLO head: box == cls, astride 5+C, box_c0 0, conf_c0 4, cls_c0 5.  RAPID on a YOLO head: astride 6+C,
+ *       conf_c0 5, cls_c0 6.)  1 <= C <= 128; RAPID also takes C == 0 (no class logit is read, class 0).
  * anchors_wh: HOST pointer (the one exception to "device pointers only") to A pairs (w,h)
  *       in pixels (A <= 16); the pairs travel as kernel arguments so the launch stays
  *       graph-capturable (YOLO, RETINA; ignored for FCOS, where A == 1).
  * Candidate order inside a level is (a, y, x), x fastest.  N = candidates per image.
- * Outputs: bbox [B,N,4] f32, class_idx [B,N] i64, score [B,N] f32.
+ * Outputs: bbox [B,N,4] f32 ([B,N,5] for RAPID), class_idx [B,N] i64, score [B,N] f32.
  * ldbox, ldcls multiples of 4; 16-byte aligned bases.
+ * RAPID (rotated boxes, bbox rows (cx, cy, w, h, deg)): cx, cy, w, h as YOLO; deg = ((s(t4)*2*pi - pi)/pi)*180 in
+ *   float32 with pi the float32 constant, in (-180, 180); score = s(conf) when C == 0, else
+ *   sqrt(s(conf) * max_c s(cls_c)) with class_idx the first argmax (torch.max).
  */
 #define MYDET_DECODE_YOLO   0
 #define MYDET_DECODE_RETINA 1
 #define MYDET_DECODE_FCOS   2
+#define MYDET_DECODE_RAPID  3
 typedef struct mydet_decode_level {
     const float *box; int64_t ldbox;     /* device */
     const float *cls; int64_t ldcls;     /* device */
@@ -329,6 +335,25 @@ int mydet_postprocess_f32(const float *bbox, const int64_t *class_idx, const flo
 int mydet_postprocess_records_f32(const float *bbox, const int64_t *class_idx, const float *score,
                                   int B, int64_t N, float conf_thres, double nms_thres,
                                   int32_t *records, void *scratch, void *stream);
+
+/* Rotated boxes (bb_format 'cxcywhd', rows (cx, cy, w, h, deg)): the same filter, top-k, sort and NMS, on columns 0-3
+ * only -- the reference's non_max_suppression builds the axis-aligned x1y1x2y2 from them and calls torchvision.ops.nms
+ * for 'cxcywhd' too (utils/structures.py:137-149; its rotated NMS is not on the inference path).  The angle travels
+ * with its box.  For every input, count / class / score / index and box columns 0-3 equal those of the 4-column
+ * entry points on bbox[..., 0:4] bit for bit, and each angle is bbox[b, index, 4].
+ *   mydet_postprocess_rot_f32:         arguments as mydet_postprocess_f32, bbox [B,N,5], out_bbox [B,topk,5].
+ *   mydet_postprocess_records_rot_f32: a ROTATED record per image, MYDET_REC_ROT_WORDS words (18 448 B): the
+ *                                      4-column record (every field at its offset; BBOX stays a 512 x 4 plane, so
+ *                                      mydet_bboxes_to_original_batched_f32 applies unchanged) + [ANGLE] 512 f32. */
+#define MYDET_REC_ANGLE     MYDET_REC_WORDS
+#define MYDET_REC_ROT_WORDS (MYDET_REC_WORDS + MYDET_REC_TOPK)
+int mydet_postprocess_rot_f32(const float *bbox, const int64_t *class_idx, const float *score,
+                              int B, int64_t N, float conf_thres, double nms_thres, int topk,
+                              int32_t *count, float *out_bbox, int64_t *out_class, float *out_score,
+                              int32_t *out_index, void *scratch, void *stream);
+int mydet_postprocess_records_rot_f32(const float *bbox, const int64_t *class_idx, const float *score,
+                                      int B, int64_t N, float conf_thres, double nms_thres,
+                                      int32_t *records, void *scratch, void *stream);
 
 /* Winograd F(4x4,3x3) form of the same 3x3 stride-1 pad-1 conv + BN + act (+ residual) as mydet_conv2d_wino_f32
  * (4x fewer multiplies than the direct form; used for the deep layers with chip-filling grids).  `u` = the

@@ -55,6 +55,9 @@ SIGNATURES = {
     'mydet_postprocess_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
                               c_ptr, c_ptr, c_ptr],
     'mydet_postprocess_records_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_ptr, c_ptr, c_ptr],
+    'mydet_postprocess_rot_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
+                                  c_ptr, c_ptr, c_ptr],
+    'mydet_postprocess_records_rot_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_ptr, c_ptr, c_ptr],
     'mydet_mbconv_tiles': [c_int, c_int, c_int],
     'mydet_mbconv_expand_dw_f32': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64] + [c_int] * 11 + [c_ptr, c_int, c_ptr, c_ptr],
     'mydet_sepconv_nodes_f32': [c_int, c_ptr, c_int, c_int, c_ptr],
@@ -82,6 +85,9 @@ REC_SCORE = REC_BBOX + 4 * REC_TOPK
 REC_CLASS = REC_SCORE + REC_TOPK
 REC_INDEX = REC_CLASS + 2 * REC_TOPK
 REC_WORDS = REC_INDEX + REC_TOPK
+# rotated record (bb_format 'cxcywhd'): the same fields at the same offsets + one angle plane behind them
+REC_ANGLE = REC_WORDS
+REC_ROT_WORDS = REC_WORDS + REC_TOPK
 
 
 class DecodeLevel(ctypes.Structure):

@@ -212,7 +212,8 @@ class Detector():
                 bb, ci, sc = self.model.forward_candidates(x)
                 return batched_post_process(bb, ci, sc, conf_thres, nms_thres)
             # the eager form of a laned graph: the same parts of the batch, one after the other -- bit-identical to the replay
-            records = torch.empty((x.shape[0], ops._lib.REC_WORDS), dtype=torch.int32, device=x.device)
+            words = ops.record_words(getattr(self.model, 'bbox_param', 4))
+            records = torch.empty((x.shape[0], words), dtype=torch.int32, device=x.device)
             lo = 0
             for part in x.tensor_split(lanes):
                 bb, ci, sc = self.model.forward_candidates(part)

@@ -136,6 +136,44 @@ def _build():
               'model.fcos.anchors': [0, 64, 128, 100000000], 'model.fcos2.ignored_threshold': 0.7})
     c.update(_test(640, 0.45))
     out['u5m_fcs2'] = c
+
+    # RAPiD, the rotated-box detector for overhead fisheye images (configs/rapid.json, rapid_psl1.json, yv3_pl1_80.json,
+    # u5m_rapid.json, d1_rapid.json): 'cxcywhd' boxes, 5 box parameters, the RAPiDLayer decode
+    rapid_anchors = [[18.7807, 33.4659], [28.8912, 61.7536], [48.6849, 68.3897], [45.0668, 101.4673], [63.0952, 113.5382],
+                     [81.3909, 134.4554], [91.7364, 144.9949], [137.5189, 178.4791], [194.4429, 250.7985]]
+
+    def rapid(c, n_cls, anchors, loss='Periodic_L1', pred_range=True, conf=0.3, size=1024, ap=0.005):
+        c.update({'general.num_class': n_cls, 'general.pred_bbox_format': 'cxcywhd', 'general.bbox_param': 5,
+                  'model.pred_layer': 'RAPiD', 'model.yolo.num_anchor_per_level': 3, 'model.rapid.anchors': anchors,
+                  'model.rapid.anchor_indices': [[0, 1, 2], [3, 4, 5], [6, 7, 8]], 'model.rapid.wh_smooth_l1_beta': 1,
+                  'model.angle.loss_angle': loss})
+        if pred_range:
+            c['model.angle.pred_range'] = 360
+        c.update(_test(size, 0.45, conf, **{'test.ap_conf_thres': ap}))
+        return c
+
+    for name, loss in (('rapid', 'Periodic_L1'), ('rapid_psl1', 'Periodic_smoothL1')):
+        c = _general('RGB_1', 32)
+        c.update(_pyramid('dark53', 3, 'yolov3'))
+        c.update({'model.rpn.name': 'yolov3'})
+        out[name] = rapid(c, 0, rapid_anchors, loss)
+
+    c = _general('RGB_1', 32)
+    c.update(_pyramid('dark53', 3, 'yolov3'))
+    c.update({'__doc': '80-cls yolov3 + periodic l1 (equivalent to = 80-cls rapid)', 'model.rpn.name': 'yolov3'})
+    out['yv3_pl1_80'] = rapid(c, 80, rapid_anchors, pred_range=False, size=608)
+
+    c = _general('RGB_1', 64)
+    c.update(_pyramid('ultralytics', 3, 'ultralytics'))
+    c.update(ul)
+    c.update({'__doc': "Ultralytics's YOLOv5-m + RAPiD", 'model.rpn.name': 'yolov3'})
+    out['u5m_rapid'] = rapid(c, 0, rapid_anchors, ap=0.01)
+
+    # EfficientNet-B1, three levels under BiFPN3 (the d1_fcs2_p3 composition), EfDetHead with three anchors per level
+    c = _efficientnet_bifpn(128, True, None, levels=3)
+    c.update(_effrpn('effrpn', 3, True))
+    out['d1_rapid'] = rapid(c, 0, [[18.8, 33.5], [28.9, 61.8], [48.7, 68.4], [45.1, 101.5], [63.1, 113.5], [81.4, 134.5],
+                                   [91.7, 145.0], [137.5, 178.5], [194.4, 250.8]])
     return out
 
 

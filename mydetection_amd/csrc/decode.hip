@@ -16,6 +16,9 @@
 //   YOLO   models/detlayers/yolov3.py:41-69    cx=(s(tx)+x)*stride, w=exp(tw)*aw, score=s(conf)*max s(cls)
 //   RETINA models/detlayers/retinanet.py:63-82 cx=acx+tx*aw, w=exp(tw)*aw, clamp [1,max(H,W)], score=max s(cls)
 //   FCOS   models/detlayers/fcos2.py:222-251   ltrb=exp(t)*stride, clamp to image, score=sqrt(s(conf)*max s(cls))
+//   RAPID  models/detlayers/rapid.py:36-81     YOLO box + deg=((s(t4)*2*pi-pi)/pi)*180, score=s(conf) (C == 0) or
+//                                               sqrt(s(conf)*max s(cls)); 5-float rows (20 B): a wave's 64 candidates
+//                                               are one contiguous 1280-byte run written as dword stores
 #include <cstdlib>
 
 #include "common.h"
@@ -145,8 +148,9 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs p) {
             // class max / first argmax (strict >: the first maximum wins, as torch.max)
             // ... and the runner-up VALUE (`second`: the largest logit at another index, equal to `best` on an exact tie): it
             // decides below whether the float32 logistic can merge the two
-            float best = cl[k_lo], second = -__builtin_inff();
-            int bi = k_lo;
+            // C == 0 (RAPiD without classes): no class logit is read, class 0, the score is the objectness alone
+            float best = p.C > 0 ? cl[k_lo] : 0.0f, second = -__builtin_inff();
+            int bi = p.C > 0 ? k_lo : 0;
             for (int k0 = k_lo + 1; k0 < k_hi; k0 += 8) {      // 8 LDS reads in flight, then the ordered compare chain
                 float x[8];
 #pragma unroll
@@ -176,12 +180,14 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs p) {
             // the cruder rule takes over (runner-up two below the best, or below 15 when the best one is past 17, where the
             // float32 logistic is exactly 1).  Correlated class logits -- many classes large at the same cell -- made the cruder
             // rule alone send a quarter of the waves of a synthetic head down the collision path (decode 0.059 -> 0.080 ms).
-            bool isolated = best > -80.0f && best < 5.0f;
-            if (best >= 5.0f) {                        // (rare: the exponential is not on the common path)
+            bool isolated = (best > -80.0f && best < 5.0f) || p.C == 0;
+            if (best >= 5.0f && p.C > 0) {                        // (rare: the exponential is not on the common path)
                 const float tie = best < 15.0f ? best - fminf(2.0f, 4.8e-7f * expf(best)) : fminf(best - 2.0f, 15.0f);
                 isolated = second < tie;
             }
-            if (isolated) {
+            if (p.C == 0) {
+                cmax = 1.0f;
+            } else if (isolated) {
                 cmax = mydet_sigmoid(best);
             } else {                                   // near saturation: compare the sigmoid values themselves
                 // ... of the classes that can tie with the best one.  The logistic is monotonic, and a logit two below the best
@@ -229,6 +235,25 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs p) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) o[j] = fminf(fmaxf(o[j], 1.0f), fmaxhw);
                 sc = cmax;
+            } else if (p.mode == MYDET_DECODE_RAPID) {
+                // float32 in the reference's operation order, and the Python float np.pi acts as the FLOAT32 constant:
+                // PyTorch casts a Python scalar to the tensor's dtype (tests/test_rapid_host.py restates this order on the
+                // reference layer's fixture and matches its angles bit for bit; the float64-scalar reading does not)
+                constexpr float pi = 3.14159265358979323846f;
+                o[0] = (mydet_sigmoid(t0) + (float)gx) * st;
+                o[1] = (mydet_sigmoid(t1) + (float)gy) * st;
+                o[2] = expf(t2) * aw;
+                o[3] = expf(t3) * ah;
+                const float rad = mydet_sigmoid(t[4]) * 2.0f * pi - pi;
+                const float deg = rad / pi * 180.0f;
+                const float conf = mydet_sigmoid(rowp[a * p.cls_astride + p.conf_c0]);
+                sc = p.C == 0 ? conf : sqrtf(conf * cmax);
+                const int64_t n = (int64_t)b * p.N + L.n_off + ((int64_t)a * L.H + gy) * L.W + gx;
+                float *d = p.bbox + n * 5;         // 20-byte rows: dword stores, consecutive lanes = consecutive rows
+                d[0] = o[0]; d[1] = o[1]; d[2] = o[2]; d[3] = o[3]; d[4] = deg;
+                p.cidx[n] = (int64_t)bi;
+                p.score[n] = sc;
+                continue;
             } else {
                 const float cx = (float)gx * st + st * 0.5f;
                 const float cy = (float)gy * st + st * 0.5f;
@@ -272,9 +297,9 @@ extern "C" int mydet_decode_levels_f32(int mode, int nlevels, const mydet_decode
                                        int box_c0, int cls_astride, int cls_c0, int conf_c0, int A, int C, int B,
                                        int img_h, int img_w, float *bbox, int64_t *class_idx, float *score, int64_t N,
                                        void *stream) {
-    if (mode < 0 || mode > 2 || !levels || nlevels <= 0 || nlevels > MAX_LEVELS || !bbox || !class_idx || !score)
+    if (mode < 0 || mode > MYDET_DECODE_RAPID || !levels || nlevels <= 0 || nlevels > MAX_LEVELS || !bbox || !class_idx || !score)
         return MYDET_E_BADARG;
-    if (A <= 0 || A > MAX_A || C <= 0 || C > 128 || B <= 0 || ((uintptr_t)bbox & 15)) return MYDET_E_BADARG;
+    if (A <= 0 || A > MAX_A || C < (mode == MYDET_DECODE_RAPID ? 0 : 1) || C > 128 || B <= 0 || ((uintptr_t)bbox & 15)) return MYDET_E_BADARG;
     DecodeArgs p;
     p.mode = mode; p.nlevels = nlevels;
     p.box_astride = box_astride; p.box_c0 = box_c0; p.cls_astride = cls_astride; p.cls_c0 = cls_c0;
@@ -285,7 +310,7 @@ extern "C" int mydet_decode_levels_f32(int mode, int nlevels, const mydet_decode
         const int cneed = (A - 1) * cls_astride + conf_c0 + 1;
         cls_need = cls_need > cneed ? cls_need : cneed;
     }
-    const int box_need = (A - 1) * box_astride + box_c0 + 4;
+    const int box_need = (A - 1) * box_astride + box_c0 + (mode == MYDET_DECODE_RAPID ? 5 : 4);
     p.same = 1;
     for (int l = 0; l < nlevels; ++l)
         if (levels[l].box != levels[l].cls || levels[l].ldbox != levels[l].ldcls) p.same = 0;

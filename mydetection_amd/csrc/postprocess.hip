@@ -21,6 +21,9 @@
 //      detections settle in a few rounds); inputs that do not settle in 12 rounds take the sequential form
 //      (one wave, 64 boxes at a time, dependent chain on the scalar unit).  Rank-by-popcount compaction follows.
 // Replaces ImageObjects.post_process / non_max_suppression (utils/structures.py:92-173).
+// The kernel is a template on the candidate row width BW: 4 (cxcywh) or 5 (cxcywhd, rotated boxes).  For BW = 5 every step
+// above reads columns 0-3 only -- the reference's NMS ignores the angle for 'cxcywhd' (utils/structures.py:137-149) -- and
+// the angle is copied with its box into the output rows (5 wide) or into the ANGLE plane of a rotated record.
 #include "common.h"
 
 namespace {
@@ -43,6 +46,8 @@ struct PPArgs {
     int64_t *ocls;
     float *oscore;
     int32_t *oidx;
+    float *oang;                      // BW = 5 only: the angle plane of a rotated record (obox then has 4-float rows), or null
+    int64_t oang_st;
     // per-image strides of the five outputs, in elements of each (dense arrays, or fields of one wire record)
     int64_t count_st, obox_st, ocls_st, oscore_st, oidx_st;
     int count_pad;                    // zero words written behind the count (record header padding)
@@ -54,6 +59,7 @@ __device__ __forceinline__ unsigned sortable(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+template <int BW>
 __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
     __shared__ unsigned long long s_key[KMAX];
     __shared__ unsigned long long s_mask[KMAX * 8];
@@ -67,7 +73,7 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
     const int b = blockIdx.x;
     const float *sc = p.score + (int64_t)b * p.N;
     const int64_t *ci = p.cidx + (int64_t)b * p.N;
-    const float *bb = p.bbox + (int64_t)b * p.N * 4;
+    const float *bb = p.bbox + (int64_t)b * p.N * BW;
     unsigned long long *keys = p.scratch + (int64_t)b * p.N;
     const int N = (int)p.N;
 
@@ -256,7 +262,13 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
     if (tid < nsel) {
         const unsigned long long k = s_key[tid];
         const unsigned idx = (unsigned)(k & ((1ull << IDX_BITS) - 1));
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(bb + (int64_t)idx * 4);
+        f32x4 v;
+        if constexpr (BW == 4) {
+            v = *reinterpret_cast<const f32x4 *>(bb + (int64_t)idx * 4);
+        } else {                                        // 20-byte rows: columns 0-3, the angle is not used here
+            const float *r = bb + (int64_t)idx * BW;
+            v = f32x4{r[0], r[1], r[2], r[3]};
+        }
         const float hw = v[2] / 2.0f, hh = v[3] / 2.0f;
         const float x1 = v[0] - hw, y1 = v[1] - hh, x2 = v[0] + hw, y2 = v[1] + hh;
         s_x1[tid] = x1; s_y1[tid] = y1; s_x2[tid] = x2; s_y2[tid] = y2;
@@ -414,7 +426,19 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
                 const int pos = before + __popcll(kept & ((1ull << (tid & 63)) - 1ull));
                 const unsigned long long k = s_key[tid];
                 const unsigned idx = (unsigned)(k & ((1ull << IDX_BITS) - 1));
-                *reinterpret_cast<f32x4 *>(p.obox + b * p.obox_st + pos * 4) = *reinterpret_cast<const f32x4 *>(bb + (int64_t)idx * 4);
+                if constexpr (BW == 4) {
+                    *reinterpret_cast<f32x4 *>(p.obox + b * p.obox_st + pos * 4) = *reinterpret_cast<const f32x4 *>(bb + (int64_t)idx * 4);
+                } else {
+                    const float *r = bb + (int64_t)idx * BW;
+                    if (p.oang) {                       // rotated record: the 512 x 4 box plane + the angle plane
+                        *reinterpret_cast<f32x4 *>(p.obox + b * p.obox_st + pos * 4) = f32x4{r[0], r[1], r[2], r[3]};
+                        p.oang[b * p.oang_st + pos] = r[4];
+                    } else {
+                        float *d = p.obox + b * p.obox_st + pos * BW;
+#pragma unroll
+                        for (int c = 0; c < BW; ++c) d[c] = r[c];
+                    }
+                }
                 p.ocls[b * p.ocls_st + pos] = ci[idx];
                 p.oscore[b * p.oscore_st + pos] = sc[idx];
                 p.oidx[b * p.oidx_st + pos] = (int32_t)idx;
@@ -422,7 +446,15 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
         }
     }
     for (int r = total + tid; r < p.topk; r += NT) {
-        *reinterpret_cast<f32x4 *>(p.obox + b * p.obox_st + r * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (BW == 4) {
+            *reinterpret_cast<f32x4 *>(p.obox + b * p.obox_st + r * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else if (p.oang) {
+            *reinterpret_cast<f32x4 *>(p.obox + b * p.obox_st + r * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+            p.oang[b * p.oang_st + r] = 0.f;
+        } else {
+#pragma unroll
+            for (int c = 0; c < BW; ++c) p.obox[b * p.obox_st + r * BW + c] = 0.f;
+        }
         p.ocls[b * p.ocls_st + r] = 0;
         p.oscore[b * p.oscore_st + r] = 0.f;
         p.oidx[b * p.oidx_st + r] = 0;
@@ -432,6 +464,7 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
 
 }  // namespace
 
+template <int BW>
 static int launch_postprocess(PPArgs &p, const float *bbox, const int64_t *class_idx, const float *score, int B, int64_t N,
                               float conf_thres, double nms_thres, int topk, void *scratch, void *stream) {
     if (B <= 0 || N < 0 || topk <= 0 || topk > KMAX) return MYDET_E_BADARG;
@@ -441,7 +474,7 @@ static int launch_postprocess(PPArgs &p, const float *bbox, const int64_t *class
     if (((uintptr_t)bbox & 15) || ((uintptr_t)p.obox & 15) || ((uintptr_t)scratch & 7) || ((uintptr_t)p.ocls & 7)) return MYDET_E_BADARG;
     p.bbox = bbox; p.cidx = class_idx; p.score = score; p.N = N; p.conf = conf_thres; p.nms = nms_thres;
     p.topk = topk; p.scratch = (unsigned long long *)scratch;
-    hipLaunchKernelGGL(postprocess_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(postprocess_kernel<BW>, dim3(B), dim3(NT), 0, (hipStream_t)stream, p);
     return mydet_launch_status();
 }
 
@@ -451,8 +484,9 @@ extern "C" int mydet_postprocess_f32(const float *bbox, const int64_t *class_idx
                                      void *scratch, void *stream) {
     PPArgs p;
     p.count = count; p.obox = out_bbox; p.ocls = out_class; p.oscore = out_score; p.oidx = out_index;
+    p.oang = nullptr; p.oang_st = 0;
     p.count_pad = 0; p.count_st = 1; p.obox_st = (int64_t)topk * 4; p.ocls_st = topk; p.oscore_st = topk; p.oidx_st = topk;
-    return launch_postprocess(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, topk, scratch, stream);
+    return launch_postprocess<4>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, topk, scratch, stream);
 }
 
 extern "C" int mydet_postprocess_records_f32(const float *bbox, const int64_t *class_idx, const float *score, int B,
@@ -460,8 +494,9 @@ extern "C" int mydet_postprocess_records_f32(const float *bbox, const int64_t *c
                                              void *scratch, void *stream) {
     if ((uintptr_t)records & 15) return MYDET_E_BADARG;
     PPArgs p;
+    p.oang = nullptr; p.oang_st = 0;
     if (!records) { p.count = nullptr; p.obox = nullptr; p.ocls = nullptr; p.oscore = nullptr; p.oidx = nullptr;
-                    return launch_postprocess(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream); }
+                    return launch_postprocess<4>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream); }
     p.count = records + MYDET_REC_COUNT;
     p.obox = reinterpret_cast<float *>(records + MYDET_REC_BBOX);
     p.oscore = reinterpret_cast<float *>(records + MYDET_REC_SCORE);
@@ -469,5 +504,33 @@ extern "C" int mydet_postprocess_records_f32(const float *bbox, const int64_t *c
     p.oidx = records + MYDET_REC_INDEX;
     p.count_pad = MYDET_REC_BBOX - 1; p.count_st = MYDET_REC_WORDS; p.obox_st = MYDET_REC_WORDS; p.oscore_st = MYDET_REC_WORDS;
     p.ocls_st = MYDET_REC_WORDS / 2; p.oidx_st = MYDET_REC_WORDS;
-    return launch_postprocess(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream);
+    return launch_postprocess<4>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream);
+}
+
+extern "C" int mydet_postprocess_rot_f32(const float *bbox, const int64_t *class_idx, const float *score, int B,
+                                         int64_t N, float conf_thres, double nms_thres, int topk, int32_t *count,
+                                         float *out_bbox, int64_t *out_class, float *out_score, int32_t *out_index,
+                                         void *scratch, void *stream) {
+    PPArgs p;
+    p.count = count; p.obox = out_bbox; p.ocls = out_class; p.oscore = out_score; p.oidx = out_index;
+    p.oang = nullptr; p.oang_st = 0;
+    p.count_pad = 0; p.count_st = 1; p.obox_st = (int64_t)topk * 5; p.ocls_st = topk; p.oscore_st = topk; p.oidx_st = topk;
+    return launch_postprocess<5>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, topk, scratch, stream);
+}
+
+extern "C" int mydet_postprocess_records_rot_f32(const float *bbox, const int64_t *class_idx, const float *score, int B,
+                                                 int64_t N, float conf_thres, double nms_thres, int32_t *records,
+                                                 void *scratch, void *stream) {
+    if (!records || ((uintptr_t)records & 15)) return MYDET_E_BADARG;
+    PPArgs p;
+    p.count = records + MYDET_REC_COUNT;
+    p.obox = reinterpret_cast<float *>(records + MYDET_REC_BBOX);
+    p.oscore = reinterpret_cast<float *>(records + MYDET_REC_SCORE);
+    p.ocls = reinterpret_cast<int64_t *>(records + MYDET_REC_CLASS);
+    p.oidx = records + MYDET_REC_INDEX;
+    p.oang = reinterpret_cast<float *>(records + MYDET_REC_ANGLE);
+    p.count_pad = MYDET_REC_BBOX - 1; p.count_st = MYDET_REC_ROT_WORDS; p.obox_st = MYDET_REC_ROT_WORDS;
+    p.oscore_st = MYDET_REC_ROT_WORDS; p.ocls_st = MYDET_REC_ROT_WORDS / 2; p.oidx_st = MYDET_REC_ROT_WORDS;
+    p.oang_st = MYDET_REC_ROT_WORDS;
+    return launch_postprocess<5>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream);
 }

@@ -115,7 +115,8 @@ class GraphedPath:
         main = torch.cuda.current_stream()
         parts = self.static_in.tensor_split(self.lanes)
         # every lane writes its rows of ONE record buffer (allocated on the joining stream); the candidates stay per lane
-        records = torch.empty((self.static_in.shape[0], ops._lib.REC_WORDS), dtype=torch.int32, device=self.static_in.device)
+        words = ops.record_words(getattr(self.model, 'bbox_param', 4))
+        records = torch.empty((self.static_in.shape[0], words), dtype=torch.int32, device=self.static_in.device)
         cands, lo = [], 0
         for i, (st, part) in enumerate(zip(self._streams, parts)):
             st.wait_stream(main)

@@ -4,8 +4,8 @@ import torch
 from ... import ops
 
 
-def alloc_outputs(nB, n, device):
-    return (torch.empty((nB, n, 4), dtype=torch.float32, device=device),
+def alloc_outputs(nB, n, device, box_width=4):
+    return (torch.empty((nB, n, box_width), dtype=torch.float32, device=device),
             torch.empty((nB, n), dtype=torch.int64, device=device),
             torch.empty((nB, n), dtype=torch.float32, device=device))
 

@@ -59,6 +59,8 @@ class OneStageBBox(torch.nn.Module):
 
         self.check_gt_assignment = cfg.get('train.check_gt_assignment', False)
         self.bb_format = cfg.get('general.pred_bbox_format', 'cxcywh')
+        # floats per candidate box: 4 (cxcywh), 5 for the rotated boxes of RAPiD (cxcywhd); the records follow it
+        self.bbox_param = cfg.get('general.bbox_param', 4)
         self.input_format = cfg['general.input_format']
         self.weights_epoch = 0
         # how many parts api.Detector evaluates an even batch in (graph.GraphedPath batch lanes): the EfficientNet-based
@@ -78,7 +80,7 @@ class OneStageBBox(torch.nn.Module):
         return super()._apply(fn, *args, **kwargs)
 
     def forward_candidates(self, x):
-        '''x [B,3,H,W] -> (bbox [B,N,4], class_idx [B,N] i64, score [B,N]) on the device.'''
+        '''x [B,3,H,W] -> (bbox [B,N,bbox_param], class_idx [B,N] i64, score [B,N]) on the device.'''
         assert x.dim() == 4
         self.img_size = x.shape[2:4]
         features = self.backbone(x)
@@ -99,7 +101,7 @@ class OneStageBBox(torch.nn.Module):
             shp = raw['bbox'].shape
             counts.append(int(torch.Size(shp[1:-1]).numel()))
         nB, n_total = x.shape[0], sum(counts)
-        bbs = torch.empty((nB, n_total, 4), dtype=torch.float32, device=x.device)
+        bbs = torch.empty((nB, n_total, self.bbox_param), dtype=torch.float32, device=x.device)
         cls_idx = torch.empty((nB, n_total), dtype=torch.int64, device=x.device)
         scores = torch.empty((nB, n_total), dtype=torch.float32, device=x.device)
         descs = [getattr(layer, '_describe', lambda *_: None)(raw, self.img_size)

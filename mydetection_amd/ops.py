@@ -16,7 +16,7 @@ import torch
 from . import _lib
 
 ACT_NONE, ACT_LEAKY, ACT_SWISH = 0, 1, 2
-DECODE_YOLO, DECODE_RETINA, DECODE_FCOS = 0, 1, 2
+DECODE_YOLO, DECODE_RETINA, DECODE_FCOS, DECODE_RAPID = 0, 1, 2, 3
 TOPK = 512
 
 
@@ -965,10 +965,17 @@ def spp_concat(x, ks=(5, 9, 13)):
     return out
 
 
+def _box_width(mode):
+    """Floats per candidate box written by a decode mode: (cx, cy, w, h), or (cx, cy, w, h, deg) for RAPiD."""
+    return 5 if mode == DECODE_RAPID else 4
+
+
 def decode(mode, box, ldbox, box_astride, box_c0, cls, ldcls, cls_astride, cls_c0, conf_c0, anchors_wh, A, C,
            B, H, W, stride, img_hw, bbox, class_idx, score, n_off):
-    """Decode one level into bbox[B,N,4] / class_idx[B,N] / score[B,N] at candidate offset n_off."""
+    """Decode one level into bbox[B,N,4] ([B,N,5] for DECODE_RAPID) / class_idx[B,N] / score[B,N] at candidate offset
+    n_off."""
     require_gpu(box, 'decode')
+    assert bbox.shape[-1] == _box_width(mode) and bbox.is_contiguous()
     N = bbox.shape[1]
     anch = None
     if anchors_wh is not None:
@@ -980,9 +987,9 @@ def decode(mode, box, ldbox, box_astride, box_c0, cls, ldcls, cls_astride, cls_c
         ctypes.c_void_p(anch.ctypes.data) if anch is not None else ctypes.c_void_p(0), A, C, B, H, W,
         float(stride), int(img_hw[0]), int(img_hw[1]), _ptr(bbox), _ptr(class_idx), _ptr(score), N, n_off,
         _stream())
-    if t0:      # algorithmic bytes: every head logit once + 28 B per candidate
-        per_pix = A * (C + 4 + (0 if mode == DECODE_RETINA else 1))
-        TIMER.stop('decode', t0, *[4.0 * B * H * W * per_pix + 28.0 * B * A * H * W] * 2)
+    if t0:      # algorithmic bytes: every head logit once + 28 B per candidate (32 B for RAPiD's 5-float rows)
+        per_pix = A * (C + _box_width(mode) + (0 if mode == DECODE_RETINA else 1))
+        TIMER.stop('decode', t0, *[4.0 * B * H * W * per_pix + (12.0 + 4 * _box_width(mode)) * B * A * H * W] * 2)
     _lib.check(code, 'mydet_decode_f32')
 
 
@@ -991,6 +998,7 @@ def decode_levels(mode, levels, box_astride, box_c0, cls_astride, cls_c0, conf_c
     """Decode every pyramid level with one launch.  levels: list of dicts with keys box, ldbox, cls, ldcls,
     anchors_wh (array-like [A,2] or None), H, W, stride, n_off."""
     require_gpu(bbox, 'decode_levels')
+    assert bbox.shape[-1] == _box_width(mode) and bbox.is_contiguous()
     n = len(levels)
     arr = (_lib.DecodeLevel * n)()
     keep = []                                         # host anchor arrays must outlive the call
@@ -1004,8 +1012,8 @@ def decode_levels(mode, levels, box_astride, box_c0, cls_astride, cls_c0, conf_c
         arr[i] = _lib.DecodeLevel(lv['box'].data_ptr(), lv['ldbox'], lv['cls'].data_ptr(), lv['ldcls'],
                                   anch.ctypes.data if anch is not None else None, lv['H'], lv['W'], float(lv['stride']),
                                   lv['n_off'])
-        per_pix = A * (C + 4 + (0 if mode == DECODE_RETINA else 1))
-        work += 4.0 * B * lv['H'] * lv['W'] * per_pix + 28.0 * B * A * lv['H'] * lv['W']
+        per_pix = A * (C + _box_width(mode) + (0 if mode == DECODE_RETINA else 1))
+        work += 4.0 * B * lv['H'] * lv['W'] * per_pix + (12.0 + 4 * _box_width(mode)) * B * A * lv['H'] * lv['W']
     t0 = TIMER.start() if TIMER else None
     code = _lib.lib().mydet_decode_levels_f32(mode, n, ctypes.cast(arr, ctypes.c_void_p), box_astride, box_c0,
                                               cls_astride, cls_c0, conf_c0, A, C, B, int(img_hw[0]), int(img_hw[1]),
@@ -1015,22 +1023,42 @@ def decode_levels(mode, levels, box_astride, box_c0, cls_astride, cls_c0, conf_c
     _lib.check(code, 'mydet_decode_levels_f32')
 
 
+def record_words(box_width):
+    """int32 words of one detection record for candidate boxes of `box_width` floats: REC_WORDS (cxcywh) or
+    REC_ROT_WORDS (cxcywhd: the same record + the angle plane)."""
+    if box_width not in (4, 5):
+        raise ValueError(f'detection records hold boxes of 4 or 5 floats, not {box_width}')
+    return _lib.REC_WORDS if box_width == 4 else _lib.REC_ROT_WORDS
+
+
 def record_views(records):
-    """Field views of a detection-record buffer (int32 [B, REC_WORDS], include/mydet.h MYDET_REC_*): nothing is
-    copied -- the dict the rest of the package works with IS the wire buffer of the multi-GPU exchange."""
+    """Field views of a detection-record buffer (int32 [B, REC_WORDS], or [B, REC_ROT_WORDS] for rotated boxes;
+    include/mydet.h MYDET_REC_*): nothing is copied -- the dict the rest of the package works with IS the wire buffer of
+    the multi-GPU exchange.  A rotated record adds 'angle' [B,512]; 'bbox' stays the [B,512,4] plane (cx, cy, w, h)."""
     B = records.shape[0]
-    assert records.dtype == torch.int32 and records.shape[1] == _lib.REC_WORDS and records.is_contiguous()
+    assert records.dtype == torch.int32 and records.shape[1] in (_lib.REC_WORDS, _lib.REC_ROT_WORDS) and records.is_contiguous()
     k = _lib.REC_TOPK
-    return {'count': records[:, _lib.REC_COUNT],
-            'bbox': records[:, _lib.REC_BBOX:_lib.REC_SCORE].view(torch.float32).view(B, k, 4),
-            'score': records[:, _lib.REC_SCORE:_lib.REC_CLASS].view(torch.float32),
-            'class_idx': records[:, _lib.REC_CLASS:_lib.REC_INDEX].view(torch.int64),
-            'index': records[:, _lib.REC_INDEX:_lib.REC_WORDS],
-            'records': records}
+    out = {'count': records[:, _lib.REC_COUNT],
+           'bbox': records[:, _lib.REC_BBOX:_lib.REC_SCORE].view(torch.float32).view(B, k, 4),
+           'score': records[:, _lib.REC_SCORE:_lib.REC_CLASS].view(torch.float32),
+           'class_idx': records[:, _lib.REC_CLASS:_lib.REC_INDEX].view(torch.int64),
+           'index': records[:, _lib.REC_INDEX:_lib.REC_WORDS],
+           'records': records}
+    if records.shape[1] == _lib.REC_ROT_WORDS:
+        out['angle'] = records[:, _lib.REC_ANGLE:_lib.REC_ROT_WORDS].view(torch.float32)
+    return out
+
+
+def record_boxes(rec, b, k):
+    """The first k boxes of image b of a record dict as [k, 4] (cxcywh) or [k, 5] (cxcywhd: the angle column appended)."""
+    if 'angle' not in rec:
+        return rec['bbox'][b, :k]
+    return torch.cat([rec['bbox'][b, :k], rec['angle'][b, :k, None]], dim=1)
 
 
 def postprocess(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, records=None):
-    """Batched filter/top-k/class-aware NMS.  bbox [B,N,4], class_idx [B,N] i64, score [B,N].
+    """Batched filter/top-k/class-aware NMS.  bbox [B,N,4], class_idx [B,N] i64, score [B,N].  bbox [B,N,5]
+    (cxcywhd) takes the rotated kernel: the same decisions on columns 0-3, rotated records ('angle' added).
 
     Returns dict of device tensors: count [B] i32, bbox [B,512,4], class_idx [B,512] i64, score [B,512],
     index [B,512] i32 -- all views of 'records' (int32 [B, REC_WORDS]), which the kernel writes directly in the
@@ -1043,17 +1071,43 @@ def postprocess(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, record
     bbox, class_idx, score = bbox.contiguous(), class_idx.contiguous(), score.contiguous()
     B, N = score.shape
     dev = bbox.device
+    words = record_words(bbox.shape[-1])
     if records is None:
-        records = torch.empty((B, _lib.REC_WORDS), dtype=torch.int32, device=dev)
-    assert records.dtype == torch.int32 and tuple(records.shape) == (B, _lib.REC_WORDS) and records.is_contiguous()
+        records = torch.empty((B, words), dtype=torch.int32, device=dev)
+    assert records.dtype == torch.int32 and tuple(records.shape) == (B, words) and records.is_contiguous()
     scratch = torch.empty((B, max(N, 1)), dtype=torch.int64, device=dev)
+    fn = 'mydet_postprocess_records_f32' if words == _lib.REC_WORDS else 'mydet_postprocess_records_rot_f32'
     t0 = TIMER.start() if TIMER else None
-    code = _lib.lib().mydet_postprocess_records_f32(_ptr(bbox), _ptr(class_idx), _ptr(score), B, N, float(conf_thres),
-                                                    float(nms_thres), _ptr(records), _ptr(scratch), _stream())
+    code = getattr(_lib.lib(), fn)(_ptr(bbox), _ptr(class_idx), _ptr(score), B, N, float(conf_thres), float(nms_thres),
+                                   _ptr(records), _ptr(scratch), _stream())
     if t0:
         TIMER.stop('postprocess', t0, float(B))
-    _lib.check(code, 'mydet_postprocess_records_f32')
+    _lib.check(code, fn)
     return record_views(records)
+
+
+def postprocess_dense(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK):
+    """The same filter/top-k/NMS into dense per-image arrays (mydet_postprocess_f32, or mydet_postprocess_rot_f32 for
+    bbox [B,N,5]): count [B] i32, bbox [B,topk,4 or 5], class_idx [B,topk] i64, score [B,topk], index [B,topk] i32."""
+    require_gpu(bbox, 'postprocess_dense')
+    assert bbox.dtype == torch.float32 and score.dtype == torch.float32 and class_idx.dtype == torch.int64
+    bbox, class_idx, score = bbox.contiguous(), class_idx.contiguous(), score.contiguous()
+    B, N = score.shape
+    width = bbox.shape[-1]
+    record_words(width)
+    dev = bbox.device
+    out = {'count': torch.empty(B, dtype=torch.int32, device=dev),
+           'bbox': torch.empty((B, topk, width), dtype=torch.float32, device=dev),
+           'class_idx': torch.empty((B, topk), dtype=torch.int64, device=dev),
+           'score': torch.empty((B, topk), dtype=torch.float32, device=dev),
+           'index': torch.empty((B, topk), dtype=torch.int32, device=dev)}
+    scratch = torch.empty((B, max(N, 1)), dtype=torch.int64, device=dev)
+    fn = 'mydet_postprocess_f32' if width == 4 else 'mydet_postprocess_rot_f32'
+    code = getattr(_lib.lib(), fn)(_ptr(bbox), _ptr(class_idx), _ptr(score), B, N, float(conf_thres), float(nms_thres),
+                                   int(topk), _ptr(out['count']), _ptr(out['bbox']), _ptr(out['class_idx']),
+                                   _ptr(out['score']), _ptr(out['index']), _ptr(scratch), _stream())
+    _lib.check(code, fn)
+    return out
 
 
 def check_counts(counts):

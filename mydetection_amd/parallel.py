@@ -8,6 +8,7 @@ kernel writes those records itself (include/mydet.h, MYDET_REC_*):
     per image  count:i32 +3 pad | 512 x (cx,cy,w,h:f32) | 512 x score:f32 | 512 x class:i64 | 512 x index:i32
   = 4100 words = 16 400 B.  32 images/GPU -> 525 KB per rank: latency-bound, one collective, no reduce, and
 no pack/unpack pass on either side -- the dict the package works with is a set of views of that buffer.
+Rotated boxes (RAPiD, 'cxcywhd') travel as rotated records: the same fields + 512 angles = 4612 words = 18 448 B.
 """
 import torch
 import torch.distributed as dist
@@ -15,7 +16,7 @@ import torch.distributed as dist
 from . import _lib
 
 TOPK = _lib.REC_TOPK
-WORDS = _lib.REC_WORDS
+WORDS = _lib.REC_WORDS              # the cxcywh record; a rotated one is _lib.REC_ROT_WORDS
 
 
 def shard_range(total, rank, world):
@@ -26,7 +27,7 @@ def shard_range(total, rank, world):
 
 
 def record_views(records):
-    """Field views of an int32 [B, WORDS] record buffer (any device)."""
+    """Field views of an int32 [B, WORDS] (or rotated [B, REC_ROT_WORDS]) record buffer (any device)."""
     from .ops import record_views as views
     return views(records)
 
@@ -37,9 +38,10 @@ def make_records(rec):
     if 'records' in rec:
         return rec
     B = rec['count'].shape[0]
-    buf = torch.zeros((B, WORDS), dtype=torch.int32, device=rec['count'].device)
+    rot = 'angle' in rec
+    buf = torch.zeros((B, _lib.REC_ROT_WORDS if rot else WORDS), dtype=torch.int32, device=rec['count'].device)
     out = record_views(buf)
-    for k in ('count', 'bbox', 'score', 'class_idx', 'index'):
+    for k in ('count', 'bbox', 'score', 'class_idx', 'index') + (('angle',) if rot else ()):
         out[k].copy_(rec[k])
     return out
 
@@ -56,7 +58,7 @@ def gather_detections(rec, group=None, always=False, total=None):
         return rec
     rank = dist.get_rank(group)
     buf = make_records(rec)['records']
-    B = buf.shape[0]
+    B, words = buf.shape
     if total is None:
         total = B * world                   # equal shards; a mismatch across ranks fails in the collective's size check
     lo, hi = shard_range(total, rank, world)
@@ -64,8 +66,8 @@ def gather_detections(rec, group=None, always=False, total=None):
         raise ValueError(f'rank {rank} holds {B} images but shard_range({total}, {rank}, {world}) is [{lo}, {hi})')
     cap = -(-total // world)                # largest shard
     if B < cap:
-        buf = torch.cat([buf, buf.new_zeros((cap - B, WORDS))])
-    out = torch.empty((world * cap, WORDS), dtype=torch.int32, device=buf.device)
+        buf = torch.cat([buf, buf.new_zeros((cap - B, words))])
+    out = torch.empty((world * cap, words), dtype=torch.int32, device=buf.device)
     dist.all_gather_into_tensor(out, buf, group=group)
     if total != world * cap:                # drop the padding row of the short shards
         keep = torch.cat([torch.arange(r * cap, r * cap + (lambda a: a[1] - a[0])(shard_range(total, r, world)))
@@ -96,9 +98,9 @@ def agree_on_lanes(choice, device=None, group=None):
 
 
 def records_to_objects(rec, img_hw=None, bb_format='cxcywh'):
-    """Fixed-size records -> List[ImageObjects] (one host sync for the counts)."""
+    """Fixed-size records -> List[ImageObjects] (one host sync for the counts); rotated records give [k, 5] boxes."""
     from .utils.structures import ImageObjects
-    from .ops import check_counts
+    from .ops import check_counts, record_boxes
     counts = check_counts(rec['count'].cpu().tolist())
-    return [ImageObjects(rec['bbox'][b, :k], rec['class_idx'][b, :k], None, rec['score'][b, :k], bb_format, img_hw)
+    return [ImageObjects(record_boxes(rec, b, k), rec['class_idx'][b, :k], None, rec['score'][b, :k], bb_format, img_hw)
             for b, k in enumerate(counts)]

@@ -53,6 +53,38 @@ def _uniform(key, shape, lo, hi):
 _YOLO_TARGETS = {'xy': (1.0, 0.0), 'wh': (0.35, 0.0), 'conf': (4.0, -13.0), 'class': (2.0, -3.5)}
 
 
+# RAPiD heads (rotated boxes; configs rapid, rapid_psl1, yv3_pl1_80, u5m_rapid on the YOLO head, d1_rapid on the EfDetHead):
+# per anchor (tx, ty, tw, th, t_angle, conf[, n_cls classes]) -- 18 or 258 rows of the YOLO head, 15 box + 3 objectness rows
+# of the EfDetHead, row counts no other configuration has.  The angle logit is wide, so sigmoid(t_angle) covers (0, 1) and
+# the angles the full (-180, 180); the objectness is far below zero with a wide spread, so the score has a long tail:
+# hundreds of the 4 032 candidates of a 256^2 input pass 0.005 and tens pass the 0.3 default (tools/gen_golden_rapid.py
+# prints the counts of every fixture it writes).
+# 'conf' is the calibrated EfDetHead's target; the YOLO head has no calibration file and its objectness bias ('yolo_conf')
+# was set from the logits the recipe gives on the reference (a spread of ~2.5 around the bias, level means apart by ~3).
+_RAPID_TARGETS = {'xy': (1.0, 0.0), 'wh': (0.35, 0.0), 'angle': (3.0, 0.0), 'conf': (4.0, -11.0), 'yolo_conf': (5.5, -5.5),
+                  'class': (2.0, -3.5)}
+_RAPID_HEAD_ROWS = (3 * 6, 3 * (6 + 80))
+
+
+def _rapid_kinds(rows_per_anchor, rows):
+    """Row kind names of a RAPiD head conv: a*(6 + n_cls) + c."""
+    c = np.arange(rows) % rows_per_anchor
+    return np.array(['xy', 'xy', 'wh', 'wh', 'angle', 'conf'] + ['class'] * (rows_per_anchor - 6))[c]
+
+
+def _rapid_yolo_head(key, shape, feature_rms):
+    """rpn.heads.conv_{i}.{weight,bias} of a RAPiD model on the YOLO head (models/rpns.py:27-33 with bbox_param 5)."""
+    level = int(key.split('conv_')[1].split('.')[0])
+    rows = shape[0]
+    kinds = np.where(_rapid_kinds(rows // 3, rows) == 'conf', 'yolo_conf', _rapid_kinds(rows // 3, rows))
+    if key.endswith('.bias'):
+        return (np.array([_RAPID_TARGETS[k][1] for k in kinds], np.float32) + _normal(key, (rows,), std=0.05)).astype(np.float32)
+    tgt = np.array([_RAPID_TARGETS[k][0] for k in kinds], np.float32)
+    fan_in = shape[1] * shape[2] * shape[3]
+    w = _normal(key, shape)
+    return (w * (tgt / (np.sqrt(fan_in) * feature_rms.get(level, 1.0))).reshape(-1, 1, 1, 1)).astype(np.float32)
+
+
 def yolo_head_unit_weight(key, shape):
     """Head conv weight before any gain: N(0, 1 / fan_in) per element, a pure function of the key."""
     fan_in = shape[1] * shape[2] * shape[3]
@@ -62,6 +94,8 @@ def yolo_head_unit_weight(key, shape):
 def _yolo_head(key, shape, n_cls=80, feature_rms=None, calib=None):
     """rpn.heads.conv_{i}.{weight,bias}: row o = a*(5+n_cls) + c  (models/rpns.py:27-33)."""
     feature_rms = _YOLO_HEAD_FEATURE_RMS if feature_rms is None else feature_rms
+    if shape[0] in _RAPID_HEAD_ROWS:
+        return _rapid_yolo_head(key, shape, feature_rms)
     level = int(key.split('conv_')[1].split('.')[0])
     rows = shape[0]
     c = np.arange(rows) % (5 + n_cls)
@@ -162,6 +196,12 @@ def _efdet_row_targets(kind, rows, from_coarsest=0):
         conf = np.arange(rows) % (_N_CLS + 1) == 0
         std[conf], bias[conf] = _EFDET_TARGETS['conf']
         bias[conf] += shift
+    if kind == 'class' and rows == 3:                  # RAPiD (d1_rapid): one objectness logit per anchor, no classes
+        std[:], bias[:] = _RAPID_TARGETS['conf']
+    if kind == 'bbox' and rows == 15:                  # RAPiD: (tx, ty, tw, th, t_angle) per anchor
+        for k, v in enumerate(_rapid_kinds(5, 15)):
+            std[k], bias[k] = _RAPID_TARGETS[v] if v == 'angle' else _EFDET_TARGETS['cell_' + v]
+        return std, bias
     if kind == 'bbox':
         # 4 channels: FCOS (models/detlayers/fcos2.py:222-251); 9 anchors: RetinaNet, cx = acx + tx * aw with anchors up
         # to 1 149 px (models/detlayers/retinanet.py:21-28,63-70) -- a centre offset of a few percent of the anchor keeps

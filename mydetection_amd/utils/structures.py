@@ -4,7 +4,8 @@ Same fields and methods as the reference ``ImageObjects``; ``post_process`` / ``
 batched HIP kernel (filter -> top-512 -> class-aware NMS) on the device that holds the
 candidates instead of copying all N candidates to the host and looping over classes with
 torchvision.ops.nms.  Results (order included) are those of the reference: class id
-ascending, score descending inside a class.
+ascending, score descending inside a class.  Rotated boxes ('cxcywhd', rows (cx, cy, w, h, deg)) take the same kernel
+on columns 0-3 -- the reference's NMS ignores the angle too (utils/structures.py:137-149) -- with the angle carried along.
 """
 import torch
 
@@ -21,8 +22,7 @@ class ImageObjects():
         bboxes: 2-d tensor, torch.float32
         cats: 1-d tensor, torch.int64, categories
         scores (optional): 1-d tensor, torch.float32, scores
-        bb_format (optional): 'cxcywh' (the hot path); 'cxcywhd' is accepted by the container
-                              but rotated boxes are outside the scope of the kernels
+        bb_format (optional): 'cxcywh', or 'cxcywhd' (rotated boxes: cx, cy, w, h, angle in degrees)
         img_hw: tuple-like, image (height, width)
     '''
     def __init__(self, bboxes, cats, masks=None, scores=None, bb_format='cxcywh', img_hw=None):
@@ -91,7 +91,7 @@ class ImageObjects():
 
     def _from_records(self, rec, b=0):
         k = ops.check_counts([int(rec['count'][b])])[0]          # the one host sync: how many survived
-        return ImageObjects(rec['bbox'][b, :k], rec['class_idx'][b, :k], None, rec['score'][b, :k],
+        return ImageObjects(ops.record_boxes(rec, b, k), rec['class_idx'][b, :k], None, rec['score'][b, :k],
                             self._bb_format, img_hw=self.img_hw)
 
     def post_process(self, conf_thres, nms_thres):
@@ -101,7 +101,7 @@ class ImageObjects():
         '''
         assert self.masks is None
         assert self.scores is not None
-        if self._bb_format != 'cxcywh':
+        if self._bb_format not in _BOX_WIDTH:
             raise NotImplementedError()
         bb, cats, sc = self._device_fields()
         rec = ops.postprocess(bb[None], cats[None], sc[None], conf_thres, nms_thres, TOPK)
@@ -121,7 +121,7 @@ class ImageObjects():
         assert dts.scores is not None
         if dts.bboxes.shape[0] == 0:
             return dts
-        if dts._bb_format != 'cxcywh':
+        if dts._bb_format not in _BOX_WIDTH:
             raise NotImplementedError()
         if len(dts) > TOPK:
             raise NotImplementedError(f'non_max_suppression handles at most {TOPK} boxes per image')
@@ -132,7 +132,8 @@ class ImageObjects():
     def bboxes_to_original_(self, pad_info):
         '''
         Recover the bbox from the padded image to the original image
-        (reference: utils/structures.py:175-189).  pad_info: (ori w, ori h, tl x, tl y, imw, imh)
+        (reference: utils/structures.py:175-189).  pad_info: (ori w, ori h, tl x, tl y, imw, imh).  Columns 0-3 only: the
+        angle of a 'cxcywhd' box is unchanged.
         '''
         assert self.masks is None, 'this func with masks is not currently supported'
         assert len(pad_info) == 6
@@ -141,7 +142,12 @@ class ImageObjects():
             if not self.bboxes.is_cuda:
                 self._device_fields()
             self.bboxes = self.bboxes.contiguous()
-            ops.bboxes_to_original_(self.bboxes, pad_info)
+            if self.bboxes.shape[1] == 4:
+                ops.bboxes_to_original_(self.bboxes, pad_info)
+            else:
+                xywh = self.bboxes[:, :4].contiguous()
+                ops.bboxes_to_original_(xywh, pad_info)
+                self.bboxes[:, :4] = xywh
         self.img_hw = (ori_h, ori_w)
 
     def sanity_check(self):
@@ -169,6 +175,9 @@ class ImageObjects():
         '''
         assert self.bboxes.dim() == 2
         assert self.bboxes.shape[0] == self.cats.shape[0] == self.scores.shape[0]
+        if eval_type == 'cxcywhd':
+            assert self._bb_format == 'cxcywhd'
+            return _json_rotated(self.bboxes.cpu(), self.scores.cpu(), self.cats.cpu(), img_id, catIdx2id)
         if eval_type != 'x1y1wh':
             raise NotImplementedError()
         assert self._bb_format == 'cxcywh'
@@ -178,6 +187,18 @@ class ImageObjects():
         table, host_map = _category_table(catIdx2id, bb.device)
         rows, cat = ops.detections_to_json(bb.contiguous()[None], sc.contiguous()[None], cats.contiguous()[None], None, table)
         return _json_rows(rows[0].cpu().tolist(), cat[0].cpu().tolist(), img_id, host_map)
+
+
+_BOX_WIDTH = {'cxcywh': 4, 'cxcywhd': 5}
+
+
+def _json_rotated(bboxes, scores, cats, img_id, catIdx2id):
+    """to_json(eval_type='cxcywhd') (reference: utils/structures.py:245-247): the five box values as Python floats, no
+    arithmetic, so it runs on the host copy of the detections."""
+    from .constants import COCO_CATEGORY_IDS
+    table = COCO_CATEGORY_IDS if catIdx2id is None else catIdx2id
+    return [{'image_id': img_id, 'category_id': table[int(c)], 'bbox': [float(t) for t in bb], 'score': float(s)}
+            for bb, c, s in zip(bboxes.tolist(), cats.tolist(), scores.tolist())]
 
 
 def _category_table(catIdx2id, device):
@@ -222,6 +243,16 @@ def batched_to_json(rec, img_ids, eval_type='x1y1wh', catIdx2id=None) -> list:
     `to_json` of every image of a batch of detection records (the concatenation the reference builds image by image,
     api/detection.py:67-74): one launch, one device->host copy.  img_ids: one id per image.
     '''
+    if eval_type == 'cxcywhd':
+        assert 'angle' in rec, "eval_type 'cxcywhd' needs rotated records"
+        counts = ops.check_counts(rec['count'].cpu().tolist())
+        bbox, angle = rec['bbox'].cpu(), rec['angle'].cpu()
+        score, cls = rec['score'].cpu(), rec['class_idx'].cpu()
+        out = []
+        for b, (k, img_id) in enumerate(zip(counts, img_ids)):
+            boxes = torch.cat([bbox[b, :k], angle[b, :k, None]], dim=1)
+            out += _json_rotated(boxes, score[b, :k], cls[b, :k], img_id, catIdx2id)
+        return out
     if eval_type != 'x1y1wh':
         raise NotImplementedError()
     table, host_map = _category_table(catIdx2id, rec['bbox'].device)
@@ -239,6 +270,8 @@ def batched_post_process(bboxes, cats, scores, conf_thres, nms_thres, records=No
     The batched form of `for d in dts: d.post_process(...)` (examples/train.py:229-232):
     bboxes [B,N,4], cats [B,N], scores [B,N] on the device -> fixed-size records
     {count [B], bbox [B,512,4], class_idx [B,512], score [B,512], index [B,512]}, no host sync.
-    records: optional int32 [B, REC_WORDS] buffer to write (rows of a larger batch's record buffer).
+    bboxes [B,N,5] (cxcywhd) take the rotated kernel: rotated records, 'angle' [B,512] added.
+    records: optional int32 [B, REC_WORDS] buffer (REC_ROT_WORDS for rotated boxes) to write (rows of a larger batch's
+    record buffer).
     '''
     return ops.postprocess(bboxes, cats, scores, conf_thres, nms_thres, TOPK, records=records)
