@@ -5,11 +5,11 @@
 // with coalesced 16-byte loads -- the pixel-major head rows are contiguous in memory -- into rows padded to an
 // odd number of floats, so that in the compute phase, where a THREAD owns one candidate (pixel, anchor) and walks
 // its 80 class logits, the 64 lanes of a wave (64 different pixels, same channel) hit 64 different banks.
-// The class max / first argmax is a sequential strict-greater scan, i.e. torch.max's order: on the logits while
-// the float32 logistic keeps them apart, on the sigmoid values themselves once the max logit is >= 5 (near
-// saturation distinct logits collapse onto one float32 sigmoid and the reference's "first index among equal
-// sigmoids" is decided by those collisions).  Box arithmetic follows the reference's operation order; the file is
-// built with -ffp-contract=off so no product is fused into a sum.  Outputs of a wave are 64 consecutive
+// The class max / first argmax is torch.max over the float32 sigmoids: a strict-greater scan of the logits finds the
+// best and the runner-up logit, and where the float32 logistic merges the two (neighbouring float32 logits share one
+// float32 sigmoid from about -2 up, where the logistic's slope shrinks a logit ulp below the ulp of its value) the
+// sigmoid values decide and the first index among equal ones wins.  Box arithmetic follows the reference's operation
+// order; the file is built with -ffp-contract=off so no product is fused into a sum.  Outputs of a wave are 64 consecutive
 // candidates: coalesced 16-byte box stores.  All pyramid levels are decoded by ONE launch (a tile belongs to a
 // level), and a workgroup prefetches its next tile into registers while it computes the current one.
 //
@@ -172,24 +172,15 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs p) {
                 best = take ? ob : best;
                 bi = take ? obi : bi;
             }
-            float cmax;
-            // Below 5 distinct logits have distinct float32 logistics.  From 5 up two logits can share one -- but only when
-            // their logistics are closer than the error of 1 / (1 + expf(-x)) there (<= 9e-8 per value: 6e-8 of 1 + e, 3e-8 of
-            // the reciprocal): with a true difference of e^-best * (best - second) >= 4.8e-7 (eight ulps) the order of the
-            // computed values is the order of the logits and the scan above has the winner.  Past 15 that gap exceeds 2 and
-            // the cruder rule takes over (runner-up two below the best, or below 15 when the best one is past 17, where the
-            // float32 logistic is exactly 1).  Correlated class logits -- many classes large at the same cell -- made the cruder
-            // rule alone send a quarter of the waves of a synthetic head down the collision path (decode 0.059 -> 0.080 ms).
-            bool isolated = (best > -80.0f && best < 5.0f) || p.C == 0;
-            if (best >= 5.0f && p.C > 0) {                        // (rare: the exponential is not on the common path)
-                const float tie = best < 15.0f ? best - fminf(2.0f, 4.8e-7f * expf(best)) : fminf(best - 2.0f, 15.0f);
-                isolated = second < tie;
-            }
-            if (p.C == 0) {
-                cmax = 1.0f;
-            } else if (isolated) {
-                cmax = mydet_sigmoid(best);
-            } else {                                   // near saturation: compare the sigmoid values themselves
+            // The scan's winner is torch.max's answer exactly when its float32 logistic is strictly above the runner-up's:
+            // no class has a logit between `second` and `best`, every other one is <= `second`, and 1 / (1 + expf(-x)) is
+            // monotone, so no other class reaches the winner's value.  Otherwise (an exact tie, or two neighbouring logits
+            // merged by float32 rounding anywhere from about -2 up) the values decide below.  Where even the best logistic is
+            // 0 (every logit below -88.7: expf(-x) overflows) the scan's winner stands: the exact logistics there are distinct
+            // float32 denormals down to -103, and the largest logit is their first maximum, as in float64.
+            float cmax = p.C == 0 ? 1.0f : mydet_sigmoid(best);
+            const bool isolated = p.C == 0 || cmax == 0.0f || mydet_sigmoid(second) < cmax;
+            if (!isolated) {                           // rare: compare the sigmoid values themselves
                 // ... of the classes that can tie with the best one.  The logistic is monotonic, and a logit two below the best
                 // (or below 15 when the best one is past 17, where the float32 logistic is exactly 1) has a float32 logistic
                 // at least four ulps smaller: it can neither win nor tie, so its logistic is not evaluated (a wave in which ONE

@@ -402,16 +402,23 @@ struct SpDecArgs {
     SpDecNode d[SP_MAX];
 };
 
-// first maximum of sigmoid(x) over increasing k.  Below 5 the logits are compared (sigmoid is monotone; decode_kernel does
-// the same); from 5 up float32 sigmoids of different logits coincide more and more (all of them from 17.4), so there
-// the sigmoid values decide and an equal value keeps the earlier class -- what torch.max over the sigmoids returns.
+// first maximum of sigmoid(x) over increasing k: the logit `best` of the class bi.  Neighbouring float32 logits share one
+// float32 sigmoid at any magnitude from about -2 up (all of them from 17.4), so a larger logit takes over only with a
+// larger sigmoid and an equal value keeps the earlier class -- what torch.max over the sigmoids returns.  A logit that is
+// not above the best one cannot have a larger sigmoid (monotone).  One in [-79, 8] that is at least 2^-9 above it has one
+// without a logistic being evaluated: the true values then differ by >= 11 ulps (slope >= 3.3e-4 on [0, 8]; below 0 a
+// relative step >= 2^-10 of a normal float, or a factor e when best <= -80), and 1 / (1 + expf(-x)) is within 2 ulps of
+// the truth.  Where the larger logistic is 0 too (logits below -88.7: expf(-x) overflows) the larger logit wins, as in
+// decode_kernel: the exact logistics there are distinct float32 denormals down to -103.  (The first class a lane sees,
+// best == -inf, is always taken.)
 __device__ __forceinline__ void dec_update(float &best, int &bi, float x, int k) {
-    if (x > best) {
-        if (x < 5.0f || mydet_sigmoid(x) > mydet_sigmoid(best)) {
-            best = x;
-            bi = k;
-        }
+    bool take = x - best >= 0x1p-9f && fabsf(x + 35.5f) <= 43.5f;
+    if (!take && x > best) {                                   // rare: where two logistics can coincide
+        const float sx = mydet_sigmoid(x);
+        take = sx > mydet_sigmoid(best) || sx == 0.0f;
     }
+    best = take ? x : best;
+    bi = take ? k : bi;
 }
 
 template <int KS, int NBA>
@@ -501,25 +508,24 @@ __global__ __launch_bounds__(256, 4) void sepconv_decode_kernel(const SpDecArgs 
                     if (k < a.n_cls) dec_update(best, bi, v[e], k);
                 }
             }
-            // the pixel's four lanes hold interleaved class subsets: the larger value wins, an equal one only with the
-            // lower class index (= the first maximum of the sequential scan)
+            // the pixel's four lanes hold interleaved class subsets: the larger sigmoid value wins, an equal one only with
+            // the lower class index (= the first maximum of the sequential scan); two values 0: the logits decide, as in dec_update
+            float sb = mydet_sigmoid(best);
 #pragma unroll
             for (int off = 16; off <= 32; off <<= 1) {
-                const float ob = __shfl_xor(best, off);
+                const float os = __shfl_xor(sb, off), ob = __shfl_xor(best, off);
                 const int obi = __shfl_xor(bi, off);
-                bool gt = ob > best, eq = ob == best;
-                if (fmaxf(ob, best) >= 5.0f) {
-                    const float so = mydet_sigmoid(ob), sb = mydet_sigmoid(best);
-                    gt = so > sb;
-                    eq = so == sb;
-                }
+                const bool zero = os == 0.0f && sb == 0.0f;
+                const bool gt = zero ? ob > best : os > sb;
+                const bool eq = zero ? ob == best : os == sb;
                 const bool take = gt || (eq && obi < bi);
+                sb = take ? os : sb;
                 best = take ? ob : best;
                 bi = take ? obi : bi;
             }
             if (kk == 0 && valid) {
                 const int64_t n = cand0 + (int64_t)an * hw;
-                a.score[n] = mydet_sigmoid(best);
+                a.score[n] = sb;
                 a.cidx[n] = (int64_t)bi;
             }
         }

@@ -986,16 +986,38 @@ def test_detector_lanes_same_bits_before_and_after_capture(monkeypatch):
             assert torch.equal(d.cats, e.cats) and torch.equal(d.scores, e.scores) and torch.equal(d.bboxes, e.bboxes)
 
 
-@pytest.mark.parametrize('variant', ['plain', 'saturated_and_tied'])
+@pytest.mark.parametrize('variant', ['plain', 'saturated_and_tied', 'sub5_collisions'])
 def test_fused_retina_decode_equals_two_launch_path(monkeypatch, variant):
     """EfDetHead + RetinaLayer: the decode in the epilogue of the towers' last layers (ops.sepconv_decode_retina: no class
     logits in memory) gives the candidates of the two-launch path (last sepconv writes logits, decode kernel reads
     them) bit for bit -- boxes, scores, class indices -- also with logits in the saturated range of the float32
-    sigmoid (>= 5: sigmoid values decide; >= 17.4: all equal 1.0, the first class wins) and with exactly tied classes."""
+    sigmoid (>= 5: sigmoid values decide; >= 17.4: all equal 1.0, the first class wins) and with exactly tied classes.
+    sub5_collisions: pairs of classes a few float32 steps apart in (-2, 5), where neighbouring logits mostly share one
+    float32 sigmoid: both paths must give torch.max's answer over those sigmoids (the earlier class where they collide),
+    which the device computes from the same logits."""
     from mydetection_amd import ops, synth
     from mydetection_amd.models.general import name_to_model
     m, cfg = name_to_model('efficientdet-d1')
     sd = synth.make_state_dict(m.state_dict(), 'efficientdet-d1')
+    pairs = {}
+    if variant == 'sub5_collisions':
+        rng = np.random.default_rng(5)
+        A, C = 9, cfg['general.num_class']
+        for lvl in range(5):
+            wk, bk = f'rpn.class_nets.{lvl}.3.pointwise.weight', f'rpn.class_nets.{lvl}.3.pointwise.bias'
+            w, b = sd[wk].clone().view(A, C, -1), sd[bk].clone().view(A, C)
+            for a in range(8):                              # anchor 8 keeps the tower's own logits
+                j = int(rng.integers(0, C - 1))
+                k = int(rng.integers(j + 1, C))             # same lane or another one (a lane holds classes 4q..4q+3 mod 16)
+                xj = np.float32(rng.uniform(-2.0, 5.0))
+                xk = xj
+                for _ in range(int(rng.choice([0, 1, 1, 1, 2, 3]))):
+                    xk = np.nextafter(xk, np.float32(np.inf))
+                w[a] = 0.0                                  # no BatchNorm after this layer: the logits are the biases
+                b[a] = -20.0 - torch.from_numpy(rng.random(C).astype(np.float32))
+                b[a, j], b[a, k] = float(xj), float(xk)
+                pairs[(lvl, a)] = b[a].clone()
+            sd[wk], sd[bk] = w.view(A * C, -1, 1, 1), b.view(-1)
     if variant == 'saturated_and_tied':
         for lvl in range(5):
             wk, bk = f'rpn.class_nets.{lvl}.3.pointwise.weight', f'rpn.class_nets.{lvl}.3.pointwise.bias'
@@ -1030,6 +1052,17 @@ def test_fused_retina_decode_equals_two_launch_path(monkeypatch, variant):
         assert ((a1 >= 70) & (a1 < 80)).all()
         assert (a2 == 5).all() and bool((sc[:, 2 * n3:3 * n3] == 1.0).all())
         assert (a3 == 20).float().mean() > 0.5 and not (a3 == 70).any()
+    if variant == 'sub5_collisions':
+        p = 1.0 / (1.0 + torch.exp(-torch.stack(list(pairs.values())).cuda()))
+        vmax, want = torch.max(p, -1)
+        top2 = torch.topk(p, 2, -1).values
+        assert int((top2[:, 0] == top2[:, 1]).sum()) >= 20, 'most pairs must share one float32 sigmoid'
+        offs = np.cumsum([0] + [9 * h * h for h in (48, 24, 12, 6, 3)])
+        for i, (lvl, a) in enumerate(pairs):
+            hw = (48 >> lvl) ** 2
+            n0 = int(offs[lvl]) + a * hw
+            assert (ci[:, n0:n0 + hw] == want[i]).all(), (lvl, a, int(want[i]))
+            assert (sc[:, n0:n0 + hw] == vmax[i]).all(), (lvl, a)
 
 
 @pytest.mark.parametrize('name', ['yolov3_80', 'efficientdet-d1'])
