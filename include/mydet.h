@@ -288,6 +288,16 @@ typedef struct mydet_decode_level {
 int mydet_decode_levels_f32(int mode, int nlevels, const mydet_decode_level *levels, int box_astride, int box_c0,
                             int cls_astride, int cls_c0, int conf_c0, int A, int C, int B, int img_h, int img_w,
                             float *bbox, int64_t *class_idx, float *score, int64_t N, void *stream);
+/* The Ultralytics (YOLOv5) decode, DetectLayer.forward models/detlayers/uv5.py:42-91 (inference branch), every level in one
+ * launch.  It has an entry point of its own because the `mode` argument above is closed: values above MYDET_DECODE_RAPID are
+ * rejected by mydet_decode_f32 / mydet_decode_levels_f32.  Layout, anchors, candidate order, outputs and argument checks
+ * are those of mydet_decode_levels_f32 with MYDET_DECODE_YOLO (1 <= C <= 128, anchors required, bbox [B,N,4]); the score
+ * and class_idx are YOLO's bit for bit.  Only the box differs, in float32 in this operation order:
+ *   s = sigmoid(t[0..3]);  cx = ((s0*2 - 0.5) + x) * stride, cy likewise with y;  w = ((s2*2) * (s2*2)) * anchor_w, h likewise.
+ * Nothing is clamped: cx, cy >= -stride/2 and w, h <= 4 * anchor. */
+int mydet_decode_uv5_levels_f32(int nlevels, const mydet_decode_level *levels, int box_astride, int box_c0,
+                                int cls_astride, int cls_c0, int conf_c0, int A, int C, int B, int img_h, int img_w,
+                                float *bbox, int64_t *class_idx, float *score, int64_t N, void *stream);
 int mydet_decode_f32(int mode,
                      const float *box, int64_t ldbox, int box_astride, int box_c0,
                      const float *cls, int64_t ldcls, int cls_astride, int cls_c0, int conf_c0,

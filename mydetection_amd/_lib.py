@@ -50,6 +50,8 @@ SIGNATURES = {
     'mydet_spp_concat_f32': [c_ptr, c_i64, c_ptr, c_i64] + [c_int] * 7 + [c_ptr],
     'mydet_decode_levels_f32': [c_int, c_int, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                 c_ptr, c_ptr, c_ptr, c_i64, c_ptr],
+    'mydet_decode_uv5_levels_f32': [c_int, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_ptr, c_ptr, c_ptr, c_i64, c_ptr],
     'mydet_decode_f32': [c_int, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_int,
                          c_int, c_int, c_int, c_f32, c_int, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr],
     'mydet_postprocess_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_int, c_ptr, c_ptr, c_ptr, c_ptr,

@@ -137,6 +137,21 @@ def _build():
     c.update(_test(640, 0.45))
     out['u5m_fcs2'] = c
 
+    # plain YOLOv5-m: the same trunk, pyramid and head under YOLOv5's own box parameterisation (configs/ulo5m.json; the four
+    # model.detect.* keys behind anchor_indices are read by the training branch alone and kept so that the dict equals the
+    # reference file's inference keys)
+    c = _general('RGB_1', 32)
+    c.update(_pyramid('ultralytics', 3, 'ultralytics'))
+    c.update(ul)
+    c.update({'__doc': "Ultralytics's YOLOv5-m", 'model.rpn.name': 'yolov3', 'model.yolo.num_anchor_per_level': 3,
+              'model.pred_layer': 'Ultralytics',
+              'model.detect.anchors': [[10, 13], [16, 30], [33, 23], [30, 61], [62, 45], [59, 119], [116, 90], [156, 198], [373, 326]],
+              'model.detect.anchor_indices': [[0, 1, 2], [3, 4, 5], [6, 7, 8]], 'model.detect.sample_selection': 'best',
+              'model.detect.confidence_target': 'zero-one', 'model.detect.negative_threshold': 0.7,
+              'model.detect.loss_bbox': 'smooth_L1'})
+    c.update(_test(640, 0.45))
+    out['ulo5m'] = c
+
     # RAPiD, the rotated-box detector for overhead fisheye images (configs/rapid.json, rapid_psl1.json, yv3_pl1_80.json,
     # u5m_rapid.json, d1_rapid.json): 'cxcywhd' boxes, 5 box parameters, the RAPiDLayer decode
     rapid_anchors = [[18.7807, 33.4659], [28.8912, 61.7536], [48.6849, 68.3897], [45.0668, 101.4673], [63.0952, 113.5382],

@@ -19,6 +19,9 @@
 //   RAPID  models/detlayers/rapid.py:36-81     YOLO box + deg=((s(t4)*2*pi-pi)/pi)*180, score=s(conf) (C == 0) or
 //                                               sqrt(s(conf)*max s(cls)); 5-float rows (20 B): a wave's 64 candidates
 //                                               are one contiguous 1280-byte run written as dword stores
+//   UV5    models/detlayers/uv5.py:42-91       s=s(t[0..3]), cx=(s0*2-0.5+x)*stride, w=(s2*2)^2*aw, score as YOLO; no
+//                                               clamp: cx >= -stride/2, w <= 4*aw.  Not a value of the public `mode`
+//                                               argument (which ends at RAPID): mydet_decode_uv5_levels_f32 selects it
 #include <cstdlib>
 
 #include "common.h"
@@ -26,6 +29,7 @@
 namespace {
 
 constexpr int MAX_A = 16;
+constexpr int DECODE_UV5 = MYDET_DECODE_RAPID + 1;       // internal: reached through its own entry point only
 constexpr int MAX_LEVELS = 5;
 constexpr int MAXV = 12;          // float4 staging registers per thread (one tile = at most MAXV * 256 float4)
 
@@ -216,6 +220,17 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs p) {
                 o[2] = expf(t2) * aw;
                 o[3] = expf(t3) * ah;
                 sc = mydet_sigmoid(rowp[a * p.cls_astride + p.conf_c0]) * cmax;
+            } else if (p.mode == DECODE_UV5) {
+                // float32 in the reference's operation order: ((s*2 - 0.5) + g) * stride and ((s*2) * (s*2)) * anchor, every
+                // operation rounded on its own (tests/test_uv5_host.py restates this order on the reference layer's fixture
+                // and matches its boxes bit for bit)
+                const float s0 = mydet_sigmoid(t0), s1 = mydet_sigmoid(t1);
+                const float s2 = mydet_sigmoid(t2) * 2.0f, s3 = mydet_sigmoid(t3) * 2.0f;
+                o[0] = ((s0 * 2.0f - 0.5f) + (float)gx) * st;
+                o[1] = ((s1 * 2.0f - 0.5f) + (float)gy) * st;
+                o[2] = (s2 * s2) * aw;
+                o[3] = (s3 * s3) * ah;
+                sc = mydet_sigmoid(rowp[a * p.cls_astride + p.conf_c0]) * cmax;
             } else if (p.mode == MYDET_DECODE_RETINA) {
                 const float acx = st * 0.5f + (float)gx * st;
                 const float acy = st * 0.5f + (float)gy * st;
@@ -282,13 +297,11 @@ unsigned magic20(unsigned q, unsigned max_i) {       // m with (i * m) >> 20 == 
     return m;
 }
 
-}  // namespace
-
-extern "C" int mydet_decode_levels_f32(int mode, int nlevels, const mydet_decode_level *levels, int box_astride,
-                                       int box_c0, int cls_astride, int cls_c0, int conf_c0, int A, int C, int B,
-                                       int img_h, int img_w, float *bbox, int64_t *class_idx, float *score, int64_t N,
-                                       void *stream) {
-    if (mode < 0 || mode > MYDET_DECODE_RAPID || !levels || nlevels <= 0 || nlevels > MAX_LEVELS || !bbox || !class_idx || !score)
+// Argument checks, tile plan and launch of every decode entry point; `mode` is a public MYDET_DECODE_* value or DECODE_UV5.
+int decode_levels(int mode, int nlevels, const mydet_decode_level *levels, int box_astride, int box_c0, int cls_astride,
+                  int cls_c0, int conf_c0, int A, int C, int B, int img_h, int img_w, float *bbox, int64_t *class_idx,
+                  float *score, int64_t N, void *stream) {
+    if (mode < 0 || mode > DECODE_UV5 || !levels || nlevels <= 0 || nlevels > MAX_LEVELS || !bbox || !class_idx || !score)
         return MYDET_E_BADARG;
     if (A <= 0 || A > MAX_A || C < (mode == MYDET_DECODE_RAPID ? 0 : 1) || C > 128 || B <= 0 || ((uintptr_t)bbox & 15)) return MYDET_E_BADARG;
     DecodeArgs p;
@@ -371,6 +384,25 @@ extern "C" int mydet_decode_levels_f32(int mode, int nlevels, const mydet_decode
     else if (need <= 10) launch_nvb<10>(needb, grid, lds, stream, p);
     else launch_nvb<12>(needb, grid, lds, stream, p);
     return mydet_launch_status();
+}
+
+}  // namespace
+
+extern "C" int mydet_decode_levels_f32(int mode, int nlevels, const mydet_decode_level *levels, int box_astride,
+                                       int box_c0, int cls_astride, int cls_c0, int conf_c0, int A, int C, int B,
+                                       int img_h, int img_w, float *bbox, int64_t *class_idx, float *score, int64_t N,
+                                       void *stream) {
+    if (mode < 0 || mode > MYDET_DECODE_RAPID) return MYDET_E_BADARG;      // the public modes end at RAPID
+    return decode_levels(mode, nlevels, levels, box_astride, box_c0, cls_astride, cls_c0, conf_c0, A, C, B, img_h, img_w,
+                         bbox, class_idx, score, N, stream);
+}
+
+extern "C" int mydet_decode_uv5_levels_f32(int nlevels, const mydet_decode_level *levels, int box_astride, int box_c0,
+                                           int cls_astride, int cls_c0, int conf_c0, int A, int C, int B, int img_h,
+                                           int img_w, float *bbox, int64_t *class_idx, float *score, int64_t N,
+                                           void *stream) {
+    return decode_levels(DECODE_UV5, nlevels, levels, box_astride, box_c0, cls_astride, cls_c0, conf_c0, A, C, B, img_h,
+                         img_w, bbox, class_idx, score, N, stream);
 }
 
 extern "C" int mydet_decode_f32(int mode, const float *box, int64_t ldbox, int box_astride, int box_c0,

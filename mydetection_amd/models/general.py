@@ -106,14 +106,18 @@ class OneStageBBox(torch.nn.Module):
         scores = torch.empty((nB, n_total), dtype=torch.float32, device=x.device)
         descs = [getattr(layer, '_describe', lambda *_: None)(raw, self.img_size)
                  for layer, raw in zip(self.det_layers, all_branch_preds)]
-        if all(d is not None for d in descs) and len({(d['mode'], d['layout'], d['A'], d['C']) for d in descs}) == 1:
+        if all(d is not None for d in descs) and \
+                len({(d['mode'], d.get('launch'), d['layout'], d['A'], d['C']) for d in descs}) == 1:
             # every level in ONE launch, written at its offset of the level-concatenated arrays
             levels, n_off = [], 0
             for d, n in zip(descs, counts):
                 levels.append(dict(d['level'], n_off=n_off))
                 n_off += n
             d = descs[0]
-            ops.decode_levels(d['mode'], levels, *d['layout'], d['A'], d['C'], nB, self.img_size, bbs, cls_idx, scores)
+            if d.get('launch') is not None:     # a decode with an entry point of its own (Ultralytics: ops.decode_uv5_levels)
+                d['launch'](levels, *d['layout'], d['A'], d['C'], nB, self.img_size, bbs, cls_idx, scores)
+            else:
+                ops.decode_levels(d['mode'], levels, *d['layout'], d['A'], d['C'], nB, self.img_size, bbs, cls_idx, scores)
             return bbs, cls_idx, scores
         n_off = 0
         for i, raw_preds in enumerate(all_branch_preds):

@@ -24,6 +24,7 @@ _DECODE_LAYERS = {                           # cfg['model.pred_layer']          
     'FCOS2': ('detlayers.fcos2', 'FCOSLayer'),
     'FCOS2_ATSS': ('detlayers.fcos2', 'FCOS_ATSS_Layer'),
     'RAPiD': ('detlayers.rapid', 'RAPiDLayer'),
+    'Ultralytics': ('detlayers.uv5', 'DetectLayer'),
 }
 
 

@@ -993,10 +993,10 @@ def decode(mode, box, ldbox, box_astride, box_c0, cls, ldcls, cls_astride, cls_c
     _lib.check(code, 'mydet_decode_f32')
 
 
-def decode_levels(mode, levels, box_astride, box_c0, cls_astride, cls_c0, conf_c0, A, C, B, img_hw, bbox, class_idx,
-                  score):
-    """Decode every pyramid level with one launch.  levels: list of dicts with keys box, ldbox, cls, ldcls,
-    anchors_wh (array-like [A,2] or None), H, W, stride, n_off."""
+def _decode_levels(entry, head, mode, levels, box_astride, box_c0, cls_astride, cls_c0, conf_c0, A, C, B, img_hw, bbox,
+                   class_idx, score):
+    """The level table, timer span and call shared by the multi-level decode entry points: `entry` is the C symbol, `head`
+    its arguments in front of the level count ((mode,) or ()), `mode` the decode whose bytes are accounted."""
     require_gpu(bbox, 'decode_levels')
     assert bbox.shape[-1] == _box_width(mode) and bbox.is_contiguous()
     n = len(levels)
@@ -1015,12 +1015,35 @@ def decode_levels(mode, levels, box_astride, box_c0, cls_astride, cls_c0, conf_c
         per_pix = A * (C + _box_width(mode) + (0 if mode == DECODE_RETINA else 1))
         work += 4.0 * B * lv['H'] * lv['W'] * per_pix + (12.0 + 4 * _box_width(mode)) * B * A * lv['H'] * lv['W']
     t0 = TIMER.start() if TIMER else None
-    code = _lib.lib().mydet_decode_levels_f32(mode, n, ctypes.cast(arr, ctypes.c_void_p), box_astride, box_c0,
-                                              cls_astride, cls_c0, conf_c0, A, C, B, int(img_hw[0]), int(img_hw[1]),
-                                              _ptr(bbox), _ptr(class_idx), _ptr(score), bbox.shape[1], _stream())
+    code = getattr(_lib.lib(), entry)(*head, n, ctypes.cast(arr, ctypes.c_void_p), box_astride, box_c0, cls_astride, cls_c0,
+                                      conf_c0, A, C, B, int(img_hw[0]), int(img_hw[1]), _ptr(bbox), _ptr(class_idx),
+                                      _ptr(score), bbox.shape[1], _stream())
     if t0:
         TIMER.stop('decode', t0, work, work)
-    _lib.check(code, 'mydet_decode_levels_f32')
+    _lib.check(code, entry)
+
+
+def decode_levels(mode, levels, box_astride, box_c0, cls_astride, cls_c0, conf_c0, A, C, B, img_hw, bbox, class_idx,
+                  score):
+    """Decode every pyramid level with one launch.  levels: list of dicts with keys box, ldbox, cls, ldcls,
+    anchors_wh (array-like [A,2] or None), H, W, stride, n_off."""
+    _decode_levels('mydet_decode_levels_f32', (mode,), mode, levels, box_astride, box_c0, cls_astride, cls_c0, conf_c0, A, C,
+                   B, img_hw, bbox, class_idx, score)
+
+
+def decode_uv5_levels(levels, box_astride, box_c0, cls_astride, cls_c0, conf_c0, A, C, B, img_hw, bbox, class_idx, score):
+    """The Ultralytics (YOLOv5) decode of every pyramid level with one launch (mydet_decode_uv5_levels_f32): arguments as
+    decode_levels without the mode; the head layout, bytes and outputs are DECODE_YOLO's."""
+    _decode_levels('mydet_decode_uv5_levels_f32', (), DECODE_YOLO, levels, box_astride, box_c0, cls_astride, cls_c0, conf_c0,
+                   A, C, B, img_hw, bbox, class_idx, score)
+
+
+def decode_uv5(box, ldbox, box_astride, box_c0, cls, ldcls, cls_astride, cls_c0, conf_c0, anchors_wh, A, C, B, H, W, stride,
+               img_hw, bbox, class_idx, score, n_off):
+    """The Ultralytics decode of one level into bbox[B,N,4] / class_idx[B,N] / score[B,N] at candidate offset n_off."""
+    require_gpu(box, 'decode_uv5')
+    level = dict(box=box, ldbox=ldbox, cls=cls, ldcls=ldcls, anchors_wh=anchors_wh, H=H, W=W, stride=stride, n_off=n_off)
+    decode_uv5_levels([level], box_astride, box_c0, cls_astride, cls_c0, conf_c0, A, C, B, img_hw, bbox, class_idx, score)
 
 
 def record_words(box_width):
