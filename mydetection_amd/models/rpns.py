@@ -297,7 +297,8 @@ class EfDetHead_wCenter(nn.Module):
     class tower (repeat x sepconv-BN-swish, dense 3x3 to n_cls [+1]), a box tower (repeat x sepconv-BN-swish) feeding
     a dense 3x3 to 4 box logits and, through one more sepconv-BN-swish, a dense 3x3 to the centerness logit.
     The class and centerness convs write channel ranges of ONE pixel-major tensor, which the decode kernel reads
-    in place.  Output dict per level: 'bbox' [B,H,W,4], 'center' [B,H,W,1], 'class' [B,H,W,n_cls] (+ 'conf').
+    in place (the centerness logit sits at the first multiple of 4 at or behind the class logits).
+    Output dict per level: 'bbox' [B,H,W,4], 'center' [B,H,W,1], 'class' [B,H,W,n_cls] (+ 'conf').
     '''
     def __init__(self, cfg: dict):
         super().__init__()
@@ -333,28 +334,31 @@ class EfDetHead_wCenter(nn.Module):
     def forward(self, features: list):
         all_level_preds = []
         cls_ch = self.n_cls + 1 if self.enable_conf else self.n_cls
+        # the centerness conv writes a channel range of its own, and a kernel-writable range starts on a 16-byte boundary
+        # (ops.nhwc_ld): the first multiple of 4 at or behind the class logits -- channel 80 for 80 classes, 84 for conf + 80
+        ct_c0 = (cls_ch + 3) // 4 * 4
         for i, x in enumerate(features):
             nB, _, nH, nW = x.shape
-            # [B,H,W,ld]: channels [0, cls_ch) class (+conf) logits, channel cls_ch the centerness logit
-            both, ld = ops.empty_nhwc(nB, cls_ch + 1, nH, nW, x.device)
+            # [B,H,W,ld]: channels [0, cls_ch) class (+conf) logits, channel ct_c0 the centerness logit
+            both, ld = ops.empty_nhwc(nB, ct_c0 + 1, nH, nW, x.device)
             t = x
             for m in list(self.class_nets[i])[:-1]:
                 t = m(t)
             self.class_nets[i][-1](t, out=both[:, :cls_ch])
             bbox_feats = self.bbox_nets[i](x)
             bbox_pred = self.bbox_lasts[i](bbox_feats)
-            self.center_nets[i][1](self.center_nets[i][0](bbox_feats), out=both[:, cls_ch:cls_ch + 1])
+            self.center_nets[i][1](self.center_nets[i][0](bbox_feats), out=both[:, ct_c0:ct_c0 + 1])
             assert bbox_pred.shape[1] == 4
             cls_v = both.permute(0, 2, 3, 1)
             raw = RawPreds()
             raw['bbox'] = bbox_pred.permute(0, 2, 3, 1)
-            raw['center'] = cls_v[..., cls_ch:cls_ch + 1]
+            raw['center'] = cls_v[..., ct_c0:ct_c0 + 1]
             if self.enable_conf:
                 raw['conf'] = cls_v[..., 0:1]
                 raw['class'] = cls_v[..., 1:cls_ch]
             else:
                 raw['class'] = cls_v[..., :cls_ch]
             raw.packed = {'box': (bbox_pred, ops.nhwc_ld(bbox_pred), 4, 0),
-                          'cls': (both, ld, cls_ch + 1, 1 if self.enable_conf else 0, cls_ch)}
+                          'cls': (both, ld, ct_c0 + 1, 1 if self.enable_conf else 0, ct_c0)}
             all_level_preds.append(raw)
         return all_level_preds

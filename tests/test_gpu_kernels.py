@@ -5,6 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _arena import arena
+
 pytestmark = pytest.mark.gpu
 
 
@@ -155,7 +157,12 @@ def test_conv_p3_vs_fp64(dev, case):
     rd = res.to(dev).contiguous(memory_format=torch.channels_last) if res is not None else None
     kw = dict(out_ld=Cout + 12) if case.get('strided') else {}
     sc_d, sh_d = (scale.to(dev) if scale is not None else None), shift.to(dev)
-    y = ops.conv3x3_p3(xd, w3, sc_d, sh_d, s, case['act'], residual=rd, **kw)
+    chk = None
+    if case.get('strided'):              # the first launch writes into a poisoned arena: [guard | B*Ho*Wo*(Cout + 12) | guard]
+        out, chk = arena(B, Cout, ref.shape[2], ref.shape[3], Cout + 12, 0, dev)
+        y = ops.conv3x3_p3(xd, w3, sc_d, sh_d, s, case['act'], residual=rd, out=out)
+    else:
+        y = ops.conv3x3_p3(xd, w3, sc_d, sh_d, s, case['act'], residual=rd, **kw)
     assert y is not None and tuple(y.shape) == tuple(ref.shape)
     y2 = ops.conv3x3_p3(xd, w3, sc_d, sh_d, s, case['act'], residual=rd, **kw)
     assert torch.equal(y, y2)
@@ -167,6 +174,9 @@ def test_conv_p3_vs_fp64(dev, case):
     assert err <= 4.0 * err32 + 1e-6, (err, err32)
     if case.get('strided'):              # nothing written behind the Cout channels of a padded output row
         assert ops.nhwc_ld(y) == Cout + 12
+        torch.cuda.synchronize()
+        chk.view_defined('conv_p3 output')
+        chk.outside_untouched('conv_p3 output')
 
 
 def test_split_bf16_non_finite_semantics(dev):
@@ -246,8 +256,18 @@ def _split_bf16_case(dev, case):
     args = (xd, wd, scale.to(dev) if scale is not None else None, shift.to(dev), k, s, (p, p, p, p), case['act'])
     ops.TIMER = ops.KernelTimer()
     p3_was, ops.CONV_P3 = ops.CONV_P3, False            # (conv_igemm_b3_kernel is under test: the patch-resident 3x3 kernel has its own test)
+    chk = None
     try:
-        y3 = ops.conv2d(*args, b3=w3, b3_min_rows=1, **kw).clone()
+        if case.get('strided'):         # padded output rows inside a poisoned arena: nothing may be written behind the Cout channels
+            out, chk = arena(B, Cout, Ho, Wo, Cout + 12, 0, dev)
+            y3 = ops.conv2d(*args, b3=w3, b3_min_rows=1, out=out, **{n: v for n, v in kw.items() if n != 'out_ld'})
+            assert ops.nhwc_ld(y3) == Cout + 12
+            torch.cuda.synchronize()
+            chk.view_defined('conv_igemm_b3 output')
+            chk.outside_untouched('conv_igemm_b3 output')
+            y3 = y3.clone()
+        else:
+            y3 = ops.conv2d(*args, b3=w3, b3_min_rows=1, **kw).clone()
     finally:
         timer, ops.TIMER = ops.TIMER, None
         ops.CONV_P3 = p3_was
@@ -412,6 +432,16 @@ def test_conv_igemm_output_slice_and_padded_ld(dev):
     assert y.shape == (1, 30, 8, 8) and ops.nhwc_ld(y) == 32
     ref = F.conv2d(x.cpu().double(), w.double())
     assert (y.cpu().double() - ref).abs().max() < 1e-4
+    # the same launch into poisoned arenas: 30 channels of a 32-float row (the head padding), and a channel slice [8, 38) of a
+    # 48-float row -- the pad lanes, the neighbour channels and both guards keep their sentinel, the slice equals the plain result
+    for ld, c0 in ((32, 0), (48, 8)):
+        out, chk = arena(1, 30, 8, 8, ld, c0, dev)
+        y2 = ops.conv2d(x, w.permute(0, 2, 3, 1).contiguous().to(dev), None, None, 1, 1, (0, 0, 0, 0), 0, out=out)
+        torch.cuda.synchronize()
+        assert y2.data_ptr() == out.data_ptr() and ops.nhwc_ld(y2) == ld
+        chk.view_defined('conv_igemm output')
+        chk.outside_untouched('conv_igemm output')
+        assert torch.equal(y2, y)
 
 
 def test_conv_stem(dev):
