@@ -225,6 +225,23 @@ int mydet_conv2d_igemm_b3_f32(const float *x, int64_t ldx, const uint16_t *w_pla
 int mydet_conv3x3_p3_f32(const float *x, int64_t ldx, const uint16_t *w_planes, const float *scale, const float *shift,
                          const float *residual, int64_t ldr, float *y, int64_t ldy, int B, int H, int W, int Cin, int Cout,
                          int stride, int act, void *stream);
+/* The 3 -> 32 stem (3x3, stride 1; mydet_conv2d_stem_f32) and the 3x3 stride-2 pad-1 layer behind it (mydet_conv3x3_p3_f32) as ONE
+ * launch (csrc/conv_stem_p3.hip): the workgroup of the second layer's 8 x 16-pixel x 64-channel tile computes the 17 x 33-pixel stem
+ * patch it needs on the matrix instructions, straight into the LDS patch its nine taps read -- the 32-channel full-resolution map is
+ * never written or read back.
+ *   y = act1(conv3x3_s2_pad1(act0(conv3x3_s1(x) * scale0 + shift0)) * scale1 + shift1),  act: MYDET_ACT_NONE | _LEAKY.
+ * x: logical [B,3,H,W] read through its element strides; stem output Hs x Ws with pad_t / pad_l as mydet_conv2d_stem_f32;
+ * y [B,Ho,Wo,ldy], Ho = (Hs - 1) / 2 + 1, Wo likewise.  w0_planes = mydet_split_bf16_f32 of the stem's OHWI weight with every row's
+ * K = 27 zero-padded to 32 (Cout 32, K 32); w1_planes = mydet_split_bf16_f32 of the second layer's [Cout][3][3][32] weight.
+ * Both layers use the split-bf16 arithmetic of mydet_conv2d_igemm_b3_f32 (float32 round-off; tests: 2e-5 * max|y| against float64).
+ * C0 == 32, stride0 == 1, stride1 == 2, Cout % 64 == 0; MYDET_E_UNSUPP otherwise (the caller then uses the two launches).
+ * ldy % 4 == 0, ldy >= Cout, y and the planes 16-byte aligned; MYDET_E_BADARG otherwise.
+ * Replaces netlist[0] and netlist[1] of models/backbones.py:14-30 (models/modules.py:76-95, twice). */
+int mydet_conv_stem_p3_f32(const float *x, int64_t sxb, int64_t sxc, int64_t sxh, int64_t sxw, const uint16_t *w0_planes,
+                           const float *scale0, const float *shift0, int act0, const uint16_t *w1_planes, const float *scale1,
+                           const float *shift1, int act1, float *y, int64_t ldy, int B, int H, int W, int C0, int Cout,
+                           int stride0, int pad_t, int pad_l, int Hs, int Ws, int stride1, void *stream);
+int mydet_conv_stem_p3_lds_bytes(void);               /* dynamic LDS of that launch (one resident patch slab + the image patch) */
 /* Test hook: the split-bf16 launcher reads MYDET_B3_WIDE / MYDET_B3_WAVES once per process; this reads them again.
  * Returns the form bits (1 = wide 128 x 256 tiles from 192 output channels, 2 = 8-wave workgroups). */
 int mydet_conv_b3_reload_tuning(void);

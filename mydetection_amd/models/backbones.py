@@ -2,7 +2,7 @@
 import torch.nn as nn
 
 from .. import ops
-from .modules import ConvBn, ConvBnLeaky, DarkBlock
+from .modules import ConvBn, ConvBnLeaky, DarkBlock, stem_p3
 
 
 class Darknet53(nn.Module):
@@ -26,7 +26,11 @@ class Darknet53(nn.Module):
 
     def forward(self, x):
         feats = []
+        y = stem_p3(self.netlist[0], self.netlist[1], x)        # stem + first stride-2 conv in one launch where it is the faster form
         for i, layer in enumerate(self.netlist):
+            if y is not None and i < 2:
+                x = y
+                continue
             x = layer(x)
             if i in (14, 23, 28):
                 feats.append(x)

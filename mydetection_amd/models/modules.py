@@ -121,6 +121,27 @@ class ConvBnLeaky(nn.Module, FusedConvMixin):
         return ops.conv2d(x, w, scale, shift, self.k, self.s, (p, p, p, p), ops.ACT_LEAKY, residual=residual, wino=u, wino4=u4, b3=b3)
 
 
+def stem_p3(cbl_0, cbl_1, x):
+    """cbl_1(cbl_0(x)) for a 3 -> 32 stride-1 stem `cbl_0` and the 3x3 stride-2 layer `cbl_1` behind it as ONE launch
+    (ops.conv_stem_p3: the 32-channel full-resolution map is never written), or None where ops.stem_p3_takes keeps the two
+    launches -- also when either module carries hooks, which only fire through its own __call__."""
+    if (cbl_0.training or cbl_1.training or (cbl_0.k, cbl_0.s, cbl_1.k, cbl_1.s) != (3, 1, 3, 2) or x.dim() != 4 or x.shape[1] != 3
+            or cbl_0.conv.out_channels != 32 or cbl_1.conv.in_channels != 32 or x.dtype != torch.float32 or not x.is_cuda
+            or cbl_0._forward_hooks or cbl_0._forward_pre_hooks or cbl_1._forward_hooks or cbl_1._forward_pre_hooks):
+        return None
+    B, _, H, W = x.shape
+    if not (ops.SPLIT_BF16 and ops.stem_p3_takes(B, H, W, cbl_1.conv.out_channels, (1, 1, 1, 1))):
+        return None
+    w0, scale0, shift0 = cbl_0._prepared(cbl_0.conv, cbl_0.bn)
+    w1, scale1, shift1 = cbl_1._prepared(cbl_1.conv, cbl_1.bn)
+    cache = cbl_0.__dict__.setdefault('_prep_cache', {})
+    hit = cache.get('stem_p3')
+    if hit is None or hit[0] is not w0:
+        hit = (w0, ops.stem_p3_weights(w0))
+        cache['stem_p3'] = hit
+    return ops.conv_stem_p3(x, hit[1], scale0, shift0, (1, 1, 1, 1), prepare_b3(cbl_1, 'b3', w1), scale1, shift1)
+
+
 class DarkBlock(nn.Module):
     '''
     Residual block in Darknet53: x + cbl_1(cbl_0(x)); the add rides in cbl_1's epilogue

@@ -514,6 +514,69 @@ def conv2d_stem(x, w_ohwi, scale, shift, stride, pad, act):
     return out
 
 
+# MYDET_STEM_P3=0 keeps Darknet-53's stem and its first stride-2 conv as two launches (A/B measurements).  The fused launch measured
+# faster at every size tried (profiles/stem_p3_fused.md: batch 32 at 640^2 1 242 -> 1 044 us, at 512^2 813 -> 685 us; batch 1 at
+# 512^2, 512 workgroups, 47 -> 29 us), so there is no size bound beyond conv_p3's own
+STEM_P3 = os.environ.get('MYDET_STEM_P3', '1') != '0'
+
+
+def stem_p3_plan(B, Hs, Ws, Cout):
+    """(workgroups, dynamic LDS bytes per workgroup) of mydet_conv_stem_p3_f32 (csrc/conv_stem_p3.hip) for a stem map of Hs x Ws: 8 x 16
+    output tiles x 64 channels; one 16-channel slab of the 17 x 36-position stride-2 patch in three bf16 planes + the 19 x 36 x 3
+    float32 image patch."""
+    Ho, Wo = (Hs - 1) // 2 + 1, (Ws - 1) // 2 + 1
+    return B * -(-Ho // 8) * -(-Wo // 16) * (Cout // 64), 3 * 17 * 36 * 32 + 3 * 19 * 36 * 4
+
+
+def stem_p3_takes(B, H, W, Cout, pad0):
+    """True when Darknet-53's first two layers take the fused launch: the second layer would run conv_p3's 8 x 16 tiles anyway (no strip
+    tiles); measured faster than the two launches at every such size tried (profiles/stem_p3_fused.md)."""
+    Hs, Ws = conv_out_size(H, 3, 1, pad0[0], pad0[2]), conv_out_size(W, 3, 1, pad0[1], pad0[3])
+    Ho, Wo = (Hs - 1) // 2 + 1, (Ws - 1) // 2 + 1
+    if not STEM_P3 or Cout % 64 or not p3_takes(B, Ho, Wo, 32, Cout, 3, 2, (1, 1, 1, 1)):
+        return False
+    return not (P3_STRIP and Wo % 16 in (4, 8))
+
+
+def stem_p3_weights(w_ohwi):
+    """The stem operand of `conv_stem_p3`: the OHWI stem weight [32, 3, 3, 3] with every row's K = 27 zero-padded to 32, as
+    `split_bf16` planes."""
+    w = torch.zeros((w_ohwi.shape[0], 1, 1, 32), dtype=torch.float32, device=w_ohwi.device)
+    w[:, 0, 0, :27] = w_ohwi.reshape(w_ohwi.shape[0], 27).float()
+    return split_bf16(w)
+
+
+def conv_stem_p3(x, w0_planes, scale0, shift0, pad0, w1_planes, scale1, shift1, act0=ACT_LEAKY, act1=ACT_LEAKY, out=None, out_ld=None):
+    """y = act1(BN1(conv3x3_s2_pad1(act0(BN0(conv3x3_s1(image)))))) in one launch (csrc/conv_stem_p3.hip, include/mydet.h:
+    mydet_conv_stem_p3_f32): the 32-channel stem map is never written.  x [B,3,H,W] in any strides; w0_planes =
+    stem_p3_weights(stem OHWI weight), w1_planes = split_bf16 of the second layer's [Cout,3,3,32] weight; pad0 = the stem's (top,
+    left, bottom, right).  Returns None when the kernel does not cover the arguments: the caller then uses conv2d_stem + conv2d."""
+    require_gpu(x, 'conv_stem_p3')
+    assert x.dtype == torch.float32 and x.shape[1] == 3
+    B, _, H, W = x.shape
+    Cout = int(shift1.shape[0])
+    Hs, Ws = conv_out_size(H, 3, 1, pad0[0], pad0[2]), conv_out_size(W, 3, 1, pad0[1], pad0[3])
+    Ho, Wo = (Hs - 1) // 2 + 1, (Ws - 1) // 2 + 1
+    if out is None:
+        out, ldy = empty_nhwc(B, Cout, Ho, Wo, x.device, out_ld)
+    else:
+        ldy = nhwc_ld(out)
+        assert ldy is not None and out.shape == (B, Cout, Ho, Wo)
+    sb, sc, sh, sw = x.stride()
+    t0 = TIMER.start() if TIMER else None
+    code = _lib.lib().mydet_conv_stem_p3_f32(_ptr(x), sb, sc, sh, sw, _ptr(w0_planes), _ptr(scale0), _ptr(shift0), act0, _ptr(w1_planes),
+                                             _ptr(scale1), _ptr(shift1), act1, _ptr(out), ldy, B, H, W, 32, Cout, 1, pad0[0], pad0[1],
+                                             Hs, Ws, 2, _stream())
+    if code == -2:
+        return None
+    if t0:      # algorithmic FLOPs and bytes of the two reference layers: stem (image in, map out) + stride-2 conv (map in, out, weights)
+        b_img, b_map, b_out = 4.0 * B * 3 * H * W, 4.0 * B * 32 * Hs * Ws, 4.0 * B * Cout * Ho * Wo
+        TIMER.stop('conv_stem_p3', t0, 2.0 * B * (Hs * Ws * 32 * 27 + Ho * Wo * Cout * 9 * 32), b_img + 2 * b_map + b_out + 4.0 * 9 * 32 * Cout,
+                   fused=b_img + b_out + 4.0 * 9 * 32 * Cout)
+    _lib.check(code, 'mydet_conv_stem_p3_f32')
+    return out
+
+
 def se_slices(n_pixels):
     """Number of pixel slices the SE average is split over (deterministic two-stage sum)."""
     return max(1, min(128, n_pixels // 16))
