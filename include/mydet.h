@@ -382,6 +382,29 @@ int mydet_postprocess_records_rot_f32(const float *bbox, const int64_t *class_id
                                       int B, int64_t N, float conf_thres, double nms_thres,
                                       int32_t *records, void *scratch, void *stream);
 
+/* Rotated-IoU NMS for 'cxcywhd' boxes (opt-in; the two entry points above are what the reference's inference path runs).
+ * Arguments, argument checks, error codes, outputs and the record (MYDET_REC_ROT_WORDS words) are those of
+ * mydet_postprocess_rot_f32 / mydet_postprocess_records_rot_f32; filter, top-k, class-aware greedy order and the tie order
+ * (score descending, then candidate index ascending, as everywhere in this file) are unchanged.  Only the pair test differs:
+ *   - the IoU of two boxes is the EXACT area of intersection of the two rotated rectangles over their union, in float32.
+ *     The rectangles have the corners of the reference's xywha2vertex (utils/bbox_ops.py:137-172: angle clockwise in image
+ *     coordinates, radians = deg * pi / 180 in float32, on deg reduced modulo 90 exactly).  The reference's iou_rle (utils/bbox_ops.py:52-100) counts the
+ *     pixels of the rasterised rectangles instead; the exact area is a documented deviation (within 7.2e-4 of the
+ *     reference's own 512^2 mask IoU on tests/golden/rot_iou.npz).
+ *   - a box is suppressed when (double)IoU >= nms_thres -- `>=`, as nms_rotbb tests it (utils/bbox_ops.py:290), where
+ *     the axis-aligned entry points use torchvision's `>`.  A pair of two zero-area boxes has no IoU (0/0) and is not
+ *     suppressed.
+ * mydet_rotated_iou_f32: the same IoU for every pair of two sets of rows (cx, cy, w, h, deg): a [Na,5], b [Nb,5] ->
+ *   out [Na,Nb] (the exact-area counterpart of iou_rle).  Na or Nb == 0 is a no-op. */
+int mydet_rotated_iou_f32(const float *a, int64_t Na, const float *b, int64_t Nb, float *out, void *stream);
+int mydet_postprocess_rotnms_f32(const float *bbox, const int64_t *class_idx, const float *score,
+                                 int B, int64_t N, float conf_thres, double nms_thres, int topk,
+                                 int32_t *count, float *out_bbox, int64_t *out_class, float *out_score,
+                                 int32_t *out_index, void *scratch, void *stream);
+int mydet_postprocess_records_rotnms_f32(const float *bbox, const int64_t *class_idx, const float *score,
+                                         int B, int64_t N, float conf_thres, double nms_thres,
+                                         int32_t *records, void *scratch, void *stream);
+
 /* Winograd F(4x4,3x3) form of the same 3x3 stride-1 pad-1 conv + BN + act (+ residual) as mydet_conv2d_wino_f32
  * (4x fewer multiplies than the direct form; used for the deep layers with chip-filling grids).  `u` = the
  * transform-domain weights made by mydet_wino4_weights_f32 from the OHWI weight (mydet_wino4_weights_floats(Cout, Cin)

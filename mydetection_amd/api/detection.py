@@ -59,6 +59,9 @@ class Detector():
     def _init_postprocess(self, cfg):
         self.conf_thres = cfg['test.default_conf_thres']
         self.nms_thres = cfg['test.nms_thres']
+        # opt-in: NMS on the rotated rectangles of a 'cxcywhd' model (no shipped config sets the key: the default is the
+        # axis-aligned NMS the reference runs); the `rotated_nms` keyword of the predict methods overrides it per call
+        self.rotated_nms = bool(cfg.get('test.rotated_nms', False))
 
     def evaluation_predict(self, eval_info: dict, **kwargs):
         '''
@@ -122,7 +125,7 @@ class Detector():
     def _predict_pil(self, pil_img, **kwargs):
         '''
         Args:
-            pil_img, preprocessing (str), input_size (int), conf_thres (float), nms_thres (float)
+            pil_img, preprocessing (str), input_size (int), conf_thres (float), nms_thres (float), rotated_nms (bool)
         '''
         assert isinstance(pil_img, PIL.Image.Image), 'input must be a PIL.Image'
         return self.predict_batch([pil_img], **kwargs)[0]
@@ -178,8 +181,11 @@ class Detector():
         boxes already in the coordinates of the original images."""
         conf_thres = kwargs.get('conf_thres', self.conf_thres)
         nms_thres = kwargs.get('nms_thres', self.nms_thres)
+        rotated_nms = bool(kwargs.get('rotated_nms', self.rotated_nms))
+        if rotated_nms and self.model.bb_format != 'cxcywhd':
+            raise ValueError(f"rotated_nms needs a 'cxcywhd' model; this one predicts {self.model.bb_format!r}")
         for idxs, x, pads, hws in self.preprocess_batch(pil_imgs, **kwargs):
-            rec = self._records(x, conf_thres, nms_thres)
+            rec = self._records(x, conf_thres, nms_thres, rotated_nms)
             if any(p is not None for p in pads):
                 ops.records_to_original_(rec, pads)
             rec['img_hw'] = hws
@@ -191,18 +197,19 @@ class Detector():
         """Forget every captured hipGraph (after editing parameters in place, or to release the graphs' activation pools)."""
         self._graphs.clear()
 
-    def _records(self, x, conf_thres, nms_thres):
+    def _records(self, x, conf_thres, nms_thres, rotated_nms=False):
         """Detection records of one network input batch (boxes in network-input coordinates): a hipGraph replay when
-        this (shape, thresholds) has been seen before, the eager launch sequence otherwise."""
+        this (shape, thresholds, kind of NMS) has been seen before, the eager launch sequence otherwise."""
         from ..utils.structures import batched_post_process
-        key = (tuple(x.shape), float(conf_thres), float(nms_thres))
+        key = (tuple(x.shape), float(conf_thres), float(nms_thres), bool(rotated_nms))
         if self.use_graph:
             cache = self._graphs
             g = cache.lookup(key)                                    # LRU; drops a graph captured before a weight change
             if g is None and cache.should_capture(key):
                 from ..graph import GraphedPath
                 # each graph owns its activations; the lane count is the detector's (below), not a timing decision
-                g = cache.insert(key, GraphedPath(self.model, x, conf_thres, nms_thres, lanes=self.batch_lanes(x.shape[0])))
+                g = cache.insert(key, GraphedPath(self.model, x, conf_thres, nms_thres, lanes=self.batch_lanes(x.shape[0]),
+                                                      rotated_nms=rotated_nms))
             if g is not None:
                 return {k: v.clone() for k, v in g(x).items()}       # the graph's own record buffers are overwritten by the next replay
             cache.note_eager(key)
@@ -210,14 +217,14 @@ class Detector():
             lanes = self.batch_lanes(x.shape[0])
             if lanes == 1:
                 bb, ci, sc = self.model.forward_candidates(x)
-                return batched_post_process(bb, ci, sc, conf_thres, nms_thres)
+                return batched_post_process(bb, ci, sc, conf_thres, nms_thres, rotated_nms=rotated_nms)
             # the eager form of a laned graph: the same parts of the batch, one after the other -- bit-identical to the replay
             words = ops.record_words(getattr(self.model, 'bbox_param', 4))
             records = torch.empty((x.shape[0], words), dtype=torch.int32, device=x.device)
             lo = 0
             for part in x.tensor_split(lanes):
                 bb, ci, sc = self.model.forward_candidates(part)
-                batched_post_process(bb, ci, sc, conf_thres, nms_thres, records=records[lo:lo + part.shape[0]])
+                batched_post_process(bb, ci, sc, conf_thres, nms_thres, records=records[lo:lo + part.shape[0]], rotated_nms=rotated_nms)
                 lo += part.shape[0]
             return ops.record_views(records)
 

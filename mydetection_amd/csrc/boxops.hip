@@ -3,7 +3,10 @@
 //   bboxes_iou          utils/bbox_ops.py:6-49   (chainercv form: en = prod(tl < br))
 //   bboxes_to_original_ utils/structures.py:175-189
 //   cxcywh_to_x1y1x2y2  utils/bbox_ops.py:309-316
+//   iou_rle             utils/bbox_ops.py:52-100  (rotated boxes; exact intersection area instead of the reference's
+//                                                  rasterised masks, rot_iou.h)
 #include "common.h"
+#include "rot_iou.h"
 
 namespace {
 
@@ -31,6 +34,19 @@ __global__ __launch_bounds__(256) void iou_kernel(const float *a, int Na, const 
         const float en = ((tlx < brx) ? 1.0f : 0.0f) * ((tly < bry) ? 1.0f : 0.0f);
         const float area_i = ((brx - tlx) * (bry - tly)) * en;
         out[i] = area_i / (area_a + area_b - area_i);
+    }
+}
+
+// Pairwise IoU [Na, Nb] of two sets of rotated boxes, rows (cx, cy, w, h, deg): one pair per thread, consecutive threads
+// walk a row of the output (coalesced stores; the `a` row is a broadcast load).  Row a is the frame of rot_iou.
+__global__ __launch_bounds__(256) void rotated_iou_kernel(const float *a, int64_t Na, const float *b, int64_t Nb, float *out) {
+    const int64_t total = Na * Nb;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t ia = i / Nb, ib = i - ia * Nb;
+        const float *pa = a + ia * 5, *pb = b + ib * 5;
+        const rotiou::Box ba = rotiou::make_box(pa[0], pa[1], pa[2], pa[3], pa[4]);
+        const rotiou::Box bq = rotiou::make_box(pb[0], pb[1], pb[2], pb[3], pb[4]);
+        out[i] = rotiou::rot_iou(ba, bq);
     }
 }
 
@@ -144,6 +160,17 @@ extern "C" int mydet_bboxes_iou_f32(const float *a, int Na, const float *b, int 
     int64_t blocks = ((int64_t)Na * Nb + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL(iou_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, Na, b, Nb, xyxy, iou);
+    return mydet_launch_status();
+}
+
+extern "C" int mydet_rotated_iou_f32(const float *a, int64_t Na, const float *b, int64_t Nb, float *out, void *stream) {
+    if (Na < 0 || Nb < 0) return MYDET_E_BADARG;
+    if (Na == 0 || Nb == 0) return 0;
+    if (!a || !b || !out) return MYDET_E_BADARG;
+    if (Na > (int64_t)0x7fffffffffffffffll / Nb) return MYDET_E_UNSUPP;
+    int64_t blocks = (Na * Nb + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(rotated_iou_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, Na, b, Nb, out);
     return mydet_launch_status();
 }
 

@@ -24,7 +24,12 @@
 // The kernel is a template on the candidate row width BW: 4 (cxcywh) or 5 (cxcywhd, rotated boxes).  For BW = 5 every step
 // above reads columns 0-3 only -- the reference's NMS ignores the angle for 'cxcywhd' (utils/structures.py:137-149) -- and
 // the angle is copied with its box into the output rows (5 wide) or into the ANGLE plane of a rotated record.
+// The second template parameter ROT (BW = 5 only; opt-in, the mydet_postprocess_*rotnms_f32 entry points) replaces step 4's
+// pair test alone: the IoU is the exact area of intersection of the two ROTATED rectangles (rot_iou.h) and a pair is
+// suppressed when (double)IoU >= thr -- the `>=` of the reference's nms_rotbb (utils/bbox_ops.py:290).  Every other step
+// is shared, so the order, the tie rule and the record layout are those of the <5, false> instance.
 #include "common.h"
+#include "rot_iou.h"
 
 namespace {
 
@@ -59,11 +64,14 @@ __device__ __forceinline__ unsigned sortable(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-template <int BW>
+template <int BW, bool ROT>
 __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
+    static_assert(!ROT || BW == 5, "the rotated IoU needs the angle column");
     __shared__ unsigned long long s_key[KMAX];
     __shared__ unsigned long long s_mask[KMAX * 8];
+    // ROT: the seven planes of rotiou::Box -- s_x1, s_y1 = centre, s_x2, s_y2 = hori, s_vx, s_vy = verti, s_area
     __shared__ float s_x1[KMAX], s_y1[KMAX], s_x2[KMAX], s_y2[KMAX], s_area[KMAX];
+    __shared__ float s_vx[ROT ? KMAX : 1], s_vy[ROT ? KMAX : 1];
     __shared__ int s_cls[KMAX], s_segend[KMAX];
     __shared__ int s_cnt[3];
     __shared__ unsigned long long s_removed[8];
@@ -262,17 +270,24 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
     if (tid < nsel) {
         const unsigned long long k = s_key[tid];
         const unsigned idx = (unsigned)(k & ((1ull << IDX_BITS) - 1));
-        f32x4 v;
-        if constexpr (BW == 4) {
-            v = *reinterpret_cast<const f32x4 *>(bb + (int64_t)idx * 4);
-        } else {                                        // 20-byte rows: columns 0-3, the angle is not used here
+        if constexpr (ROT) {
             const float *r = bb + (int64_t)idx * BW;
-            v = f32x4{r[0], r[1], r[2], r[3]};
+            const rotiou::Box q = rotiou::make_box(r[0], r[1], r[2], r[3], r[4]);
+            s_x1[tid] = q.cx; s_y1[tid] = q.cy; s_x2[tid] = q.hx; s_y2[tid] = q.hy; s_vx[tid] = q.vx; s_vy[tid] = q.vy;
+            s_area[tid] = q.area;
+        } else {
+            f32x4 v;
+            if constexpr (BW == 4) {
+                v = *reinterpret_cast<const f32x4 *>(bb + (int64_t)idx * 4);
+            } else {                                    // 20-byte rows: columns 0-3, the angle is not used here
+                const float *r = bb + (int64_t)idx * BW;
+                v = f32x4{r[0], r[1], r[2], r[3]};
+            }
+            const float hw = v[2] / 2.0f, hh = v[3] / 2.0f;
+            const float x1 = v[0] - hw, y1 = v[1] - hh, x2 = v[0] + hw, y2 = v[1] + hh;
+            s_x1[tid] = x1; s_y1[tid] = y1; s_x2[tid] = x2; s_y2[tid] = y2;
+            s_area[tid] = (x2 - x1) * (y2 - y1);
         }
-        const float hw = v[2] / 2.0f, hh = v[3] / 2.0f;
-        const float x1 = v[0] - hw, y1 = v[1] - hh, x2 = v[0] + hw, y2 = v[1] + hh;
-        s_x1[tid] = x1; s_y1[tid] = y1; s_x2[tid] = x2; s_y2[tid] = y2;
-        s_area[tid] = (x2 - x1) * (y2 - y1);
         s_cls[tid] = (int)(k >> CLS_SHIFT);
     }
     __syncthreads();
@@ -298,7 +313,13 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
             for (int w = (i + 1) >> 6; w * 64 < e; ++w) {
                 const int j = w * 64 + lane;
                 bool sup = false;
-                if (j > i && j < e) {
+                if constexpr (ROT) {
+                    if (j > i && j < e) {
+                        const rotiou::Box bi{ix1, iy1, ix2, iy2, s_vx[i], s_vy[i], ia};
+                        const rotiou::Box bj{s_x1[j], s_y1[j], s_x2[j], s_y2[j], s_vx[j], s_vy[j], s_area[j]};
+                        sup = (double)rotiou::rot_iou(bi, bj) >= p.nms;          // NaN (both areas 0): not suppressed
+                    }
+                } else if (j > i && j < e) {
                     const float xx1 = fmaxf(ix1, s_x1[j]), yy1 = fmaxf(iy1, s_y1[j]);
                     const float xx2 = fminf(ix2, s_x2[j]), yy2 = fminf(iy2, s_y2[j]);
                     const float ww = fmaxf(0.0f, xx2 - xx1), hh = fmaxf(0.0f, yy2 - yy1);
@@ -464,7 +485,7 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
 
 }  // namespace
 
-template <int BW>
+template <int BW, bool ROT = false>
 static int launch_postprocess(PPArgs &p, const float *bbox, const int64_t *class_idx, const float *score, int B, int64_t N,
                               float conf_thres, double nms_thres, int topk, void *scratch, void *stream) {
     if (B <= 0 || N < 0 || topk <= 0 || topk > KMAX) return MYDET_E_BADARG;
@@ -474,7 +495,7 @@ static int launch_postprocess(PPArgs &p, const float *bbox, const int64_t *class
     if (((uintptr_t)bbox & 15) || ((uintptr_t)p.obox & 15) || ((uintptr_t)scratch & 7) || ((uintptr_t)p.ocls & 7)) return MYDET_E_BADARG;
     p.bbox = bbox; p.cidx = class_idx; p.score = score; p.N = N; p.conf = conf_thres; p.nms = nms_thres;
     p.topk = topk; p.scratch = (unsigned long long *)scratch;
-    hipLaunchKernelGGL(postprocess_kernel<BW>, dim3(B), dim3(NT), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((postprocess_kernel<BW, ROT>), dim3(B), dim3(NT), 0, (hipStream_t)stream, p);
     return mydet_launch_status();
 }
 
@@ -533,4 +554,34 @@ extern "C" int mydet_postprocess_records_rot_f32(const float *bbox, const int64_
     p.oscore_st = MYDET_REC_ROT_WORDS; p.ocls_st = MYDET_REC_ROT_WORDS / 2; p.oidx_st = MYDET_REC_ROT_WORDS;
     p.oang_st = MYDET_REC_ROT_WORDS;
     return launch_postprocess<5>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream);
+}
+
+// The rotated-IoU forms of the two entry points above: arguments, checks and outputs are theirs, the pair test of the NMS
+// is rotiou::rot_iou with `>=` (include/mydet.h).
+extern "C" int mydet_postprocess_rotnms_f32(const float *bbox, const int64_t *class_idx, const float *score, int B,
+                                            int64_t N, float conf_thres, double nms_thres, int topk, int32_t *count,
+                                            float *out_bbox, int64_t *out_class, float *out_score, int32_t *out_index,
+                                            void *scratch, void *stream) {
+    PPArgs p;
+    p.count = count; p.obox = out_bbox; p.ocls = out_class; p.oscore = out_score; p.oidx = out_index;
+    p.oang = nullptr; p.oang_st = 0;
+    p.count_pad = 0; p.count_st = 1; p.obox_st = (int64_t)topk * 5; p.ocls_st = topk; p.oscore_st = topk; p.oidx_st = topk;
+    return launch_postprocess<5, true>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, topk, scratch, stream);
+}
+
+extern "C" int mydet_postprocess_records_rotnms_f32(const float *bbox, const int64_t *class_idx, const float *score, int B,
+                                                    int64_t N, float conf_thres, double nms_thres, int32_t *records,
+                                                    void *scratch, void *stream) {
+    if (!records || ((uintptr_t)records & 15)) return MYDET_E_BADARG;
+    PPArgs p;
+    p.count = records + MYDET_REC_COUNT;
+    p.obox = reinterpret_cast<float *>(records + MYDET_REC_BBOX);
+    p.oscore = reinterpret_cast<float *>(records + MYDET_REC_SCORE);
+    p.ocls = reinterpret_cast<int64_t *>(records + MYDET_REC_CLASS);
+    p.oidx = records + MYDET_REC_INDEX;
+    p.oang = reinterpret_cast<float *>(records + MYDET_REC_ANGLE);
+    p.count_pad = MYDET_REC_BBOX - 1; p.count_st = MYDET_REC_ROT_WORDS; p.obox_st = MYDET_REC_ROT_WORDS;
+    p.oscore_st = MYDET_REC_ROT_WORDS; p.ocls_st = MYDET_REC_ROT_WORDS / 2; p.oidx_st = MYDET_REC_ROT_WORDS;
+    p.oang_st = MYDET_REC_ROT_WORDS;
+    return launch_postprocess<5, true>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream);
 }

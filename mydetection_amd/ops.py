@@ -1142,15 +1142,26 @@ def record_boxes(rec, b, k):
     return torch.cat([rec['bbox'][b, :k], rec['angle'][b, :k, None]], dim=1)
 
 
-def postprocess(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, records=None):
+def _rot_entry(width, rotated_nms, plain, rot, rotnms):
+    """Entry point for boxes of `width` floats; `rotated_nms` (cxcywhd only) selects the rotated-IoU NMS."""
+    if rotated_nms and width != 5:
+        raise ValueError(f"rotated_nms needs 'cxcywhd' boxes (5 floats per row), not rows of {width}")
+    return plain if width == 4 else (rotnms if rotated_nms else rot)
+
+
+def postprocess(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, records=None, rotated_nms=False):
     """Batched filter/top-k/class-aware NMS.  bbox [B,N,4], class_idx [B,N] i64, score [B,N].  bbox [B,N,5]
     (cxcywhd) takes the rotated kernel: the same decisions on columns 0-3, rotated records ('angle' added).
+    rotated_nms=True (cxcywhd only, ValueError otherwise): the NMS compares the rotated rectangles -- exact intersection
+    area, suppress at IoU >= nms_thres (include/mydet.h: mydet_postprocess_records_rotnms_f32); same records.
 
     Returns dict of device tensors: count [B] i32, bbox [B,512,4], class_idx [B,512] i64, score [B,512],
     index [B,512] i32 -- all views of 'records' (int32 [B, REC_WORDS]), which the kernel writes directly in the
     wire layout of the all-gather (parallel.gather_detections).  Class ids must lie in [0, 4096): an image whose
     selected candidates break that gets count = -1 (`check_counts` raises on it) instead of aliased classes.
     """
+    fn = _rot_entry(bbox.shape[-1], rotated_nms, 'mydet_postprocess_records_f32', 'mydet_postprocess_records_rot_f32',
+                    'mydet_postprocess_records_rotnms_f32')
     require_gpu(bbox, 'postprocess')
     assert bbox.dtype == torch.float32 and score.dtype == torch.float32 and class_idx.dtype == torch.int64
     assert topk == TOPK
@@ -1162,7 +1173,6 @@ def postprocess(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, record
         records = torch.empty((B, words), dtype=torch.int32, device=dev)
     assert records.dtype == torch.int32 and tuple(records.shape) == (B, words) and records.is_contiguous()
     scratch = torch.empty((B, max(N, 1)), dtype=torch.int64, device=dev)
-    fn = 'mydet_postprocess_records_f32' if words == _lib.REC_WORDS else 'mydet_postprocess_records_rot_f32'
     t0 = TIMER.start() if TIMER else None
     code = getattr(_lib.lib(), fn)(_ptr(bbox), _ptr(class_idx), _ptr(score), B, N, float(conf_thres), float(nms_thres),
                                    _ptr(records), _ptr(scratch), _stream())
@@ -1172,9 +1182,11 @@ def postprocess(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, record
     return record_views(records)
 
 
-def postprocess_dense(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK):
+def postprocess_dense(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, rotated_nms=False):
     """The same filter/top-k/NMS into dense per-image arrays (mydet_postprocess_f32, or mydet_postprocess_rot_f32 for
-    bbox [B,N,5]): count [B] i32, bbox [B,topk,4 or 5], class_idx [B,topk] i64, score [B,topk], index [B,topk] i32."""
+    bbox [B,N,5], mydet_postprocess_rotnms_f32 with rotated_nms): count [B] i32, bbox [B,topk,4 or 5], class_idx [B,topk] i64,
+    score [B,topk], index [B,topk] i32."""
+    fn = _rot_entry(bbox.shape[-1], rotated_nms, 'mydet_postprocess_f32', 'mydet_postprocess_rot_f32', 'mydet_postprocess_rotnms_f32')
     require_gpu(bbox, 'postprocess_dense')
     assert bbox.dtype == torch.float32 and score.dtype == torch.float32 and class_idx.dtype == torch.int64
     bbox, class_idx, score = bbox.contiguous(), class_idx.contiguous(), score.contiguous()
@@ -1188,7 +1200,6 @@ def postprocess_dense(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK):
            'score': torch.empty((B, topk), dtype=torch.float32, device=dev),
            'index': torch.empty((B, topk), dtype=torch.int32, device=dev)}
     scratch = torch.empty((B, max(N, 1)), dtype=torch.int64, device=dev)
-    fn = 'mydet_postprocess_f32' if width == 4 else 'mydet_postprocess_rot_f32'
     code = getattr(_lib.lib(), fn)(_ptr(bbox), _ptr(class_idx), _ptr(score), B, N, float(conf_thres), float(nms_thres),
                                    int(topk), _ptr(out['count']), _ptr(out['bbox']), _ptr(out['class_idx']),
                                    _ptr(out['score']), _ptr(out['index']), _ptr(scratch), _stream())
@@ -1213,6 +1224,19 @@ def bboxes_iou(a, b, xyxy=False):
     code = _lib.lib().mydet_bboxes_iou_f32(_ptr(a), a.shape[0], _ptr(b), b.shape[0], 1 if xyxy else 0, _ptr(out),
                                            _stream())
     _lib.check(code, 'mydet_bboxes_iou_f32')
+    return out
+
+
+def rotated_iou(a, b):
+    """Pairwise IoU [Na, Nb] of rotated boxes, rows (cx, cy, w, h, deg): exact intersection area
+    (include/mydet.h: mydet_rotated_iou_f32)."""
+    require_gpu(a, 'rotated_iou')
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != 5 or b.shape[1] != 5:
+        raise ValueError(f'rotated_iou: [N,5] and [M,5] boxes expected, got {tuple(a.shape)} and {tuple(b.shape)}')
+    a, b = a.contiguous().float(), b.to(a.device).contiguous().float()
+    out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
+    code = _lib.lib().mydet_rotated_iou_f32(_ptr(a), a.shape[0], _ptr(b), b.shape[0], _ptr(out), _stream())
+    _lib.check(code, 'mydet_rotated_iou_f32')
     return out
 
 

@@ -6,6 +6,9 @@ candidates instead of copying all N candidates to the host and looping over clas
 torchvision.ops.nms.  Results (order included) are those of the reference: class id
 ascending, score descending inside a class.  Rotated boxes ('cxcywhd', rows (cx, cy, w, h, deg)) take the same kernel
 on columns 0-3 -- the reference's NMS ignores the angle too (utils/structures.py:137-149) -- with the angle carried along.
+`rotated_nms=True` / `rotated=True` (opt-in, 'cxcywhd' only) runs the NMS on the rotated rectangles instead: exact
+intersection area, suppress at IoU >= nms_thres -- what the reference's commented-out nms_rotbb branch
+(utils/structures.py:144-148) would do, with an exact area in place of its rasterised masks.
 """
 import torch
 
@@ -94,31 +97,35 @@ class ImageObjects():
         return ImageObjects(ops.record_boxes(rec, b, k), rec['class_idx'][b, :k], None, rec['score'][b, :k],
                             self._bb_format, img_hw=self.img_hw)
 
-    def post_process(self, conf_thres, nms_thres):
+    def post_process(self, conf_thres, nms_thres, rotated_nms=False):
         '''
         Confidence threshold + top-512 + class-aware NMS (reference: utils/structures.py:92-106),
         one HIP launch.  Returns a new ImageObjects whose tensors stay on the device.
+        rotated_nms: compare the rotated rectangles ('cxcywhd' only; ValueError otherwise).
         '''
         assert self.masks is None
         assert self.scores is not None
+        _check_rotated(rotated_nms, self._bb_format)
         if self._bb_format not in _BOX_WIDTH:
             raise NotImplementedError()
         bb, cats, sc = self._device_fields()
-        rec = ops.postprocess(bb[None], cats[None], sc[None], conf_thres, nms_thres, TOPK)
+        rec = ops.postprocess(bb[None], cats[None], sc[None], conf_thres, nms_thres, TOPK, rotated_nms=rotated_nms)
         return self._from_records(rec)
 
-    def nms(self, nms_thres=0.45):
-        return ImageObjects.non_max_suppression(self, nms_thres)
+    def nms(self, nms_thres=0.45, rotated=False):
+        return ImageObjects.non_max_suppression(self, nms_thres, rotated=rotated)
 
     @staticmethod
-    def non_max_suppression(dts, nms_thres: float):
+    def non_max_suppression(dts, nms_thres: float, rotated=False):
         '''
         Class-aware NMS (reference: utils/structures.py:111-173).  At most 512 boxes, as in the
         reference call chain (post_process caps at 512 before calling nms).
+        rotated: compare the rotated rectangles ('cxcywhd' only; ValueError otherwise).
         '''
         assert isinstance(dts, ImageObjects)
         assert dts.masks is None, 'nms with masks is not currently supported'
         assert dts.scores is not None
+        _check_rotated(rotated, dts._bb_format)
         if dts.bboxes.shape[0] == 0:
             return dts
         if dts._bb_format not in _BOX_WIDTH:
@@ -126,7 +133,7 @@ class ImageObjects():
         if len(dts) > TOPK:
             raise NotImplementedError(f'non_max_suppression handles at most {TOPK} boxes per image')
         bb, cats, sc = dts._device_fields()
-        rec = ops.postprocess(bb[None], cats[None], sc[None], float('-inf'), nms_thres, TOPK)
+        rec = ops.postprocess(bb[None], cats[None], sc[None], float('-inf'), nms_thres, TOPK, rotated_nms=rotated)
         return dts._from_records(rec)
 
     def bboxes_to_original_(self, pad_info):
@@ -190,6 +197,11 @@ class ImageObjects():
 
 
 _BOX_WIDTH = {'cxcywh': 4, 'cxcywhd': 5}
+
+
+def _check_rotated(rotated_nms, bb_format):
+    if rotated_nms and bb_format != 'cxcywhd':
+        raise ValueError(f"rotated NMS is defined for bb_format 'cxcywhd' only, not {bb_format!r}")
 
 
 def _json_rotated(bboxes, scores, cats, img_id, catIdx2id):
@@ -265,7 +277,7 @@ def batched_to_json(rec, img_ids, eval_type='x1y1wh', catIdx2id=None) -> list:
     return out
 
 
-def batched_post_process(bboxes, cats, scores, conf_thres, nms_thres, records=None):
+def batched_post_process(bboxes, cats, scores, conf_thres, nms_thres, records=None, rotated_nms=False):
     '''
     The batched form of `for d in dts: d.post_process(...)` (examples/train.py:229-232):
     bboxes [B,N,4], cats [B,N], scores [B,N] on the device -> fixed-size records
@@ -273,5 +285,6 @@ def batched_post_process(bboxes, cats, scores, conf_thres, nms_thres, records=No
     bboxes [B,N,5] (cxcywhd) take the rotated kernel: rotated records, 'angle' [B,512] added.
     records: optional int32 [B, REC_WORDS] buffer (REC_ROT_WORDS for rotated boxes) to write (rows of a larger batch's
     record buffer).
+    rotated_nms: the NMS compares the rotated rectangles (cxcywhd only; ValueError for [B,N,4]); same rotated records.
     '''
-    return ops.postprocess(bboxes, cats, scores, conf_thres, nms_thres, TOPK, records=records)
+    return ops.postprocess(bboxes, cats, scores, conf_thres, nms_thres, TOPK, records=records, rotated_nms=rotated_nms)
