@@ -581,6 +581,20 @@ int mydet_bboxes_to_original_f32(float *bbox, int64_t n, float ori_w, float ori_
 int mydet_preprocess_u8_f32(const unsigned char *img, int B, int H, int W, float *out, int Hp, int Wp, int norm,
                             const float *mean3, const float *std3, void *stream);
 
+/* Video frames -> network input in ONE launch: B uint8 frames [H][W][3] of one size (frame b at src + b*src_img_bytes,
+ * rows src_row_bytes apart, so a crop of a larger buffer is read in place) -> float32 [B,3,Hp,Wp].  Inside the oh x ow
+ * window at (top, left) the output is the Pillow-exact bilinear resize of the frame (mydet_resize_bilinear_u8: same
+ * DEVICE tables, NULL tables = that axis keeps its size) put through the arithmetic of mydet_preprocess_u8_f32;
+ * outside it, what that function gives for a zero pixel.  Bit-identical to the two calls it fuses; the uint8 image
+ * between them exists only in LDS.  ksx / ksy above MYDET_FRAMES_MAX_TAPS (a downscale beyond 8x), a window that does
+ * not fit Hp x Wp, and null or non-positive arguments are MYDET_E_BADARG.  mean3/std3 are HOST pointers to 3 floats. */
+#define MYDET_FRAMES_MAX_TAPS 17
+int mydet_frames_to_input_f32(const unsigned char *src, int B, int H, int W, int64_t src_img_bytes, int64_t src_row_bytes,
+                              float *out, int Hp, int Wp, int oh, int ow, int top, int left,
+                              const int32_t *bounds_x, const int32_t *kx, int ksx,
+                              const int32_t *bounds_y, const int32_t *ky, int ksy,
+                              int norm, const float *mean3, const float *std3, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,8 @@ SIGNATURES = {
     'mydet_detections_to_json_f64': [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_resize_bilinear_u8': [c_ptr, c_int, c_int, c_i64, c_ptr, c_int, c_int, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_ptr],
     'mydet_preprocess_u8_f32': [c_ptr, c_int, c_int, c_int, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
+    'mydet_frames_to_input_f32': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_cxcywh_to_x1y1x2y2_f32': [c_ptr, c_ptr, c_i64, c_int, c_ptr],
     'mydet_bboxes_to_original_f32': [c_ptr, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr],
 }
@@ -137,6 +139,7 @@ class LrTbLevel(ctypes.Structure):
 
 LR_TB_MAX_LEVELS = 8                # MYDET_LR_TB_MAX_LEVELS of include/mydet.h
 LR_TB_MAX_C = 128                   # MYDET_LR_TB_MAX_C
+FRAMES_MAX_TAPS = 17                # MYDET_FRAMES_MAX_TAPS: filter taps per axis mydet_frames_to_input_f32 takes
 
 _lib = None
 

@@ -239,6 +239,101 @@ class Detector():
             return 1
         return min(want, batch) if env.isdigit() else (want if batch % want == 0 else 1)
 
+    @staticmethod
+    def _frame_groups(frames):
+        """Frames as uint8 tensors grouped by size: (number of frames, [(indices, [tensors [n,H,W,3]])]).  Accepts a
+        torch.uint8 tensor or numpy.uint8 array of shape [B,H,W,3] or [H,W,3], on the host or the device, or a list of them;
+        anything else is a TypeError (type, dtype) or a ValueError (shape).  Touches no device."""
+        items = list(frames) if isinstance(frames, (list, tuple)) else [frames]
+        groups, n = {}, 0
+        for f in items:
+            if isinstance(f, np.ndarray):
+                if f.dtype != np.uint8:
+                    raise TypeError(f'predict_frames: uint8 frames expected, got a numpy array of dtype {f.dtype}')
+            elif isinstance(f, torch.Tensor):
+                if f.dtype != torch.uint8:
+                    raise TypeError(f'predict_frames: uint8 frames expected, got a tensor of dtype {f.dtype}')
+            else:
+                raise TypeError(f'predict_frames: a uint8 torch.Tensor or numpy.ndarray (or a list of them) expected, got {type(f).__name__}')
+            if f.ndim not in (3, 4) or f.shape[-1] != 3 or min(f.shape) < 1:
+                raise ValueError(f'predict_frames: frames of shape [B,H,W,3] or [H,W,3] expected, got {tuple(f.shape)}')
+            t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
+            t = t.unsqueeze(0) if t.dim() == 3 else t
+            idxs, parts = groups.setdefault((t.shape[1], t.shape[2]), ([], []))
+            idxs += range(n, n + t.shape[0])
+            parts.append(t)
+            n += t.shape[0]
+        return n, list(groups.values())
+
+    def _frame_records(self, frames, **kwargs):
+        """Detection records of uint8 frames: yields (indices, records) per network input size, like _records_by_size (same
+        batches in the same order, so the same bits).  Frames of one size on the host cross to the device in one copy,
+        frames on the device are read in place; one fused launch (ops.frames_to_input) per frame size builds their
+        network input."""
+        _, groups = self._frame_groups(frames)
+        pre_proc = kwargs.get('preprocessing', self.preprocess)
+        input_size = kwargs.get('input_size', self.input_size)
+        conf_thres = kwargs.get('conf_thres', self.conf_thres)
+        nms_thres = kwargs.get('nms_thres', self.nms_thres)
+        rotated_nms = bool(kwargs.get('rotated_nms', self.rotated_nms))
+        if rotated_nms and self.model.bb_format != 'cxcywhd':
+            raise ValueError(f"rotated_nms needs a 'cxcywhd' model; this one predicts {self.model.bb_format!r}")
+        dev = next(self.model.parameters()).device
+        by_input = {}
+        for idxs, parts in groups:
+            geo = self._geometry(parts[0].shape[1], parts[0].shape[2], pre_proc, input_size)
+            by_input.setdefault(geo[2], []).append((idxs, parts, geo))
+        for members in by_input.values():
+            idxs, xs, pads, hws = [], [], [], []
+            for part_idxs, parts, geo in members:
+                if len(parts) > 1:                                   # a list: gather it where it already is
+                    where = dev if all(t.device == dev for t in parts) else torch.device('cpu')
+                    parts = [torch.cat([t.to(where) for t in parts])]
+                u8 = parts[0].to(dev, non_blocking=True)
+                xs.append(ops.frames_to_input(u8, geo, self.model.input_format))
+                idxs += part_idxs
+                pads += [geo[3]] * len(part_idxs)
+                hws += [(u8.shape[1], u8.shape[2]) if geo[3] is not None else geo[2]] * len(part_idxs)
+            x = xs[0]
+            if len(xs) > 1:                                          # several frame sizes, one input size: one batch, in input order
+                order = sorted(range(len(idxs)), key=idxs.__getitem__)
+                x = torch.cat(xs)[torch.tensor(order, device=dev)]
+                idxs, pads, hws = [idxs[k] for k in order], [pads[k] for k in order], [hws[k] for k in order]
+            rec = self._records(x, conf_thres, nms_thres, rotated_nms)
+            if any(p is not None for p in pads):
+                ops.records_to_original_(rec, pads)
+            rec['img_hw'] = hws
+            yield idxs, rec
+
+    def predict_frames(self, frames, **kwargs):
+        """predict_batch for decoded video: `frames` is a torch.uint8 tensor or numpy.uint8 array [B,H,W,3] (or [H,W,3]) in
+        RGB order, on the host or already on the device, or a list of such frames (grouped by size).  No PIL object and no
+        per-frame copy or launch: resize, padding, /255 and normalisation of a whole group are one HIP launch that gives
+        the bits of preprocess_batch, so the detections equal predict_batch on PIL.Image.fromarray of the same frames.
+        Keyword arguments as in _predict_pil.  Returns a list of ImageObjects in original-frame coordinates."""
+        from ..parallel import records_to_objects
+        out = []
+        for idxs, rec in self._frame_records(frames, **kwargs):
+            out += [None] * (max(idxs) + 1 - len(out))
+            objs = records_to_objects(rec, bb_format=self.model.bb_format)
+            for j, o, hw in zip(idxs, objs, rec['img_hw']):
+                o.img_hw = hw
+                out[j] = o
+        return out
+
+    def frames_to_json(self, frames, img_ids, eval_type='x1y1wh', catIdx2id=None, **kwargs):
+        """COCO-style rows of uint8 frames (see predict_frames), image by image: the counterpart of _json_batch."""
+        from ..utils.structures import batched_to_json
+        out = [None] * len(img_ids)
+        for idxs, rec in self._frame_records(frames, **kwargs):
+            rows = batched_to_json(rec, [img_ids[j] for j in idxs], eval_type, catIdx2id)
+            counts = ops.check_counts(rec['count'].cpu().tolist())
+            o = 0
+            for j, k in zip(idxs, counts):
+                out[j] = rows[o:o + k]
+                o += k
+        return [d for per_img in out for d in per_img]
+
     def predict_batch(self, pil_imgs, **kwargs):
         """Batched form of detect_one (the reference loops image by image, api/detection.py:67-74): images that share a
         network input size go through ONE forward + ONE batched post-process.  Returns a list of ImageObjects in the

@@ -1267,7 +1267,6 @@ def bboxes_to_original_(bbox, pad_info):
 def resize_bilinear_u8(src_u8, out_hw, dst=None, top=0, left=0):
     """PIL-exact bilinear resize of one uint8 image [H,W,3] on the device (include/mydet.h: mydet_resize_bilinear_u8).
     dst: optional uint8 [Hd,Wd,3] to write into at (top, left) -- e.g. one image of a zero-padded batch buffer."""
-    from .utils.image_ops import resample_tables
     require_gpu(src_u8, 'resize_bilinear_u8')
     assert src_u8.dtype == torch.uint8 and src_u8.dim() == 3 and src_u8.shape[2] == 3 and src_u8.is_contiguous()
     H, W, _ = src_u8.shape
@@ -1276,21 +1275,7 @@ def resize_bilinear_u8(src_u8, out_hw, dst=None, top=0, left=0):
         dst = torch.empty((oh, ow, 3), dtype=torch.uint8, device=src_u8.device)
     assert dst.dtype == torch.uint8 and dst.dim() == 3 and dst.shape[2] == 3 and dst.stride(2) == 1 and dst.stride(1) == 3
     assert top + oh <= dst.shape[0] and left + ow <= dst.shape[1]
-    tabs = []
-    for n_in, n_out in ((W, ow), (H, oh)):
-        if n_in == n_out:
-            tabs.append((None, None, 0))
-        else:
-            key = (n_in, n_out, str(src_u8.device))
-            hit = _RESAMPLE_CACHE.get(key)
-            if hit is None:
-                b, k = resample_tables(n_in, n_out)
-                hit = (torch.from_numpy(b).to(src_u8.device), torch.from_numpy(k).to(src_u8.device), k.shape[1])
-                if len(_RESAMPLE_CACHE) > 256:
-                    _RESAMPLE_CACHE.clear()
-                _RESAMPLE_CACHE[key] = hit
-            tabs.append(hit)
-    (bx, kx, ksx), (by, ky, ksy) = tabs
+    (bx, kx, ksx), (by, ky, ksy) = _resample_tables_on(src_u8.device, H, W, oh, ow)
     dptr = ctypes.c_void_p(dst.data_ptr() + top * dst.stride(0) + left * 3)
     code = _lib.lib().mydet_resize_bilinear_u8(_ptr(src_u8), H, W, W * 3, dptr, oh, ow, dst.stride(0), _ptr(bx), _ptr(kx), ksx,
                                                _ptr(by), _ptr(ky), ksy, _stream())
@@ -1299,6 +1284,69 @@ def resize_bilinear_u8(src_u8, out_hw, dst=None, top=0, left=0):
 
 
 _RESAMPLE_CACHE = {}
+
+
+def _resample_tables_on(device, H, W, oh, ow):
+    """Device copies of Pillow's coefficient tables for (H, W) -> (oh, ow), cached per axis and device:
+    ((bounds_x, kx, ksx), (bounds_y, ky, ksy)); (None, None, 0) for an axis that keeps its size."""
+    from .utils.image_ops import resample_tables
+    tabs = []
+    for n_in, n_out in ((W, ow), (H, oh)):
+        if n_in == n_out:
+            tabs.append((None, None, 0))
+        else:
+            key = (n_in, n_out, str(device))
+            hit = _RESAMPLE_CACHE.get(key)
+            if hit is None:
+                b, k = resample_tables(n_in, n_out)
+                hit = (torch.from_numpy(b).to(device), torch.from_numpy(k).to(device), k.shape[1])
+                if len(_RESAMPLE_CACHE) > 256:
+                    _RESAMPLE_CACHE.clear()
+                _RESAMPLE_CACHE[key] = hit
+            tabs.append(hit)
+    return tabs
+
+
+def frames_to_input(frames_u8, geometry, input_format, out=None):
+    """uint8 frames [B,H,W,3] (or [H,W,3]) of one size on the device -> the float32 network input [B,3,Hp,Wp] in ONE launch
+    (include/mydet.h: mydet_frames_to_input_f32): PIL-exact resize, zero padding, /255 and normalisation, the bits
+    resize_bilinear_u8 + preprocess_u8 give.  geometry: Detector._geometry's tuple (resize target (h, w) or None,
+    (top, left), (Hp, Wp), pad_info).  The frames are read through their strides when pixels are packed (a crop of a
+    larger buffer is used in place); a downscale whose filter has more taps than the kernel stages
+    (_lib.FRAMES_MAX_TAPS) goes through the two existing kernels instead.  out: optional float32 [B,3,Hp,Wp] view."""
+    require_gpu(frames_u8, 'frames_to_input')
+    if frames_u8.dtype != torch.uint8:
+        raise TypeError(f'frames_to_input: uint8 frames expected, got {frames_u8.dtype}')
+    if frames_u8.dim() == 3:
+        frames_u8 = frames_u8.unsqueeze(0)
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or min(frames_u8.shape) < 1:
+        raise ValueError(f'frames_to_input: frames of shape [B,H,W,3] or [H,W,3] expected, got {tuple(frames_u8.shape)}')
+    if input_format not in ('RGB_1', 'RGB_1_norm'):
+        raise NotImplementedError()
+    B, H, W, _ = frames_u8.shape
+    target, (top, left), (Hp, Wp), _ = geometry
+    oh, ow = (int(target[0]), int(target[1])) if target is not None else (H, W)
+    if min(oh, ow) < 1 or top < 0 or left < 0 or top + oh > Hp or left + ow > Wp:
+        raise ValueError(f'frames_to_input: a {oh}x{ow} window at ({top}, {left}) does not fit the {Hp}x{Wp} input')
+    if frames_u8.stride(3) != 1 or frames_u8.stride(2) != 3 or frames_u8.stride(1) < 3 * W:
+        frames_u8 = frames_u8.contiguous()
+    if out is None:
+        out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=frames_u8.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, 3, Hp, Wp) and out.is_contiguous() and out.device == frames_u8.device
+    (bx, kx, ksx), (by, ky, ksy) = _resample_tables_on(frames_u8.device, H, W, oh, ow)
+    if max(ksx, ksy) > _lib.FRAMES_MAX_TAPS:
+        buf = torch.zeros((B, Hp, Wp, 3), dtype=torch.uint8, device=frames_u8.device)
+        for n in range(B):
+            resize_bilinear_u8(frames_u8[n].contiguous(), (oh, ow), buf[n], top, left)
+        return out.copy_(preprocess_u8(buf, (Hp, Wp), input_format))
+    norm = 1 if input_format == 'RGB_1_norm' else 0
+    mean = np.asarray(IMAGENET_MEAN, dtype=np.float32)
+    std = np.asarray(IMAGENET_STD, dtype=np.float32)
+    code = _lib.lib().mydet_frames_to_input_f32(_ptr(frames_u8), B, H, W, frames_u8.stride(0), frames_u8.stride(1),
+                                                _ptr(out), Hp, Wp, oh, ow, top, left, _ptr(bx), _ptr(kx), ksx, _ptr(by), _ptr(ky), ksy,
+                                                norm, ctypes.c_void_p(mean.ctypes.data), ctypes.c_void_p(std.ctypes.data), _stream())
+    _lib.check(code, 'mydet_frames_to_input_f32')
+    return out
 
 
 def records_to_original_(rec, pad_infos):
