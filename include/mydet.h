@@ -595,6 +595,44 @@ int mydet_frames_to_input_f32(const unsigned char *src, int B, int H, int W, int
                               const int32_t *bounds_y, const int32_t *ky, int ksy,
                               int norm, const float *mean3, const float *std3, void *stream);
 
+/* NV12 video frames (what hardware decoders produce): per frame a Y plane [H][W] and an interleaved chroma plane of
+ * ceil(H/2) rows of ceil(W/2) (U, V) byte pairs; odd H and W are legal.  Frame b of a plane is at ptr + b*img_bytes, its
+ * rows row_bytes apart (y_row_bytes >= W, uv_row_bytes >= 2*ceil(W/2); the planes may be separate allocations or the two
+ * parts of one decoder surface).  Conversion, 8-bit fixed point on signed 32-bit integers, >> an arithmetic shift,
+ * clip8 a clamp to 0..255, chroma nearest-neighbour (pixel (y, x) uses the pair (y >> 1, x >> 1)):
+ *     C = Y - 16 (limited range) or Y (full range),  D = U - 128,  E = V - 128
+ *     R = clip8((cy*C         + crv*E + 128) >> 8)
+ *     G = clip8((cy*C - cgu*D - cgv*E + 128) >> 8)
+ *     B = clip8((cy*C + cbu*D         + 128) >> 8)
+ * with round(256 * x) of the matrix (Kr, Kb = 0.299, 0.114 for BT.601, 0.2126, 0.0722 for BT.709; limited range scales
+ * luma by 255/219 and chroma by 255/224):
+ *     matrix, full_range     cy  crv  cgu  cgv  cbu
+ *     0 (BT.601), 0         298  409  100  208  516
+ *     1 (BT.709), 0         298  459   55  136  541
+ *     0 (BT.601), 1         256  359   88  183  454
+ *     1 (BT.709), 1         256  403   48  120  475
+ * Another selector value, a pitch below the row's bytes, a negative frame stride and null or non-positive arguments are
+ * MYDET_E_BADARG.  No reference counterpart.
+ *
+ * mydet_nv12_to_rgb_u8: the conversion alone, to packed uint8 RGB [B][H][W][3] (frame b at dst + b*dst_img_bytes, rows
+ * dst_row_bytes >= 3*W apart). */
+int mydet_nv12_to_rgb_u8(const unsigned char *y, int64_t y_img_bytes, int64_t y_row_bytes,
+                         const unsigned char *uv, int64_t uv_img_bytes, int64_t uv_row_bytes, int B, int H, int W,
+                         unsigned char *dst, int64_t dst_img_bytes, int64_t dst_row_bytes,
+                         int matrix, int full_range, void *stream);
+
+/* mydet_nv12_to_input_f32: NV12 frames -> float32 [B,3,Hp,Wp] in ONE launch: exactly what mydet_frames_to_input_f32 writes
+ * for the RGB frames mydet_nv12_to_rgb_u8 gives, bit for bit, with no RGB image in memory (the converted source window of
+ * a tile lives in LDS).  Geometry, tables, norm, mean3/std3 and their checks as for mydet_frames_to_input_f32, including
+ * MYDET_FRAMES_MAX_TAPS. */
+int mydet_nv12_to_input_f32(const unsigned char *y, int64_t y_img_bytes, int64_t y_row_bytes,
+                            const unsigned char *uv, int64_t uv_img_bytes, int64_t uv_row_bytes, int B, int H, int W,
+                            int matrix, int full_range,
+                            float *out, int Hp, int Wp, int oh, int ow, int top, int left,
+                            const int32_t *bounds_x, const int32_t *kx, int ksx,
+                            const int32_t *bounds_y, const int32_t *ky, int ksy,
+                            int norm, const float *mean3, const float *std3, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

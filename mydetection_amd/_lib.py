@@ -81,6 +81,10 @@ SIGNATURES = {
     'mydet_preprocess_u8_f32': [c_ptr, c_int, c_int, c_int, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_frames_to_input_f32': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
+    'mydet_nv12_to_rgb_u8': [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr],
+    'mydet_nv12_to_input_f32': [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int,
+                                c_ptr, c_int, c_int, c_int, c_int, c_int, c_int,
+                                c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_cxcywh_to_x1y1x2y2_f32': [c_ptr, c_ptr, c_i64, c_int, c_ptr],
     'mydet_bboxes_to_original_f32': [c_ptr, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr],
 }

@@ -271,6 +271,20 @@ class Detector():
         frames on the device are read in place; one fused launch (ops.frames_to_input) per frame size builds their
         network input."""
         _, groups = self._frame_groups(frames)
+
+        def rgb_input(parts):
+            def build(geo, dev):
+                ps = parts
+                if len(ps) > 1:                                      # a list: gather it where it already is
+                    where = dev if all(t.device == dev for t in ps) else torch.device('cpu')
+                    ps = [torch.cat([t.to(where) for t in ps])]
+                return ops.frames_to_input(ps[0].to(dev, non_blocking=True), geo, self.model.input_format)
+            return build
+        return self._records_of_inputs([(idxs, tuple(parts[0].shape[1:3]), rgb_input(parts)) for idxs, parts in groups], **kwargs)
+
+    def _records_of_inputs(self, groups, **kwargs):
+        """The part of _frame_records that does not depend on the pixel format.  groups: [(frame indices, (H, W) of those
+        frames, build(geometry, device) -> their float32 network input)]."""
         pre_proc = kwargs.get('preprocessing', self.preprocess)
         input_size = kwargs.get('input_size', self.input_size)
         conf_thres = kwargs.get('conf_thres', self.conf_thres)
@@ -280,20 +294,16 @@ class Detector():
             raise ValueError(f"rotated_nms needs a 'cxcywhd' model; this one predicts {self.model.bb_format!r}")
         dev = next(self.model.parameters()).device
         by_input = {}
-        for idxs, parts in groups:
-            geo = self._geometry(parts[0].shape[1], parts[0].shape[2], pre_proc, input_size)
-            by_input.setdefault(geo[2], []).append((idxs, parts, geo))
+        for idxs, hw, build in groups:
+            geo = self._geometry(hw[0], hw[1], pre_proc, input_size)
+            by_input.setdefault(geo[2], []).append((idxs, hw, build, geo))
         for members in by_input.values():
             idxs, xs, pads, hws = [], [], [], []
-            for part_idxs, parts, geo in members:
-                if len(parts) > 1:                                   # a list: gather it where it already is
-                    where = dev if all(t.device == dev for t in parts) else torch.device('cpu')
-                    parts = [torch.cat([t.to(where) for t in parts])]
-                u8 = parts[0].to(dev, non_blocking=True)
-                xs.append(ops.frames_to_input(u8, geo, self.model.input_format))
+            for part_idxs, hw, build, geo in members:
+                xs.append(build(geo, dev))
                 idxs += part_idxs
                 pads += [geo[3]] * len(part_idxs)
-                hws += [(u8.shape[1], u8.shape[2]) if geo[3] is not None else geo[2]] * len(part_idxs)
+                hws += [hw if geo[3] is not None else geo[2]] * len(part_idxs)
             x = xs[0]
             if len(xs) > 1:                                          # several frame sizes, one input size: one batch, in input order
                 order = sorted(range(len(idxs)), key=idxs.__getitem__)
@@ -311,9 +321,13 @@ class Detector():
         per-frame copy or launch: resize, padding, /255 and normalisation of a whole group are one HIP launch that gives
         the bits of preprocess_batch, so the detections equal predict_batch on PIL.Image.fromarray of the same frames.
         Keyword arguments as in _predict_pil.  Returns a list of ImageObjects in original-frame coordinates."""
+        return self._objects_of_records(self._frame_records(frames, **kwargs))
+
+    def _objects_of_records(self, records):
+        """ImageObjects in frame order from the (indices, records) pairs of _records_of_inputs."""
         from ..parallel import records_to_objects
         out = []
-        for idxs, rec in self._frame_records(frames, **kwargs):
+        for idxs, rec in records:
             out += [None] * (max(idxs) + 1 - len(out))
             objs = records_to_objects(rec, bb_format=self.model.bb_format)
             for j, o, hw in zip(idxs, objs, rec['img_hw']):
@@ -323,9 +337,13 @@ class Detector():
 
     def frames_to_json(self, frames, img_ids, eval_type='x1y1wh', catIdx2id=None, **kwargs):
         """COCO-style rows of uint8 frames (see predict_frames), image by image: the counterpart of _json_batch."""
+        return self._json_of_records(self._frame_records(frames, **kwargs), img_ids, eval_type, catIdx2id)
+
+    def _json_of_records(self, records, img_ids, eval_type, catIdx2id):
+        """COCO-style rows in frame order from the (indices, records) pairs of _records_of_inputs."""
         from ..utils.structures import batched_to_json
         out = [None] * len(img_ids)
-        for idxs, rec in self._frame_records(frames, **kwargs):
+        for idxs, rec in records:
             rows = batched_to_json(rec, [img_ids[j] for j in idxs], eval_type, catIdx2id)
             counts = ops.check_counts(rec['count'].cpu().tolist())
             o = 0
@@ -333,6 +351,75 @@ class Detector():
                 out[j] = rows[o:o + k]
                 o += k
         return [d for per_img in out for d in per_img]
+
+    @staticmethod
+    def _nv12_planes(y, uv=None, device=None):
+        """NV12 frames as two uint8 tensors: (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]).  y, uv: torch.uint8 tensors or
+        numpy.uint8 arrays, y of shape [B,H,W] or [H,W] and uv of shape [B,ceil(H/2),ceil(W/2),2] (or without B); with
+        uv=None, y is a decoder's single surface [B,H*3/2,W] (or 2-d) with even H and W, split into two views that share
+        its storage.  Anything else is a TypeError (type, dtype) or a ValueError (shape).  device: where the data goes
+        before the split -- one copy per plane or surface, none for what is already there; None leaves it where it is,
+        and then no device is touched."""
+        planes = []
+        for name, f in (('y', y), ('uv', uv)):
+            if f is None and name == 'uv':
+                continue
+            if isinstance(f, np.ndarray):
+                if f.dtype != np.uint8:
+                    raise TypeError(f'predict_frames_nv12: uint8 planes expected, got a numpy array of dtype {f.dtype} for {name}')
+                f = torch.from_numpy(np.ascontiguousarray(f))
+            elif isinstance(f, torch.Tensor):
+                if f.dtype != torch.uint8:
+                    raise TypeError(f'predict_frames_nv12: uint8 planes expected, got a tensor of dtype {f.dtype} for {name}')
+            else:
+                raise TypeError(f'predict_frames_nv12: a uint8 torch.Tensor or numpy.ndarray expected for {name}, got {type(f).__name__}')
+            planes.append(f)
+        y = planes[0]
+        if y.dim() not in (2, 3) or min(y.shape) < 1:
+            what = 'a surface of shape [B,H*3/2,W] or [H*3/2,W]' if uv is None else 'a Y plane of shape [B,H,W] or [H,W]'
+            raise ValueError(f'predict_frames_nv12: {what} expected, got {tuple(y.shape)}')
+        if uv is None:
+            rows, W = y.shape[-2:]
+            H = rows // 3 * 2
+            if rows % 3 or W % 2:                                    # an odd H would give 3k + 2 rows
+                raise ValueError(f'predict_frames_nv12: a single NV12 surface has H*3/2 rows with even H and W, got {tuple(y.shape)}')
+            s = y if device is None else y.to(device, non_blocking=True)
+            s = s.unsqueeze(0) if s.dim() == 2 else s
+            return s[:, :H], s[:, H:].unflatten(2, (W // 2, 2))
+        uv = planes[1]
+        if y.dim() == 2:
+            y, uv = y.unsqueeze(0), (uv.unsqueeze(0) if uv.dim() == 3 else uv)
+        B, H, W = y.shape
+        if tuple(uv.shape) != (B, (H + 1) // 2, (W + 1) // 2, 2):
+            raise ValueError(f'predict_frames_nv12: a UV plane of shape {(B, (H + 1) // 2, (W + 1) // 2, 2)} expected for Y '
+                             f'{tuple(y.shape)}, got {tuple(uv.shape)}')
+        if device is not None:
+            y, uv = y.to(device, non_blocking=True), uv.to(device, non_blocking=True)
+        return y, uv
+
+    def _nv12_records(self, y, uv, matrix, full_range, **kwargs):
+        """_frame_records for NV12 frames of one size: one fused launch (ops.nv12_to_input) builds the network input from
+        the two planes; everything after it is _records_of_inputs, as for RGB frames."""
+        ops.nv12_matrix_id(matrix)
+        yp, uvp = self._nv12_planes(y, uv, device=next(self.model.parameters()).device)
+
+        def build(geo, dev):
+            return ops.nv12_to_input(yp, uvp, geo, self.model.input_format, matrix, full_range)
+        return self._records_of_inputs([(list(range(yp.shape[0])), (yp.shape[1], yp.shape[2]), build)], **kwargs)
+
+    def predict_frames_nv12(self, y, uv=None, *, matrix='bt601', full_range=False, **kwargs):
+        """predict_frames for NV12 video, the format decoders produce: y is the uint8 Y plane [B,H,W] (or [H,W]) and uv the
+        interleaved chroma plane [B,ceil(H/2),ceil(W/2),2]; or, with uv=None, y is the single surface [B,H*3/2,W] (or 2-d)
+        with even H and W, split into the two plane views without a copy.  torch tensors or numpy arrays; host data
+        crosses in one copy per plane or surface, device tensors are read in place through their strides.  matrix:
+        'bt601' or 'bt709'; full_range: Y in 0..255 instead of 16..235 (formula: include/mydet.h).  Returns
+        exactly what predict_frames returns for the converted RGB frames (ops.nv12_to_rgb), which are never built: one
+        HIP launch reads the planes.  One call takes one frame size.  Keyword arguments as in _predict_pil."""
+        return self._objects_of_records(self._nv12_records(y, uv, matrix, full_range, **kwargs))
+
+    def frames_nv12_to_json(self, y, uv, img_ids, eval_type='x1y1wh', catIdx2id=None, *, matrix='bt601', full_range=False, **kwargs):
+        """COCO-style rows of NV12 frames (see predict_frames_nv12): the counterpart of frames_to_json."""
+        return self._json_of_records(self._nv12_records(y, uv, matrix, full_range, **kwargs), img_ids, eval_type, catIdx2id)
 
     def predict_batch(self, pil_imgs, **kwargs):
         """Batched form of detect_one (the reference loops image by image, api/detection.py:67-74): images that share a

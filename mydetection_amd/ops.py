@@ -1349,6 +1349,92 @@ def frames_to_input(frames_u8, geometry, input_format, out=None):
     return out
 
 
+NV12_MATRICES = {'bt601': 0, 'bt709': 1}          # the matrix selector of include/mydet.h, where the coefficient table lives
+
+
+def nv12_matrix_id(matrix):
+    """The C selector of a matrix name; a ValueError for an unknown one (raised before any device is touched)."""
+    if matrix not in NV12_MATRICES:
+        raise ValueError(f'nv12: matrix {matrix!r} is not one of {sorted(NV12_MATRICES)}')
+    return NV12_MATRICES[matrix]
+
+
+def _nv12_planes(y, uv, what):
+    """The checks nv12_to_rgb and nv12_to_input share: (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2], 2-d input?) on the device, read in
+    place through their frame and row strides when pixels (Y) and pairs (UV) are packed."""
+    for t, name in ((y, 'y'), (uv, 'uv')):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise TypeError(f'{what}: a uint8 tensor expected for {name}, got {t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}')
+    require_gpu(y, what)
+    require_gpu(uv, what)
+    single = y.dim() == 2
+    if single:
+        y = y.unsqueeze(0)
+        uv = uv.unsqueeze(0) if uv.dim() == 3 else uv
+    if y.dim() != 3 or min(y.shape) < 1:
+        raise ValueError(f'{what}: a Y plane of shape [B,H,W] or [H,W] expected, got {tuple(y.shape)}')
+    B, H, W = y.shape
+    if tuple(uv.shape) != (B, (H + 1) // 2, (W + 1) // 2, 2):
+        raise ValueError(f'{what}: a UV plane of shape {(B, (H + 1) // 2, (W + 1) // 2, 2)} expected for Y {tuple(y.shape)}, got {tuple(uv.shape)}')
+    if y.device != uv.device:
+        raise ValueError(f'{what}: y is on {y.device}, uv on {uv.device}')
+    if y.stride(2) != 1 or y.stride(1) < W or y.stride(0) < 0:
+        y = y.contiguous()
+    if uv.stride(3) != 1 or uv.stride(2) != 2 or uv.stride(1) < 2 * uv.shape[2] or uv.stride(0) < 0:
+        uv = uv.contiguous()
+    return y, uv, single
+
+
+def nv12_to_rgb(y, uv, matrix='bt601', full_range=False, out=None):
+    """NV12 frames on the device -> packed uint8 RGB [B,H,W,3] ([H,W,3] for a 2-d y) (include/mydet.h: mydet_nv12_to_rgb_u8,
+    where the formula and the coefficient table are).  y: uint8 [B,H,W] or [H,W], element stride 1 along W; uv: uint8
+    [B,ceil(H/2),ceil(W/2),2], last two dimensions packed; any row and frame strides, read in place.  matrix: 'bt601' or
+    'bt709'; full_range: Y in 0..255 instead of 16..235.  out: optional uint8 [B,H,W,3] view with packed pixels."""
+    m = nv12_matrix_id(matrix)
+    y, uv, single = _nv12_planes(y, uv, 'nv12_to_rgb')
+    B, H, W = y.shape
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=y.device)
+    dst = out.unsqueeze(0) if out.dim() == 3 else out
+    assert dst.dtype == torch.uint8 and tuple(dst.shape) == (B, H, W, 3) and dst.device == y.device
+    assert dst.stride(3) == 1 and dst.stride(2) == 3 and dst.stride(1) >= 3 * W and dst.stride(0) >= 0
+    code = _lib.lib().mydet_nv12_to_rgb_u8(_ptr(y), y.stride(0), y.stride(1), _ptr(uv), uv.stride(0), uv.stride(1), B, H, W,
+                                           _ptr(dst), dst.stride(0), dst.stride(1), m, int(bool(full_range)), _stream())
+    _lib.check(code, 'mydet_nv12_to_rgb_u8')
+    return dst[0] if single else dst
+
+
+def nv12_to_input(y, uv, geometry, input_format, matrix='bt601', full_range=False, out=None):
+    """NV12 frames of one size on the device -> the float32 network input [B,3,Hp,Wp] in ONE launch (include/mydet.h:
+    mydet_nv12_to_input_f32): the bits of frames_to_input(nv12_to_rgb(y, uv, matrix, full_range), geometry, input_format)
+    without the RGB frames.  y, uv, matrix, full_range as in nv12_to_rgb; geometry, input_format, out and the tap limit as
+    in frames_to_input -- past the limit the frames are converted and go through frames_to_input's own fallback."""
+    m = nv12_matrix_id(matrix)
+    y, uv, _ = _nv12_planes(y, uv, 'nv12_to_input')
+    if input_format not in ('RGB_1', 'RGB_1_norm'):
+        raise NotImplementedError()
+    B, H, W = y.shape
+    target, (top, left), (Hp, Wp), _ = geometry
+    oh, ow = (int(target[0]), int(target[1])) if target is not None else (H, W)
+    if min(oh, ow) < 1 or top < 0 or left < 0 or top + oh > Hp or left + ow > Wp:
+        raise ValueError(f'nv12_to_input: a {oh}x{ow} window at ({top}, {left}) does not fit the {Hp}x{Wp} input')
+    (bx, kx, ksx), (by, ky, ksy) = _resample_tables_on(y.device, H, W, oh, ow)
+    if max(ksx, ksy) > _lib.FRAMES_MAX_TAPS:
+        return frames_to_input(nv12_to_rgb(y, uv, matrix, full_range), geometry, input_format, out)
+    if out is None:
+        out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=y.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, 3, Hp, Wp) and out.is_contiguous() and out.device == y.device
+    norm = 1 if input_format == 'RGB_1_norm' else 0
+    mean = np.asarray(IMAGENET_MEAN, dtype=np.float32)
+    std = np.asarray(IMAGENET_STD, dtype=np.float32)
+    code = _lib.lib().mydet_nv12_to_input_f32(_ptr(y), y.stride(0), y.stride(1), _ptr(uv), uv.stride(0), uv.stride(1), B, H, W,
+                                              m, int(bool(full_range)), _ptr(out), Hp, Wp, oh, ow, top, left,
+                                              _ptr(bx), _ptr(kx), ksx, _ptr(by), _ptr(ky), ksy, norm,
+                                              ctypes.c_void_p(mean.ctypes.data), ctypes.c_void_p(std.ctypes.data), _stream())
+    _lib.check(code, 'mydet_nv12_to_input_f32')
+    return out
+
+
 def records_to_original_(rec, pad_infos):
     """bboxes_to_original_ for a whole batch of records in place: pad_infos = one (ori w, ori h, tl x, tl y, imw, imh)
     per image (a row of ones-and-zeros (1, 1, 0, 0, 1, 1) leaves an image's boxes unchanged bit for bit)."""
