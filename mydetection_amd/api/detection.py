@@ -240,6 +240,17 @@ class Detector():
         return min(want, batch) if env.isdigit() else (want if batch % want == 0 else 1)
 
     @staticmethod
+    def _uint8_tensor(f, what):
+        """f, a torch.uint8 tensor or numpy.uint8 array, as a tensor (no copy of a contiguous array); a TypeError worded with
+        `what` (the caller and the argument) for any other type or dtype."""
+        if not isinstance(f, (np.ndarray, torch.Tensor)):
+            raise TypeError(f'{what}: a uint8 torch.Tensor or numpy.ndarray expected, got {type(f).__name__}')
+        is_np = isinstance(f, np.ndarray)
+        if f.dtype != (np.uint8 if is_np else torch.uint8):
+            raise TypeError(f"{what}: uint8 expected, got a {'numpy array' if is_np else 'tensor'} of dtype {f.dtype}")
+        return torch.from_numpy(np.ascontiguousarray(f)) if is_np else f
+
+    @staticmethod
     def _frame_groups(frames):
         """Frames as uint8 tensors grouped by size: (number of frames, [(indices, [tensors [n,H,W,3]])]).  Accepts a
         torch.uint8 tensor or numpy.uint8 array of shape [B,H,W,3] or [H,W,3], on the host or the device, or a list of them;
@@ -247,17 +258,9 @@ class Detector():
         items = list(frames) if isinstance(frames, (list, tuple)) else [frames]
         groups, n = {}, 0
         for f in items:
-            if isinstance(f, np.ndarray):
-                if f.dtype != np.uint8:
-                    raise TypeError(f'predict_frames: uint8 frames expected, got a numpy array of dtype {f.dtype}')
-            elif isinstance(f, torch.Tensor):
-                if f.dtype != torch.uint8:
-                    raise TypeError(f'predict_frames: uint8 frames expected, got a tensor of dtype {f.dtype}')
-            else:
-                raise TypeError(f'predict_frames: a uint8 torch.Tensor or numpy.ndarray (or a list of them) expected, got {type(f).__name__}')
+            t = Detector._uint8_tensor(f, 'predict_frames: frames (or a list of them)')
             if f.ndim not in (3, 4) or f.shape[-1] != 3 or min(f.shape) < 1:
                 raise ValueError(f'predict_frames: frames of shape [B,H,W,3] or [H,W,3] expected, got {tuple(f.shape)}')
-            t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
             t = t.unsqueeze(0) if t.dim() == 3 else t
             idxs, parts = groups.setdefault((t.shape[1], t.shape[2]), ([], []))
             idxs += range(n, n + t.shape[0])
@@ -360,21 +363,9 @@ class Detector():
         its storage.  Anything else is a TypeError (type, dtype) or a ValueError (shape).  device: where the data goes
         before the split -- one copy per plane or surface, none for what is already there; None leaves it where it is,
         and then no device is touched."""
-        planes = []
-        for name, f in (('y', y), ('uv', uv)):
-            if f is None and name == 'uv':
-                continue
-            if isinstance(f, np.ndarray):
-                if f.dtype != np.uint8:
-                    raise TypeError(f'predict_frames_nv12: uint8 planes expected, got a numpy array of dtype {f.dtype} for {name}')
-                f = torch.from_numpy(np.ascontiguousarray(f))
-            elif isinstance(f, torch.Tensor):
-                if f.dtype != torch.uint8:
-                    raise TypeError(f'predict_frames_nv12: uint8 planes expected, got a tensor of dtype {f.dtype} for {name}')
-            else:
-                raise TypeError(f'predict_frames_nv12: a uint8 torch.Tensor or numpy.ndarray expected for {name}, got {type(f).__name__}')
-            planes.append(f)
-        y = planes[0]
+        y = Detector._uint8_tensor(y, 'predict_frames_nv12: y')
+        if uv is not None:
+            uv = Detector._uint8_tensor(uv, 'predict_frames_nv12: uv')
         if y.dim() not in (2, 3) or min(y.shape) < 1:
             what = 'a surface of shape [B,H*3/2,W] or [H*3/2,W]' if uv is None else 'a Y plane of shape [B,H,W] or [H,W]'
             raise ValueError(f'predict_frames_nv12: {what} expected, got {tuple(y.shape)}')
@@ -386,7 +377,6 @@ class Detector():
             s = y if device is None else y.to(device, non_blocking=True)
             s = s.unsqueeze(0) if s.dim() == 2 else s
             return s[:, :H], s[:, H:].unflatten(2, (W // 2, 2))
-        uv = planes[1]
         if y.dim() == 2:
             y, uv = y.unsqueeze(0), (uv.unsqueeze(0) if uv.dim() == 3 else uv)
         B, H, W = y.shape
@@ -425,11 +415,4 @@ class Detector():
         """Batched form of detect_one (the reference loops image by image, api/detection.py:67-74): images that share a
         network input size go through ONE forward + ONE batched post-process.  Returns a list of ImageObjects in the
         original image coordinates, in input order."""
-        from ..parallel import records_to_objects
-        out = [None] * len(pil_imgs)
-        for idxs, rec in self._records_by_size(pil_imgs, **kwargs):
-            objs = records_to_objects(rec, bb_format=self.model.bb_format)
-            for j, o, hw in zip(idxs, objs, rec['img_hw']):
-                o.img_hw = hw
-                out[j] = o
-        return out
+        return self._objects_of_records(self._records_by_size(pil_imgs, **kwargs))

@@ -5,7 +5,7 @@
 //   cxcywh_to_x1y1x2y2  utils/bbox_ops.py:309-316
 //   iou_rle             utils/bbox_ops.py:52-100  (rotated boxes; exact intersection area instead of the reference's
 //                                                  rasterised masks, rot_iou.h)
-#include "common.h"
+#include "pixel_math.h"
 #include "rot_iou.h"
 
 namespace {
@@ -210,17 +210,14 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char *im
     const int64_t t = i / Wp;
     const int y = (int)(t % Hp);
     const int64_t b = t / Hp;
-    float v[3] = {0.f, 0.f, 0.f};
+    int v[3] = {0, 0, 0};
     if (y < H && x < W) {
         const unsigned char *p = img + ((b * H + y) * W + x) * 3;
-        v[0] = (float)p[0] / 255.0f; v[1] = (float)p[1] / 255.0f; v[2] = (float)p[2] / 255.0f;
-    }
-    if (norm) {
-        v[0] = (v[0] - m0) / s0; v[1] = (v[1] - m1) / s1; v[2] = (v[2] - m2) / s2;
+        v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
     }
     const int64_t plane = (int64_t)Hp * Wp;
     float *o = out + b * 3 * plane + (int64_t)y * Wp + x;
-    o[0] = v[0]; o[plane] = v[1]; o[2 * plane] = v[2];
+    o[0] = px_to_float(v[0], norm, m0, s0); o[plane] = px_to_float(v[1], norm, m1, s1); o[2 * plane] = px_to_float(v[2], norm, m2, s2);
 }
 }  // namespace
 
@@ -254,43 +251,34 @@ struct ResizeArgs {
     const int32_t *bx, *kx, *by, *ky;          // bounds [o][2] = (first tap, taps), weights [o][ks]
 };
 
-__device__ __forceinline__ int clip8(int v) {
-    v >>= 22;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const ResizeArgs p) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= p.oh * p.ow) return;
     const int y = i / p.ow, x = i - y * p.ow;
     const int y0 = p.by ? p.by[2 * y] : y, ny = p.by ? p.by[2 * y + 1] : 1;
     const int x0 = p.bx ? p.bx[2 * x] : x, nx = p.bx ? p.bx[2 * x + 1] : 1;
-    int acc[3] = {1 << 21, 1 << 21, 1 << 21};
+    PxFilter acc;
     int last[3] = {0, 0, 0};
     for (int j = 0; j < ny; ++j) {
         const unsigned char *row = p.src + (int64_t)(y0 + j) * p.src_row;
         int h[3];
         if (p.bx) {
-            int a[3] = {1 << 21, 1 << 21, 1 << 21};
+            PxFilter a;
             for (int t = 0; t < nx; ++t) {
-                const int w = p.kx[x * p.ksx + t];
                 const unsigned char *px = row + (x0 + t) * 3;
-                a[0] += px[0] * w; a[1] += px[1] * w; a[2] += px[2] * w;
+                a.add(px[0], px[1], px[2], p.kx[x * p.ksx + t]);
             }
-            h[0] = clip8(a[0]); h[1] = clip8(a[1]); h[2] = clip8(a[2]);
+            h[0] = a.clip8(0); h[1] = a.clip8(1); h[2] = a.clip8(2);
         } else {
             const unsigned char *px = row + x * 3;
             h[0] = px[0]; h[1] = px[1]; h[2] = px[2];
         }
-        if (p.by) {
-            const int w = p.ky[y * p.ksy + j];
-            acc[0] += h[0] * w; acc[1] += h[1] * w; acc[2] += h[2] * w;
-        }
+        if (p.by) acc.add(h[0], h[1], h[2], p.ky[y * p.ksy + j]);
         last[0] = h[0]; last[1] = h[1]; last[2] = h[2];
     }
     unsigned char *o = p.dst + (int64_t)y * p.dst_row + x * 3;
     if (p.by) {
-        o[0] = (unsigned char)clip8(acc[0]); o[1] = (unsigned char)clip8(acc[1]); o[2] = (unsigned char)clip8(acc[2]);
+        o[0] = (unsigned char)acc.clip8(0); o[1] = (unsigned char)acc.clip8(1); o[2] = (unsigned char)acc.clip8(2);
     } else {
         o[0] = (unsigned char)last[0]; o[1] = (unsigned char)last[1]; o[2] = (unsigned char)last[2];
     }

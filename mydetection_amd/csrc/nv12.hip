@@ -11,8 +11,8 @@
 //   B = clip8((cy*C + cbu*D         + 128) >> 8)
 // with round(256 * x) of the BT.601 / BT.709 matrices in NV_COEF below, the only copy of the table.
 //
-// The fused kernel keeps the tile shape, the stage of horizontally resampled rows, the vertical pass and the stores of
-// frames_to_input_kernel (its code object is left untouched, so its tile code is restated here).  The horizontal pass differs: the
+// The fused kernel is built from the tile pipeline of frames_tile.h, like frames_to_input_kernel: the same tile, stage of
+// horizontally resampled rows, vertical pass and stores, from the same functions.  The horizontal pass differs: the
 // taps of neighbouring output columns overlap (7 taps for 3 source pixels per column at 1080p -> 360), so the source is
 // converted once per pixel and not once per tap.  NV_ROWS source rows of the tile's column window [c0, c0 + max_cols) are read
 // as quads -- one Y dword and one chroma dword per thread (a quad starts at a multiple of 4, so both are at byte c of their
@@ -23,11 +23,10 @@
 // at most 39 KiB + 8 * 528 * 4 B = 55.5 KiB at MYDET_FRAMES_MAX_TAPS, 15 + 6.4 KiB for 1080p -> 360 rows.  Every table entry
 // is clamped before it addresses either plane or the LDS window, so a malformed table gives wrong pixels, never an access
 // outside the planes or the stage.
-#include "common.h"
+#include "frames_tile.h"
 
 namespace {
 
-constexpr int FR_TH = 16, FR_TW = 64;      // the output tile of frames.hip
 constexpr int NV_ROWS = 8;                 // source rows converted per step
 
 // cy, crv, cgu, cgv, cbu, luma offset: [matrix: 0 = BT.601, 1 = BT.709][range: 0 = limited, 1 = full]
@@ -45,10 +44,8 @@ struct Nv12Src {
 
 struct Nv12InputArgs {
     Nv12Src s;
-    float *out;
-    int Hp, Wp, oh, ow, top, left, ksx, ksy, max_rows, max_cols, norm;
-    const int32_t *bx, *kx, *by, *ky;          // bounds [o][2] = (first tap, taps), weights [o][ks]; null = pass skipped
-    float m[3], sd[3];
+    int max_cols;
+    FrOut o;
 };
 
 struct Nv12RgbArgs {
@@ -58,16 +55,10 @@ struct Nv12RgbArgs {
     int dst_words;                             // dst rows can be written as aligned dwords
 };
 
-__device__ __forceinline__ int nv_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ int nv_clip8(int v) { return nv_clamp(v >> 22, 0, 255); }     // Pillow's 8-bit filter rounding
-
 __device__ __forceinline__ uint32_t nv_rgb(const Nv12Coef &k, int Y, int U, int V) {
     const int c = k.cy * (Y - k.yoff) + 128, d = U - 128, e = V - 128;
-    const int r = nv_clamp((c + k.crv * e) >> 8, 0, 255);
-    const int g = nv_clamp((c - k.cgu * d - k.cgv * e) >> 8, 0, 255);
-    const int b = nv_clamp((c + k.cbu * d) >> 8, 0, 255);
-    return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
+    return px_pack(px_clamp((c + k.crv * e) >> 8, 0, 255), px_clamp((c - k.cgu * d - k.cgv * e) >> 8, 0, 255),
+                   px_clamp((c + k.cbu * d) >> 8, 0, 255));
 }
 
 // Four neighbouring pixels of source row `row` from column c (c % 4 == 0) as packed dwords; a pixel at or beyond W is zero.
@@ -121,78 +112,42 @@ __global__ __launch_bounds__(256) void nv12_to_rgb_kernel(const Nv12RgbArgs p) {
     }
 }
 
-// N = pixels per thread along x of the vertical pass and the stores: 4 (float4 stores, Wp % 4 == 0) or 1
+// N = pixels per thread along x of the vertical pass and the stores: 4 or 1 (frames_tile.h)
 template <int N>
 __global__ __launch_bounds__(256) void nv12_to_input_kernel(const Nv12InputArgs p) {
     extern __shared__ __align__(16) uint32_t nv_lds[];
     uint32_t *stage = nv_lds;                                           // [max_rows][FR_TW] horizontally resampled pixels
-    int32_t *wts = reinterpret_cast<int32_t *>(nv_lds + p.max_rows * FR_TW);   // [ksx][FR_TW] horizontal weights, tap-major
-    uint32_t *raw = nv_lds + (p.max_rows + p.ksx) * FR_TW;              // [NV_ROWS][max_cols] converted source pixels
+    int32_t *wts = reinterpret_cast<int32_t *>(nv_lds + p.o.max_rows * FR_TW);   // [ksx][FR_TW] horizontal weights, tap-major
+    uint32_t *raw = nv_lds + (p.o.max_rows + p.o.ksx) * FR_TW;          // [NV_ROWS][max_cols] converted source pixels
     const int tid = threadIdx.x;
     const int tx0 = blockIdx.x * FR_TW, ty0 = blockIdx.y * FR_TH, b = blockIdx.z;
-    const int H = p.s.H, W = p.s.W;
 
-    // rows / columns of the resized image that fall into this tile
-    const int wy_lo = max(ty0 - p.top, 0), wy_hi = min(ty0 + FR_TH - p.top, p.oh);
-    const int wx_lo = max(tx0 - p.left, 0), wx_hi = min(tx0 + FR_TW - p.left, p.ow);
-    const bool live = wy_lo < wy_hi && wx_lo < wx_hi;                   // uniform over the workgroup
-    int r0 = 0, nrows = 1;
-    if (live) {
-        int r1;
-        if (p.by) {
-            r0 = p.by[2 * wy_lo];
-            r1 = p.by[2 * (wy_hi - 1)] + p.by[2 * (wy_hi - 1) + 1];
-        } else {
-            r0 = wy_lo;
-            r1 = wy_hi;
-        }
-        r0 = nv_clamp(r0, 0, H - 1);
-        nrows = nv_clamp(r1 - r0, 1, min(p.max_rows, H - r0));
+    const FrWindow win = fr_window(p.o, p.s.H, tx0, ty0);
+    if (win.live) {
         // first column of the window, on a quad: the first tap of the tile's first column (taps start in column order)
-        const int c0 = nv_clamp(p.bx ? p.bx[2 * wx_lo] : wx_lo, 0, W - 1) & ~3;
-
-        if (p.bx) {                                                     // read after the first barrier below
-            for (int i = tid; i < FR_TW * p.ksx; i += 256) {
-                const int col = i / p.ksx, t = i - col * p.ksx;
-                const int wx = tx0 + col - p.left;
-                wts[t * FR_TW + col] = (wx >= 0 && wx < p.ow) ? p.kx[wx * p.ksx + t] : 0;
-            }
-        }
+        const int c0 = px_clamp(p.o.bx ? p.o.bx[2 * win.wx_lo] : win.wx_lo, 0, p.s.W - 1) & ~3;
+        if (p.o.bx) fr_stage_weights(p.o, wts, tx0, tid);               // read after the first barrier below
         // a thread owns one column of the tile: its taps are raw[xs, xs + nx)
         const int col = tid & (FR_TW - 1), wv = tid >> 6;
-        const int wx = tx0 + col - p.left;
-        const bool inside = wx >= 0 && wx < p.ow;
-        int xs = 0, nx = 1;
-        if (inside) {
-            int x0 = wx;
-            if (p.bx) {
-                x0 = nv_clamp(p.bx[2 * wx], 0, W - 1);
-                nx = nv_clamp(p.bx[2 * wx + 1], 0, min(p.ksx, W - x0));
-            }
-            xs = nv_clamp(x0 - c0, 0, p.max_cols - 1);
-            nx = min(nx, p.max_cols - xs);
-        }
+        const FrColumn c = fr_column(p.o, p.s.W, tx0, col);
+        const int xs = px_clamp(c.x0 - c0, 0, p.max_cols - 1), nx = min(c.nx, p.max_cols - xs);
         const unsigned char *ysrc = p.s.y + (int64_t)b * p.s.y_img, *uvsrc = p.s.uv + (int64_t)b * p.s.uv_img;
         const int nq = p.max_cols >> 2;
-        for (int rb = 0; rb < nrows; rb += NV_ROWS) {
-            const int nr = min(NV_ROWS, nrows - rb);
+        for (int rb = 0; rb < win.nrows; rb += NV_ROWS) {
+            const int nr = min(NV_ROWS, win.nrows - rb);
             if (rb) __syncthreads();                                    // the previous step's taps have been read
             for (int r = wv; r < nr; r += 256 / FR_TW)                  // a wave converts a row of the window
                 for (int q = col; q < nq; q += FR_TW)
-                    *reinterpret_cast<uint4 *>(raw + r * p.max_cols + 4 * q) = nv_quad(p.s, ysrc, uvsrc, r0 + rb + r, c0 + 4 * q);
+                    *reinterpret_cast<uint4 *>(raw + r * p.max_cols + 4 * q) = nv_quad(p.s, ysrc, uvsrc, win.r0 + rb + r, c0 + 4 * q);
             __syncthreads();
             for (int r = wv; r < nr; r += 256 / FR_TW) {                // horizontal pass
                 uint32_t v = 0;
-                if (inside) {
+                if (c.inside) {
                     const uint32_t *px = raw + r * p.max_cols + xs;
-                    if (p.bx) {
-                        int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
-                        for (int t = 0; t < nx; ++t) {
-                            const int w = wts[t * FR_TW + col];
-                            const uint32_t s = px[t];
-                            a0 += (int)(s & 255u) * w; a1 += (int)((s >> 8) & 255u) * w; a2 += (int)(s >> 16) * w;
-                        }
-                        v = (uint32_t)nv_clip8(a0) | ((uint32_t)nv_clip8(a1) << 8) | ((uint32_t)nv_clip8(a2) << 16);
+                    if (p.o.bx) {
+                        PxFilter f;
+                        for (int t = 0; t < nx; ++t) f.add(px[t], wts[t * FR_TW + col]);
+                        v = f.pixel();
                     } else {
                         v = px[0];
                     }
@@ -202,73 +157,7 @@ __global__ __launch_bounds__(256) void nv12_to_input_kernel(const Nv12InputArgs 
         }
     }
     __syncthreads();
-
-    // vertical pass + float conversion: a thread owns N neighbouring pixels of a row
-    constexpr int XT = FR_TW / N;                                       // threads along x
-    const int xq = tid % XT;
-    const int ox = tx0 + xq * N;
-    if (ox >= p.Wp) return;                                             // N == 4: Wp % 4 == 0, a quad is in or out as a whole
-    const int64_t plane = (int64_t)p.Hp * p.Wp;
-    for (int ly = tid / XT; ly < FR_TH; ly += 256 / XT) {
-        const int oy = ty0 + ly;
-        if (oy >= p.Hp) break;
-        const int wy = oy - p.top;
-        uint32_t q[N];
-#pragma unroll
-        for (int e = 0; e < N; ++e) q[e] = 0;
-        if (live && wy >= 0 && wy < p.oh) {
-            if (p.by) {
-                const int y0 = p.by[2 * wy], ny = nv_clamp(p.by[2 * wy + 1], 0, p.ksy);
-                int acc[N][3];
-#pragma unroll
-                for (int e = 0; e < N; ++e) acc[e][0] = acc[e][1] = acc[e][2] = 1 << 21;
-                for (int j = 0; j < ny; ++j) {
-                    const int w = p.ky[wy * p.ksy + j];
-                    const int rr = nv_clamp(y0 + j - r0, 0, nrows - 1);
-                    uint32_t h[N];
-                    if constexpr (N == 4) {
-                        const uint4 t4 = *reinterpret_cast<const uint4 *>(stage + rr * FR_TW + xq * 4);
-                        h[0] = t4.x; h[1] = t4.y; h[2] = t4.z; h[3] = t4.w;
-                    } else {
-                        h[0] = stage[rr * FR_TW + xq];
-                    }
-#pragma unroll
-                    for (int e = 0; e < N; ++e) {
-                        acc[e][0] += (int)(h[e] & 255u) * w;
-                        acc[e][1] += (int)((h[e] >> 8) & 255u) * w;
-                        acc[e][2] += (int)((h[e] >> 16) & 255u) * w;
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < N; ++e)
-                    q[e] = (uint32_t)nv_clip8(acc[e][0]) | ((uint32_t)nv_clip8(acc[e][1]) << 8) | ((uint32_t)nv_clip8(acc[e][2]) << 16);
-            } else {
-                const int rr = nv_clamp(wy - r0, 0, nrows - 1);
-                if constexpr (N == 4) {
-                    const uint4 t4 = *reinterpret_cast<const uint4 *>(stage + rr * FR_TW + xq * 4);
-                    q[0] = t4.x; q[1] = t4.y; q[2] = t4.z; q[3] = t4.w;
-                } else {
-                    q[0] = stage[rr * FR_TW + xq];
-                }
-            }
-        }
-        float *o = p.out + (int64_t)b * 3 * plane + (int64_t)oy * p.Wp + ox;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float f[N];
-#pragma unroll
-            for (int e = 0; e < N; ++e) {
-                f[e] = (float)((q[e] >> (8 * c)) & 255u) / 255.0f;
-                if (p.norm) f[e] = (f[e] - p.m[c]) / p.sd[c];
-            }
-            if constexpr (N == 4) {
-                f32x4 v = {f[0], f[1], f[2], f[3]};
-                *reinterpret_cast<f32x4 *>(o + c * plane) = v;
-            } else {
-                o[c * plane] = f[0];
-            }
-        }
-    }
+    fr_vertical_store<N>(p.o, stage, win, tx0, ty0, b, tid);
 }
 
 // The checks both entry points share; fills `s`
@@ -309,37 +198,20 @@ extern "C" int mydet_nv12_to_input_f32(const unsigned char *y, int64_t y_img_byt
     Nv12InputArgs p;
     const int code = nv12_source(p.s, y, y_img_bytes, y_row_bytes, uv, uv_img_bytes, uv_row_bytes, B, H, W, matrix, full_range);
     if (code) return code;
-    if (!out || Hp <= 0 || Wp <= 0 || oh <= 0 || ow <= 0 || top < 0 || left < 0) return MYDET_E_BADARG;
-    if ((int64_t)top + oh > Hp || (int64_t)left + ow > Wp) return MYDET_E_BADARG;
-    if ((bounds_x == nullptr) != (kx == nullptr) || (bounds_y == nullptr) != (ky == nullptr)) return MYDET_E_BADARG;
-    if ((!bounds_x && W != ow) || (!bounds_y && H != oh)) return MYDET_E_BADARG;
-    if ((bounds_x && (ksx <= 0 || ksx > MYDET_FRAMES_MAX_TAPS)) || (bounds_y && (ksy <= 0 || ksy > MYDET_FRAMES_MAX_TAPS)))
-        return MYDET_E_BADARG;
-    if (norm && (!mean3 || !std3)) return MYDET_E_BADARG;
-    const int gy = (Hp + FR_TH - 1) / FR_TH;
-    if (B > 65535 || gy > 65535) return MYDET_E_UNSUPP;
-    p.out = out; p.Hp = Hp; p.Wp = Wp; p.oh = oh; p.ow = ow; p.top = top; p.left = left;
-    p.ksx = bounds_x ? ksx : 0; p.ksy = bounds_y ? ksy : 0; p.norm = norm ? 1 : 0;
-    p.bx = bounds_x; p.kx = kx; p.by = bounds_y; p.ky = ky;
-    for (int c = 0; c < 3; ++c) {
-        p.m[c] = norm ? mean3[c] : 0.f;
-        p.sd[c] = norm ? std3[c] : 1.f;
-    }
-    // source rows under FR_TH output rows and source columns under FR_TW output columns: last tap of the last - first tap of the
-    // first <= (n - 1) * scale + 2 * support + 1 <= (n - 1) * scale + ksize by Pillow's rule (support = max(scale, 1),
-    // ksize = 2 * ceil(support) + 1); + 2 spare.  The column window starts on a quad (+ 3) and is a whole number of quads.
-    int64_t rows = FR_TH, cols = FR_TW;
-    if (bounds_y) rows = (int64_t)((double)(FR_TH - 1) * (double)H / (double)oh) + ksy + 2;
+    dim3 grid;
+    const int tile = fr_tile_setup(p.o, grid, B, H, W, out, Hp, Wp, oh, ow, top, left, bounds_x, kx, ksx, bounds_y, ky, ksy, norm,
+                                   mean3, std3);
+    if (tile) return tile;
+    // source columns under FR_TW output columns, by the rule of max_rows (frames_tile.h): <= (FR_TW - 1) * scale + ksx, + 2 spare.
+    // The column window starts on a quad (+ 3) and is a whole number of quads.
+    int64_t cols = FR_TW;
     if (bounds_x) cols = (int64_t)((double)(FR_TW - 1) * (double)W / (double)ow) + ksx + 2;
-    if (rows > H) rows = H;
     cols = (cols + 3 + 3) / 4 * 4;
     if (cols > ((int64_t)W + 3) / 4 * 4) cols = ((int64_t)W + 3) / 4 * 4;
-    p.max_rows = (int)rows;
     p.max_cols = (int)cols;
-    const size_t lds = ((size_t)(p.max_rows + p.ksx) * FR_TW + (size_t)NV_ROWS * p.max_cols) * sizeof(uint32_t);
+    const size_t lds = fr_tile_lds_bytes(p.o) + (size_t)NV_ROWS * p.max_cols * sizeof(uint32_t);
     if (lds > 64 * 1024) return MYDET_E_UNSUPP;
-    const dim3 grid((unsigned)((Wp + FR_TW - 1) / FR_TW), (unsigned)gy, (unsigned)B);
-    if ((Wp & 3) == 0 && ((uintptr_t)out & 15) == 0)
+    if (fr_quad_stores(p.o))
         hipLaunchKernelGGL(nv12_to_input_kernel<4>, grid, dim3(256), lds, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL(nv12_to_input_kernel<1>, grid, dim3(256), lds, (hipStream_t)stream, p);

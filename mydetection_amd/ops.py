@@ -1307,6 +1307,23 @@ def _resample_tables_on(device, H, W, oh, ow):
     return tabs
 
 
+def _input_window(what, B, H, W, device, geometry, input_format, out):
+    """What frames_to_input and nv12_to_input (`what`, for the messages) share for B source frames of H x W on `device`:
+    (out, (oh, ow), (top, left), taps of the longer filter, the C arguments from `out` to `std3` -- the same run in both
+    entry points of include/mydet.h).  out is allocated when None and checked otherwise."""
+    norm = _norm_args(input_format)
+    target, (top, left), (Hp, Wp), _ = geometry
+    oh, ow = (int(target[0]), int(target[1])) if target is not None else (H, W)
+    if min(oh, ow) < 1 or top < 0 or left < 0 or top + oh > Hp or left + ow > Wp:
+        raise ValueError(f'{what}: a {oh}x{ow} window at ({top}, {left}) does not fit the {Hp}x{Wp} input')
+    if out is None:
+        out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, 3, Hp, Wp) and out.is_contiguous() and out.device == device
+    (bx, kx, ksx), (by, ky, ksy) = _resample_tables_on(device, H, W, oh, ow)
+    tail = (_ptr(out), Hp, Wp, oh, ow, top, left, _ptr(bx), _ptr(kx), ksx, _ptr(by), _ptr(ky), ksy) + norm
+    return out, (oh, ow), (top, left), max(ksx, ksy), tail
+
+
 def frames_to_input(frames_u8, geometry, input_format, out=None):
     """uint8 frames [B,H,W,3] (or [H,W,3]) of one size on the device -> the float32 network input [B,3,Hp,Wp] in ONE launch
     (include/mydet.h: mydet_frames_to_input_f32): PIL-exact resize, zero padding, /255 and normalisation, the bits
@@ -1321,30 +1338,17 @@ def frames_to_input(frames_u8, geometry, input_format, out=None):
         frames_u8 = frames_u8.unsqueeze(0)
     if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or min(frames_u8.shape) < 1:
         raise ValueError(f'frames_to_input: frames of shape [B,H,W,3] or [H,W,3] expected, got {tuple(frames_u8.shape)}')
-    if input_format not in ('RGB_1', 'RGB_1_norm'):
-        raise NotImplementedError()
     B, H, W, _ = frames_u8.shape
-    target, (top, left), (Hp, Wp), _ = geometry
-    oh, ow = (int(target[0]), int(target[1])) if target is not None else (H, W)
-    if min(oh, ow) < 1 or top < 0 or left < 0 or top + oh > Hp or left + ow > Wp:
-        raise ValueError(f'frames_to_input: a {oh}x{ow} window at ({top}, {left}) does not fit the {Hp}x{Wp} input')
+    out, (oh, ow), (top, left), taps, tail = _input_window('frames_to_input', B, H, W, frames_u8.device, geometry, input_format, out)
     if frames_u8.stride(3) != 1 or frames_u8.stride(2) != 3 or frames_u8.stride(1) < 3 * W:
         frames_u8 = frames_u8.contiguous()
-    if out is None:
-        out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=frames_u8.device)
-    assert out.dtype == torch.float32 and tuple(out.shape) == (B, 3, Hp, Wp) and out.is_contiguous() and out.device == frames_u8.device
-    (bx, kx, ksx), (by, ky, ksy) = _resample_tables_on(frames_u8.device, H, W, oh, ow)
-    if max(ksx, ksy) > _lib.FRAMES_MAX_TAPS:
+    if taps > _lib.FRAMES_MAX_TAPS:
+        Hp, Wp = geometry[2]
         buf = torch.zeros((B, Hp, Wp, 3), dtype=torch.uint8, device=frames_u8.device)
         for n in range(B):
             resize_bilinear_u8(frames_u8[n].contiguous(), (oh, ow), buf[n], top, left)
         return out.copy_(preprocess_u8(buf, (Hp, Wp), input_format))
-    norm = 1 if input_format == 'RGB_1_norm' else 0
-    mean = np.asarray(IMAGENET_MEAN, dtype=np.float32)
-    std = np.asarray(IMAGENET_STD, dtype=np.float32)
-    code = _lib.lib().mydet_frames_to_input_f32(_ptr(frames_u8), B, H, W, frames_u8.stride(0), frames_u8.stride(1),
-                                                _ptr(out), Hp, Wp, oh, ow, top, left, _ptr(bx), _ptr(kx), ksx, _ptr(by), _ptr(ky), ksy,
-                                                norm, ctypes.c_void_p(mean.ctypes.data), ctypes.c_void_p(std.ctypes.data), _stream())
+    code = _lib.lib().mydet_frames_to_input_f32(_ptr(frames_u8), B, H, W, frames_u8.stride(0), frames_u8.stride(1), *tail, _stream())
     _lib.check(code, 'mydet_frames_to_input_f32')
     return out
 
@@ -1411,26 +1415,12 @@ def nv12_to_input(y, uv, geometry, input_format, matrix='bt601', full_range=Fals
     in frames_to_input -- past the limit the frames are converted and go through frames_to_input's own fallback."""
     m = nv12_matrix_id(matrix)
     y, uv, _ = _nv12_planes(y, uv, 'nv12_to_input')
-    if input_format not in ('RGB_1', 'RGB_1_norm'):
-        raise NotImplementedError()
     B, H, W = y.shape
-    target, (top, left), (Hp, Wp), _ = geometry
-    oh, ow = (int(target[0]), int(target[1])) if target is not None else (H, W)
-    if min(oh, ow) < 1 or top < 0 or left < 0 or top + oh > Hp or left + ow > Wp:
-        raise ValueError(f'nv12_to_input: a {oh}x{ow} window at ({top}, {left}) does not fit the {Hp}x{Wp} input')
-    (bx, kx, ksx), (by, ky, ksy) = _resample_tables_on(y.device, H, W, oh, ow)
-    if max(ksx, ksy) > _lib.FRAMES_MAX_TAPS:
+    out, _, _, taps, tail = _input_window('nv12_to_input', B, H, W, y.device, geometry, input_format, out)
+    if taps > _lib.FRAMES_MAX_TAPS:
         return frames_to_input(nv12_to_rgb(y, uv, matrix, full_range), geometry, input_format, out)
-    if out is None:
-        out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=y.device)
-    assert out.dtype == torch.float32 and tuple(out.shape) == (B, 3, Hp, Wp) and out.is_contiguous() and out.device == y.device
-    norm = 1 if input_format == 'RGB_1_norm' else 0
-    mean = np.asarray(IMAGENET_MEAN, dtype=np.float32)
-    std = np.asarray(IMAGENET_STD, dtype=np.float32)
     code = _lib.lib().mydet_nv12_to_input_f32(_ptr(y), y.stride(0), y.stride(1), _ptr(uv), uv.stride(0), uv.stride(1), B, H, W,
-                                              m, int(bool(full_range)), _ptr(out), Hp, Wp, oh, ow, top, left,
-                                              _ptr(bx), _ptr(kx), ksx, _ptr(by), _ptr(ky), ksy, norm,
-                                              ctypes.c_void_p(mean.ctypes.data), ctypes.c_void_p(std.ctypes.data), _stream())
+                                              m, int(bool(full_range)), *tail, _stream())
     _lib.check(code, 'mydet_nv12_to_input_f32')
     return out
 
@@ -1471,6 +1461,15 @@ def detections_to_json(bbox, score, cls, count=None, cat_table=None):
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
+_MEAN_F32 = np.asarray(IMAGENET_MEAN, dtype=np.float32)          # module-level: the kernels' launch reads them through pointers
+_STD_F32 = np.asarray(IMAGENET_STD, dtype=np.float32)
+
+
+def _norm_args(input_format):
+    """The (norm, mean3, std3) arguments of the input kernels for an input format."""
+    if input_format not in ('RGB_1', 'RGB_1_norm'):
+        raise NotImplementedError()
+    return 1 if input_format == 'RGB_1_norm' else 0, ctypes.c_void_p(_MEAN_F32.ctypes.data), ctypes.c_void_p(_STD_F32.ctypes.data)
 
 
 def preprocess_u8(img_u8, out_hw, input_format):
@@ -1484,13 +1483,7 @@ def preprocess_u8(img_u8, out_hw, input_format):
     img_u8 = img_u8.contiguous()
     B, H, W, _ = img_u8.shape
     Hp, Wp = out_hw
-    if input_format not in ('RGB_1', 'RGB_1_norm'):
-        raise NotImplementedError()
-    norm = 1 if input_format == 'RGB_1_norm' else 0
-    mean = np.asarray(IMAGENET_MEAN, dtype=np.float32)
-    std = np.asarray(IMAGENET_STD, dtype=np.float32)
     out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=img_u8.device)
-    code = _lib.lib().mydet_preprocess_u8_f32(_ptr(img_u8), B, H, W, _ptr(out), Hp, Wp, norm,
-                                              ctypes.c_void_p(mean.ctypes.data), ctypes.c_void_p(std.ctypes.data), _stream())
+    code = _lib.lib().mydet_preprocess_u8_f32(_ptr(img_u8), B, H, W, _ptr(out), Hp, Wp, *_norm_args(input_format), _stream())
     _lib.check(code, 'mydet_preprocess_u8_f32')
     return out
