@@ -251,6 +251,16 @@ int mydet_conv_b3_reload_tuning(void);
  * computes its rounds with.  Returns the count or a negative MYDET_E_*.  No reference counterpart. */
 int mydet_conv_igemm_occupancy(int cfg, int *assumed);
 
+/* Test hook (host only, no GPU call): the plan mydet_conv2d_igemm_f32 uses for a layer on a chip of `cus` CUs.
+ * cfg < 0: the rule's own choice (choose_cfg); otherwise that configuration.  out[7] = {cfg id, BM, BN, BK,
+ * tiles in the main launch, tail tiles cut along K, cuts per tail tile (1 = no tail)}.  Returns 0 or MYDET_E_*.
+ * taps = KH * KW; workspace_bytes <= 0 = no workspace (never a tail).  It is the launcher's own arithmetic, not a copy: the
+ * tile table and the round / K-cut rule are the functions the launch calls.  (Not part of it: the 1x1 layers with at most 48
+ * output channels and 65 536 rows or more, which mydet_conv2d_igemm_f32 hands to the skinny pointwise kernel first.)
+ * No reference counterpart. */
+int mydet_conv_igemm_plan(int cfg, int B, int Ho, int Wo, int Cin, int Cout, int taps,
+                          int64_t workspace_bytes, int cus, int32_t *out);
+
 /* Focus.forward of the Ultralytics backbone (external/ultralytics/common.py:79-86): 2x2 space-to-depth,
  *   y[b, yo, xo, g*C + c] = x[b, c, 2*yo + dy, 2*xo + dx],  g = 0:(dy 0, dx 0) 1:(dy 1, dx 0) 2:(dy 0, dx 1) 3:(dy 1, dx 1)
  * -- the channel order of torch.cat([x[..., ::2, ::2], x[..., 1::2, ::2], x[..., ::2, 1::2], x[..., 1::2, 1::2]], 1).

@@ -925,17 +925,21 @@ int launch_fixup_act(const ConvArgs &a, int ntail, hipStream_t stream) {
 // remainder.  When that happens (and the caller gave workspace) the remainder tiles are instead cut along K into
 // `splits` slices that together fill the chip once, their partial tiles go to the workspace, and a small fixup
 // launch sums them in slice order and applies the epilogue: deterministic, no atomics.
-template <int BM, int BN, int WM, int WN, int BK>
-int launch(const ConvArgs &a0, int slots, hipStream_t stream) {
-    ConvArgs a = a0;
-    const int mtiles = (a.M + BM - 1) / BM;
-    a.ntiles = (a.Cout + BN - 1) / BN;
-    const int total = mtiles * a.ntiles;
-    const size_t lds = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float);
-    const bool cin = (a.Cin % BK) == 0;
-    const int nk = (a.K + BK - 1) / BK;
+struct TilePlan {
+    int ntiles, total;      // tiles along N, tiles in all
+    int rem, splits;        // tiles past the last whole round, K slices each of them would be cut into
+    bool split;             // the remainder runs as a K-cut tail (rem tiles x splits slices + the fixup launch)
+};
+
+// The arithmetic of `launch` (host only): one function for the launch and for mydet_conv_igemm_plan.  ws_bytes = 0: no workspace.
+TilePlan plan_tiles(int M, int Cout, int K, int BM, int BN, int BK, int slots, size_t ws_bytes) {
+    TilePlan pl;
+    const int mtiles = (M + BM - 1) / BM;
+    pl.ntiles = (Cout + BN - 1) / BN;
+    const int total = pl.total = mtiles * pl.ntiles;
+    const int nk = (K + BK - 1) / BK;
     const int rounds = total / slots;
-    int rem = total % slots;
+    const int rem = pl.rem = total % slots;
     // a grid that fills less than a quarter of one round (batch-1 / small-map layers: M = Ho*Wo is a few tiles) is cut along K
     // as a whole, so the chip is busy instead of a handful of CUs walking all of K
     // (a quarter, not half: between the two the K slices and the fixup launch cost more than the idle CUs -- round 4: batch 1
@@ -944,13 +948,26 @@ int launch(const ConvArgs &a0, int slots, hipStream_t stream) {
     int splits = rem > 0 ? slots / rem : 0;
     if (splits > 16) splits = 16;
     if (splits > nk / 4) splits = nk / 4;
+    pl.splits = splits;
     const size_t need = (size_t)rem * (splits > 0 ? splits : 0) * BM * BN * sizeof(float);
     // only long-K layers: on short ones the two extra launches cost more than the spared round
     // (shorter K -- 8 or 16 slabs, the 256->128 / 512->256 1x1 layers of YOLOv3 -- measured 1-3 % SLOWER with the tail cut)
     // and at most four whole rounds: after more, the workgroups no longer finish together and the partial last round is cheap
     // already (128->256 stride 2 @160^2, 6.25 rounds: headline 1 454 -> 1 459 images/s without its tail; the same holds for F(4x4))
-    const bool split = rem > 0 && splits >= 2 && a0.ws && need <= a0.ws_bytes &&
-                       (small || (nk >= 32 && rounds >= 2 && rounds <= 4 && rem * 2 <= slots));
+    pl.split = rem > 0 && splits >= 2 && ws_bytes > 0 && need <= ws_bytes &&
+               (small || (nk >= 32 && rounds >= 2 && rounds <= 4 && rem * 2 <= slots));
+    return pl;
+}
+
+template <int BM, int BN, int WM, int WN, int BK>
+int launch(const ConvArgs &a0, int slots, hipStream_t stream) {
+    ConvArgs a = a0;
+    const TilePlan pl = plan_tiles(a.M, a.Cout, a.K, BM, BN, BK, slots, a0.ws ? a0.ws_bytes : 0);
+    a.ntiles = pl.ntiles;
+    const int total = pl.total, rem = pl.rem, splits = pl.splits;
+    const bool split = pl.split;
+    const size_t lds = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float);
+    const bool cin = (a.Cin % BK) == 0;
     a.tile0 = 0; a.splits = 1;
     a.nblk = split ? total - rem : total;
     int rc = 0;
@@ -1089,19 +1106,33 @@ int cfg6_per_cu() {
 }
 
 // Tile configurations (id -> BM x BN, wave grid, BK).  MYDET_CONV_CFG=<id> forces one (tuning only).
-int launch_cfg(int id, const ConvArgs &a, hipStream_t s) {
-    const int cus = mydet_cu_count();
+template <int BM_, int BN_, int WM_, int WN_, int BK_>
+struct Tile {
+    static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, BK = BK_;
+};
+
+// The one table of them: f(tile, resident workgroups per CU -- LDS / register limited), for the launch and for the plan hook
+template <class F>
+int with_cfg(int id, F &&f) {
     switch (id) {
-        // last argument: resident workgroups = CUs (256 on MI355X) x (LDS / register limited workgroups per CU)
-        case 0: return launch<128, 128, 2, 2, 32>(a, 2 * cus, s);
-        case 1: return launch<128, 64, 2, 2, 32>(a, 2 * cus, s);
-        case 2: return launch<128, 32, 4, 1, 32>(a, 3 * cus, s);
-        case 3: return launch<64, 64, 2, 2, 32>(a, 4 * cus, s);
-        case 6: return launch<128, 64, 2, 2, 16>(a, cfg6_per_cu() * cus, s);
-        case 9: return launch<128, 96, 4, 1, 32>(a, 2 * cus, s);       // Cout in (64, 96]: 80 / 88 channels
-        case 8: return launch<128, 128, 2, 4, 32>(a, 2 * cus, s);     // 8 waves, wave tile 64x32
+        case 0: return f(Tile<128, 128, 2, 2, 32>{}, 2);
+        case 1: return f(Tile<128, 64, 2, 2, 32>{}, 2);
+        case 2: return f(Tile<128, 32, 4, 1, 32>{}, 3);
+        case 3: return f(Tile<64, 64, 2, 2, 32>{}, 4);
+        case 6: return f(Tile<128, 64, 2, 2, 16>{}, cfg6_per_cu());
+        case 9: return f(Tile<128, 96, 4, 1, 32>{}, 2);       // Cout in (64, 96]: 80 / 88 channels
+        case 8: return f(Tile<128, 128, 2, 4, 32>{}, 2);      // 8 waves, wave tile 64x32
         default: return MYDET_E_BADARG;
     }
+}
+
+int launch_cfg(int id, const ConvArgs &a, hipStream_t s) {
+    const int cus = mydet_cu_count();
+    // last argument: resident workgroups = CUs (256 on MI355X) x workgroups per CU
+    return with_cfg(id, [&](auto t, int per_cu) {
+        using T = decltype(t);
+        return launch<T::BM, T::BN, T::WM, T::WN, T::BK>(a, per_cu * cus, s);
+    });
 }
 
 int forced_cfg() {      // MYDET_CONV_CFG=<id>: tuning only; read per call so that one process can sweep the configurations
@@ -1195,6 +1226,26 @@ extern "C" int mydet_conv2d_igemm_f32(const float *x, int64_t ldx, const float *
         if (rc != MYDET_E_UNSUPP) return rc;
     }
     return launch_cfg(choose_cfg(M64, Cin, Cout, KH * KW), a, s);
+}
+
+/* Test hook (host only, no GPU call): the plan mydet_conv2d_igemm_f32 uses for a layer on a chip of `cus` CUs (include/mydet.h). */
+extern "C" int mydet_conv_igemm_plan(int cfg, int B, int Ho, int Wo, int Cin, int Cout, int taps, int64_t workspace_bytes, int cus,
+                                     int32_t *out) {
+    if (!out || B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || taps <= 0 || cus <= 0 || cus > (1 << 20) || (Cin & 3))
+        return MYDET_E_BADARG;
+    const int64_t M64 = (int64_t)B * Ho * Wo, K64 = (int64_t)taps * Cin;
+    if (M64 > (int64_t)1 << 30 || K64 > (int64_t)1 << 30) return MYDET_E_BADARG;
+    const int id = cfg < 0 ? choose_cfg(M64, Cin, Cout, taps) : cfg;
+    return with_cfg(id, [&](auto t, int per_cu) {
+        using T = decltype(t);
+        const TilePlan pl = plan_tiles((int)M64, Cout, (int)K64, T::BM, T::BN, T::BK, per_cu * cus,
+                                       workspace_bytes > 0 ? (size_t)workspace_bytes : 0);
+        out[0] = id; out[1] = T::BM; out[2] = T::BN; out[3] = T::BK;
+        out[4] = pl.split ? pl.total - pl.rem : pl.total;
+        out[5] = pl.split ? pl.rem : 0;
+        out[6] = pl.split ? pl.splits : 1;
+        return 0;
+    });
 }
 
 extern "C" int64_t mydet_split_bf16_elems(int Cout, int K) {

@@ -57,18 +57,20 @@ def _conv_case(dev, B, Cin, Cout, k, s, H, W, act, residual=False, bias_only=Fal
     assert err <= tol, f'conv mismatch {err} > {tol}'
 
 
+# the tile configuration and K cut each case takes on 256 CUs, from mydet_conv_igemm_plan (tests/test_host_cpu.py pins the rule,
+# tests/test_gpu_igemm_tiles.py runs every configuration): cfg id, tile BM x BN x BK, "cut n" = the whole small grid cut n ways along K
 @pytest.mark.parametrize('case', [
-    dict(B=2, Cin=32, Cout=64, k=3, s=2, H=32, W=32, act=1),                   # stride-2 downsample
-    dict(B=2, Cin=64, Cout=32, k=1, s=1, H=16, W=24, act=1),                   # DarkBlock 1x1, BN=32 tile
-    dict(B=1, Cin=32, Cout=64, k=3, s=1, H=16, W=16, act=1, residual=True),    # DarkBlock 3x3 + residual
-    dict(B=2, Cin=128, Cout=256, k=3, s=1, H=20, W=20, act=1, residual=True),  # 128x128 / 128x64 tiles
-    dict(B=3, Cin=256, Cout=255, k=1, s=1, H=13, W=11, act=0, bias_only=True), # YOLO head: ragged M and N
-    dict(B=1, Cin=768, Cout=256, k=1, s=1, H=8, W=8, act=1),                   # FPN concat input, small M
-    dict(B=4, Cin=512, Cout=1024, k=3, s=1, H=10, W=10, act=1),                # deep K = 4608
-    dict(B=2, Cin=24, Cout=144, k=1, s=1, H=12, W=12, act=2),                  # generic-K path (Cin % 32 != 0), swish
-    dict(B=1, Cin=88, Cout=88, k=3, s=1, H=10, W=10, act=0, bias_only=True),   # generic-K 3x3
-    dict(B=1, Cin=32, Cout=32, k=3, s=2, H=16, W=16, act=2, pad=(0, 0, 1, 1)), # static-SAME asymmetric pad
-    dict(B=32, Cin=64, Cout=128, k=3, s=2, H=64, W=64, act=1),                 # big grid (XCD remap path)
+    dict(B=2, Cin=32, Cout=64, k=3, s=2, H=32, W=32, act=1),                   # stride-2 downsample: cfg 6 (128x64x16), cut 4
+    dict(B=2, Cin=64, Cout=32, k=1, s=1, H=16, W=24, act=1),                   # DarkBlock 1x1: cfg 2 (128x32x32)
+    dict(B=1, Cin=32, Cout=64, k=3, s=1, H=16, W=16, act=1, residual=True),    # DarkBlock 3x3 + residual: cfg 6, cut 4
+    dict(B=2, Cin=128, Cout=256, k=3, s=1, H=20, W=20, act=1, residual=True),  # K = 1152, 52 tiles: cfg 3 (64x64x32), cut 9
+    dict(B=3, Cin=256, Cout=255, k=1, s=1, H=13, W=11, act=0, bias_only=True), # YOLO head: ragged M and N, cfg 3, no cut
+    dict(B=1, Cin=768, Cout=256, k=1, s=1, H=8, W=8, act=1),                   # FPN concat input, small M: cfg 3, cut 6
+    dict(B=4, Cin=512, Cout=1024, k=3, s=1, H=10, W=10, act=1),                # deep K = 4608: cfg 3, 112 tiles cut 9
+    dict(B=2, Cin=24, Cout=144, k=1, s=1, H=12, W=12, act=2),                  # generic-K path (Cin % 32 != 0), swish: cfg 6, no cut
+    dict(B=1, Cin=88, Cout=88, k=3, s=1, H=10, W=10, act=0, bias_only=True),   # generic-K 3x3: cfg 3, cut 6
+    dict(B=1, Cin=32, Cout=32, k=3, s=2, H=16, W=16, act=2, pad=(0, 0, 1, 1)), # static-SAME asymmetric pad: cfg 2, one tile
+    dict(B=32, Cin=64, Cout=128, k=3, s=2, H=64, W=64, act=1),                 # big grid (XCD remap path): cfg 3, 1024 tiles = one round
 ])
 def test_conv_igemm_vs_fp64(dev, case):
     _conv_case(dev, **case)
@@ -1004,7 +1006,13 @@ def test_maxpool_and_bifpn_fuse(dev):
 def test_conv_igemm_split_k_tail(dev, B, Cin, Cout, k, HW):
     """Grids of R full rounds + a small remainder run the remainder tiles split along K (partials in the
     workspace, summed in fixed order by the fixup launch); result must match a float32 CPU conv."""
-    from mydetection_amd import ops
+    import ctypes
+    from mydetection_amd import _lib, ops
+    # the tail exists on THIS chip (the launcher's own plan; the round counts above are for 256 CUs: tests/test_host_cpu.py pins them)
+    plan = (ctypes.c_int32 * 7)()
+    _lib.check(_lib.lib().mydet_conv_igemm_plan(-1, B, HW, HW, Cin, Cout, k * k, ops.WORKSPACE_BYTES,
+                                                torch.cuda.get_device_properties(0).multi_processor_count, plan), 'mydet_conv_igemm_plan')
+    assert plan[4] > 0 and plan[5] > 0 and plan[6] >= 2, f'no K-cut tail after whole rounds on this chip: {list(plan)}'
     g = torch.Generator().manual_seed(8)
     x = torch.randn(B, Cin, HW, HW, generator=g)
     w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5

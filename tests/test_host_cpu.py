@@ -771,3 +771,103 @@ def test_split_bf16_dispatch_rule():
     assert ops.b3_takes(px(16, 40), 672, 112, 1, ops.B3_GATED_MIN_ROWS, min_cout=ops.B3_GATED_MIN_COUT)
     assert ops.b3_takes(px(8, 20), 1152, 192, 1, ops.B3_GATED_MIN_ROWS, min_cout=ops.B3_GATED_MIN_COUT)
     assert not ops.b3_takes(px(16, 80), 240, 40, 1, ops.B3_GATED_MIN_ROWS, min_cout=ops.B3_GATED_MIN_COUT)
+
+
+def _igemm_plan(cfg, B, Ho, Wo, Cin, Cout, taps, ws_bytes=64 << 20, cus=256):
+    """mydet_conv_igemm_plan as a dict, or the negative MYDET_E_* code."""
+    from mydetection_amd import _lib
+    out = (ctypes.c_int32 * 7)()
+    rc = _lib.lib().mydet_conv_igemm_plan(cfg, B, Ho, Wo, Cin, Cout, taps, ws_bytes, cus, out)
+    if rc:
+        return rc
+    return dict(zip(('id', 'BM', 'BN', 'BK', 'main', 'tail', 'cuts'), out))
+
+
+IGEMM_TILES = {0: (128, 128, 32), 1: (128, 64, 32), 2: (128, 32, 32), 3: (64, 64, 32), 6: (128, 64, 16), 8: (128, 128, 32), 9: (128, 96, 32)}
+
+
+def test_conv_igemm_dispatch_rule():
+    """The float32 implicit GEMM's launch plan (mydet_conv_igemm_plan: host only, the launcher's own tile table, tile rule and
+    round / K-cut arithmetic) on a chip of 256 CUs: the configuration of the layers that the comments in choose_cfg cite, the
+    invariants of every plan over a grid of shapes, and the two plans that test_conv_igemm_split_k_tail's comments claim."""
+    ws = 64 << 20
+    # ---- pinned layers: (Cin, Cout, taps, M) -> id
+    pinned = [
+        (24, 144, 1, 2 * 12 * 12, 6),           # short generic K: BK = 16
+        (64, 32, 1, 2 * 16 * 24, 2),            # narrow outputs: the 32-wide tile
+        (480, 80, 1, 51200, 9),                 # 80 channels behind a long K, batch 32 at 40^2: the 96-wide tile ...
+        (480, 80, 1, 12800, 3),                 # ... not at batch 8
+        (480, 88, 1, 51200, 9),                 # "80 / 88 channels": the whole range (64, 96] ...
+        (384, 96, 1, 40000, 9), (384, 65, 1, 40000, 9), (384, 97, 1, 40000, 3), (384, 64, 1, 40000, 6),
+        (352, 96, 1, 40000, 3), (384, 96, 1, 39999, 3), (384, 96, 9, 40000, 3),      # ... from K = 384 and 40 000 rows, 1x1 only
+        (192, 1152, 1, 6400, 8),                # short K, very wide outputs: the 8-wave tile; K <= 256 keeps it at any row count
+        (192, 1152, 1, 3200, 8),
+        (320, 1920, 1, 6400, 8),                # K in (256, 512]: only from 4 800 rows up ("320->1920 47 -> 44 us" below)
+        (320, 1920, 1, 3200, 3),
+        (128, 64, 1, 32 * 160 * 160, 6),        # 33..64 outputs behind K >= 96: BK = 16
+        (64, 64, 1, 32 * 160 * 160, 1),         # ... behind a shorter K
+        (64, 128, 9, 32 * 160 * 160, 8),        # 3x3, K >= 512, big grid
+        (256, 255, 1, 3 * 13 * 11, 3),          # the YOLO head
+    ]
+    for Cin, Cout, taps, M, want in pinned:
+        p = _igemm_plan(-1, 1, 1, M, Cin, Cout, taps, ws)
+        assert p['id'] == want and (p['BM'], p['BN'], p['BK']) == IGEMM_TILES[want], (Cin, Cout, taps, M, p)
+    # every id reports its own tile (a table entry that launches another id's tile shows here)
+    for cfg, tile in IGEMM_TILES.items():
+        p = _igemm_plan(cfg, 2, 20, 20, 64, 128, 1, ws)
+        assert p['id'] == cfg and (p['BM'], p['BN'], p['BK']) == tile, p
+
+    # ---- rule grid
+    cins = (4, 8, 16, 24, 32, 40, 64, 88, 96, 128, 192, 256, 260, 320, 384, 480, 512, 768, 1024, 1152)
+    couts = (4, 16, 32, 33, 48, 64, 65, 80, 88, 96, 97, 128, 144, 255, 256, 512, 1023, 1024, 1152, 1920)
+    rows = (64, 189, 1000, 3200, 4799, 4800, 12800, 39999, 40000, 51200, 102400, 1 << 18, 1 << 20)
+    seen, tails, small_cuts = set(), 0, 0
+
+    def check(p, M, Cin, Cout, taps, ws_bytes):
+        BM, BN, BK = p['BM'], p['BN'], p['BK']
+        total = -(-M // BM) * -(-Cout // BN)
+        nk = -(-(taps * Cin) // BK)
+        assert p['main'] + p['tail'] == total and p['main'] >= 0 and p['tail'] >= 0, (p, M, Cin, Cout, taps)
+        assert (p['cuts'] == 1) == (p['tail'] == 0), (p, M, Cin, Cout, taps)
+        if p['tail']:
+            assert 2 <= p['cuts'] <= min(16, nk // 4), (p, M, Cin, Cout, taps)
+            assert p['tail'] * p['cuts'] * BM * BN * 4 <= ws_bytes, (p, M, Cin, Cout, taps)
+        if ws_bytes == 0:
+            assert p['tail'] == 0 and p['main'] == total, (p, M, Cin, Cout, taps)
+
+    for Cin in cins:
+        for Cout in couts:
+            for taps in (1, 9):
+                for M in rows:
+                    p = _igemm_plan(-1, 1, 1, M, Cin, Cout, taps, ws)
+                    seen.add(p['id'])
+                    assert (p['BM'], p['BN'], p['BK']) == IGEMM_TILES[p['id']]
+                    check(p, M, Cin, Cout, taps, ws)
+                    tails += p['tail'] > 0
+                    small_cuts += p['tail'] > 0 and p['main'] == 0
+                    q = _igemm_plan(-1, 1, 1, M, Cin, Cout, taps, 0)
+                    assert q['id'] == p['id']
+                    check(q, M, Cin, Cout, taps, 0)
+                    if M in (189, 12800, 102400):               # the same invariants on every tile, forced
+                        for cfg in IGEMM_TILES:
+                            for ws_bytes in (ws, 1 << 20):      # (a small workspace: plans whose tail does not fit have none)
+                                f = _igemm_plan(cfg, 1, 1, M, Cin, Cout, taps, ws_bytes)
+                                assert f['id'] == cfg
+                                check(f, M, Cin, Cout, taps, ws_bytes)
+    assert seen == {1, 2, 3, 6, 8, 9}, seen                 # 0 is reachable by MYDET_CONV_CFG only
+    assert tails >= 50 and small_cuts >= 20                 # both K-cut forms (tail after whole rounds, small grid) occur on this grid
+    # the factorisation of M does not matter, and another chip size moves the rounds
+    assert _igemm_plan(-1, 11, 80, 80, 1024, 128, 1, ws) == _igemm_plan(-1, 1, 1, 70400, 1024, 128, 1, ws)
+    assert _igemm_plan(-1, 11, 80, 80, 1024, 128, 1, ws, cus=304) != _igemm_plan(-1, 11, 80, 80, 1024, 128, 1, ws)
+
+    # ---- the two shapes of test_conv_igemm_split_k_tail: what its comments say, as facts
+    assert _igemm_plan(-1, 11, 80, 80, 1024, 128, 1, ws) == dict(id=3, BM=64, BN=64, BK=32, main=2 * 1024, tail=152, cuts=6)
+    assert _igemm_plan(-1, 69, 32, 32, 128, 256, 9, ws) == dict(id=8, BM=128, BN=128, BK=32, main=2 * 512, tail=80, cuts=6)
+    # the small-grid cut: 1 x 3 tiles of 64 x 64 are under a quarter of the 1 024 slots, 24 slabs of K: cut 6 ways (nk / 4)
+    assert _igemm_plan(-1, 1, 8, 8, 768, 136, 1, ws) == dict(id=3, BM=64, BN=64, BK=32, main=0, tail=3, cuts=6)
+
+    # ---- bad ids and arguments
+    for cfg in (4, 5, 7, 10):
+        assert _igemm_plan(cfg, 2, 20, 20, 64, 128, 1, ws) == -1
+    assert _igemm_plan(-1, 0, 20, 20, 64, 128, 1, ws) == -1 and _igemm_plan(-1, 2, 20, 20, 64, 128, 1, ws, cus=0) == -1
+    assert _igemm_plan(-1, 2, 20, 20, 66, 128, 1, ws) == -1
