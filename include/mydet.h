@@ -225,6 +225,13 @@ int mydet_conv2d_igemm_b3_f32(const float *x, int64_t ldx, const uint16_t *w_pla
 int mydet_conv3x3_p3_f32(const float *x, int64_t ldx, const uint16_t *w_planes, const float *scale, const float *shift,
                          const float *residual, int64_t ldr, float *y, int64_t ldy, int B, int H, int W, int Cin, int Cout,
                          int stride, int act, void *stream);
+/* Test and dispatch hook (host only, no GPU call): the tile plan mydet_conv3x3_p3_f32 launches for an Ho x Wo map of Cout output
+ * channels.  out[8] = {channel tile BN (64 | 128), strip shape of the remainder columns (0 none, 1 = 16 x 8, 2 = 32 x 4 tiles),
+ * tx_n, ty_n (8 x 16 tiles per image row / column), main_tiles = tx_n * ty_n, tiles_img (+ the strip tiles, which start at column
+ * 16 * tx_n), channel tiles, dynamic LDS bytes of the kernel form}; workgroups = B * tiles_img * channel tiles.  It is the launcher's
+ * own function, not a copy, and reads the same MYDET_P3_FORM / MYDET_P3_STRIP (once per process).  Returns 0, MYDET_E_BADARG or
+ * (stride not 1 | 2) MYDET_E_UNSUPP.  No reference counterpart. */
+int mydet_conv3x3_p3_plan(int Ho, int Wo, int Cout, int stride, int32_t *out);
 /* The 3 -> 32 stem (3x3, stride 1; mydet_conv2d_stem_f32) and the 3x3 stride-2 pad-1 layer behind it (mydet_conv3x3_p3_f32) as ONE
  * launch (csrc/conv_stem_p3.hip): the workgroup of the second layer's 8 x 16-pixel x 64-channel tile computes the 17 x 33-pixel stem
  * patch it needs on the matrix instructions, straight into the LDS patch its nine taps read -- the 32-channel full-resolution map is

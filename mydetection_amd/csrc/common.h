@@ -78,6 +78,17 @@ __device__ __forceinline__ void mydet_lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// Buffer descriptor over [base, base + bytes) for the raw_buffer_load / _store builtins (wave-uniform; out-of-range offsets read 0
+// and drop stores).  The size is capped below 2 GB: callers keep their byte offsets inside that.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mydet_rsrc(const void *base, int64_t bytes) {
+    const uint64_t a = (uint64_t)base;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    const int64_t capped = bytes > 0x7FFFFFF0ll ? 0x7FFFFFF0ll : bytes;
+    const int n = __builtin_amdgcn_readfirstlane((int)capped);
+    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, n, 0x00020000);
+}
+
 // Bijective XCD-aware remap (8 XCDs, blocks dealt round-robin): blocks that land on one
 // XCD get a contiguous range of logical ids, so neighbouring tiles share that XCD's L2.
 __device__ __forceinline__ int mydet_xcd_remap(int bid, int nblk) {

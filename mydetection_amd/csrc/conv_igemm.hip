@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "split_bf16.h"
 
 namespace {
 
@@ -55,23 +56,14 @@ __device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, unsigne
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float *base, int64_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const int64_t capped = bytes > 0x7FFFFFF0ll ? 0x7FFFFFF0ll : bytes;
-    const int n = __builtin_amdgcn_readfirstlane((int)capped);
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, n, 0x00020000);
-}
-
 // Epilogue: lane = output channel, register = output pixel.  Stores (and residual loads) are
 // buffer ops whose per-lane offset is fixed and whose row term is a scalar: one v_add per element.
 // Ragged tiles route out-of-range elements to offset 0xFFFFFFFF, which the range check drops.
 template <int ACT, bool RES, bool FULL, int TM, int TN>
 __device__ __forceinline__ void epilogue(const ConvArgs &p, f32x16 (&acc)[TM][TN], int m_base, int n_base,
                                          int fr, int fh, const float (&pscl)[TN], const float (&psft)[TN]) {
-    const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y, (int64_t)p.M * p.ldy * 4);
-    const __amdgpu_buffer_rsrc_t rr = make_rsrc(RES ? p.res : p.y, (int64_t)p.M * (RES ? p.ldr : p.ldy) * 4);
+    const __amdgpu_buffer_rsrc_t yr = mydet_rsrc(p.y, (int64_t)p.M * p.ldy * 4);
+    const __amdgpu_buffer_rsrc_t rr = mydet_rsrc(RES ? p.res : p.y, (int64_t)p.M * (RES ? p.ldr : p.ldy) * 4);
     const unsigned ldy4 = (unsigned)p.ldy * 4u, ldr4 = (unsigned)p.ldr * 4u;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -135,12 +127,12 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
     const int hwo = p.Ho * p.Wo;
     const int b0 = m0 / hwo;
     const int64_t img = (int64_t)p.H * p.W * p.ldx;
-    const __amdgpu_buffer_rsrc_t xr = make_rsrc(p.x + b0 * img, (p.B - b0) * img * 4);
-    const __amdgpu_buffer_rsrc_t wr = make_rsrc(p.w, (int64_t)p.Cout * p.K * 4);
+    const __amdgpu_buffer_rsrc_t xr = mydet_rsrc(p.x + b0 * img, (p.B - b0) * img * 4);
+    const __amdgpu_buffer_rsrc_t wr = mydet_rsrc(p.w, (int64_t)p.Cout * p.K * 4);
     const int64_t img1 = (int64_t)(p.H >> 1) * (p.W >> 1) * p.ldx1;      // CAT: the half-resolution source
-    const __amdgpu_buffer_rsrc_t xr1 = make_rsrc(CAT ? p.x1 + b0 * img1 : p.w, CAT ? (p.B - b0) * img1 * 4 : 16);
+    const __amdgpu_buffer_rsrc_t xr1 = mydet_rsrc(CAT ? p.x1 + b0 * img1 : p.w, CAT ? (p.B - b0) * img1 * 4 : 16);
     // SE gate (1x1 convs only): A[m][k] is multiplied by gate[image(m)][k] while it is staged
-    const __amdgpu_buffer_rsrc_t gr = make_rsrc(GATE ? p.gate : p.w, (int64_t)p.B * p.Cin * 4);
+    const __amdgpu_buffer_rsrc_t gr = mydet_rsrc(GATE ? p.gate : p.w, (int64_t)p.B * p.Cin * 4);
 
     // ---- staging role: chunk (4 floats) `sc` of rows sr + RP*i
     const int sc = tid % CH, sr = tid / CH;
@@ -358,19 +350,6 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
 // finite tensors, and guarding the split costs two vector-ALU instructions per element in the loop that bounds these kernels.
 constexpr int B3_COUT_PAD = 256;            // rows of the weight operand are padded to this (split_bf16_kernel)
 __device__ __host__ __forceinline__ int b3_unit(int rr, int h) { return 2 * rr + (h ^ ((rr >> 2) & 1)); }
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split3(const f32x4 v, bf16x4 &p0, bf16x4 &p1, bf16x4 &p2) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const __bf16 h0 = (__bf16)v[e];
-        const float r1 = v[e] - (float)h0;
-        const __bf16 h1 = (__bf16)r1;
-        const float r2 = r1 - (float)h1;
-        p0[e] = h0; p1[e] = h1; p2[e] = (__bf16)r2;
-    }
-}
 
 #ifndef B3_PF
 #define B3_PF 2          // slabs prefetched into registers beyond the one staged (2, 3, 4, 6 measured equal: profiles/HISTORY.md)
@@ -398,9 +377,9 @@ __global__ __launch_bounds__(128 * WN, 2) void conv_igemm_b3_kernel(const ConvAr
     const int hwo = p.Ho * p.Wo;
     const int b0 = m0 / hwo;
     const int64_t img = (int64_t)p.H * p.W * p.ldx;
-    const __amdgpu_buffer_rsrc_t xr = make_rsrc(p.x + b0 * img, (p.B - b0) * img * 4);
+    const __amdgpu_buffer_rsrc_t xr = mydet_rsrc(p.x + b0 * img, (p.B - b0) * img * 4);
     const int CoutP = (p.Cout + B3_COUT_PAD - 1) / B3_COUT_PAD * B3_COUT_PAD;
-    const __amdgpu_buffer_rsrc_t wr = make_rsrc(reinterpret_cast<const float *>(p.wsplit), (int64_t)((p.K + 15) >> 4) * 3 * CoutP * 32);
+    const __amdgpu_buffer_rsrc_t wr = mydet_rsrc(p.wsplit, (int64_t)((p.K + 15) >> 4) * 3 * CoutP * 32);
 
     // ---- staging roles.  A: chunk (4 floats) sc of rows sr + RP i.  B: chunk (8 bf16) bh of row br, all three planes.
     constexpr int RP = NT / 4;
@@ -409,7 +388,7 @@ __global__ __launch_bounds__(128 * WN, 2) void conv_igemm_b3_kernel(const ConvAr
     int aoff[AI];
     unsigned amask[AI];
     unsigned goff[AI];                               // GATE: byte offset of the row's image (+ this thread's channel quad) in gate[B][Cin]
-    const __amdgpu_buffer_rsrc_t gr = make_rsrc(GATE ? p.gate : p.x, (int64_t)p.B * p.Cin * 4);
+    const __amdgpu_buffer_rsrc_t gr = mydet_rsrc(GATE ? p.gate : p.x, (int64_t)p.B * p.Cin * 4);
     const bool flat = ntaps == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.Ho == p.H && p.Wo == p.W;
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
@@ -535,14 +514,13 @@ __global__ __launch_bounds__(128 * WN, 2) void conv_igemm_b3_kernel(const ConvAr
             for (int pl = 0; pl < 3; ++pl) bf[j][pl] = *reinterpret_cast<const bf16x8 *>(b + pl * PLANE_B + j * 32 * ROWB);
         // the six piece products, small ones first (the running sum absorbs them at its own rounding either way); a piece pair
         // sweeps all blocks of the wave tile before the next pair, so MFMAs on one accumulator are TM * TN instructions apart
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
         for (int t = 0; t < 6; ++t)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[t]], bf[j][PB[t]], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][SPLIT_PA[t]], bf[j][SPLIT_PB[t]], acc[i][j], 0, 0, 0);
     };
 
     load_slab(kt0, areg[0], breg[0]);
@@ -609,9 +587,9 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_b3w_kernel(const ConvArgs p
     const int hwo = p.Ho * p.Wo;
     const int b0 = m0 / hwo;
     const int64_t img = (int64_t)p.H * p.W * p.ldx;
-    const __amdgpu_buffer_rsrc_t xr = make_rsrc(p.x + b0 * img, (p.B - b0) * img * 4);
+    const __amdgpu_buffer_rsrc_t xr = mydet_rsrc(p.x + b0 * img, (p.B - b0) * img * 4);
     const int CoutP = (p.Cout + B3_COUT_PAD - 1) / B3_COUT_PAD * B3_COUT_PAD;
-    const __amdgpu_buffer_rsrc_t wr = make_rsrc(reinterpret_cast<const float *>(p.wsplit), (int64_t)(p.K >> 4) * 3 * CoutP * 32);
+    const __amdgpu_buffer_rsrc_t wr = mydet_rsrc(p.wsplit, (int64_t)(p.K >> 4) * 3 * CoutP * 32);
     const unsigned plane_bytes = (unsigned)CoutP * 32u, slab_bytes = 3u * plane_bytes;
 
     // ---- activation staging role: chunk (4 floats) sc of row sr
@@ -719,14 +697,13 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_b3w_kernel(const ConvArgs p
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) bf[j][pl] = *reinterpret_cast<const bf16x8 *>(b + pl * PLANE_B + j * 1024);
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
         for (int t = 0; t < 6; ++t)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[t]], bf[j][PB[t]], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][SPLIT_PA[t]], bf[j][SPLIT_PB[t]], acc[i][j], 0, 0, 0);
     };
 
     // prologue.  Requests, oldest first: B(kt0), B(kt0+1), A(kt0), A(kt0+1), A(kt0+2)

@@ -24,20 +24,16 @@
 // activation as conv_stem_kernel's epilogue (its fmaf chain over the 27 taps becomes the MFMA's sum: equal to float32 round-off).
 // Main: conv_p3_kernel's, bit for bit the same order.  Both held to 2e-5 * max|y| against float64 (tests/test_gpu_stem_p3.py).
 // Replaces netlist[0] + netlist[1] of models/backbones.py:14-30 (two ATen conv2d / batch_norm / leaky_relu chains, models/modules.py:76-95).
-#include "common.h"
+#include "p3_tile.h"
 
 namespace {
 
-constexpr unsigned OOB = 0xFFFFFFFFu;
-constexpr int SP_COUT_PAD = 256;                 // rows of the weight planes (split_bf16_kernel)
-
-// conv_p3.hip: P3Geom<2, 0>
-constexpr int SP_PH = 17, SP_PW = 33, SP_ROWLEN = 36, SP_PJ0 = 17, SP_ROWB = 32;
+typedef P3Geom<2, 0> SPG;                        // conv_p3's stride-2 8 x 16 tile
+constexpr int SP_PH = SPG::PH, SP_PW = SPG::PW;
 constexpr int SP_NPIX = SP_PH * SP_PW;           // 561 stem pixels per tile
 constexpr int SP_NBLK = (SP_NPIX + 31) / 32;     // 18 blocks of 32 pixels
 constexpr int SP_BPW = (SP_NBLK + 3) / 4;        // blocks per wave (waves 0, 1: 5; waves 2, 3: 4)
-constexpr int SP_PLANE = SP_PH * SP_ROWLEN * SP_ROWB;
-constexpr int SP_SLAB = 3 * SP_PLANE;            // 58 752 B
+constexpr int SP_SLAB = SPG::LDS;                // 58 752 B
 constexpr int SP_IH = SP_PH + 2, SP_IW = SP_PW + 2, SP_ILD = 36;       // image patch, LDS row length
 constexpr int SP_ICH = SP_IH * SP_ILD;           // floats per image channel in LDS
 constexpr int SP_LDS = SP_SLAB + 3 * SP_ICH * 4; // 66 960 B
@@ -51,49 +47,9 @@ struct StemP3Args {
     int tx_n, ntn, nblk, tiles_img;
 };
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t sp_rsrc(const void *base, int64_t bytes) {          // == conv_p3.hip: p3_rsrc
-    const uint64_t a = (uint64_t)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const int64_t capped = bytes > 0x7FFFFFF0ll ? 0x7FFFFFF0ll : bytes;
-    const int n = __builtin_amdgcn_readfirstlane((int)capped);
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, n, 0x00020000);
-}
-
-__device__ __forceinline__ void sp_split1(const float v, __bf16 &p0, __bf16 &p1, __bf16 &p2) {         // == conv_p3.hip: p3_split3
-    const __bf16 h0 = (__bf16)v;
-    const float r1 = v - (float)h0;
-    const __bf16 h1 = (__bf16)r1;
-    const float r2 = r1 - (float)h1;
-    p0 = h0; p1 = h1; p2 = (__bf16)r2;
-}
-
-// patch position / half swap of stem pixel (py, px) of the tile: conv_p3.hip's stride-2 SHAPE-0 layout
-__device__ __forceinline__ int sp_pos(int py, int px) { return py * SP_ROWLEN + (px & 1) * SP_PJ0 + (px >> 1); }
-__device__ __forceinline__ int sp_sigma(int px) { return ((px >> 1) >> 3) & 1; }
-
-// four consecutive channels (quad `fh` of half `half` of the resident slab) of one patch pixel -> the three planes
-__device__ __forceinline__ void sp_store_quad(char *patch, int pos, int sig, int half, int fh, const float (&v)[4]) {
-    bf16x4 q0, q1, q2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        __bf16 h0, h1, h2;
-        sp_split1(v[e], h0, h1, h2);
-        q0[e] = h0; q1[e] = h1; q2[e] = h2;
-    }
-    char *d = patch + pos * SP_ROWB + ((half ^ sig) * 16) + fh * 8;
-    *reinterpret_cast<bf16x4 *>(d) = q0;
-    *reinterpret_cast<bf16x4 *>(d + SP_PLANE) = q1;
-    *reinterpret_cast<bf16x4 *>(d + 2 * SP_PLANE) = q2;
-}
-
 template <int ACT>
 __global__ __launch_bounds__(256, 2) void conv_stem_p3_kernel(const StemP3Args p) {
     extern __shared__ __attribute__((aligned(16))) char smem_sp[];
-    constexpr int TWL = 4, TW = 16, RPB = 2, TM = 2, WN = 2;            // conv_p3's BN = 64 roles: waves = 2 row groups x 2 column blocks
     char *patch = smem_sp;
     float *img = reinterpret_cast<float *>(smem_sp + SP_SLAB);
 
@@ -104,9 +60,8 @@ __global__ __launch_bounds__(256, 2) void conv_stem_p3_kernel(const StemP3Args p
     const int oy0 = ty * 8, ox0 = tx * 16, n0 = nt * 64;
     const int sy0 = 2 * oy0 - 1, sx0 = 2 * ox0 - 1;                     // stem-map coordinates of the patch origin
     const int tid = threadIdx.x;
-    const int wave = tid >> 6, lane = tid & 63;
-    const int wm = wave / WN, wn = wave % WN;
-    const int fr = lane & 31, fh = lane >> 5;
+    P3Main<2, 64, 0> mp(tid);                                            // conv_p3's BN = 64 roles: waves = 2 row groups x 2 column blocks
+    const int wave = mp.wave, fr = mp.fr, fh = mp.fh;
 
     // ---- image patch -> LDS (float32, planar, rows of SP_ILD)
     {
@@ -132,23 +87,19 @@ __global__ __launch_bounds__(256, 2) void conv_stem_p3_kernel(const StemP3Args p
         }
     }
 
-    // ---- weights: the lane's 16-byte unit of a 32-row block in a (slab, plane) piece of the planes (split_bf16_kernel)
-    const unsigned unit = (unsigned)((2 * fr + (fh ^ ((fr >> 2) & 1))) * 16);
-    const int CoutP = (p.Cout + SP_COUT_PAD - 1) / SP_COUT_PAD * SP_COUT_PAD;
-    const __amdgpu_buffer_rsrc_t wr = sp_rsrc(p.wsplit, (int64_t)9 * 2 * 3 * CoutP * 32);
-    const unsigned boff = (unsigned)((n0 + wn * 32) * 32) + unit;
-    const unsigned plane_bytes = (unsigned)CoutP * 32u, slab_bytes = 3u * plane_bytes;
+    const unsigned unit = p3_b_unit(fr, fh);
+    mp.weights(p.wsplit, p.Cout, 2, n0);
 
     float keep[SP_BPW][8];                           // stem channels 16 .. 31 of the wave's pixels, until slab 0's taps are done
     {
-        // stem weights (32 rows: block 0 of planes padded to SP_COUT_PAD rows), two k-steps x three planes
-        const __amdgpu_buffer_rsrc_t w0r = sp_rsrc(p.w0, (int64_t)2 * 3 * SP_COUT_PAD * 32);
+        // stem weights (32 rows: block 0 of planes padded to P3_COUT_PAD rows), two k-steps x three planes
+        const __amdgpu_buffer_rsrc_t w0r = mydet_rsrc(p.w0, (int64_t)2 * 3 * P3_COUT_PAD * 32);
         bf16x8 wf[2][3];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
-                wf[ks][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w0r, unit, (ks * 3 + pl) * SP_COUT_PAD * 32, 0));
+                wf[ks][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w0r, unit, (ks * 3 + pl) * P3_COUT_PAD * 32, 0));
         // the lane's channels: register r of the accumulator = channel (r & 3) + 8 (r >> 2) + 4 fh
         float sc0[16], sh0[16];
 #pragma unroll
@@ -184,32 +135,31 @@ __global__ __launch_bounds__(256, 2) void conv_stem_p3_kernel(const StemP3Args p
                     float v = ib[koff[j]];
                     if (j >= 11 && fh) v = 0.0f;     // k 27 .. 31
                     __bf16 h0, h1, h2;
-                    sp_split1(v, h0, h1, h2);
+                    split3(v, h0, h1, h2);
                     pa[j >> 3][0][j & 7] = h0; pa[j >> 3][1][j & 7] = h1; pa[j >> 3][2][j & 7] = h2;
                 }
                 f32x16 acc;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-                constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};  // (pixel piece, weight piece): small products first
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                     for (int tt = 0; tt < 6; ++tt)
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks][PB[tt]], pa[ks][PA[tt]], acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks][SPLIT_PB[tt]], pa[ks][SPLIT_PA[tt]], acc, 0, 0, 0);     // (pixel piece PA, weight piece PB)
                 // folded BN + activation; a pixel outside the stem map is the second conv's padding: 0
                 const int sy = sy0 + py, sx = sx0 + px;
                 const bool inside = (unsigned)sy < (unsigned)p.Hs && (unsigned)sx < (unsigned)p.Ws;
-                const int pos = sp_pos(py, px), sig = sp_sigma(px);
+                const int pos = p3_pos<2, 0>(py, px), sig = p3_pix_sigma<2, 0>(py, px);
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    float o[4];
+                    f32x4 o;                         // four consecutive channels: quad fh of half g & 1 of slab g >> 1
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int r = 4 * g + e;
                         o[e] = inside ? mydet_act(acc[r] * sc0[r] + sh0[r], p.act0) : 0.0f;
                     }
                     if (g < 2) {
-                        if (mok) sp_store_quad(patch, pos, sig, g & 1, fh, o);
+                        if (mok) p3_store_quad<2, 0>(patch, p3_quad_off(pos, sig, g & 1, fh), o);
                     } else {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) keep[bi][(g - 2) * 4 + e] = o[e];
@@ -219,54 +169,38 @@ __global__ __launch_bounds__(256, 2) void conv_stem_p3_kernel(const StemP3Args p
         }
     }
 
-    // ---- main phase: conv_p3_kernel's K loop (S = 2, SHAPE 0, BN = 64) over the resident slab
-    const int oxl = fr & (TW - 1);
-    int apos[TM], apy[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int oyl = wm * (TM * RPB) + i * RPB + (fr >> TWL);
-        apy[i] = 2 * oyl;
-        apos[i] = apy[i] * SP_ROWLEN + oxl;
-    }
-    f32x16 acc[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    const int nch = n0 + wn * 32 + fr;               // the lane's output channel
-    const float pscl = p.scale ? p.scale[nch < p.Cout ? nch : 0] : 1.0f;
-    const float psft = p.shift ? p.shift[nch < p.Cout ? nch : 0] : 0.0f;
-
-    bf16x8 breg[3][3];                               // B fragments of three (slab, tap) steps in flight
-    auto load_b = [&](int cs, int tap, bf16x8 (&brg)[3]) {             // weights of (slab cs, tap): slab kt = tap * 2 + cs of the planes
+    // ---- main phase (p3_tile.h) over the resident slab
+    P3Main<2, 64, 0>::Regs rg;
+    mp.rows(rg, p.scale, p.shift, p.Cout, n0);
+    constexpr int TM = P3Main<2, 64, 0>::TM, ROWLEN = SPG::ROWLEN, PJ0 = SPG::PJ0, PLANE_P = SPG::PLANE, ROWB = P3_ROWB;
+    const int oxl = mp.oxl;
+    auto load_b = [&](int cs, int tap, bf16x8 (&brg)[3]) {             // conv_p3.hip's, nsl = 2
         const unsigned kt = (unsigned)(tap * 2 + cs);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-            brg[pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wr, cs < 2 ? boff : OOB,
-                                                     __builtin_amdgcn_readfirstlane(kt * slab_bytes + (unsigned)pl * plane_bytes), 0));
+            brg[pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(mp.wr, cs < 2 ? mp.boff : P3_OOB,
+                                                     __builtin_amdgcn_readfirstlane(kt * mp.slab_bytes + (unsigned)pl * mp.plane_bytes), 0));
     };
-    auto compute = [&](int tap, const bf16x8 (&bf)[3]) {
+    auto compute = [&](int tap, const bf16x8 (&bf)[3]) {                // conv_p3.hip's, S = 2, SHAPE 0
         const int kh = tap / 3, kw = tap - kh * 3;
         bf16x8 af[TM][3];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-            const int pos = apos[i] + kh * SP_ROWLEN + (kw & 1) * SP_PJ0 + (kw >> 1);
-            const int sig = ((oxl + (kw >> 1)) >> 3) & 1;
-            const char *a = patch + pos * SP_ROWB + ((fh ^ sig) * 16);
+            const int pos = rg.apos[i] + kh * ROWLEN + (kw & 1) * PJ0 + (kw >> 1);
+            const int sig = p3_sigma<0>(rg.apy[i] + kh, oxl + (kw >> 1));
+            const char *a = patch + pos * ROWB + ((fh ^ sig) * 16);
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) af[i][pl] = *reinterpret_cast<const bf16x8 *>(a + pl * SP_PLANE);
+            for (int pl = 0; pl < 3; ++pl) af[i][pl] = *reinterpret_cast<const bf16x8 *>(a + pl * PLANE_P);
         }
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};          // small piece products first
 #pragma unroll
         for (int tt = 0; tt < 6; ++tt)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[tt]], bf[PB[tt]], acc[i], 0, 0, 0);
+                rg.acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][SPLIT_PA[tt]], bf[SPLIT_PB[tt]], rg.acc[i], 0, 0, 0);
     };
-
-    load_b(0, 0, breg[0]);
-    load_b(0, 1, breg[1]);
-    load_b(0, 2, breg[2]);
+    load_b(0, 0, rg.breg[0]);
+    load_b(0, 1, rg.breg[1]);
+    load_b(0, 2, rg.breg[2]);
 #pragma unroll
     for (int cs = 0; cs < 2; ++cs) {
         if (cs == 1) {
@@ -276,11 +210,11 @@ __global__ __launch_bounds__(256, 2) void conv_stem_p3_kernel(const StemP3Args p
                 const int m = (wave + 4 * bi) * 32 + fr;
                 if (m < SP_NPIX) {
                     const int py = m / SP_PW, px = m - py * SP_PW;
-                    const int pos = sp_pos(py, px), sig = sp_sigma(px);
+                    const int pos = p3_pos<2, 0>(py, px), sig = p3_pix_sigma<2, 0>(py, px);
 #pragma unroll
                     for (int g = 0; g < 2; ++g) {
-                        const float o[4] = {keep[bi][4 * g], keep[bi][4 * g + 1], keep[bi][4 * g + 2], keep[bi][4 * g + 3]};
-                        sp_store_quad(patch, pos, sig, g, fh, o);
+                        const f32x4 o = {keep[bi][4 * g], keep[bi][4 * g + 1], keep[bi][4 * g + 2], keep[bi][4 * g + 3]};
+                        p3_store_quad<2, 0>(patch, p3_quad_off(pos, sig, g, fh), o);
                     }
                 }
             }
@@ -288,31 +222,12 @@ __global__ __launch_bounds__(256, 2) void conv_stem_p3_kernel(const StemP3Args p
         mydet_lds_barrier();
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
-            compute(tap, breg[tap % 3]);
+            compute(tap, rg.breg[tap % 3]);
             const int t3 = tap + 3;
-            load_b(cs + t3 / 9, t3 % 9, breg[tap % 3]);
+            load_b(cs + t3 / 9, t3 % 9, rg.breg[tap % 3]);
         }
     }
-
-    // ---- epilogue (conv_p3_kernel's): lane = output channel, register = output pixel of the 2-row x 16-column block
-    const int64_t opix = (int64_t)p.Ho * p.Wo;       // (descriptors per image: byte offsets stay inside one image's output)
-    const __amdgpu_buffer_rsrc_t yr = sp_rsrc(p.y + b * opix * p.ldy, opix * p.ldy * 4);
-    const unsigned ldy4 = (unsigned)p.ldy * 4u;
-    const bool nok = nch < p.Cout;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int oyb = oy0 + wm * (TM * RPB) + i * RPB;         // first output row of the block
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int dr = (r & 3) + 8 * (r >> 2) + 4 * fh;
-            const int oy = oyb + (dr >> TWL), ox = ox0 + (dr & (TW - 1));
-            const bool ok = nok && oy < p.Ho && ox < p.Wo;
-            const unsigned off = ok ? (unsigned)(oy * p.Wo + ox) * ldy4 + (unsigned)nch * 4u : OOB;
-            float v = acc[i][r] * pscl + psft;
-            if (ACT == MYDET_ACT_LEAKY) v = v > 0.0f ? v : v * 0.1f;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yr, off, 0, 0);
-        }
-    }
+    mp.template store<ACT, false>(rg, p.y, p.ldy, nullptr, 0, p.Ho, p.Wo, p.Cout, b, oy0, ox0);
 }
 
 template <int ACT>
@@ -345,8 +260,9 @@ extern "C" int mydet_conv_stem_p3_f32(const float *x, int64_t sxb, int64_t sxc, 
     p.Ho = (Hs - 1) / 2 + 1; p.Wo = (Ws - 1) / 2 + 1;
     // 32-bit byte offsets inside the kernel, relative to the workgroup's image: one image's output stays below 2 GB
     if ((int64_t)p.Ho * p.Wo * ldy * 4 > 0x7FFFFFF0ll) return MYDET_E_UNSUPP;
-    p.tx_n = (p.Wo + 15) / 16; p.ntn = Cout / 64;
-    p.tiles_img = p.tx_n * ((p.Ho + 7) / 8);
+    const P3Plan pl = mydet_p3_plan(p.Ho, p.Wo, Cout, 2, false);       // ragged 8 x 16 tiles whatever the width: no strip tiles
+    p.tx_n = pl.tx_n; p.ntn = Cout / 64;
+    p.tiles_img = pl.tiles_img;
     const int64_t nblk = (int64_t)B * p.tiles_img * p.ntn;
     if (nblk > 0x7FFFFFFF || nblk <= 0) return MYDET_E_UNSUPP;
     p.nblk = (int)nblk;

@@ -59,15 +59,6 @@ __device__ __forceinline__ int sk_begin(int w, const WinoArgs &p) { return w * p
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float *base, int64_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const int64_t capped = bytes > 0x7FFFFFF0ll ? 0x7FFFFFF0ll : bytes;
-    const int n = __builtin_amdgcn_readfirstlane((int)capped);
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, n, 0x00020000);
-}
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // y = act(Y*scale + shift) + residual for one item: lane = tile m0 + 32*wt + 16*blk + fr, its four components =
@@ -83,9 +74,9 @@ __device__ __forceinline__ void wino_epilogue(const WinoArgs &p, const f32x4 (&o
     const f32x4 scl = p.scale ? *reinterpret_cast<const f32x4 *>(p.scale + nc) : f32x4{1.f, 1.f, 1.f, 1.f};
     const f32x4 sft = p.shift ? *reinterpret_cast<const f32x4 *>(p.shift + nc) : f32x4{0.f, 0.f, 0.f, 0.f};
     const int64_t oimg = (int64_t)p.H * p.W;
-    const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y + b0 * oimg * p.ldy, (p.B - b0) * oimg * p.ldy * 4);
+    const __amdgpu_buffer_rsrc_t yr = mydet_rsrc(p.y + b0 * oimg * p.ldy, (p.B - b0) * oimg * p.ldy * 4);
     const __amdgpu_buffer_rsrc_t rr =
-        make_rsrc(RES ? p.res + b0 * oimg * p.ldr : p.y, (p.B - b0) * oimg * (RES ? p.ldr : p.ldy) * 4);
+        mydet_rsrc(RES ? p.res + b0 * oimg * p.ldr : p.y, (p.B - b0) * oimg * (RES ? p.ldr : p.ldy) * 4);
     unsigned yo[2][4];                                 // byte offsets of the 2 x 4 output pixels (OOB when masked)
     f32x4 rv[2][4];
 #pragma unroll
@@ -167,7 +158,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_wino_kernel(con
     // the NEXT piece before the epilogue of the current one, so that piece's first slab is already in flight.
     int item, k_lo, k_hi, m0, n0, b0;
     __amdgpu_buffer_rsrc_t xr;
-    const __amdgpu_buffer_rsrc_t ur = make_rsrc(p.u, (int64_t)p.Cin * 16 * p.CoutP * 4);
+    const __amdgpu_buffer_rsrc_t ur = mydet_rsrc(p.u, (int64_t)p.Cin * 16 * p.CoutP * 4);
     unsigned off[16], uoff;
     auto setup = [&]() -> bool {                       // next piece of this workgroup, false when there is none
         if (round < rounds) {
@@ -189,7 +180,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_wino_kernel(con
         // staging: every thread brings one channel of one tile's patch (16 dwords) and NU float4 of weights; a wave
         // covers 8 tiles x the 8 channels of the slab: one 32-byte run per patch pixel and load instruction
         const int64_t img = (int64_t)p.H * p.W * p.ldx;
-        xr = make_rsrc(p.x + b0 * img, (p.B - b0) * img * 4);
+        xr = mydet_rsrc(p.x + b0 * img, (p.B - b0) * img * 4);
         const int mt = m0 + slot;
         const int mm = mt < p.MT ? mt : p.MT - 1;
         const int b = mm / tpi, r = mm - b * tpi, ty = r / p.TW, tx = r - ty * p.TW;
@@ -376,9 +367,9 @@ __global__ __launch_bounds__(64 * NW) void conv_wino_fixup_kernel(const WinoArgs
     const f32x4 scl = p.scale ? *reinterpret_cast<const f32x4 *>(p.scale + nc) : f32x4{1.f, 1.f, 1.f, 1.f};
     const f32x4 sft = p.shift ? *reinterpret_cast<const f32x4 *>(p.shift + nc) : f32x4{0.f, 0.f, 0.f, 0.f};
     const int64_t oimg = (int64_t)p.H * p.W;
-    const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y + b0 * oimg * p.ldy, (p.B - b0) * oimg * p.ldy * 4);
+    const __amdgpu_buffer_rsrc_t yr = mydet_rsrc(p.y + b0 * oimg * p.ldy, (p.B - b0) * oimg * p.ldy * 4);
     const __amdgpu_buffer_rsrc_t rr =
-        make_rsrc(RES ? p.res + b0 * oimg * p.ldr : p.y, (p.B - b0) * oimg * (RES ? p.ldr : p.ldy) * 4);
+        mydet_rsrc(RES ? p.res + b0 * oimg * p.ldr : p.y, (p.B - b0) * oimg * (RES ? p.ldr : p.ldy) * 4);
     unsigned yo;
     f32x4 rv = {0.f, 0.f, 0.f, 0.f};
     {

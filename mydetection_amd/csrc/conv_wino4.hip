@@ -70,15 +70,6 @@ struct W4Args {
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const float *base, int64_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const int64_t capped = bytes > 0x7FFFFFF0ll ? 0x7FFFFFF0ll : bytes;
-    const int n = __builtin_amdgcn_readfirstlane((int)capped);
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, n, 0x00020000);
-}
-
 // Bt x (x = six values): all six rows, or only rows 0-2 / 3-5 (the column pass of a thread that owns half the rows)
 #define W4_BT_LO(o, x0, x1, x2, x3, x4, x5)               \
     {                                                     \
@@ -121,7 +112,7 @@ __global__ __launch_bounds__(256, 2) void wino4_input_kernel(const W4Args p) {
     // the range check sees the voffset only, and a negative one would read as out of range (those addresses are never
     // touched: row -1 and column -1 are masked to OOB below)
     const int64_t lead = (int64_t)(p.W + 1) * p.ldx;
-    const __amdgpu_buffer_rsrc_t xr = rsrc(p.x + b0 * img - lead, ((p.B - b0) * img + lead) * 4);
+    const __amdgpu_buffer_rsrc_t xr = mydet_rsrc(p.x + b0 * img - lead, ((p.B - b0) * img + lead) * 4);
     const int mm = mt < p.MT ? mt : p.MT - 1;
     const int b = mm / tpi, r = mm - b * tpi, ty = r / p.TW, tx = r - ty * p.TW;
     const int iy0 = 4 * ty - 1, ix0 = 4 * tx - 1;
@@ -207,14 +198,14 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino4_kernel(const W4Args p) 
     // pieces (one per wave instruction), wave w copies pieces w, w + 4, ... of each operand.
     //   U: piece = two runs of 32 float4 (the block's channels) 16*CoutP bytes apart (layout of wino4_weights_kernel)
     //   V: the stage is one contiguous 18 KB run of the workspace
-    const __amdgpu_buffer_rsrc_t ur = rsrc(p.u, (int64_t)p.Cin * 36 * p.CoutP * 4);
+    const __amdgpu_buffer_rsrc_t ur = mydet_rsrc(p.u, (int64_t)p.Cin * 36 * p.CoutP * 4);
     const unsigned urun = (unsigned)p.CoutP * 16u;
     const unsigned uoff = (unsigned)((n0 + (lane & 31)) * 16) + (lane >> 5) * urun;
 #ifdef MYDET_DIAG
     const int dmode = p.dbg & 7;
-    const __amdgpu_buffer_rsrc_t vr = rsrc(p.v + (int64_t)(dmode == 1 ? 0 : mb) * nk * (V_BYTES / 4), (int64_t)nk * V_BYTES);
+    const __amdgpu_buffer_rsrc_t vr = mydet_rsrc(p.v + (int64_t)(dmode == 1 ? 0 : mb) * nk * (V_BYTES / 4), (int64_t)nk * V_BYTES);
 #else
-    const __amdgpu_buffer_rsrc_t vr = rsrc(p.v + (int64_t)mb * nk * (V_BYTES / 4), (int64_t)nk * V_BYTES);
+    const __amdgpu_buffer_rsrc_t vr = mydet_rsrc(p.v + (int64_t)mb * nk * (V_BYTES / 4), (int64_t)nk * V_BYTES);
 #endif
     const unsigned voff = (unsigned)(lane * 16);
     auto load_stage = [&](int kt) __attribute__((always_inline)) {
@@ -248,8 +239,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino4_kernel(const W4Args p) 
     const int n = n0 + wc * 16 + fq * 4;
     const bool nok = n < p.Cout;                       // Cout % 4 == 0
     const int64_t oimg = (int64_t)p.H * p.W;
-    const __amdgpu_buffer_rsrc_t yr = rsrc(p.y + b0 * oimg * p.ldy, (p.B - b0) * oimg * p.ldy * 4);
-    const __amdgpu_buffer_rsrc_t rr = rsrc(RES ? p.res + b0 * oimg * p.ldr : p.y, (p.B - b0) * oimg * (RES ? p.ldr : p.ldy) * 4);
+    const __amdgpu_buffer_rsrc_t yr = mydet_rsrc(p.y + b0 * oimg * p.ldy, (p.B - b0) * oimg * p.ldy * 4);
+    const __amdgpu_buffer_rsrc_t rr = mydet_rsrc(RES ? p.res + b0 * oimg * p.ldr : p.y, (p.B - b0) * oimg * (RES ? p.ldr : p.ldy) * 4);
     unsigned ybase, rbase;
     bool orow[4], ocol[4];
     {
@@ -388,8 +379,8 @@ __global__ __launch_bounds__(64 * NW) void wino4_fixup_kernel(const W4Args p) {
     const f32x4 scl = p.scale ? *reinterpret_cast<const f32x4 *>(p.scale + nc) : f32x4{1.f, 1.f, 1.f, 1.f};
     const f32x4 sft = p.shift ? *reinterpret_cast<const f32x4 *>(p.shift + nc) : f32x4{0.f, 0.f, 0.f, 0.f};
     const int64_t oimg = (int64_t)p.H * p.W;
-    const __amdgpu_buffer_rsrc_t yr = rsrc(p.y + b0 * oimg * p.ldy, (p.B - b0) * oimg * p.ldy * 4);
-    const __amdgpu_buffer_rsrc_t rr = rsrc(RES ? p.res + b0 * oimg * p.ldr : p.y, (p.B - b0) * oimg * (RES ? p.ldr : p.ldy) * 4);
+    const __amdgpu_buffer_rsrc_t yr = mydet_rsrc(p.y + b0 * oimg * p.ldy, (p.B - b0) * oimg * p.ldy * 4);
+    const __amdgpu_buffer_rsrc_t rr = mydet_rsrc(RES ? p.res + b0 * oimg * p.ldr : p.y, (p.B - b0) * oimg * (RES ? p.ldr : p.ldy) * 4);
     const int mt = m0 + wt * 16 + fr;
     const int mm = mt < p.MT ? mt : p.MT - 1;
     const int b = mm / tpi, r = mm - b * tpi, ty = r / p.TW, tx = r - ty * p.TW;

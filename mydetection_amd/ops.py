@@ -6,7 +6,9 @@ module inputs/outputs have the reference's shapes while kernels see NHWC.
 Every function launches hand-written HIP kernels; no arithmetic falls back to ATen (a
 input in a foreign layout is re-laid out with one tensor copy before the launch).
 """
+import collections
 import ctypes
+import functools
 import os
 import threading
 
@@ -329,28 +331,33 @@ P3_MIN_WGS = int(os.environ.get('MYDET_P3_MIN_WGS', '512'))             # a full
                                                                         # stride-2 layer @64->32 (1 024 workgroups) joins: 2 601-2 622 vs 2 597-2 601 images/s
 P3_S1_MAX_CIN = int(os.environ.get('MYDET_P3_S1_MAX_CIN', '32'))      # stride-1 layers up to this many input channels
 # tiles must be mostly real pixels: 0.75 admits the 40-wide (13 tiles for 1 600 pixels: 0.96) and 20-wide (4 for 400: 0.78) maps of Darknet-53 at
-# 640^2 with their strip tiles, not a ragged 8 x 16 column on a 20-wide map (0.52).  MYDET_P3_STRIP=0: no strip tiles (the library reads it too)
+# 640^2 with their strip tiles, not a ragged 8 x 16 column on a 20-wide map (0.52)
 P3_MIN_FILL = float(os.environ.get('MYDET_P3_MIN_FILL', '0.75'))
-P3_STRIP = os.environ.get('MYDET_P3_STRIP', '1') != '0'
+
+P3Plan = collections.namedtuple('P3Plan', 'bn strip tx_n ty_n main_tiles tiles_img ntn lds')
+
+
+@functools.lru_cache(maxsize=None)
+def p3_plan(Ho, Wo, Cout, stride):
+    """The tile plan mydet_conv3x3_p3_f32 launches for an Ho x Wo x Cout output map (mydet_conv3x3_p3_plan: the launcher's own function,
+    csrc/conv_p3.hip, MYDET_P3_FORM / MYDET_P3_STRIP included): 8 x 16 tiles; at stride 2 a remainder of 8 / 4 columns goes to 16 x 8 /
+    32 x 4 strip tiles (strip 1 / 2), any other remainder to a ragged column.  Memoised: the eager conv2d path asks per layer and call."""
+    out = (ctypes.c_int32 * 8)()
+    _lib.check(_lib.lib().mydet_conv3x3_p3_plan(Ho, Wo, Cout, stride, out), 'mydet_conv3x3_p3_plan')
+    return P3Plan(*out)
 
 
 def p3_tiles(Ho, Wo, stride):
-    """Workgroup tiles of 128 output pixels per image and channel tile that mydet_conv3x3_p3_f32 launches (csrc/conv_p3.hip): 8 x 16
-    tiles; at stride 2 a remainder of 8 / 4 columns goes to 16 x 8 / 32 x 4 strip tiles, any other remainder to a ragged column."""
-    rem = Wo % 16
-    strip = stride == 2 and rem in (4, 8) and P3_STRIP
-    tiles = (Wo // 16 if strip else -(-Wo // 16)) * -(-Ho // 8)
-    if strip:
-        tiles += -(-Ho // 16) if rem == 8 else -(-Ho // 32)
-    return tiles
+    """Workgroup tiles of 128 output pixels per image and channel tile that mydet_conv3x3_p3_f32 launches."""
+    return p3_plan(Ho, Wo, 64, stride).tiles_img
 
 
 def p3_takes(B, Ho, Wo, Cin, Cout, k, stride, pad):
     """True when conv2d(..., b3=) hands the layer to conv3x3_p3."""
     if not (CONV_P3 and SPLIT_BF16) or k != 3 or stride not in (1, 2) or tuple(pad) != (1, 1, 1, 1) or Cin % 16:
         return False
-    tiles = p3_tiles(Ho, Wo, stride)
-    if B * tiles * -(-Cout // (128 if Cout > 64 else 64)) < P3_MIN_WGS or Ho * Wo < P3_MIN_FILL * 128 * tiles:
+    plan = p3_plan(Ho, Wo, Cout, stride)
+    if B * plan.tiles_img * plan.ntn < P3_MIN_WGS or Ho * Wo < P3_MIN_FILL * 128 * plan.tiles_img:
         return False
     return stride == 2 or Cin <= P3_S1_MAX_CIN
 
@@ -535,7 +542,7 @@ def stem_p3_takes(B, H, W, Cout, pad0):
     Ho, Wo = (Hs - 1) // 2 + 1, (Ws - 1) // 2 + 1
     if not STEM_P3 or Cout % 64 or not p3_takes(B, Ho, Wo, 32, Cout, 3, 2, (1, 1, 1, 1)):
         return False
-    return not (P3_STRIP and Wo % 16 in (4, 8))
+    return p3_plan(Ho, Wo, Cout, 2).strip == 0
 
 
 def stem_p3_weights(w_ohwi):

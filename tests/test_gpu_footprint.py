@@ -25,7 +25,7 @@ What cannot be proven from outside the library, a limit of these tests: the tile
 no host-side rule -- the float32 implicit GEMM's 128 x 128 / 128 x 64 / 64 x 64 x 32 / BN = 32 tiles and its XCD-remapped grid, the
 split-bf16 kernel's 64-row vs 128-row gated tiles.  Their cases take the shapes that the case lists of tests/test_gpu_kernels.py name
 for the form, and assert what is observable: the family's span, and for EVERY case whether the launch left partial tiles in the
-split-K workspace (`kcut`).  Where a host-side rule exists it is asserted: ops.b3_takes, ops.p3_tiles (tile count, strip form,
+split-K workspace (`kcut`).  Where a host-side rule exists it is asserted: ops.b3_takes, ops.p3_plan (the launcher's own plan: tile count, strip form,
 channel tile), ops.wino4_items and the launcher's own mydet_wino4_tail_plan.
 
 Every entry of the issue's table takes foreign pointers and strides, so none is left out.  The share buffer of the in-launch
@@ -258,15 +258,15 @@ def test_footprint_conv_split_bf16(dev, case, monkeypatch):
     dict(B=2, Cin=16, Cout=40, s=2, H=70, W=8, act=1, kcut=False, bn=64, strip='32x4', tiles=2),                           # 4 columns only: 32 x 4 strips over 35 rows
 ])
 def test_footprint_conv_p3(dev, case):
-    """tiles: the 128-pixel tiles per image, asserted against ops.p3_tiles -- the dispatch rule's Python restatement of the C launcher's
-    tiling (8 x 16 tiles; at stride 2 a remainder of 8 / 4 columns as 16 x 8 / 32 x 4 strip tiles), the only host-side statement of it:
-    a mirror, not the launcher itself.  bn / strip only label the form the shape is meant to reach (channel tile 128 from 65 output
-    channels up; strip form of the remainder columns); the library offers nothing to check them against."""
+    """bn / strip / tiles: the channel tile (128 from 65 output channels up), the strip form of the remainder columns and the 128-pixel tiles
+    per image the shape is meant to reach, asserted against the launcher's own plan (mydet_conv3x3_p3_plan through ops.p3_plan: 8 x 16
+    tiles; at stride 2 a remainder of 8 / 4 columns as 16 x 8 / 32 x 4 strip tiles), which is also what ops.p3_tiles returns."""
     from mydetection_amd import ops
     case = dict(case, k=3)
     bn, strip, tiles = case.pop('bn'), case.pop('strip'), case.pop('tiles')
     Ho, Wo = (case['H'] - 1) // case['s'] + 1, (case['W'] - 1) // case['s'] + 1
-    assert ops.P3_STRIP and bn in (64, 128) and strip in (None, '16x8', '32x4')
+    plan = ops.p3_plan(Ho, Wo, case['Cout'], case['s'])
+    assert (plan.bn, plan.strip, plan.tiles_img) == (bn, {None: 0, '16x8': 1, '32x4': 2}[strip], tiles)
     assert ops.p3_tiles(Ho, Wo, case['s']) == tiles
     _conv_footprint(dev, 'p3', case)
 

@@ -300,7 +300,7 @@ def test_graph_cache_policy_and_workspace_refs():
 
 
 def test_conv_p3_patch_layout_is_conflict_free():
-    """The LDS layout of conv_p3_kernel's input patch (csrc/conv_p3.hip: P3Geom, the position / sigma formulas in its header) against
+    """The LDS layout of conv_p3_kernel's input patch (csrc/p3_tile.h: P3Shape, the position / sigma formulas in its header) against
     the ds_read_b128 lane groups and bank rule of MI355X_MICROARCH.md, replayed on the host (tools/r06/p3_layout_search.py): every
     A-fragment read of every tap, row block and lane group touches sixteen distinct 16-byte slots -- for both strides.  (On the GPU:
     SQ_LDS_BANK_CONFLICT = 0, profiles/r06_conv_p3.txt.)  The constants are read from the kernel source so that the two cannot drift."""
@@ -309,9 +309,9 @@ def test_conv_p3_patch_layout_is_conflict_free():
     spec = importlib.util.spec_from_file_location('p3_layout_search', os.path.join(ROOT, 'tools', 'r06', 'p3_layout_search.py'))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    src = open(os.path.join(ROOT, 'mydetection_amd', 'csrc', 'conv_p3.hip')).read()
+    src = open(os.path.join(ROOT, 'mydetection_amd', 'csrc', 'p3_tile.h')).read()
     geo = {(int(m.group(1)), int(m.group(2))): tuple(int(v) for v in m.group(3, 4, 5, 6, 7))
-           for m in re.finditer(r'P3Geom<(\d), (\d)> \{ static constexpr int TH = (\d+), TWL = (\d+), PH = (\d+), ROWLEN = (\d+), PJ0 = (\d+); \}', src)}
+           for m in re.finditer(r'P3Shape<(\d), (\d)> \{ static constexpr int TH = (\d+), TWL = (\d+), PH = (\d+), ROWLEN = (\d+), PJ0 = (\d+); \}', src)}
     # (stride, shape) -> (tile rows, log2 tile columns, patch rows, positions per patch row, positions of the even columns)
     assert geo == {(2, 0): (8, 4, 17, 36, 17), (1, 0): (8, 4, 10, 24, 0), (2, 1): (16, 3, 33, 20, 9), (2, 2): (32, 2, 65, 9, 5)}, geo
     assert 'return SHAPE == 0 ? (j >> 3) & 1 : ((j >> 3) + (py >> 1)) & 1;' in src            # the swizzle bit, staging and fragment reads alike
@@ -749,6 +749,43 @@ def test_conv_p3_dispatch_rule():
     # only 3x3, pad 1, stride 1 | 2, Cin % 16 == 0
     assert not ops.p3_takes(32, 320, 320, 32, 64, 1, 1, (0, 0, 0, 0)) and not ops.p3_takes(32, 320, 320, 32, 64, 3, 2, (0, 0, 1, 1))
     assert not ops.p3_takes(32, 320, 320, 24, 64, 3, 2, pad) and not ops.p3_takes(32, 320, 320, 32, 64, 3, 3, pad)
+
+
+def test_conv_p3_plan_covers_every_pixel_once():
+    """mydet_conv3x3_p3_plan (host only: the function the mydet_conv3x3_p3_f32 launcher fills its arguments from).  The tile rectangles
+    rebuilt from its fields -- tx_n x ty_n tiles of 8 x 16 pixels, then 16 x 8 (strip 1) or 32 x 4 (strip 2) tiles from column 16 * tx_n
+    down the map -- cover every output pixel exactly once, tiles_img counts them, the channel tile is 128 from 65 output channels up, and
+    the LDS bytes are 3 planes x PH x ROWLEN positions x 32 bytes of the larger patch the form holds (csrc/p3_tile.h: P3Shape)."""
+    import numpy as np
+    from mydetection_amd import _lib
+    lib = _lib.lib()
+    out = (ctypes.c_int32 * 8)()
+    patch = {(2, 0): 17 * 36, (1, 0): 10 * 24, (2, 1): 33 * 20, (2, 2): 65 * 9}                 # PH * ROWLEN of (stride, shape)
+    strips = set()
+    for stride in (1, 2):
+        for Cout in (40, 64, 65, 192):
+            for Ho in range(1, 71):
+                for Wo in range(1, 71):
+                    assert lib.mydet_conv3x3_p3_plan(Ho, Wo, Cout, stride, out) == 0
+                    bn, strip, tx_n, ty_n, main_tiles, tiles_img, ntn, lds = out
+                    assert bn == (128 if Cout > 64 else 64) and ntn == -(-Cout // bn)
+                    assert strip == ({8: 1, 4: 2}.get(Wo % 16, 0) if stride == 2 else 0), (Ho, Wo, stride)
+                    strips.add((stride, strip))
+                    rects = [(8 * ty, 16 * tx, 8, 16) for ty in range(ty_n) for tx in range(tx_n)]
+                    assert main_tiles == len(rects)
+                    if strip:
+                        th, tw = ((16, 8), (32, 4))[strip - 1]
+                        rects += [(oy, 16 * tx_n, th, tw) for oy in range(0, Ho, th)]
+                    assert tiles_img == len(rects)
+                    cover = np.zeros((Ho, Wo), np.int32)
+                    for oy, ox, th, tw in rects:
+                        assert oy < Ho and ox < Wo                                    # no tile wholly outside the map
+                        cover[oy:oy + th, ox:ox + tw] += 1
+                    assert (cover == 1).all(), (Ho, Wo, stride)
+                    assert lds == 3 * 32 * max(patch[(stride, 0)], patch[(stride, strip)]) <= 65536
+    assert strips == {(1, 0), (2, 0), (2, 1), (2, 2)}
+    assert lib.mydet_conv3x3_p3_plan(8, 8, 64, 3, out) == -2 and lib.mydet_conv3x3_p3_plan(0, 8, 64, 2, out) == -1
+    assert lib.mydet_conv3x3_p3_plan(8, 8, 64, 2, None) == -1
 
 
 def test_split_bf16_dispatch_rule():

@@ -51,29 +51,48 @@ def test_symbol_in_header_and_library():
                                              1, 1, 1, 16, 32, 2, null) == -1
 
 
-def test_kernel_resources_allow_two_workgroups_per_cu():
+def _kernel_resources(substr):
+    """{kernel name: registers, scratch and static LDS} of the built library's kernels whose name holds `substr` (code-object metadata)."""
     from mydetection_amd import _lib
-    if not os.path.exists('/opt/rocm/lib/llvm/bin/llvm-readelf'):
-        pytest.skip('no llvm-readelf on this machine')
     spec = importlib.util.spec_from_file_location('check_store_hazard', os.path.join(ROOT, 'tools', 'check_store_hazard.py'))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     found = {}
     for _, text in mod.code_objects(_lib.LIB_PATH, notes=True):
-        if 'conv_stem_p3_kernel' not in text:
+        if substr not in text:
             continue
         for block in re.split(r'\n\s*-?\s*\.agpr_count:', text)[1:]:      # one block per kernel: .agpr_count is its first key
             name = re.findall(r'\n\s*\.name:\s+(\S+)', block)
-            name = [n for n in name if 'conv_stem_p3_kernel' in n]
+            name = [n for n in name if substr in n]
             if not name:
                 continue
             field = {k: int(re.search(r'\.' + k + r':\s+(\d+)', block).group(1))
                      for k in ('vgpr_count', 'private_segment_fixed_size', 'group_segment_fixed_size')}
             field['agpr_count'] = int(re.match(r'\s*(\d+)', block).group(1))
             found[name[0]] = field
+    return found
+
+
+def test_kernel_resources_allow_two_workgroups_per_cu():
+    import ctypes as ct
+    from mydetection_amd import _lib
+    if not os.path.exists('/opt/rocm/lib/llvm/bin/llvm-readelf'):
+        pytest.skip('no llvm-readelf on this machine')
+    found = _kernel_resources('conv_stem_p3_kernel')
     assert len(found) == 2, found                                       # act NONE and LEAKY
     lds = _lib.lib().mydet_conv_stem_p3_lds_bytes()
     for name, f in found.items():
         assert f['private_segment_fixed_size'] == 0, (name, f)          # no spills
         assert f['vgpr_count'] <= VGPRS_PER_SIMD_LANE // 2, (name, f)   # (vgpr_count includes the accumulation registers) two waves per SIMD
         assert 2 * (f['group_segment_fixed_size'] + lds) <= LDS_PER_CU, (name, f)
+    # conv_p3_kernel<S, BN, STRIP, ACT, RES>: stride 1 x {64, 128} x 4 epilogues + stride 2 x {64, 128} x 3 strip forms x 4 epilogues
+    found = _kernel_resources('conv_p3_kernel')
+    assert len(found) == 32, sorted(found)
+    out = (ct.c_int32 * 8)()
+    for name, f in found.items():
+        S, BN, STRIP = (int(v) for v in re.search(r'conv_p3_kernelILi(\d+)ELi(\d+)ELi(\d+)E', name).groups())
+        Wo = 16 + {0: 0, 1: 8, 2: 4}[STRIP]                             # a width that takes the form
+        assert _lib.lib().mydet_conv3x3_p3_plan(16, Wo, BN, S, out) == 0 and (out[0], out[1]) == (BN, STRIP), (name, list(out))
+        assert f['private_segment_fixed_size'] == 0, (name, f)
+        assert f['vgpr_count'] <= VGPRS_PER_SIMD_LANE // 2, (name, f)
+        assert 2 * (f['group_segment_fixed_size'] + out[7]) <= LDS_PER_CU, (name, f)
