@@ -650,6 +650,51 @@ int mydet_nv12_to_input_f32(const unsigned char *y, int64_t y_img_bytes, int64_t
                             const int32_t *bounds_y, const int32_t *ky, int ksy,
                             int norm, const float *mean3, const float *std3, void *stream);
 
+/* The 4:2:0 family: one source descriptor for every layout a decoder gives.  Per frame a Y plane of H rows of W samples and
+ * chroma at half resolution, ceil(H/2) rows for ceil(W/2) pixel pairs; odd H and W are legal for every layout.
+ *     layout            bytes/sample  chroma                                        sample -> 8 bit
+ *     MYDET_YUV420_NV12      1        plane[1]: (U, V) pairs, plane[2] NULL         as is
+ *     MYDET_YUV420_NV21      1        plane[1]: (V, U) pairs, plane[2] NULL         as is
+ *     MYDET_YUV420_I420      1        plane[1]: U, plane[2]: V, ceil(W/2) samples   as is
+ *     MYDET_YUV420_P010      2, LE    plane[1]: (U, V) pairs, plane[2] NULL         v10 = word >> 6   (low six bits ignored)
+ *     MYDET_YUV420_I010      2, LE    plane[1]: U, plane[2]: V                      v10 = word & 1023 (high six bits ignored)
+ * YV12 is I420 with plane[1] and plane[2] exchanged by the caller.  A 10-bit sample becomes 8 bits by
+ *     s8 = min(255, (v10 + 2) >> 2)                       for Y, U and V alike
+ * (limited-range 64 / 512 / 940 become 16 / 128 / 235; the clamp is reached from v10 >= 1022).  From there the conversion
+ * is the NV12 one above, unchanged: the same formula, the same four (matrix, full_range) rows of the one table, chroma
+ * nearest-neighbour at (y >> 1, x >> 1).  So every layout gives the bits NV12 gives for the same 8-bit samples.
+ *
+ * Frame b of plane i is at plane[i] + b*img_bytes[i], its rows row_bytes[i] apart.  MYDET_E_BADARG, with nothing
+ * launched: an unknown layout, matrix or range; a null src or plane[0] or plane[1]; plane[2] non-null for a semi-planar
+ * layout or null for a planar one; a pitch below the row's bytes (Y: W*bps; interleaved chroma: 2*ceil(W/2)*bps; a planar
+ * chroma plane: ceil(W/2)*bps); a negative frame stride; non-positive sizes; for the two 16-bit layouts any odd address,
+ * pitch or frame stride.  `reserved` is ignored.  The kernels read a plane with wide loads when its address, pitch and
+ * frame stride are multiples of: NV12 / NV21 4; I420 4 (Y), 2 (U, V); P010 8; I010 8 (Y), 4 (U, V) -- and sample by sample
+ * otherwise, with the same result.  No reference counterpart. */
+#define MYDET_YUV420_NV12 0
+#define MYDET_YUV420_NV21 1
+#define MYDET_YUV420_I420 2
+#define MYDET_YUV420_P010 3
+#define MYDET_YUV420_I010 4
+typedef struct mydet_yuv420_src {
+    const void *plane[3];            /* Y; interleaved chroma or U; V or NULL */
+    int64_t img_bytes[3], row_bytes[3];
+    int layout, matrix, full_range, reserved;
+} mydet_yuv420_src;
+
+/* mydet_yuv420_to_rgb_u8: mydet_nv12_to_rgb_u8 for any layout (dst as there). */
+int mydet_yuv420_to_rgb_u8(const mydet_yuv420_src *src, int B, int H, int W,
+                           unsigned char *dst, int64_t dst_img_bytes, int64_t dst_row_bytes, void *stream);
+
+/* mydet_yuv420_to_input_f32: mydet_nv12_to_input_f32 for any layout, in ONE launch: the bits mydet_frames_to_input_f32
+ * writes for the RGB frames mydet_yuv420_to_rgb_u8 gives.  Geometry, tables, norm, mean3/std3, their checks and
+ * MYDET_FRAMES_MAX_TAPS as there.  The two mydet_nv12_* entry points are this pair with layout MYDET_YUV420_NV12. */
+int mydet_yuv420_to_input_f32(const mydet_yuv420_src *src, int B, int H, int W,
+                              float *out, int Hp, int Wp, int oh, int ow, int top, int left,
+                              const int32_t *bounds_x, const int32_t *kx, int ksx,
+                              const int32_t *bounds_y, const int32_t *ky, int ksy,
+                              int norm, const float *mean3, const float *std3, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,10 @@ SIGNATURES = {
     'mydet_nv12_to_input_f32': [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int,
                                 c_ptr, c_int, c_int, c_int, c_int, c_int, c_int,
                                 c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
+    'mydet_yuv420_to_rgb_u8': [c_ptr, c_int, c_int, c_int, c_ptr, c_i64, c_i64, c_ptr],
+    'mydet_yuv420_to_input_f32': [c_ptr, c_int, c_int, c_int,
+                                  c_ptr, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_cxcywh_to_x1y1x2y2_f32': [c_ptr, c_ptr, c_i64, c_int, c_ptr],
     'mydet_bboxes_to_original_f32': [c_ptr, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr],
 }
@@ -146,6 +150,17 @@ class LrTbLevel(ctypes.Structure):
 LR_TB_MAX_LEVELS = 8                # MYDET_LR_TB_MAX_LEVELS of include/mydet.h
 LR_TB_MAX_C = 128                   # MYDET_LR_TB_MAX_C
 FRAMES_MAX_TAPS = 17                # MYDET_FRAMES_MAX_TAPS: filter taps per axis mydet_frames_to_input_f32 takes
+
+
+
+class Yuv420Src(ctypes.Structure):
+    """mydet_yuv420_src (include/mydet.h)."""
+    _fields_ = [('plane', c_ptr * 3), ('img_bytes', c_i64 * 3), ('row_bytes', c_i64 * 3), ('layout', c_int), ('matrix', c_int),
+                ('full_range', c_int), ('reserved', c_int)]
+
+
+# MYDET_YUV420_* of include/mydet.h
+YUV420_NV12, YUV420_NV21, YUV420_I420, YUV420_P010, YUV420_I010 = range(5)
 
 _lib = None
 

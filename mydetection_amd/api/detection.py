@@ -411,6 +411,94 @@ class Detector():
         """COCO-style rows of NV12 frames (see predict_frames_nv12): the counterpart of frames_to_json."""
         return self._json_of_records(self._nv12_records(y, uv, matrix, full_range, **kwargs), img_ids, eval_type, catIdx2id)
 
+    @staticmethod
+    def _yuv_planes(planes, layout, device=None):
+        """4:2:0 frames of `layout` (ops.YUV420_LAYOUTS) as the tensors ops.yuv420_to_input takes: [y [B,H,W], uv
+        [B,ceil(H/2),ceil(W/2),2]] or [y, u, v] with chroma planes [B,ceil(H/2),ceil(W/2)] ('yv12': y, v, u).  planes: a tuple
+        of torch tensors or numpy arrays (2-d planes mean one frame) -- uint8 for the 8-bit layouts, numpy.uint16 / torch.int16
+        / torch.uint16 words for 'p010' and 'i010' -- or ONE array: a decoder's contiguous surface [B,H*3/2,W] (or 2-d) with
+        even H and W, Y then the chroma plane(s) in storage order, split into views that share its storage.  Anything else is
+        a ValueError (layout name, shape) or a TypeError (type, dtype).  device: where the data goes before the split -- one
+        copy per plane or surface, none for what is already there; None leaves it where it is, and then no device is touched."""
+        _, bps, planar = ops.yuv420_layout(layout)
+        what = 'predict_frames_yuv'
+        np_dtype = np.uint8 if bps == 1 else np.uint16
+        torch_dtypes = ops.yuv420_sample_dtypes(bps)
+
+        def tensor(f):
+            if not isinstance(f, (np.ndarray, torch.Tensor)):
+                raise TypeError(f'{what}: {layout!r} planes are torch.Tensors or numpy.ndarrays, got {type(f).__name__}')
+            if isinstance(f, np.ndarray):
+                if f.dtype != np_dtype:
+                    raise TypeError(f'{what}: {layout!r} planes are numpy arrays of dtype {np.dtype(np_dtype)}, got {f.dtype}')
+                f = np.ascontiguousarray(f)
+                return torch.from_numpy(f if bps == 1 else f.view(np.int16))        # the same bits
+            if f.dtype not in torch_dtypes:
+                raise TypeError(f"{what}: {layout!r} planes are tensors of dtype {' or '.join(str(d) for d in torch_dtypes)}, got {f.dtype}")
+            return f if f.dtype in (torch.uint8, torch.int16) else f.view(torch.int16)
+
+        if isinstance(planes, (np.ndarray, torch.Tensor)):
+            s = tensor(planes)
+            if s.dim() not in (2, 3) or min(s.shape) < 1:
+                raise ValueError(f'{what}: a surface of shape [B,H*3/2,W] or [H*3/2,W] expected, got {tuple(s.shape)}')
+            rows, W = s.shape[-2:]
+            H = rows // 3 * 2
+            if rows % 3 or W % 2:                                    # an odd H would give 3k + 2 rows
+                raise ValueError(f'{what}: a single {layout!r} surface has H*3/2 rows with even H and W, got {tuple(s.shape)}')
+            s = s if device is None else s.to(device, non_blocking=True)
+            s = s.unsqueeze(0) if s.dim() == 2 else s
+            if not planar:
+                return [s[:, :H], s[:, H:].unflatten(2, (W // 2, 2))]
+            if not s[0].is_contiguous():
+                s = s.contiguous()
+            chroma = s[:, H:].flatten(1)                             # a view: the rows of a frame are packed
+            n = (H // 2) * (W // 2)
+            return [s[:, :H], chroma[:, :n].unflatten(1, (H // 2, W // 2)), chroma[:, n:].unflatten(1, (H // 2, W // 2))]
+        if not isinstance(planes, (tuple, list)):
+            raise TypeError(f'{what}: a tuple of planes or one surface array expected, got {type(planes).__name__}')
+        ts = [tensor(f) for f in planes]
+        if len(ts) != (3 if planar else 2):
+            raise ValueError(f"{what}: {layout!r} takes the planes {'(y, u, v)' if planar else '(y, uv)'}, got {len(ts)}")
+        y = ts[0]
+        if y.dim() not in (2, 3) or min(y.shape) < 1:
+            raise ValueError(f'{what}: a Y plane of shape [B,H,W] or [H,W] expected, got {tuple(y.shape)}')
+        if y.dim() == 2:
+            ts = [t.unsqueeze(0) if t.dim() == (2 if planar or i == 0 else 3) else t for i, t in enumerate(ts)]
+        shapes = ops.yuv420_plane_shapes(layout, *ts[0].shape)
+        for t, shape in zip(ts[1:], shapes[1:]):
+            if tuple(t.shape) != shape:
+                raise ValueError(f'{what}: {layout!r} chroma planes of shape {shape} expected for Y {tuple(ts[0].shape)}, got {tuple(t.shape)}')
+        if device is not None:
+            ts = [t.to(device, non_blocking=True) for t in ts]
+        return ts
+
+    def _yuv_records(self, planes, layout, matrix, full_range, **kwargs):
+        """_frame_records for 4:2:0 frames of one size: one fused launch (ops.yuv420_to_input) builds the network input from
+        the planes; everything after it is _records_of_inputs, as for RGB frames."""
+        ops.yuv420_layout(layout)
+        ops.nv12_matrix_id(matrix)
+        ts = tuple(self._yuv_planes(planes, layout, device=next(self.model.parameters()).device))
+
+        def build(geo, dev):
+            return ops.yuv420_to_input(ts, layout, geo, self.model.input_format, matrix, full_range)
+        return self._records_of_inputs([(list(range(ts[0].shape[0])), (ts[0].shape[1], ts[0].shape[2]), build)], **kwargs)
+
+    def predict_frames_yuv(self, planes, layout, *, matrix='bt601', full_range=False, **kwargs):
+        """predict_frames for 4:2:0 video in any layout decoders give: 'nv12', 'nv21' (8-bit, interleaved chroma), 'i420',
+        'yv12' (8-bit, planar), 'p010' (10 bits in the high end of 16-bit words, interleaved) and 'i010' (yuv420p10le: 10
+        bits in the low end, planar).  planes: (y, uv) or (y, u, v) ('yv12': (y, v, u)) as torch tensors or numpy arrays, or a
+        single decoder surface [B,H*3/2,W] with even H and W (see _yuv_planes); host data crosses in one copy per plane or
+        surface, device tensors are read in place through their strides.  A 10-bit sample becomes 8 bits by
+        min(255, (v + 2) >> 2); from there the conversion is NV12's (include/mydet.h).  Returns exactly what
+        predict_frames returns for the converted RGB frames (ops.yuv420_to_rgb), which are never built: one HIP launch
+        reads the planes.  One call takes one frame size.  Keyword arguments as in _predict_pil."""
+        return self._objects_of_records(self._yuv_records(planes, layout, matrix, full_range, **kwargs))
+
+    def frames_yuv_to_json(self, planes, layout, img_ids, eval_type='x1y1wh', catIdx2id=None, *, matrix='bt601', full_range=False,
+                           **kwargs):
+        """COCO-style rows of 4:2:0 frames (see predict_frames_yuv): the counterpart of frames_to_json."""
+        return self._json_of_records(self._yuv_records(planes, layout, matrix, full_range, **kwargs), img_ids, eval_type, catIdx2id)
+
     def predict_batch(self, pil_imgs, **kwargs):
         """Batched form of detect_one (the reference loops image by image, api/detection.py:67-74): images that share a
         network input size go through ONE forward + ONE batched post-process.  Returns a list of ImageObjects in the

@@ -1432,6 +1432,122 @@ def nv12_to_input(y, uv, geometry, input_format, matrix='bt601', full_range=Fals
     return out
 
 
+# layout name -> (selector of include/mydet.h, bytes per sample, planar chroma).  'yv12' is I420 with V stored first: its planes
+# are taken in storage order (y, v, u) and exchanged here, so C has no sixth selector.
+YUV420_LAYOUTS = {'nv12': (_lib.YUV420_NV12, 1, False), 'nv21': (_lib.YUV420_NV21, 1, False), 'i420': (_lib.YUV420_I420, 1, True),
+                  'yv12': (_lib.YUV420_I420, 1, True), 'p010': (_lib.YUV420_P010, 2, False), 'i010': (_lib.YUV420_I010, 2, True)}
+
+
+def yuv420_layout(layout):
+    """(selector, bytes per sample, planar) of a layout name; a ValueError for an unknown one (raised before any device is touched)."""
+    if not isinstance(layout, str) or layout not in YUV420_LAYOUTS:
+        raise ValueError(f'yuv420: layout {layout!r} is not one of {sorted(YUV420_LAYOUTS)}')
+    return YUV420_LAYOUTS[layout]
+
+
+def yuv420_sample_dtypes(bps):
+    """The torch dtypes a plane of `bps` bytes per sample may have: uint8; int16 (the same bits) and, where this torch has it, uint16."""
+    if bps == 1:
+        return (torch.uint8,)
+    return (torch.int16,) + ((torch.uint16,) if hasattr(torch, 'uint16') else ())
+
+
+def yuv420_plane_shapes(layout, B, H, W):
+    """The shapes of the planes of B frames of H x W: Y, then one interleaved chroma plane or two planar ones."""
+    _, _, planar = yuv420_layout(layout)
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+    return [(B, H, W)] + ([(B, ch, cw)] * 2 if planar else [(B, ch, cw, 2)])
+
+
+def _yuv420_planes(planes, layout, what):
+    """The checks yuv420_to_rgb and yuv420_to_input share: ([y, chroma or u(, v)] in the order of mydet_yuv420_src.plane, 2-d
+    input?), on the device, read in place through their frame and row strides when samples (and pairs) are packed.  Type,
+    dtype and shape errors are raised before any device is touched."""
+    _, bps, planar = yuv420_layout(layout)
+    if not isinstance(planes, (tuple, list)):
+        raise TypeError(f'{what}: a tuple of planes expected, got {type(planes).__name__}')
+    dtypes = yuv420_sample_dtypes(bps)
+    for t in planes:
+        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
+            raise TypeError(f"{what}: {layout!r} planes are tensors of dtype {' or '.join(str(d) for d in dtypes)}, got "
+                            f'{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}')
+    names = '(y, u, v)' if planar else '(y, uv)'
+    if len(planes) != (3 if planar else 2):
+        raise ValueError(f'{what}: {layout!r} takes the planes {names}, got {len(planes)}')
+    planes = [t.view(torch.int16) if t.dtype not in (torch.uint8, torch.int16) else t for t in planes]
+    single = planes[0].dim() == 2
+    if single:
+        planes = [t.unsqueeze(0) if t.dim() == (2 if planar or i == 0 else 3) else t for i, t in enumerate(planes)]
+    y = planes[0]
+    if y.dim() != 3 or min(y.shape) < 1:
+        raise ValueError(f'{what}: a Y plane of shape [B,H,W] or [H,W] expected, got {tuple(y.shape)}')
+    want = yuv420_plane_shapes(layout, *y.shape)
+    for t, shape in zip(planes[1:], want[1:]):
+        if tuple(t.shape) != shape:
+            raise ValueError(f'{what}: {layout!r} chroma planes of shape {shape} expected for Y {tuple(y.shape)}, got {tuple(t.shape)}')
+    for t in planes:
+        require_gpu(t, what)
+        if t.device != y.device:
+            raise ValueError(f'{what}: y is on {y.device}, another plane on {t.device}')
+    for i, t in enumerate(planes):
+        inner = t.dim() == 4                                             # pairs: the last two dimensions are packed
+        if t.stride(-1) != 1 or (inner and t.stride(2) != 2) or t.stride(1) < t.shape[2] * (2 if inner else 1) or t.stride(0) < 0:
+            planes[i] = t.contiguous()
+    if layout == 'yv12':
+        planes[1], planes[2] = planes[2], planes[1]
+    return planes, single
+
+
+def _yuv420_src(planes, layout, matrix, full_range):
+    """mydet_yuv420_src of checked planes (_yuv420_planes)."""
+    sel, bps, _ = yuv420_layout(layout)
+    src = _lib.Yuv420Src()
+    for i, t in enumerate(planes):
+        src.plane[i], src.img_bytes[i], src.row_bytes[i] = _ptr(t), t.stride(0) * bps, t.stride(1) * bps
+    src.layout, src.matrix, src.full_range = sel, matrix, int(bool(full_range))
+    return src
+
+
+def yuv420_to_rgb(planes, layout, matrix='bt601', full_range=False, out=None):
+    """4:2:0 frames on the device -> packed uint8 RGB [B,H,W,3] ([H,W,3] for 2-d planes) (include/mydet.h:
+    mydet_yuv420_to_rgb_u8, where the layouts, the 10-bit rule and the formula are).  layout: 'nv12', 'nv21', 'p010' with
+    planes (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]); 'i420', 'i010' with (y, u, v), 'yv12' with (y, v, u), chroma planes
+    [B,ceil(H/2),ceil(W/2)].  uint8 for the 8-bit layouts, int16 or uint16 words for 'p010' / 'i010'.  Samples (and pairs)
+    packed, any row and frame strides, read in place.  matrix, full_range, out as in nv12_to_rgb."""
+    yuv420_layout(layout)
+    m = nv12_matrix_id(matrix)
+    planes, single = _yuv420_planes(planes, layout, 'yuv420_to_rgb')
+    B, H, W = planes[0].shape
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=planes[0].device)
+    dst = out.unsqueeze(0) if out.dim() == 3 else out
+    assert dst.dtype == torch.uint8 and tuple(dst.shape) == (B, H, W, 3) and dst.device == planes[0].device
+    assert dst.stride(3) == 1 and dst.stride(2) == 3 and dst.stride(1) >= 3 * W and dst.stride(0) >= 0
+    src = _yuv420_src(planes, layout, m, full_range)
+    code = _lib.lib().mydet_yuv420_to_rgb_u8(ctypes.byref(src), B, H, W, _ptr(dst), dst.stride(0), dst.stride(1), _stream())
+    _lib.check(code, 'mydet_yuv420_to_rgb_u8')
+    return dst[0] if single else dst
+
+
+def yuv420_to_input(planes, layout, geometry, input_format, matrix='bt601', full_range=False, out=None):
+    """4:2:0 frames of one size on the device -> the float32 network input [B,3,Hp,Wp] in ONE launch (include/mydet.h:
+    mydet_yuv420_to_input_f32): the bits of frames_to_input(yuv420_to_rgb(planes, layout, matrix, full_range), geometry,
+    input_format) without the RGB frames.  planes, layout, matrix, full_range as in yuv420_to_rgb; geometry, input_format,
+    out and the tap limit as in frames_to_input -- past the limit the frames are converted and go through frames_to_input's
+    own fallback."""
+    yuv420_layout(layout)
+    m = nv12_matrix_id(matrix)
+    checked, _ = _yuv420_planes(planes, layout, 'yuv420_to_input')
+    B, H, W = checked[0].shape
+    out, _, _, taps, tail = _input_window('yuv420_to_input', B, H, W, checked[0].device, geometry, input_format, out)
+    if taps > _lib.FRAMES_MAX_TAPS:
+        return frames_to_input(yuv420_to_rgb(planes, layout, matrix, full_range), geometry, input_format, out)
+    src = _yuv420_src(checked, layout, m, full_range)
+    code = _lib.lib().mydet_yuv420_to_input_f32(ctypes.byref(src), B, H, W, *tail, _stream())
+    _lib.check(code, 'mydet_yuv420_to_input_f32')
+    return out
+
+
 def records_to_original_(rec, pad_infos):
     """bboxes_to_original_ for a whole batch of records in place: pad_infos = one (ori w, ori h, tl x, tl y, imw, imh)
     per image (a row of ones-and-zeros (1, 1, 0, 0, 1, 1) leaves an image's boxes unchanged bit for bit)."""
