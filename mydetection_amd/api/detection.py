@@ -356,62 +356,6 @@ class Detector():
         return [d for per_img in out for d in per_img]
 
     @staticmethod
-    def _nv12_planes(y, uv=None, device=None):
-        """NV12 frames as two uint8 tensors: (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]).  y, uv: torch.uint8 tensors or
-        numpy.uint8 arrays, y of shape [B,H,W] or [H,W] and uv of shape [B,ceil(H/2),ceil(W/2),2] (or without B); with
-        uv=None, y is a decoder's single surface [B,H*3/2,W] (or 2-d) with even H and W, split into two views that share
-        its storage.  Anything else is a TypeError (type, dtype) or a ValueError (shape).  device: where the data goes
-        before the split -- one copy per plane or surface, none for what is already there; None leaves it where it is,
-        and then no device is touched."""
-        y = Detector._uint8_tensor(y, 'predict_frames_nv12: y')
-        if uv is not None:
-            uv = Detector._uint8_tensor(uv, 'predict_frames_nv12: uv')
-        if y.dim() not in (2, 3) or min(y.shape) < 1:
-            what = 'a surface of shape [B,H*3/2,W] or [H*3/2,W]' if uv is None else 'a Y plane of shape [B,H,W] or [H,W]'
-            raise ValueError(f'predict_frames_nv12: {what} expected, got {tuple(y.shape)}')
-        if uv is None:
-            rows, W = y.shape[-2:]
-            H = rows // 3 * 2
-            if rows % 3 or W % 2:                                    # an odd H would give 3k + 2 rows
-                raise ValueError(f'predict_frames_nv12: a single NV12 surface has H*3/2 rows with even H and W, got {tuple(y.shape)}')
-            s = y if device is None else y.to(device, non_blocking=True)
-            s = s.unsqueeze(0) if s.dim() == 2 else s
-            return s[:, :H], s[:, H:].unflatten(2, (W // 2, 2))
-        if y.dim() == 2:
-            y, uv = y.unsqueeze(0), (uv.unsqueeze(0) if uv.dim() == 3 else uv)
-        B, H, W = y.shape
-        if tuple(uv.shape) != (B, (H + 1) // 2, (W + 1) // 2, 2):
-            raise ValueError(f'predict_frames_nv12: a UV plane of shape {(B, (H + 1) // 2, (W + 1) // 2, 2)} expected for Y '
-                             f'{tuple(y.shape)}, got {tuple(uv.shape)}')
-        if device is not None:
-            y, uv = y.to(device, non_blocking=True), uv.to(device, non_blocking=True)
-        return y, uv
-
-    def _nv12_records(self, y, uv, matrix, full_range, **kwargs):
-        """_frame_records for NV12 frames of one size: one fused launch (ops.nv12_to_input) builds the network input from
-        the two planes; everything after it is _records_of_inputs, as for RGB frames."""
-        ops.nv12_matrix_id(matrix)
-        yp, uvp = self._nv12_planes(y, uv, device=next(self.model.parameters()).device)
-
-        def build(geo, dev):
-            return ops.nv12_to_input(yp, uvp, geo, self.model.input_format, matrix, full_range)
-        return self._records_of_inputs([(list(range(yp.shape[0])), (yp.shape[1], yp.shape[2]), build)], **kwargs)
-
-    def predict_frames_nv12(self, y, uv=None, *, matrix='bt601', full_range=False, **kwargs):
-        """predict_frames for NV12 video, the format decoders produce: y is the uint8 Y plane [B,H,W] (or [H,W]) and uv the
-        interleaved chroma plane [B,ceil(H/2),ceil(W/2),2]; or, with uv=None, y is the single surface [B,H*3/2,W] (or 2-d)
-        with even H and W, split into the two plane views without a copy.  torch tensors or numpy arrays; host data
-        crosses in one copy per plane or surface, device tensors are read in place through their strides.  matrix:
-        'bt601' or 'bt709'; full_range: Y in 0..255 instead of 16..235 (formula: include/mydet.h, DESIGN.md).  Returns
-        exactly what predict_frames returns for the converted RGB frames (ops.nv12_to_rgb), which are never built: one
-        HIP launch reads the planes.  One call takes one frame size.  Keyword arguments as in _predict_pil."""
-        return self._objects_of_records(self._nv12_records(y, uv, matrix, full_range, **kwargs))
-
-    def frames_nv12_to_json(self, y, uv, img_ids, eval_type='x1y1wh', catIdx2id=None, *, matrix='bt601', full_range=False, **kwargs):
-        """COCO-style rows of NV12 frames (see predict_frames_nv12): the counterpart of frames_to_json."""
-        return self._json_of_records(self._nv12_records(y, uv, matrix, full_range, **kwargs), img_ids, eval_type, catIdx2id)
-
-    @staticmethod
     def _yuv_planes(planes, layout, device=None):
         """4:2:0 frames of `layout` (ops.YUV420_LAYOUTS) as the tensors ops.yuv420_to_input takes: [y [B,H,W], uv
         [B,ceil(H/2),ceil(W/2),2]] or [y, u, v] with chroma planes [B,ceil(H/2),ceil(W/2)] ('yv12': y, v, u).  planes: a tuple
@@ -423,22 +367,17 @@ class Detector():
         _, bps, planar = ops.yuv420_layout(layout)
         what = 'predict_frames_yuv'
         np_dtype = np.uint8 if bps == 1 else np.uint16
-        torch_dtypes = ops.yuv420_sample_dtypes(bps)
 
-        def tensor(f):
-            if not isinstance(f, (np.ndarray, torch.Tensor)):
-                raise TypeError(f'{what}: {layout!r} planes are torch.Tensors or numpy.ndarrays, got {type(f).__name__}')
-            if isinstance(f, np.ndarray):
-                if f.dtype != np_dtype:
-                    raise TypeError(f'{what}: {layout!r} planes are numpy arrays of dtype {np.dtype(np_dtype)}, got {f.dtype}')
-                f = np.ascontiguousarray(f)
-                return torch.from_numpy(f if bps == 1 else f.view(np.int16))        # the same bits
-            if f.dtype not in torch_dtypes:
-                raise TypeError(f"{what}: {layout!r} planes are tensors of dtype {' or '.join(str(d) for d in torch_dtypes)}, got {f.dtype}")
-            return f if f.dtype in (torch.uint8, torch.int16) else f.view(torch.int16)
+        def tensor(f):                                               # a numpy array as a tensor; ops has the rules for tensors
+            if not isinstance(f, np.ndarray):
+                return f
+            if f.dtype != np_dtype:
+                raise TypeError(f'{what}: {layout!r} planes are numpy arrays of dtype {np.dtype(np_dtype)}, got {f.dtype}')
+            f = np.ascontiguousarray(f)
+            return torch.from_numpy(f if bps == 1 else f.view(np.int16))            # the same bits
 
         if isinstance(planes, (np.ndarray, torch.Tensor)):
-            s = tensor(planes)
+            s = ops.yuv420_samples(tensor(planes), layout, what)
             if s.dim() not in (2, 3) or min(s.shape) < 1:
                 raise ValueError(f'{what}: a surface of shape [B,H*3/2,W] or [H*3/2,W] expected, got {tuple(s.shape)}')
             rows, W = s.shape[-2:]
@@ -456,18 +395,7 @@ class Detector():
             return [s[:, :H], chroma[:, :n].unflatten(1, (H // 2, W // 2)), chroma[:, n:].unflatten(1, (H // 2, W // 2))]
         if not isinstance(planes, (tuple, list)):
             raise TypeError(f'{what}: a tuple of planes or one surface array expected, got {type(planes).__name__}')
-        ts = [tensor(f) for f in planes]
-        if len(ts) != (3 if planar else 2):
-            raise ValueError(f"{what}: {layout!r} takes the planes {'(y, u, v)' if planar else '(y, uv)'}, got {len(ts)}")
-        y = ts[0]
-        if y.dim() not in (2, 3) or min(y.shape) < 1:
-            raise ValueError(f'{what}: a Y plane of shape [B,H,W] or [H,W] expected, got {tuple(y.shape)}')
-        if y.dim() == 2:
-            ts = [t.unsqueeze(0) if t.dim() == (2 if planar or i == 0 else 3) else t for i, t in enumerate(ts)]
-        shapes = ops.yuv420_plane_shapes(layout, *ts[0].shape)
-        for t, shape in zip(ts[1:], shapes[1:]):
-            if tuple(t.shape) != shape:
-                raise ValueError(f'{what}: {layout!r} chroma planes of shape {shape} expected for Y {tuple(ts[0].shape)}, got {tuple(t.shape)}')
+        ts, _ = ops.yuv420_check_planes([tensor(f) for f in planes], layout, what)
         if device is not None:
             ts = [t.to(device, non_blocking=True) for t in ts]
         return ts
@@ -476,7 +404,7 @@ class Detector():
         """_frame_records for 4:2:0 frames of one size: one fused launch (ops.yuv420_to_input) builds the network input from
         the planes; everything after it is _records_of_inputs, as for RGB frames."""
         ops.yuv420_layout(layout)
-        ops.nv12_matrix_id(matrix)
+        ops.yuv_matrix_id(matrix)
         ts = tuple(self._yuv_planes(planes, layout, device=next(self.model.parameters()).device))
 
         def build(geo, dev):
@@ -498,6 +426,21 @@ class Detector():
                            **kwargs):
         """COCO-style rows of 4:2:0 frames (see predict_frames_yuv): the counterpart of frames_to_json."""
         return self._json_of_records(self._yuv_records(planes, layout, matrix, full_range, **kwargs), img_ids, eval_type, catIdx2id)
+
+    def predict_frames_nv12(self, y, uv=None, *, matrix='bt601', full_range=False, **kwargs):
+        """predict_frames for NV12 video, the format decoders produce: y is the uint8 Y plane [B,H,W] (or [H,W]) and uv the
+        interleaved chroma plane [B,ceil(H/2),ceil(W/2),2]; or, with uv=None, y is the single surface [B,H*3/2,W] (or 2-d)
+        with even H and W, split into the two plane views without a copy.  torch tensors or numpy arrays; host data
+        crosses in one copy per plane or surface, device tensors are read in place through their strides.  matrix:
+        'bt601' or 'bt709'; full_range: Y in 0..255 instead of 16..235 (formula: include/mydet.h, DESIGN.md).  Returns
+        exactly what predict_frames returns for the converted RGB frames (ops.nv12_to_rgb), which are never built: one
+        HIP launch reads the planes.  One call takes one frame size.  Keyword arguments as in _predict_pil."""
+        return self.predict_frames_yuv(y if uv is None else (y, uv), 'nv12', matrix=matrix, full_range=full_range, **kwargs)
+
+    def frames_nv12_to_json(self, y, uv, img_ids, eval_type='x1y1wh', catIdx2id=None, *, matrix='bt601', full_range=False, **kwargs):
+        """COCO-style rows of NV12 frames (see predict_frames_nv12): the counterpart of frames_to_json."""
+        return self.frames_yuv_to_json(y if uv is None else (y, uv), 'nv12', img_ids, eval_type, catIdx2id, matrix=matrix,
+                                       full_range=full_range, **kwargs)
 
     def predict_batch(self, pil_imgs, **kwargs):
         """Batched form of detect_one (the reference loops image by image, api/detection.py:67-74): images that share a

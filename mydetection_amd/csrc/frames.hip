@@ -7,7 +7,7 @@
 //   filter rounding and the float conversion are the same functions those kernels call (pixel_math.h).
 //
 // The tile, the stage of horizontally resampled rows, the vertical pass and the stores are frames_tile.h, shared with
-// nv12.hip; this file is the horizontal pass over packed RGB bytes in global memory and the entry point.
+// yuv420.hip; this file is the horizontal pass over packed RGB bytes in global memory and the entry point.
 //
 // LDS: (rows + ksx) * FR_TW dwords, rows <= (FR_TH - 1) * H / oh + ksy + 2.  With MYDET_FRAMES_MAX_TAPS = 17 (a downscale
 // of up to 8x: ksize = 2 * ceil(scale) + 1) that is at most 139 + 17 rows of 256 bytes = 39 KiB, and 53 + 7 rows (15 KiB)

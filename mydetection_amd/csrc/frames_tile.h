@@ -1,5 +1,5 @@
-// The tile pipeline of the frame-input kernels (frames.hip: uint8 RGB frames, nv12.hip: NV12 planes): both give float32
-// [B,3,Hp,Wp] and differ only in where the horizontal taps come from.
+// The tile pipeline of the frame-input kernels (frames.hip: uint8 RGB frames, yuv420.hip: 4:2:0 planes in any layout): both
+// give float32 [B,3,Hp,Wp] and differ only in where the horizontal taps come from.
 //
 // A workgroup of 256 threads owns FR_TH x FR_TW output pixels (all three planes).  The vertical taps of its rows span the
 // source rows [r0, r0 + nrows); the horizontally resampled pixels of those rows and the tile's columns go to the LDS stage

@@ -1,4 +1,4 @@
-// The 8-bit pixel arithmetic every image kernel shares (boxops.hip, frames.hip, nv12.hip), defined once so that "the bits
+// The 8-bit pixel arithmetic every image kernel shares (boxops.hip, frames.hip, yuv420.hip), defined once so that "the bits
 // of mydet_resize_bilinear_u8 + mydet_preprocess_u8_f32" is one piece of code and not a promise between copies.
 #pragma once
 #include "common.h"

@@ -15,17 +15,18 @@
 //   R = clip8((cy*C         + crv*E + 128) >> 8)
 //   G = clip8((cy*C - cgu*D - cgv*E + 128) >> 8)
 //   B = clip8((cy*C + cbu*D         + 128) >> 8)
-// with round(256 * x) of the BT.601 / BT.709 matrices in NV_COEF below, the only copy of the table.
+// with round(256 * x) of the BT.601 / BT.709 matrices in YUV_COEF below, the only copy of the table.
 //
 // The fused kernel is built from the tile pipeline of frames_tile.h, like frames_to_input_kernel: the same tile, stage of
 // horizontally resampled rows, vertical pass and stores, from the same functions.  The horizontal pass differs: the
 // taps of neighbouring output columns overlap (7 taps for 3 source pixels per column at 1080p -> 360), so the source is
-// converted once per pixel and not once per tap.  NV_ROWS source rows of the tile's column window [c0, c0 + max_cols) are read
-// as quads -- for NV12 one Y dword and one chroma dword per thread (a quad starts at a multiple of 4, so both are at byte c of
-// their rows; the other layouts: yuv_quad), a wave reads whole row segments -- converted, and written to LDS as packed dwords (r | g << 8 | b << 16) with one
-// 16-byte write.  The taps are then LDS reads (lane stride = the scale factor in dwords), and the result goes to the stage.
+// converted once per pixel and not once per tap.  YUV_ROWS source rows of the tile's column window [c0, c0 + max_cols) are read
+// as quads: a thread fetches four neighbouring pixels from a column that is a multiple of 4 (yuv_quad, where the reads of each
+// layout are listed; a wave reads whole row segments), converts them and writes them to LDS as packed dwords
+// (r | g << 8 | b << 16) with one 16-byte write.  The taps are then LDS reads (lane stride = the scale factor in dwords), and
+// the result goes to the stage.
 //
-// LDS: (max_rows + ksx) * FR_TW dwords as in frames.hip + NV_ROWS * max_cols dwords, max_cols <= (FR_TW - 1) * W / ow + ksx + 8:
+// LDS: (max_rows + ksx) * FR_TW dwords as in frames.hip + YUV_ROWS * max_cols dwords, max_cols <= (FR_TW - 1) * W / ow + ksx + 8:
 // at most 39 KiB + 8 * 528 * 4 B = 55.5 KiB at MYDET_FRAMES_MAX_TAPS, 15 + 6.4 KiB for 1080p -> 360 rows.  Every table entry
 // is clamped before it addresses either plane or the LDS window, so a malformed table gives wrong pixels, never an access
 // outside the planes or the stage.
@@ -33,11 +34,11 @@
 
 namespace {
 
-constexpr int NV_ROWS = 8;                 // source rows converted per step
+constexpr int YUV_ROWS = 8;                 // source rows converted per step
 
 // cy, crv, cgu, cgv, cbu, luma offset: [matrix: 0 = BT.601, 1 = BT.709][range: 0 = limited, 1 = full]
-struct Nv12Coef { int cy, crv, cgu, cgv, cbu, yoff; };
-constexpr Nv12Coef NV_COEF[2][2] = {{{298, 409, 100, 208, 516, 16}, {256, 359, 88, 183, 454, 0}},
+struct YuvCoef { int cy, crv, cgu, cgv, cbu, yoff; };
+constexpr YuvCoef YUV_COEF[2][2] = {{{298, 409, 100, 208, 516, 16}, {256, 359, 88, 183, 454, 0}},
                                     {{298, 459, 55, 136, 541, 16}, {256, 403, 48, 120, 475, 0}}};
 
 // One source of the 4:2:0 family (include/mydet.h: mydet_yuv420_src).  p[2] is null for the semi-planar layouts.
@@ -47,7 +48,7 @@ struct YuvSrc {
     int H, W;
     int wide;                                  // every plane allows the wide reads of its layout (yuv_quad)
     uint32_t pair_sel;                         // v_perm_b32 selector that puts the two chroma pairs of a quad into (U, V) order
-    Nv12Coef k;
+    YuvCoef k;
 };
 
 struct YuvInputArgs {
@@ -63,7 +64,7 @@ struct YuvRgbArgs {
     int dst_words;                             // dst rows can be written as aligned dwords
 };
 
-__device__ __forceinline__ uint32_t nv_rgb(const Nv12Coef &k, int Y, int U, int V) {
+__device__ __forceinline__ uint32_t yuv_rgb(const YuvCoef &k, int Y, int U, int V) {
     const int c = k.cy * (Y - k.yoff) + 128, d = U - 128, e = V - 128;
     return px_pack(px_clamp((c + k.crv * e) >> 8, 0, 255), px_clamp((c - k.cgu * d - k.cgv * e) >> 8, 0, 255),
                    px_clamp((c + k.cbu * d) >> 8, 0, 255));
@@ -143,7 +144,7 @@ __device__ __forceinline__ uint4 yuv_quad(const YuvSrc &s, int b, int row, int c
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const uint32_t pair = cw >> (16 * (k >> 1));
-        v[k] = k < ny ? nv_rgb(s.k, (yw >> (8 * k)) & 255u, pair & 255u, (pair >> 8) & 255u) : 0u;
+        v[k] = k < ny ? yuv_rgb(s.k, (yw >> (8 * k)) & 255u, pair & 255u, (pair >> 8) & 255u) : 0u;
     }
     return make_uint4(v[0], v[1], v[2], v[3]);
 }
@@ -173,10 +174,10 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const YuvRgbArgs p) {
 // N = pixels per thread along x of the vertical pass and the stores: 4 or 1 (frames_tile.h); BPS, PLANAR: the fetch (yuv_quad)
 template <int N, int BPS, bool PLANAR>
 __global__ __launch_bounds__(256) void yuv_to_input_kernel(const YuvInputArgs p) {
-    extern __shared__ __align__(16) uint32_t nv_lds[];
-    uint32_t *stage = nv_lds;                                           // [max_rows][FR_TW] horizontally resampled pixels
-    int32_t *wts = reinterpret_cast<int32_t *>(nv_lds + p.o.max_rows * FR_TW);   // [ksx][FR_TW] horizontal weights, tap-major
-    uint32_t *raw = nv_lds + (p.o.max_rows + p.o.ksx) * FR_TW;          // [NV_ROWS][max_cols] converted source pixels
+    extern __shared__ __align__(16) uint32_t yuv_lds[];
+    uint32_t *stage = yuv_lds;                                           // [max_rows][FR_TW] horizontally resampled pixels
+    int32_t *wts = reinterpret_cast<int32_t *>(yuv_lds + p.o.max_rows * FR_TW);   // [ksx][FR_TW] horizontal weights, tap-major
+    uint32_t *raw = yuv_lds + (p.o.max_rows + p.o.ksx) * FR_TW;          // [YUV_ROWS][max_cols] converted source pixels
     const int tid = threadIdx.x;
     const int tx0 = blockIdx.x * FR_TW, ty0 = blockIdx.y * FR_TH, b = blockIdx.z;
 
@@ -190,8 +191,8 @@ __global__ __launch_bounds__(256) void yuv_to_input_kernel(const YuvInputArgs p)
         const FrColumn c = fr_column(p.o, p.s.W, tx0, col);
         const int xs = px_clamp(c.x0 - c0, 0, p.max_cols - 1), nx = min(c.nx, p.max_cols - xs);
         const int nq = p.max_cols >> 2;
-        for (int rb = 0; rb < win.nrows; rb += NV_ROWS) {
-            const int nr = min(NV_ROWS, win.nrows - rb);
+        for (int rb = 0; rb < win.nrows; rb += YUV_ROWS) {
+            const int nr = min(YUV_ROWS, win.nrows - rb);
             if (rb) __syncthreads();                                    // the previous step's taps have been read
             for (int r = wv; r < nr; r += 256 / FR_TW)                  // a wave converts a row of the window
                 for (int q = col; q < nq; q += FR_TW)
@@ -254,7 +255,7 @@ int yuv_source(YuvSrc &s, int &bps, bool &planar, const mydet_yuv420_src *src, i
     }
     s.H = H; s.W = W;
     s.pair_sel = v_first ? 0x02030001u : 0x03020100u;
-    s.k = NV_COEF[src->matrix][src->full_range];
+    s.k = YUV_COEF[src->matrix][src->full_range];
     return 0;
 }
 
@@ -267,8 +268,16 @@ int yuv_source(YuvSrc &s, int &bps, bool &planar, const mydet_yuv420_src *src, i
         else { CALL(2, true); }                            \
     } while (0)
 
-int yuv_to_rgb(const mydet_yuv420_src *src, int B, int H, int W, unsigned char *dst, int64_t dst_img_bytes, int64_t dst_row_bytes,
-               void *stream) {
+// The NV12 entry points' arguments as a source descriptor
+mydet_yuv420_src nv12_src(const unsigned char *y, int64_t y_img, int64_t y_row, const unsigned char *uv, int64_t uv_img, int64_t uv_row,
+                          int matrix, int full_range) {
+    return {{y, uv, nullptr}, {y_img, uv_img, 0}, {y_row, uv_row, 0}, MYDET_YUV420_NV12, matrix, full_range, 0};
+}
+
+}  // namespace
+
+extern "C" int mydet_yuv420_to_rgb_u8(const mydet_yuv420_src *src, int B, int H, int W, unsigned char *dst, int64_t dst_img_bytes,
+                                      int64_t dst_row_bytes, void *stream) {
     YuvRgbArgs p;
     int bps;
     bool planar;
@@ -286,9 +295,10 @@ int yuv_to_rgb(const mydet_yuv420_src *src, int B, int H, int W, unsigned char *
     return mydet_launch_status();
 }
 
-int yuv_to_input(const mydet_yuv420_src *src, int B, int H, int W, float *out, int Hp, int Wp, int oh, int ow, int top, int left,
-                 const int32_t *bounds_x, const int32_t *kx, int ksx, const int32_t *bounds_y, const int32_t *ky, int ksy, int norm,
-                 const float *mean3, const float *std3, void *stream) {
+extern "C" int mydet_yuv420_to_input_f32(const mydet_yuv420_src *src, int B, int H, int W, float *out, int Hp, int Wp, int oh, int ow,
+                                         int top, int left, const int32_t *bounds_x, const int32_t *kx, int ksx,
+                                         const int32_t *bounds_y, const int32_t *ky, int ksy, int norm, const float *mean3,
+                                         const float *std3, void *stream) {
     YuvInputArgs p;
     int bps;
     bool planar;
@@ -305,7 +315,7 @@ int yuv_to_input(const mydet_yuv420_src *src, int B, int H, int W, float *out, i
     cols = (cols + 3 + 3) / 4 * 4;
     if (cols > ((int64_t)W + 3) / 4 * 4) cols = ((int64_t)W + 3) / 4 * 4;
     p.max_cols = (int)cols;
-    const size_t lds = fr_tile_lds_bytes(p.o) + (size_t)NV_ROWS * p.max_cols * sizeof(uint32_t);
+    const size_t lds = fr_tile_lds_bytes(p.o) + (size_t)YUV_ROWS * p.max_cols * sizeof(uint32_t);
     if (lds > 64 * 1024) return MYDET_E_UNSUPP;
     const bool quads = fr_quad_stores(p.o);
 #define YUV_INPUT(BPS, PLANAR)                                                                                          \
@@ -316,31 +326,11 @@ int yuv_to_input(const mydet_yuv420_src *src, int B, int H, int W, float *out, i
     return mydet_launch_status();
 }
 
-// The NV12 entry points' arguments as a source descriptor
-mydet_yuv420_src nv12_src(const unsigned char *y, int64_t y_img, int64_t y_row, const unsigned char *uv, int64_t uv_img, int64_t uv_row,
-                          int matrix, int full_range) {
-    return {{y, uv, nullptr}, {y_img, uv_img, 0}, {y_row, uv_row, 0}, MYDET_YUV420_NV12, matrix, full_range, 0};
-}
-
-}  // namespace
-
-extern "C" int mydet_yuv420_to_rgb_u8(const mydet_yuv420_src *src, int B, int H, int W, unsigned char *dst, int64_t dst_img_bytes,
-                                      int64_t dst_row_bytes, void *stream) {
-    return yuv_to_rgb(src, B, H, W, dst, dst_img_bytes, dst_row_bytes, stream);
-}
-
-extern "C" int mydet_yuv420_to_input_f32(const mydet_yuv420_src *src, int B, int H, int W, float *out, int Hp, int Wp, int oh, int ow,
-                                         int top, int left, const int32_t *bounds_x, const int32_t *kx, int ksx,
-                                         const int32_t *bounds_y, const int32_t *ky, int ksy, int norm, const float *mean3,
-                                         const float *std3, void *stream) {
-    return yuv_to_input(src, B, H, W, out, Hp, Wp, oh, ow, top, left, bounds_x, kx, ksx, bounds_y, ky, ksy, norm, mean3, std3, stream);
-}
-
 extern "C" int mydet_nv12_to_rgb_u8(const unsigned char *y, int64_t y_img_bytes, int64_t y_row_bytes, const unsigned char *uv,
                                     int64_t uv_img_bytes, int64_t uv_row_bytes, int B, int H, int W, unsigned char *dst,
                                     int64_t dst_img_bytes, int64_t dst_row_bytes, int matrix, int full_range, void *stream) {
     const mydet_yuv420_src src = nv12_src(y, y_img_bytes, y_row_bytes, uv, uv_img_bytes, uv_row_bytes, matrix, full_range);
-    return yuv_to_rgb(&src, B, H, W, dst, dst_img_bytes, dst_row_bytes, stream);
+    return mydet_yuv420_to_rgb_u8(&src, B, H, W, dst, dst_img_bytes, dst_row_bytes, stream);
 }
 
 extern "C" int mydet_nv12_to_input_f32(const unsigned char *y, int64_t y_img_bytes, int64_t y_row_bytes, const unsigned char *uv,
@@ -349,5 +339,6 @@ extern "C" int mydet_nv12_to_input_f32(const unsigned char *y, int64_t y_img_byt
                                        const int32_t *kx, int ksx, const int32_t *bounds_y, const int32_t *ky, int ksy, int norm,
                                        const float *mean3, const float *std3, void *stream) {
     const mydet_yuv420_src src = nv12_src(y, y_img_bytes, y_row_bytes, uv, uv_img_bytes, uv_row_bytes, matrix, full_range);
-    return yuv_to_input(&src, B, H, W, out, Hp, Wp, oh, ow, top, left, bounds_x, kx, ksx, bounds_y, ky, ksy, norm, mean3, std3, stream);
+    return mydet_yuv420_to_input_f32(&src, B, H, W, out, Hp, Wp, oh, ow, top, left, bounds_x, kx, ksx, bounds_y, ky, ksy, norm, mean3, std3,
+                                     stream);
 }

@@ -1315,7 +1315,7 @@ def _resample_tables_on(device, H, W, oh, ow):
 
 
 def _input_window(what, B, H, W, device, geometry, input_format, out):
-    """What frames_to_input and nv12_to_input (`what`, for the messages) share for B source frames of H x W on `device`:
+    """What frames_to_input and yuv420_to_input (`what`, for the messages) share for B source frames of H x W on `device`:
     (out, (oh, ow), (top, left), taps of the longer filter, the C arguments from `out` to `std3` -- the same run in both
     entry points of include/mydet.h).  out is allocated when None and checked otherwise."""
     norm = _norm_args(input_format)
@@ -1360,76 +1360,14 @@ def frames_to_input(frames_u8, geometry, input_format, out=None):
     return out
 
 
-NV12_MATRICES = {'bt601': 0, 'bt709': 1}          # the matrix selector of include/mydet.h, where the coefficient table lives
+YUV_MATRICES = {'bt601': 0, 'bt709': 1}           # the matrix selector of include/mydet.h, where the coefficient table lives
 
 
-def nv12_matrix_id(matrix):
+def yuv_matrix_id(matrix):
     """The C selector of a matrix name; a ValueError for an unknown one (raised before any device is touched)."""
-    if matrix not in NV12_MATRICES:
-        raise ValueError(f'nv12: matrix {matrix!r} is not one of {sorted(NV12_MATRICES)}')
-    return NV12_MATRICES[matrix]
-
-
-def _nv12_planes(y, uv, what):
-    """The checks nv12_to_rgb and nv12_to_input share: (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2], 2-d input?) on the device, read in
-    place through their frame and row strides when pixels (Y) and pairs (UV) are packed."""
-    for t, name in ((y, 'y'), (uv, 'uv')):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-            raise TypeError(f'{what}: a uint8 tensor expected for {name}, got {t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}')
-    require_gpu(y, what)
-    require_gpu(uv, what)
-    single = y.dim() == 2
-    if single:
-        y = y.unsqueeze(0)
-        uv = uv.unsqueeze(0) if uv.dim() == 3 else uv
-    if y.dim() != 3 or min(y.shape) < 1:
-        raise ValueError(f'{what}: a Y plane of shape [B,H,W] or [H,W] expected, got {tuple(y.shape)}')
-    B, H, W = y.shape
-    if tuple(uv.shape) != (B, (H + 1) // 2, (W + 1) // 2, 2):
-        raise ValueError(f'{what}: a UV plane of shape {(B, (H + 1) // 2, (W + 1) // 2, 2)} expected for Y {tuple(y.shape)}, got {tuple(uv.shape)}')
-    if y.device != uv.device:
-        raise ValueError(f'{what}: y is on {y.device}, uv on {uv.device}')
-    if y.stride(2) != 1 or y.stride(1) < W or y.stride(0) < 0:
-        y = y.contiguous()
-    if uv.stride(3) != 1 or uv.stride(2) != 2 or uv.stride(1) < 2 * uv.shape[2] or uv.stride(0) < 0:
-        uv = uv.contiguous()
-    return y, uv, single
-
-
-def nv12_to_rgb(y, uv, matrix='bt601', full_range=False, out=None):
-    """NV12 frames on the device -> packed uint8 RGB [B,H,W,3] ([H,W,3] for a 2-d y) (include/mydet.h: mydet_nv12_to_rgb_u8,
-    where the formula and the coefficient table are).  y: uint8 [B,H,W] or [H,W], element stride 1 along W; uv: uint8
-    [B,ceil(H/2),ceil(W/2),2], last two dimensions packed; any row and frame strides, read in place.  matrix: 'bt601' or
-    'bt709'; full_range: Y in 0..255 instead of 16..235.  out: optional uint8 [B,H,W,3] view with packed pixels."""
-    m = nv12_matrix_id(matrix)
-    y, uv, single = _nv12_planes(y, uv, 'nv12_to_rgb')
-    B, H, W = y.shape
-    if out is None:
-        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=y.device)
-    dst = out.unsqueeze(0) if out.dim() == 3 else out
-    assert dst.dtype == torch.uint8 and tuple(dst.shape) == (B, H, W, 3) and dst.device == y.device
-    assert dst.stride(3) == 1 and dst.stride(2) == 3 and dst.stride(1) >= 3 * W and dst.stride(0) >= 0
-    code = _lib.lib().mydet_nv12_to_rgb_u8(_ptr(y), y.stride(0), y.stride(1), _ptr(uv), uv.stride(0), uv.stride(1), B, H, W,
-                                           _ptr(dst), dst.stride(0), dst.stride(1), m, int(bool(full_range)), _stream())
-    _lib.check(code, 'mydet_nv12_to_rgb_u8')
-    return dst[0] if single else dst
-
-
-def nv12_to_input(y, uv, geometry, input_format, matrix='bt601', full_range=False, out=None):
-    """NV12 frames of one size on the device -> the float32 network input [B,3,Hp,Wp] in ONE launch (include/mydet.h:
-    mydet_nv12_to_input_f32): the bits of frames_to_input(nv12_to_rgb(y, uv, matrix, full_range), geometry, input_format)
-    without the RGB frames.  y, uv, matrix, full_range as in nv12_to_rgb; geometry, input_format, out and the tap limit as
-    in frames_to_input -- past the limit the frames are converted and go through frames_to_input's own fallback."""
-    m = nv12_matrix_id(matrix)
-    y, uv, _ = _nv12_planes(y, uv, 'nv12_to_input')
-    B, H, W = y.shape
-    out, _, _, taps, tail = _input_window('nv12_to_input', B, H, W, y.device, geometry, input_format, out)
-    if taps > _lib.FRAMES_MAX_TAPS:
-        return frames_to_input(nv12_to_rgb(y, uv, matrix, full_range), geometry, input_format, out)
-    code = _lib.lib().mydet_nv12_to_input_f32(_ptr(y), y.stride(0), y.stride(1), _ptr(uv), uv.stride(0), uv.stride(1), B, H, W,
-                                              m, int(bool(full_range)), *tail, _stream())
-    _lib.check(code, 'mydet_nv12_to_input_f32')
-    return out
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f'yuv420: matrix {matrix!r} is not one of {sorted(YUV_MATRICES)}')
+    return YUV_MATRICES[matrix]
 
 
 # layout name -> (selector of include/mydet.h, bytes per sample, planar chroma).  'yv12' is I420 with V stored first: its planes
@@ -1459,22 +1397,25 @@ def yuv420_plane_shapes(layout, B, H, W):
     return [(B, H, W)] + ([(B, ch, cw)] * 2 if planar else [(B, ch, cw, 2)])
 
 
-def _yuv420_planes(planes, layout, what):
-    """The checks yuv420_to_rgb and yuv420_to_input share: ([y, chroma or u(, v)] in the order of mydet_yuv420_src.plane, 2-d
-    input?), on the device, read in place through their frame and row strides when samples (and pairs) are packed.  Type,
-    dtype and shape errors are raised before any device is touched."""
-    _, bps, planar = yuv420_layout(layout)
-    if not isinstance(planes, (tuple, list)):
-        raise TypeError(f'{what}: a tuple of planes expected, got {type(planes).__name__}')
-    dtypes = yuv420_sample_dtypes(bps)
-    for t in planes:
-        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
-            raise TypeError(f"{what}: {layout!r} planes are tensors of dtype {' or '.join(str(d) for d in dtypes)}, got "
-                            f'{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}')
+def yuv420_samples(t, layout, what):
+    """One plane of `layout` as the tensor the kernels read: a TypeError, worded with `what` (the caller), for anything but a
+    tensor of the layout's dtype; uint16 words come back as an int16 view of the same bits.  Touches no device."""
+    dtypes = yuv420_sample_dtypes(yuv420_layout(layout)[1])
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
+        raise TypeError(f"{what}: {layout!r} planes are tensors of dtype {' or '.join(str(d) for d in dtypes)}, got "
+                        f'{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}')
+    return t if t.dtype in (torch.uint8, torch.int16) else t.view(torch.int16)
+
+
+def yuv420_check_planes(planes, layout, what):
+    """The rules every list of planes of `layout` meets, on any device and touching none: (the planes [y [B,H,W], chroma or
+    u(, v)] in the order given, 2-d input?).  Each plane by yuv420_samples, the layout's number of planes, 2-d planes mean
+    one frame, chroma of yuv420_plane_shapes.  Errors in that order, worded with `what` (the caller)."""
+    planar = yuv420_layout(layout)[2]
+    planes = [yuv420_samples(t, layout, what) for t in planes]
     names = '(y, u, v)' if planar else '(y, uv)'
     if len(planes) != (3 if planar else 2):
         raise ValueError(f'{what}: {layout!r} takes the planes {names}, got {len(planes)}')
-    planes = [t.view(torch.int16) if t.dtype not in (torch.uint8, torch.int16) else t for t in planes]
     single = planes[0].dim() == 2
     if single:
         planes = [t.unsqueeze(0) if t.dim() == (2 if planar or i == 0 else 3) else t for i, t in enumerate(planes)]
@@ -1485,11 +1426,20 @@ def _yuv420_planes(planes, layout, what):
     for t, shape in zip(planes[1:], want[1:]):
         if tuple(t.shape) != shape:
             raise ValueError(f'{what}: {layout!r} chroma planes of shape {shape} expected for Y {tuple(y.shape)}, got {tuple(t.shape)}')
-    for t in planes:
-        require_gpu(t, what)
-        if t.device != y.device:
-            raise ValueError(f'{what}: y is on {y.device}, another plane on {t.device}')
+    return planes, single
+
+
+def _yuv420_planes(planes, layout, what):
+    """What yuv420_to_rgb and yuv420_to_input share: the checked planes (yuv420_check_planes) in the order of
+    mydet_yuv420_src.plane and whether the input was 2-d; on the device, read in place through their frame and row strides
+    when samples (and pairs) are packed.  Type, dtype and shape errors are raised before any device is touched."""
+    if not isinstance(planes, (tuple, list)):
+        raise TypeError(f'{what}: a tuple of planes expected, got {type(planes).__name__}')
+    planes, single = yuv420_check_planes(planes, layout, what)
     for i, t in enumerate(planes):
+        require_gpu(t, what)
+        if t.device != planes[0].device:
+            raise ValueError(f'{what}: y is on {planes[0].device}, another plane on {t.device}')
         inner = t.dim() == 4                                             # pairs: the last two dimensions are packed
         if t.stride(-1) != 1 or (inner and t.stride(2) != 2) or t.stride(1) < t.shape[2] * (2 if inner else 1) or t.stride(0) < 0:
             planes[i] = t.contiguous()
@@ -1513,9 +1463,10 @@ def yuv420_to_rgb(planes, layout, matrix='bt601', full_range=False, out=None):
     mydet_yuv420_to_rgb_u8, where the layouts, the 10-bit rule and the formula are).  layout: 'nv12', 'nv21', 'p010' with
     planes (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]); 'i420', 'i010' with (y, u, v), 'yv12' with (y, v, u), chroma planes
     [B,ceil(H/2),ceil(W/2)].  uint8 for the 8-bit layouts, int16 or uint16 words for 'p010' / 'i010'.  Samples (and pairs)
-    packed, any row and frame strides, read in place.  matrix, full_range, out as in nv12_to_rgb."""
+    packed, any row and frame strides, read in place.  matrix: 'bt601' or 'bt709'; full_range: Y in 0..255 instead of 16..235.
+    out: optional uint8 [B,H,W,3] view with packed pixels."""
     yuv420_layout(layout)
-    m = nv12_matrix_id(matrix)
+    m = yuv_matrix_id(matrix)
     planes, single = _yuv420_planes(planes, layout, 'yuv420_to_rgb')
     B, H, W = planes[0].shape
     if out is None:
@@ -1536,7 +1487,7 @@ def yuv420_to_input(planes, layout, geometry, input_format, matrix='bt601', full
     out and the tap limit as in frames_to_input -- past the limit the frames are converted and go through frames_to_input's
     own fallback."""
     yuv420_layout(layout)
-    m = nv12_matrix_id(matrix)
+    m = yuv_matrix_id(matrix)
     checked, _ = _yuv420_planes(planes, layout, 'yuv420_to_input')
     B, H, W = checked[0].shape
     out, _, _, taps, tail = _input_window('yuv420_to_input', B, H, W, checked[0].device, geometry, input_format, out)
@@ -1546,6 +1497,22 @@ def yuv420_to_input(planes, layout, geometry, input_format, matrix='bt601', full
     code = _lib.lib().mydet_yuv420_to_input_f32(ctypes.byref(src), B, H, W, *tail, _stream())
     _lib.check(code, 'mydet_yuv420_to_input_f32')
     return out
+
+
+def nv12_to_rgb(y, uv, matrix='bt601', full_range=False, out=None):
+    """NV12 frames on the device -> packed uint8 RGB [B,H,W,3] ([H,W,3] for a 2-d y) (include/mydet.h: mydet_nv12_to_rgb_u8,
+    where the formula and the coefficient table are).  y: uint8 [B,H,W] or [H,W], element stride 1 along W; uv: uint8
+    [B,ceil(H/2),ceil(W/2),2], last two dimensions packed; any row and frame strides, read in place.  matrix: 'bt601' or
+    'bt709'; full_range: Y in 0..255 instead of 16..235.  out: optional uint8 [B,H,W,3] view with packed pixels."""
+    return yuv420_to_rgb((y, uv), 'nv12', matrix, full_range, out)
+
+
+def nv12_to_input(y, uv, geometry, input_format, matrix='bt601', full_range=False, out=None):
+    """NV12 frames of one size on the device -> the float32 network input [B,3,Hp,Wp] in ONE launch (include/mydet.h:
+    mydet_nv12_to_input_f32): the bits of frames_to_input(nv12_to_rgb(y, uv, matrix, full_range), geometry, input_format)
+    without the RGB frames.  y, uv, matrix, full_range as in nv12_to_rgb; geometry, input_format, out and the tap limit as
+    in frames_to_input -- past the limit the frames are converted and go through frames_to_input's own fallback."""
+    return yuv420_to_input((y, uv), 'nv12', geometry, input_format, matrix, full_range, out)
 
 
 def records_to_original_(rec, pad_infos):

@@ -155,7 +155,7 @@ def test_fused_launch_with_the_other_table_rows(matrix, full_range, fmt):
 
 @pytest.mark.parametrize('fmt', FORMATS)
 def test_tap_limit_fallback(fmt, monkeypatch):
-    """144 x 72 -> 16 x 8 has two taps more than the kernel stages: the planes are converted (ops.nv12_to_rgb) and take the RGB
+    """144 x 72 -> 16 x 8 has two taps more than the kernel stages: the planes are converted (ops.yuv420_to_rgb) and take the RGB
     path's own fallback -- the bits frames_to_input gives for the numpy-converted frames."""
     from mydetection_amd import _lib, ops
     assert _taps(144, 16) == _lib.FRAMES_MAX_TAPS + 2
@@ -163,8 +163,8 @@ def test_tap_limit_fallback(fmt, monkeypatch):
     y, uv = _nv12_ref.random_nv12(2, 144, 72, seed=144)
     want = ops.frames_to_input(torch.from_numpy(_nv12_ref.nv12_to_rgb(y, uv)).cuda(), geo, fmt)
     calls = []
-    real = ops.nv12_to_rgb
-    monkeypatch.setattr(ops, 'nv12_to_rgb', lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    real = ops.yuv420_to_rgb
+    monkeypatch.setattr(ops, 'yuv420_to_rgb', lambda *a, **k: (calls.append(1), real(*a, **k))[1])
     yd, uvd = _layouts(y, uv)['pitched']
     got = ops.nv12_to_input(yd, uvd, geo, fmt)
     assert calls == [1] and torch.equal(got, want)

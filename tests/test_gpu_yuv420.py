@@ -186,14 +186,27 @@ def test_torch_uint16_planes_are_the_same_bits():
 
 @pytest.mark.parametrize('case', ['up_37x53_odd_origin', 'down3_120x200_to_40x67'])
 def test_nv12_through_the_new_entry_points_equals_the_nv12_ops(case):
-    from mydetection_amd import ops
+    """The two mydet_nv12_* C entry points, which no Python op calls, through ctypes on the tensors' pointers and byte strides:
+    the bits ops.yuv420_to_rgb / ops.yuv420_to_input give for layout 'nv12' (and those the restatement gives)."""
+    from mydetection_amd import _lib, ops
+    lib = _lib.lib()
     y, uv, rgb, geo = _case(case)
     for name, (yd, uvd) in _layouts((y, uv), 'nv12').items():
-        assert torch.equal(ops.yuv420_to_rgb((yd, uvd), 'nv12'), ops.nv12_to_rgb(yd, uvd)), name
-        assert torch.equal(ops.yuv420_to_rgb((yd, uvd), 'nv12', 'bt709', True), ops.nv12_to_rgb(yd, uvd, 'bt709', True)), name
-        assert torch.equal(ops.nv12_to_rgb(yd, uvd).cpu(), torch.from_numpy(rgb[:yd.shape[0]])), name
+        B, H, W = yd.shape
+        src = (yd.data_ptr(), yd.stride(0), yd.stride(1), uvd.data_ptr(), uvd.stride(0), uvd.stride(1), B, H, W)
+        for matrix, full_range in (('bt601', False), ('bt709', True)):
+            got = torch.full((B, H, W, 3), 0x5A, dtype=torch.uint8, device='cuda')
+            code = lib.mydet_nv12_to_rgb_u8(*src, got.data_ptr(), got.stride(0), got.stride(1), ops.yuv_matrix_id(matrix), int(full_range),
+                                            ops._stream())
+            assert code == 0 and torch.equal(got, ops.yuv420_to_rgb((yd, uvd), 'nv12', matrix, full_range)), (name, matrix)
+        assert torch.equal(got.cpu(), torch.from_numpy(_case(case, 'bt709', True)[2][:B])), name
+        assert torch.equal(ops.nv12_to_rgb(yd, uvd).cpu(), torch.from_numpy(rgb[:B])), name
         for fmt in FORMATS:
-            assert torch.equal(ops.yuv420_to_input((yd, uvd), 'nv12', geo, fmt), ops.nv12_to_input(yd, uvd, geo, fmt)), (name, fmt)
+            out, _, _, taps, tail = ops._input_window('nv12', B, H, W, yd.device, geo, fmt, None)
+            assert taps <= _lib.FRAMES_MAX_TAPS
+            out.fill_(float('nan'))
+            code = lib.mydet_nv12_to_input_f32(*src, 0, 0, *tail, ops._stream())
+            assert code == 0 and torch.equal(out, ops.yuv420_to_input((yd, uvd), 'nv12', geo, fmt)), (name, fmt)
 
 
 @pytest.mark.parametrize('layout', ['nv21', 'yv12', 'i010'])

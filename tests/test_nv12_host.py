@@ -1,4 +1,4 @@
-"""CPU tests of the NV12 input path: Detector._nv12_planes (plane splitting and validation, no device), the C ABI of
+"""CPU tests of the NV12 input path: Detector._yuv_planes for layout 'nv12' (plane splitting and validation, no device), the C ABI of
 mydet_nv12_to_rgb_u8 / mydet_nv12_to_input_f32 (exported, declared, bound, argument checks before any launch), and that an
 unknown matrix name is refused before any device is touched."""
 import ctypes
@@ -14,9 +14,9 @@ from test_frames_host import _header, _meta_detector
 NAMES = ('mydet_nv12_to_rgb_u8', 'mydet_nv12_to_input_f32')
 
 
-def _planes(*a, **k):
+def _planes(y, uv=None, device=None):
     from mydetection_amd.api import Detector
-    return Detector._nv12_planes(*a, **k)
+    return Detector._yuv_planes(y if uv is None else (y, uv), 'nv12', device)
 
 
 def test_the_reference_table_is_the_rounded_matrices():
@@ -50,7 +50,7 @@ def test_planes_reject_wrong_shapes():
     with pytest.raises(ValueError, match=r'\(1, 4, 4, 2\) expected'):
         _planes(u8(8, 8), u8(4, 4))
     for bad_surface in (u8(2, 13, 8), u8(14, 8), u8(2, 12, 7), u8(8, 8)):        # rows != 3H/2, odd H (9 + 5 rows), odd W
-        with pytest.raises(ValueError, match='single NV12 surface'):
+        with pytest.raises(ValueError, match="single 'nv12' surface"):
             _planes(bad_surface)
 
 
@@ -141,7 +141,7 @@ def test_unknown_matrix_is_refused_before_any_device_is_touched():
         det.frames_nv12_to_json(y, uv, [0], matrix='rec709')
     with pytest.raises(TypeError, match='float32'):                              # and bad planes, on a meta-device model
         det.predict_frames_nv12(np.zeros((12, 8), np.float32))
-    with pytest.raises(ValueError, match='single NV12 surface'):
+    with pytest.raises(ValueError, match="single 'nv12' surface"):
         det.predict_frames_nv12(np.zeros((13, 8), np.uint8))
 
 

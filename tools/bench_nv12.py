@@ -51,7 +51,7 @@ def main():
     n_nv12, n_rgb = -(-300 * 2 ** 20 // nv12_bytes), -(-300 * 2 ** 20 // rgb_bytes)
     # single surfaces [B, H*3/2, W], as a decoder hands them over; the planes are views
     surfaces = [torch.from_numpy(rng.integers(0, 256, size=(B, H * 3 // 2, W), dtype=np.uint8)).to(dev) for _ in range(n_nv12)]
-    planes = [Detector._nv12_planes(s) for s in surfaces]
+    planes = [Detector._yuv_planes(s, 'nv12') for s in surfaces]
     rgbs = [ops.nv12_to_rgb(*planes[i % n_nv12]) for i in range(n_rgb)]
     turn = [0]
 

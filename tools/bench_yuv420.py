@@ -12,7 +12,9 @@ The method is tools/bench_nv12.py's: (a), (b) and (c) of a layout are compared b
 samples n, n', and a, b, c of every layout (n' is n again: the spread of two runs of the same code), each sample = `reps`
 back-to-back calls between two device events; medians.  The frames rotate through enough device buffers to exceed the
 256 MiB Infinity Cache, so the source comes from HBM.  Bytes per launch are computed from the shapes (source read once,
-output written once); the torch repack of (b) moves at least the bytes listed (its intermediates are not counted)."""
+output written once); the torch repack of (b) moves at least the bytes listed (its intermediates are not counted).
+ops.nv12_to_input is ops.yuv420_to_input with layout 'nv12', so (n) takes the Python path and the C entry point of (a): the
+two differ in the kernel instance and the bytes read alone."""
 import argparse
 import json
 import os
