@@ -422,6 +422,44 @@ int mydet_postprocess_records_rotnms_f32(const float *bbox, const int64_t *class
                                          int B, int64_t N, float conf_thres, double nms_thres,
                                          int32_t *records, void *scratch, void *stream);
 
+/* Merge of tile records: tiled ("sliced") detection on large frames.  The detector ran on T windows of each of B frames
+ * (overlapping tiles at native resolution, optionally the whole frame as one more window); this call turns the B x T
+ * per-window records into B per-frame records with one more class-aware NMS in frame coordinates.  No reference counterpart.
+ * In : the record of window t of frame b at tile_records + t*tile_stride_words + b*frame_stride_words: a record of
+ *      MYDET_REC_WORDS (box_width 4) or MYDET_REC_ROT_WORDS (box_width 5) words whose boxes are in the window's own pixel
+ *      coordinates (the state after mydet_bboxes_to_original_batched_f32).  Tile-major [T][B] and frame-major [B][T] buffers
+ *      are both strides of this form.  origins: DEVICE int32 [T][2] = (x0, y0) of each window in the frame.
+ * Candidates: frame b has T*512 of them.  Candidate t*512 + k, k < count[b,t], is slot k of that record with
+ *      cx + (float)x0_t and cy + (float)y0_t (one float32 add each); w, h, angle, score and class unchanged.  Slots
+ *      k >= count carry a NaN score and are never selected.  If any window of a frame has count == MYDET_COUNT_BAD_CLASS,
+ *      so has the frame's record.
+ * Out: records [B], wire layout, exactly what mydet_postprocess_records_f32 (box_width 4), mydet_postprocess_records_rot_f32
+ *      (5) or, with rotated_nms != 0, mydet_postprocess_records_rotnms_f32 gives on those candidates with conf_thres = -inf:
+ *      top-k 512 by (score descending, candidate index ascending) -- on a score tie the earlier window wins --, the
+ *      class-aware greedy NMS, output order class ascending then score descending, every slot past the count zero.
+ *      INDEX holds t*512 + k: window index >> 9 and slot index & 511 of every survivor.  records must not overlap
+ *      tile_records.
+ * metric: the pair test of the axis-aligned NMS.
+ *      MYDET_MERGE_IOU  inter / (area_i + area_j - inter), the test of mydet_postprocess_f32.
+ *      MYDET_MERGE_IOS  "intersection over smaller": inter / fminf(area_i, area_j) in float32, inter and the areas computed
+ *                       in the same operation order as for the IoU; a box is suppressed when (double)value > nms_thres; two
+ *                       boxes without area give 0/0 and are not suppressed.  It merges an object cut by a window seam: the
+ *                       truncated box lies inside the whole one, so its IoU is small and its IoS about 1.
+ *      MYDET_MERGE_IOS with rotated_nms is MYDET_E_UNSUPP.
+ * scratch: mydet_merge_tile_records_scratch_bytes(B, T, box_width) bytes (the candidate arrays and the selection's key
+ *      strip; 0 for arguments the merge rejects), 16-byte aligned; the call is two launches on `stream` (a gather of the
+ *      candidates, then the post-process kernel itself) and stream-ordered.
+ * MYDET_E_BADARG: B <= 0; T outside [1, MYDET_TILES_MAX]; box_width not 4 or 5; an unknown metric; rotated_nms with
+ *      box_width 4; a null pointer; tile_records, records or scratch not 16-byte aligned; a stride that is negative or no
+ *      multiple of 4 words; scratch_bytes too small. */
+#define MYDET_TILES_MAX 64
+#define MYDET_MERGE_IOU 0
+#define MYDET_MERGE_IOS 1
+int64_t mydet_merge_tile_records_scratch_bytes(int B, int T, int box_width);
+int mydet_merge_tile_records_f32(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words,
+                                 int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
+                                 int rotated_nms, int32_t *records, void *scratch, int64_t scratch_bytes, void *stream);
+
 /* Winograd F(4x4,3x3) form of the same 3x3 stride-1 pad-1 conv + BN + act (+ residual) as mydet_conv2d_wino_f32
  * (4x fewer multiplies than the direct form; used for the deep layers with chip-filling grids).  `u` = the
  * transform-domain weights made by mydet_wino4_weights_f32 from the OHWI weight (mydet_wino4_weights_floats(Cout, Cin)

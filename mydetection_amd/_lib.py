@@ -69,6 +69,8 @@ SIGNATURES = {
                                      c_ptr, c_ptr, c_ptr],
     'mydet_postprocess_records_rotnms_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_ptr, c_ptr, c_ptr],
     'mydet_rotated_iou_f32': [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr],
+    'mydet_merge_tile_records_scratch_bytes': [c_int, c_int, c_int],
+    'mydet_merge_tile_records_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_f64, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr],
     'mydet_mbconv_tiles': [c_int, c_int, c_int],
     'mydet_mbconv_expand_dw_f32': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64] + [c_int] * 11 + [c_ptr, c_int, c_ptr, c_ptr],
     'mydet_sepconv_nodes_f32': [c_int, c_ptr, c_int, c_int, c_ptr],
@@ -97,7 +99,8 @@ SIGNATURES = {
 
 
 
-RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems'}
+RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems',
+               'mydet_merge_tile_records_scratch_bytes'}
 
 # detection record layout (MYDET_REC_* of include/mydet.h), in int32 words
 REC_TOPK = 512
@@ -109,6 +112,9 @@ REC_WORDS = REC_INDEX + REC_TOPK
 # rotated record (bb_format 'cxcywhd'): the same fields at the same offsets + one angle plane behind them
 REC_ANGLE = REC_WORDS
 REC_ROT_WORDS = REC_WORDS + REC_TOPK
+# merge of tile records (mydet_merge_tile_records_f32): MYDET_TILES_MAX windows per frame, MYDET_MERGE_* pair tests
+TILES_MAX = 64
+MERGE_IOU, MERGE_IOS = 0, 1
 
 
 class DecodeLevel(ctypes.Structure):

@@ -1,4 +1,5 @@
-"""Inference entry point of the package: `Detector` (mirror of the reference's api.detection.Detector)."""
-from .detection import Detector
+"""Inference entry point of the package: `Detector` (mirror of the reference's api.detection.Detector) and `Tiles`, the
+argument of its tiled detection on large frames."""
+from .detection import Detector, Tiles
 
-__all__ = ['Detector']
+__all__ = ['Detector', 'Tiles']

@@ -16,6 +16,31 @@ from ..utils import image_ops as imgUtils
 from ..utils.structures import ImageObjects
 
 
+class Tiles:
+    """Tiled ("sliced") detection on large frames, the `tiles=` argument of Detector.predict_frames and its YUV / json forms:
+    the detector runs on overlapping windows of the frame at native resolution (ops.tile_windows: tiles of `size` = (h, w)
+    or one int, clipped to the frame, `overlap` a fraction of the tile) and, with `full_frame`, on the whole frame as well;
+    one more class-aware NMS on the device merges the windows' detections in frame coordinates (ops.merge_tile_records).
+    nms_thres: the threshold of that merge (None: the call's nms_thres).  metric: its pair test, 'iou' or 'ios' --
+    intersection over the smaller area, which also merges an object cut by a window seam with its whole view in the next
+    window (not with rotated_nms)."""
+    _align = 1                        # origins and sizes are multiples of this; the 4:2:0 methods use 2 at least
+
+    def __init__(self, size, overlap=0.2, full_frame=True, nms_thres=None, metric='iou'):
+        self.size = (int(size), int(size)) if isinstance(size, int) else tuple(int(v) for v in size)
+        if len(self.size) != 2 or min(self.size) < 1:
+            raise ValueError(f'Tiles: size = (h, w) with positive entries expected, got {size!r}')
+        if not 0 <= overlap < 1:
+            raise ValueError(f'Tiles: overlap {overlap!r} is outside [0, 1)')
+        ops.merge_metric_id(metric)
+        self.overlap, self.full_frame, self.metric = float(overlap), bool(full_frame), metric
+        self.nms_thres = None if nms_thres is None else float(nms_thres)
+
+    def __repr__(self):
+        return (f'Tiles({self.size}, overlap={self.overlap}, full_frame={self.full_frame}, nms_thres={self.nms_thres}, '
+                f'metric={self.metric!r})')
+
+
 class Detector():
     '''Wrapper for image object detectors
 
@@ -272,7 +297,10 @@ class Detector():
         """Detection records of uint8 frames: yields (indices, records) per network input size, like _records_by_size (same
         batches in the same order, so the same bits).  Frames of one size on the host cross to the device in one copy,
         frames on the device are read in place; one fused launch (ops.frames_to_input) per frame size builds their
-        network input."""
+        network input.  tiles: a Tiles, or None (see predict_frames)."""
+        tiles = kwargs.pop('tiles', None)
+        if tiles is not None:
+            return self._tiled_frame_records(frames, tiles, **kwargs)
         _, groups = self._frame_groups(frames)
 
         def rgb_input(parts):
@@ -318,12 +346,85 @@ class Detector():
             rec['img_hw'] = hws
             yield idxs, rec
 
+    def _check_tiles(self, tiles, kwargs):
+        """The argument rules of a tiled call that need no frame: touches no device."""
+        if not isinstance(tiles, Tiles):
+            raise TypeError(f'tiles: a mydetection_amd.api.Tiles (or None) expected, got {type(tiles).__name__}')
+        if tiles.metric == 'ios' and bool(kwargs.get('rotated_nms', self.rotated_nms)):
+            raise ValueError("tiles: metric 'ios' is defined for the axis-aligned test only, not with rotated_nms")
+
+    def _tiled_frame_records(self, frames, tiles, **kwargs):
+        """_frame_records with tiles: uint8 frames of ONE size; every window is a crop view of the frames on the device, read
+        in place by its input launch."""
+        self._check_tiles(tiles, kwargs)
+        n, groups = self._frame_groups(frames)
+        if len(groups) != 1:
+            raise ValueError('predict_frames: a tiled call takes frames of one size, got '
+                             f'{[tuple(parts[0].shape[1:3]) for _, parts in groups]}')
+        parts = groups[0][1]
+        H, W = parts[0].shape[1:3]
+        windows = ops.tile_windows(H, W, tiles.size, tiles.overlap, tiles.full_frame, tiles._align)
+        dev = next(self.model.parameters()).device
+        if len(parts) > 1:                                           # a list: gather it where it already is
+            where = dev if all(t.device == dev for t in parts) else torch.device('cpu')
+            parts = [torch.cat([t.to(where) for t in parts])]
+        fr = parts[0].to(dev, non_blocking=True)
+
+        def window_input(win, geo, out):
+            y0, x0, h, w = win
+            ops.frames_to_input(fr[:, y0:y0 + h, x0:x0 + w], geo, self.model.input_format, out=out)
+        return self._records_of_windows(n, (H, W), windows, window_input, tiles, **kwargs)
+
+    def _records_of_windows(self, B, hw, windows, window_input, tiles, **kwargs):
+        """The part of a tiled call that does not depend on the pixel format: [(frame indices, merged records)] of B frames
+        of size hw.  windows: ops.tile_windows' list; window_input(window, geometry, out) writes the network input of all B
+        frames' crops at that window into `out`.  Windows of one network input size are one [n*B,3,Hp,Wp] batch, window-major,
+        built in place; the full-frame window joins the tiles' batch when its input size equals theirs and is a second
+        batch otherwise.  Forward and post-process are self._records (graph capture by shape as everywhere), then the boxes
+        go back to window pixels and ONE merge launch pair makes the B frame records."""
+        pre_proc = kwargs.get('preprocessing', self.preprocess)
+        input_size = kwargs.get('input_size', self.input_size)
+        conf_thres = kwargs.get('conf_thres', self.conf_thres)
+        nms_thres = kwargs.get('nms_thres', self.nms_thres)
+        rotated_nms = bool(kwargs.get('rotated_nms', self.rotated_nms))
+        if rotated_nms and self.model.bb_format != 'cxcywhd':
+            raise ValueError(f"rotated_nms needs a 'cxcywhd' model; this one predicts {self.model.bb_format!r}")
+        dev = next(self.model.parameters()).device
+        T = len(windows)
+        by_input = {}
+        for i, (_, _, h, w) in enumerate(windows):
+            geo = self._geometry(h, w, pre_proc, input_size)
+            by_input.setdefault(geo[2], []).append((i, geo))
+        batches = []
+        for (Hp, Wp), members in by_input.items():
+            x = torch.empty((len(members) * B, 3, Hp, Wp), dtype=torch.float32, device=dev)
+            for n, (i, geo) in enumerate(members):
+                window_input(windows[i], geo, x[n * B:(n + 1) * B])
+            # the views of ONE buffer (a graph replay hands out the fields as separate copies)
+            rec = ops.record_views(self._records(x, conf_thres, nms_thres, rotated_nms)['records'])
+            pads = [geo[3] for _, geo in members for _ in range(B)]
+            if any(p is not None for p in pads):
+                ops.records_to_original_(rec, pads)
+            batches.append(([i for i, _ in members], rec['records']))
+        tile_records = batches[0][1]
+        if len(batches) > 1:                                         # window order again: records only, 16 KiB each
+            tile_records = tile_records.new_empty((T, B, tile_records.shape[1]))
+            for idx, r in batches:
+                tile_records[idx] = r.view(len(idx), B, -1)
+        merged = ops.merge_tile_records(tile_records, B, T, [(x0, y0) for y0, x0, _, _ in windows],
+                                        nms_thres if tiles.nms_thres is None else tiles.nms_thres, tiles.metric, rotated_nms)
+        merged['img_hw'] = [tuple(hw)] * B
+        return [(list(range(B)), merged)]
+
     def predict_frames(self, frames, **kwargs):
         """predict_batch for decoded video: `frames` is a torch.uint8 tensor or numpy.uint8 array [B,H,W,3] (or [H,W,3]) in
         RGB order, on the host or already on the device, or a list of such frames (grouped by size).  No PIL object and no
         per-frame copy or launch: resize, padding, /255 and normalisation of a whole group are one HIP launch that gives
         the bits of preprocess_batch, so the detections equal predict_batch on PIL.Image.fromarray of the same frames.
-        Keyword arguments as in _predict_pil.  Returns a list of ImageObjects in original-frame coordinates."""
+        Keyword arguments as in _predict_pil, and tiles: None, or a Tiles for tiled detection on large frames (frames of one
+        size): every window's input is one launch over a crop view of all frames, the windows of one size are one forward
+        batch, and one more NMS on the device merges their detections in frame coordinates (include/mydet.h:
+        mydet_merge_tile_records_f32).  Returns a list of ImageObjects in original-frame coordinates."""
         return self._objects_of_records(self._frame_records(frames, **kwargs))
 
     def _objects_of_records(self, records):
@@ -402,9 +503,23 @@ class Detector():
 
     def _yuv_records(self, planes, layout, matrix, full_range, **kwargs):
         """_frame_records for 4:2:0 frames of one size: one fused launch (ops.yuv420_to_input) builds the network input from
-        the planes; everything after it is _records_of_inputs, as for RGB frames."""
+        the planes; everything after it is _records_of_inputs, as for RGB frames.  tiles: a Tiles, or None (see
+        predict_frames): windows with even origins and sizes, so every window of the planes is itself a 4:2:0 frame."""
+        tiles = kwargs.pop('tiles', None)
         ops.yuv420_layout(layout)
         ops.yuv_matrix_id(matrix)
+        if tiles is not None:
+            self._check_tiles(tiles, kwargs)
+            y = self._yuv_planes(planes, layout)[0]                  # the checks alone: no device is touched
+            B, H, W = y.shape
+            windows = ops.tile_windows(H, W, tiles.size, tiles.overlap, tiles.full_frame, tiles._align * (2 if tiles._align % 2 else 1))
+            ts = self._yuv_planes(planes, layout, device=next(self.model.parameters()).device)
+
+            def window_input(win, geo, out):
+                y0, x0, h, w = win
+                crop = [ts[0][:, y0:y0 + h, x0:x0 + w]] + [t[:, y0 // 2:(y0 + h) // 2, x0 // 2:(x0 + w) // 2] for t in ts[1:]]
+                ops.yuv420_to_input(crop, layout, geo, self.model.input_format, matrix, full_range, out=out)
+            return self._records_of_windows(B, (H, W), windows, window_input, tiles, **kwargs)
         ts = tuple(self._yuv_planes(planes, layout, device=next(self.model.parameters()).device))
 
         def build(geo, dev):
@@ -419,7 +534,8 @@ class Detector():
         surface, device tensors are read in place through their strides.  A 10-bit sample becomes 8 bits by
         min(255, (v + 2) >> 2); from there the conversion is NV12's (include/mydet.h).  Returns exactly what
         predict_frames returns for the converted RGB frames (ops.yuv420_to_rgb), which are never built: one HIP launch
-        reads the planes.  One call takes one frame size.  Keyword arguments as in _predict_pil."""
+        reads the planes.  One call takes one frame size.  Keyword arguments as in _predict_pil and predict_frames (tiles:
+        even frame and tile sizes)."""
         return self._objects_of_records(self._yuv_records(planes, layout, matrix, full_range, **kwargs))
 
     def frames_yuv_to_json(self, planes, layout, img_ids, eval_type='x1y1wh', catIdx2id=None, *, matrix='bt601', full_range=False,

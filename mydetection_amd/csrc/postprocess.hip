@@ -28,6 +28,8 @@
 // pair test alone: the IoU is the exact area of intersection of the two ROTATED rectangles (rot_iou.h) and a pair is
 // suppressed when (double)IoU >= thr -- the `>=` of the reference's nms_rotbb (utils/bbox_ops.py:290).  Every other step
 // is shared, so the order, the tie rule and the record layout are those of the <5, false> instance.
+// The third template parameter IOS (axis-aligned pair test only; the merge of tile records below) divides the intersection
+// by the smaller of the two areas instead of by the union.
 #include "common.h"
 #include "rot_iou.h"
 
@@ -64,9 +66,10 @@ __device__ __forceinline__ unsigned sortable(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-template <int BW, bool ROT>
+template <int BW, bool ROT, bool IOS = false>
 __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
     static_assert(!ROT || BW == 5, "the rotated IoU needs the angle column");
+    static_assert(!(ROT && IOS), "intersection over smaller is defined for the axis-aligned test only");
     __shared__ unsigned long long s_key[KMAX];
     __shared__ unsigned long long s_mask[KMAX * 8];
     // ROT: the seven planes of rotiou::Box -- s_x1, s_y1 = centre, s_x2, s_y2 = hori, s_vx, s_vy = verti, s_area
@@ -324,7 +327,9 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
                     const float xx2 = fminf(ix2, s_x2[j]), yy2 = fminf(iy2, s_y2[j]);
                     const float ww = fmaxf(0.0f, xx2 - xx1), hh = fmaxf(0.0f, yy2 - yy1);
                     const float inter = ww * hh;
-                    const float ovr = inter / (ia + s_area[j] - inter);
+                    float ovr;
+                    if constexpr (IOS) ovr = inter / fminf(ia, s_area[j]);       // 0/0 (two boxes without area): NaN, not suppressed
+                    else ovr = inter / (ia + s_area[j] - inter);
                     sup = (double)ovr > p.nms;
                 }
                 const unsigned long long bits = __ballot(sup);
@@ -485,7 +490,20 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
 
 }  // namespace
 
-template <int BW, bool ROT = false>
+// the fields of a wire record (MYDET_REC_*; rot: the rotated record with its angle plane) as the outputs of the kernel
+static void record_outputs(PPArgs &p, int32_t *records, bool rot) {
+    const int64_t words = rot ? MYDET_REC_ROT_WORDS : MYDET_REC_WORDS;
+    p.count = records + MYDET_REC_COUNT;
+    p.obox = reinterpret_cast<float *>(records + MYDET_REC_BBOX);
+    p.oscore = reinterpret_cast<float *>(records + MYDET_REC_SCORE);
+    p.ocls = reinterpret_cast<int64_t *>(records + MYDET_REC_CLASS);
+    p.oidx = records + MYDET_REC_INDEX;
+    p.oang = rot ? reinterpret_cast<float *>(records + MYDET_REC_ANGLE) : nullptr;
+    p.count_pad = MYDET_REC_BBOX - 1; p.count_st = words; p.obox_st = words; p.oscore_st = words;
+    p.ocls_st = words / 2; p.oidx_st = words; p.oang_st = rot ? words : 0;
+}
+
+template <int BW, bool ROT = false, bool IOS = false>
 static int launch_postprocess(PPArgs &p, const float *bbox, const int64_t *class_idx, const float *score, int B, int64_t N,
                               float conf_thres, double nms_thres, int topk, void *scratch, void *stream) {
     if (B <= 0 || N < 0 || topk <= 0 || topk > KMAX) return MYDET_E_BADARG;
@@ -495,7 +513,7 @@ static int launch_postprocess(PPArgs &p, const float *bbox, const int64_t *class
     if (((uintptr_t)bbox & 15) || ((uintptr_t)p.obox & 15) || ((uintptr_t)scratch & 7) || ((uintptr_t)p.ocls & 7)) return MYDET_E_BADARG;
     p.bbox = bbox; p.cidx = class_idx; p.score = score; p.N = N; p.conf = conf_thres; p.nms = nms_thres;
     p.topk = topk; p.scratch = (unsigned long long *)scratch;
-    hipLaunchKernelGGL((postprocess_kernel<BW, ROT>), dim3(B), dim3(NT), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((postprocess_kernel<BW, ROT, IOS>), dim3(B), dim3(NT), 0, (hipStream_t)stream, p);
     return mydet_launch_status();
 }
 
@@ -518,13 +536,7 @@ extern "C" int mydet_postprocess_records_f32(const float *bbox, const int64_t *c
     p.oang = nullptr; p.oang_st = 0;
     if (!records) { p.count = nullptr; p.obox = nullptr; p.ocls = nullptr; p.oscore = nullptr; p.oidx = nullptr;
                     return launch_postprocess<4>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream); }
-    p.count = records + MYDET_REC_COUNT;
-    p.obox = reinterpret_cast<float *>(records + MYDET_REC_BBOX);
-    p.oscore = reinterpret_cast<float *>(records + MYDET_REC_SCORE);
-    p.ocls = reinterpret_cast<int64_t *>(records + MYDET_REC_CLASS);
-    p.oidx = records + MYDET_REC_INDEX;
-    p.count_pad = MYDET_REC_BBOX - 1; p.count_st = MYDET_REC_WORDS; p.obox_st = MYDET_REC_WORDS; p.oscore_st = MYDET_REC_WORDS;
-    p.ocls_st = MYDET_REC_WORDS / 2; p.oidx_st = MYDET_REC_WORDS;
+    record_outputs(p, records, false);
     return launch_postprocess<4>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream);
 }
 
@@ -544,15 +556,7 @@ extern "C" int mydet_postprocess_records_rot_f32(const float *bbox, const int64_
                                                  void *scratch, void *stream) {
     if (!records || ((uintptr_t)records & 15)) return MYDET_E_BADARG;
     PPArgs p;
-    p.count = records + MYDET_REC_COUNT;
-    p.obox = reinterpret_cast<float *>(records + MYDET_REC_BBOX);
-    p.oscore = reinterpret_cast<float *>(records + MYDET_REC_SCORE);
-    p.ocls = reinterpret_cast<int64_t *>(records + MYDET_REC_CLASS);
-    p.oidx = records + MYDET_REC_INDEX;
-    p.oang = reinterpret_cast<float *>(records + MYDET_REC_ANGLE);
-    p.count_pad = MYDET_REC_BBOX - 1; p.count_st = MYDET_REC_ROT_WORDS; p.obox_st = MYDET_REC_ROT_WORDS;
-    p.oscore_st = MYDET_REC_ROT_WORDS; p.ocls_st = MYDET_REC_ROT_WORDS / 2; p.oidx_st = MYDET_REC_ROT_WORDS;
-    p.oang_st = MYDET_REC_ROT_WORDS;
+    record_outputs(p, records, true);
     return launch_postprocess<5>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream);
 }
 
@@ -574,14 +578,106 @@ extern "C" int mydet_postprocess_records_rotnms_f32(const float *bbox, const int
                                                     void *scratch, void *stream) {
     if (!records || ((uintptr_t)records & 15)) return MYDET_E_BADARG;
     PPArgs p;
-    p.count = records + MYDET_REC_COUNT;
-    p.obox = reinterpret_cast<float *>(records + MYDET_REC_BBOX);
-    p.oscore = reinterpret_cast<float *>(records + MYDET_REC_SCORE);
-    p.ocls = reinterpret_cast<int64_t *>(records + MYDET_REC_CLASS);
-    p.oidx = records + MYDET_REC_INDEX;
-    p.oang = reinterpret_cast<float *>(records + MYDET_REC_ANGLE);
-    p.count_pad = MYDET_REC_BBOX - 1; p.count_st = MYDET_REC_ROT_WORDS; p.obox_st = MYDET_REC_ROT_WORDS;
-    p.oscore_st = MYDET_REC_ROT_WORDS; p.ocls_st = MYDET_REC_ROT_WORDS / 2; p.oidx_st = MYDET_REC_ROT_WORDS;
-    p.oang_st = MYDET_REC_ROT_WORDS;
+    record_outputs(p, records, true);
     return launch_postprocess<5, true>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream);
+}
+
+// ---- merge of tile records (tiled detection on large frames; include/mydet.h) ----
+// The detections of T windows of a frame, already in window pixel coordinates, become the candidates of ONE more run of the
+// kernel above: a gather launch writes the B x T*512 candidate arrays into scratch (box centres shifted by the window origin),
+// then postprocess_kernel runs on them with conf = -inf.  Nothing of the selection or the NMS is restated here.
+namespace {
+
+struct MergeArgs {
+    const int32_t *rec;               // record of tile t of frame b at rec + t*tile_st + b*frame_st (words)
+    int64_t tile_st, frame_st;
+    const int32_t *origins;           // [T][2] = (x0, y0)
+    int T;
+    float *bbox;                      // [B][T*512][BW]
+    int64_t *cidx;                    // [B][T*512]
+    float *score;                     // [B][T*512]
+};
+
+// One thread per candidate slot (b = blockIdx.y, t*512 + k = blockIdx.x * 256 + tid): lane k reads the 16-byte box row k of
+// the tile's box plane and writes the 16-byte candidate row k -- 1 KiB per wave instruction either way.  Slots past the
+// tile's count get a NaN score (it fails `>=` against every threshold), box 0 and class 0, so every word of the candidate
+// arrays is defined.  A tile whose count is the bad-class sentinel plants ONE candidate with score +inf and class -1 in its
+// slot 0: it is among the top 512 whatever else the frame holds, and the kernel above then fails the frame the way it fails
+// any image with such a class (count = MYDET_COUNT_BAD_CLASS, zero rows).
+template <int BW>
+__global__ __launch_bounds__(256) void merge_gather_kernel(const MergeArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;          // grid.x * 256 == T * 512 exactly
+    const int t = i >> 9, k = i & (KMAX - 1);
+    const int b = blockIdx.y;
+    const int32_t *r = a.rec + (int64_t)t * a.tile_st + (int64_t)b * a.frame_st;
+    const int count = r[MYDET_REC_COUNT];
+    const int64_t o = (int64_t)b * a.T * KMAX + i;
+    f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+    float ang = 0.f, sc = __uint_as_float(0x7FC00000u);
+    int64_t c = 0;
+    if (count < 0) {
+        if (k == 0) { sc = __uint_as_float(0x7F800000u); c = -1; }
+    } else if (k < count) {                                // a count above 512 cannot come from the kernel above; k < 512 anyway
+        v = *reinterpret_cast<const f32x4 *>(r + MYDET_REC_BBOX + 4 * k);
+        v[0] = v[0] + (float)a.origins[2 * t];
+        v[1] = v[1] + (float)a.origins[2 * t + 1];
+        sc = reinterpret_cast<const float *>(r + MYDET_REC_SCORE)[k];
+        c = reinterpret_cast<const int64_t *>(r + MYDET_REC_CLASS)[k];
+        if constexpr (BW == 5) ang = reinterpret_cast<const float *>(r + MYDET_REC_ANGLE)[k];
+    }
+    if constexpr (BW == 4) {
+        *reinterpret_cast<f32x4 *>(a.bbox + o * 4) = v;
+    } else {                                               // 20-byte rows are not 16-byte aligned: five dword stores
+        float *d = a.bbox + o * 5;
+        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3]; d[4] = ang;
+    }
+    a.cidx[o] = c;
+    a.score[o] = sc;
+}
+
+}  // namespace
+
+// candidate arrays + the key strip of postprocess_kernel: per candidate BW floats, an int64 class, a float score, an 8-byte key
+// (every part a multiple of 16 bytes: B * T * 512 candidates)
+extern "C" int64_t mydet_merge_tile_records_scratch_bytes(int B, int T, int box_width) {
+    if (B <= 0 || T < 1 || T > MYDET_TILES_MAX || (box_width != 4 && box_width != 5)) return 0;
+    return (int64_t)B * T * KMAX * (4 * box_width + 8 + 4 + 8);
+}
+
+extern "C" int mydet_merge_tile_records_f32(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words,
+                                            int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
+                                            int rotated_nms, int32_t *records, void *scratch, int64_t scratch_bytes, void *stream) {
+    if (B <= 0 || T < 1 || T > MYDET_TILES_MAX) return MYDET_E_BADARG;
+    if (box_width != 4 && box_width != 5) return MYDET_E_BADARG;
+    if (metric != MYDET_MERGE_IOU && metric != MYDET_MERGE_IOS) return MYDET_E_BADARG;
+    if (rotated_nms && box_width != 5) return MYDET_E_BADARG;
+    if (!tile_records || !origins || !records || !scratch) return MYDET_E_BADARG;
+    // a record is read with 16-byte loads: the base and both strides keep that alignment
+    if (((uintptr_t)tile_records & 15) || ((uintptr_t)records & 15) || ((uintptr_t)scratch & 15) || ((uintptr_t)origins & 3)) return MYDET_E_BADARG;
+    if (tile_stride_words < 0 || frame_stride_words < 0 || (tile_stride_words & 3) || (frame_stride_words & 3)) return MYDET_E_BADARG;
+    if (scratch_bytes < mydet_merge_tile_records_scratch_bytes(B, T, box_width)) return MYDET_E_BADARG;
+    if (metric == MYDET_MERGE_IOS && rotated_nms) return MYDET_E_UNSUPP;
+    const int64_t N = (int64_t)T * KMAX, BN = (int64_t)B * N;
+    MergeArgs a;
+    a.rec = tile_records; a.tile_st = tile_stride_words; a.frame_st = frame_stride_words; a.origins = origins; a.T = T;
+    a.bbox = reinterpret_cast<float *>(scratch);
+    a.cidx = reinterpret_cast<int64_t *>(a.bbox + BN * box_width);
+    a.score = reinterpret_cast<float *>(a.cidx + BN);
+    void *keys = a.score + BN;
+    const dim3 grid((unsigned)(N / 256), (unsigned)B);
+    if (box_width == 4) hipLaunchKernelGGL((merge_gather_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((merge_gather_kernel<5>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    const int st = mydet_launch_status();
+    if (st) return st;
+    PPArgs p;
+    record_outputs(p, records, box_width == 5);
+    const float conf = -__builtin_inff();
+    if (box_width == 4)
+        return metric == MYDET_MERGE_IOS
+                   ? launch_postprocess<4, false, true>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream)
+                   : launch_postprocess<4>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream);
+    if (rotated_nms) return launch_postprocess<5, true>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream);
+    return metric == MYDET_MERGE_IOS
+               ? launch_postprocess<5, false, true>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream)
+               : launch_postprocess<5>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream);
 }

@@ -9,6 +9,7 @@ input in a foreign layout is re-laid out with one tensor copy before the launch)
 import collections
 import ctypes
 import functools
+import math
 import os
 import threading
 
@@ -1222,6 +1223,100 @@ def check_counts(counts):
         raise ValueError(f'postprocess: class ids outside [0, 4096) among the selected candidates of image(s) {bad}; '
                          'the class-aware NMS key holds 12 class bits')
     return counts
+
+
+def tile_windows(H, W, size, overlap=0.2, full_frame=True, align=1):
+    """The windows (y0, x0, h, w) of tiled detection on an H x W frame, as a list.  Host arithmetic only.
+    size = (th, tw) (or one int), clipped to the frame: every tile is h = min(th, H) by w = min(tw, W).  Per axis the step is
+    max(align, floor(h * (1 - overlap)) // align * align); origins are 0, step, 2*step, ... while origin + h < H, then H - h
+    (the last tile ends at the frame's edge), duplicates dropped.  Row-major by (y0, x0).  With full_frame and more than one
+    tile the window (0, 0, H, W) follows last.  align=2 is for 4:2:0 planes: H, W, h, w must be even, every origin then is,
+    and a window of the planes is itself a 4:2:0 frame.  ValueError for an overlap outside [0, 1), a non-positive size, a
+    size that breaks the alignment, or more than _lib.TILES_MAX windows."""
+    th, tw = (size, size) if isinstance(size, int) else size
+    H, W, th, tw, align = int(H), int(W), int(th), int(tw), int(align)
+    if min(H, W) < 1 or min(th, tw) < 1 or align < 1:
+        raise ValueError(f'tile_windows: positive sizes expected, got a {H}x{W} frame, tiles {th}x{tw}, align {align}')
+    if not 0 <= overlap < 1:
+        raise ValueError(f'tile_windows: overlap {overlap!r} is outside [0, 1)')
+    h, w = min(th, H), min(tw, W)
+    if any(v % align for v in (H, W, h, w)):
+        raise ValueError(f'tile_windows: align={align} needs frame and tile sizes that are multiples of it, got a {H}x{W} frame '
+                         f'and {h}x{w} tiles')
+
+    def origins(n, t):
+        step = max(align, math.floor(t * (1 - overlap)) // align * align)
+        return list(range(0, n - t, step)) + [n - t]                 # origin + t < n, then the tile that ends at the edge
+    windows = [(y0, x0, h, w) for y0 in origins(H, h) for x0 in origins(W, w)]
+    if full_frame and len(windows) > 1:
+        windows.append((0, 0, H, W))
+    if len(windows) > _lib.TILES_MAX:
+        raise ValueError(f'tile_windows: {len(windows)} windows of {h}x{w} on a {H}x{W} frame; at most {_lib.TILES_MAX} are merged')
+    return windows
+
+
+MERGE_METRICS = {'iou': _lib.MERGE_IOU, 'ios': _lib.MERGE_IOS}          # MYDET_MERGE_* of include/mydet.h
+
+
+def merge_metric_id(metric):
+    """The C selector of a pair-test name; a ValueError for an unknown one (raised before any device is touched)."""
+    if not isinstance(metric, str) or metric not in MERGE_METRICS:
+        raise ValueError(f'merge_tile_records: metric {metric!r} is not one of {sorted(MERGE_METRICS)}')
+    return MERGE_METRICS[metric]
+
+
+def merge_tile_records(rec, B, T, origins, nms_thres, metric='iou', rotated_nms=False, records=None):
+    """The records of T windows of each of B frames -> B records in frame coordinates, by one more class-aware NMS on the
+    device (include/mydet.h: mydet_merge_tile_records_f32, where the candidate order, the tie rule and the pair tests are).
+    rec: the window records, boxes in window pixel coordinates -- an int32 tensor [T*B, words] (tile-major: window t of
+    frame b in row t*B + b) or [T, B, words] with any strides along T and B (a frame-major buffer is
+    buf.view(B, T, words).transpose(0, 1)), or the record_views dict of such a [T*B, words] buffer.  origins: T pairs
+    (x0, y0), or an int32 device tensor [T, 2].  metric: 'iou' or 'ios' (intersection over the smaller area); rotated_nms:
+    the rotated-IoU test (rotated records and 'iou' only).  records: optional int32 [B, words] buffer to write.  Returns the
+    record_views dict of the merged records; 'index' holds t*512 + k of every survivor."""
+    m = merge_metric_id(metric)
+    if isinstance(rec, dict):
+        views, rec = rec, rec['records']
+        if views['bbox'].data_ptr() != rec.data_ptr() + 4 * _lib.REC_BBOX:
+            raise ValueError("merge_tile_records: the fields of this record dict are copies, not views of its 'records' buffer")
+    require_gpu(rec, 'merge_tile_records')
+    B, T = int(B), int(T)
+    words = rec.shape[-1]
+    if rec.dtype != torch.int32 or words not in (_lib.REC_WORDS, _lib.REC_ROT_WORDS):
+        raise ValueError(f'merge_tile_records: int32 records of {_lib.REC_WORDS} or {_lib.REC_ROT_WORDS} words expected, got '
+                         f'{rec.dtype} {tuple(rec.shape)}')
+    width = 4 if words == _lib.REC_WORDS else 5
+    if rotated_nms and width != 5:
+        raise ValueError("rotated_nms needs 'cxcywhd' records (the rotated record with its angle plane)")
+    if rotated_nms and m == _lib.MERGE_IOS:
+        raise ValueError("merge_tile_records: metric 'ios' is defined for the axis-aligned test only, not with rotated_nms")
+    if not 1 <= T <= _lib.TILES_MAX or B < 1:
+        raise ValueError(f'merge_tile_records: B >= 1 and 1 <= T <= {_lib.TILES_MAX} expected, got B = {B}, T = {T}')
+    if rec.dim() == 2:
+        rec = rec.contiguous().view(T, B, words) if rec.shape[0] == T * B else rec
+    if tuple(rec.shape) != (T, B, words):
+        raise ValueError(f'merge_tile_records: records of shape [{T * B}, {words}] or [{T}, {B}, {words}] expected, got {tuple(rec.shape)}')
+    if rec.stride(2) != 1 or rec.stride(0) % 4 or rec.stride(1) % 4 or min(rec.stride(0), rec.stride(1)) < 0:
+        rec = rec.contiguous()
+    dev = rec.device
+    if isinstance(origins, torch.Tensor):
+        org = origins
+    else:
+        org = torch.tensor([[int(x0), int(y0)] for x0, y0 in origins], dtype=torch.int32).reshape(-1, 2).to(dev, non_blocking=True)
+    if org.dtype != torch.int32 or tuple(org.shape) != (T, 2) or org.device != dev or not org.is_contiguous():
+        raise ValueError(f'merge_tile_records: {T} origins (x0, y0) expected (an int32 tensor [{T}, 2] on {dev}), got {tuple(org.shape)}')
+    if records is None:
+        records = torch.empty((B, words), dtype=torch.int32, device=dev)
+    assert records.dtype == torch.int32 and tuple(records.shape) == (B, words) and records.is_contiguous() and records.device == dev
+    nbytes = _lib.lib().mydet_merge_tile_records_scratch_bytes(B, T, width)
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    t0 = TIMER.start() if TIMER else None
+    code = _lib.lib().mydet_merge_tile_records_f32(_ptr(rec), rec.stride(0), rec.stride(1), B, T, width, _ptr(org), float(nms_thres), m,
+                                                   int(bool(rotated_nms)), _ptr(records), _ptr(scratch), nbytes, _stream())
+    if t0:
+        TIMER.stop('merge_tile_records', t0, float(B))
+    _lib.check(code, 'mydet_merge_tile_records_f32')
+    return record_views(records)
 
 
 def bboxes_iou(a, b, xyxy=False):
