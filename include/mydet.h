@@ -460,6 +460,69 @@ int mydet_merge_tile_records_f32(const int32_t *tile_records, int64_t tile_strid
                                  int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
                                  int rotated_nms, int32_t *records, void *scratch, int64_t scratch_bytes, void *stream);
 
+/* Tracking of detections across video frames on the device: persistent identities and Kalman-filtered boxes from the detection
+ * records of consecutive frames.  The state model is the reference's KFTracklet (utils/structures.py:445-529) over
+ * RotBBoxKalmanFilter (utils/kalman_filter.py:77-142): constant velocity on (cx, cy, w, h, angle), diagonal P0 / Q / R with the
+ * rows of cx, cy, w, h and of their velocities scaled by the box area w*h, the angle kept in [0, 180), a score with momentum.
+ * Its 10 x 10 covariance stays five 2 x 2 blocks (pxx, pxv, pvv), which is how it is stored.  The reference has no loop around
+ * that model; the association below is this library's.
+ *
+ * One launch advances S independent streams by F consecutive frames each (one workgroup per stream, the frames in order).
+ * In : the record of frame f of stream s at records + s*stream_stride_words + f*frame_stride_words: a record of MYDET_REC_WORDS
+ *      (box_width 4) or MYDET_REC_ROT_WORDS (box_width 5) words in frame coordinates (after
+ *      mydet_bboxes_to_original_batched_f32).  A 4-wide record runs the same filter with angle 0.
+ * Per frame, in this order (float32; csrc/track.hip is built with -ffp-contract=off and DESIGN.md section 4 has the operation order):
+ *   predict   every live track: a = w*h of the state before the step; pxx += 2 pxv + pvv + q_x, pxv += pvv, pvv += q_v with
+ *             q_x = q[i]*a, q_v = q[5+i]*a for i < 4 and q[4], q[9] for the angle; x += v; angle %= 180 (Python's %: in
+ *             [0, 180)); from the second consecutive prediction on, score *= momentum; missed += 1.
+ *   associate detections in (score descending, record slot ascending) order.  Each takes, among the live tracks of its own
+ *             class that no earlier detection took, the one whose predicted box has the largest IoU with it, if that IoU is
+ *             > match_thres; on equal IoU the lower track slot.  IoU: MYDET_TRACK_MATCH_IOU the axis-aligned IoU of
+ *             mydet_postprocess_f32 on (cx, cy, w, h) (box i = the detection, j = the track); MYDET_TRACK_MATCH_ROTATED
+ *             (box_width 5 only) the exact rotated IoU of mydet_rotated_iou_f32, a = the detection, b = the track.
+ *   update    every matched track (KFTracklet.update): z4 = angle % 180, replaced by the nearest of z4, z4 - 180, z4 + 180 to the
+ *             state angle (the first on a tie); a = w*h of the predicted state; per parameter y = z - x, inv = 1 / (pxx + r),
+ *             r = r[i]*a (i < 4) or r[4]; kx = pxx*inv, kv = pxv*inv; x += kx*y, v += kv*y; pxx -= kx*pxx, pxv -= kx*pxv,
+ *             pvv -= kv*pxv (old values on the right); angle %= 180; score = momentum*score + (1 - momentum)*detection score;
+ *             missed = 0.
+ *   retire    a live track with score < min_score, cx, cy, w or h < 0, cx > img_w, cy > img_h, w > img_w, h > img_h
+ *             (KFTracklet.is_feasible), or missed >= max_missed.  Its slot becomes free (all zero) and its id is never used again.
+ *   births    every unmatched detection with score >= new_thres, in the association order, into the lowest free slot (slots
+ *             freed in this frame included) with the stream's next id (int64, from 1): x = the box with angle % 180, v = 0,
+ *             pxx = p0[i]*a (i < 4) or p0[4], pvv = p0[5+i]*a or p0[9], pxv = 0, score = the detection's, missed = 0.  Without
+ *             a free slot the detection is dropped and counted.
+ * Out (dense, frame o = s*F + f): out_box [S*F][max_tracks][5], out_score, out_class i64, out_id i64 (0: a free slot),
+ *      out_missed i32 (0: matched or born in this frame; k: k frames since; -1: a free slot) [S*F][max_tracks];
+ *      out_count [S*F] the live tracks after the frame, out_dropped [S*F].  A frame whose record count is
+ *      MYDET_COUNT_BAD_CLASS leaves the state as it is; its out_count is that sentinel, its slots are written as free.
+ * params: HOST pointer; the struct travels as a kernel argument.  p0, q, r are VARIANCES (the reference's constants squared).
+ * state: S * mydet_track_state_words(max_tracks) int32 words, 16-byte aligned, caller-owned, persistent between launches and
+ *      initialised by mydet_track_reset.  Per stream, in words, MT = max_tracks:
+ *        [0, 2) next id (int64)   [2] live tracks   [3, 8) zero
+ *        [8, 8 + 2 MT) class (int64 [MT])           then id (int64 [MT]; 0 = free)
+ *        then float planes [5][MT] each: x (cx, cy, w, h, angle), v, pxx, pxv, pvv
+ *        then score [MT] f32, missed [MT] i32; zero padding to a multiple of 4 words.
+ * MYDET_E_BADARG: S, F or max_tracks < 1; box_width not 4 or 5; an unknown params->match, or MATCH_ROTATED with box_width 4; a null
+ *      pointer; records or state not 16-byte aligned; a stride that is negative or no multiple of 4 words; a misaligned
+ *      output.  MYDET_E_UNSUPP: max_tracks > MYDET_TRACK_MAX_TRACKS.  mydet_track_state_words is 0 for such a max_tracks. */
+#define MYDET_TRACK_MAX_TRACKS    512
+#define MYDET_TRACK_STATE_HEADER  8      /* words before the planes */
+#define MYDET_TRACK_SLOT_WORDS    31     /* words per track: 2 + 2 + 25 + 1 + 1 */
+#define MYDET_TRACK_MATCH_IOU     0
+#define MYDET_TRACK_MATCH_ROTATED 1
+typedef struct mydet_track_params {
+    float p0[10], q[10], r[5];           /* variances: initial covariance, process noise, measurement noise */
+    float momentum, min_score, new_thres, match_thres;
+    float img_h, img_w;
+    int max_missed, match;
+} mydet_track_params;
+int64_t mydet_track_state_words(int max_tracks);
+int mydet_track_reset(int32_t *state, int S, int max_tracks, void *stream);
+int mydet_track_frames_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                           int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                           float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                           int32_t *out_count, int32_t *out_dropped, void *stream);
+
 /* Winograd F(4x4,3x3) form of the same 3x3 stride-1 pad-1 conv + BN + act (+ residual) as mydet_conv2d_wino_f32
  * (4x fewer multiplies than the direct form; used for the deep layers with chip-filling grids).  `u` = the
  * transform-domain weights made by mydet_wino4_weights_f32 from the OHWI weight (mydet_wino4_weights_floats(Cout, Cin)

@@ -71,6 +71,9 @@ SIGNATURES = {
     'mydet_rotated_iou_f32': [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr],
     'mydet_merge_tile_records_scratch_bytes': [c_int, c_int, c_int],
     'mydet_merge_tile_records_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_f64, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr],
+    'mydet_track_state_words': [c_int],
+    'mydet_track_reset': [c_ptr, c_int, c_int, c_ptr],
+    'mydet_track_frames_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
     'mydet_mbconv_tiles': [c_int, c_int, c_int],
     'mydet_mbconv_expand_dw_f32': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64] + [c_int] * 11 + [c_ptr, c_int, c_ptr, c_ptr],
     'mydet_sepconv_nodes_f32': [c_int, c_ptr, c_int, c_int, c_ptr],
@@ -100,7 +103,7 @@ SIGNATURES = {
 
 
 RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems',
-               'mydet_merge_tile_records_scratch_bytes'}
+               'mydet_merge_tile_records_scratch_bytes', 'mydet_track_state_words'}
 
 # detection record layout (MYDET_REC_* of include/mydet.h), in int32 words
 REC_TOPK = 512
@@ -115,6 +118,10 @@ REC_ROT_WORDS = REC_WORDS + REC_TOPK
 # merge of tile records (mydet_merge_tile_records_f32): MYDET_TILES_MAX windows per frame, MYDET_MERGE_* pair tests
 TILES_MAX = 64
 MERGE_IOU, MERGE_IOS = 0, 1
+# tracking (mydet_track_frames_f32): MYDET_TRACK_* of include/mydet.h
+TRACK_MAX_TRACKS = 512
+TRACK_STATE_HEADER, TRACK_SLOT_WORDS = 8, 31
+TRACK_MATCH_IOU, TRACK_MATCH_ROTATED = 0, 1
 
 
 class DecodeLevel(ctypes.Structure):
@@ -163,6 +170,13 @@ class Yuv420Src(ctypes.Structure):
     """mydet_yuv420_src (include/mydet.h)."""
     _fields_ = [('plane', c_ptr * 3), ('img_bytes', c_i64 * 3), ('row_bytes', c_i64 * 3), ('layout', c_int), ('matrix', c_int),
                 ('full_range', c_int), ('reserved', c_int)]
+
+
+class TrackParams(ctypes.Structure):
+    """mydet_track_params (include/mydet.h): p0, q, r are variances."""
+    _fields_ = [('p0', c_f32 * 10), ('q', c_f32 * 10), ('r', c_f32 * 5), ('momentum', c_f32), ('min_score', c_f32),
+                ('new_thres', c_f32), ('match_thres', c_f32), ('img_h', c_f32), ('img_w', c_f32), ('max_missed', c_int),
+                ('match', c_int)]
 
 
 # MYDET_YUV420_* of include/mydet.h

@@ -341,6 +341,8 @@ class Detector():
                 x = torch.cat(xs)[torch.tensor(order, device=dev)]
                 idxs, pads, hws = [idxs[k] for k in order], [pads[k] for k in order], [hws[k] for k in order]
             rec = self._records(x, conf_thres, nms_thres, rotated_nms)
+            if kwargs.get('_whole_records'):                         # the views of ONE buffer (a graph replay hands out copies)
+                rec = ops.record_views(rec['records'])
             if any(p is not None for p in pads):
                 ops.records_to_original_(rec, pads)
             rec['img_hw'] = hws
@@ -424,8 +426,65 @@ class Detector():
         Keyword arguments as in _predict_pil, and tiles: None, or a Tiles for tiled detection on large frames (frames of one
         size): every window's input is one launch over a crop view of all frames, the windows of one size are one forward
         batch, and one more NMS on the device merges their detections in frame coordinates (include/mydet.h:
-        mydet_merge_tile_records_f32).  Returns a list of ImageObjects in original-frame coordinates."""
-        return self._objects_of_records(self._frame_records(frames, **kwargs))
+        mydet_merge_tile_records_f32).  Returns a list of ImageObjects in original-frame coordinates.
+        tracker: None, or a mydetection_amd.api.Tracker (frames of one size, a multiple of its `streams` of them: stream s owns
+        the consecutive frames s*F .. s*F + F-1).  One more launch on the device (include/mydet.h: mydet_track_frames_f32)
+        associates the call's detections with the tracker's tracks, and each ImageObjects then holds the tracks matched or born
+        in its frame -- bboxes the Kalman-filtered state, scores the track scores, cats the classes, obj_ids (int64) the
+        persistent identities -- and, with coasting=True, the live tracks without a detection in that frame as well."""
+        tracker, coasting = self._pop_tracker(kwargs)
+        if tracker is None:
+            return self._objects_of_records(self._frame_records(frames, **kwargs))
+        n, groups = self._frame_groups(frames)
+        if len(groups) != 1:
+            raise ValueError('predict_frames: a tracked call takes frames of one size, got '
+                             f'{[tuple(parts[0].shape[1:3]) for _, parts in groups]}')
+        hw = tuple(int(v) for v in groups[0][1][0].shape[1:3])
+        tracker.check_call(n, hw, self.model.bb_format)
+        return self._tracked_objects(self._frame_records(frames, _whole_records=True, **kwargs), hw, tracker, coasting, kwargs)
+
+    @staticmethod
+    def _pop_tracker(kwargs):
+        """(tracker, coasting) out of a frame method's keyword arguments; a TypeError for anything but a Tracker."""
+        from .tracking import Tracker
+        tracker, coasting = kwargs.pop('tracker', None), bool(kwargs.pop('coasting', False))
+        if tracker is not None and not isinstance(tracker, Tracker):
+            raise TypeError(f'tracker: a mydetection_amd.api.Tracker (or None) expected, got {type(tracker).__name__}')
+        return tracker, coasting
+
+    @staticmethod
+    def _no_tracker(kwargs, what):
+        if 'tracker' in kwargs or 'coasting' in kwargs:
+            raise TypeError(f'{what}: track ids in the json rows are not built; use the predict_frames form with tracker=')
+
+    def _tracked_objects(self, records, frame_hw, tracker, coasting, kwargs):
+        """The tracked form of _objects_of_records: one eager tracker launch on the call's records (frame coordinates, one
+        buffer), then per frame the ImageObjects of the tracks with missed == 0 (coasting: of every live track).  Two host
+        synchronisations: the frame counts, and the indices of the selected slots."""
+        from ..utils.structures import ImageObjects
+        records = list(records)
+        assert len(records) == 1, 'one frame size gives one network input size'
+        idxs, rec = records[0]
+        assert idxs == list(range(len(idxs)))
+        hw = rec['img_hw'][0]                                        # what the untracked call reports
+        width = 5 if 'angle' in rec else 4
+        state = tracker.bind(frame_hw, width, rec['records'].device)
+        params = tracker.params(frame_hw, tracker.resolve_match(self.model.bb_format), kwargs.get('conf_thres', self.conf_thres))
+        out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks)
+        B, mt = len(idxs), tracker.max_tracks
+        missed = out['missed'].view(B, mt)
+        keep = (missed >= 0) if coasting else (missed == 0)
+        ops.check_counts(out['count'].view(B).cpu().tolist())
+        sel = keep.nonzero()
+        per_frame = torch.bincount(sel[:, 0], minlength=B).cpu().tolist()
+        box, score, cls, ids = out['box'].view(B * mt, 5), out['score'].view(-1), out['cls'].view(-1), out['id'].view(-1)
+        flat = sel[:, 0] * mt + sel[:, 1]
+        objs, lo = [], 0
+        for k in per_frame:
+            rows = flat[lo:lo + k]
+            lo += k
+            objs.append(ImageObjects(box[rows][:, :width], cls[rows], None, score[rows], self.model.bb_format, hw, obj_ids=ids[rows]))
+        return objs
 
     def _objects_of_records(self, records):
         """ImageObjects in frame order from the (indices, records) pairs of _records_of_inputs."""
@@ -441,6 +500,7 @@ class Detector():
 
     def frames_to_json(self, frames, img_ids, eval_type='x1y1wh', catIdx2id=None, **kwargs):
         """COCO-style rows of uint8 frames (see predict_frames), image by image: the counterpart of _json_batch."""
+        self._no_tracker(kwargs, 'frames_to_json')
         return self._json_of_records(self._frame_records(frames, **kwargs), img_ids, eval_type, catIdx2id)
 
     def _json_of_records(self, records, img_ids, eval_type, catIdx2id):
@@ -535,12 +595,21 @@ class Detector():
         min(255, (v + 2) >> 2); from there the conversion is NV12's (include/mydet.h).  Returns exactly what
         predict_frames returns for the converted RGB frames (ops.yuv420_to_rgb), which are never built: one HIP launch
         reads the planes.  One call takes one frame size.  Keyword arguments as in _predict_pil and predict_frames (tiles:
-        even frame and tile sizes)."""
-        return self._objects_of_records(self._yuv_records(planes, layout, matrix, full_range, **kwargs))
+        even frame and tile sizes; tracker, coasting)."""
+        tracker, coasting = self._pop_tracker(kwargs)
+        if tracker is None:
+            return self._objects_of_records(self._yuv_records(planes, layout, matrix, full_range, **kwargs))
+        ops.yuv420_layout(layout)
+        y = self._yuv_planes(planes, layout)[0]                      # the checks alone: no device is touched
+        hw = tuple(int(v) for v in y.shape[1:3])
+        tracker.check_call(y.shape[0], hw, self.model.bb_format)
+        return self._tracked_objects(self._yuv_records(planes, layout, matrix, full_range, _whole_records=True, **kwargs), hw, tracker,
+                                     coasting, kwargs)
 
     def frames_yuv_to_json(self, planes, layout, img_ids, eval_type='x1y1wh', catIdx2id=None, *, matrix='bt601', full_range=False,
                            **kwargs):
         """COCO-style rows of 4:2:0 frames (see predict_frames_yuv): the counterpart of frames_to_json."""
+        self._no_tracker(kwargs, 'frames_yuv_to_json')
         return self._json_of_records(self._yuv_records(planes, layout, matrix, full_range, **kwargs), img_ids, eval_type, catIdx2id)
 
     def predict_frames_nv12(self, y, uv=None, *, matrix='bt601', full_range=False, **kwargs):

@@ -1,0 +1,77 @@
+"""`Tracker`: the `tracker=` argument of Detector.predict_frames and its YUV forms -- identities that persist from frame to
+frame and Kalman-filtered boxes, computed on the device from the call's own detection records (ops.track_frames;
+include/mydet.h: mydet_track_frames_f32 has the rules).  The state model is the reference's KFTracklet
+(utils/structures.py:445-529); the reference has no loop around it, the association is this package's."""
+from .. import ops
+
+
+class Tracker:
+    """State and parameters of `streams` independent video streams, at most `max_tracks` (<= 512) live tracks each.
+
+    match: the pair test of the association, 'iou' (axis-aligned, on cx, cy, w, h) or 'rotated' (the exact rotated IoU;
+    'cxcywhd' models only); None = 'rotated' for a 'cxcywhd' model, 'iou' otherwise.  A detection continues a track of its
+    class when their IoU is > match_thres; an unmatched detection with score >= new_thres (None: the call's conf_thres) starts
+    one; a track is dropped after max_missed frames without a match, when its score (momentum) falls below min_score, or when
+    its box leaves the frame.  p0, q, r: the filter's standard deviations (KFTracklet's constants by default).
+    The first call binds the tracker to that call's frame size (H, W), box format and device; `state` is then the int32
+    [streams, words] device buffer (ops.track_state_views names its fields) and reset() empties it (ids start at 1 again).
+    A batch of B frames is `streams` runs of B / streams consecutive frames: frame f of stream s is frame s * (B / streams) + f."""
+
+    def __init__(self, streams=1, max_tracks=256, match=None, match_thres=0.3, new_thres=None, max_missed=30, momentum=0.8,
+                 min_score=0.1, p0=ops.TRACK_P0, q=ops.TRACK_Q, r=ops.TRACK_R):
+        self.streams, self.max_tracks = int(streams), int(max_tracks)
+        if self.streams < 1:
+            raise ValueError(f'Tracker: streams >= 1 expected, got {streams!r}')
+        ops.track_state_words(self.max_tracks)
+        if match is not None:
+            ops.track_match_id(match)
+        self.match = match
+        self.match_thres, self.new_thres = float(match_thres), None if new_thres is None else float(new_thres)
+        self.max_missed, self.momentum, self.min_score = int(max_missed), float(momentum), float(min_score)
+        self.p0, self.q, self.r = tuple(p0), tuple(q), tuple(r)
+        self.params((1, 1), 'iou', 0.0)                              # the range checks, before any device is touched
+        self.state = None
+        self.img_hw = None
+        self.box_width = None
+
+    def __repr__(self):
+        return (f'Tracker(streams={self.streams}, max_tracks={self.max_tracks}, match={self.match!r}, match_thres={self.match_thres}, '
+                f'new_thres={self.new_thres}, max_missed={self.max_missed}, momentum={self.momentum}, min_score={self.min_score})')
+
+    def params(self, img_hw, match, conf_thres):
+        """The kernel's parameter struct for a frame size, a resolved pair test and the call's conf_thres."""
+        return ops.track_params(img_hw, match, self.match_thres, conf_thres if self.new_thres is None else self.new_thres,
+                                self.max_missed, self.momentum, self.min_score, self.p0, self.q, self.r)
+
+    def resolve_match(self, bb_format):
+        """The pair test for a model's box format; a ValueError for 'rotated' on a model without angles."""
+        if self.match is None:
+            return 'rotated' if bb_format == 'cxcywhd' else 'iou'
+        if self.match == 'rotated' and bb_format != 'cxcywhd':
+            raise ValueError(f"tracker: match 'rotated' needs a 'cxcywhd' model; this one predicts {bb_format!r}")
+        return self.match
+
+    def check_call(self, n_frames, img_hw, bb_format):
+        """The argument rules of a tracked call that need no device: the batch is whole runs of every stream, and the frame
+        size and box format are those the tracker was bound to."""
+        self.resolve_match(bb_format)
+        if n_frames < 1 or n_frames % self.streams:
+            raise ValueError(f'tracker: a batch of {n_frames} frames is not a multiple of streams = {self.streams}')
+        width = 5 if bb_format == 'cxcywhd' else 4
+        if self.img_hw is not None and (tuple(img_hw) != self.img_hw or width != self.box_width):
+            raise ValueError(f'tracker: bound to {self.img_hw[0]}x{self.img_hw[1]} frames with {self.box_width}-wide boxes by its first call, '
+                             f'got {img_hw[0]}x{img_hw[1]} with {width}-wide boxes (one frame size per tracker)')
+
+    def bind(self, img_hw, box_width, device):
+        """First call: take the frame size and allocate the state on the records' device."""
+        if self.state is None:
+            self.state = ops.track_state(self.streams, self.max_tracks, device)
+            self.img_hw, self.box_width = (int(img_hw[0]), int(img_hw[1])), int(box_width)
+        elif self.state.device != device:
+            raise ValueError(f'tracker: its state lives on {self.state.device}, this call runs on {device}')
+        return self.state
+
+    def reset(self):
+        """Forget every track; the next id of every stream is 1 again.  The frame size stays bound."""
+        if self.state is not None:
+            ops.track_reset_(self.state, self.max_tracks)

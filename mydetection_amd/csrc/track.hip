@@ -1,0 +1,385 @@
+// Multi-object tracking on the device: detection records of consecutive frames -> persistent identities and Kalman-filtered
+// boxes, without a per-frame copy of the records to the host.
+//
+// State model: the reference's KFTracklet (utils/structures.py:445-529) over RotBBoxKalmanFilter (utils/kalman_filter.py:77-142):
+// a constant-velocity Kalman filter on (cx, cy, w, h, angle).  F couples parameter i only with its own velocity, H selects the five
+// parameters and P0, Q, R are diagonal (the area scaling multiplies whole rows of diagonal matrices), so the 10 x 10 covariance
+// is five independent symmetric 2 x 2 blocks (pxx, pxv, pvv) for ever and the 5 x 5 inverse of the update is five reciprocals.
+// The reference ships no loop around that model; the association rules are this project's (include/mydet.h).
+//
+// One workgroup per stream, thread = track slot: a track lives in its thread's registers for all F frames of the launch and
+// only the frame's detections go through LDS.  Per frame:
+//   1. stage the <= 512 detections of the record in LDS with their pair-test planes (corners + area, or the rotiou::Box of
+//      rot_iou.h) and rank them by (score descending, record slot ascending);
+//   2. predict every live track;
+//   3. greedy association: the walk over the ranked detections is sequential, its body is lane-per-track -- every thread
+//      computes the IoU of its own predicted box with the detection, a 64-bit key (IoU bits, ~slot) is maximised over the wave
+//      by shuffles and over the waves through LDS: one barrier per detection;
+//   4. matched tracks take the Kalman update; 5. infeasible and long-missed tracks are retired; 6. the unmatched detections
+//      above new_thres are born into the lowest free slots -- ranks by ballot and popcount, no serial loop.
+// Built with -ffp-contract=off: the float32 operation order below IS the definition (tests/_track_ref.py restates it in numpy
+// and is held to the reference's float64 on tests/golden/kf_tracklet.npz).
+#include "common.h"
+#include "rot_iou.h"
+
+namespace {
+
+constexpr int KMAX = MYDET_REC_TOPK;
+constexpr int TMAX = MYDET_TRACK_MAX_TRACKS;
+constexpr int NWMAX = TMAX / 64;
+
+struct TrackArgs {
+    const int32_t *rec;               // record of frame f of stream s at rec + s*stream_st + f*frame_st (words)
+    int64_t stream_st, frame_st;
+    int F, MT;
+    mydet_track_params p;
+    int32_t *state;
+    int64_t state_words;              // per stream
+    float *obox, *oscore;
+    int64_t *ocls, *oid;
+    int32_t *omissed, *ocount, *odropped;
+};
+
+__device__ __forceinline__ unsigned sortable(float f) {
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// Python's a % 180 (the sign of the divisor): fmodf is exact, the one rounding is the add
+__device__ __forceinline__ float mod180(float a) {
+    const float r = fmodf(a, 180.0f);
+    if (r == 0.0f) return 0.0f;
+    return r < 0.0f ? r + 180.0f : r;
+}
+
+__device__ __forceinline__ int prefix_bits(const unsigned long long *mask, int i) {
+    int k = 0;
+    for (int w = 0; w < (i >> 6); ++w) k += __popcll(mask[w]);
+    return k + __popcll(mask[i >> 6] & ((1ull << (i & 63)) - 1ull));
+}
+
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(v, off, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+template <int BW, bool ROT>
+__global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
+    static_assert(!ROT || BW == 5, "the rotated IoU needs the angle column");
+    __shared__ float s_z[5][KMAX];                    // the frame's detections: cx, cy, w, h, angle (0 for BW = 4)
+    __shared__ float s_g[ROT ? 7 : 5][KMAX];          // pair-test planes: x1, y1, x2, y2, area | the seven fields of rotiou::Box
+    __shared__ float s_sc[KMAX];
+    __shared__ int64_t s_cl[KMAX];
+    __shared__ int s_order[KMAX];                     // rank -> record slot
+    __shared__ int s_dmatch[KMAX];                    // rank -> matched track slot, or -1
+    __shared__ int s_bpos[KMAX];                      // k-th birth -> rank
+    __shared__ unsigned long long s_red[2][NWMAX];
+    __shared__ unsigned long long s_bmask[KMAX / 64], s_fmask[NWMAX];
+
+    const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
+    const int s = blockIdx.x, MT = a.MT;
+    const mydet_track_params &P = a.p;
+
+    // state views (include/mydet.h: the layout is public)
+    int32_t *st = a.state + (int64_t)s * a.state_words;
+    int64_t *g_cls = reinterpret_cast<int64_t *>(st + MYDET_TRACK_STATE_HEADER);
+    int64_t *g_id = g_cls + MT;
+    float *g_x = reinterpret_cast<float *>(g_id + MT);
+    float *g_v = g_x + 5 * MT, *g_pxx = g_v + 5 * MT, *g_pxv = g_pxx + 5 * MT, *g_pvv = g_pxv + 5 * MT;
+    float *g_score = g_pvv + 5 * MT;
+    int32_t *g_missed = reinterpret_cast<int32_t *>(g_score + MT);
+
+    const bool slot_ok = tid < MT;
+    float x[5], v[5], pxx[5], pxv[5], pvv[5], score = 0.0f;
+    int missed = 0;
+    int64_t cls = 0, id = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) { x[i] = v[i] = pxx[i] = pxv[i] = pvv[i] = 0.0f; }
+    if (slot_ok) {
+        cls = g_cls[tid]; id = g_id[tid];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            x[i] = g_x[i * MT + tid]; v[i] = g_v[i * MT + tid];
+            pxx[i] = g_pxx[i * MT + tid]; pxv[i] = g_pxv[i * MT + tid]; pvv[i] = g_pvv[i * MT + tid];
+        }
+        score = g_score[tid]; missed = g_missed[tid];
+    }
+    int64_t next_id = *reinterpret_cast<const int64_t *>(st);
+    int nlive = st[2];
+    const float one_minus_m = 1.0f - P.momentum;
+
+    for (int f = 0; f < a.F; ++f) {
+        const int32_t *r = a.rec + (int64_t)s * a.stream_st + (int64_t)f * a.frame_st;
+        const int64_t o = (int64_t)s * a.F + f;
+        const int cnt = r[MYDET_REC_COUNT];
+        if (cnt < 0) {                                             // a bad-class frame: the state stands, the outputs say so
+            if (slot_ok) {
+                float *ob = a.obox + (o * MT + tid) * 5;
+                ob[0] = 0.0f; ob[1] = 0.0f; ob[2] = 0.0f; ob[3] = 0.0f; ob[4] = 0.0f;
+                a.oscore[o * MT + tid] = 0.0f; a.ocls[o * MT + tid] = 0; a.oid[o * MT + tid] = 0; a.omissed[o * MT + tid] = -1;
+            }
+            if (tid == 0) { a.ocount[o] = MYDET_COUNT_BAD_CLASS; a.odropped[o] = 0; }
+            continue;
+        }
+        const int n = cnt < KMAX ? cnt : KMAX;
+        const int n64 = (n + 63) & ~63;
+        __syncthreads();                                           // the previous frame is done with the LDS
+
+        // 1. the detections
+        for (int d = tid; d < n; d += nthr) {
+            const f32x4 b = *reinterpret_cast<const f32x4 *>(r + MYDET_REC_BBOX + 4 * d);
+            float ang = 0.0f;
+            if constexpr (BW == 5) ang = reinterpret_cast<const float *>(r + MYDET_REC_ANGLE)[d];
+            s_z[0][d] = b[0]; s_z[1][d] = b[1]; s_z[2][d] = b[2]; s_z[3][d] = b[3]; s_z[4][d] = ang;
+            s_sc[d] = reinterpret_cast<const float *>(r + MYDET_REC_SCORE)[d];
+            s_cl[d] = reinterpret_cast<const int64_t *>(r + MYDET_REC_CLASS)[d];
+            if constexpr (ROT) {
+                const rotiou::Box q = rotiou::make_box(b[0], b[1], b[2], b[3], ang);
+                s_g[0][d] = q.cx; s_g[1][d] = q.cy; s_g[2][d] = q.hx; s_g[3][d] = q.hy; s_g[4][d] = q.vx; s_g[5][d] = q.vy;
+                s_g[6][d] = q.area;
+            } else {
+                const float hw = b[2] / 2.0f, hh = b[3] / 2.0f;
+                const float x1 = b[0] - hw, y1 = b[1] - hh, x2 = b[0] + hw, y2 = b[1] + hh;
+                s_g[0][d] = x1; s_g[1][d] = y1; s_g[2][d] = x2; s_g[3][d] = y2; s_g[4][d] = (x2 - x1) * (y2 - y1);
+            }
+        }
+        if (tid < KMAX / 64) s_bmask[tid] = 0ull;
+        if (tid < NWMAX) s_fmask[tid] = 0ull;
+        __syncthreads();
+        // rank by (score descending, record slot ascending): a total order on the score's bits, so the ranks are a permutation
+        for (int d = tid; d < n; d += nthr) {
+            const unsigned kd = sortable(s_sc[d]);
+            int rank = 0;
+            for (int e = 0; e < n; ++e) {
+                const unsigned ke = sortable(s_sc[e]);
+                rank += (ke > kd || (ke == kd && e < d)) ? 1 : 0;
+            }
+            s_order[rank] = d;
+        }
+
+        // 2. predict (RotBBoxKalmanFilter.predict, then KFTracklet.predict's angle and score rules)
+        bool live = slot_ok && id != 0;
+        if (live) {
+            const float area = x[2] * x[3];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                const float qx = i < 4 ? P.q[i] * area : P.q[i], qv = i < 4 ? P.q[5 + i] * area : P.q[5 + i];
+                const float t = pxv[i] + pvv[i];
+                pxx[i] = ((pxx[i] + pxv[i]) + t) + qx;
+                pxv[i] = t;
+                pvv[i] = pvv[i] + qv;
+                x[i] = x[i] + v[i];
+            }
+            x[4] = mod180(x[4]);
+            if (missed >= 1) score = P.momentum * score;
+            missed += 1;
+        }
+        // the predicted box's side of the pair test
+        float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f, t4 = 0.f, t5 = 0.f, t6 = 0.f;
+        if (live) {
+            if constexpr (ROT) {
+                const rotiou::Box q = rotiou::make_box(x[0], x[1], x[2], x[3], x[4]);
+                t0 = q.cx; t1 = q.cy; t2 = q.hx; t3 = q.hy; t4 = q.vx; t5 = q.vy; t6 = q.area;
+            } else {
+                const float hw = x[2] / 2.0f, hh = x[3] / 2.0f;
+                t0 = x[0] - hw; t1 = x[1] - hh; t2 = x[0] + hw; t3 = x[1] + hh; t4 = (t2 - t0) * (t3 - t1);
+            }
+        }
+        const int any_live = __syncthreads_or(live ? 1 : 0);      // also: s_order is complete
+
+        // 3. greedy association
+        int md = -1;                                               // the record slot this track took
+        if (any_live) {
+            for (int p = 0; p < n; ++p) {
+                const int d = s_order[p];
+                unsigned long long key = 0ull;
+                if (live && md < 0 && cls == s_cl[d]) {
+                    float iou;
+                    if constexpr (ROT) {
+                        const rotiou::Box bi{s_g[0][d], s_g[1][d], s_g[2][d], s_g[3][d], s_g[4][d], s_g[5][d], s_g[6][d]};
+                        const rotiou::Box bj{t0, t1, t2, t3, t4, t5, t6};
+                        iou = rotiou::rot_iou(bi, bj);
+                    } else {
+                        const float xx1 = fmaxf(s_g[0][d], t0), yy1 = fmaxf(s_g[1][d], t1);
+                        const float xx2 = fminf(s_g[2][d], t2), yy2 = fminf(s_g[3][d], t3);
+                        const float ww = fmaxf(0.0f, xx2 - xx1), hh = fmaxf(0.0f, yy2 - yy1);
+                        const float inter = ww * hh;
+                        iou = inter / (s_g[4][d] + t4 - inter);
+                    }
+                    if (iou > P.match_thres)                       // a NaN (0/0) never matches
+                        key = ((unsigned long long)__float_as_uint(fmaxf(iou, 0.0f)) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)tid);
+                }
+                key = wave_max(key);
+                if (lane == 0) s_red[p & 1][wave] = key;
+                __syncthreads();
+                unsigned long long best = 0ull;
+                for (int w = 0; w < nwave; ++w) { const unsigned long long k = s_red[p & 1][w]; best = k > best ? k : best; }
+                const int win = best ? (int)(0xFFFFFFFFu - (unsigned)best) : -1;
+                if (win == tid) md = d;
+                if (tid == 0) s_dmatch[p] = win;
+            }
+        } else {
+            for (int p = tid; p < n; p += nthr) s_dmatch[p] = -1;
+        }
+
+        // 4. update the matched tracks (KFTracklet.update)
+        if (md >= 0) {
+            float z[5];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) z[i] = s_z[i][md];
+            const float za = mod180(z[4]);
+            const float c1 = za - 180.0f, c2 = za + 180.0f;
+            float zb = za, dmin = fabsf(za - x[4]);
+            const float d1 = fabsf(c1 - x[4]), d2 = fabsf(c2 - x[4]);
+            if (d1 < dmin) { zb = c1; dmin = d1; }
+            if (d2 < dmin) { zb = c2; dmin = d2; }
+            z[4] = zb;
+            const float area = x[2] * x[3];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                const float rr = i < 4 ? P.r[i] * area : P.r[i];
+                const float y = z[i] - x[i];
+                const float inv = 1.0f / (pxx[i] + rr);
+                const float kx = pxx[i] * inv, kv = pxv[i] * inv;
+                x[i] = x[i] + kx * y;
+                v[i] = v[i] + kv * y;
+                const float oxx = pxx[i], oxv = pxv[i];
+                pxx[i] = oxx - kx * oxx;
+                pxv[i] = oxv - kx * oxv;
+                pvv[i] = pvv[i] - kv * oxv;
+            }
+            x[4] = mod180(x[4]);
+            score = P.momentum * score + one_minus_m * s_sc[md];
+            missed = 0;
+        }
+
+        // 5. retire (KFTracklet.is_feasible on the current box, or max_missed frames without a match)
+        if (live) {
+            const bool bad = score < P.min_score || x[0] < 0.0f || x[1] < 0.0f || x[2] < 0.0f || x[3] < 0.0f || x[0] > P.img_w ||
+                             x[1] > P.img_h || x[2] > P.img_w || x[3] > P.img_h || missed >= P.max_missed;
+            if (bad) {
+                live = false;
+#pragma unroll
+                for (int i = 0; i < 5; ++i) { x[i] = v[i] = pxx[i] = pxv[i] = pvv[i] = 0.0f; }
+                score = 0.0f; missed = 0; cls = 0; id = 0;
+            }
+        }
+        __syncthreads();                                           // s_dmatch is complete
+
+        // 6. births: the k-th unmatched detection above new_thres (in rank order) goes to the k-th lowest free slot
+        for (int p0 = 0; p0 < n64; p0 += nthr) {
+            const int p = p0 + tid;
+            const bool flag = p < n && s_dmatch[p] < 0 && s_sc[s_order[p]] >= P.new_thres;
+            const unsigned long long bits = __ballot(flag);
+            if (lane == 0 && p < KMAX) s_bmask[p >> 6] = bits;
+        }
+        {
+            const unsigned long long bits = __ballot(slot_ok && !live);
+            if (lane == 0) s_fmask[wave] = bits;
+        }
+        __syncthreads();
+        for (int p = tid; p < n; p += nthr)
+            if ((s_bmask[p >> 6] >> (p & 63)) & 1ull) s_bpos[prefix_bits(s_bmask, p)] = p;
+        __syncthreads();
+        int nbirth = 0, nfree = 0;
+#pragma unroll
+        for (int w = 0; w < KMAX / 64; ++w) nbirth += __popcll(s_bmask[w]);
+#pragma unroll
+        for (int w = 0; w < NWMAX; ++w) nfree += __popcll(s_fmask[w]);
+        const int born = nbirth < nfree ? nbirth : nfree;
+        if (slot_ok && !live) {
+            const int fr = prefix_bits(s_fmask, tid);
+            if (fr < born) {                                       // RotBBoxKalmanFilter.initiate
+                const int d = s_order[s_bpos[fr]];
+#pragma unroll
+                for (int i = 0; i < 5; ++i) x[i] = s_z[i][d];
+                x[4] = mod180(x[4]);
+                const float area = x[2] * x[3];
+#pragma unroll
+                for (int i = 0; i < 5; ++i) {
+                    v[i] = 0.0f;
+                    pxx[i] = i < 4 ? P.p0[i] * area : P.p0[i];
+                    pxv[i] = 0.0f;
+                    pvv[i] = i < 4 ? P.p0[5 + i] * area : P.p0[5 + i];
+                }
+                score = s_sc[d]; missed = 0; cls = s_cl[d]; id = next_id + fr;
+                live = true;
+            }
+        }
+        next_id += born;
+        nlive = MT - nfree + born;
+
+        // the frame's outputs
+        if (slot_ok) {
+            float *ob = a.obox + (o * MT + tid) * 5;
+            ob[0] = x[0]; ob[1] = x[1]; ob[2] = x[2]; ob[3] = x[3]; ob[4] = x[4];
+            a.oscore[o * MT + tid] = score; a.ocls[o * MT + tid] = cls; a.oid[o * MT + tid] = id;
+            a.omissed[o * MT + tid] = live ? missed : -1;
+        }
+        if (tid == 0) { a.ocount[o] = nlive; a.odropped[o] = nbirth - born; }
+    }
+
+    if (slot_ok) {
+        g_cls[tid] = cls; g_id[tid] = id;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            g_x[i * MT + tid] = x[i]; g_v[i * MT + tid] = v[i];
+            g_pxx[i * MT + tid] = pxx[i]; g_pxv[i * MT + tid] = pxv[i]; g_pvv[i * MT + tid] = pvv[i];
+        }
+        g_score[tid] = score; g_missed[tid] = missed;
+    }
+    if (tid == 0) { *reinterpret_cast<int64_t *>(st) = next_id; st[2] = nlive; }
+}
+
+__global__ __launch_bounds__(256) void track_reset_kernel(int32_t *state, int64_t words) {
+    int32_t *st = state + (int64_t)blockIdx.x * words;
+    for (int64_t i = threadIdx.x; i < words; i += 256) st[i] = i == 0 ? 1 : 0;      // next id 1, everything else 0
+}
+
+}  // namespace
+
+extern "C" int64_t mydet_track_state_words(int max_tracks) {
+    if (max_tracks < 1 || max_tracks > MYDET_TRACK_MAX_TRACKS) return 0;
+    return ((int64_t)MYDET_TRACK_STATE_HEADER + (int64_t)MYDET_TRACK_SLOT_WORDS * max_tracks + 3) / 4 * 4;
+}
+
+extern "C" int mydet_track_reset(int32_t *state, int S, int max_tracks, void *stream) {
+    if (S <= 0 || max_tracks < 1 || !state || ((uintptr_t)state & 15)) return MYDET_E_BADARG;
+    if (max_tracks > MYDET_TRACK_MAX_TRACKS) return MYDET_E_UNSUPP;
+    hipLaunchKernelGGL(track_reset_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, state, mydet_track_state_words(max_tracks));
+    return mydet_launch_status();
+}
+
+extern "C" int mydet_track_frames_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                      int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                      float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                      int32_t *out_count, int32_t *out_dropped, void *stream) {
+    if (S <= 0 || F <= 0 || max_tracks < 1) return MYDET_E_BADARG;
+    if (box_width != 4 && box_width != 5) return MYDET_E_BADARG;
+    if (!records || !params || !state || !out_box || !out_score || !out_class || !out_id || !out_missed || !out_count || !out_dropped)
+        return MYDET_E_BADARG;
+    if (params->match != MYDET_TRACK_MATCH_IOU && params->match != MYDET_TRACK_MATCH_ROTATED) return MYDET_E_BADARG;
+    if (params->match == MYDET_TRACK_MATCH_ROTATED && box_width != 5) return MYDET_E_BADARG;
+    // a record's box plane is read with 16-byte loads: the base and both strides keep that alignment
+    if (((uintptr_t)records & 15) || ((uintptr_t)state & 15)) return MYDET_E_BADARG;
+    if (stream_stride_words < 0 || frame_stride_words < 0 || (stream_stride_words & 3) || (frame_stride_words & 3)) return MYDET_E_BADARG;
+    if (((uintptr_t)out_box & 3) || ((uintptr_t)out_score & 3) || ((uintptr_t)out_class & 7) || ((uintptr_t)out_id & 7) ||
+        ((uintptr_t)out_missed & 3) || ((uintptr_t)out_count & 3) || ((uintptr_t)out_dropped & 3))
+        return MYDET_E_BADARG;
+    if (max_tracks > MYDET_TRACK_MAX_TRACKS) return MYDET_E_UNSUPP;
+    TrackArgs a;
+    a.rec = records; a.stream_st = stream_stride_words; a.frame_st = frame_stride_words; a.F = F; a.MT = max_tracks;
+    a.p = *params;
+    a.state = state; a.state_words = mydet_track_state_words(max_tracks);
+    a.obox = out_box; a.oscore = out_score; a.ocls = out_class; a.oid = out_id; a.omissed = out_missed; a.ocount = out_count;
+    a.odropped = out_dropped;
+    const dim3 grid((unsigned)S), block((unsigned)((max_tracks + 63) / 64 * 64));
+    if (box_width == 4) hipLaunchKernelGGL((track_kernel<4, false>), grid, block, 0, (hipStream_t)stream, a);
+    else if (params->match == MYDET_TRACK_MATCH_ROTATED) hipLaunchKernelGGL((track_kernel<5, true>), grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((track_kernel<5, false>), grid, block, 0, (hipStream_t)stream, a);
+    return mydet_launch_status();
+}

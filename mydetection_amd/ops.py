@@ -1319,6 +1319,171 @@ def merge_tile_records(rec, B, T, origins, nms_thres, metric='iou', rotated_nms=
     return record_views(records)
 
 
+TRACK_MATCHES = {'iou': _lib.TRACK_MATCH_IOU, 'rotated': _lib.TRACK_MATCH_ROTATED}        # MYDET_TRACK_MATCH_* of include/mydet.h
+# KFTracklet's constants (reference utils/structures.py:457-460): standard deviations; the kernel takes their squares
+TRACK_P0 = (0.1, 0.1, 0.1, 0.1, 10, 0.1, 0.1, 0.1, 0.1, 10)
+TRACK_Q = (0.049, 0.032, 0.052, 0.097, 13.62, 0.01, 0.01, 0.01, 0.01, 1)
+TRACK_R = (0.073, 0.064, 0.124, 0.163, 24.39)
+
+
+def track_match_id(match):
+    """The C selector of a tracker's pair test; a ValueError for an unknown one (raised before any device is touched)."""
+    if not isinstance(match, str) or match not in TRACK_MATCHES:
+        raise ValueError(f'track_frames: match {match!r} is not one of {sorted(TRACK_MATCHES)}')
+    return TRACK_MATCHES[match]
+
+
+def track_state_words(max_tracks):
+    """int32 words of one stream's tracker state (include/mydet.h: mydet_track_state_words); host arithmetic only."""
+    max_tracks = int(max_tracks)
+    if not 1 <= max_tracks <= _lib.TRACK_MAX_TRACKS:
+        raise ValueError(f'tracker: 1 <= max_tracks <= {_lib.TRACK_MAX_TRACKS} expected, got {max_tracks}')
+    return (_lib.TRACK_STATE_HEADER + _lib.TRACK_SLOT_WORDS * max_tracks + 3) // 4 * 4
+
+
+def track_variances(std, n, what):
+    """n standard deviations -> float32 variances (squared in double, rounded once), as the kernel's parameter struct holds them."""
+    v = np.asarray(std, dtype=np.float64).reshape(-1)
+    if v.shape != (n,) or not np.all(np.isfinite(v)) or np.any(v < 0):
+        raise ValueError(f'tracker: {what} = {n} finite, non-negative standard deviations expected, got {std!r}')
+    return np.square(v).astype(np.float32)
+
+
+def track_params(img_hw, match='iou', match_thres=0.3, new_thres=0.3, max_missed=30, momentum=0.8, min_score=0.1, p0=TRACK_P0,
+                 q=TRACK_Q, r=TRACK_R):
+    """The parameter struct of mydet_track_frames_f32 (a _lib.TrackParams) from the reference's units: p0, q, r are standard
+    deviations (KFTracklet's by default).  ValueError for anything out of range; touches no device."""
+    m = track_match_id(match)
+    max_missed = int(max_missed)
+    if max_missed < 1:
+        raise ValueError(f'tracker: max_missed >= 1 expected, got {max_missed}')
+    if not 0 <= float(momentum) <= 1:
+        raise ValueError(f'tracker: momentum in [0, 1] expected, got {momentum!r}')
+    h, w = (float(v) for v in img_hw)
+    if not (h > 0 and w > 0):
+        raise ValueError(f'tracker: a positive frame size (H, W) expected, got {img_hw!r}')
+    p = _lib.TrackParams()
+    p.p0[:], p.q[:], p.r[:] = track_variances(p0, 10, 'p0').tolist(), track_variances(q, 10, 'q').tolist(), track_variances(r, 5, 'r').tolist()
+    p.momentum, p.min_score, p.new_thres, p.match_thres = float(momentum), float(min_score), float(new_thres), float(match_thres)
+    p.img_h, p.img_w, p.max_missed, p.match = h, w, max_missed, m
+    return p
+
+
+def track_state(streams, max_tracks, device):
+    """A reset tracker state: int32 [streams, track_state_words(max_tracks)] (include/mydet.h has the layout)."""
+    words = track_state_words(max_tracks)
+    streams = int(streams)
+    if streams < 1:
+        raise ValueError(f'tracker: streams >= 1 expected, got {streams}')
+    state = torch.empty((streams, words), dtype=torch.int32, device=device)
+    return track_reset_(state, max_tracks)
+
+
+def _check_track_state(state, max_tracks, what):
+    words = track_state_words(max_tracks)
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != words or not state.is_contiguous():
+        got = f'{state.dtype} {tuple(state.shape)}' if isinstance(state, torch.Tensor) else type(state).__name__
+        raise ValueError(f'{what}: a contiguous int32 state [streams, {words}] for max_tracks = {max_tracks} expected, got {got}')
+    require_gpu(state, what)
+    return words
+
+
+def track_reset_(state, max_tracks):
+    """Reset a tracker state in place (mydet_track_reset): no tracks, the next id of every stream is 1."""
+    _check_track_state(state, max_tracks, 'track_reset_')
+    code = _lib.lib().mydet_track_reset(_ptr(state), state.shape[0], int(max_tracks), _stream())
+    _lib.check(code, 'mydet_track_reset')
+    return state
+
+
+def track_state_views(state, max_tracks=None):
+    """Field views of a tracker state int32 [S, words] (include/mydet.h: mydet_track_frames_f32), nothing copied: a dict of
+    x, v, pxx, pxv, pvv float32 [S,5,MT] (rows cx, cy, w, h, angle), score float32 [S,MT], cls, id int64 [S,MT] (id 0 = a free
+    slot), missed int32 [S,MT], next_id int64 [S], live int32 [S].  max_tracks: taken from the row length when None.  Works on
+    any device (tests read a host copy)."""
+    if state.dtype != torch.int32 or state.dim() != 2 or not state.is_contiguous():
+        raise ValueError(f'track_state_views: a contiguous int32 state [streams, words] expected, got {state.dtype} {tuple(state.shape)}')
+    S, words = state.shape
+    if max_tracks is None:
+        max_tracks = (words - _lib.TRACK_STATE_HEADER) // _lib.TRACK_SLOT_WORDS
+    mt = int(max_tracks)
+    if words != track_state_words(mt):
+        raise ValueError(f'track_state_views: {words} words per stream is not the state of max_tracks = {mt}')
+    o = _lib.TRACK_STATE_HEADER
+    out = {'next_id': state[:, 0:2].view(torch.int64)[:, 0], 'live': state[:, 2]}
+    out['cls'] = state[:, o:o + 2 * mt].view(torch.int64)
+    out['id'] = state[:, o + 2 * mt:o + 4 * mt].view(torch.int64)
+    o += 4 * mt
+    for name in ('x', 'v', 'pxx', 'pxv', 'pvv'):
+        out[name] = state[:, o:o + 5 * mt].view(torch.float32).view(S, 5, mt)
+        o += 5 * mt
+    out['score'] = state[:, o:o + mt].view(torch.float32)
+    out['missed'] = state[:, o + mt:o + 2 * mt]
+    return out
+
+
+def track_frames(records, tracker_state, params, frames_per_stream=None, max_tracks=None, out=None):
+    """Advance S streams by F frames each in ONE launch (include/mydet.h: mydet_track_frames_f32, where the rules are).
+    records: the detection records in frame coordinates -- an int32 tensor [S*F, words] (frame f of stream s in row s*F + f) or
+    [S, F, words] with any strides along S and F that are multiples of 4 words, or the record_views dict of a [S*F, words]
+    buffer; words = REC_WORDS (cxcywh) or REC_ROT_WORDS (cxcywhd).  tracker_state: int32 [S, track_state_words(max_tracks)]
+    from track_state, updated in place.  params: track_params(...).  frames_per_stream: F for 2-d records (default: rows / S).
+    Returns a dict of device tensors: box [S,F,MT,5], score [S,F,MT], cls, id int64 [S,F,MT] (id 0 = a free slot), missed int32
+    [S,F,MT] (0 = matched or born in this frame, -1 = a free slot), count int32 [S,F] (live tracks; MYDET_COUNT_BAD_CLASS for
+    a bad-class frame, which leaves the state alone), dropped int32 [S,F].  out: such a dict to write into."""
+    if not isinstance(params, _lib.TrackParams):
+        raise TypeError(f'track_frames: params is a _lib.TrackParams (ops.track_params), got {type(params).__name__}')
+    if isinstance(records, dict):
+        views, records = records, records['records']
+        if views['bbox'].data_ptr() != records.data_ptr() + 4 * _lib.REC_BBOX:
+            raise ValueError("track_frames: the fields of this record dict are copies, not views of its 'records' buffer")
+    if not isinstance(tracker_state, torch.Tensor) or tracker_state.dim() != 2:
+        raise ValueError('track_frames: tracker_state is the int32 [streams, words] tensor of ops.track_state')
+    S = tracker_state.shape[0]
+    if max_tracks is None:
+        max_tracks = (tracker_state.shape[1] - _lib.TRACK_STATE_HEADER) // _lib.TRACK_SLOT_WORDS
+    mt = int(max_tracks)
+    words = records.shape[-1]
+    if records.dtype != torch.int32 or words not in (_lib.REC_WORDS, _lib.REC_ROT_WORDS):
+        raise ValueError(f'track_frames: int32 records of {_lib.REC_WORDS} or {_lib.REC_ROT_WORDS} words expected, got '
+                         f'{records.dtype} {tuple(records.shape)}')
+    width = 4 if words == _lib.REC_WORDS else 5
+    if params.match == _lib.TRACK_MATCH_ROTATED and width != 5:
+        raise ValueError("track_frames: match 'rotated' needs 'cxcywhd' records (the rotated record with its angle plane)")
+    if records.dim() == 2:
+        F = records.shape[0] // S if frames_per_stream is None else int(frames_per_stream)
+        if F < 1 or records.shape[0] != S * F:
+            raise ValueError(f'track_frames: {records.shape[0]} records are not F frames of each of {S} streams')
+        records = records.contiguous().view(S, F, words)
+    if records.dim() != 3 or records.shape[0] != S or records.shape[1] < 1:
+        raise ValueError(f'track_frames: records of shape [S*F, {words}] or [{S}, F, {words}] expected, got {tuple(records.shape)}')
+    F = records.shape[1]
+    _check_track_state(tracker_state, mt, 'track_frames')
+    require_gpu(records, 'track_frames')
+    if records.device != tracker_state.device:
+        raise ValueError(f'track_frames: records on {records.device}, state on {tracker_state.device}')
+    if records.stride(2) != 1 or records.stride(0) % 4 or records.stride(1) % 4 or min(records.stride(0), records.stride(1)) < 0:
+        records = records.contiguous()
+    dev = records.device
+    shapes = {'box': ((S, F, mt, 5), torch.float32), 'score': ((S, F, mt), torch.float32), 'cls': ((S, F, mt), torch.int64),
+              'id': ((S, F, mt), torch.int64), 'missed': ((S, F, mt), torch.int32), 'count': ((S, F), torch.int32),
+              'dropped': ((S, F), torch.int32)}
+    if out is None:
+        out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+    for k, (shape, dt) in shapes.items():
+        t = out[k]
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f'track_frames: out[{k!r}] must be a contiguous {dt} tensor {shape} on {dev}')
+    t0 = TIMER.start() if TIMER else None
+    code = _lib.lib().mydet_track_frames_f32(_ptr(records), records.stride(0), records.stride(1), S, F, width, ctypes.byref(params), mt,
+                                             _ptr(tracker_state), _ptr(out['box']), _ptr(out['score']), _ptr(out['cls']),
+                                             _ptr(out['id']), _ptr(out['missed']), _ptr(out['count']), _ptr(out['dropped']), _stream())
+    if t0:
+        TIMER.stop('track_frames', t0, float(S * F))
+    _lib.check(code, 'mydet_track_frames_f32')
+    return out
+
+
 def bboxes_iou(a, b, xyxy=False):
     require_gpu(a, 'bboxes_iou')
     a, b = a.contiguous().float(), b.contiguous().float()

@@ -27,8 +27,10 @@ class ImageObjects():
         scores (optional): 1-d tensor, torch.float32, scores
         bb_format (optional): 'cxcywh', or 'cxcywhd' (rotated boxes: cx, cy, w, h, angle in degrees)
         img_hw: tuple-like, image (height, width)
+        obj_ids (optional): 1-d tensor, torch.int64, persistent track identities (Detector.predict_frames(tracker=)); else None
     '''
-    def __init__(self, bboxes, cats, masks=None, scores=None, bb_format='cxcywh', img_hw=None):
+    def __init__(self, bboxes, cats, masks=None, scores=None, bb_format='cxcywh', img_hw=None, obj_ids=None):
+        self.obj_ids: torch.LongTensor = obj_ids
         self.bboxes: torch.FloatTensor = bboxes
         self.cats: torch.LongTensor = cats
         self.masks: torch.BoolTensor = masks
@@ -44,7 +46,7 @@ class ImageObjects():
         c = self.cats[idx]
         m = self.masks[idx, :, :] if self.masks is not None else None
         s = self.scores[idx] if self.scores is not None else None
-        return ImageObjects(b, c, m, s, self._bb_format, self.img_hw)
+        return ImageObjects(b, c, m, s, self._bb_format, self.img_hw, None if self.obj_ids is None else self.obj_ids[idx])
 
     def __len__(self):
         return self.bboxes.shape[0]
@@ -55,6 +57,7 @@ class ImageObjects():
         self.cats = self.cats.cpu()
         self.scores = self.scores.cpu() if self.scores is not None else None
         self.masks = self.masks.cpu() if self.masks is not None else None
+        self.obj_ids = self.obj_ids.cpu() if self.obj_ids is not None else None
 
     def cuda_(self, device='cuda'):
         '''Move all attributes to the GPU in-place (the kernels need them there)'''
@@ -62,6 +65,7 @@ class ImageObjects():
         self.cats = self.cats.to(device)
         self.scores = self.scores.to(device) if self.scores is not None else None
         self.masks = self.masks.to(device) if self.masks is not None else None
+        self.obj_ids = self.obj_ids.to(device) if self.obj_ids is not None else None
 
     def sort_by_score_(self, descending=True):
         '''Sort the bounding boxes by scores in-place'''
@@ -71,6 +75,8 @@ class ImageObjects():
         self.bboxes = self.bboxes[idxs, :]
         self.cats = self.cats[idxs]
         self.scores = self.scores[idxs]
+        if self.obj_ids is not None:
+            self.obj_ids = self.obj_ids[idxs]
 
     def category_filter_(self, categories) -> None:
         '''Keep the objects in the given category set and discard others in-place.'''
@@ -82,6 +88,8 @@ class ImageObjects():
         self.cats = self.cats[keep_mask]
         if self.scores is not None:
             self.scores = self.scores[keep_mask]
+        if self.obj_ids is not None:
+            self.obj_ids = self.obj_ids[keep_mask]
 
     # ------------------------------------------------------------------ post-processing
     def _device_fields(self):
