@@ -796,6 +796,98 @@ int mydet_yuv420_to_input_f32(const mydet_yuv420_src *src, int B, int H, int W,
                               const int32_t *bounds_y, const int32_t *ky, int ksy,
                               int norm, const float *mean3, const float *std3, void *stream);
 
+/* Overlay renderer: outlines of axis-aligned and rotated boxes, optional translucent fills and text labels, painted IN PLACE
+ * into uint8 RGB frames or into the planes of the 8-bit 4:2:0 layouts, one launch per batch (csrc/draw.hip).  It stands where
+ * the reference's utils/visualization.py:draw_bboxes_on_np and ImageObjects.draw_on_np (utils/structures.py) stand, with their
+ * intent and call shape -- not cv2's pixels: the raster rules are this library's own, and they are these.
+ *
+ * Geometry.  The centre of pixel (row i, column j) is (j + 0.5, i + 0.5).  A row of the list is (cx, cy, w, h) in frame pixels
+ *   and an angle in degrees (0 without an angle plane).  With c = cos(angle), s = sin(angle), dx = j + 0.5 - cx, dy = i + 0.5 - cy:
+ *       a = |dx*c + dy*s|,   b = |-dx*s + dy*c|
+ *   (the reference's vertex convention, pts @ [[c, s], [-s, c]]: clockwise on screen).  angle == 0 uses c = 1, s = 0 exactly, with
+ *   no trigonometric call; otherwise c, s = cosf, sinf of fmodf(angle, 360) * (pi / 180) in float32.  All arithmetic is float32
+ *   and uncontracted.
+ * Outline of thickness t (1..MYDET_DRAW_MAX_THICKNESS): painted iff a <= w/2 + t/2 and b <= h/2 + t/2 and not
+ *   (a < w/2 - t/2 and b < h/2 - t/2): centred on the rectangle's edge, mitred corners; a box thinner than t is solid.  Opaque.
+ * Fill (fill_alpha 1..255; 0 = none): every pixel with a <= w/2 and b <= h/2 becomes, per channel and in integers,
+ *   (colour * alpha + old * (255 - alpha) + 127) / 255.
+ * Label (label_flags; parts in the order class, score, id, one space between two parts; a part whose plane is NULL, or an empty name, is left out):
+ *   class  names[cls] (ASCII, up to MYDET_DRAW_NAME_BYTES characters, NUL-terminated when shorter) when a names table is given
+ *          and 0 <= cls < n_names, else the decimal class index ('-' first when negative), cut to MYDET_DRAW_NAME_BYTES characters
+ *   score  d.dd of n = min(100, floor(score * 100 + 0.5)) in float32; NaN or a score <= 0 gives 0.00
+ *   id     '#', then the decimal of id mod 10^10 (non-negative)
+ *   -- at most MYDET_DRAW_MAX_GLYPHS glyphs, from a monospace cell atlas [96][ch][cw] of 0 / 1 bytes for ASCII 32..127 (another
+ *   byte shows '?').  The rectangle is ch rows x n*cw columns; left column clamp(floor(cx - w/2 - t/2), 0, max(0, W - n*cw)), top
+ *   row clamp(floor(cy - h/2 - t/2) - ch, 0, max(0, H - ch)); clipped to the frame.  Background: the box colour, opaque; text:
+ *   white when 299 R + 587 G + 114 B < 150000, black otherwise.
+ * Order.  Per frame rows count - 1 down to 0, for each row fill, outline, label: row 0 (a record's highest score) ends up on top.
+ * Skipped: a row with a non-finite cx, cy, w, h or angle, or with w <= 0 or h <= 0; a frame with count <= 0 (that includes
+ *   MYDET_COUNT_BAD_CLASS).  A count above K means K; a NULL count means K for every frame.  Everything is clipped to the frame:
+ *   a box of any size or position is legal and nothing outside the H x W view is written (or read).
+ * Colour, per row: palette[key mod n_palette] (non-negative mod) with key the class (MYDET_DRAW_COLOR_CLASS) or the id
+ *   (MYDET_DRAW_COLOR_ID; 0 when that plane is NULL), or the fixed `color` (MYDET_DRAW_COLOR_FIXED).
+ * 4:2:0 targets (NV12, NV21, I420; YV12 = I420 with the planes exchanged by the caller; odd H and W legal).  Luma is painted
+ *   per pixel with Y of the colour.  A chroma sample covers its quad of luma pixels (2 x 2, fewer at odd edges) and receives, in
+ *   paint order and once each, every operation (fill, outline, label) that hits any pixel of its quad; the operation's colour
+ *   is its colour at the first pixel of the quad it hits, in raster order (this matters inside labels only); a fill blends U and
+ *   V with the formula above.  RGB -> Y'CbCr is fixed point with 8 fraction bits, `>>` arithmetic, each result clamped to 0..255:
+ *       Y = ((yr*R + yg*G + yb*B + 128) >> 8) + (16 limited | 0 full),  U = ((ur*R + ug*G + ub*B + 128) >> 8) + 128,  V likewise
+ *     matrix, full_range     yr   yg  yb     ur   ug   ub     vr    vg   vb
+ *     0 (BT.601), 0          66  129  25    -38  -74  112    112   -94  -18
+ *     0 (BT.601), 1          77  150  29    -43  -85  128    128  -107  -21
+ *     1 (BT.709), 0          47  157  16    -26  -86  112    112  -102  -10
+ *     1 (BT.709), 1          54  183  18    -29  -99  128    128  -116  -12
+ *   (within 1 code value of the float64 matrix rounded to nearest for all 2^24 colours; every grey gives U = V = 128).
+ *   MYDET_YUV420_P010 / _I010 targets are not drawn: MYDET_E_BADARG.
+ *
+ * mydet_draw_list: DEVICE pointers with ELEMENT strides per frame and per row, so the planes of a detection record are read
+ *   in place (box = the [B,512,4] plane, four floats of a row adjacent; angle, score, cls and id each their own plane) and a
+ *   dense [B,K,5] array by the same struct (angle = box + 4 with the box strides).  angle, score, cls, id and count may be NULL.
+ *   K <= MYDET_DRAW_MAX_BOXES rows per frame and launch.
+ * mydet_draw_style: palette DEVICE uint8 [n_palette][3]; atlas DEVICE uint8 [96][ch][cw] (needed when label_flags != 0; ch in
+ *   8..64, cw in 1..64); names DEVICE uint8 [n_names][MYDET_DRAW_NAME_BYTES] or NULL.
+ * Frames of mydet_draw_boxes_rgb_u8 are [H][W][3], frame b at dst + b*dst_img_bytes, rows dst_row_bytes >= 3*W apart (as the
+ *   source of mydet_frames_to_input_f32: a crop view is drawn in place).  mydet_draw_boxes_yuv420_u8 takes the plane descriptor
+ *   of the input side and WRITES the planes.  Pixel groups are loaded and stored with dword accesses when address, pitch and
+ *   frame stride are multiples of: RGB 4; NV12 / NV21 4 (both planes); I420 4 (Y), 2 (U, V: 16-bit accesses) -- and byte by byte
+ *   otherwise, and in a row's partial last group, with the same result.  A tile (64 x 16 pixels RGB, 128 x 16 for 4:2:0) that no
+ *   box or label reaches (the bounding box of a row's outer rectangle, less -- without a fill -- the tiles inside the outline's
+ *   hole, and its label rectangle) is neither read nor written; in the others only pixel groups that some operation hit are stored.
+ * MYDET_E_BADARG, with nothing launched: a null list, style, box plane or target; non-positive B, H, W; a pitch below the
+ *   row's bytes; a negative stride; K outside 1..MYDET_DRAW_MAX_BOXES; thickness outside 1..MYDET_DRAW_MAX_THICKNESS; fill_alpha
+ *   outside 0..255; an unknown colour mode or a palette mode without a palette; unknown label flags; labels without an atlas, ch
+ *   outside 8..64 or cw outside 1..64; names with n_names < 1; an unknown layout, matrix or range, a 10-bit layout, plane[2]
+ *   not matching the layout. */
+#define MYDET_DRAW_MAX_BOXES     512
+#define MYDET_DRAW_MAX_THICKNESS 64
+#define MYDET_DRAW_MAX_GLYPHS    33
+#define MYDET_DRAW_NAME_BYTES    16
+#define MYDET_DRAW_COLOR_CLASS   0
+#define MYDET_DRAW_COLOR_ID      1
+#define MYDET_DRAW_COLOR_FIXED   2
+#define MYDET_DRAW_LABEL_CLASS   1
+#define MYDET_DRAW_LABEL_SCORE   2
+#define MYDET_DRAW_LABEL_ID      4
+typedef struct mydet_draw_list {
+    const float *box;      int64_t box_frame_stride, box_row_stride;       /* (cx, cy, w, h) adjacent; strides in floats */
+    const float *angle;    int64_t angle_frame_stride, angle_row_stride;   /* degrees, or NULL */
+    const float *score;    int64_t score_frame_stride, score_row_stride;   /* or NULL */
+    const int64_t *cls;    int64_t cls_frame_stride, cls_row_stride;       /* or NULL */
+    const int64_t *id;     int64_t id_frame_stride, id_row_stride;         /* or NULL */
+    const int32_t *count;  int64_t count_stride;                           /* rows to draw per frame, or NULL = K */
+    int K, reserved;
+} mydet_draw_list;
+typedef struct mydet_draw_style {
+    int thickness, fill_alpha, color_mode, label_flags;
+    unsigned char color[4];                                                /* R, G, B of MYDET_DRAW_COLOR_FIXED; [3] ignored */
+    int n_palette, ch, cw, n_names;
+    const unsigned char *palette, *atlas, *names;
+} mydet_draw_style;
+int mydet_draw_boxes_rgb_u8(unsigned char *dst, int B, int H, int W, int64_t dst_img_bytes, int64_t dst_row_bytes,
+                            const mydet_draw_list *list, const mydet_draw_style *style, void *stream);
+int mydet_draw_boxes_yuv420_u8(const mydet_yuv420_src *planes, int B, int H, int W, const mydet_draw_list *list,
+                               const mydet_draw_style *style, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

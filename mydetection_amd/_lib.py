@@ -96,6 +96,8 @@ SIGNATURES = {
     'mydet_yuv420_to_input_f32': [c_ptr, c_int, c_int, c_int,
                                   c_ptr, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
+    'mydet_draw_boxes_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr],
+    'mydet_draw_boxes_yuv420_u8': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_cxcywh_to_x1y1x2y2_f32': [c_ptr, c_ptr, c_i64, c_int, c_ptr],
     'mydet_bboxes_to_original_f32': [c_ptr, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr],
 }
@@ -122,6 +124,10 @@ MERGE_IOU, MERGE_IOS = 0, 1
 TRACK_MAX_TRACKS = 512
 TRACK_STATE_HEADER, TRACK_SLOT_WORDS = 8, 31
 TRACK_MATCH_IOU, TRACK_MATCH_ROTATED = 0, 1
+# overlay renderer (mydet_draw_boxes_*): MYDET_DRAW_* of include/mydet.h
+DRAW_MAX_BOXES, DRAW_MAX_THICKNESS, DRAW_MAX_GLYPHS, DRAW_NAME_BYTES = 512, 64, 33, 16
+DRAW_COLOR_CLASS, DRAW_COLOR_ID, DRAW_COLOR_FIXED = 0, 1, 2
+DRAW_LABEL_CLASS, DRAW_LABEL_SCORE, DRAW_LABEL_ID = 1, 2, 4
 
 
 class DecodeLevel(ctypes.Structure):
@@ -177,6 +183,23 @@ class TrackParams(ctypes.Structure):
     _fields_ = [('p0', c_f32 * 10), ('q', c_f32 * 10), ('r', c_f32 * 5), ('momentum', c_f32), ('min_score', c_f32),
                 ('new_thres', c_f32), ('match_thres', c_f32), ('img_h', c_f32), ('img_w', c_f32), ('max_missed', c_int),
                 ('match', c_int)]
+
+
+class DrawList(ctypes.Structure):
+    """mydet_draw_list (include/mydet.h): device pointers with element strides per frame and per row."""
+    _fields_ = [('box', c_ptr), ('box_frame_stride', c_i64), ('box_row_stride', c_i64),
+                ('angle', c_ptr), ('angle_frame_stride', c_i64), ('angle_row_stride', c_i64),
+                ('score', c_ptr), ('score_frame_stride', c_i64), ('score_row_stride', c_i64),
+                ('cls', c_ptr), ('cls_frame_stride', c_i64), ('cls_row_stride', c_i64),
+                ('id', c_ptr), ('id_frame_stride', c_i64), ('id_row_stride', c_i64),
+                ('count', c_ptr), ('count_stride', c_i64), ('K', c_int), ('reserved', c_int)]
+
+
+class DrawStyle(ctypes.Structure):
+    """mydet_draw_style (include/mydet.h)."""
+    _fields_ = [('thickness', c_int), ('fill_alpha', c_int), ('color_mode', c_int), ('label_flags', c_int),
+                ('color', ctypes.c_ubyte * 4), ('n_palette', c_int), ('ch', c_int), ('cw', c_int), ('n_names', c_int),
+                ('palette', c_ptr), ('atlas', c_ptr), ('names', c_ptr)]
 
 
 # MYDET_YUV420_* of include/mydet.h

@@ -1,6 +1,7 @@
 """Inference entry point of the package: `Detector` (mirror of the reference's api.detection.Detector), `Tiles`, the
-argument of its tiled detection on large frames, and `Tracker`, the argument that turns its frame methods into a tracker."""
-from .detection import Detector, Tiles
+argument of its tiled detection on large frames, `Tracker`, the argument that turns its frame methods into a tracker,
+and `Draw`, the settings of its annotate_frames methods."""
+from .detection import Detector, Draw, Tiles
 from .tracking import Tracker
 
-__all__ = ['Detector', 'Tiles', 'Tracker']
+__all__ = ['Detector', 'Draw', 'Tiles', 'Tracker']

@@ -41,6 +41,43 @@ class Tiles:
                 f'metric={self.metric!r})')
 
 
+class Draw:
+    """The settings of Detector.annotate_frames and its YUV forms: what the overlay renderer paints (ops.draw_boxes;
+    include/mydet.h has the raster rules).  thickness: the outline's, 1..64 pixels; None = max(1, round(H / 360)) for frames
+    of H rows (the reference's line_width).  labels: any of 'class', 'score', 'id' ('id' shows with a tracker only).
+    label_height: rows of a label cell, 8..64; None = round(H / 45) kept inside 10..64.  fill_alpha: 0 (no fill) .. 255.
+    color_by: 'class', 'id' or None = 'id' with a tracker and 'class' without; color: one (r, g, b) for every box instead.
+    class_names: a list of ASCII names for the class part (16 characters are shown); None = the class index."""
+
+    def __init__(self, thickness=None, labels=('class', 'score'), label_height=None, fill_alpha=0, color_by=None, color=None,
+                 class_names=None):
+        if color_by is not None and (not isinstance(color_by, str) or color_by not in ('class', 'id')):
+            raise ValueError(f"Draw: color_by {color_by!r} is not 'class', 'id' or None")
+        # ops.draw_style has the rules; None entries are checked with a stand-in and resolved per frame size
+        ops.draw_style(2 if thickness is None else thickness, fill_alpha, color_by or 'class', color, labels,
+                       16 if label_height is None else label_height, class_names)
+        self.thickness, self.label_height, self.fill_alpha = thickness, label_height, fill_alpha
+        self.labels = (labels,) if isinstance(labels, str) else tuple(labels or ())
+        self.color_by, self.color = color_by, color
+        self.class_names = None if class_names is None else list(class_names)
+        self._styles = {}
+
+    def __repr__(self):
+        return (f'Draw(thickness={self.thickness}, labels={self.labels}, label_height={self.label_height}, fill_alpha={self.fill_alpha}, '
+                f'color_by={self.color_by!r}, color={self.color}, class_names={None if self.class_names is None else len(self.class_names)})')
+
+    def style(self, frame_hw, tracked=False):
+        """The ops.DrawStyle for frames of size frame_hw (cached: its device tables are made once)."""
+        from ..utils.visualization import default_label_height
+        h = int(frame_hw[0])
+        key = (max(1, round(h / 360)) if self.thickness is None else self.thickness,
+               default_label_height(h) if self.label_height is None else self.label_height,
+               self.color_by or ('id' if tracked else 'class'))
+        if key not in self._styles:
+            self._styles[key] = ops.draw_style(min(key[0], 64), self.fill_alpha, key[2], self.color, self.labels, key[1], self.class_names)
+        return self._styles[key]
+
+
 class Detector():
     '''Wrapper for image object detectors
 
@@ -138,13 +175,21 @@ class Detector():
     def detect_one(self, **kwargs):
         '''
         object detection in one single image: (img_path: str) or (pil_img: PIL.Image);
-        see _predict_pil() for the optional arguments.  Drawing (return_img/show_img) is not
-        part of the inference path and is not provided.
+        see _predict_pil() for the optional arguments.  return_img=True returns the image as a numpy array with the detections
+        drawn on it (ImageObjects.draw_on_np, the overlay renderer on the device), as the reference does; the drawing
+        keywords of utils.visualization.draw_bboxes_on_np are passed on.  show_img (a matplotlib window) is not provided.
         '''
         assert 'pil_img' in kwargs or 'img_path' in kwargs
         img = kwargs.pop('pil_img', None) or imgUtils.imread_pil(kwargs.pop('img_path'))
-        if kwargs.get('return_img', False) or kwargs.get('show_img', False):
-            raise NotImplementedError('visualisation is outside the inference hot path')
+        if kwargs.get('show_img', False):
+            raise NotImplementedError('show_img opens a window; use return_img=True and show the array')
+        draw_kw = {k: kwargs.pop(k) for k in ('color', 'line_width', 'put_text', 'show_class', 'class_names', 'label_height', 'fill_alpha')
+                   if k in kwargs}
+        if kwargs.pop('return_img', False):
+            detections = self._predict_pil(img, **kwargs)
+            np_img = np.array(img.convert('RGB'))
+            detections.draw_on_np(np_img, class_map='COCO', **draw_kw)
+            return np_img
         return self._predict_pil(img, **kwargs)
 
     def _predict_pil(self, pil_img, **kwargs):
@@ -626,6 +671,97 @@ class Detector():
         """COCO-style rows of NV12 frames (see predict_frames_nv12): the counterpart of frames_to_json."""
         return self.frames_yuv_to_json(y if uv is None else (y, uv), 'nv12', img_ids, eval_type, catIdx2id, matrix=matrix,
                                        full_range=full_range, **kwargs)
+
+    @staticmethod
+    def _check_draw(draw, what):
+        if not isinstance(draw, Draw):
+            raise TypeError(f'{what}: draw is a mydetection_amd.api.Draw, got {type(draw).__name__}')
+
+    def _draw_objects(self, target, layout, objs, style, matrix='bt601', full_range=False):
+        """Paint a list of ImageObjects (one per frame) into the device frames or planes: the tracked form of the drawing."""
+        from ..utils.visualization import objects_to_rows
+        dev = (target if layout is None else target[0]).device
+        boxes, counts, scores, classes, ids = objects_to_rows(objs, dev)
+        if layout is None:
+            ops.draw_boxes(target, boxes, style, counts=counts, scores=scores, classes=classes, ids=ids)
+        else:
+            ops.draw_boxes_yuv420(target, layout, boxes, style, counts=counts, scores=scores, classes=classes, ids=ids, matrix=matrix,
+                                  full_range=full_range)
+
+    def annotate_frames(self, frames, draw=None, **kwargs):
+        """predict_frames plus the overlay: returns (objects, drawn).  objects is exactly what predict_frames(frames, **kwargs)
+        returns; drawn is the uint8 batch [B,H,W,3] on the device with boxes, fills and labels painted by ONE more launch
+        (include/mydet.h: mydet_draw_boxes_rgb_u8) -- the input itself, drawn in place, when it is a single device tensor with
+        packed pixels, else the device batch the call had to build anyway.  Frames of one size (ValueError otherwise).  draw: a
+        Draw (default Draw()).  tiles=, tracker= and coasting= as in predict_frames.  An untracked call draws straight from the
+        records buffer, before any host synchronisation; a tracked call draws the returned tracks, with their ids."""
+        draw = Draw() if draw is None else draw
+        self._check_draw(draw, 'annotate_frames')
+        tracker, coasting = self._pop_tracker(kwargs)
+        n, groups = self._frame_groups(frames)
+        if len(groups) != 1:
+            raise ValueError(f'annotate_frames: frames of one size expected, got {[tuple(parts[0].shape[1:3]) for _, parts in groups]}')
+        if tracker is not None:
+            tracker.check_call(n, tuple(int(v) for v in groups[0][1][0].shape[1:3]), self.model.bb_format)
+        dev = next(self.model.parameters()).device
+        parts = groups[0][1]
+        if len(parts) > 1:
+            where = dev if all(t.device == dev for t in parts) else torch.device('cpu')
+            parts = [torch.cat([t.to(where) for t in parts])]
+        fr = parts[0].to(dev, non_blocking=True)
+        if fr.stride(3) != 1 or fr.stride(2) != 3 or fr.stride(1) < 3 * fr.shape[2] or fr.stride(0) < 0:
+            fr = fr.contiguous()
+        hw = (int(fr.shape[1]), int(fr.shape[2]))
+        style = draw.style(hw, tracker is not None)
+        if tracker is not None:
+            objs = self.predict_frames(fr, tracker=tracker, coasting=coasting, **kwargs)
+            self._draw_objects(fr, None, objs, style)
+            return objs, fr
+        records = list(self._frame_records(fr, _whole_records=True, **kwargs))
+        for idxs, rec in records:                                    # one frame size: one group, in frame order
+            assert idxs == list(range(n))
+            ops.draw_records(fr, rec, style)
+        return self._objects_of_records(records), fr
+
+    def annotate_frames_yuv(self, planes, layout, draw=None, *, matrix='bt601', full_range=False, **kwargs):
+        """predict_frames_yuv plus the overlay, painted into the planes (include/mydet.h: mydet_draw_boxes_yuv420_u8): returns
+        (objects, drawn).  layout: 'nv12', 'nv21', 'i420' or 'yv12'; the 10-bit layouts are not drawn into (ValueError).  drawn:
+        the planes on the device, in the order given -- the input tensors themselves when they are device tensors -- or, for a
+        single surface, the surface.  matrix and full_range also say how the colours become Y'CbCr.  Otherwise as annotate_frames."""
+        draw = Draw() if draw is None else draw
+        self._check_draw(draw, 'annotate_frames_yuv')
+        if ops.yuv420_layout(layout)[1] != 1:
+            raise ValueError(f'annotate_frames_yuv: layout {layout!r} is not drawn into; the 8-bit layouts nv12, nv21, i420 and yv12 are')
+        ops.yuv_matrix_id(matrix)
+        tracker, coasting = self._pop_tracker(kwargs)
+        y = self._yuv_planes(planes, layout)[0]                      # the checks alone: no device is touched
+        if tracker is not None:
+            tracker.check_call(y.shape[0], tuple(int(v) for v in y.shape[1:3]), self.model.bb_format)
+        dev = next(self.model.parameters()).device
+        surface = None
+        if isinstance(planes, (np.ndarray, torch.Tensor)):
+            surface = (torch.from_numpy(np.ascontiguousarray(planes)) if isinstance(planes, np.ndarray) else planes).to(dev, non_blocking=True)
+            if not (surface[0] if surface.dim() == 3 else surface).is_contiguous():
+                surface = surface.contiguous()                       # the planar split needs packed rows to stay a view
+            ts = tuple(self._yuv_planes(surface, layout, device=dev))
+        else:
+            ts = tuple(self._yuv_planes(planes, layout, device=dev))
+        hw = (int(ts[0].shape[1]), int(ts[0].shape[2]))
+        style = draw.style(hw, tracker is not None)
+        drawn = ts if surface is None else surface
+        if tracker is not None:
+            objs = self.predict_frames_yuv(ts, layout, matrix=matrix, full_range=full_range, tracker=tracker, coasting=coasting, **kwargs)
+            self._draw_objects(ts, layout, objs, style, matrix, full_range)
+            return objs, drawn
+        records = list(self._yuv_records(ts, layout, matrix, full_range, _whole_records=True, **kwargs))
+        for idxs, rec in records:
+            assert idxs == list(range(ts[0].shape[0]))
+            ops.draw_records(ts, rec, style, layout=layout, matrix=matrix, full_range=full_range)
+        return self._objects_of_records(records), drawn
+
+    def annotate_frames_nv12(self, y, uv=None, draw=None, *, matrix='bt601', full_range=False, **kwargs):
+        """annotate_frames_yuv for NV12: (y, uv) planes, or with uv=None the single surface [B,H*3/2,W] (see predict_frames_nv12)."""
+        return self.annotate_frames_yuv(y if uv is None else (y, uv), 'nv12', draw, matrix=matrix, full_range=full_range, **kwargs)
 
     def predict_batch(self, pil_imgs, **kwargs):
         """Batched form of detect_one (the reference loops image by image, api/detection.py:67-74): images that share a

@@ -1837,3 +1837,411 @@ def preprocess_u8(img_u8, out_hw, input_format):
     code = _lib.lib().mydet_preprocess_u8_f32(_ptr(img_u8), B, H, W, _ptr(out), Hp, Wp, *_norm_args(input_format), _stream())
     _lib.check(code, 'mydet_preprocess_u8_f32')
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Overlay renderer (include/mydet.h: mydet_draw_boxes_rgb_u8 / mydet_draw_boxes_yuv420_u8, where the raster rules are).
+# draw_palette, rgb_to_yuv and draw_label_text are host functions and ARE the documented rules for colour and text.
+
+DRAW_LABELS = {'class': _lib.DRAW_LABEL_CLASS, 'score': _lib.DRAW_LABEL_SCORE, 'id': _lib.DRAW_LABEL_ID}
+DRAW_COLOR_MODES = {'class': _lib.DRAW_COLOR_CLASS, 'id': _lib.DRAW_COLOR_ID, 'fixed': _lib.DRAW_COLOR_FIXED}
+# RGB -> Y'CbCr rows with 8 fraction bits, (matrix id, full range) -> (Y row, U row, V row, luma offset): the table of include/mydet.h
+DRAW_YUV_ROWS = {(0, 0): ((66, 129, 25), (-38, -74, 112), (112, -94, -18), 16),
+                 (0, 1): ((77, 150, 29), (-43, -85, 128), (128, -107, -21), 0),
+                 (1, 0): ((47, 157, 16), (-26, -86, 112), (112, -102, -10), 16),
+                 (1, 1): ((54, 183, 18), (-29, -99, 128), (128, -116, -12), 0)}
+DRAW_PALETTE_HUES, DRAW_PALETTE_STEP = 1530, 946
+
+
+def draw_palette(n=256):
+    """The colour table of the renderer, uint8 numpy [n, 3], by integer arithmetic alone: entry i is the fully saturated,
+    full-value colour of hue h = (i * 946) mod 1530 on a wheel of 6 * 255 steps (946 / 1530 is the golden-ratio step), i.e.
+    with sector = h // 255 and f = h % 255 the channels (255, f, 0), (255 - f, 255, 0), (0, 255, f), (0, 255 - f, 255),
+    (f, 0, 255), (255, 0, 255 - f) for sectors 0..5.  Deterministic; entries are pairwise distinct for n <= 765."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f'draw_palette: n >= 1 expected, got {n}')
+    h = (np.arange(n, dtype=np.int64) * DRAW_PALETTE_STEP) % DRAW_PALETTE_HUES
+    sector, f = h // 255, h % 255
+    up, down, hi, lo = f, 255 - f, np.full(n, 255), np.zeros(n, dtype=np.int64)
+    r = np.choose(sector, [hi, down, lo, lo, up, hi])
+    g = np.choose(sector, [up, hi, hi, down, lo, lo])
+    b = np.choose(sector, [lo, lo, up, hi, hi, down])
+    return np.stack([r, g, b], axis=1).astype(np.uint8)
+
+
+def rgb_to_yuv(rgb, matrix='bt601', full_range=False):
+    """uint8 RGB [..., 3] (numpy) -> uint8 (Y, U, V) [..., 3] by the renderer's fixed-point rows (include/mydet.h):
+    Y = ((yr R + yg G + yb B + 128) >> 8) + (0 | 16), U = ((...) >> 8) + 128, V likewise, each clamped to 0..255."""
+    yr, ur, vr, yoff = DRAW_YUV_ROWS[(yuv_matrix_id(matrix), int(bool(full_range)))]
+    c = np.asarray(rgb).astype(np.int64)
+    if c.shape[-1] != 3:
+        raise ValueError(f'rgb_to_yuv: [..., 3] expected, got {c.shape}')
+    out = [((c * np.asarray(row, dtype=np.int64)).sum(-1) + 128 >> 8) + off for row, off in ((yr, yoff), (ur, 128), (vr, 128))]
+    return np.clip(np.stack(out, axis=-1), 0, 255).astype(np.uint8)
+
+
+def draw_label_flags(labels):
+    """The C label flags of an iterable of 'class' / 'score' / 'id' (or of the flags themselves); a ValueError otherwise."""
+    if isinstance(labels, (int, np.integer)) and not isinstance(labels, bool):
+        if not 0 <= int(labels) <= 7:
+            raise ValueError(f'draw: label flags in 0..7 expected, got {labels}')
+        return int(labels)
+    if labels is None:
+        return 0
+    if isinstance(labels, str):
+        labels = (labels,)
+    flags = 0
+    for name in labels:
+        if not isinstance(name, str) or name not in DRAW_LABELS:
+            raise ValueError(f'draw: label {name!r} is not one of {sorted(DRAW_LABELS)}')
+        flags |= DRAW_LABELS[name]
+    return flags
+
+
+def draw_label_text(cls=None, score=None, id=None, names=None, flags=('class', 'score', 'id')):
+    """The text the renderer writes for one row (the rule of include/mydet.h as host code).  Parts in the order class, score,
+    id, one space between two parts; a part that is not in `flags`, whose value is None or that is empty is left out.  class: names[cls]
+    cut to 16 characters when `names` is given and 0 <= cls < len(names), else the decimal class index cut to 16 characters;
+    score: d.dd of min(100, floor(score * 100 + 0.5)) in float32, 0.00 for NaN or a score <= 0; id: '#' and id mod 10^10."""
+    flags = draw_label_flags(flags)
+    parts = []
+    if flags & _lib.DRAW_LABEL_CLASS and cls is not None:
+        c = int(cls)
+        parts.append((str(names[c]) if names is not None and 0 <= c < len(names) else str(c))[:_lib.DRAW_NAME_BYTES])
+    if flags & _lib.DRAW_LABEL_SCORE and score is not None:
+        s, v = np.float32(score), 0
+        if s > 0:                                                    # NaN compares false
+            f = np.float32(np.float32(s * np.float32(100.0)) + np.float32(0.5))
+            v = 100 if f >= 100 else int(np.floor(f))
+        parts.append(f'{v // 100}.{v // 10 % 10}{v % 10}')
+    if flags & _lib.DRAW_LABEL_ID and id is not None:
+        parts.append(f'#{int(id) % 10 ** 10}')
+    return ' '.join(p for p in parts if p)
+
+
+_ATLAS_HOST = {}
+_ATLAS_DEVICE = {}
+
+
+def _glyph_atlas_host(height):
+    """uint8 numpy [96, height, cw] of 0 / 1: ASCII 32..127, one glyph per fixed cell, rendered with Pillow's default font without
+    anti-aliasing and binarised at 128.  Sized (FreeType) when this Pillow has ImageFont.load_default(size=): the largest size at which the ink of
+    every glyph fits the rows; otherwise the built-in bitmap font, repeated by the whole factor that fits."""
+    if height in _ATLAS_HOST:
+        return _ATLAS_HOST[height]
+    from PIL import Image, ImageDraw, ImageFont
+    chars = [chr(c) for c in range(32, 127)]                         # 127 (DEL) has no glyph: an empty cell
+    font, scale, boxes = None, 1, None
+    try:
+        for size in range(2 * height, 3, -1):                        # the largest size whose ink (all glyphs) fits the rows
+            f = ImageFont.load_default(size=size)
+            bs = [f.getbbox(c, mode='1') for c in chars]
+            if max(b[3] for b in bs) - min(b[1] for b in bs) <= height:
+                font, boxes = f, bs
+                break
+    except (TypeError, AttributeError, OSError):
+        font = None
+    if font is None:
+        font = ImageFont.load_default()
+        boxes = [font.getbbox(c) for c in chars]
+        scale = max(1, height // max(1, max(b[3] for b in boxes) - min(b[1] for b in boxes)))
+    x0, y0 = min(b[0] for b in boxes), min(b[1] for b in boxes)
+    cell_w = max(1, max(b[2] for b in boxes) - x0)
+    cell_h = max(1, -(-height // scale))
+    top = max(0, (cell_h - (max(b[3] for b in boxes) - y0)) // 2)
+    atlas = np.zeros((96, height, cell_w * scale), dtype=np.uint8)
+    for k, c in enumerate(chars):
+        img = Image.new('L', (cell_w, cell_h), 0)
+        pen = ImageDraw.Draw(img)
+        pen.fontmode = '1'                                           # hinted, not anti-aliased: thin strokes survive at small sizes
+        pen.text((-x0, top - y0), c, fill=255, font=font)
+        g = (np.asarray(img) >= 128).astype(np.uint8)
+        g = np.repeat(np.repeat(g, scale, axis=0), scale, axis=1)[:height]
+        atlas[k, :g.shape[0]] = g
+    _ATLAS_HOST[height] = atlas
+    return atlas
+
+
+def glyph_atlas(height, device=None):
+    """The renderer's monospace glyph atlas for label cells of `height` rows (8..64): uint8 [96, height, cw] of 0 / 1 for
+    ASCII 32..127, built at run time on the host from Pillow's default font (no font file ships with the package) and cached
+    per (device, height).  device=None: the host tensor."""
+    height = int(height)
+    if not 8 <= height <= 64:
+        raise ValueError(f'glyph_atlas: a cell height in 8..64 expected, got {height}')
+    host = _glyph_atlas_host(height)
+    if host.shape[2] > 64:
+        raise ValueError(f'glyph_atlas: cells of height {height} are {host.shape[2]} wide; the renderer takes at most 64')
+    if device is None:
+        return torch.from_numpy(host)
+    key = (str(torch.device(device)), height)
+    if key not in _ATLAS_DEVICE:
+        _ATLAS_DEVICE[key] = torch.from_numpy(host).to(device)
+    return _ATLAS_DEVICE[key]
+
+
+class DrawStyle:
+    """What ops.draw_style returns: the checked settings on the host; the device tables (palette, atlas, names) are made the
+    first time a device draws with it."""
+
+    def __init__(self, thickness, fill_alpha, color_mode, color, labels, label_height, names, n_palette):
+        self.thickness, self.fill_alpha, self.color_mode, self.color = thickness, fill_alpha, color_mode, color
+        self.label_flags, self.label_height, self.names, self.n_palette = labels, label_height, names, n_palette
+        self._tables = {}
+
+    def __repr__(self):
+        return (f'DrawStyle(thickness={self.thickness}, fill_alpha={self.fill_alpha}, color_mode={self.color_mode}, color={self.color}, '
+                f'label_flags={self.label_flags}, label_height={self.label_height}, names={None if self.names is None else len(self.names)})')
+
+    def struct(self, device):
+        """(mydet_draw_style for `device`, the tensors it points to)."""
+        key = str(torch.device(device))
+        if key not in self._tables:
+            palette = torch.from_numpy(draw_palette(self.n_palette)).to(device)
+            atlas = glyph_atlas(self.label_height, device) if self.label_flags else None
+            names = None
+            if self.names is not None and len(self.names):
+                table = np.zeros((len(self.names), _lib.DRAW_NAME_BYTES), dtype=np.uint8)
+                for k, name in enumerate(self.names):
+                    raw = name.encode('ascii', 'replace')[:_lib.DRAW_NAME_BYTES]
+                    table[k, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+                names = torch.from_numpy(table).to(device)
+            self._tables[key] = (palette, atlas, names)
+        palette, atlas, names = self._tables[key]
+        s = _lib.DrawStyle()
+        s.thickness, s.fill_alpha, s.color_mode, s.label_flags = self.thickness, self.fill_alpha, self.color_mode, self.label_flags
+        s.color[:] = list(self.color) + [0]
+        s.n_palette, s.palette = palette.shape[0], _ptr(palette)
+        if atlas is not None:
+            s.atlas, s.ch, s.cw = _ptr(atlas), atlas.shape[1], atlas.shape[2]
+        if names is not None:
+            s.names, s.n_names = _ptr(names), names.shape[0]
+        return s, (palette, atlas, names)
+
+
+def draw_style(thickness=2, fill_alpha=0, color_by='class', color=None, labels=(), label_height=16, class_names=None, n_palette=256):
+    """The settings of a draw call, checked here and touching no device (a DrawStyle).  thickness: the outline's, 1..64 pixels;
+    fill_alpha: 0 (no fill) .. 255; color_by: 'class' or 'id' (palette[key mod n_palette], ops.draw_palette) or 'fixed';
+    color: (r, g, b) -- given, it implies 'fixed'; labels: any of 'class', 'score', 'id'; label_height: rows of a label cell, 8..64
+    (ops.glyph_atlas); class_names: a list of ASCII names (16 characters are shown), None = the class index is shown."""
+    if isinstance(thickness, bool) or not isinstance(thickness, (int, np.integer)) or not 1 <= thickness <= _lib.DRAW_MAX_THICKNESS:
+        raise ValueError(f'draw_style: an integer thickness in 1..{_lib.DRAW_MAX_THICKNESS} expected, got {thickness!r}')
+    if isinstance(fill_alpha, bool) or not isinstance(fill_alpha, (int, np.integer)) or not 0 <= fill_alpha <= 255:
+        raise ValueError(f'draw_style: an integer fill_alpha in 0..255 expected, got {fill_alpha!r}')
+    if color is not None:
+        color_by = 'fixed'
+        c = tuple(color) if isinstance(color, (tuple, list, np.ndarray)) else None
+        if c is None or len(c) != 3 or any(isinstance(v, (bool, float)) or not 0 <= int(v) <= 255 for v in c):
+            raise ValueError(f'draw_style: color = (r, g, b) of integers in 0..255 expected, got {color!r}')
+        color = tuple(int(v) for v in c)
+    if not isinstance(color_by, str) or color_by not in DRAW_COLOR_MODES:
+        raise ValueError(f'draw_style: color_by {color_by!r} is not one of {sorted(DRAW_COLOR_MODES)}')
+    if color_by == 'fixed' and color is None:
+        raise ValueError("draw_style: color_by 'fixed' needs color = (r, g, b)")
+    flags = draw_label_flags(labels)
+    label_height = int(label_height)
+    if not 8 <= label_height <= 64:
+        raise ValueError(f'draw_style: a label_height in 8..64 expected, got {label_height}')
+    if class_names is not None:
+        class_names = list(class_names)
+        if not all(isinstance(n, str) for n in class_names):
+            raise TypeError('draw_style: class_names is a list of str')
+    n_palette = int(n_palette)
+    if n_palette < 1:
+        raise ValueError(f'draw_style: n_palette >= 1 expected, got {n_palette}')
+    return DrawStyle(int(thickness), int(fill_alpha), DRAW_COLOR_MODES[color_by], color or (0, 0, 0), flags, label_height, class_names, n_palette)
+
+
+def _draw_check_style(style, what):
+    if not isinstance(style, DrawStyle):
+        raise TypeError(f'{what}: style is an ops.DrawStyle (ops.draw_style), got {type(style).__name__}')
+
+
+def _draw_rows(what, B, boxes, counts, scores, classes, ids):
+    """The checked dense row tensors of a draw call (no device touched): boxes [B,K,4|5] float32 and the optional planes."""
+    if not isinstance(boxes, torch.Tensor) or boxes.dtype != torch.float32:
+        raise TypeError(f'{what}: boxes is a float32 tensor, got {boxes.dtype if isinstance(boxes, torch.Tensor) else type(boxes).__name__}')
+    if boxes.dim() == 2:
+        boxes = boxes.unsqueeze(0)
+    if boxes.dim() != 3 or boxes.shape[2] not in (4, 5) or boxes.shape[0] != B:
+        raise ValueError(f'{what}: boxes of shape [{B},K,4|5] (or [K,4|5] for one frame) expected, got {tuple(boxes.shape)}')
+    K = boxes.shape[1]
+    planes = {}
+    for name, t, dt in (('scores', scores, torch.float32), ('classes', classes, torch.int64), ('ids', ids, torch.int64)):
+        if t is None:
+            planes[name] = None
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise TypeError(f'{what}: {name} is a {dt} tensor, got {t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}')
+        t = t.unsqueeze(0) if t.dim() == 1 else t
+        if tuple(t.shape) != (B, K):
+            raise ValueError(f'{what}: {name} of shape [{B},{K}] expected, got {tuple(t.shape)}')
+        planes[name] = t
+    if counts is not None:
+        if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32:
+            raise TypeError(f'{what}: counts is an int32 tensor, got {counts.dtype if isinstance(counts, torch.Tensor) else type(counts).__name__}')
+        counts = counts.reshape(-1)
+        if counts.shape[0] != B:
+            raise ValueError(f'{what}: counts of shape [{B}] expected, got {tuple(counts.shape)}')
+    return boxes, counts, planes
+
+
+def _draw_rgb_target(what, frames):
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+        raise TypeError(f'{what}: uint8 frames expected, got {frames.dtype if isinstance(frames, torch.Tensor) else type(frames).__name__}')
+    fr = frames.unsqueeze(0) if frames.dim() == 3 else frames
+    if fr.dim() != 4 or fr.shape[3] != 3 or min(fr.shape) < 1:
+        raise ValueError(f'{what}: frames of shape [B,H,W,3] or [H,W,3] expected, got {tuple(frames.shape)}')
+    if fr.stride(3) != 1 or fr.stride(2) != 3 or fr.stride(1) < 3 * fr.shape[2] or fr.stride(0) < 0:
+        raise ValueError(f'{what}: frames are drawn in place and need packed pixels (strides {tuple(fr.stride())} of {tuple(fr.shape)})')
+    return fr
+
+
+def _draw_yuv_target(what, planes, layout):
+    sel, bps, planar = yuv420_layout(layout)
+    if bps != 1:
+        raise ValueError(f'{what}: layout {layout!r} is not drawn into; the 8-bit layouts nv12, nv21, i420 and yv12 are')
+    if not isinstance(planes, (tuple, list)):
+        raise TypeError(f'{what}: a tuple of planes expected, got {type(planes).__name__}')
+    planes, single = yuv420_check_planes(planes, layout, what)
+    for t in planes:
+        inner = t.dim() == 4
+        if t.stride(-1) != 1 or (inner and t.stride(2) != 2) or t.stride(1) < t.shape[2] * (2 if inner else 1) or t.stride(0) < 0:
+            raise ValueError(f'{what}: planes are drawn in place and need packed samples (strides {tuple(t.stride())} of {tuple(t.shape)})')
+    if layout == 'yv12':
+        planes[1], planes[2] = planes[2], planes[1]
+    return planes
+
+
+def _draw_on_device(what, target_planes, tensors):
+    dev = target_planes[0].device
+    for t in list(target_planes) + [t for t in tensors if t is not None]:
+        require_gpu(t, what)
+        if t.device != dev:
+            raise ValueError(f'{what}: the target is on {dev}, another tensor on {t.device}')
+    return dev
+
+
+def _draw_launch(target, yuv, lst, style, dev):
+    """One launch: target = the [B,H,W,3] frames or the checked planes; yuv = None or (layout, matrix id, full_range)."""
+    s, keep = style.struct(dev)
+    t0 = TIMER.start() if TIMER else None
+    if yuv is None:
+        B, H, W, _ = target.shape
+        code = _lib.lib().mydet_draw_boxes_rgb_u8(_ptr(target), B, H, W, target.stride(0), target.stride(1), ctypes.byref(lst), ctypes.byref(s),
+                                                  _stream())
+        name = 'mydet_draw_boxes_rgb_u8'
+    else:
+        layout, m, full = yuv
+        B, H, W = target[0].shape
+        src = _yuv420_src(target, layout, m, full)
+        code = _lib.lib().mydet_draw_boxes_yuv420_u8(ctypes.byref(src), B, H, W, ctypes.byref(lst), ctypes.byref(s), _stream())
+        name = 'mydet_draw_boxes_yuv420_u8'
+    if t0:
+        TIMER.stop('draw_boxes', t0, float(B))
+    del keep
+    _lib.check(code, name)
+
+
+def _draw_dense(what, target, yuv, B, boxes, style, counts, scores, classes, ids):
+    _draw_check_style(style, what)
+    boxes, counts, planes = _draw_rows(what, B, boxes, counts, scores, classes, ids)
+    tp = [target] if yuv is None else list(target)
+    dev = _draw_on_device(what, tp, [boxes, counts] + list(planes.values()))
+    K = boxes.shape[1]
+    if K == 0:
+        return
+    boxes = boxes.contiguous()
+    sc, cl, idp = (None if t is None else t.contiguous() for t in (planes['scores'], planes['classes'], planes['ids']))
+    if counts is not None:
+        counts = counts.contiguous()
+    width = boxes.shape[2]
+    step = _lib.DRAW_MAX_BOXES
+    for lo in reversed(range(0, K, step)):                           # rows K-1 .. 0 are the paint order: the last chunk first
+        n = min(step, K - lo)
+        lst = _lib.DrawList()
+        lst.box, lst.box_frame_stride, lst.box_row_stride = boxes.data_ptr() + 4 * lo * width, K * width, width
+        if width == 5:
+            lst.angle, lst.angle_frame_stride, lst.angle_row_stride = boxes.data_ptr() + 4 * (lo * width + 4), K * width, width
+        for field, t, size in (('score', sc, 4), ('cls', cl, 8), ('id', idp, 8)):
+            if t is not None:
+                setattr(lst, field, t.data_ptr() + size * lo)
+                setattr(lst, field + '_frame_stride', K)
+                setattr(lst, field + '_row_stride', 1)
+        chunk_counts = None
+        if counts is not None:
+            chunk_counts = counts if K <= step else (counts - lo).clamp_(0, n).to(torch.int32)
+            lst.count, lst.count_stride = _ptr(chunk_counts), 1
+        lst.K = n
+        _draw_launch(target, yuv, lst, style, dev)
+        del chunk_counts
+
+
+def draw_boxes(frames, boxes, style, counts=None, scores=None, classes=None, ids=None):
+    """Paint boxes into uint8 RGB frames on the device, IN PLACE, one launch per 512 rows (include/mydet.h:
+    mydet_draw_boxes_rgb_u8, where the raster rules are).  frames: [B,H,W,3] or [H,W,3] with packed pixels, any row and frame
+    strides (a crop view is drawn in place).  boxes: float32 [B,K,4|5] or [K,4|5], rows (cx, cy, w, h[, degrees]).  counts:
+    int32 [B], rows to draw per frame (None: all K; above K means K).  scores float32, classes, ids int64 [B,K]: what labels and
+    colours read; None leaves that label part out (colour key 0).  Rows are painted K-1 down to 0, so row 0 ends up on top; more
+    than 512 rows go in chunks that keep this order.  style: ops.draw_style(...).  Returns `frames`."""
+    fr = _draw_rgb_target('draw_boxes', frames)
+    _draw_dense('draw_boxes', fr, None, fr.shape[0], boxes, style, counts, scores, classes, ids)
+    return frames
+
+
+def draw_boxes_yuv420(planes, layout, boxes, style, counts=None, scores=None, classes=None, ids=None, matrix='bt601', full_range=False):
+    """draw_boxes into the planes of 4:2:0 frames, IN PLACE (include/mydet.h: mydet_draw_boxes_yuv420_u8): layout 'nv12', 'nv21'
+    with planes (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]), 'i420' with (y, u, v), 'yv12' with (y, v, u); uint8, packed samples,
+    any row and frame strides; odd H and W are legal.  'p010' / 'i010' are not drawn into (ValueError).  matrix, full_range:
+    how the colours become Y'CbCr (ops.rgb_to_yuv), the selectors of the input side.  Returns `planes`."""
+    m = yuv_matrix_id(matrix)
+    ts = _draw_yuv_target('draw_boxes_yuv420', planes, layout)
+    _draw_dense('draw_boxes_yuv420', ts, (layout, m, full_range), ts[0].shape[0], boxes, style, counts, scores, classes, ids)
+    return planes
+
+
+def draw_records(target, rec, style, layout=None, matrix='bt601', full_range=False, ids=None):
+    """Paint the detections of a record dict (ops.record_views; plain or rotated) into `target`, IN PLACE, in one launch that
+    reads the record's planes through their strides -- nothing is copied or synchronised.  target: uint8 RGB frames
+    [B,H,W,3] (layout None) or the planes of `layout` as in draw_boxes_yuv420.  The dict must hold views of its 'records'
+    buffer (a ValueError for copies, as in track_frames).  ids: optional int64 [B,512].  Returns `target`."""
+    what = 'draw_records'
+    _draw_check_style(style, what)
+    if not isinstance(rec, dict) or 'records' not in rec or 'bbox' not in rec:
+        raise TypeError(f'{what}: rec is the dict of ops.record_views, got {type(rec).__name__}')
+    records = rec['records']
+    if not isinstance(records, torch.Tensor) or records.dtype != torch.int32 or records.dim() != 2 or \
+            records.shape[1] not in (_lib.REC_WORDS, _lib.REC_ROT_WORDS) or records.stride(1) != 1 or records.stride(0) < 0:
+        raise ValueError(f'{what}: int32 records [B, {_lib.REC_WORDS} | {_lib.REC_ROT_WORDS}] expected')
+    if rec['bbox'].data_ptr() != records.data_ptr() + 4 * _lib.REC_BBOX:
+        raise ValueError(f"{what}: the fields of this record dict are copies, not views of its 'records' buffer")
+    B = records.shape[0]
+    if layout is None:
+        tgt, yuv = _draw_rgb_target(what, target), None
+        tp = [tgt]
+    else:
+        m = yuv_matrix_id(matrix)
+        tgt = _draw_yuv_target(what, target, layout)
+        yuv, tp = (layout, m, full_range), tgt
+    if tp[0].shape[0] != B:
+        raise ValueError(f'{what}: {tp[0].shape[0]} frames and {B} records')
+    if ids is not None and (not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or tuple(ids.shape) != (B, _lib.REC_TOPK)):
+        raise ValueError(f'{what}: ids is an int64 tensor [{B},{_lib.REC_TOPK}]')
+    dev = _draw_on_device(what, tp, [records, ids])
+    base, fs = records.data_ptr(), records.stride(0)
+    lst = _lib.DrawList()
+    lst.box, lst.box_frame_stride, lst.box_row_stride = base + 4 * _lib.REC_BBOX, fs, 4
+    if records.shape[1] == _lib.REC_ROT_WORDS:
+        lst.angle, lst.angle_frame_stride, lst.angle_row_stride = base + 4 * _lib.REC_ANGLE, fs, 1
+    lst.score, lst.score_frame_stride, lst.score_row_stride = base + 4 * _lib.REC_SCORE, fs, 1
+    lst.cls, lst.cls_frame_stride, lst.cls_row_stride = base + 4 * _lib.REC_CLASS, fs // 2, 1      # int64 elements: fs is even
+    if fs % 2:
+        raise ValueError(f'{what}: a record stride of an even number of words expected, got {fs}')
+    if ids is not None:
+        ids = ids.contiguous()
+        lst.id, lst.id_frame_stride, lst.id_row_stride = _ptr(ids), _lib.REC_TOPK, 1
+    lst.count, lst.count_stride = base + 4 * _lib.REC_COUNT, fs
+    lst.K = _lib.REC_TOPK
+    _draw_launch(tgt, yuv, lst, style, dev)
+    return target

@@ -165,6 +165,12 @@ class ImageObjects():
                 self.bboxes[:, :4] = xywh
         self.img_hw = (ori_h, ori_w)
 
+    def draw_on_np(self, np_img, class_map='COCO', **kwargs):
+        """Draw the boxes on a numpy uint8 image [h,w,3] in place (reference: utils/structures.py:215-219); see
+        utils.visualization.draw_bboxes_on_np for the keywords."""
+        from .visualization import draw_bboxes_on_np
+        return draw_bboxes_on_np(np_img, self, class_map=class_map, **kwargs)
+
     def sanity_check(self):
         '''Integrity check (reference: utils/structures.py:191-213).'''
         assert self.bboxes.dtype == torch.float and self.bboxes.dim() == 2
