@@ -1,4 +1,4 @@
-"""float64 restatements shared by the footprint tests (plain torch, CPU)."""
+"""float64 restatements shared by the footprint and branch-coverage tests (plain torch, CPU)."""
 import torch
 import torch.nn.functional as F
 
@@ -35,6 +35,26 @@ def sepconv_node_f64(inputs, modes, fuse_w, w_dw, w_pw, scale, shift, act):
     y = F.conv2d(y, w_pw.double().reshape(w_pw.shape[0], C, 1, 1))
     y = y * (scale.double().view(1, -1, 1, 1) if scale is not None else 1.0) + shift.double().view(1, -1, 1, 1)
     return act_f64(y, act)
+
+
+def retina_decode_f64(cls_logits, box_logits, anchors_wh, stride, img_hw):
+    """RetinaLayer (models/detlayers/retinanet.py) on float64 head logits [B, A*n_cls, H, W] / [B, A*4, H, W], candidates in
+    (a, y, x) order: centre = stride/2 + x*stride + t*aw, size = exp(t)*aw, all four clamped to [1, max(img_h, img_w)];
+    score = sigmoid(max logit), class = argmax.  Returns bbox [B,N,4], raw (bbox before the clamp), anchor ([B,N,4]: aw, ah, aw, ah),
+    score, class_idx [B,N] and gap [B,N], the distance between the two largest logits of a candidate."""
+    B, _, H, W = box_logits.shape
+    A = anchors_wh.shape[0]
+    cl = cls_logits.double().view(B, A, -1, H, W)
+    top = cl.topk(2, dim=2)
+    t = box_logits.double().view(B, A, 4, H, W)
+    aw, ah = (anchors_wh.double()[:, i].view(1, A, 1, 1) for i in (0, 1))
+    acx = (stride / 2 + torch.arange(W, dtype=torch.float64) * stride).view(1, 1, 1, W)
+    acy = (stride / 2 + torch.arange(H, dtype=torch.float64) * stride).view(1, 1, H, 1)
+    raw = torch.stack([acx + t[:, :, 0] * aw, acy + t[:, :, 1] * ah, torch.exp(t[:, :, 2]) * aw, torch.exp(t[:, :, 3]) * ah], dim=-1)
+    anchor = torch.stack([aw, ah, aw, ah], dim=-1).expand(B, A, H, W, 4)
+    return dict(bbox=raw.clamp(1.0, float(max(img_hw))).reshape(B, -1, 4), raw=raw.reshape(B, -1, 4), anchor=anchor.reshape(B, -1, 4),
+                score=torch.sigmoid(top.values[:, :, 0]).reshape(B, -1), class_idx=top.indices[:, :, 0].reshape(B, -1),
+                gap=(top.values[:, :, 0] - top.values[:, :, 1]).reshape(B, -1))
 
 
 def lr_tb_layer_f64(x, lr0, tb0, lr1, blr, tb1, btb):

@@ -470,7 +470,8 @@ def test_footprint_bifpn_fuse_inputs(dev):
 # ---------------------------------------------------------------------------------------------------- depthwise
 @pytest.mark.parametrize('k,s,pad,C,H,W,act', [(3, 1, (1, 1, 1, 1), 32, 20, 24, 2), (3, 2, (0, 0, 1, 1), 96, 16, 16, 2),
                                               (5, 1, (2, 2, 2, 2), 144, 12, 10, 2), (5, 2, (1, 1, 2, 2), 240, 10, 10, 2),
-                                              (3, 1, (1, 1, 1, 1), 88, 5, 5, 0), (3, 1, (1, 1, 1, 1), 16, 41, 70, 2)])
+                                              (3, 1, (1, 1, 1, 1), 88, 5, 5, 0), (3, 1, (1, 1, 1, 1), 16, 41, 70, 2),
+                                              (3, 1, (1, 1, 1, 1), 8, 12, 16, 2)])      # under 16 channels: the two-row register-blocked form
 @pytest.mark.parametrize('squeeze', [False, True])
 def test_footprint_dwconv(dev, k, s, pad, C, H, W, act, squeeze):
     """mydet_dwconv_f32 through ctypes (ops.dwconv allocates y): y an arena, and with squeeze the partial-sum buffer [B,S+1,C] too

@@ -735,7 +735,9 @@ def test_nms_standalone_and_to_original(dev, golden):
 @pytest.mark.parametrize('k,s,pad,C,H,W,act', [(3, 1, (1, 1, 1, 1), 32, 20, 24, 2), (3, 2, (0, 0, 1, 1), 96, 16, 16, 2),
                                               (5, 1, (2, 2, 2, 2), 144, 12, 10, 2), (5, 2, (1, 1, 2, 2), 240, 10, 10, 2),
                                               (3, 1, (1, 1, 1, 1), 88, 5, 5, 0), (3, 1, (1, 1, 1, 1), 16, 41, 70, 2),
-                                              (5, 1, (2, 2, 2, 2), 24, 19, 33, 2), (3, 1, (1, 1, 1, 1), 672, 40, 40, 2)])
+                                              (5, 1, (2, 2, 2, 2), 24, 19, 33, 2), (3, 1, (1, 1, 1, 1), 672, 40, 40, 2),
+                                              # stride 2 with an odd Wo (single outputs) and with Wo % 4 == 0 (four-wide strips)
+                                              (3, 2, (0, 0, 1, 1), 24, 14, 18, 2), (5, 2, (1, 1, 2, 2), 40, 16, 16, 2)])
 def test_dwconv(dev, k, s, pad, C, H, W, act):
     from mydetection_amd import ops
     g = torch.Generator().manual_seed(3)
@@ -937,7 +939,10 @@ def test_se_gate_inside_depthwise_launch(dev, kind, C, Cse, k, s, H, W):
     # K not a multiple of 16 (masked last chunk) and output channels cut into slabs
     (40, 240, 81, 83, False, False, 2), (112, 672, 41, 39, False, False, 2), (80, 480, 40, 40, False, True, 2),
     (192, 1152, 20, 20, False, False, 2), (88, 88, 37, 41, False, False, 0), (24, 144, 90, 77, False, False, 1),
-    (40, 40, 181, 183, True, True, 0), (4, 12, 64, 64, False, False, 0), (236, 100, 33, 31, False, True, 0)])
+    (40, 40, 181, 183, True, True, 0), (4, 12, 64, 64, False, False, 0), (236, 100, 33, 31, False, True, 0),
+    # KC = ceil(Cin / 16) = 4, 8, 10, with and without the gate (575 pixels per image: above the gate's 512, blocks straddle the images)
+    (64, 24, 23, 25, True, True, 0), (60, 40, 23, 25, False, False, 2), (128, 32, 23, 25, True, False, 0),
+    (124, 200, 17, 19, False, True, 1), (160, 40, 23, 25, True, True, 0), (148, 48, 23, 25, False, False, 0)])
 def test_pointwise_skinny(dev, monkeypatch, Cin, Cout, H, W, gated, res, act):
     """The LDS-free skinny 1x1 kernel (csrc/pointwise.hip; mydet_conv2d_igemm_f32 routes Cout <= 48, Cin in
     {16, 32, 96, 144, 240}, >= 65 536 pixels to it): against a float64 conv, with the SE gate on x, BatchNorm terms,
@@ -966,7 +971,9 @@ def test_pointwise_skinny(dev, monkeypatch, Cin, Cout, H, W, gated, res, act):
     monkeypatch.setenv('MYDET_PW_WIDE', '1')              # every shape of this test through pointwise.hip
     y = ops.conv2d(*args, **kw)
     tol = 2e-5 * max(1.0, ref.abs().max().item())
-    assert (y.cpu().double() - ref).abs().max() < tol
+    err = (y.cpu().double() - ref).abs().max().item()
+    print(f'pointwise_skinny {Cin}->{Cout} {H}x{W} KC {(Cin + 15) // 16}: err {err:.3e} = {err / tol:.3f} of the bound {tol:.3e}')
+    assert err < tol
     y_pad = ops.conv2d(*args, out_ld=Cout + 8, **kw)                  # a leading dimension wider than Cout
     assert torch.equal(y_pad.contiguous(), y.contiguous())
     monkeypatch.setenv('MYDET_PW_SKINNY', '0')
