@@ -91,6 +91,19 @@ int mydet_wino_weights_f32(const float *w_ohwi, int Cout, int Cin, float *u, voi
 int mydet_conv2d_wino_f32(const float *x, int64_t ldx, const float *u, const float *scale, const float *shift,
                           const float *residual, int64_t ldr, void *workspace, int64_t workspace_bytes, float *y,
                           int64_t ldy, int B, int H, int W, int Cin, int Cout, int act, void *stream);
+/* Test hook (host only, no GPU call): the plan mydet_conv2d_wino_f32 uses for a layer on a chip of `cus` CUs with a workspace
+ * of `workspace_bytes` (<= 0 = none: never stream-K).  It is the launcher's own arithmetic, not a copy: the launch takes its numbers
+ * from the same function, with the device's CU count for `cus`, and both honour the once-per-process tuning values MYDET_WINO_NW /
+ * MYDET_WINO_SK.  out[10] = {
+ *   [0] NW: waves per workgroup, 4 (32 tiles of 2x2 outputs per item) or 8 (64 tiles); 8 from Cin = 128 up,
+ *   [1] schedule: 0 plain (one workgroup per item, all of K), 1 stream-K (persistent workgroups),
+ *   [2] items = tile blocks x 64-channel blocks,   [3] nk = Cin / 8 slab iterations per item,
+ *   [4] nwg: persistent workgroups (0 when plain),  [5] whole items per workgroup before the tail (1 when plain),
+ *   [6] tail items, cut along K: workgroup w owns the slab iterations [floor(w * T / nwg), floor((w + 1) * T / nwg)) of their
+ *       item-major sequence, T = tail items * nk,   [7] skq, [8] skr: T = skq * nwg + skr,
+ *   [9] 1 when the fixup launch (tail items x 8 workgroups) follows }.
+ * Returns 0, MYDET_E_BADARG, or MYDET_E_UNSUPP for the shapes mydet_conv2d_wino_f32 does not take.  No reference counterpart. */
+int mydet_wino_plan(int B, int H, int W, int Cin, int Cout, int64_t workspace_bytes, int cus, int32_t *out);
 
 /* First-layer convolution (Cin == 3, 3x3) reading the image with arbitrary strides
  * (NCHW as handed over by api/detection.py:160-166, or channels-last) and writing NHWC.

@@ -21,6 +21,7 @@ SIGNATURES = {
     'mydet_wino_weights_f32': [c_ptr, c_int, c_int, c_ptr, c_ptr],
     'mydet_conv2d_wino_f32': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64] + [c_int] * 6
     + [c_ptr],
+    'mydet_wino_plan': [c_int] * 5 + [c_i64, c_int, c_ptr],
     'mydet_wino4_weights_floats': [c_int, c_int],
     'mydet_wino4_weights_f32': [c_ptr, c_int, c_int, c_ptr, c_ptr],
     'mydet_wino4_workspace_bytes': [c_int, c_int, c_int, c_int, c_int],

@@ -452,45 +452,6 @@ int forced_sk() {
     return v;
 }
 
-template <int ACT, bool RES, int NW>
-int launch_nw(WinoArgs a, hipStream_t stream) {
-    constexpr int TILES = 8 * NW, NT = 64 * NW;
-    constexpr int LDS = (U_BYTES + 8 * 4 * TILES * 16) * (NW == 8 ? 2 : 1);
-    static unsigned long long attr_set = 0, attr_set_sk = 0;  // > 64 KiB of dynamic LDS needs the opt-in once per device
-    if (const int e = mydet_lds_opt_in(attr_set, &conv_wino_kernel<ACT, RES, NW, false>, LDS)) return e;
-    if (const int e = mydet_lds_opt_in(attr_set_sk, &conv_wino_kernel<ACT, RES, NW, true>, LDS)) return e;
-    a.nblk = (int)(((int64_t)a.MT + TILES - 1) / TILES) * a.ntn;
-    a.nk = a.Cin >> 3;
-    // stream-K when the grid is at least two resident rounds (below that the plain grid is already one round or
-    // its prologue/epilogue overlap is what matters) and the caller gave room for the partial tiles
-    const int resident = mydet_cu_count() * (NW == 8 ? 1 : 2);
-    const size_t need = (size_t)2 * resident * 8 * NT * sizeof(f32x4);
-    // (measured: pays on the 64-tile shape, whose single workgroup per CU exposes the partial last round; not on the
-    // 32-tile shape, MYDET_WINO_SK=1 forces it there)
-    // ... or a grid that fills less than half of the chip (batch-1 / small-map layers): then ALL items are cut along K.
-    // Every persistent workgroup must own at least one slab iteration of the cut part (the fixup sums the pieces of
-    // ALL workgroups between two item boundaries), so the grid shrinks to the iteration count when that is smaller.
-    const bool big = a.nblk >= 2 * resident, small = a.nblk * 2 <= resident && a.nk >= 8;
-    int nwg = resident;
-    if (small && (int64_t)a.nblk * a.nk < resident) nwg = a.nblk * a.nk;
-    const int64_t tail_total = (int64_t)(a.nblk - (a.nblk / nwg) * nwg) * a.nk;
-    const bool covered = tail_total == 0 || tail_total >= nwg;
-    if (forced_sk() != 0 && (NW == 8 || forced_sk() == 1) && a.ws && need <= a.ws_bytes && (big || small) && covered) {
-        a.nwg = nwg;
-        a.skq = (int)(tail_total / nwg); a.skr = (int)(tail_total % nwg);
-        hipLaunchKernelGGL((conv_wino_kernel<ACT, RES, NW, true>), dim3(nwg), dim3(NT), LDS, stream, a);
-        int rc = mydet_launch_status();
-        if (rc || nwg < 2) return rc;
-        const int tail_items = a.nblk - (a.nblk / nwg) * nwg;
-        if (tail_items == 0) return rc;
-        hipLaunchKernelGGL((conv_wino_fixup_kernel<ACT, RES, NW>), dim3(tail_items, 8), dim3(NT), 0, stream, a);
-        return mydet_launch_status();
-    }
-    a.nwg = 0; a.skq = 0; a.skr = 0;
-    hipLaunchKernelGGL((conv_wino_kernel<ACT, RES, NW, false>), dim3(a.nblk), dim3(NT), LDS, stream, a);
-    return mydet_launch_status();
-}
-
 int forced_nw() {
     static int v = -2;
     if (v == -2) {
@@ -500,10 +461,70 @@ int forced_nw() {
     return v;
 }
 
+// The launch plan (host only): one function for the launch and for mydet_wino_plan.
+//   sk = false: one workgroup per item, all of K (conv_wino_kernel<.., SK = false>, grid nblk).
+//   sk = true : `nwg` persistent workgroups take `rounds` whole items each, then equal shares of the tail_items * nk slab
+//               iterations = skq * nwg + skr of the remaining items; `fixup`: conv_wino_fixup_kernel follows (tail_items x 8).
+struct WinoPlan { int nw; bool sk; int nblk, nk, nwg, rounds, tail_items, skq, skr; bool fixup; };
+
+// MT tiles, ntn channel blocks of 64; ws_bytes = 0: no workspace; `cus`: the chip's CU count
+WinoPlan wino_plan(int MT, int ntn, int Cin, size_t ws_bytes, int cus) {
+    WinoPlan pl;
+    const int fnw = forced_nw() > 0 ? forced_nw() : (Cin >= 128 ? 8 : 4);
+    const int NW = pl.nw = fnw == 8 ? 8 : 4;
+    const int TILES = 8 * NW, NT = 64 * NW;
+    pl.nblk = (int)(((int64_t)MT + TILES - 1) / TILES) * ntn;
+    pl.nk = Cin >> 3;
+    // stream-K when the grid is at least two resident rounds (below that the plain grid is already one round or
+    // its prologue/epilogue overlap is what matters) and the caller gave room for the partial tiles
+    const int resident = cus * (NW == 8 ? 1 : 2);
+    const size_t need = (size_t)2 * resident * 8 * NT * sizeof(f32x4);
+    // (measured: pays on the 64-tile shape, whose single workgroup per CU exposes the partial last round; not on the
+    // 32-tile shape, MYDET_WINO_SK=1 forces it there)
+    // ... or a grid that fills less than half of the chip (batch-1 / small-map layers): then ALL items are cut along K.
+    // Every persistent workgroup must own at least one slab iteration of the cut part (the fixup sums the pieces of
+    // ALL workgroups between two item boundaries), so the grid shrinks to the iteration count when that is smaller.
+    const bool big = pl.nblk >= 2 * resident, small = pl.nblk * 2 <= resident && pl.nk >= 8;
+    int nwg = resident;
+    if (small && (int64_t)pl.nblk * pl.nk < resident) nwg = pl.nblk * pl.nk;
+    const int tail_items = pl.nblk - (pl.nblk / nwg) * nwg;
+    const int64_t tail_total = (int64_t)tail_items * pl.nk;
+    const bool covered = tail_total == 0 || tail_total >= nwg;
+    pl.sk = forced_sk() != 0 && (NW == 8 || forced_sk() == 1) && ws_bytes > 0 && need <= ws_bytes && (big || small) && covered;
+    if (pl.sk) {
+        pl.nwg = nwg; pl.rounds = pl.nblk / nwg; pl.tail_items = tail_items;
+        pl.skq = (int)(tail_total / nwg); pl.skr = (int)(tail_total % nwg);
+        pl.fixup = nwg >= 2 && tail_items > 0;
+    } else {
+        pl.nwg = 0; pl.rounds = 1; pl.tail_items = 0; pl.skq = 0; pl.skr = 0; pl.fixup = false;
+    }
+    return pl;
+}
+
+template <int ACT, bool RES, int NW>
+int launch_nw(WinoArgs a, const WinoPlan &pl, hipStream_t stream) {
+    constexpr int TILES = 8 * NW, NT = 64 * NW;
+    constexpr int LDS = (U_BYTES + 8 * 4 * TILES * 16) * (NW == 8 ? 2 : 1);
+    static unsigned long long attr_set = 0, attr_set_sk = 0;  // > 64 KiB of dynamic LDS needs the opt-in once per device
+    if (const int e = mydet_lds_opt_in(attr_set, &conv_wino_kernel<ACT, RES, NW, false>, LDS)) return e;
+    if (const int e = mydet_lds_opt_in(attr_set_sk, &conv_wino_kernel<ACT, RES, NW, true>, LDS)) return e;
+    a.nblk = pl.nblk; a.nk = pl.nk;
+    a.nwg = pl.nwg; a.skq = pl.skq; a.skr = pl.skr;
+    if (pl.sk) {
+        hipLaunchKernelGGL((conv_wino_kernel<ACT, RES, NW, true>), dim3(pl.nwg), dim3(NT), LDS, stream, a);
+        const int rc = mydet_launch_status();
+        if (rc || !pl.fixup) return rc;
+        hipLaunchKernelGGL((conv_wino_fixup_kernel<ACT, RES, NW>), dim3(pl.tail_items, 8), dim3(NT), 0, stream, a);
+        return mydet_launch_status();
+    }
+    hipLaunchKernelGGL((conv_wino_kernel<ACT, RES, NW, false>), dim3(a.nblk), dim3(NT), LDS, stream, a);
+    return mydet_launch_status();
+}
+
 template <int ACT, bool RES>
 int launch_inst(const WinoArgs &a, hipStream_t stream) {
-    const int nw = forced_nw() > 0 ? forced_nw() : (a.Cin >= 128 ? 8 : 4);
-    return nw == 8 ? launch_nw<ACT, RES, 8>(a, stream) : launch_nw<ACT, RES, 4>(a, stream);
+    const WinoPlan pl = wino_plan(a.MT, a.ntn, a.Cin, a.ws ? a.ws_bytes : 0, mydet_cu_count());
+    return pl.nw == 8 ? launch_nw<ACT, RES, 8>(a, pl, stream) : launch_nw<ACT, RES, 4>(a, pl, stream);
 }
 
 }  // namespace
@@ -558,4 +579,18 @@ extern "C" int mydet_conv2d_wino_f32(const float *x, int64_t ldx, const float *u
         case MYDET_ACT_SWISH: return res ? launch_inst<MYDET_ACT_SWISH, true>(a, s) : launch_inst<MYDET_ACT_SWISH, false>(a, s);
         default: return res ? launch_inst<MYDET_ACT_NONE, true>(a, s) : launch_inst<MYDET_ACT_NONE, false>(a, s);
     }
+}
+
+/* Test hook (host only, no GPU call): the plan mydet_conv2d_wino_f32 uses on a chip of `cus` CUs -- wino_plan, the function the launch
+ * takes its numbers from.  out[10] = {NW, schedule, items, nk, nwg, whole items per workgroup, tail items, skq, skr, fixup follows}
+ * (include/mydet.h). */
+extern "C" int mydet_wino_plan(int B, int H, int W, int Cin, int Cout, int64_t workspace_bytes, int cus, int32_t *out) {
+    if (!out || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || cus <= 0 || cus > (1 << 20)) return MYDET_E_BADARG;
+    if ((Cin & 7) || (Cout & 3)) return MYDET_E_UNSUPP;
+    const int64_t MT = (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2);
+    if (MT > (int64_t)1 << 30) return MYDET_E_UNSUPP;
+    const WinoPlan pl = wino_plan((int)MT, (Cout + 63) / 64, Cin, workspace_bytes > 0 ? (size_t)workspace_bytes : 0, cus);
+    out[0] = pl.nw; out[1] = pl.sk; out[2] = pl.nblk; out[3] = pl.nk; out[4] = pl.nwg; out[5] = pl.rounds;
+    out[6] = pl.tail_items; out[7] = pl.skq; out[8] = pl.skr; out[9] = pl.fixup;
+    return 0;
 }

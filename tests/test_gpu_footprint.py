@@ -272,18 +272,27 @@ def test_footprint_conv_p3(dev, case):
 
 
 # ---------------------------------------------------------------------------------------------------- Winograd F(2x2,3x3)
+# plan = (NW, stream-K schedule, items, whole items per workgroup, items cut along K) of the launch on the 256 CUs of the MI355X: what the
+# comments say, asserted through the launcher's own mydet_wino_plan; its fixup flag must be the case's `kcut`
 @pytest.mark.parametrize('case', [
-    dict(B=1, Cin=32, Cout=64, H=16, W=16, act=1, residual=True, kcut=False),                 # whole tiles
-    dict(B=3, Cin=64, Cout=128, H=13, W=11, act=1, kcut=False),                               # odd H and W
-    dict(B=1, Cin=88, Cout=88, H=10, W=10, act=0, bias_only=True, kcut=False),                # Cout % 64 != 0 (zero-padded U rows)
-    dict(B=2, Cin=88, Cout=84, H=5, W=5, act=2, kcut=False),                                  # ragged everything
-    dict(B=16, Cin=64, Cout=128, H=80, W=80, act=1, kcut=False),                  # big grid of the 32-tile shape: plain rounds
-    dict(B=32, Cin=128, Cout=256, H=40, W=40, act=1, residual=True, kcut=True),   # 64-tile shape, 3.125 items per workgroup: stream-K + conv_wino_fixup_kernel
-    dict(B=1, Cin=128, Cout=128, H=8, W=8, act=1, residual=True, kcut=True),      # small grid cut along K
-    dict(B=2, Cin=256, Cout=192, H=6, W=7, act=0, bias_only=True, kcut=True),     # small, ragged, cut along K
+    dict(B=1, Cin=32, Cout=64, H=16, W=16, act=1, residual=True, kcut=False, plan=(4, 0, 2, 1, 0)),      # whole tiles
+    dict(B=3, Cin=64, Cout=128, H=13, W=11, act=1, kcut=False, plan=(4, 0, 8, 1, 0)),                    # odd H and W
+    dict(B=1, Cin=88, Cout=88, H=10, W=10, act=0, bias_only=True, kcut=False, plan=(4, 0, 2, 1, 0)),     # Cout % 64 != 0 (zero-padded U rows)
+    dict(B=2, Cin=88, Cout=84, H=5, W=5, act=2, kcut=False, plan=(4, 0, 2, 1, 0)),                       # ragged everything
+    dict(B=16, Cin=64, Cout=128, H=80, W=80, act=1, kcut=False, plan=(4, 0, 1600, 1, 0)),     # big grid of the 32-tile shape: plain rounds
+    dict(B=32, Cin=128, Cout=256, H=40, W=40, act=1, residual=True, kcut=True,    # 64-tile shape, 3.125 items per workgroup: stream-K + conv_wino_fixup_kernel
+         plan=(8, 1, 800, 3, 32)),
+    dict(B=1, Cin=128, Cout=128, H=8, W=8, act=1, residual=True, kcut=True, plan=(8, 1, 2, 0, 2)),       # small grid cut along K
+    dict(B=2, Cin=256, Cout=192, H=6, W=7, act=0, bias_only=True, kcut=True, plan=(8, 1, 3, 0, 3)),      # small, ragged, cut along K
 ])
 def test_footprint_conv_winograd(dev, case):
-    _conv_footprint(dev, 'wino', dict(case, k=3, s=1))
+    from mydetection_amd import _lib, ops
+    case = dict(case, k=3, s=1)
+    out = (ctypes.c_int32 * 10)()
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    _lib.check(_lib.lib().mydet_wino_plan(case['B'], case['H'], case['W'], case['Cin'], case['Cout'], ops.WORKSPACE_BYTES, cus, out), 'mydet_wino_plan')
+    assert (out[0], out[1], out[2], out[5], out[6]) == case.pop('plan') and bool(out[9]) == case['kcut'], (case, list(out))
+    _conv_footprint(dev, 'wino', case)
 
 
 # ---------------------------------------------------------------------------------------------------- Winograd F(4x4,3x3)

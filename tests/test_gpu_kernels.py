@@ -320,24 +320,56 @@ def test_conv1x1_upcat_equals_two_launches(dev, shape):
     assert ops.conv1x1_upcat(lo, hi, w[:64].contiguous(), sc[:64].contiguous(), sh[:64].contiguous(), ops.ACT_LEAKY) is None
 
 
+def _wino_plan(dev, B, H, W, Cin, Cout):
+    """The F(2x2) launcher's own plan for a layer on this device (mydet_wino_plan; tests/test_host_cpu.py pins the rule)."""
+    import ctypes
+    from mydetection_amd import _lib, ops
+    out = (ctypes.c_int32 * 10)()
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    _lib.check(_lib.lib().mydet_wino_plan(B, H, W, Cin, Cout, ops.WORKSPACE_BYTES, cus, out), 'mydet_wino_plan')
+    return dict(zip(('nw', 'sk', 'items', 'nk', 'nwg', 'rounds', 'tail', 'skq', 'skr', 'fixup'), out))
+
+
+# `plan`: what each comment says of the launch, on the 256 CUs of the MI355X, asserted through mydet_wino_plan before the run (nw = waves
+# per workgroup: 4 = 32-tile items, 8 = 64-tile items; sk = stream-K schedule; nwg = persistent workgroups; rounds = whole items per
+# workgroup; tail = items cut along K; fixup = conv_wino_fixup_kernel follows).  tests/test_gpu_wino_branches.py runs the other branches.
 @pytest.mark.parametrize('case', [
-    dict(B=1, Cin=32, Cout=64, H=16, W=16, act=1, residual=True),      # DarkBlock 3x3 + residual, one workgroup row
-    dict(B=2, Cin=128, Cout=256, H=20, W=20, act=1, residual=True),    # 4 channel blocks, tiles straddle images
-    dict(B=4, Cin=512, Cout=1024, H=10, W=10, act=1),                  # deep K: 64 slabs
-    dict(B=3, Cin=64, Cout=128, H=13, W=11, act=1),                    # odd H and W: half-empty edge tiles
-    dict(B=1, Cin=88, Cout=88, H=10, W=10, act=0, bias_only=True),     # Cout % 64 != 0 (zero-padded U rows)
-    dict(B=2, Cin=88, Cout=84, H=5, W=5, act=2),                       # ragged everything, swish
-    dict(B=32, Cin=64, Cout=128, H=40, W=40, act=1, residual=True),    # big grid (XCD remap path)
-    dict(B=32, Cin=128, Cout=256, H=40, W=40, act=1, residual=True),   # stream-K, 64-tile shape: 3.125 items/workgroup
-    dict(B=16, Cin=64, Cout=128, H=80, W=80, act=1),                   # stream-K, 32-tile shape
-    dict(B=24, Cin=136, Cout=200, H=37, W=37, act=2, residual=True),   # stream-K with ragged tiles, channels and K=17 slabs
-    dict(B=1, Cin=128, Cout=128, H=8, W=8, act=1, residual=True),      # small grid cut along K: 2 items x 16 slabs on 32 workgroups
-    dict(B=1, Cin=512, Cout=1024, H=16, W=16, act=1, residual=True),   # batch-1 deep layer: 16 items x 64 slabs over the whole chip
-    dict(B=2, Cin=256, Cout=192, H=6, W=7, act=0, bias_only=True),     # small, ragged: 3 items x 32 slabs on 96 workgroups
+    dict(B=1, Cin=32, Cout=64, H=16, W=16, act=1, residual=True,       # DarkBlock 3x3 + residual, one workgroup row
+         plan=dict(nw=4, sk=0, items=2, nk=4)),
+    dict(B=2, Cin=128, Cout=256, H=20, W=20, act=1, residual=True,     # 4 channel blocks, tiles straddle images: 16 items, all cut along K
+         plan=dict(nw=8, sk=1, items=16, nk=16, nwg=256, rounds=0, tail=16, skq=1, skr=0, fixup=1)),
+    dict(B=4, Cin=512, Cout=1024, H=10, W=10, act=1,                   # deep K: 64 slabs (32 items, each cut 8 ways)
+         plan=dict(nw=8, sk=1, items=32, nk=64, nwg=256, rounds=0, tail=32, skq=8, skr=0, fixup=1)),
+    dict(B=3, Cin=64, Cout=128, H=13, W=11, act=1,                     # odd H and W: half-empty edge tiles
+         plan=dict(nw=4, sk=0, items=8, nk=8)),
+    dict(B=1, Cin=88, Cout=88, H=10, W=10, act=0, bias_only=True,      # Cout % 64 != 0 (zero-padded U rows)
+         plan=dict(nw=4, sk=0, items=2, nk=11)),
+    dict(B=2, Cin=88, Cout=84, H=5, W=5, act=2,                        # ragged everything, swish
+         plan=dict(nw=4, sk=0, items=2, nk=11)),
+    dict(B=32, Cin=64, Cout=128, H=40, W=40, act=1, residual=True,     # big grid (XCD remap path) of the 32-tile shape: plain
+         plan=dict(nw=4, sk=0, items=800, nk=8)),
+    dict(B=32, Cin=128, Cout=256, H=40, W=40, act=1, residual=True,    # stream-K, 64-tile shape: 3.125 items/workgroup
+         plan=dict(nw=8, sk=1, items=800, nk=16, nwg=256, rounds=3, tail=32, skq=2, skr=0, fixup=1)),
+    dict(B=16, Cin=64, Cout=128, H=80, W=80, act=1,                    # 6.25 rounds of the 32-tile shape: plain (stream-K is opt-in there)
+         plan=dict(nw=4, sk=0, items=1600, nk=8)),
+    dict(B=24, Cin=136, Cout=200, H=37, W=37, act=2, residual=True,    # stream-K with ragged tiles, channels and K=17 slabs
+         plan=dict(nw=8, sk=1, items=544, nk=17, nwg=256, rounds=2, tail=32, skq=2, skr=32, fixup=1)),
+    dict(B=1, Cin=128, Cout=128, H=8, W=8, act=1, residual=True,       # small grid cut along K: 2 items x 16 slabs on 32 workgroups
+         plan=dict(nw=8, sk=1, items=2, nk=16, nwg=32, rounds=0, tail=2, skq=1, skr=0, fixup=1)),
+    dict(B=1, Cin=512, Cout=1024, H=16, W=16, act=1, residual=True,    # batch-1 deep layer: 16 items x 64 slabs over the whole chip
+         plan=dict(nw=8, sk=1, items=16, nk=64, nwg=256, rounds=0, tail=16, skq=4, skr=0, fixup=1)),
+    dict(B=2, Cin=256, Cout=192, H=6, W=7, act=0, bias_only=True,      # small, ragged: 3 items x 32 slabs on 96 workgroups
+         plan=dict(nw=8, sk=1, items=3, nk=32, nwg=96, rounds=0, tail=3, skq=1, skr=0, fixup=1)),
 ])
 def test_conv_winograd_vs_fp64(dev, case):
     """Fused Winograd F(2x2,3x3) kernel (3x3, stride 1, pad 1) against the same float64 reference and tolerance
     as the direct implicit-GEMM kernel."""
+    case = dict(case)
+    want = case.pop('plan')
+    plan = _wino_plan(dev, case['B'], case['H'], case['W'], case['Cin'], case['Cout'])
+    if not want['sk']:
+        want = dict(want, nwg=0, rounds=1, tail=0, skq=0, skr=0, fixup=0)
+    assert plan == want, (case, plan)
     _conv_case(dev, k=3, s=1, wino=True, **case)
 
 

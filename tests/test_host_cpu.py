@@ -908,3 +908,193 @@ def test_conv_igemm_dispatch_rule():
         assert _igemm_plan(cfg, 2, 20, 20, 64, 128, 1, ws) == -1
     assert _igemm_plan(-1, 0, 20, 20, 64, 128, 1, ws) == -1 and _igemm_plan(-1, 2, 20, 20, 64, 128, 1, ws, cus=0) == -1
     assert _igemm_plan(-1, 2, 20, 20, 66, 128, 1, ws) == -1
+
+
+WINO_PLAN_KEYS = ('nw', 'sk', 'items', 'nk', 'nwg', 'rounds', 'tail', 'skq', 'skr', 'fixup')
+
+
+def _wino_plan(B, H, W, Cin, Cout, ws_bytes=64 << 20, cus=256):
+    """mydet_wino_plan as a dict, or the negative MYDET_E_* code."""
+    from mydetection_amd import _lib
+    out = (ctypes.c_int32 * 10)()
+    rc = _lib.lib().mydet_wino_plan(B, H, W, Cin, Cout, ws_bytes, cus, out)
+    if rc:
+        return rc
+    return dict(zip(WINO_PLAN_KEYS, out))
+
+
+def _wino_env_untuned():
+    """The F(2x2) launcher reads MYDET_WINO_NW / MYDET_WINO_SK once per process: the rule below is the untuned one."""
+    return not (os.environ.get('MYDET_WINO_NW') or os.environ.get('MYDET_WINO_SK'))
+
+
+def test_wino_plan_rule():
+    """The F(2x2) launch plan (mydet_wino_plan: host only, the function launch_inst / launch_nw of conv_wino.hip take their numbers from)
+    on a chip of 256 CUs with ops.WORKSPACE_BYTES of workspace.  Items = ceil(tiles / 64) * ceil(Cout / 64) for NW = 8 (32-tile items
+    for NW = 4); a B x 2 x 2 map is B tiles, so B = 64 * n with 64 output channels is n items."""
+    from mydetection_amd import ops
+    assert _wino_env_untuned(), 'MYDET_WINO_NW / MYDET_WINO_SK are set: this test pins the untuned rule'
+    ws = ops.WORKSPACE_BYTES
+    assert ws == 64 << 20
+    PLAIN = dict(sk=0, nwg=0, rounds=1, tail=0, skq=0, skr=0, fixup=0)
+
+    def items8(n, Cin=128, ws_bytes=ws, cus=256):          # n items of the 64-tile shape
+        p = _wino_plan(64 * n, 2, 2, Cin, 64, ws_bytes, cus)
+        assert p['nw'] == 8 and p['items'] == n and p['nk'] == Cin // 8, (n, p)
+        return p
+
+    # ---- Cin < 128: NW = 4 (32-tile items), always plain, whatever the item count
+    for Cin in (8, 64, 120):
+        for tiles in (1, 32, 33, 64 * 64, 64 * 256, 64 * 511, 64 * 512, 64 * 528, 64 * 800, 64 * 1600):
+            p = _wino_plan(tiles, 2, 2, Cin, 128, ws)
+            assert p == dict(PLAIN, nw=4, items=-(-tiles // 32) * 2, nk=Cin // 8), (Cin, tiles, p)
+    # ---- Cin >= 128: NW = 8
+    # small (at most half a round of items): ALL items cut along K, nwg = min(256, items * nk)
+    for n in (1, 2, 15, 16, 17, 127, 128):
+        p = items8(n)
+        nwg = min(256, 16 * n)
+        assert p == dict(nw=8, sk=1, items=n, nk=16, nwg=nwg, rounds=0, tail=n, skq=16 * n // nwg, skr=16 * n % nwg, fixup=1), (n, p)
+    assert items8(15)['nwg'] == 240 and items8(16)['nwg'] == 256            # shrunk to the iteration count below 256 only
+    assert items8(3, Cin=256)['nwg'] == 96 and items8(4, Cin=512)['nwg'] == 256 and items8(2, Cin=160)['nwg'] == 40
+    # 129 .. 511 items: plain
+    for n in (129, 200, 256, 257, 511):
+        assert items8(n) == dict(PLAIN, nw=8, items=n, nk=16), n
+    # 512 items: stream-K, whole rounds only, no fixup launch
+    assert items8(512) == dict(nw=8, sk=1, items=512, nk=16, nwg=256, rounds=2, tail=0, skq=0, skr=0, fixup=0)
+    assert items8(768)['rounds'] == 3 and items8(768)['fixup'] == 0
+    # 513 .. 527 items at nk = 16: the tail has fewer slab iterations than workgroups -- not covered, plain
+    for n in range(513, 528):
+        assert items8(n) == dict(PLAIN, nw=8, items=n, nk=16), n
+    # 528 items: the smallest covered tail, one slab per workgroup
+    assert items8(528) == dict(nw=8, sk=1, items=528, nk=16, nwg=256, rounds=2, tail=16, skq=1, skr=0, fixup=1)
+    assert items8(529) == dict(nw=8, sk=1, items=529, nk=16, nwg=256, rounds=2, tail=17, skq=1, skr=16, fixup=1)
+    # (a longer K covers sooner: 8 tail items of 32 slabs)
+    assert items8(519, Cin=256)['sk'] == 0 and items8(520, Cin=256) == dict(nw=8, sk=1, items=520, nk=32, nwg=256, rounds=2, tail=8, skq=1,
+                                                                             skr=0, fixup=1)
+    # the claim of test_conv_winograd_vs_fp64's comment: B = 1, 128 -> 128, 8 x 8 is 2 items x 16 slabs on 32 workgroups
+    assert _wino_plan(1, 8, 8, 128, 128, ws) == dict(nw=8, sk=1, items=2, nk=16, nwg=32, rounds=0, tail=2, skq=1, skr=0, fixup=1)
+    # the workspace: 2 slots x 256 workgroups x 8 float4 x 512 threads, whatever nwg is; none, or a byte short: plain
+    need = 2 * 256 * 8 * 512 * 16
+    for n in (2, 128, 512, 528, 800):
+        assert items8(n, ws_bytes=need)['sk'] == 1, n
+        for short in (0, -1, need - 1):
+            assert items8(n, ws_bytes=short) == dict(PLAIN, nw=8, items=n, nk=16), (n, short)
+    # another chip size moves every boundary
+    assert items8(152, cus=304)['sk'] == 1 and items8(153, cus=304)['sk'] == 0 and items8(607, cus=304)['sk'] == 0
+    assert items8(608, cus=304) == dict(nw=8, sk=1, items=608, nk=16, nwg=304, rounds=2, tail=0, skq=0, skr=0, fixup=0)
+    # arguments
+    from mydetection_amd import _lib
+    assert _wino_plan(0, 8, 8, 128, 128) == -1 and _wino_plan(1, 8, 8, 128, 128, cus=0) == -1
+    assert _lib.lib().mydet_wino_plan(1, 8, 8, 128, 128, ws, 256, None) == -1
+    assert _wino_plan(1, 8, 8, 132, 128) == -2 and _wino_plan(1, 8, 8, 128, 126) == -2
+
+
+def _sk_begin(w, p):
+    """sk_begin of conv_wino.hip: first slab iteration of persistent workgroup w."""
+    return w * p['skq'] + (w * p['skr']) // p['nwg']
+
+
+def _sk_pieces(p):
+    """The kernel's `setup`, restated: for every workgroup of a stream-K plan its pieces of the tail, (tail item, k_lo, k_hi, workspace
+    slot or None for a piece that covers its item's whole K and goes through the epilogue)."""
+    nk, pieces = p['nk'], []
+    for w in range(p['nwg']):
+        it, it_end = _sk_begin(w, p), _sk_begin(w + 1, p)
+        mine = []
+        while it < it_end:
+            ti = it // nk
+            k_lo = it - ti * nk
+            k_hi = nk if nk - k_lo < it_end - it else k_lo + (it_end - it)
+            it += k_hi - k_lo
+            whole = k_lo == 0 and k_hi == nk
+            mine.append((ti, k_lo, k_hi, None if whole else 2 * w + (1 if k_lo == 0 else 0)))
+        pieces.append(mine)
+    return pieces
+
+
+def _sk_fixup(p, ti):
+    """conv_wino_fixup_kernel's closed forms for tail item ti: None when it returns as 'not cut', else the slots it sums, in order."""
+    nk, nwg = p['nk'], p['nwg']
+    total = p['skq'] * nwg + p['skr']
+    first = ti * nk
+    w = ((first + 1) * nwg + total - 1) // total
+    if w >= nwg or _sk_begin(w, p) >= first + nk:
+        return None
+    last = min(nwg, ((first + nk) * nwg + total - 1) // total)
+    return [2 * (w - 1) + 1] + [2 * v for v in range(w, last)]
+
+
+def test_wino_stream_k_partition():
+    """The stream-K tail of the F(2x2) kernel, from the plan's skq / skr / nwg / nk alone: sk_begin, the kernel's `setup` and the fixup
+    kernel's closed forms (`w`, `last`) restated in Python and held to a brute-force walk, over seeded shapes on 256, 128 and 304 CUs.
+
+    Recorded from this walk (asserted below, so a change shows): the fixup kernel's "not cut" return IS reached -- when the tail is
+    nearly a whole round (skq = nk - 1, skr > 0) some shares are exactly nk slabs and a few of them start on an item boundary, e.g. 756
+    items of 16 slabs on 256 CUs (tail 244, skq = 15, skr = 64: tail items 60, 121, 182 and 243 are each one workgroup's whole share);
+    such an item goes through the main kernel's own epilogue and its fixup workgroups return, and the restated closed forms agree with the
+    walk on every one of them.  No plan has nwg < 2 with a tail (nwg = 1 needs a one-CU chip, whose every grid is whole rounds; a small
+    grid has at least 8 slabs), so the plan's `nwg >= 2` condition on the fixup launch (the launcher's `nwg < 2` return) never decides.  It is left in place.
+    Also recorded: with skr != 0 the shares do not divide the items and workgroups hold the end of one item (slot 2w) and the start
+    of the next (slot 2w + 1) at once -- e.g. B = 1, 128 -> 384, 32 x 30 on 256 CUs (24 items x 16 slabs, skq = 1, skr = 128), the
+    shape tests/test_gpu_wino_branches.py runs as case g."""
+    from mydetection_amd import ops
+    assert _wino_env_untuned(), 'MYDET_WINO_NW / MYDET_WINO_SK are set: this test walks the untuned rule'
+    ws = ops.WORKSPACE_BYTES
+    rng = __import__('random').Random(11)
+    shapes = [(32, 40, 40, 128, 256), (24, 37, 37, 136, 200), (1, 8, 8, 128, 128), (1, 16, 16, 512, 1024), (2, 6, 7, 256, 192),
+              (1, 32, 30, 128, 384), (1, 92, 90, 128, 1024), (2, 64, 64, 128, 1024), (1, 8, 8, 512, 256), (1, 15, 13, 160, 256)]
+    for _ in range(150):                                 # small grids: a few tiles, any K from 16 slabs
+        shapes.append((rng.randint(1, 3), rng.randint(3, 40), rng.randint(3, 40), 8 * rng.randint(16, 80), 4 * rng.randint(1, 160)))
+    for _ in range(250):                                 # big grids: at least two rounds of items
+        shapes.append((rng.randint(4, 40), rng.randint(30, 90), rng.randint(30, 90), 8 * rng.randint(16, 40), 4 * rng.randint(32, 260)))
+    seen = dict(big=0, small=0, straddle=0, uncut=0, no_fixup=0, long_sum=0)
+    for B, H, W, Cin, Cout in shapes:
+        for cus in (256, 128, 304):
+            p = _wino_plan(B, H, W, Cin, Cout, ws, cus)
+            assert p['nw'] == 8 and p['nk'] == Cin // 8 and p['items'] == -(-(B * ((H + 1) // 2) * ((W + 1) // 2)) // 64) * -(-Cout // 64)
+            if not p['sk']:
+                assert p['nwg'] == 0 and p['fixup'] == 0 and p['tail'] == 0
+                continue
+            nk, nwg, tail = p['nk'], p['nwg'], p['tail']
+            assert 1 <= nwg <= cus and p['rounds'] == p['items'] // nwg and tail == p['items'] - p['rounds'] * nwg
+            assert p['skq'] * nwg + p['skr'] == tail * nk and 0 <= p['skr'] < nwg
+            assert p['rounds'] >= 2 or p['rounds'] == 0          # big, or small with every item in the tail
+            seen['big' if p['rounds'] else 'small'] += 1
+            assert 2 * nwg * 8 * 64 * p['nw'] * 16 <= ws
+            assert p['fixup'] == (1 if tail else 0) and (tail == 0 or nwg >= 2)
+            if tail == 0:
+                seen['no_fixup'] += 1
+                continue
+            assert _sk_begin(0, p) == 0 and _sk_begin(nwg, p) == tail * nk
+            pieces = _sk_pieces(p)
+            owner = {}
+            by_item = [[] for _ in range(tail)]
+            for w, mine in enumerate(pieces):
+                assert mine, f'workgroup {w} has an empty share: {p}'
+                slots = [s for *_, s in mine if s is not None]
+                assert len(slots) == len(set(slots)) <= 2 and all(s // 2 == w for s in slots), (w, mine, p)
+                assert sum(1 for _, k_lo, _, s in mine if s is not None and k_lo > 0) <= 1
+                assert sum(1 for _, k_lo, _, s in mine if s is not None and k_lo == 0) <= 1
+                seen['straddle'] += len(slots) == 2
+                for ti, k_lo, k_hi, s in mine:
+                    assert 0 <= ti < tail and 0 <= k_lo < k_hi <= nk
+                    for k in range(k_lo, k_hi):
+                        assert (ti, k) not in owner, f'slab {k} of tail item {ti} belongs to workgroups {owner[(ti, k)]} and {w}: {p}'
+                        owner[(ti, k)] = w
+                    by_item[ti].append((k_lo, k_hi, s))
+            assert len(owner) == tail * nk                       # every (tail item, slab) exactly once
+            for ti, parts in enumerate(by_item):
+                parts.sort()
+                assert parts[0][0] == 0 and parts[-1][1] == nk and all(a[1] == b[0] for a, b in zip(parts, parts[1:]))
+                summed = _sk_fixup(p, ti)
+                if len(parts) == 1:                              # one workgroup took the whole item through its own epilogue
+                    assert parts[0][2] is None and summed is None, (ti, parts, summed, p)
+                    seen['uncut'] += 1
+                else:
+                    assert summed == [s for *_, s in parts], (ti, parts, summed, p)
+                    seen['long_sum'] += len(parts) > 17
+    assert seen['big'] >= 100 and seen['small'] >= 100, seen
+    assert seen['straddle'] >= 100 and seen['no_fixup'] >= 1 and seen['long_sum'] >= 100, seen
+    assert seen['uncut'] >= 20, seen                             # the fixup's 'not cut' return is live (docstring)
+    p = _wino_plan(7, 47, 47, 128, 768, ws, 256)
+    assert (p['items'], p['tail'], p['skq'], p['skr']) == (756, 244, 15, 64) and [t for t in range(244) if _sk_fixup(p, t) is None] == [60, 121, 182, 243]
