@@ -360,6 +360,9 @@ int mydet_decode_f32(int mode,
  *   topk highest (ties: lowest candidate index); per class ascending: greedy NMS on
  *   x1y1x2y2 = (cx-w/2, cy-h/2, cx+w/2, cy+h/2), suppress when (double)IoU > nms_thres;
  *   survivors ordered class ascending, score descending (ties: lowest index).
+ *   Order of the scores: that of float32 `<`, from -inf to +inf, subnormals included (nothing is flushed).  -0.0 and +0.0
+ *   are ONE score: they tie, and the lowest index wins, in the top-k and inside a class; out_score keeps each candidate's
+ *   own bits.  A NaN score fails the filter for every conf_thres (a NaN conf_thres included) and is never selected.
  * In : bbox [B,N,4], class_idx [B,N] i64, score [B,N].   N < 2^20, class ids in [0, 2^12): an image in which a
  *      candidate that passes the filter / top-k carries a class id outside that range gets
  *      count = MYDET_COUNT_BAD_CLASS (-1) and all-zero rows instead of silently aliased classes.

@@ -61,8 +61,11 @@ struct PPArgs {
     unsigned long long *scratch;
 };
 
+// Order-preserving map of the float32 scores that pass the filter (never a NaN) to unsigned.  -0.0f takes the key of +0.0f:
+// the two compare equal, so between them the candidate index decides, as it does for any other tie.
 __device__ __forceinline__ unsigned sortable(float f) {
-    const unsigned u = __float_as_uint(f);
+    unsigned u = __float_as_uint(f);
+    if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
