@@ -904,6 +904,72 @@ int mydet_draw_boxes_rgb_u8(unsigned char *dst, int B, int H, int W, int64_t dst
 int mydet_draw_boxes_yuv420_u8(const mydet_yuv420_src *planes, int B, int H, int W, const mydet_draw_list *list,
                                const mydet_draw_style *style, void *stream);
 
+/* Object chips: the image of every box of a list, cut out of uint8 RGB frames or of 4:2:0 planes, turned upright and resampled
+ * to one fixed size ch x cw, one launch per batch (csrc/crop.hip).  What attribute and re-identification classifiers, plate and
+ * face recognisers and thumbnails take.  No reference counterpart: the sampling rules are this library's own, and they are these.
+ *
+ * Boxes.  The list is the renderer's mydet_draw_list, read in place: a record buffer's planes or a dense [B,K,5] array; a row is
+ *   (cx, cy, w, h) in frame pixels and an angle in degrees (0 without an angle plane); score, cls and id are ignored.
+ * Slots.  Frame b has n_b = min(count_b, K, M) chips (a NULL count plane: min(K, M); a count <= 0, which includes
+ *   MYDET_COUNT_BAD_CLASS: 0).  The chip of row m < n_b is slot (b, m), at out + b*frame_stride + m*slot_stride (elements of the
+ *   output type): MYDET_CROP_U8 chips are uint8 [ch][cw][3], MYDET_CROP_F32 chips are float32 [3][ch][cw].  Slots m >= n_b are NOT
+ *   WRITTEN: their workgroups return before they touch memory.  A row m < n_b with a non-finite cx, cy, w, h or angle, or with
+ *   w <= 0 or h <= 0, gets a chip of the `fill` colour, so the slot index always equals the row index.
+ * Rotation.  angle == 0 uses c = 1, s = 0 with no trigonometric call.  With r = fmodf(angle, 360): r = +90 or -270 gives
+ *   (c, s) = (0, 1), r = +-180 gives (-1, 0), r = +270 or -90 gives (0, -1), exactly; any other angle gives c, s = cosf, sinf of
+ *   r * (pi / 180) in float32, as in the overlay renderer (which has no exact quarter turns).
+ * Coordinates, all float32 and uncontracted, in the order written.  sx = (w * pad) / cw, sy = (h * pad) / ch (pad > 1 adds
+ *   context around the box).  nx = clamp((int)ceilf(sx), 1, 4), ny likewise from sy: nx * ny sub-samples per chip pixel, so a
+ *   downscale up to 4x does not alias; a larger one does (4 x 4 samples spread evenly over the pixel's footprint).  For chip pixel
+ *   (row i, column j) and sub-sample (p, q), 0 <= p < ny, 0 <= q < nx:
+ *       lx = ((float)j + ((float)q + 0.5f) / nx - 0.5f * cw) * sx
+ *       ly = ((float)i + ((float)p + 0.5f) / ny - 0.5f * ch) * sy
+ *       X  = cx + lx*c - ly*s
+ *       Y  = cy + lx*s + ly*c
+ *   the inverse of the renderer's a = dx*c + dy*s, b = -dx*s + dy*c: the chip's x axis runs along the box's w, so a rotated
+ *   object comes out upright.  (X, Y) is a point of the frame in the renderer's convention: pixel (y, x) has its centre at
+ *   (x + 0.5, y + 0.5).
+ * Sample.  The point is quantised to 1/32 pixel: qx = (int)floorf((X - 0.5f) * 32 + 0.5f), x0 = qx >> 5 (arithmetic shift),
+ *   fx = qx & 31; qy, y0, fy likewise from Y.  Bilinear, per channel, in integers, from the pixels p00 = (y0, x0), p01 = (y0, x0 + 1),
+ *   p10 = (y0 + 1, x0), p11 = (y0 + 1, x0 + 1):
+ *       top = p00*(32 - fx) + p01*fx,  bot = p10*(32 - fx) + p11*fx,  v = (top*(32 - fy) + bot*fy + 512) >> 10
+ *   A tap outside the H x W view reads as the `fill` colour; nothing outside the view is addressed.  A point whose floorf value
+ *   is NaN or beyond +-2^29 in either axis (no view reaches there: H, W <= 2^24, MYDET_E_UNSUPP beyond) has four fill taps.
+ * Chip value, per channel: (sum of v over the nx*ny sub-samples + (n >> 1)) / n with n = nx*ny, an integer in 0..255.
+ *   MYDET_CROP_F32 writes that value through the arithmetic of mydet_preprocess_u8_f32: x / 255, then with norm != 0
+ *   (x - mean) / std per channel; mean3 / std3 are HOST pointers to 3 floats (read only when norm != 0).
+ * 4:2:0 sources (mydet_crop_boxes_yuv420; all five layouts, the 10-bit ones included, YV12 as I420 with the planes exchanged):
+ *   every tap is converted by the formula, the table and the 10-bit rule of mydet_yuv420_to_rgb_u8, chroma nearest at
+ *   (y >> 1, x >> 1), so the chips are, bit for bit, the chips of the RGB frames that function gives -- which are never built.
+ *   `fill` is an RGB colour here too.
+ * Stores.  16 bytes per lane into each float plane, dwords of packed pixels for uint8, when cw % 4 == 0, the output address is
+ *   a multiple of 16 (float) or 4 (uint8) and both strides are multiples of 4 elements; element by element otherwise, with the
+ *   same result.
+ * MYDET_E_BADARG, with nothing launched: a null list, out, box plane, source or output pointer; non-positive B, H, W; a source
+ *   pitch below the row's bytes; a negative stride; slot_stride < 3*ch*cw; K outside 1..MYDET_DRAW_MAX_BOXES; M outside
+ *   1..MYDET_CROP_MAX_SLOTS; ch or cw outside 1..MYDET_CROP_MAX_SIDE; pad not finite or <= 0; an unknown kind; norm != 0 with a
+ *   null mean3 or std3; and what mydet_yuv420_src refuses on the input side (layout, matrix, range, planes, pitches, odd 16-bit
+ *   addresses). */
+#define MYDET_CROP_MAX_SIDE  256
+#define MYDET_CROP_MAX_SLOTS 512
+#define MYDET_CROP_U8        0
+#define MYDET_CROP_F32       1
+typedef struct mydet_crop_out {
+    int ch, cw;                      /* chip rows, columns */
+    int M;                           /* chip slots per frame */
+    int kind;                        /* MYDET_CROP_U8 | MYDET_CROP_F32 */
+    float pad;                       /* the box is scaled by this before it is cut out */
+    unsigned char fill[4];           /* R, G, B of taps outside the view and of skipped rows; [3] ignored */
+    int norm, reserved;
+    const float *mean3, *std3;       /* HOST pointers, as in mydet_preprocess_u8_f32 */
+    void *out;                       /* DEVICE: uint8 or float32 by `kind` */
+    int64_t slot_stride, frame_stride;   /* elements between the chips of a frame / between frames */
+} mydet_crop_out;
+int mydet_crop_boxes_rgb(const unsigned char *src, int B, int H, int W, int64_t src_img_bytes, int64_t src_row_bytes,
+                         const mydet_draw_list *list, const mydet_crop_out *out, void *stream);
+int mydet_crop_boxes_yuv420(const mydet_yuv420_src *src, int B, int H, int W,
+                            const mydet_draw_list *list, const mydet_crop_out *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

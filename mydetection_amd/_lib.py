@@ -99,6 +99,8 @@ SIGNATURES = {
                                   c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_draw_boxes_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr],
     'mydet_draw_boxes_yuv420_u8': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
+    'mydet_crop_boxes_rgb': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr],
+    'mydet_crop_boxes_yuv420': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_cxcywh_to_x1y1x2y2_f32': [c_ptr, c_ptr, c_i64, c_int, c_ptr],
     'mydet_bboxes_to_original_f32': [c_ptr, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr],
 }
@@ -129,6 +131,9 @@ TRACK_MATCH_IOU, TRACK_MATCH_ROTATED = 0, 1
 DRAW_MAX_BOXES, DRAW_MAX_THICKNESS, DRAW_MAX_GLYPHS, DRAW_NAME_BYTES = 512, 64, 33, 16
 DRAW_COLOR_CLASS, DRAW_COLOR_ID, DRAW_COLOR_FIXED = 0, 1, 2
 DRAW_LABEL_CLASS, DRAW_LABEL_SCORE, DRAW_LABEL_ID = 1, 2, 4
+# object chips (mydet_crop_boxes_*): MYDET_CROP_* of include/mydet.h
+CROP_MAX_SIDE, CROP_MAX_SLOTS = 256, 512
+CROP_U8, CROP_F32 = 0, 1
 
 
 class DecodeLevel(ctypes.Structure):
@@ -201,6 +206,13 @@ class DrawStyle(ctypes.Structure):
     _fields_ = [('thickness', c_int), ('fill_alpha', c_int), ('color_mode', c_int), ('label_flags', c_int),
                 ('color', ctypes.c_ubyte * 4), ('n_palette', c_int), ('ch', c_int), ('cw', c_int), ('n_names', c_int),
                 ('palette', c_ptr), ('atlas', c_ptr), ('names', c_ptr)]
+
+
+class CropOut(ctypes.Structure):
+    """mydet_crop_out (include/mydet.h): mean3 / std3 are host pointers, out a device pointer, strides in elements."""
+    _fields_ = [('ch', c_int), ('cw', c_int), ('M', c_int), ('kind', c_int), ('pad', c_f32), ('fill', ctypes.c_ubyte * 4),
+                ('norm', c_int), ('reserved', c_int), ('mean3', c_ptr), ('std3', c_ptr), ('out', c_ptr),
+                ('slot_stride', c_i64), ('frame_stride', c_i64)]
 
 
 # MYDET_YUV420_* of include/mydet.h

@@ -78,6 +78,28 @@ class Draw:
         return self._styles[key]
 
 
+class Chips:
+    """The settings of Detector.crop_frames and its YUV forms: the image of every detected object, cut out of the frame, turned
+    upright and resampled to one size on the device (ops.crop_boxes; include/mydet.h has the sampling rules).  size: (height,
+    width) of a chip, each 1..256.  pad: the box is scaled by it before it is cut out (1.2 = 20 % context), finite and > 0.
+    max_per_frame: chip slots per frame, 1..512; a frame with more objects gets chips for its first max_per_frame rows.  out:
+    'input' = float32 [3,h,w] chips, / 255 and normalised by the model's own input_format (what a classifier on the same
+    preprocessing takes); 'uint8' = [h,w,3] pixels.  fill: the (r, g, b) of everything outside the frame."""
+
+    def __init__(self, size=(128, 64), pad=1.0, max_per_frame=64, out='input', fill=(0, 0, 0)):
+        if max_per_frame is None:
+            raise ValueError('Chips: max_per_frame is an int in 1..512, got None')
+        (self.size, self.max_per_frame, self.pad, self.fill, _, _) = ops.crop_settings('Chips', size, max_per_frame, pad, fill, out, None)
+        self.out = out
+
+    def __repr__(self):
+        return f'Chips(size={self.size}, pad={self.pad}, max_per_frame={self.max_per_frame}, out={self.out!r}, fill={self.fill})'
+
+    def kwargs(self, input_format):
+        """The keyword arguments of the ops.crop_* functions for a model of `input_format`."""
+        return dict(size=self.size, max_per_frame=self.max_per_frame, pad=self.pad, fill=self.fill, out=self.out, input_format=input_format)
+
+
 class Detector():
     '''Wrapper for image object detectors
 
@@ -762,6 +784,86 @@ class Detector():
     def annotate_frames_nv12(self, y, uv=None, draw=None, *, matrix='bt601', full_range=False, **kwargs):
         """annotate_frames_yuv for NV12: (y, uv) planes, or with uv=None the single surface [B,H*3/2,W] (see predict_frames_nv12)."""
         return self.annotate_frames_yuv(y if uv is None else (y, uv), 'nv12', draw, matrix=matrix, full_range=full_range, **kwargs)
+
+    @staticmethod
+    def _check_chips(chips, what):
+        if not isinstance(chips, Chips):
+            raise TypeError(f'{what}: chips is a mydetection_amd.api.Chips, got {type(chips).__name__}')
+
+    @staticmethod
+    def _chip_views(buf, objs):
+        """One view per frame of the chip buffer [B,M,...]: the chips of the frame's first min(len(objects), M) rows."""
+        return [buf[b, :min(len(o), buf.shape[1])] for b, o in enumerate(objs)]
+
+    def _crop_objects(self, source, layout, objs, chips, matrix='bt601', full_range=False):
+        """The chips of a list of ImageObjects (one per frame) out of the device frames or planes: the tracked form."""
+        from ..utils.visualization import objects_to_rows
+        dev = (source if layout is None else source[0]).device
+        boxes, counts = objects_to_rows(objs, dev)[:2]
+        kw = chips.kwargs(self.model.input_format)
+        if layout is None:
+            return ops.crop_boxes(source, boxes, counts=counts, **kw)
+        return ops.crop_boxes_yuv420(source, layout, boxes, counts=counts, matrix=matrix, full_range=full_range, **kw)
+
+    def crop_frames(self, frames, chips=None, **kwargs):
+        """predict_frames plus the object chips: returns (objects, chips).  objects is exactly what predict_frames(frames,
+        **kwargs) returns; chips is a list with one entry per frame, entry b a view [n_b,3,h,w] float32 (Chips(out='uint8'):
+        [n_b,h,w,3] uint8) of ONE device buffer written by ONE more launch (include/mydet.h: mydet_crop_boxes_rgb): chip k of
+        frame b shows row k of objects[b] -- its box scaled by `pad`, cut out of the frame, turned upright when the model
+        predicts rotated boxes, resampled to `size`.  A frame with more objects than chips.max_per_frame gets chips for its
+        first max_per_frame rows only (n_b = min(len(objects[b]), max_per_frame)).  Frames of one size (ValueError otherwise).
+        chips: a Chips (default Chips()).  tiles=, tracker= and coasting= as in predict_frames.  An untracked call launches
+        straight from the records buffer, before any host synchronisation; a tracked call crops the tracks' filtered boxes."""
+        chips = Chips() if chips is None else chips
+        self._check_chips(chips, 'crop_frames')
+        tracker, coasting = self._pop_tracker(kwargs)
+        n, groups = self._frame_groups(frames)
+        if len(groups) != 1:
+            raise ValueError(f'crop_frames: frames of one size expected, got {[tuple(parts[0].shape[1:3]) for _, parts in groups]}')
+        if tracker is not None:
+            tracker.check_call(n, tuple(int(v) for v in groups[0][1][0].shape[1:3]), self.model.bb_format)
+        dev = next(self.model.parameters()).device
+        parts = groups[0][1]
+        if len(parts) > 1:
+            where = dev if all(t.device == dev for t in parts) else torch.device('cpu')
+            parts = [torch.cat([t.to(where) for t in parts])]
+        fr = parts[0].to(dev, non_blocking=True)
+        if fr.stride(3) != 1 or fr.stride(2) != 3 or fr.stride(1) < 3 * fr.shape[2] or fr.stride(0) < 0:
+            fr = fr.contiguous()
+        if tracker is not None:
+            objs = self.predict_frames(fr, tracker=tracker, coasting=coasting, **kwargs)
+            return objs, self._chip_views(self._crop_objects(fr, None, objs, chips), objs)
+        records = list(self._frame_records(fr, _whole_records=True, **kwargs))
+        assert len(records) == 1 and records[0][0] == list(range(n))  # one frame size: one group, in frame order
+        buf = ops.crop_records(fr, records[0][1], **chips.kwargs(self.model.input_format))
+        objs = self._objects_of_records(records)
+        return objs, self._chip_views(buf, objs)
+
+    def crop_frames_yuv(self, planes, layout, chips=None, *, matrix='bt601', full_range=False, **kwargs):
+        """predict_frames_yuv plus the object chips, cut straight out of the planes (include/mydet.h: mydet_crop_boxes_yuv420):
+        returns (objects, chips) as crop_frames does, the chips being those of the converted RGB frames (ops.yuv420_to_rgb),
+        which are never built.  Every layout of predict_frames_yuv is accepted, the 10-bit ones included: crops only read."""
+        chips = Chips() if chips is None else chips
+        self._check_chips(chips, 'crop_frames_yuv')
+        ops.yuv420_layout(layout)
+        ops.yuv_matrix_id(matrix)
+        tracker, coasting = self._pop_tracker(kwargs)
+        y = self._yuv_planes(planes, layout)[0]                      # the checks alone: no device is touched
+        if tracker is not None:
+            tracker.check_call(y.shape[0], tuple(int(v) for v in y.shape[1:3]), self.model.bb_format)
+        ts = tuple(self._yuv_planes(planes, layout, device=next(self.model.parameters()).device))
+        if tracker is not None:
+            objs = self.predict_frames_yuv(ts, layout, matrix=matrix, full_range=full_range, tracker=tracker, coasting=coasting, **kwargs)
+            return objs, self._chip_views(self._crop_objects(ts, layout, objs, chips, matrix, full_range), objs)
+        records = list(self._yuv_records(ts, layout, matrix, full_range, _whole_records=True, **kwargs))
+        assert len(records) == 1 and records[0][0] == list(range(ts[0].shape[0]))
+        buf = ops.crop_records(ts, records[0][1], layout=layout, matrix=matrix, full_range=full_range, **chips.kwargs(self.model.input_format))
+        objs = self._objects_of_records(records)
+        return objs, self._chip_views(buf, objs)
+
+    def crop_frames_nv12(self, y, uv=None, chips=None, *, matrix='bt601', full_range=False, **kwargs):
+        """crop_frames_yuv for NV12: (y, uv) planes, or with uv=None the single surface [B,H*3/2,W] (see predict_frames_nv12)."""
+        return self.crop_frames_yuv(y if uv is None else (y, uv), 'nv12', chips, matrix=matrix, full_range=full_range, **kwargs)
 
     def predict_batch(self, pil_imgs, **kwargs):
         """Batched form of detect_one (the reference loops image by image, api/detection.py:67-74): images that share a

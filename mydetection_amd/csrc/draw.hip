@@ -11,6 +11,7 @@
 // hits are compacted in paint order into LDS (geometry, colours, label text: 84 bytes each, 21 KiB).  A tile without a hit in
 // any chunk reads and writes no pixel.  The others load their pixels once, walk the short list per pixel and store the pixel
 // groups that changed: with dword stores when address, pitch and frame stride allow (see the header), byte by byte otherwise.
+#include "box_rot.h"
 #include "pixel_math.h"
 
 namespace {
@@ -156,11 +157,7 @@ __device__ int draw_collect(const DrawArgs &p, int b, int hi, int tx0, int ty0, 
         const float ang = l.angle ? l.angle[(int64_t)b * l.angle_frame_stride + (int64_t)r * l.angle_row_stride] : 0.0f;
         const bool ok = isfinite(cx) && isfinite(cy) && isfinite(w) && isfinite(h) && isfinite(ang) && w > 0.0f && h > 0.0f;
         if (ok) {
-            if (ang != 0.0f) {
-                const float rad = fmodf(ang, 360.0f) * 0.017453292519943295f;
-                c = cosf(rad);
-                s = sinf(rad);
-            }
+            box_rotation<false>(ang, c, s);
             const float ow = w * 0.5f + ht, oh = h * 0.5f + ht;
             const float ex = fabsf(c) * ow + fabsf(s) * oh + 1.0f, ey = fabsf(s) * ow + fabsf(c) * oh + 1.0f;
             hit = !(cx - ex > (float)(tx0 + TW) || cx + ex < (float)tx0 || cy - ey > (float)(ty0 + TH) || cy + ey < (float)ty0);

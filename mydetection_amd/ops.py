@@ -2245,3 +2245,190 @@ def draw_records(target, rec, style, layout=None, matrix='bt601', full_range=Fal
     lst.K = _lib.REC_TOPK
     _draw_launch(tgt, yuv, lst, style, dev)
     return target
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Object chips (include/mydet.h: mydet_crop_boxes_rgb / mydet_crop_boxes_yuv420, where the sampling rules are).
+
+CROP_OUTPUTS = ('uint8', 'input')
+
+
+def crop_settings(what, size, max_per_frame, pad, fill, out, input_format):
+    """The checked settings of a crop call (no device touched): ((ch, cw), M or None, pad, (r, g, b), float output?, input format).
+    size = (height, width), each 1..256; max_per_frame None or 1..512; pad finite and > 0; fill three integers 0..255; out 'uint8'
+    or 'input' (float32 chips in the arithmetic of preprocess_u8 for input_format 'RGB_1' (None) or 'RGB_1_norm')."""
+    try:
+        ch, cw = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f'{what}: size = (height, width) expected, got {size!r}') from None
+    if not (1 <= ch <= _lib.CROP_MAX_SIDE and 1 <= cw <= _lib.CROP_MAX_SIDE):
+        raise ValueError(f'{what}: size = (height, width) with entries in 1..{_lib.CROP_MAX_SIDE} expected, got {size!r}')
+    if max_per_frame is not None:
+        if isinstance(max_per_frame, bool) or not isinstance(max_per_frame, int) or not 1 <= max_per_frame <= _lib.CROP_MAX_SLOTS:
+            raise ValueError(f'{what}: max_per_frame is None or an int in 1..{_lib.CROP_MAX_SLOTS}, got {max_per_frame!r}')
+    pad = float(pad)
+    if not (math.isfinite(pad) and pad > 0) or float(np.float32(pad)) <= 0 or not math.isfinite(float(np.float32(pad))):
+        raise ValueError(f'{what}: pad is a finite number > 0, got {pad!r}')
+    try:
+        fill = tuple(int(v) for v in fill)
+    except (TypeError, ValueError):
+        raise ValueError(f'{what}: fill = (r, g, b) expected, got {fill!r}') from None
+    if len(fill) != 3 or min(fill) < 0 or max(fill) > 255:
+        raise ValueError(f'{what}: fill = (r, g, b) with entries in 0..255 expected, got {fill!r}')
+    if not isinstance(out, str) or out not in CROP_OUTPUTS:
+        raise ValueError(f'{what}: out {out!r} is not one of {CROP_OUTPUTS}')
+    input_format = 'RGB_1' if input_format is None else input_format
+    if input_format not in ('RGB_1', 'RGB_1_norm'):
+        raise ValueError(f"{what}: input_format {input_format!r} is not 'RGB_1' or 'RGB_1_norm'")
+    return (ch, cw), max_per_frame, pad, fill, out == 'input', input_format
+
+
+def _crop_rgb_source(what, frames):
+    """uint8 frames [B,H,W,3] or [H,W,3] as the view the kernel reads: in place when pixels are packed, else one copy."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+        raise TypeError(f'{what}: uint8 frames expected, got {frames.dtype if isinstance(frames, torch.Tensor) else type(frames).__name__}')
+    fr = frames.unsqueeze(0) if frames.dim() == 3 else frames
+    if fr.dim() != 4 or fr.shape[3] != 3 or min(fr.shape) < 1:
+        raise ValueError(f'{what}: frames of shape [B,H,W,3] or [H,W,3] expected, got {tuple(frames.shape)}')
+    if fr.stride(3) != 1 or fr.stride(2) != 3 or fr.stride(1) < 3 * fr.shape[2] or fr.stride(0) < 0:
+        fr = fr.contiguous()
+    return fr
+
+
+def _crop_dst(what, dst, B, M, chip, f32, dev):
+    """The chip tensor: zeros when dst is None; else dst checked -- [B,M,ch,cw,3] uint8 or [B,M,3,ch,cw] float32 on `dev`, every
+    chip contiguous, any non-negative slot and frame strides."""
+    ch, cw = chip
+    shape = (B, M, 3, ch, cw) if f32 else (B, M, ch, cw, 3)
+    dtype = torch.float32 if f32 else torch.uint8
+    if dst is None:
+        return torch.zeros(shape, dtype=dtype, device=dev)
+    if not isinstance(dst, torch.Tensor) or dst.dtype != dtype:
+        raise TypeError(f'{what}: dst is a {dtype} tensor, got {dst.dtype if isinstance(dst, torch.Tensor) else type(dst).__name__}')
+    if tuple(dst.shape) != shape:
+        raise ValueError(f'{what}: dst of shape {shape} expected, got {tuple(dst.shape)}')
+    if dst.device != dev:
+        raise ValueError(f'{what}: the source is on {dev}, dst on {dst.device}')
+    if M and (not dst[0, 0].is_contiguous() or dst.stride(1) < 3 * ch * cw or dst.stride(0) < 0):
+        raise ValueError(f'{what}: dst needs contiguous chips (strides {tuple(dst.stride())} of {tuple(dst.shape)})')
+    return dst
+
+
+def _crop_launch(source, yuv, lst, settings, M, dst):
+    """One launch: source = the [B,H,W,3] frames or the checked planes; yuv = None or (layout, matrix id, full_range)."""
+    chip, _, pad, fill, f32, input_format = settings
+    o = _lib.CropOut()
+    o.ch, o.cw, o.M, o.kind, o.pad = chip[0], chip[1], M, _lib.CROP_F32 if f32 else _lib.CROP_U8, pad
+    o.fill[0], o.fill[1], o.fill[2] = fill
+    o.norm, o.mean3, o.std3 = _norm_args(input_format)
+    o.out, o.slot_stride, o.frame_stride = dst.data_ptr(), dst.stride(1), dst.stride(0)
+    t0 = TIMER.start() if TIMER else None
+    if yuv is None:
+        B, H, W, _ = source.shape
+        code = _lib.lib().mydet_crop_boxes_rgb(_ptr(source), B, H, W, source.stride(0), source.stride(1), ctypes.byref(lst), ctypes.byref(o),
+                                               _stream())
+        name = 'mydet_crop_boxes_rgb'
+    else:
+        layout, m, full = yuv
+        B, H, W = source[0].shape
+        src = _yuv420_src(source, layout, m, full)
+        code = _lib.lib().mydet_crop_boxes_yuv420(ctypes.byref(src), B, H, W, ctypes.byref(lst), ctypes.byref(o), _stream())
+        name = 'mydet_crop_boxes_yuv420'
+    if t0:
+        TIMER.stop('crop_boxes', t0, float(B))
+    _lib.check(code, name)
+
+
+def _crop_dense(what, source, yuv, B, boxes, settings, counts, dst):
+    boxes, counts, _ = _draw_rows(what, B, boxes, counts, None, None, None)
+    tp = [source] if yuv is None else list(source)
+    dev = _draw_on_device(what, tp, [boxes, counts])
+    K = min(boxes.shape[1], _lib.DRAW_MAX_BOXES)                     # rows past the launch's 512 get no chip
+    M = settings[1] if settings[1] is not None else K
+    dst = _crop_dst(what, dst, B, M, settings[0], settings[4], dev)
+    if K == 0 or M == 0:
+        return dst
+    boxes = boxes.contiguous()
+    width, rows = boxes.shape[2], boxes.shape[1]
+    lst = _lib.DrawList()
+    lst.box, lst.box_frame_stride, lst.box_row_stride = boxes.data_ptr(), rows * width, width
+    if width == 5:
+        lst.angle, lst.angle_frame_stride, lst.angle_row_stride = boxes.data_ptr() + 16, rows * width, width
+    if counts is not None:
+        counts = counts.contiguous()
+        lst.count, lst.count_stride = _ptr(counts), 1
+    lst.K = K
+    _crop_launch(source, yuv, lst, settings, M, dst)
+    return dst
+
+
+def crop_boxes(frames, boxes, size, counts=None, max_per_frame=None, pad=1.0, fill=(0, 0, 0), out='uint8', input_format=None, dst=None):
+    """The chips of boxes: every box cut out of uint8 RGB frames on the device, turned upright and resampled to size = (height,
+    width), in ONE launch (include/mydet.h: mydet_crop_boxes_rgb, where the sampling rules are).  frames: [B,H,W,3] or [H,W,3],
+    read in place through their strides when pixels are packed (a crop view is read in place).  boxes: float32 [B,K,4|5] or
+    [K,4|5], rows (cx, cy, w, h[, degrees]) in frame pixels; of more than 512 rows the first 512 are read.  counts: int32 [B],
+    the rows of each frame that are boxes (None: all K).  max_per_frame: the chip slots M per frame (None: K); a frame gets the
+    chips of its first min(count, K, M) rows.  pad: the box is scaled by it first (1.2 = 20 % context).  fill: the (r, g, b) of
+    everything outside the frame and of rows that are not boxes (non-finite, w <= 0 or h <= 0).  out: 'uint8' gives
+    [B,M,ch,cw,3] uint8; 'input' gives [B,M,3,ch,cw] float32, value / 255 and, with input_format 'RGB_1_norm', the ImageNet
+    normalisation -- the arithmetic of preprocess_u8.  dst: an optional tensor of that shape to write into (contiguous chips,
+    any slot and frame strides): only chips m < min(count, K, M) are written; without it the chips are new and the others zero."""
+    what = 'crop_boxes'
+    settings = crop_settings(what, size, max_per_frame, pad, fill, out, input_format)
+    fr = _crop_rgb_source(what, frames)
+    return _crop_dense(what, fr, None, fr.shape[0], boxes, settings, counts, dst)
+
+
+def crop_boxes_yuv420(planes, layout, boxes, size, counts=None, max_per_frame=None, pad=1.0, fill=(0, 0, 0), out='uint8', input_format=None,
+                      dst=None, matrix='bt601', full_range=False):
+    """crop_boxes out of 4:2:0 frames (include/mydet.h: mydet_crop_boxes_yuv420): the bits of crop_boxes on
+    yuv420_to_rgb(planes, layout, matrix, full_range), which is never built.  planes, layout, matrix, full_range as in
+    yuv420_to_rgb: every layout, the 10-bit ones included, odd H and W.  fill is an RGB colour."""
+    what = 'crop_boxes_yuv420'
+    yuv420_layout(layout)
+    m = yuv_matrix_id(matrix)
+    settings = crop_settings(what, size, max_per_frame, pad, fill, out, input_format)
+    ts, _ = _yuv420_planes(planes, layout, what)
+    return _crop_dense(what, ts, (layout, m, full_range), ts[0].shape[0], boxes, settings, counts, dst)
+
+
+def crop_records(source, rec, size, layout=None, max_per_frame=None, pad=1.0, fill=(0, 0, 0), out='uint8', input_format=None, dst=None,
+                 matrix='bt601', full_range=False):
+    """The chips of the detections of a record dict (ops.record_views; plain or rotated) in ONE launch that reads the record's
+    planes in place through their strides -- nothing is copied or synchronised.  source: uint8 RGB frames [B,H,W,3] (layout
+    None) or the planes of `layout` as in crop_boxes_yuv420.  The dict must hold views of its 'records' buffer (a ValueError
+    for copies, as in draw_records).  max_per_frame: chip slots per frame (None: 512); chip m of frame b shows the record's row
+    m.  Everything else as in crop_boxes."""
+    what = 'crop_records'
+    settings = crop_settings(what, size, max_per_frame, pad, fill, out, input_format)
+    if not isinstance(rec, dict) or 'records' not in rec or 'bbox' not in rec:
+        raise TypeError(f'{what}: rec is the dict of ops.record_views, got {type(rec).__name__}')
+    records = rec['records']
+    if not isinstance(records, torch.Tensor) or records.dtype != torch.int32 or records.dim() != 2 or \
+            records.shape[1] not in (_lib.REC_WORDS, _lib.REC_ROT_WORDS) or records.stride(1) != 1 or records.stride(0) < 0:
+        raise ValueError(f'{what}: int32 records [B, {_lib.REC_WORDS} | {_lib.REC_ROT_WORDS}] expected')
+    if rec['bbox'].data_ptr() != records.data_ptr() + 4 * _lib.REC_BBOX:
+        raise ValueError(f"{what}: the fields of this record dict are copies, not views of its 'records' buffer")
+    B = records.shape[0]
+    if layout is None:
+        src, yuv = _crop_rgb_source(what, source), None
+        tp = [src]
+    else:
+        yuv420_layout(layout)
+        m = yuv_matrix_id(matrix)
+        src, _ = _yuv420_planes(source, layout, what)
+        yuv, tp = (layout, m, full_range), src
+    if tp[0].shape[0] != B:
+        raise ValueError(f'{what}: {tp[0].shape[0]} frames and {B} records')
+    dev = _draw_on_device(what, tp, [records])
+    M = settings[1] if settings[1] is not None else _lib.REC_TOPK
+    dst = _crop_dst(what, dst, B, M, settings[0], settings[4], dev)
+    base, fs = records.data_ptr(), records.stride(0)
+    lst = _lib.DrawList()
+    lst.box, lst.box_frame_stride, lst.box_row_stride = base + 4 * _lib.REC_BBOX, fs, 4
+    if records.shape[1] == _lib.REC_ROT_WORDS:
+        lst.angle, lst.angle_frame_stride, lst.angle_row_stride = base + 4 * _lib.REC_ANGLE, fs, 1
+    lst.count, lst.count_stride = base + 4 * _lib.REC_COUNT, fs
+    lst.K = _lib.REC_TOPK
+    _crop_launch(src, yuv, lst, settings, M, dst)
+    return dst
