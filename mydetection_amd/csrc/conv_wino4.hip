@@ -25,7 +25,15 @@
 //     stage kt; ONE barrier per stage.  One ds_read_b128 per operand feeds four MFMAs.  The loop body is DMA issue,
 //     18 LDS reads and 36 MFMAs -- no VALU.
 //     Output channels are MFMA rows, so a lane ends up with 4 consecutive channels of a tile: after At M A, sixteen
-//     16-byte stores; the residual loads of a row are in flight before its first store.
+//     16-byte stores.
+//     Residual instances: the 16 residual quads of a lane never sit in registers together (144 accumulators + 64 did not
+//     fit: 36 spilled registers, and every wave waited for its residual IN FRONT of the last stage's MFMAs).  The last K
+//     stage is peeled: scale / shift, then the residual of output rows 0-1 (8 quads) are requested, the 36 MFMAs run with
+//     no wait, and nothing closes the stage (no DMA in flight, no LDS buffer reused).  Rows 2-3 are requested after the
+//     column pass of the output transform, into the registers of the 12 accumulators that die there, and land under the
+//     row pass, activation and eight stores of rows 0-1.  Every wait is hipcc's own, at the add that consumes the quad
+//     (rolling vmcnt(15)); 220-228 VGPRs, no scratch (tests/test_wino4_no_scratch.py; profiles/wino4_residual.md).
+//     The plain and PART instances are instruction for instruction what they were.
 // Replaces the same ATen chain as conv_wino.hip (models/modules.py:69-73,94-95).
 #include <cstdlib>
 #include <type_traits>
@@ -258,7 +266,16 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino4_kernel(const W4Args p) 
             ocol[i] = ox + i < p.W;
         }
     }
-    f32x4 rv[16];                                      // residual of the 4x4 outputs: loaded under the last stage's MFMAs
+    // residual of the 4x4 outputs, fetched in two halves of eight quads so that it fits beside the 144 accumulators:
+    // output rows 0-1 under the last stage's MFMAs, rows 2-3 after the column pass of the output transform (see there)
+    f32x4 rv[16];
+    auto load_res = [&](int a) __attribute__((always_inline)) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            rv[4 * a + c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                          rr, orow[a] && ocol[c] ? rbase : OOB,
+                                                          __builtin_amdgcn_readfirstlane((unsigned)((a * p.W + c) * p.ldr * 4)), 0));
+    };
 
     const int kt0 = PART ? (int)((unsigned)(nk * piece) / (unsigned)p.splits) : 0;
     const int kt1 = PART ? (int)((unsigned)(nk * (piece + 1)) / (unsigned)p.splits) : nk;
@@ -268,39 +285,46 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino4_kernel(const W4Args p) 
 #ifdef MYDET_DIAG
     const uint64_t dbg_t0 = __builtin_amdgcn_s_memtime(), dbg_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    for (int kt = kt0; kt < kt1; ++kt) {
+    // one K stage: 18 LDS reads and 36 MFMAs; fragment reads run one position group ahead of the MFMAs (two register sets)
+#define W4_MMA_STAGE(kt)                                                                                               \
+    {                                                                                                                  \
+        const char *cu = smem + ((kt) & 1) * STAGE + rd_u;                                                             \
+        const char *cv = smem + ((kt) & 1) * STAGE + rd_v;                                                             \
+        f32x4 fu[2], fv[2];                                                                                            \
+        fu[0] = *reinterpret_cast<const f32x4 *>(cu);                                                                  \
+        fv[0] = *reinterpret_cast<const f32x4 *>(cv);                                                                  \
+        _Pragma("unroll") for (int g = 0; g < NPG; ++g) {                                                              \
+            if (g + 1 < NPG) {                                                                                         \
+                fu[(g + 1) & 1] = *reinterpret_cast<const f32x4 *>(cu + (g + 1) * (KC * CH * 16));                     \
+                fv[(g + 1) & 1] = *reinterpret_cast<const f32x4 *>(cv + (g + 1) * (KC * TILES * 16));                  \
+            }                                                                                                          \
+            __builtin_amdgcn_sched_barrier(0);                                                                         \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e)                                                              \
+                acc[4 * g + e] = __builtin_amdgcn_mfma_f32_16x16x4f32(fu[g & 1][e], fv[g & 1][e], acc[4 * g + e], 0, 0, 0); \
+            __builtin_amdgcn_sched_barrier(0);                                                                         \
+        }                                                                                                              \
+    }
+    // RES: the last stage is peeled (below); the other instances close every stage, the last one included, as before
+    for (int kt = kt0; kt < (RES ? kt1 - 1 : kt1); ++kt) {
         if (kt + 1 < kt1) load_stage(kt + 1);          // its buffer was last read before the previous barrier
-        if (RES && kt == kt1 - 1) {
-#pragma unroll
-            for (int o = 0; o < 16; ++o)
-                rv[o] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                      rr, orow[o >> 2] && ocol[o & 3] ? rbase : OOB,
-                                                      __builtin_amdgcn_readfirstlane((unsigned)(((o >> 2) * p.W + (o & 3)) * p.ldr * 4)), 0));
-        }
-        const char *cu = smem + (kt & 1) * STAGE + rd_u;
-        const char *cv = smem + (kt & 1) * STAGE + rd_v;
-        // fragment reads run one position group ahead of the MFMAs (two register sets)
-        f32x4 fu[2], fv[2];
-        fu[0] = *reinterpret_cast<const f32x4 *>(cu);
-        fv[0] = *reinterpret_cast<const f32x4 *>(cv);
-#pragma unroll
-        for (int g = 0; g < NPG; ++g) {
-            if (g + 1 < NPG) {
-                fu[(g + 1) & 1] = *reinterpret_cast<const f32x4 *>(cu + (g + 1) * (KC * CH * 16));
-                fv[(g + 1) & 1] = *reinterpret_cast<const f32x4 *>(cv + (g + 1) * (KC * TILES * 16));
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                acc[4 * g + e] = __builtin_amdgcn_mfma_f32_16x16x4f32(fu[g & 1][e], fv[g & 1][e], acc[4 * g + e], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // (also after the last stage: the residual loads issued under it are then complete before the epilogue.  An earlier
-        // arrangement of those loads gave wrong residuals without it; in the present one hipcc's own count is right --
-        // listing in profiles/r03_isa_notes.md -- and the wait is kept because it is free)
+        W4_MMA_STAGE(kt)
         __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): the next stage has landed
         __syncthreads();
     }
+    const int nc = nok ? n : 0;
+    f32x4 scl, sft;                                    // scale / shift of the lane's four channels
+    if (RES) {
+        // last stage: no DMA is in flight and no LDS buffer is reused after it, so nothing closes it -- no wait, no barrier.
+        // The residual of output rows 0-1 (8 quads) is requested first and is waited for where the row pass first adds
+        // it (hipcc's own vmcnt count; loads return in order).  Scale and shift go in front of it: waiting for them then
+        // drains no residual load.
+        scl = p.scale ? *reinterpret_cast<const f32x4 *>(p.scale + nc) : f32x4{1.f, 1.f, 1.f, 1.f};
+        sft = p.shift ? *reinterpret_cast<const f32x4 *>(p.shift + nc) : f32x4{0.f, 0.f, 0.f, 0.f};
+        load_res(0);
+        load_res(1);
+        W4_MMA_STAGE(kt1 - 1)
+    }
+#undef W4_MMA_STAGE
 
 #ifdef MYDET_DIAG
     if ((p.dbg & 8) && tid == 0) {                     // shader cycles / 100 MHz ticks of the K loop, per workgroup
@@ -311,9 +335,10 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino4_kernel(const W4Args p) 
 #endif
     // ---- epilogue: output transform Y = At M A in place on the accumulators: the column pass leaves
     // s[a][m] = sum_i At[a][i] M[i][m] in acc[6a + m], the row pass takes out[c] = sum_m s[a][m] At[c][m]
-    const int nc = nok ? n : 0;
-    const f32x4 scl = p.scale ? *reinterpret_cast<const f32x4 *>(p.scale + nc) : f32x4{1.f, 1.f, 1.f, 1.f};
-    const f32x4 sft = p.shift ? *reinterpret_cast<const f32x4 *>(p.shift + nc) : f32x4{0.f, 0.f, 0.f, 0.f};
+    if (!RES) {
+        scl = p.scale ? *reinterpret_cast<const f32x4 *>(p.scale + nc) : f32x4{1.f, 1.f, 1.f, 1.f};
+        sft = p.shift ? *reinterpret_cast<const f32x4 *>(p.shift + nc) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll
     for (int m = 0; m < 6; ++m) {
         const f32x4 p1 = acc[6 + m] + acc[12 + m], m1 = acc[6 + m] - acc[12 + m];
@@ -322,6 +347,18 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino4_kernel(const W4Args p) 
         acc[6 + m] = m1 + 2.0f * m2;
         acc[12 + m] = p1 + 4.0f * p2;
         acc[18 + m] = m1 + 8.0f * m2 + acc[30 + m];
+    }
+    if (RES) {
+        // acc[24..35] are dead from here: their 48 registers take the residual of output rows 2-3, which lands under the
+        // row pass, activation and eight stores of rows 0-1
+        // (the empty asm pins the column pass in front of the loads: left alone, hipcc sinks three quarters of it into
+        // the row pass, where all 36 accumulators are still live beside the residual)
+#pragma unroll
+        for (int q = 0; q < 24; q += 6)
+            asm volatile("" : "+v"(acc[q]), "+v"(acc[q + 1]), "+v"(acc[q + 2]), "+v"(acc[q + 3]), "+v"(acc[q + 4]), "+v"(acc[q + 5]));
+        load_res(2);
+        load_res(3);
+        __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
@@ -346,7 +383,10 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino4_kernel(const W4Args p) 
                 if (ACT == MYDET_ACT_LEAKY) v[e] = v[e] > 0.0f ? v[e] : v[e] * 0.1f;
                 if (ACT == MYDET_ACT_SWISH) v[e] = v[e] * mydet_sigmoid_fast(v[e]);
             }
-            if (RES) v += rv[4 * a + c];
+            if (RES) {                                 // one rounding of its own: never contracted with the activation's multiply
+#pragma clang fp contract(off)
+                v += rv[4 * a + c];
+            }
             // the pixel offset goes into the voffset, NOT the scalar offset: with an SGPR soffset hipcc leaves no wait
             // state between a 16-byte store and the VALU that next overwrites its data registers (LLVM pads that hazard
             // only for stores without an SGPR soffset; listing: profiles/r03_isa_notes.md), and on MI355X such a store
@@ -414,7 +454,10 @@ __global__ __launch_bounds__(64 * NW) void wino4_fixup_kernel(const W4Args p) {
             if (ACT == MYDET_ACT_LEAKY) v[e] = v[e] > 0.0f ? v[e] : v[e] * 0.1f;
             if (ACT == MYDET_ACT_SWISH) v[e] = v[e] * mydet_sigmoid_fast(v[e]);
         }
-        if (RES) v += rv[c];
+        if (RES) {                                     // (as in the GEMM kernel: a rounding of its own)
+#pragma clang fp contract(off)
+            v += rv[c];
+        }
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), yr, yo[c], 0, 0);
     }
 }
