@@ -3,6 +3,7 @@
 Same constructor and methods; the model forward and all post-processing run as HIP kernels
 on the MI355X and only the surviving detections come back to the host.
 """
+import collections
 import os
 
 import numpy as np
@@ -98,6 +99,122 @@ class Chips:
     def kwargs(self, input_format):
         """The keyword arguments of the ops.crop_* functions for a model of `input_format`."""
         return dict(size=self.size, max_per_frame=self.max_per_frame, pad=self.pad, fill=self.fill, out=self.out, input_format=input_format)
+
+
+# what the keyword arguments of a frame method say (Detector._call_settings reads them, nothing else does)
+_Call = collections.namedtuple('_Call', 'preprocessing input_size conf_thres nms_thres rotated_nms tiles whole')
+
+
+class _Frames:
+    """B frames of one size for the frame methods of Detector `det`: what differs by pixel format, and nothing else.  The
+    constructors make the host-side checks and set n (= B), hw = (H, W) and idxs, the frames' places in the call's list; no
+    device is touched before on_device(), which moves the frames to the model's device once.  Subclasses give on_device(),
+    input(), align() (of a Tiles' windows), image() -> (what the ops.draw_* / ops.crop_* functions take first, their layout
+    keywords) and drawn()."""
+
+    def device(self):
+        return next(self.det.model.parameters()).device
+
+    def draw(self, found, style):
+        """Paint `found` -- a record dict, read in place, or a list of ImageObjects, one per frame -- into the frames; returns
+        what annotate_frames* returns as `drawn`."""
+        from ..utils.visualization import objects_to_rows
+        image, yuv = self.image()
+        if isinstance(found, dict):
+            ops.draw_records(image, found, style, **yuv)
+        else:
+            boxes, counts, scores, classes, ids = objects_to_rows(found, self.device())
+            (ops.draw_boxes_yuv420 if yuv else ops.draw_boxes)(image, boxes=boxes, style=style, counts=counts, scores=scores, classes=classes,
+                                                               ids=ids, **yuv)
+        return self.drawn()
+
+    def crop(self, found, chip_kwargs):
+        """The chip buffer [B,M,...] of `found` (as in draw); chip_kwargs: Chips.kwargs(...)."""
+        from ..utils.visualization import objects_to_rows
+        image, yuv = self.image()
+        if isinstance(found, dict):
+            return ops.crop_records(image, found, **yuv, **chip_kwargs)
+        boxes, counts = objects_to_rows(found, self.device())[:2]
+        return (ops.crop_boxes_yuv420 if yuv else ops.crop_boxes)(image, boxes=boxes, counts=counts, **yuv, **chip_kwargs)
+
+
+class _RgbFrames(_Frames):
+    """uint8 RGB frames [B,H,W,3]: the tensors `parts` of one size from Detector._frame_groups.  packed: the call goes on to
+    draw into or read the frames, which takes packed pixels -- frames that are not are copied once, on the device."""
+
+    def __init__(self, det, idxs, parts, packed=False):
+        self.det, self.idxs, self.parts, self.packed = det, idxs, parts, packed
+        self.n, self.hw, self.frames = len(idxs), (int(parts[0].shape[1]), int(parts[0].shape[2])), None
+
+    def on_device(self):
+        if self.frames is None:
+            dev, parts = self.device(), self.parts
+            if len(parts) > 1:                                       # a list: gather it where it already is
+                where = dev if all(t.device == dev for t in parts) else torch.device('cpu')
+                parts = [torch.cat([t.to(where) for t in parts])]
+            self.frames = parts[0].to(dev, non_blocking=True)
+            if self.packed and not ops.packed_pixels(self.frames):
+                self.frames = self.frames.contiguous()
+        return self.frames
+
+    def input(self, geometry, out=None, window=None):
+        """The float32 network input of the frames, or of their crop view at window = (y0, x0, h, w): one launch."""
+        fr = self.on_device()
+        if window is not None:
+            y0, x0, h, w = window
+            fr = fr[:, y0:y0 + h, x0:x0 + w]
+        return ops.frames_to_input(fr, geometry, self.det.model.input_format, out=out)
+
+    def align(self, tiles):
+        return tiles._align
+
+    def image(self):
+        return self.on_device(), {}
+
+    drawn = on_device
+
+
+class _Yuv420Frames(_Frames):
+    """The planes of 4:2:0 frames of `layout` with their matrix and range; planes as Detector._yuv_planes takes them.
+    drawn_by: the method that goes on to draw into the planes (8-bit layouts only; a single surface then stays one tensor,
+    which is what comes back as `drawn`)."""
+
+    def __init__(self, det, planes, layout, matrix, full_range, drawn_by=None):
+        if ops.yuv420_layout(layout)[1] != 1 and drawn_by is not None:
+            raise ValueError(f'{drawn_by}: layout {layout!r} is not drawn into; the 8-bit layouts nv12, nv21, i420 and yv12 are')
+        ops.yuv_matrix_id(matrix)
+        y = det._yuv_planes(planes, layout)[0]                       # the checks alone: no device is touched
+        self.det, self.given, self.yuv, self.in_place = det, planes, dict(layout=layout, matrix=matrix, full_range=full_range), drawn_by is not None
+        self.n, self.hw, self.idxs = int(y.shape[0]), (int(y.shape[1]), int(y.shape[2])), list(range(y.shape[0]))
+        self.planes = self.surface = None
+
+    def on_device(self):
+        if self.planes is None:
+            dev, given = self.device(), self.given
+            if self.in_place and isinstance(given, (np.ndarray, torch.Tensor)):
+                given = (torch.from_numpy(np.ascontiguousarray(given)) if isinstance(given, np.ndarray) else given).to(dev, non_blocking=True)
+                if not (given[0] if given.dim() == 3 else given).is_contiguous():
+                    given = given.contiguous()                       # the planar split needs packed rows to stay a view
+                self.surface = given
+            self.planes = tuple(self.det._yuv_planes(given, self.yuv['layout'], device=dev))
+        return self.planes
+
+    def input(self, geometry, out=None, window=None):
+        """As _RgbFrames.input; a window with even origin and size is itself a 4:2:0 frame."""
+        ts = self.on_device()
+        if window is not None:
+            y0, x0, h, w = window
+            ts = [ts[0][:, y0:y0 + h, x0:x0 + w]] + [t[:, y0 // 2:(y0 + h) // 2, x0 // 2:(x0 + w) // 2] for t in ts[1:]]
+        return ops.yuv420_to_input(ts, self.yuv['layout'], geometry, self.det.model.input_format, self.yuv['matrix'], self.yuv['full_range'], out=out)
+
+    def align(self, tiles):
+        return tiles._align * (2 if tiles._align % 2 else 1)
+
+    def image(self):
+        return self.on_device(), self.yuv
+
+    def drawn(self):
+        return self.on_device() if self.surface is None else self.surface
 
 
 class Detector():
@@ -360,117 +477,96 @@ class Detector():
             n += t.shape[0]
         return n, list(groups.values())
 
-    def _frame_records(self, frames, **kwargs):
-        """Detection records of uint8 frames: yields (indices, records) per network input size, like _records_by_size (same
-        batches in the same order, so the same bits).  Frames of one size on the host cross to the device in one copy,
-        frames on the device are read in place; one fused launch (ops.frames_to_input) per frame size builds their
-        network input.  tiles: a Tiles, or None (see predict_frames)."""
-        tiles = kwargs.pop('tiles', None)
-        if tiles is not None:
-            return self._tiled_frame_records(frames, tiles, **kwargs)
+    def _rgb_sources(self, frames, what=None):
+        """The frame sources of uint8 RGB frames (_frame_groups: host checks only), one per frame size.  what: the method that
+        goes on to draw into or cut chips out of the frames -- frames of one size (ValueError), packed on the device."""
         _, groups = self._frame_groups(frames)
+        if what is not None and len(groups) != 1:
+            raise ValueError(f'{what}: frames of one size expected, got {[tuple(parts[0].shape[1:3]) for _, parts in groups]}')
+        return [_RgbFrames(self, idxs, parts, packed=what is not None) for idxs, parts in groups]
 
-        def rgb_input(parts):
-            def build(geo, dev):
-                ps = parts
-                if len(ps) > 1:                                      # a list: gather it where it already is
-                    where = dev if all(t.device == dev for t in ps) else torch.device('cpu')
-                    ps = [torch.cat([t.to(where) for t in ps])]
-                return ops.frames_to_input(ps[0].to(dev, non_blocking=True), geo, self.model.input_format)
-            return build
-        return self._records_of_inputs([(idxs, tuple(parts[0].shape[1:3]), rgb_input(parts)) for idxs, parts in groups], **kwargs)
+    @staticmethod
+    def _one_source(sources, kind):
+        if len(sources) != 1:
+            raise ValueError(f'predict_frames: a {kind} call takes frames of one size, got {[src.hw for src in sources]}')
+        return sources[0]
 
-    def _records_of_inputs(self, groups, **kwargs):
-        """The part of _frame_records that does not depend on the pixel format.  groups: [(frame indices, (H, W) of those
-        frames, build(geometry, device) -> their float32 network input)]."""
-        pre_proc = kwargs.get('preprocessing', self.preprocess)
-        input_size = kwargs.get('input_size', self.input_size)
-        conf_thres = kwargs.get('conf_thres', self.conf_thres)
-        nms_thres = kwargs.get('nms_thres', self.nms_thres)
+    def _call_settings(self, kwargs, whole=False):
+        """What the keyword arguments of a frame method say, read once (a _Call), with the argument rules that need no frame
+        and no device.  whole: the records are wanted as the views of ONE buffer (the tests' `_whole_records` asks for it too)."""
+        tiles = kwargs.get('tiles')
+        if tiles is not None and not isinstance(tiles, Tiles):
+            raise TypeError(f'tiles: a mydetection_amd.api.Tiles (or None) expected, got {type(tiles).__name__}')
         rotated_nms = bool(kwargs.get('rotated_nms', self.rotated_nms))
+        if tiles is not None and tiles.metric == 'ios' and rotated_nms:
+            raise ValueError("tiles: metric 'ios' is defined for the axis-aligned test only, not with rotated_nms")
         if rotated_nms and self.model.bb_format != 'cxcywhd':
             raise ValueError(f"rotated_nms needs a 'cxcywhd' model; this one predicts {self.model.bb_format!r}")
-        dev = next(self.model.parameters()).device
+        return _Call(kwargs.get('preprocessing', self.preprocess), kwargs.get('input_size', self.input_size),
+                     kwargs.get('conf_thres', self.conf_thres), kwargs.get('nms_thres', self.nms_thres), rotated_nms, tiles,
+                     bool(whole or kwargs.get('_whole_records')))
+
+    def _frame_records(self, frames, **kwargs):
+        """Detection records of uint8 frames: yields (indices, records) per network input size, like _records_by_size (same
+        batches in the same order, so the same bits).  tiles: a Tiles, or None (see predict_frames)."""
+        return self._source_records(self._rgb_sources(frames), self._call_settings(kwargs))
+
+    def _source_records(self, sources, call):
+        """[(frame indices, records)] of frame sources, boxes in frame coordinates: per network input size, or, tiled, of the
+        one source's frames after the merge."""
+        if call.tiles is None:
+            return self._records_of_inputs(sources, call)
+        return self._records_of_windows(self._one_source(sources, 'tiled'), call)
+
+    def _records_of_inputs(self, sources, call):
+        """The untiled records: sources of one network input size are one batch, in input order (one fused launch per source
+        builds its part: ops.frames_to_input / ops.yuv420_to_input), and yield one (indices, records)."""
         by_input = {}
-        for idxs, hw, build in groups:
-            geo = self._geometry(hw[0], hw[1], pre_proc, input_size)
-            by_input.setdefault(geo[2], []).append((idxs, hw, build, geo))
+        for src in sources:
+            geo = self._geometry(src.hw[0], src.hw[1], call.preprocessing, call.input_size)
+            by_input.setdefault(geo[2], []).append((src, geo))
         for members in by_input.values():
             idxs, xs, pads, hws = [], [], [], []
-            for part_idxs, hw, build, geo in members:
-                xs.append(build(geo, dev))
-                idxs += part_idxs
-                pads += [geo[3]] * len(part_idxs)
-                hws += [hw if geo[3] is not None else geo[2]] * len(part_idxs)
+            for src, geo in members:
+                xs.append(src.input(geo))
+                idxs += src.idxs
+                pads += [geo[3]] * src.n
+                hws += [src.hw if geo[3] is not None else geo[2]] * src.n
             x = xs[0]
             if len(xs) > 1:                                          # several frame sizes, one input size: one batch, in input order
                 order = sorted(range(len(idxs)), key=idxs.__getitem__)
-                x = torch.cat(xs)[torch.tensor(order, device=dev)]
+                x = torch.cat(xs)[torch.tensor(order, device=x.device)]
                 idxs, pads, hws = [idxs[k] for k in order], [pads[k] for k in order], [hws[k] for k in order]
-            rec = self._records(x, conf_thres, nms_thres, rotated_nms)
-            if kwargs.get('_whole_records'):                         # the views of ONE buffer (a graph replay hands out copies)
+            rec = self._records(x, call.conf_thres, call.nms_thres, call.rotated_nms)
+            if call.whole:                                           # the views of ONE buffer (a graph replay hands out copies)
                 rec = ops.record_views(rec['records'])
             if any(p is not None for p in pads):
                 ops.records_to_original_(rec, pads)
             rec['img_hw'] = hws
             yield idxs, rec
 
-    def _check_tiles(self, tiles, kwargs):
-        """The argument rules of a tiled call that need no frame: touches no device."""
-        if not isinstance(tiles, Tiles):
-            raise TypeError(f'tiles: a mydetection_amd.api.Tiles (or None) expected, got {type(tiles).__name__}')
-        if tiles.metric == 'ios' and bool(kwargs.get('rotated_nms', self.rotated_nms)):
-            raise ValueError("tiles: metric 'ios' is defined for the axis-aligned test only, not with rotated_nms")
-
-    def _tiled_frame_records(self, frames, tiles, **kwargs):
-        """_frame_records with tiles: uint8 frames of ONE size; every window is a crop view of the frames on the device, read
-        in place by its input launch."""
-        self._check_tiles(tiles, kwargs)
-        n, groups = self._frame_groups(frames)
-        if len(groups) != 1:
-            raise ValueError('predict_frames: a tiled call takes frames of one size, got '
-                             f'{[tuple(parts[0].shape[1:3]) for _, parts in groups]}')
-        parts = groups[0][1]
-        H, W = parts[0].shape[1:3]
-        windows = ops.tile_windows(H, W, tiles.size, tiles.overlap, tiles.full_frame, tiles._align)
-        dev = next(self.model.parameters()).device
-        if len(parts) > 1:                                           # a list: gather it where it already is
-            where = dev if all(t.device == dev for t in parts) else torch.device('cpu')
-            parts = [torch.cat([t.to(where) for t in parts])]
-        fr = parts[0].to(dev, non_blocking=True)
-
-        def window_input(win, geo, out):
-            y0, x0, h, w = win
-            ops.frames_to_input(fr[:, y0:y0 + h, x0:x0 + w], geo, self.model.input_format, out=out)
-        return self._records_of_windows(n, (H, W), windows, window_input, tiles, **kwargs)
-
-    def _records_of_windows(self, B, hw, windows, window_input, tiles, **kwargs):
-        """The part of a tiled call that does not depend on the pixel format: [(frame indices, merged records)] of B frames
-        of size hw.  windows: ops.tile_windows' list; window_input(window, geometry, out) writes the network input of all B
-        frames' crops at that window into `out`.  Windows of one network input size are one [n*B,3,Hp,Wp] batch, window-major,
-        built in place; the full-frame window joins the tiles' batch when its input size equals theirs and is a second
-        batch otherwise.  Forward and post-process are self._records (graph capture by shape as everywhere), then the boxes
-        go back to window pixels and ONE merge launch pair makes the B frame records."""
-        pre_proc = kwargs.get('preprocessing', self.preprocess)
-        input_size = kwargs.get('input_size', self.input_size)
-        conf_thres = kwargs.get('conf_thres', self.conf_thres)
-        nms_thres = kwargs.get('nms_thres', self.nms_thres)
-        rotated_nms = bool(kwargs.get('rotated_nms', self.rotated_nms))
-        if rotated_nms and self.model.bb_format != 'cxcywhd':
-            raise ValueError(f"rotated_nms needs a 'cxcywhd' model; this one predicts {self.model.bb_format!r}")
+    def _records_of_windows(self, src, call):
+        """The tiled records, [(frame indices, merged records)] of the B frames of one source.  Every window
+        (ops.tile_windows) is a crop view of the frames on the device, read in place by its input launch.  Windows of one
+        network input size are one [n*B,3,Hp,Wp] batch, window-major, built in place; the full-frame window joins the tiles'
+        batch when its input size equals theirs and is a second batch otherwise.  Forward and post-process are self._records
+        (graph capture by shape as everywhere), then the boxes go back to window pixels and ONE merge launch pair makes the B
+        frame records."""
+        tiles, B = call.tiles, src.n
+        windows = ops.tile_windows(src.hw[0], src.hw[1], tiles.size, tiles.overlap, tiles.full_frame, src.align(tiles))
         dev = next(self.model.parameters()).device
         T = len(windows)
         by_input = {}
         for i, (_, _, h, w) in enumerate(windows):
-            geo = self._geometry(h, w, pre_proc, input_size)
+            geo = self._geometry(h, w, call.preprocessing, call.input_size)
             by_input.setdefault(geo[2], []).append((i, geo))
         batches = []
         for (Hp, Wp), members in by_input.items():
             x = torch.empty((len(members) * B, 3, Hp, Wp), dtype=torch.float32, device=dev)
             for n, (i, geo) in enumerate(members):
-                window_input(windows[i], geo, x[n * B:(n + 1) * B])
+                src.input(geo, out=x[n * B:(n + 1) * B], window=windows[i])
             # the views of ONE buffer (a graph replay hands out the fields as separate copies)
-            rec = ops.record_views(self._records(x, conf_thres, nms_thres, rotated_nms)['records'])
+            rec = ops.record_views(self._records(x, call.conf_thres, call.nms_thres, call.rotated_nms)['records'])
             pads = [geo[3] for _, geo in members for _ in range(B)]
             if any(p is not None for p in pads):
                 ops.records_to_original_(rec, pads)
@@ -481,9 +577,42 @@ class Detector():
             for idx, r in batches:
                 tile_records[idx] = r.view(len(idx), B, -1)
         merged = ops.merge_tile_records(tile_records, B, T, [(x0, y0) for y0, x0, _, _ in windows],
-                                        nms_thres if tiles.nms_thres is None else tiles.nms_thres, tiles.metric, rotated_nms)
-        merged['img_hw'] = [tuple(hw)] * B
+                                        call.nms_thres if tiles.nms_thres is None else tiles.nms_thres, tiles.metric, call.rotated_nms)
+        merged['img_hw'] = [src.hw] * B
         return [(list(range(B)), merged)]
+
+    def _detect(self, make_sources, kwargs, draw=None, chips=None):
+        """The one path behind every frame method that returns objects.  make_sources(): the call's frame sources, built (and
+        so checked) once the tracker's type is known to be right; draw: a Draw, or chips: a Chips, for the methods that go on
+        to paint or cut out what was found (one source).  Returns the ImageObjects in frame order -- with draw, (objects,
+        what the source calls drawn); with chips, (objects, chip views).  An untracked call hands the records buffer to the
+        draw or crop launch before any host synchronisation; a tracked call hands it to the tracker (_tracked_objects) and
+        paints or cuts out the returned tracks."""
+        tracker, coasting = self._pop_tracker(kwargs)
+        sources = make_sources()
+        used = draw is not None or chips is not None
+        if tracker is not None:
+            src = self._one_source(sources, 'tracked')
+            tracker.check_call(src.n, src.hw, self.model.bb_format)
+        elif used:
+            src, = sources                                           # a plain call alone takes any number of sizes, none included
+        call = self._call_settings(kwargs, whole=tracker is not None or used)
+        records = self._source_records(sources, call)
+        if tracker is not None:
+            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, call.conf_thres)
+        elif used:
+            records = list(records)
+            (idxs, found), = records                                 # one frame size: one group, in frame order
+            assert idxs == list(range(src.n))
+        if draw is not None:
+            made = src.draw(found, draw.style(src.hw, tracker is not None))
+        elif chips is not None:
+            made = src.crop(found, chips.kwargs(self.model.input_format))
+        if tracker is None:                                          # after the launch: this is where the host waits for the counts
+            objs = self._objects_of_records(records)
+        if chips is not None:
+            made = self._chip_views(made, objs)
+        return (objs, made) if used else objs
 
     def predict_frames(self, frames, **kwargs):
         """predict_batch for decoded video: `frames` is a torch.uint8 tensor or numpy.uint8 array [B,H,W,3] (or [H,W,3]) in
@@ -499,16 +628,7 @@ class Detector():
         associates the call's detections with the tracker's tracks, and each ImageObjects then holds the tracks matched or born
         in its frame -- bboxes the Kalman-filtered state, scores the track scores, cats the classes, obj_ids (int64) the
         persistent identities -- and, with coasting=True, the live tracks without a detection in that frame as well."""
-        tracker, coasting = self._pop_tracker(kwargs)
-        if tracker is None:
-            return self._objects_of_records(self._frame_records(frames, **kwargs))
-        n, groups = self._frame_groups(frames)
-        if len(groups) != 1:
-            raise ValueError('predict_frames: a tracked call takes frames of one size, got '
-                             f'{[tuple(parts[0].shape[1:3]) for _, parts in groups]}')
-        hw = tuple(int(v) for v in groups[0][1][0].shape[1:3])
-        tracker.check_call(n, hw, self.model.bb_format)
-        return self._tracked_objects(self._frame_records(frames, _whole_records=True, **kwargs), hw, tracker, coasting, kwargs)
+        return self._detect(lambda: self._rgb_sources(frames), kwargs)
 
     @staticmethod
     def _pop_tracker(kwargs):
@@ -524,7 +644,7 @@ class Detector():
         if 'tracker' in kwargs or 'coasting' in kwargs:
             raise TypeError(f'{what}: track ids in the json rows are not built; use the predict_frames form with tracker=')
 
-    def _tracked_objects(self, records, frame_hw, tracker, coasting, kwargs):
+    def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres):
         """The tracked form of _objects_of_records: one eager tracker launch on the call's records (frame coordinates, one
         buffer), then per frame the ImageObjects of the tracks with missed == 0 (coasting: of every live track).  Two host
         synchronisations: the frame counts, and the indices of the selected slots."""
@@ -536,7 +656,7 @@ class Detector():
         hw = rec['img_hw'][0]                                        # what the untracked call reports
         width = 5 if 'angle' in rec else 4
         state = tracker.bind(frame_hw, width, rec['records'].device)
-        params = tracker.params(frame_hw, tracker.resolve_match(self.model.bb_format), kwargs.get('conf_thres', self.conf_thres))
+        params = tracker.params(frame_hw, tracker.resolve_match(self.model.bb_format), conf_thres)
         out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks)
         B, mt = len(idxs), tracker.max_tracks
         missed = out['missed'].view(B, mt)
@@ -628,31 +748,6 @@ class Detector():
             ts = [t.to(device, non_blocking=True) for t in ts]
         return ts
 
-    def _yuv_records(self, planes, layout, matrix, full_range, **kwargs):
-        """_frame_records for 4:2:0 frames of one size: one fused launch (ops.yuv420_to_input) builds the network input from
-        the planes; everything after it is _records_of_inputs, as for RGB frames.  tiles: a Tiles, or None (see
-        predict_frames): windows with even origins and sizes, so every window of the planes is itself a 4:2:0 frame."""
-        tiles = kwargs.pop('tiles', None)
-        ops.yuv420_layout(layout)
-        ops.yuv_matrix_id(matrix)
-        if tiles is not None:
-            self._check_tiles(tiles, kwargs)
-            y = self._yuv_planes(planes, layout)[0]                  # the checks alone: no device is touched
-            B, H, W = y.shape
-            windows = ops.tile_windows(H, W, tiles.size, tiles.overlap, tiles.full_frame, tiles._align * (2 if tiles._align % 2 else 1))
-            ts = self._yuv_planes(planes, layout, device=next(self.model.parameters()).device)
-
-            def window_input(win, geo, out):
-                y0, x0, h, w = win
-                crop = [ts[0][:, y0:y0 + h, x0:x0 + w]] + [t[:, y0 // 2:(y0 + h) // 2, x0 // 2:(x0 + w) // 2] for t in ts[1:]]
-                ops.yuv420_to_input(crop, layout, geo, self.model.input_format, matrix, full_range, out=out)
-            return self._records_of_windows(B, (H, W), windows, window_input, tiles, **kwargs)
-        ts = tuple(self._yuv_planes(planes, layout, device=next(self.model.parameters()).device))
-
-        def build(geo, dev):
-            return ops.yuv420_to_input(ts, layout, geo, self.model.input_format, matrix, full_range)
-        return self._records_of_inputs([(list(range(ts[0].shape[0])), (ts[0].shape[1], ts[0].shape[2]), build)], **kwargs)
-
     def predict_frames_yuv(self, planes, layout, *, matrix='bt601', full_range=False, **kwargs):
         """predict_frames for 4:2:0 video in any layout decoders give: 'nv12', 'nv21' (8-bit, interleaved chroma), 'i420',
         'yv12' (8-bit, planar), 'p010' (10 bits in the high end of 16-bit words, interleaved) and 'i010' (yuv420p10le: 10
@@ -663,21 +758,14 @@ class Detector():
         predict_frames returns for the converted RGB frames (ops.yuv420_to_rgb), which are never built: one HIP launch
         reads the planes.  One call takes one frame size.  Keyword arguments as in _predict_pil and predict_frames (tiles:
         even frame and tile sizes; tracker, coasting)."""
-        tracker, coasting = self._pop_tracker(kwargs)
-        if tracker is None:
-            return self._objects_of_records(self._yuv_records(planes, layout, matrix, full_range, **kwargs))
-        ops.yuv420_layout(layout)
-        y = self._yuv_planes(planes, layout)[0]                      # the checks alone: no device is touched
-        hw = tuple(int(v) for v in y.shape[1:3])
-        tracker.check_call(y.shape[0], hw, self.model.bb_format)
-        return self._tracked_objects(self._yuv_records(planes, layout, matrix, full_range, _whole_records=True, **kwargs), hw, tracker,
-                                     coasting, kwargs)
+        return self._detect(lambda: [_Yuv420Frames(self, planes, layout, matrix, full_range)], kwargs)
 
     def frames_yuv_to_json(self, planes, layout, img_ids, eval_type='x1y1wh', catIdx2id=None, *, matrix='bt601', full_range=False,
                            **kwargs):
         """COCO-style rows of 4:2:0 frames (see predict_frames_yuv): the counterpart of frames_to_json."""
         self._no_tracker(kwargs, 'frames_yuv_to_json')
-        return self._json_of_records(self._yuv_records(planes, layout, matrix, full_range, **kwargs), img_ids, eval_type, catIdx2id)
+        records = self._source_records([_Yuv420Frames(self, planes, layout, matrix, full_range)], self._call_settings(kwargs))
+        return self._json_of_records(records, img_ids, eval_type, catIdx2id)
 
     def predict_frames_nv12(self, y, uv=None, *, matrix='bt601', full_range=False, **kwargs):
         """predict_frames for NV12 video, the format decoders produce: y is the uint8 Y plane [B,H,W] (or [H,W]) and uv the
@@ -695,20 +783,11 @@ class Detector():
                                        full_range=full_range, **kwargs)
 
     @staticmethod
-    def _check_draw(draw, what):
-        if not isinstance(draw, Draw):
-            raise TypeError(f'{what}: draw is a mydetection_amd.api.Draw, got {type(draw).__name__}')
-
-    def _draw_objects(self, target, layout, objs, style, matrix='bt601', full_range=False):
-        """Paint a list of ImageObjects (one per frame) into the device frames or planes: the tracked form of the drawing."""
-        from ..utils.visualization import objects_to_rows
-        dev = (target if layout is None else target[0]).device
-        boxes, counts, scores, classes, ids = objects_to_rows(objs, dev)
-        if layout is None:
-            ops.draw_boxes(target, boxes, style, counts=counts, scores=scores, classes=classes, ids=ids)
-        else:
-            ops.draw_boxes_yuv420(target, layout, boxes, style, counts=counts, scores=scores, classes=classes, ids=ids, matrix=matrix,
-                                  full_range=full_range)
+    def _setting(given, kind, what):
+        """The Draw or Chips (`kind`) of a call: the default one for None, a TypeError for anything else."""
+        if given is not None and not isinstance(given, kind):
+            raise TypeError(f'{what}: {kind.__name__.lower()} is a mydetection_amd.api.{kind.__name__}, got {type(given).__name__}')
+        return kind() if given is None else given
 
     def annotate_frames(self, frames, draw=None, **kwargs):
         """predict_frames plus the overlay: returns (objects, drawn).  objects is exactly what predict_frames(frames, **kwargs)
@@ -717,93 +796,26 @@ class Detector():
         packed pixels, else the device batch the call had to build anyway.  Frames of one size (ValueError otherwise).  draw: a
         Draw (default Draw()).  tiles=, tracker= and coasting= as in predict_frames.  An untracked call draws straight from the
         records buffer, before any host synchronisation; a tracked call draws the returned tracks, with their ids."""
-        draw = Draw() if draw is None else draw
-        self._check_draw(draw, 'annotate_frames')
-        tracker, coasting = self._pop_tracker(kwargs)
-        n, groups = self._frame_groups(frames)
-        if len(groups) != 1:
-            raise ValueError(f'annotate_frames: frames of one size expected, got {[tuple(parts[0].shape[1:3]) for _, parts in groups]}')
-        if tracker is not None:
-            tracker.check_call(n, tuple(int(v) for v in groups[0][1][0].shape[1:3]), self.model.bb_format)
-        dev = next(self.model.parameters()).device
-        parts = groups[0][1]
-        if len(parts) > 1:
-            where = dev if all(t.device == dev for t in parts) else torch.device('cpu')
-            parts = [torch.cat([t.to(where) for t in parts])]
-        fr = parts[0].to(dev, non_blocking=True)
-        if fr.stride(3) != 1 or fr.stride(2) != 3 or fr.stride(1) < 3 * fr.shape[2] or fr.stride(0) < 0:
-            fr = fr.contiguous()
-        hw = (int(fr.shape[1]), int(fr.shape[2]))
-        style = draw.style(hw, tracker is not None)
-        if tracker is not None:
-            objs = self.predict_frames(fr, tracker=tracker, coasting=coasting, **kwargs)
-            self._draw_objects(fr, None, objs, style)
-            return objs, fr
-        records = list(self._frame_records(fr, _whole_records=True, **kwargs))
-        for idxs, rec in records:                                    # one frame size: one group, in frame order
-            assert idxs == list(range(n))
-            ops.draw_records(fr, rec, style)
-        return self._objects_of_records(records), fr
+        draw = self._setting(draw, Draw, 'annotate_frames')
+        return self._detect(lambda: self._rgb_sources(frames, 'annotate_frames'), kwargs, draw=draw)
 
     def annotate_frames_yuv(self, planes, layout, draw=None, *, matrix='bt601', full_range=False, **kwargs):
         """predict_frames_yuv plus the overlay, painted into the planes (include/mydet.h: mydet_draw_boxes_yuv420_u8): returns
         (objects, drawn).  layout: 'nv12', 'nv21', 'i420' or 'yv12'; the 10-bit layouts are not drawn into (ValueError).  drawn:
         the planes on the device, in the order given -- the input tensors themselves when they are device tensors -- or, for a
         single surface, the surface.  matrix and full_range also say how the colours become Y'CbCr.  Otherwise as annotate_frames."""
-        draw = Draw() if draw is None else draw
-        self._check_draw(draw, 'annotate_frames_yuv')
-        if ops.yuv420_layout(layout)[1] != 1:
-            raise ValueError(f'annotate_frames_yuv: layout {layout!r} is not drawn into; the 8-bit layouts nv12, nv21, i420 and yv12 are')
-        ops.yuv_matrix_id(matrix)
-        tracker, coasting = self._pop_tracker(kwargs)
-        y = self._yuv_planes(planes, layout)[0]                      # the checks alone: no device is touched
-        if tracker is not None:
-            tracker.check_call(y.shape[0], tuple(int(v) for v in y.shape[1:3]), self.model.bb_format)
-        dev = next(self.model.parameters()).device
-        surface = None
-        if isinstance(planes, (np.ndarray, torch.Tensor)):
-            surface = (torch.from_numpy(np.ascontiguousarray(planes)) if isinstance(planes, np.ndarray) else planes).to(dev, non_blocking=True)
-            if not (surface[0] if surface.dim() == 3 else surface).is_contiguous():
-                surface = surface.contiguous()                       # the planar split needs packed rows to stay a view
-            ts = tuple(self._yuv_planes(surface, layout, device=dev))
-        else:
-            ts = tuple(self._yuv_planes(planes, layout, device=dev))
-        hw = (int(ts[0].shape[1]), int(ts[0].shape[2]))
-        style = draw.style(hw, tracker is not None)
-        drawn = ts if surface is None else surface
-        if tracker is not None:
-            objs = self.predict_frames_yuv(ts, layout, matrix=matrix, full_range=full_range, tracker=tracker, coasting=coasting, **kwargs)
-            self._draw_objects(ts, layout, objs, style, matrix, full_range)
-            return objs, drawn
-        records = list(self._yuv_records(ts, layout, matrix, full_range, _whole_records=True, **kwargs))
-        for idxs, rec in records:
-            assert idxs == list(range(ts[0].shape[0]))
-            ops.draw_records(ts, rec, style, layout=layout, matrix=matrix, full_range=full_range)
-        return self._objects_of_records(records), drawn
+        draw = self._setting(draw, Draw, 'annotate_frames_yuv')
+        return self._detect(lambda: [_Yuv420Frames(self, planes, layout, matrix, full_range, drawn_by='annotate_frames_yuv')], kwargs,
+                            draw=draw)
 
     def annotate_frames_nv12(self, y, uv=None, draw=None, *, matrix='bt601', full_range=False, **kwargs):
         """annotate_frames_yuv for NV12: (y, uv) planes, or with uv=None the single surface [B,H*3/2,W] (see predict_frames_nv12)."""
         return self.annotate_frames_yuv(y if uv is None else (y, uv), 'nv12', draw, matrix=matrix, full_range=full_range, **kwargs)
 
     @staticmethod
-    def _check_chips(chips, what):
-        if not isinstance(chips, Chips):
-            raise TypeError(f'{what}: chips is a mydetection_amd.api.Chips, got {type(chips).__name__}')
-
-    @staticmethod
     def _chip_views(buf, objs):
         """One view per frame of the chip buffer [B,M,...]: the chips of the frame's first min(len(objects), M) rows."""
         return [buf[b, :min(len(o), buf.shape[1])] for b, o in enumerate(objs)]
-
-    def _crop_objects(self, source, layout, objs, chips, matrix='bt601', full_range=False):
-        """The chips of a list of ImageObjects (one per frame) out of the device frames or planes: the tracked form."""
-        from ..utils.visualization import objects_to_rows
-        dev = (source if layout is None else source[0]).device
-        boxes, counts = objects_to_rows(objs, dev)[:2]
-        kw = chips.kwargs(self.model.input_format)
-        if layout is None:
-            return ops.crop_boxes(source, boxes, counts=counts, **kw)
-        return ops.crop_boxes_yuv420(source, layout, boxes, counts=counts, matrix=matrix, full_range=full_range, **kw)
 
     def crop_frames(self, frames, chips=None, **kwargs):
         """predict_frames plus the object chips: returns (objects, chips).  objects is exactly what predict_frames(frames,
@@ -814,52 +826,15 @@ class Detector():
         first max_per_frame rows only (n_b = min(len(objects[b]), max_per_frame)).  Frames of one size (ValueError otherwise).
         chips: a Chips (default Chips()).  tiles=, tracker= and coasting= as in predict_frames.  An untracked call launches
         straight from the records buffer, before any host synchronisation; a tracked call crops the tracks' filtered boxes."""
-        chips = Chips() if chips is None else chips
-        self._check_chips(chips, 'crop_frames')
-        tracker, coasting = self._pop_tracker(kwargs)
-        n, groups = self._frame_groups(frames)
-        if len(groups) != 1:
-            raise ValueError(f'crop_frames: frames of one size expected, got {[tuple(parts[0].shape[1:3]) for _, parts in groups]}')
-        if tracker is not None:
-            tracker.check_call(n, tuple(int(v) for v in groups[0][1][0].shape[1:3]), self.model.bb_format)
-        dev = next(self.model.parameters()).device
-        parts = groups[0][1]
-        if len(parts) > 1:
-            where = dev if all(t.device == dev for t in parts) else torch.device('cpu')
-            parts = [torch.cat([t.to(where) for t in parts])]
-        fr = parts[0].to(dev, non_blocking=True)
-        if fr.stride(3) != 1 or fr.stride(2) != 3 or fr.stride(1) < 3 * fr.shape[2] or fr.stride(0) < 0:
-            fr = fr.contiguous()
-        if tracker is not None:
-            objs = self.predict_frames(fr, tracker=tracker, coasting=coasting, **kwargs)
-            return objs, self._chip_views(self._crop_objects(fr, None, objs, chips), objs)
-        records = list(self._frame_records(fr, _whole_records=True, **kwargs))
-        assert len(records) == 1 and records[0][0] == list(range(n))  # one frame size: one group, in frame order
-        buf = ops.crop_records(fr, records[0][1], **chips.kwargs(self.model.input_format))
-        objs = self._objects_of_records(records)
-        return objs, self._chip_views(buf, objs)
+        chips = self._setting(chips, Chips, 'crop_frames')
+        return self._detect(lambda: self._rgb_sources(frames, 'crop_frames'), kwargs, chips=chips)
 
     def crop_frames_yuv(self, planes, layout, chips=None, *, matrix='bt601', full_range=False, **kwargs):
         """predict_frames_yuv plus the object chips, cut straight out of the planes (include/mydet.h: mydet_crop_boxes_yuv420):
         returns (objects, chips) as crop_frames does, the chips being those of the converted RGB frames (ops.yuv420_to_rgb),
         which are never built.  Every layout of predict_frames_yuv is accepted, the 10-bit ones included: crops only read."""
-        chips = Chips() if chips is None else chips
-        self._check_chips(chips, 'crop_frames_yuv')
-        ops.yuv420_layout(layout)
-        ops.yuv_matrix_id(matrix)
-        tracker, coasting = self._pop_tracker(kwargs)
-        y = self._yuv_planes(planes, layout)[0]                      # the checks alone: no device is touched
-        if tracker is not None:
-            tracker.check_call(y.shape[0], tuple(int(v) for v in y.shape[1:3]), self.model.bb_format)
-        ts = tuple(self._yuv_planes(planes, layout, device=next(self.model.parameters()).device))
-        if tracker is not None:
-            objs = self.predict_frames_yuv(ts, layout, matrix=matrix, full_range=full_range, tracker=tracker, coasting=coasting, **kwargs)
-            return objs, self._chip_views(self._crop_objects(ts, layout, objs, chips, matrix, full_range), objs)
-        records = list(self._yuv_records(ts, layout, matrix, full_range, _whole_records=True, **kwargs))
-        assert len(records) == 1 and records[0][0] == list(range(ts[0].shape[0]))
-        buf = ops.crop_records(ts, records[0][1], layout=layout, matrix=matrix, full_range=full_range, **chips.kwargs(self.model.input_format))
-        objs = self._objects_of_records(records)
-        return objs, self._chip_views(buf, objs)
+        chips = self._setting(chips, Chips, 'crop_frames_yuv')
+        return self._detect(lambda: [_Yuv420Frames(self, planes, layout, matrix, full_range)], kwargs, chips=chips)
 
     def crop_frames_nv12(self, y, uv=None, chips=None, *, matrix='bt601', full_range=False, **kwargs):
         """crop_frames_yuv for NV12: (y, uv) planes, or with uv=None the single surface [B,H*3/2,W] (see predict_frames_nv12)."""

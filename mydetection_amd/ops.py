@@ -1143,6 +1143,20 @@ def record_views(records):
     return out
 
 
+def _record_buffer(what, rec):
+    """The 'records' buffer of a record dict (record_views), checked: int32 [B, REC_WORDS | REC_ROT_WORDS] with packed words,
+    and the dict's fields views of it -- a graph replay hands out copies, which say nothing about the buffer a launch reads."""
+    if not isinstance(rec, dict) or 'records' not in rec or 'bbox' not in rec:
+        raise TypeError(f'{what}: rec is the dict of ops.record_views, got {type(rec).__name__}')
+    records = rec['records']
+    if not isinstance(records, torch.Tensor) or records.dtype != torch.int32 or records.dim() != 2 or \
+            records.shape[1] not in (_lib.REC_WORDS, _lib.REC_ROT_WORDS) or records.stride(1) != 1 or records.stride(0) < 0:
+        raise ValueError(f'{what}: int32 records [B, {_lib.REC_WORDS} | {_lib.REC_ROT_WORDS}] expected')
+    if rec['bbox'].data_ptr() != records.data_ptr() + 4 * _lib.REC_BBOX:
+        raise ValueError(f"{what}: the fields of this record dict are copies, not views of its 'records' buffer")
+    return records
+
+
 def record_boxes(rec, b, k):
     """The first k boxes of image b of a record dict as [k, 4] (cxcywh) or [k, 5] (cxcywhd: the angle column appended)."""
     if 'angle' not in rec:
@@ -1276,9 +1290,7 @@ def merge_tile_records(rec, B, T, origins, nms_thres, metric='iou', rotated_nms=
     record_views dict of the merged records; 'index' holds t*512 + k of every survivor."""
     m = merge_metric_id(metric)
     if isinstance(rec, dict):
-        views, rec = rec, rec['records']
-        if views['bbox'].data_ptr() != rec.data_ptr() + 4 * _lib.REC_BBOX:
-            raise ValueError("merge_tile_records: the fields of this record dict are copies, not views of its 'records' buffer")
+        rec = _record_buffer('merge_tile_records', rec)
     require_gpu(rec, 'merge_tile_records')
     B, T = int(B), int(T)
     words = rec.shape[-1]
@@ -1434,9 +1446,7 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     if not isinstance(params, _lib.TrackParams):
         raise TypeError(f'track_frames: params is a _lib.TrackParams (ops.track_params), got {type(params).__name__}')
     if isinstance(records, dict):
-        views, records = records, records['records']
-        if views['bbox'].data_ptr() != records.data_ptr() + 4 * _lib.REC_BBOX:
-            raise ValueError("track_frames: the fields of this record dict are copies, not views of its 'records' buffer")
+        records = _record_buffer('track_frames', records)
     if not isinstance(tracker_state, torch.Tensor) or tracker_state.dim() != 2:
         raise ValueError('track_frames: tracker_state is the int32 [streams, words] tensor of ops.track_state')
     S = tracker_state.shape[0]
@@ -1591,6 +1601,12 @@ def _input_window(what, B, H, W, device, geometry, input_format, out):
     return out, (oh, ow), (top, left), max(ksx, ksy), tail
 
 
+def packed_pixels(frames):
+    """Whether a kernel can read or write uint8 frames [B,H,W,3] through their strides: the three bytes of a pixel and the
+    pixels of a row are packed; any row and frame strides."""
+    return frames.stride(3) == 1 and frames.stride(2) == 3 and frames.stride(1) >= 3 * frames.shape[2] and frames.stride(0) >= 0
+
+
 def frames_to_input(frames_u8, geometry, input_format, out=None):
     """uint8 frames [B,H,W,3] (or [H,W,3]) of one size on the device -> the float32 network input [B,3,Hp,Wp] in ONE launch
     (include/mydet.h: mydet_frames_to_input_f32): PIL-exact resize, zero padding, /255 and normalisation, the bits
@@ -1607,7 +1623,7 @@ def frames_to_input(frames_u8, geometry, input_format, out=None):
         raise ValueError(f'frames_to_input: frames of shape [B,H,W,3] or [H,W,3] expected, got {tuple(frames_u8.shape)}')
     B, H, W, _ = frames_u8.shape
     out, (oh, ow), (top, left), taps, tail = _input_window('frames_to_input', B, H, W, frames_u8.device, geometry, input_format, out)
-    if frames_u8.stride(3) != 1 or frames_u8.stride(2) != 3 or frames_u8.stride(1) < 3 * W:
+    if not packed_pixels(frames_u8):
         frames_u8 = frames_u8.contiguous()
     if taps > _lib.FRAMES_MAX_TAPS:
         Hp, Wp = geometry[2]
@@ -1689,19 +1705,23 @@ def yuv420_check_planes(planes, layout, what):
     return planes, single
 
 
-def _yuv420_planes(planes, layout, what):
-    """What yuv420_to_rgb and yuv420_to_input share: the checked planes (yuv420_check_planes) in the order of
-    mydet_yuv420_src.plane and whether the input was 2-d; on the device, read in place through their frame and row strides
-    when samples (and pairs) are packed.  Type, dtype and shape errors are raised before any device is touched."""
+def _yuv420_planes(planes, layout, what, in_place=False):
+    """What every kernel on 4:2:0 frames shares: the checked planes (yuv420_check_planes) in the order of
+    mydet_yuv420_src.plane and whether the input was 2-d; on the device, used in place through their frame and row strides
+    when samples (and pairs) are packed -- planes that are not are copied, or refused (ValueError) when the kernel writes them
+    (in_place).  Type, dtype, shape and in-place errors are raised before any device is touched."""
     if not isinstance(planes, (tuple, list)):
         raise TypeError(f'{what}: a tuple of planes expected, got {type(planes).__name__}')
     planes, single = yuv420_check_planes(planes, layout, what)
     for i, t in enumerate(planes):
+        inner = t.dim() == 4                                             # pairs: the last two dimensions are packed
+        packed = t.stride(-1) == 1 and (not inner or t.stride(2) == 2) and t.stride(1) >= t.shape[2] * (2 if inner else 1) and t.stride(0) >= 0
+        if in_place and not packed:
+            raise ValueError(f'{what}: planes are drawn in place and need packed samples (strides {tuple(t.stride())} of {tuple(t.shape)})')
         require_gpu(t, what)
         if t.device != planes[0].device:
             raise ValueError(f'{what}: y is on {planes[0].device}, another plane on {t.device}')
-        inner = t.dim() == 4                                             # pairs: the last two dimensions are packed
-        if t.stride(-1) != 1 or (inner and t.stride(2) != 2) or t.stride(1) < t.shape[2] * (2 if inner else 1) or t.stride(0) < 0:
+        if not packed:
             planes[i] = t.contiguous()
     if layout == 'yv12':
         planes[1], planes[2] = planes[2], planes[1]
@@ -1733,7 +1753,7 @@ def yuv420_to_rgb(planes, layout, matrix='bt601', full_range=False, out=None):
         out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=planes[0].device)
     dst = out.unsqueeze(0) if out.dim() == 3 else out
     assert dst.dtype == torch.uint8 and tuple(dst.shape) == (B, H, W, 3) and dst.device == planes[0].device
-    assert dst.stride(3) == 1 and dst.stride(2) == 3 and dst.stride(1) >= 3 * W and dst.stride(0) >= 0
+    assert packed_pixels(dst)
     src = _yuv420_src(planes, layout, m, full_range)
     code = _lib.lib().mydet_yuv420_to_rgb_u8(ctypes.byref(src), B, H, W, _ptr(dst), dst.stride(0), dst.stride(1), _stream())
     _lib.check(code, 'mydet_yuv420_to_rgb_u8')
@@ -2058,8 +2078,8 @@ def _draw_check_style(style, what):
         raise TypeError(f'{what}: style is an ops.DrawStyle (ops.draw_style), got {type(style).__name__}')
 
 
-def _draw_rows(what, B, boxes, counts, scores, classes, ids):
-    """The checked dense row tensors of a draw call (no device touched): boxes [B,K,4|5] float32 and the optional planes."""
+def _box_rows(what, B, boxes, counts, scores, classes, ids):
+    """The checked dense row tensors of a draw or crop call (no device touched): boxes [B,K,4|5] float32 and the optional planes."""
     if not isinstance(boxes, torch.Tensor) or boxes.dtype != torch.float32:
         raise TypeError(f'{what}: boxes is a float32 tensor, got {boxes.dtype if isinstance(boxes, torch.Tensor) else type(boxes).__name__}')
     if boxes.dim() == 2:
@@ -2087,94 +2107,122 @@ def _draw_rows(what, B, boxes, counts, scores, classes, ids):
     return boxes, counts, planes
 
 
-def _draw_rgb_target(what, frames):
-    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
-        raise TypeError(f'{what}: uint8 frames expected, got {frames.dtype if isinstance(frames, torch.Tensor) else type(frames).__name__}')
-    fr = frames.unsqueeze(0) if frames.dim() == 3 else frames
+def _image(what, image, layout, matrix, full_range, in_place):
+    """The image side of a draw or crop call: (what the kernel is given -- the uint8 frames [B,H,W,3] (layout None) or the
+    checked planes of `layout` (_yuv420_planes) --, None or (layout, matrix id, full_range), B).  Frames and planes are used
+    through their strides when pixels or samples are packed; those that are not are copied, or, when the kernel writes them
+    (in_place), refused with a ValueError, as the 10-bit layouts then are."""
+    if layout is not None:
+        if yuv420_layout(layout)[1] != 1 and in_place:
+            raise ValueError(f'{what}: layout {layout!r} is not drawn into; the 8-bit layouts nv12, nv21, i420 and yv12 are')
+        m = yuv_matrix_id(matrix)
+        planes, _ = _yuv420_planes(image, layout, what, in_place)
+        return planes, (layout, m, full_range), planes[0].shape[0]
+    if not isinstance(image, torch.Tensor) or image.dtype != torch.uint8:
+        raise TypeError(f'{what}: uint8 frames expected, got {image.dtype if isinstance(image, torch.Tensor) else type(image).__name__}')
+    fr = image.unsqueeze(0) if image.dim() == 3 else image
     if fr.dim() != 4 or fr.shape[3] != 3 or min(fr.shape) < 1:
-        raise ValueError(f'{what}: frames of shape [B,H,W,3] or [H,W,3] expected, got {tuple(frames.shape)}')
-    if fr.stride(3) != 1 or fr.stride(2) != 3 or fr.stride(1) < 3 * fr.shape[2] or fr.stride(0) < 0:
-        raise ValueError(f'{what}: frames are drawn in place and need packed pixels (strides {tuple(fr.stride())} of {tuple(fr.shape)})')
-    return fr
+        raise ValueError(f'{what}: frames of shape [B,H,W,3] or [H,W,3] expected, got {tuple(image.shape)}')
+    if not packed_pixels(fr):
+        if in_place:
+            raise ValueError(f'{what}: frames are drawn in place and need packed pixels (strides {tuple(fr.stride())} of {tuple(fr.shape)})')
+        fr = fr.contiguous()
+    return fr, None, fr.shape[0]
 
 
-def _draw_yuv_target(what, planes, layout):
-    sel, bps, planar = yuv420_layout(layout)
-    if bps != 1:
-        raise ValueError(f'{what}: layout {layout!r} is not drawn into; the 8-bit layouts nv12, nv21, i420 and yv12 are')
-    if not isinstance(planes, (tuple, list)):
-        raise TypeError(f'{what}: a tuple of planes expected, got {type(planes).__name__}')
-    planes, single = yuv420_check_planes(planes, layout, what)
-    for t in planes:
-        inner = t.dim() == 4
-        if t.stride(-1) != 1 or (inner and t.stride(2) != 2) or t.stride(1) < t.shape[2] * (2 if inner else 1) or t.stride(0) < 0:
-            raise ValueError(f'{what}: planes are drawn in place and need packed samples (strides {tuple(t.stride())} of {tuple(t.shape)})')
-    if layout == 'yv12':
-        planes[1], planes[2] = planes[2], planes[1]
-    return planes
-
-
-def _draw_on_device(what, target_planes, tensors):
-    dev = target_planes[0].device
-    for t in list(target_planes) + [t for t in tensors if t is not None]:
+def _same_device(what, image, tensors):
+    """The device of the frames or planes of _image, which every tensor of `tensors` (None entries aside) shares."""
+    planes = [image] if isinstance(image, torch.Tensor) else list(image)
+    dev = planes[0].device
+    for t in planes + [t for t in tensors if t is not None]:
         require_gpu(t, what)
         if t.device != dev:
             raise ValueError(f'{what}: the target is on {dev}, another tensor on {t.device}')
     return dev
 
 
-def _draw_launch(target, yuv, lst, style, dev):
-    """One launch: target = the [B,H,W,3] frames or the checked planes; yuv = None or (layout, matrix id, full_range)."""
-    s, keep = style.struct(dev)
+def _list_of_records(what, records, labels, ids):
+    """The _lib.DrawList of a checked records buffer (_record_buffer), read in place through its strides: the boxes, the
+    angles of rotated records and the counts; with `labels` the score and class planes as well.  ids: None, or a contiguous
+    int64 [B,512] that the caller keeps alive."""
+    base, fs = records.data_ptr(), records.stride(0)
+    lst = _lib.DrawList()
+    lst.box, lst.box_frame_stride, lst.box_row_stride = base + 4 * _lib.REC_BBOX, fs, 4
+    if records.shape[1] == _lib.REC_ROT_WORDS:
+        lst.angle, lst.angle_frame_stride, lst.angle_row_stride = base + 4 * _lib.REC_ANGLE, fs, 1
+    if labels:
+        if fs % 2:
+            raise ValueError(f'{what}: a record stride of an even number of words expected, got {fs}')
+        lst.score, lst.score_frame_stride, lst.score_row_stride = base + 4 * _lib.REC_SCORE, fs, 1
+        lst.cls, lst.cls_frame_stride, lst.cls_row_stride = base + 4 * _lib.REC_CLASS, fs // 2, 1      # int64 elements: fs is even
+    if ids is not None:
+        lst.id, lst.id_frame_stride, lst.id_row_stride = _ptr(ids), _lib.REC_TOPK, 1
+    lst.count, lst.count_stride = base + 4 * _lib.REC_COUNT, fs
+    lst.K = _lib.REC_TOPK
+    return lst
+
+
+def _list_of_rows(boxes, lo, n, counts, planes):
+    """The _lib.DrawList of rows lo .. lo + n - 1 of dense rows, all contiguous and kept alive by the caller: boxes float32
+    [B,K,4|5]; counts: None or int32 [B], the rows of this run that are boxes; planes: {'score': float32 [B,K], 'cls' and
+    'id': int64 [B,K]}, entries that are None or missing left out."""
+    K, width = boxes.shape[1:]
+    lst = _lib.DrawList()
+    lst.box, lst.box_frame_stride, lst.box_row_stride = boxes.data_ptr() + 4 * lo * width, K * width, width
+    if width == 5:
+        lst.angle, lst.angle_frame_stride, lst.angle_row_stride = boxes.data_ptr() + 4 * (lo * width + 4), K * width, width
+    for field, size in (('score', 4), ('cls', 8), ('id', 8)):
+        if planes.get(field) is not None:
+            setattr(lst, field, planes[field].data_ptr() + size * lo)
+            setattr(lst, field + '_frame_stride', K)
+            setattr(lst, field + '_row_stride', 1)
+    if counts is not None:
+        lst.count, lst.count_stride = _ptr(counts), 1
+    lst.K = n
+    return lst
+
+
+def _launch_on_image(timer_name, image, yuv, rgb_entry, yuv_entry, *tail):
+    """One launch of a kernel on the frames or planes of _image: the entry point for packed RGB frames or the one for
+    mydet_yuv420_src, each followed by the `tail` arguments and the stream, inside one TIMER span of `timer_name`."""
     t0 = TIMER.start() if TIMER else None
     if yuv is None:
-        B, H, W, _ = target.shape
-        code = _lib.lib().mydet_draw_boxes_rgb_u8(_ptr(target), B, H, W, target.stride(0), target.stride(1), ctypes.byref(lst), ctypes.byref(s),
-                                                  _stream())
-        name = 'mydet_draw_boxes_rgb_u8'
+        B, H, W, _ = image.shape
+        name = rgb_entry
+        code = getattr(_lib.lib(), name)(_ptr(image), B, H, W, image.stride(0), image.stride(1), *tail, _stream())
     else:
-        layout, m, full = yuv
-        B, H, W = target[0].shape
-        src = _yuv420_src(target, layout, m, full)
-        code = _lib.lib().mydet_draw_boxes_yuv420_u8(ctypes.byref(src), B, H, W, ctypes.byref(lst), ctypes.byref(s), _stream())
-        name = 'mydet_draw_boxes_yuv420_u8'
+        B, H, W = image[0].shape
+        name = yuv_entry
+        src = _yuv420_src(image, yuv[0], yuv[1], yuv[2])
+        code = getattr(_lib.lib(), name)(ctypes.byref(src), B, H, W, *tail, _stream())
     if t0:
-        TIMER.stop('draw_boxes', t0, float(B))
-    del keep
+        TIMER.stop(timer_name, t0, float(B))
     _lib.check(code, name)
 
 
-def _draw_dense(what, target, yuv, B, boxes, style, counts, scores, classes, ids):
+def _draw_launch(image, yuv, lst, style, dev):
+    s, keep = style.struct(dev)
+    _launch_on_image('draw_boxes', image, yuv, 'mydet_draw_boxes_rgb_u8', 'mydet_draw_boxes_yuv420_u8', ctypes.byref(lst), ctypes.byref(s))
+    del keep
+
+
+def _draw_dense(what, image, yuv, B, boxes, style, counts, scores, classes, ids):
     _draw_check_style(style, what)
-    boxes, counts, planes = _draw_rows(what, B, boxes, counts, scores, classes, ids)
-    tp = [target] if yuv is None else list(target)
-    dev = _draw_on_device(what, tp, [boxes, counts] + list(planes.values()))
+    boxes, counts, planes = _box_rows(what, B, boxes, counts, scores, classes, ids)
+    dev = _same_device(what, image, [boxes, counts] + list(planes.values()))
     K = boxes.shape[1]
     if K == 0:
         return
     boxes = boxes.contiguous()
-    sc, cl, idp = (None if t is None else t.contiguous() for t in (planes['scores'], planes['classes'], planes['ids']))
+    planes = {field: None if planes[name] is None else planes[name].contiguous()
+              for field, name in (('score', 'scores'), ('cls', 'classes'), ('id', 'ids'))}
     if counts is not None:
         counts = counts.contiguous()
-    width = boxes.shape[2]
     step = _lib.DRAW_MAX_BOXES
     for lo in reversed(range(0, K, step)):                           # rows K-1 .. 0 are the paint order: the last chunk first
         n = min(step, K - lo)
-        lst = _lib.DrawList()
-        lst.box, lst.box_frame_stride, lst.box_row_stride = boxes.data_ptr() + 4 * lo * width, K * width, width
-        if width == 5:
-            lst.angle, lst.angle_frame_stride, lst.angle_row_stride = boxes.data_ptr() + 4 * (lo * width + 4), K * width, width
-        for field, t, size in (('score', sc, 4), ('cls', cl, 8), ('id', idp, 8)):
-            if t is not None:
-                setattr(lst, field, t.data_ptr() + size * lo)
-                setattr(lst, field + '_frame_stride', K)
-                setattr(lst, field + '_row_stride', 1)
-        chunk_counts = None
-        if counts is not None:
-            chunk_counts = counts if K <= step else (counts - lo).clamp_(0, n).to(torch.int32)
-            lst.count, lst.count_stride = _ptr(chunk_counts), 1
-        lst.K = n
-        _draw_launch(target, yuv, lst, style, dev)
+        chunk_counts = counts if counts is None or K <= step else (counts - lo).clamp_(0, n).to(torch.int32)
+        _draw_launch(image, yuv, _list_of_rows(boxes, lo, n, chunk_counts, planes), style, dev)
         del chunk_counts
 
 
@@ -2185,8 +2233,8 @@ def draw_boxes(frames, boxes, style, counts=None, scores=None, classes=None, ids
     int32 [B], rows to draw per frame (None: all K; above K means K).  scores float32, classes, ids int64 [B,K]: what labels and
     colours read; None leaves that label part out (colour key 0).  Rows are painted K-1 down to 0, so row 0 ends up on top; more
     than 512 rows go in chunks that keep this order.  style: ops.draw_style(...).  Returns `frames`."""
-    fr = _draw_rgb_target('draw_boxes', frames)
-    _draw_dense('draw_boxes', fr, None, fr.shape[0], boxes, style, counts, scores, classes, ids)
+    what = 'draw_boxes'
+    _draw_dense(what, *_image(what, frames, None, None, None, True), boxes, style, counts, scores, classes, ids)
     return frames
 
 
@@ -2195,9 +2243,8 @@ def draw_boxes_yuv420(planes, layout, boxes, style, counts=None, scores=None, cl
     with planes (y [B,H,W], uv [B,ceil(H/2),ceil(W/2),2]), 'i420' with (y, u, v), 'yv12' with (y, v, u); uint8, packed samples,
     any row and frame strides; odd H and W are legal.  'p010' / 'i010' are not drawn into (ValueError).  matrix, full_range:
     how the colours become Y'CbCr (ops.rgb_to_yuv), the selectors of the input side.  Returns `planes`."""
-    m = yuv_matrix_id(matrix)
-    ts = _draw_yuv_target('draw_boxes_yuv420', planes, layout)
-    _draw_dense('draw_boxes_yuv420', ts, (layout, m, full_range), ts[0].shape[0], boxes, style, counts, scores, classes, ids)
+    what = 'draw_boxes_yuv420'
+    _draw_dense(what, *_image(what, planes, layout, matrix, full_range, True), boxes, style, counts, scores, classes, ids)
     return planes
 
 
@@ -2208,42 +2255,15 @@ def draw_records(target, rec, style, layout=None, matrix='bt601', full_range=Fal
     buffer (a ValueError for copies, as in track_frames).  ids: optional int64 [B,512].  Returns `target`."""
     what = 'draw_records'
     _draw_check_style(style, what)
-    if not isinstance(rec, dict) or 'records' not in rec or 'bbox' not in rec:
-        raise TypeError(f'{what}: rec is the dict of ops.record_views, got {type(rec).__name__}')
-    records = rec['records']
-    if not isinstance(records, torch.Tensor) or records.dtype != torch.int32 or records.dim() != 2 or \
-            records.shape[1] not in (_lib.REC_WORDS, _lib.REC_ROT_WORDS) or records.stride(1) != 1 or records.stride(0) < 0:
-        raise ValueError(f'{what}: int32 records [B, {_lib.REC_WORDS} | {_lib.REC_ROT_WORDS}] expected')
-    if rec['bbox'].data_ptr() != records.data_ptr() + 4 * _lib.REC_BBOX:
-        raise ValueError(f"{what}: the fields of this record dict are copies, not views of its 'records' buffer")
-    B = records.shape[0]
-    if layout is None:
-        tgt, yuv = _draw_rgb_target(what, target), None
-        tp = [tgt]
-    else:
-        m = yuv_matrix_id(matrix)
-        tgt = _draw_yuv_target(what, target, layout)
-        yuv, tp = (layout, m, full_range), tgt
-    if tp[0].shape[0] != B:
-        raise ValueError(f'{what}: {tp[0].shape[0]} frames and {B} records')
+    records = _record_buffer(what, rec)
+    image, yuv, B = _image(what, target, layout, matrix, full_range, True)
+    if B != records.shape[0]:
+        raise ValueError(f'{what}: {B} frames and {records.shape[0]} records')
     if ids is not None and (not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or tuple(ids.shape) != (B, _lib.REC_TOPK)):
         raise ValueError(f'{what}: ids is an int64 tensor [{B},{_lib.REC_TOPK}]')
-    dev = _draw_on_device(what, tp, [records, ids])
-    base, fs = records.data_ptr(), records.stride(0)
-    lst = _lib.DrawList()
-    lst.box, lst.box_frame_stride, lst.box_row_stride = base + 4 * _lib.REC_BBOX, fs, 4
-    if records.shape[1] == _lib.REC_ROT_WORDS:
-        lst.angle, lst.angle_frame_stride, lst.angle_row_stride = base + 4 * _lib.REC_ANGLE, fs, 1
-    lst.score, lst.score_frame_stride, lst.score_row_stride = base + 4 * _lib.REC_SCORE, fs, 1
-    lst.cls, lst.cls_frame_stride, lst.cls_row_stride = base + 4 * _lib.REC_CLASS, fs // 2, 1      # int64 elements: fs is even
-    if fs % 2:
-        raise ValueError(f'{what}: a record stride of an even number of words expected, got {fs}')
-    if ids is not None:
-        ids = ids.contiguous()
-        lst.id, lst.id_frame_stride, lst.id_row_stride = _ptr(ids), _lib.REC_TOPK, 1
-    lst.count, lst.count_stride = base + 4 * _lib.REC_COUNT, fs
-    lst.K = _lib.REC_TOPK
-    _draw_launch(tgt, yuv, lst, style, dev)
+    dev = _same_device(what, image, [records, ids])
+    ids = None if ids is None else ids.contiguous()
+    _draw_launch(image, yuv, _list_of_records(what, records, True, ids), style, dev)
     return target
 
 
@@ -2283,18 +2303,6 @@ def crop_settings(what, size, max_per_frame, pad, fill, out, input_format):
     return (ch, cw), max_per_frame, pad, fill, out == 'input', input_format
 
 
-def _crop_rgb_source(what, frames):
-    """uint8 frames [B,H,W,3] or [H,W,3] as the view the kernel reads: in place when pixels are packed, else one copy."""
-    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
-        raise TypeError(f'{what}: uint8 frames expected, got {frames.dtype if isinstance(frames, torch.Tensor) else type(frames).__name__}')
-    fr = frames.unsqueeze(0) if frames.dim() == 3 else frames
-    if fr.dim() != 4 or fr.shape[3] != 3 or min(fr.shape) < 1:
-        raise ValueError(f'{what}: frames of shape [B,H,W,3] or [H,W,3] expected, got {tuple(frames.shape)}')
-    if fr.stride(3) != 1 or fr.stride(2) != 3 or fr.stride(1) < 3 * fr.shape[2] or fr.stride(0) < 0:
-        fr = fr.contiguous()
-    return fr
-
-
 def _crop_dst(what, dst, B, M, chip, f32, dev):
     """The chip tensor: zeros when dst is None; else dst checked -- [B,M,ch,cw,3] uint8 or [B,M,3,ch,cw] float32 on `dev`, every
     chip contiguous, any non-negative slot and frame strides."""
@@ -2314,51 +2322,27 @@ def _crop_dst(what, dst, B, M, chip, f32, dev):
     return dst
 
 
-def _crop_launch(source, yuv, lst, settings, M, dst):
-    """One launch: source = the [B,H,W,3] frames or the checked planes; yuv = None or (layout, matrix id, full_range)."""
+def _crop_launch(image, yuv, lst, settings, M, dst):
     chip, _, pad, fill, f32, input_format = settings
     o = _lib.CropOut()
     o.ch, o.cw, o.M, o.kind, o.pad = chip[0], chip[1], M, _lib.CROP_F32 if f32 else _lib.CROP_U8, pad
     o.fill[0], o.fill[1], o.fill[2] = fill
     o.norm, o.mean3, o.std3 = _norm_args(input_format)
     o.out, o.slot_stride, o.frame_stride = dst.data_ptr(), dst.stride(1), dst.stride(0)
-    t0 = TIMER.start() if TIMER else None
-    if yuv is None:
-        B, H, W, _ = source.shape
-        code = _lib.lib().mydet_crop_boxes_rgb(_ptr(source), B, H, W, source.stride(0), source.stride(1), ctypes.byref(lst), ctypes.byref(o),
-                                               _stream())
-        name = 'mydet_crop_boxes_rgb'
-    else:
-        layout, m, full = yuv
-        B, H, W = source[0].shape
-        src = _yuv420_src(source, layout, m, full)
-        code = _lib.lib().mydet_crop_boxes_yuv420(ctypes.byref(src), B, H, W, ctypes.byref(lst), ctypes.byref(o), _stream())
-        name = 'mydet_crop_boxes_yuv420'
-    if t0:
-        TIMER.stop('crop_boxes', t0, float(B))
-    _lib.check(code, name)
+    _launch_on_image('crop_boxes', image, yuv, 'mydet_crop_boxes_rgb', 'mydet_crop_boxes_yuv420', ctypes.byref(lst), ctypes.byref(o))
 
 
-def _crop_dense(what, source, yuv, B, boxes, settings, counts, dst):
-    boxes, counts, _ = _draw_rows(what, B, boxes, counts, None, None, None)
-    tp = [source] if yuv is None else list(source)
-    dev = _draw_on_device(what, tp, [boxes, counts])
+def _crop_dense(what, image, yuv, B, boxes, settings, counts, dst):
+    boxes, counts, _ = _box_rows(what, B, boxes, counts, None, None, None)
+    dev = _same_device(what, image, [boxes, counts])
     K = min(boxes.shape[1], _lib.DRAW_MAX_BOXES)                     # rows past the launch's 512 get no chip
     M = settings[1] if settings[1] is not None else K
     dst = _crop_dst(what, dst, B, M, settings[0], settings[4], dev)
     if K == 0 or M == 0:
         return dst
     boxes = boxes.contiguous()
-    width, rows = boxes.shape[2], boxes.shape[1]
-    lst = _lib.DrawList()
-    lst.box, lst.box_frame_stride, lst.box_row_stride = boxes.data_ptr(), rows * width, width
-    if width == 5:
-        lst.angle, lst.angle_frame_stride, lst.angle_row_stride = boxes.data_ptr() + 16, rows * width, width
-    if counts is not None:
-        counts = counts.contiguous()
-        lst.count, lst.count_stride = _ptr(counts), 1
-    lst.K = K
-    _crop_launch(source, yuv, lst, settings, M, dst)
+    counts = None if counts is None else counts.contiguous()
+    _crop_launch(image, yuv, _list_of_rows(boxes, 0, K, counts, {}), settings, M, dst)
     return dst
 
 
@@ -2375,8 +2359,7 @@ def crop_boxes(frames, boxes, size, counts=None, max_per_frame=None, pad=1.0, fi
     any slot and frame strides): only chips m < min(count, K, M) are written; without it the chips are new and the others zero."""
     what = 'crop_boxes'
     settings = crop_settings(what, size, max_per_frame, pad, fill, out, input_format)
-    fr = _crop_rgb_source(what, frames)
-    return _crop_dense(what, fr, None, fr.shape[0], boxes, settings, counts, dst)
+    return _crop_dense(what, *_image(what, frames, None, None, None, False), boxes, settings, counts, dst)
 
 
 def crop_boxes_yuv420(planes, layout, boxes, size, counts=None, max_per_frame=None, pad=1.0, fill=(0, 0, 0), out='uint8', input_format=None,
@@ -2385,11 +2368,8 @@ def crop_boxes_yuv420(planes, layout, boxes, size, counts=None, max_per_frame=No
     yuv420_to_rgb(planes, layout, matrix, full_range), which is never built.  planes, layout, matrix, full_range as in
     yuv420_to_rgb: every layout, the 10-bit ones included, odd H and W.  fill is an RGB colour."""
     what = 'crop_boxes_yuv420'
-    yuv420_layout(layout)
-    m = yuv_matrix_id(matrix)
     settings = crop_settings(what, size, max_per_frame, pad, fill, out, input_format)
-    ts, _ = _yuv420_planes(planes, layout, what)
-    return _crop_dense(what, ts, (layout, m, full_range), ts[0].shape[0], boxes, settings, counts, dst)
+    return _crop_dense(what, *_image(what, planes, layout, matrix, full_range, False), boxes, settings, counts, dst)
 
 
 def crop_records(source, rec, size, layout=None, max_per_frame=None, pad=1.0, fill=(0, 0, 0), out='uint8', input_format=None, dst=None,
@@ -2401,34 +2381,12 @@ def crop_records(source, rec, size, layout=None, max_per_frame=None, pad=1.0, fi
     m.  Everything else as in crop_boxes."""
     what = 'crop_records'
     settings = crop_settings(what, size, max_per_frame, pad, fill, out, input_format)
-    if not isinstance(rec, dict) or 'records' not in rec or 'bbox' not in rec:
-        raise TypeError(f'{what}: rec is the dict of ops.record_views, got {type(rec).__name__}')
-    records = rec['records']
-    if not isinstance(records, torch.Tensor) or records.dtype != torch.int32 or records.dim() != 2 or \
-            records.shape[1] not in (_lib.REC_WORDS, _lib.REC_ROT_WORDS) or records.stride(1) != 1 or records.stride(0) < 0:
-        raise ValueError(f'{what}: int32 records [B, {_lib.REC_WORDS} | {_lib.REC_ROT_WORDS}] expected')
-    if rec['bbox'].data_ptr() != records.data_ptr() + 4 * _lib.REC_BBOX:
-        raise ValueError(f"{what}: the fields of this record dict are copies, not views of its 'records' buffer")
-    B = records.shape[0]
-    if layout is None:
-        src, yuv = _crop_rgb_source(what, source), None
-        tp = [src]
-    else:
-        yuv420_layout(layout)
-        m = yuv_matrix_id(matrix)
-        src, _ = _yuv420_planes(source, layout, what)
-        yuv, tp = (layout, m, full_range), src
-    if tp[0].shape[0] != B:
-        raise ValueError(f'{what}: {tp[0].shape[0]} frames and {B} records')
-    dev = _draw_on_device(what, tp, [records])
+    records = _record_buffer(what, rec)
+    image, yuv, B = _image(what, source, layout, matrix, full_range, False)
+    if B != records.shape[0]:
+        raise ValueError(f'{what}: {B} frames and {records.shape[0]} records')
+    dev = _same_device(what, image, [records])
     M = settings[1] if settings[1] is not None else _lib.REC_TOPK
     dst = _crop_dst(what, dst, B, M, settings[0], settings[4], dev)
-    base, fs = records.data_ptr(), records.stride(0)
-    lst = _lib.DrawList()
-    lst.box, lst.box_frame_stride, lst.box_row_stride = base + 4 * _lib.REC_BBOX, fs, 4
-    if records.shape[1] == _lib.REC_ROT_WORDS:
-        lst.angle, lst.angle_frame_stride, lst.angle_row_stride = base + 4 * _lib.REC_ANGLE, fs, 1
-    lst.count, lst.count_stride = base + 4 * _lib.REC_COUNT, fs
-    lst.K = _lib.REC_TOPK
-    _crop_launch(src, yuv, lst, settings, M, dst)
+    _crop_launch(image, yuv, _list_of_records(what, records, False, None), settings, M, dst)
     return dst

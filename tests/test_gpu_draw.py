@@ -413,3 +413,44 @@ def test_annotate_frames_nv12_and_detect_one_return_img(detector):
     assert np.array_equal(np_img, _drawn_from_objects(frames[:1], [dts], st)[0].cpu().numpy())
     with pytest.raises(NotImplementedError):
         det.detect_one(pil_img=img, show_img=True, **kw)
+
+
+def test_annotate_and_crop_launch_what_predict_launches_plus_one(detector):
+    """What the docstrings of annotate_frames* and crop_frames* promise, in the launch counts of an ops.KernelTimer: each call
+    is its predict_frames* call plus ONE 'draw_boxes' / 'crop_boxes' launch -- RGB and NV12; plain, tiled and tracked -- and
+    the tracked predict_frames* is the untracked one plus ONE 'track_frames'."""
+    from mydetection_amd import ops
+    from mydetection_amd.api import Tiles, Tracker
+    det = detector
+    kw = dict(input_size=128, conf_thres=0.001)
+    frames = _frames(2, 150, 200, seed=90)
+    y, uv = np.ascontiguousarray(frames[:, :, :, 0]), np.full((2, 75, 100, 2), 128, np.uint8)
+
+    def launches(method, *args, **extra):
+        ops.TIMER = ops.KernelTimer()
+        method(*args, **kw, **extra)
+        torch.cuda.synchronize()
+        return {name: n for name, (n, _, _) in ops.TIMER.summary().items()}
+
+    def plus(counts, name):
+        assert name not in counts
+        return dict(counts, **{name: 1})
+
+    modes = {'plain': dict, 'tiled': lambda: {'tiles': Tiles((96, 128), overlap=0.25)},
+             'tracked': lambda: {'tracker': Tracker(min_score=0.0005)}}     # synthetic weights: keep the low scores alive
+    graph, timer = det.use_graph, ops.TIMER
+    det.use_graph = False
+    try:
+        predicted = {}
+        for mode, extra in modes.items():
+            rgb = predicted[mode, 'rgb'] = launches(det.predict_frames, frames, **extra())
+            assert launches(det.annotate_frames, frames, **extra()) == plus(rgb, 'draw_boxes'), mode
+            assert launches(det.crop_frames, frames, **extra()) == plus(rgb, 'crop_boxes'), mode
+            nv12 = predicted[mode, 'nv12'] = launches(det.predict_frames_nv12, y, uv, **extra())
+            assert launches(det.annotate_frames_nv12, y, uv, **extra()) == plus(nv12, 'draw_boxes'), mode
+            assert launches(det.crop_frames_nv12, y, uv, **extra()) == plus(nv12, 'crop_boxes'), mode
+        for fmt in ('rgb', 'nv12'):
+            assert predicted['tracked', fmt] == plus(predicted['plain', fmt], 'track_frames')
+            assert predicted['tiled', fmt]['merge_tile_records'] == 1 and 'merge_tile_records' not in predicted['plain', fmt]
+    finally:
+        det.use_graph, ops.TIMER = graph, timer

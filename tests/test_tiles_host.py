@@ -222,6 +222,16 @@ def test_detector_rejects_bad_tiled_calls_before_any_gpu_work():
         det.frames_nv12_to_json(y, uv, [0, 1], tiles=Tiles((64, 96), metric='ios'), rotated_nms=True)
     with pytest.raises(TypeError, match='Tiles'):
         det.frames_yuv_to_json((y, uv), 'nv12', [0, 1], tiles=(64, 96))
+    # an empty batch (the last one of a video reader) is no error without tiles: nothing in, nothing out
+    assert det.predict_frames([]) == [] and det.frames_to_json([], []) == []
+    with pytest.raises(ValueError, match='one size'):
+        det.predict_frames([], tiles=Tiles((96, 128)))
+    # the argument rules come before any attribute of the detector is read
+    from mydetection_amd.api import Detector
+    with pytest.raises(TypeError, match='Tiles'):
+        Detector.__new__(Detector).predict_frames(a, tiles='x')
+    with pytest.raises(TypeError, match='tracker'):
+        Detector.__new__(Detector).annotate_frames(np.zeros((8, 8, 3), np.float32), tracker='x')
 
 
 def test_merge_tile_records_has_no_cpu_path():
