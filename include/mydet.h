@@ -62,6 +62,10 @@ int mydet_abi_version(void);
  * Also covers: MBConv expand/project convs (external/efficientnet/model.py:75,85), BiFPN
  * input projections (models/fpns.py:446-448), SeparableConv2d.pointwise (models/modules.py:20),
  * C6/C7 convs (models/backbones.py:183-200), dense cls_last conv (models/rpns.py:155-158).
+ * Size limits (32-bit byte offsets; MYDET_E_UNSUPP beyond, nothing launched): the WHOLE output B*Ho*Wo*ldy*4, the whole
+ * residual B*Ho*Wo*ldr*4 and the gate B*Cin*4 below 2^31 - 16 bytes (a 64-channel 320x320 output: up to batch 81); the input may be
+ * larger -- only H*W*ldx*4 * (256 / (Ho*Wo) + 2), the images one tile can touch, must stay below 2^31 - 16; B*Ho*Wo <= 2^30.
+ * The same limits hold for mydet_conv2d_igemm_b3_f32 and mydet_conv1x1_upcat_f32 (both of its inputs as windows).
  */
 int mydet_conv2d_igemm_f32(const float *x, int64_t ldx, const float *w,
                            const float *scale, const float *shift,
@@ -85,6 +89,9 @@ int mydet_conv2d_igemm_f32(const float *x, int64_t ldx, const float *w,
  *    was cut leave partial outputs here and a fixup launch sums them in K order (deterministic).
  * Needs Cin % 8 == 0, Cout % 4 == 0, ldy % 4 == 0 (ldr % 4 == 0), 16-byte aligned pointers; otherwise
  * MYDET_E_UNSUPP and the caller uses mydet_conv2d_igemm_f32.
+ * Size limit (32-bit byte offsets inside a workgroup's window; MYDET_E_UNSUPP beyond): input, output and residual may be of any
+ * size, but H*W*max(ldx, ldy, ldr)*4 * (64 / (tiles per image) + 2) -- the images the 64 2x2-output tiles of one workgroup can
+ * touch -- must stay below 2^31 - 16 bytes; B * tiles per image <= 2^30.
  */
 int64_t mydet_wino_weights_floats(int Cout, int Cin);
 int mydet_wino_weights_f32(const float *w_ohwi, int Cout, int Cin, float *u, void *stream);
@@ -125,6 +132,8 @@ int mydet_conv2d_stem_f32(const float *x, int64_t sxb, int64_t sxc, int64_t sxh,
  * external/efficientnet/model.py:81) without another pass over y; deterministic (no atomics).
  * S must be mydet_dwconv_slices(Ho, Wo, C, K, stride): the number of slices the kernel chosen for the layer writes
  * (one per 8 x 16 output tile for the LDS-tiled stride-1 kernel, which takes the layers of 32 channels and more).
+ * Sizes: x and y are addressed with 64-bit offsets (no byte limit); with se_partial or an in-launch tail the grid has one row per
+ * image and B <= 65535 (MYDET_E_BADARG beyond) -- mydet_channel_sums_f32 and mydet_se_gate_f32 likewise.
  */
 /* Squeeze-excite tail inside the launch that produces the depthwise output (optional last argument of mydet_dwconv_f32,
  * mydet_mbconv_expand_dw_f32, mydet_stem_dw_f32; NULL = none).  The launch then also writes
@@ -233,6 +242,8 @@ int mydet_conv2d_igemm_b3_f32(const float *x, int64_t ldx, const uint16_t *w_pla
  * (tap, slab): results equal the other kernels' to float32 round-off (tests: 2e-5 * max|y| against float64).
  *   y = act((conv3x3(x) * scale + shift)) + residual,  Ho = (H - 1) / stride + 1, Wo likewise;  act: MYDET_ACT_NONE | _LEAKY.
  * Cin % 16 == 0, ldx % 4 == 0; MYDET_E_UNSUPP otherwise (the caller then uses mydet_conv2d_igemm_b3_f32 / _igemm_f32).
+ * Size limits (descriptors per image; MYDET_E_UNSUPP beyond): (H+1)*(W+1)*ldx*4 and Ho*Wo*max(ldy, ldr)*4 at most 2^31 - 16 bytes,
+ * fewer than 2^31 workgroups; the batch may carry every tensor past 4 GiB.  mydet_conv_stem_p3_f32: the same for its output.
  * Replaces the ATen chain of models/modules.py:76-95 for the stride-2 ConvBnLeaky layers of models/backbones.py:14-30 and the
  * 32 -> 64 layer of the first DarkBlock (models/modules.py:56-73). */
 int mydet_conv3x3_p3_f32(const float *x, int64_t ldx, const uint16_t *w_planes, const float *scale, const float *shift,
@@ -548,6 +559,8 @@ int mydet_track_frames_f32(const int32_t *records, int64_t stream_stride_words, 
  * of the chip plus a small remainder, the remainder runs as K pieces that a fourth launch sums in K order -- deterministic);
  * stream-ordered, so one buffer serves every layer of a stream.
  * MYDET_E_UNSUPP (-2) for shapes it does not cover: the caller then uses mydet_conv2d_wino_f32 / _igemm_f32.
+ * Size limit: as mydet_conv2d_wino_f32 with 32 tiles of 4x4 outputs per workgroup -- H*W*max(ldx, ldy, ldr)*4 * (32 / (tiles per
+ * image) + 2) below 2^31 - 16 bytes; tensors and the workspace (about 2.25 x the input) may pass 4 GiB.
  * Replaces the same reference code as mydet_conv2d_igemm_f32 (models/modules.py:69-73,94-95). */
 int64_t mydet_wino4_weights_floats(int Cout, int Cin);
 int mydet_wino4_weights_f32(const float *w, int Cout, int Cin, float *u, void *stream);

@@ -1184,6 +1184,7 @@ extern "C" int mydet_conv2d_igemm_f32(const float *x, int64_t ldx, const float *
     ConvArgs a;
     if (a_gate && (KH != 1 || KW != 1 || stride != 1 || act != MYDET_ACT_NONE || ((uintptr_t)a_gate & 15)))
         return MYDET_E_UNSUPP;
+    if (a_gate && (int64_t)B * Cin * 4 >= 0x7FFFFFF0ll) return MYDET_E_UNSUPP;      // gate[B][Cin] is read through one descriptor
     a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.res = residual; a.gate = a_gate; a.y = y;
     a.ldx = ldx; a.ldr = ldr; a.ldy = ldy;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride;
@@ -1277,6 +1278,7 @@ extern "C" int mydet_conv2d_igemm_b3_f32(const float *x, int64_t ldx, const uint
     const int64_t span_imgs = 256 / ((int64_t)Ho * Wo) + 2;
     if (M64 * ldy * 4 >= 0x7FFFFFF0ll || (residual && M64 * ldr * 4 >= 0x7FFFFFF0ll)) return MYDET_E_UNSUPP;
     if (KH * KW > 31 || img_bytes * span_imgs >= 0x7FFFFFF0ll || mydet_split_bf16_elems(Cout, (int)K64) * 2 >= 0x7FFFFFF0ll) return MYDET_E_UNSUPP;
+    if (a_gate && (int64_t)B * Cin * 4 >= 0x7FFFFFF0ll) return MYDET_E_UNSUPP;      // gate[B][Cin] is read through one descriptor
     ConvArgs a;
     a.x = x; a.w = nullptr; a.scale = scale; a.shift = shift; a.res = residual; a.gate = a_gate; a.y = y;
     a.ldx = ldx; a.ldr = ldr; a.ldy = ldy;

@@ -380,6 +380,44 @@ def split_bf16(w_ohwi):
     return out
 
 
+# The conv kernels address their tensors through buffer descriptors with 32-bit byte offsets (csrc/common.h: mydet_rsrc covers at
+# most this many bytes, 16 short of 2 GiB); each launcher refuses (MYDET_E_UNSUPP) what its offsets cannot reach -- INTEGRATION.md,
+# "Limits the reference does not have"
+CONV_OFFSET_LIMIT = 0x7FFFFFF0
+
+
+def conv_size_refusals(family, B, H, W, Ho, Wo, ldx, ldy, ldr=0):
+    """The size rules of one conv launcher that a layer breaks: [(tensor, bytes, rule)], empty when its size is not the reason of a
+    refusal.  family: 'igemm' (mydet_conv2d_igemm_f32 / _b3_f32: the whole output and residual, and the input images one 256-row tile
+    can touch), 'wino' / 'wino4' (mydet_conv2d_wino_f32 / _wino4_f32: the images of any of the three tensors that one workgroup's
+    64 / 32 tiles can touch).  ldr = 0: no residual."""
+    out = []
+    if family == 'igemm':
+        for name, ld in (('output', ldy), ('residual', ldr)):
+            if B * Ho * Wo * ld * 4 >= CONV_OFFSET_LIMIT:
+                out.append((name, B * Ho * Wo * ld * 4, f'the whole {name} of the direct implicit GEMM must stay below {CONV_OFFSET_LIMIT} bytes (2 GiB - 16)'))
+        span = 256 // (Ho * Wo) + 2
+        if H * W * ldx * 4 * span >= CONV_OFFSET_LIMIT:
+            out.append(('input', H * W * ldx * 4 * span, f'the {span} input images one 256-row tile can touch must stay below {CONV_OFFSET_LIMIT} bytes'))
+    else:
+        tiles, t = (64, 2) if family == 'wino' else (32, 4)
+        span = tiles // (-(-H // t) * -(-W // t)) + 2
+        for name, ld in (('input', ldx), ('output', ldy), ('residual', ldr)):
+            if H * W * ld * 4 * span >= CONV_OFFSET_LIMIT:
+                out.append((name, H * W * ld * 4 * span, f'the {span} {name} images one workgroup of {tiles} tiles can touch must stay below {CONV_OFFSET_LIMIT} bytes'))
+    return out
+
+
+def _check_conv(code, entry, family, *shape):
+    """_lib.check for a conv entry; a refusal (MYDET_E_UNSUPP) that the tensors' sizes explain names the limit and the byte size."""
+    if code == -2:
+        broken = conv_size_refusals(family, *shape)
+        if broken:
+            raise _lib.MydetError(f'{entry} failed: unsupported configuration: ' +
+                                  '; '.join(f'{name}: {nbytes} bytes, {rule}' for name, nbytes, rule in broken))
+    _lib.check(code, entry)
+
+
 def conv2d(x, w_ohwi, scale, shift, k, stride, pad, act, residual=None, out=None, out_ld=None, gate=None, wino=None,
            wino4=None, interior=None, b3=None, b3_min_rows=None):
     """y = act(conv(x * gate)*scale + shift) + residual.  x logical [B,Cin,H,W]; pad=(top,left,bottom,right);
@@ -424,7 +462,7 @@ def conv2d(x, w_ohwi, scale, shift, k, stride, pad, act, residual=None, out=None
             name = f'conv_wino4 {Cin}->{Cout} k3s1 {H}x{W}' if TIMER_DETAIL else 'conv_wino4'
             TIMER.stop(name, t0, 2.0 * B * Ho * Wo * Cout * 9 * Cin,
                        4.0 * (B * H * W * Cin + B * Ho * Wo * Cout * (2 if residual is not None else 1) + 9 * Cin * Cout))
-        _lib.check(code, 'mydet_conv2d_wino4_f32')
+        _check_conv(code, 'mydet_conv2d_wino4_f32', 'wino4', B, H, W, Ho, Wo, ldx, ldy, ldr)
         return out
     if (wino is not None and WINOGRAD and gate is None and k == 3 and stride == 1 and tuple(pad) == (1, 1, 1, 1)
             and ldy % 4 == 0 and ldr % 4 == 0):
@@ -437,7 +475,7 @@ def conv2d(x, w_ohwi, scale, shift, k, stride, pad, act, residual=None, out=None
             name = f'conv_wino {Cin}->{Cout} k3s1 {H}x{W}' if TIMER_DETAIL else 'conv_wino'
             TIMER.stop(name, t0, 2.0 * B * Ho * Wo * Cout * 9 * Cin,
                        4.0 * (B * H * W * Cin + B * Ho * Wo * Cout * (2 if residual is not None else 1) + 9 * Cin * Cout))
-        _lib.check(code, 'mydet_conv2d_wino_f32')
+        _check_conv(code, 'mydet_conv2d_wino_f32', 'wino', B, H, W, Ho, Wo, ldx, ldy, ldr)
         return out
     ws = conv_workspace(x.device)
     if (b3 is not None and b3_takes(B * Ho * Wo, Cin, Cout, k, b3_min_rows, min_cout=B3_GATED_MIN_COUT if gate is not None else 128)
@@ -465,7 +503,7 @@ def conv2d(x, w_ohwi, scale, shift, k, stride, pad, act, residual=None, out=None
         b_rest = 4.0 * (k * k * Cin * Cout) + (b_out if residual is not None else 0.0)
         TIMER.stop(name, t0, 2.0 * B * Ho * Wo * Cout * k * k * Cin, b_in + b_out + b_rest,
                    (0.0 if interior == 'in' else b_in) + (0.0 if interior == 'out' else b_out) + b_rest)
-    _lib.check(code, 'mydet_conv2d_igemm_f32')
+    _check_conv(code, 'mydet_conv2d_igemm_f32', 'igemm', B, H, W, Ho, Wo, ldx, ldy, ldr)
     return out
 
 
