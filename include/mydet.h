@@ -983,6 +983,99 @@ int mydet_crop_boxes_rgb(const unsigned char *src, int B, int H, int W, int64_t 
 int mydet_crop_boxes_yuv420(const mydet_yuv420_src *src, int B, int H, int W,
                             const mydet_draw_list *list, const mydet_crop_out *out, void *stream);
 
+/* Scoring detections against ground truth: COCO's bbox evaluation with useCats = 1, in three stream-ordered launches
+ * (csrc/evalmatch.hip).  Replaces utils/evaluation/coco.py (coco_evaluate_bbox, myCOCOeval) and utils/evaluation/cepdof.py
+ * (evaluate_json, CEPDOFeval) of the reference, which sit on pycocotools: its computeIoU, evaluateImg and accumulate.  The
+ * summary (12 stats and the text) is host code.  Defaults: iouThrs = np.linspace(.5, .95, 10), recThrs = np.linspace(0, 1, 101),
+ * maxDets = [1, 10, 100], areaRng = [[0, 1e10], [0, 32^2], [32^2, 96^2], [96^2, 1e10]]; every threshold array is computed by
+ * numpy on the host and passed in as float64 through a HOST pointer, so the bits are numpy's.
+ *
+ * Packing (host side; mydetection_amd.ops.eval_pack).
+ *   Images are indexed i in the order of the sorted unique image ids of the ground truth, categories k in the order of its sorted
+ *   unique category ids.  A group is one (image, category) pair, g = k*I + i (category-major).  Detections whose image or
+ *   category id is not in the ground truth are dropped.  Per group the detections are in (score descending, input order) order
+ *   (a stable sort) and cut to maxDets[-1]; the ground truths keep annotation order.  Dense arrays, D detections, G ground truths:
+ *     dt_start, gt_start  int32 [I*K + 1]          rows of group g: [start[g], start[g + 1])
+ *     dt_score, dt_area   float64 [D];  gt_area float64 [G]
+ *     gt_flags            uint8 [G]: bit 0 (MYDET_EVAL_GT_IGNORE) ignore, bit 1 (MYDET_EVAL_GT_CROWD) iscrowd
+ *     boxes               float64 (x, y, w, h) rows, rotated == 0;  float32 (cx, cy, w, h, deg) rows, rotated == 1
+ *     groups              int32 [n_groups]: the groups that hold a detection or a ground truth, ascending (the launches run
+ *                         over these only: I*K may be 400 000 with most groups empty)
+ *     pair_start          int64 [n_groups + 1]: listed group c owns IoU entries [pair_start[c], pair_start[c + 1]), Dg*Gg of them,
+ *                         detection-major: entry pair_start[c] + d*Gg + j is (detection of rank d, ground truth j)
+ *   Defaults.  coco: gt.ignore = iscrowd; dt.area = w*h if absent.  cepdof: gt.area = w*h if absent, gt.ignore = ignore or
+ *   iscrowd, dt.area = w*h if absent, dt.category_id = 1 if absent.
+ *   order int32 [D] is the per-category global order: category k's detections, order[cat_start[k] .. cat_start[k + 1]), sorted by
+ *   (score descending, image index ascending, rank in group ascending); dt_rank int32 [D] is a detection's rank in its group.
+ *
+ * IoU (mydet_eval_ious_f64): one thread per pair, float64 [n_pairs] out; it is also what pycocotools keeps as `ious`.
+ *   Axis-aligned, all float64 and uncontracted, in this order: da = dw*dh, ga = gw*gh; w = fmin(dx+dw, gx+gw) - fmax(dx, gx), if
+ *   w <= 0 the IoU is 0; h likewise, if h <= 0 the IoU is 0; i = w*h; u = da for a crowd ground truth, else da + ga - i;
+ *   iou = i/u.
+ *   Rotated: the float32 IoU of mydet_rotated_iou_f32 (a = the detection, b = the ground truth) widened to float64.  Crowd flags
+ *   do not change it (the reference passes iscrowd = 0 there).  This is the exact-area deviation from the reference's rasterised
+ *   iou_rle, the same one as for the rotated NMS.
+ *
+ * Matching (mydet_eval_match_f64): per group, per area range a = (lo_a, hi_a) and per threshold t, independently.
+ *   gtIg[j] = ignore[j] or area[j] < lo_a or area[j] > hi_a.  Ground truths are visited in (gtIg ascending, annotation order)
+ *   order, detections in rank order.  For a detection, start with best = min(t, 1 - 1e-10) and m = none; for every ground truth
+ *   j in that order: skip j if it is already matched at (a, t) and is not crowd; stop if m is set, gtIg[m] == 0 and gtIg[j] == 1;
+ *   skip j if iou[d, j] < best; otherwise best = iou[d, j], m = j (an equal IoU moves the match to the later ground truth).  If m
+ *   is set the detection is matched at (a, t), its ignore flag is gtIg[m], and m is marked matched.  Afterwards an unmatched
+ *   detection is ignored if dt_area < lo_a or dt_area > hi_a.
+ *   Outputs: dt_matched, dt_ignored uint32 [A][D], bit t = matched / ignored at (a, t); dt_gt (may be NULL) int32 [A][T][D], the
+ *   matched ground-truth row (an index into the G rows) or -1.  Rows of detections are written for every listed group.
+ *
+ * Accumulating (mydet_eval_accumulate_f64): per (k, a, m), the detections of category k in `order` with rank < maxDets[m].
+ *   npig = the number of ground truths of the category with gtIg == 0; if npig == 0, precision, recall and scores are -1.
+ *   Otherwise, per t: tp and fp are the cumulative integer counts of (matched and not ignored) and (not matched and not
+ *   ignored); in float64 rc = tp/npig and pr = tp/(fp + tp + 2^-52); pr[i] becomes max(pr[i:]); recall = rc[-1], or 0 without
+ *   detections; for each recall threshold r, p is the first index with rc[p] >= recThrs[r], precision = pr[p] and score =
+ *   dt_score[order[p]], both 0 when there is no such index.
+ *   Outputs, every element written: precision [T,R,K,A,M], recall [T,K,A,M], scores [T,R,K,A,M], float64 -- the reference's
+ *   eval['precision' | 'recall' | 'scores'].
+ *
+ * Every pointer of mydet_eval_set and every array argument below is a DEVICE pointer, except iou_thrs, area_rng ([A][2]: lo, hi),
+ * max_dets and rec_thrs, which are HOST pointers read before the launch.
+ * MYDET_E_BADARG, nothing launched -- all three: a null set; rotated not 0 | 1; I or K < 1 or I*K beyond int32; a negative
+ *   count; D or G beyond int32; n_groups > I*K, or 0 with D > 0 or G > 0; max_dt > D, max_gt > G, n_pairs > D*G; a null dt_start or
+ *   gt_start; null groups / pair_start with n_groups > 0; a null detection array with D > 0 or ground-truth array with G > 0; a
+ *   null output that would be written.  match and accumulate: T, A (M, R) < 1; a null threshold array; a NaN IoU threshold; an
+ *   area range with lo > hi or a NaN; maxDets not ascending or < 1; recThrs not ascending or NaN; null order, dt_rank or masks with
+ *   D > 0; a null cat_start.
+ * MYDET_E_UNSUPP, nothing launched: max_gt > MYDET_EVAL_MAX_GT (ground truths of one group); max_dt or maxDets[-1] >
+ *   MYDET_EVAL_MAX_DT; T > MYDET_EVAL_MAX_THRS (the masks are 32 bits); A > MYDET_EVAL_MAX_AREAS; M > MYDET_EVAL_MAX_DETS;
+ *   R > MYDET_EVAL_MAX_RECS.  A group whose table holds more ground truths than max_gt promised is left unwritten by the matcher.
+ * No launch needs scratch memory or a workspace.  D == 0: ious and match return 0 at once; accumulate still writes its outputs. */
+#define MYDET_EVAL_MAX_GT    1024
+#define MYDET_EVAL_MAX_DT    1024
+#define MYDET_EVAL_MAX_THRS  32
+#define MYDET_EVAL_MAX_AREAS 8
+#define MYDET_EVAL_MAX_DETS  8
+#define MYDET_EVAL_MAX_RECS  128
+#define MYDET_EVAL_GT_IGNORE 1
+#define MYDET_EVAL_GT_CROWD  2
+typedef struct mydet_eval_set {
+    int rotated;                     /* 0: float64 (x, y, w, h) boxes; 1: float32 (cx, cy, w, h, deg) boxes */
+    int I, K;                        /* images, categories */
+    int n_groups;                    /* listed (non-empty) groups */
+    int max_dt, max_gt;              /* the largest detection / ground-truth count of one group */
+    int64_t D, G, n_pairs;           /* detections, ground truths, IoU entries (pair_start[n_groups]) */
+    const int32_t *groups;
+    const int32_t *dt_start, *gt_start;
+    const int64_t *pair_start;
+    const void *dt_box, *gt_box;
+    const double *dt_score, *dt_area, *gt_area;
+    const unsigned char *gt_flags;
+} mydet_eval_set;
+int mydet_eval_ious_f64(const mydet_eval_set *set, double *ious, void *stream);
+int mydet_eval_match_f64(const mydet_eval_set *set, const double *ious, const double *iou_thrs, int T, const double *area_rng, int A,
+                         uint32_t *dt_matched, uint32_t *dt_ignored, int32_t *dt_gt, void *stream);
+int mydet_eval_accumulate_f64(const mydet_eval_set *set, const int32_t *order, const int32_t *cat_start, const int32_t *dt_rank,
+                              const uint32_t *dt_matched, const uint32_t *dt_ignored, int T, const double *area_rng, int A,
+                              const int32_t *max_dets, int M, const double *rec_thrs, int R, double *precision, double *recall,
+                              double *scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

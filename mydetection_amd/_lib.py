@@ -101,6 +101,10 @@ SIGNATURES = {
     'mydet_draw_boxes_yuv420_u8': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_crop_boxes_rgb': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr],
     'mydet_crop_boxes_yuv420': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
+    'mydet_eval_ious_f64': [c_ptr, c_ptr, c_ptr],
+    'mydet_eval_match_f64': [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_eval_accumulate_f64': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr,
+                                  c_ptr, c_ptr],
     'mydet_cxcywh_to_x1y1x2y2_f32': [c_ptr, c_ptr, c_i64, c_int, c_ptr],
     'mydet_bboxes_to_original_f32': [c_ptr, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr],
 }
@@ -134,6 +138,9 @@ DRAW_LABEL_CLASS, DRAW_LABEL_SCORE, DRAW_LABEL_ID = 1, 2, 4
 # object chips (mydet_crop_boxes_*): MYDET_CROP_* of include/mydet.h
 CROP_MAX_SIDE, CROP_MAX_SLOTS = 256, 512
 CROP_U8, CROP_F32 = 0, 1
+# scoring (mydet_eval_*): MYDET_EVAL_* of include/mydet.h
+EVAL_MAX_GT, EVAL_MAX_DT, EVAL_MAX_THRS, EVAL_MAX_AREAS, EVAL_MAX_DETS, EVAL_MAX_RECS = 1024, 1024, 32, 8, 8, 128
+EVAL_GT_IGNORE, EVAL_GT_CROWD = 1, 2
 
 
 class DecodeLevel(ctypes.Structure):
@@ -213,6 +220,14 @@ class CropOut(ctypes.Structure):
     _fields_ = [('ch', c_int), ('cw', c_int), ('M', c_int), ('kind', c_int), ('pad', c_f32), ('fill', ctypes.c_ubyte * 4),
                 ('norm', c_int), ('reserved', c_int), ('mean3', c_ptr), ('std3', c_ptr), ('out', c_ptr),
                 ('slot_stride', c_i64), ('frame_stride', c_i64)]
+
+
+class EvalSet(ctypes.Structure):
+    """mydet_eval_set (include/mydet.h): the packed detections and ground truths, device pointers."""
+    _fields_ = [('rotated', c_int), ('I', c_int), ('K', c_int), ('n_groups', c_int), ('max_dt', c_int), ('max_gt', c_int),
+                ('D', c_i64), ('G', c_i64), ('n_pairs', c_i64), ('groups', c_ptr), ('dt_start', c_ptr), ('gt_start', c_ptr),
+                ('pair_start', c_ptr), ('dt_box', c_ptr), ('gt_box', c_ptr), ('dt_score', c_ptr), ('dt_area', c_ptr), ('gt_area', c_ptr),
+                ('gt_flags', c_ptr)]
 
 
 # MYDET_YUV420_* of include/mydet.h

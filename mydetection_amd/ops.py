@@ -2428,3 +2428,247 @@ def crop_records(source, rec, size, layout=None, max_per_frame=None, pad=1.0, fi
     dst = _crop_dst(what, dst, B, M, settings[0], settings[4], dev)
     _crop_launch(image, yuv, _list_of_records(what, records, False, None), settings, M, dst)
     return dst
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# Scoring detections against ground truth (include/mydet.h: mydet_eval_set and the three mydet_eval_* launches; the rules are
+# there).  eval_pack and eval_summarize are host numpy; everything between them runs on the device.
+EVAL_KINDS = ('coco', 'cepdof')
+
+
+class EvalParams:
+    """The evaluation parameters of COCO's bbox evaluation, with its defaults: the attributes pycocotools' Params has."""
+
+    def __init__(self):
+        self.imgIds, self.catIds = [], []
+        self.iouThrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+        self.recThrs = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+        self.maxDets = [1, 10, 100]
+        self.areaRng = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]
+        self.areaRngLbl = ['all', 'small', 'medium', 'large']
+        self.useCats = 1
+        self.useSegm = None
+        self.iouType = 'bbox'
+
+
+def _eval_kind(kind):
+    if kind not in EVAL_KINDS:
+        raise ValueError(f'kind {kind!r}: one of {EVAL_KINDS} expected')
+    return kind == 'cepdof'
+
+
+def eval_columns(rows, kind):
+    """JSON detection rows -> the columns eval_pack takes: image_id and category_id (lists), bbox float64 [N, 4 | 5], score and
+    area float64 [N].  area defaults to w*h; with kind 'cepdof' category_id defaults to 1."""
+    width = 5 if _eval_kind(kind) else 4
+    n = len(rows)
+    return {'image_id': [r['image_id'] for r in rows],
+            'category_id': [r.get('category_id', 1) for r in rows] if width == 5 else [r['category_id'] for r in rows],
+            'bbox': np.array([r['bbox'][:width] for r in rows], dtype=np.float64).reshape(n, width),
+            'score': np.array([r['score'] for r in rows], dtype=np.float64).reshape(n),
+            'area': np.array([r['area'] if 'area' in r else r['bbox'][2] * r['bbox'][3] for r in rows], dtype=np.float64).reshape(n)}
+
+
+def _eval_starts(groups, n):
+    out = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(groups, minlength=n), out=out[1:])
+    return out
+
+
+def eval_pack(dts, gt, kind, max_det=100):
+    """Host-only: detections (JSON rows, or the columns of eval_columns) and a loaded ground-truth dict ('images', 'categories',
+    'annotations') -> the dense numpy arrays of mydet_eval_set (include/mydet.h, 'Packing'), cut to max_det = maxDets[-1] per
+    group.  Beside the arrays the dict holds I, K, D, G, n_pairs, max_dt, max_gt, rotated, img_ids, cat_ids and dt_rows / gt_rows:
+    the input row and the annotation each packed row came from."""
+    rotated = _eval_kind(kind)
+    width = 5 if rotated else 4
+    cols = dts if isinstance(dts, dict) else eval_columns(dts, kind)
+    img_ids = sorted(set(im['id'] for im in gt['images']))
+    cat_ids = sorted(set(c['id'] for c in gt['categories']))
+    I, K = len(img_ids), len(cat_ids)
+    if I < 1 or K < 1 or I * K >= 2 ** 31:
+        raise ValueError(f'eval_pack: {I} images x {K} categories')
+    if int(max_det) < 1:
+        raise ValueError(f'eval_pack: max_det {max_det}')
+    img_index = {v: n for n, v in enumerate(img_ids)}
+    cat_index = {v: n for n, v in enumerate(cat_ids)}
+
+    def groups_of(images, cats):
+        i = np.fromiter((img_index.get(v, -1) for v in images), dtype=np.int64, count=len(images))
+        k = np.fromiter((cat_index.get(v, -1) for v in cats), dtype=np.int64, count=len(cats))
+        keep = np.nonzero((i >= 0) & (k >= 0))[0]
+        return keep, k[keep] * I + i[keep]
+
+    anns = gt['annotations']
+    keep, g = groups_of([a['image_id'] for a in anns], [a['category_id'] for a in anns])
+    o = np.argsort(g, kind='stable')
+    gt_rows, gt_g = keep[o], g[o]
+    G = len(gt_rows)
+    picked = [anns[r] for r in gt_rows]
+    gt_box = np.array([a['bbox'][:width] for a in picked], dtype=np.float64).reshape(G, width)
+    if rotated:
+        gt_area = np.array([a['area'] if 'area' in a else a['bbox'][2] * a['bbox'][3] for a in picked], dtype=np.float64).reshape(G)
+        ignore = [bool(a.get('ignore', False) or a.get('iscrowd', False)) for a in picked]
+    else:
+        gt_area = np.array([a['area'] for a in picked], dtype=np.float64).reshape(G)
+        ignore = [bool(a.get('iscrowd', 0)) for a in picked]
+    crowd = [bool(a.get('iscrowd', 0)) for a in picked]
+    gt_flags = (np.array(ignore, dtype=np.uint8).reshape(G) * _lib.EVAL_GT_IGNORE
+                + np.array(crowd, dtype=np.uint8).reshape(G) * _lib.EVAL_GT_CROWD).astype(np.uint8)
+    gt_start = _eval_starts(gt_g, I * K)
+
+    keep, g = groups_of(cols['image_id'], cols['category_id'])
+    score = np.asarray(cols['score'], dtype=np.float64)[keep]
+    o = np.lexsort((-score, g))                              # stable: equal scores of a group keep input order
+    g = g[o]
+    rank = np.arange(len(g), dtype=np.int64) - _eval_starts(g, I * K)[g]
+    cut = rank < int(max_det)
+    dt_rows, dt_g, dt_rank = keep[o][cut], g[cut], rank[cut]
+    D = len(dt_rows)
+    dt_box = np.asarray(cols['bbox'], dtype=np.float64).reshape(-1, width)[dt_rows]
+    dt_score = np.asarray(cols['score'], dtype=np.float64)[dt_rows]
+    dt_area = np.asarray(cols['area'], dtype=np.float64)[dt_rows]
+    dt_start = _eval_starts(dt_g, I * K)
+    dt_cat = dt_g // I
+    order = np.lexsort((-dt_score, dt_cat))                  # stable: equal scores keep (image index, rank) order
+    cat_start = _eval_starts(dt_cat, K)
+
+    nd, ng = np.diff(dt_start), np.diff(gt_start)
+    groups = np.nonzero((nd > 0) | (ng > 0))[0]
+    pair_start = np.zeros(len(groups) + 1, dtype=np.int64)
+    np.cumsum(nd[groups] * ng[groups], out=pair_start[1:])
+    box_type = np.float32 if rotated else np.float64
+    return {'kind': kind, 'rotated': int(rotated), 'I': I, 'K': K, 'D': D, 'G': G, 'n_pairs': int(pair_start[-1]),
+            'max_dt': int(nd.max()) if D else 0, 'max_gt': int(ng.max()) if G else 0, 'img_ids': img_ids, 'cat_ids': cat_ids,
+            'dt_rows': dt_rows, 'gt_rows': gt_rows,
+            'groups': groups.astype(np.int32), 'pair_start': pair_start,
+            'dt_start': dt_start.astype(np.int32), 'gt_start': gt_start.astype(np.int32),
+            'dt_box': np.ascontiguousarray(dt_box.astype(box_type)), 'gt_box': np.ascontiguousarray(gt_box.astype(box_type)),
+            'dt_score': dt_score, 'dt_area': dt_area, 'gt_area': gt_area, 'gt_flags': gt_flags,
+            'dt_rank': dt_rank.astype(np.int32), 'order': order.astype(np.int32), 'cat_start': cat_start.astype(np.int32)}
+
+
+EVAL_SET_ARRAYS = ('groups', 'dt_start', 'gt_start', 'pair_start', 'dt_box', 'gt_box', 'dt_score', 'dt_area', 'gt_area', 'gt_flags')
+
+
+class EvalSet:
+    """The arrays of eval_pack as tensors on one device (`.t`), with the mydet_eval_set that points at them (`.c`)."""
+
+    def __init__(self, pack, device=None):
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError('EvalSet: no GPU is visible; mydetection_amd scores on MI355X only (there is no CPU path in this package)')
+            device = 'cuda'
+        self.pack = pack
+        self.t = {k: torch.from_numpy(np.ascontiguousarray(pack[k])).to(device) for k in EVAL_SET_ARRAYS + ('dt_rank', 'order', 'cat_start')}
+        require_gpu(self.t['dt_start'], 'EvalSet')
+        self.device = self.t['dt_start'].device
+        self.c = eval_set_struct(pack, {k: self.t[k].data_ptr() for k in EVAL_SET_ARRAYS})
+
+
+def eval_set_struct(pack, pointers):
+    """_lib.EvalSet from the scalars of a pack and a name -> address mapping (a null pointer for an absent or empty array)."""
+    c = _lib.EvalSet()
+    for k in ('rotated', 'I', 'K', 'max_dt', 'max_gt', 'D', 'G', 'n_pairs'):
+        setattr(c, k, int(pack[k]))
+    c.n_groups = len(pack['groups'])
+    for k in EVAL_SET_ARRAYS:
+        setattr(c, k, pointers.get(k) if len(pack[k]) else None)
+    return c
+
+
+def _eval_thresholds(values, what, width=None):
+    a = np.ascontiguousarray(np.asarray(values, dtype=np.float64))
+    if width is not None:
+        a = np.ascontiguousarray(a.reshape(-1, width))
+    elif a.ndim != 1:
+        raise ValueError(f'{what}: a 1-d array expected')
+    return a
+
+
+def eval_ious(es):
+    """float64 [n_pairs]: the IoU of every (detection, ground truth) pair of every group, one launch."""
+    out = torch.empty((es.pack['n_pairs'],), dtype=torch.float64, device=es.device)
+    with torch.cuda.device(es.device):
+        code = _lib.lib().mydet_eval_ious_f64(ctypes.byref(es.c), _ptr(out), _stream())
+    _lib.check(code, 'mydet_eval_ious_f64')
+    return out
+
+
+def eval_match(es, ious, iou_thrs, area_rng, rows=False):
+    """The greedy matching of every group at every (area range, IoU threshold), one launch: (matched, ignored, gt_row).  matched
+    and ignored are int32 [A, D] holding 32-bit masks over the thresholds (bit t); gt_row is int32 [A, T, D], the matched
+    ground-truth row or -1 (None unless rows=True)."""
+    thr, rng = _eval_thresholds(iou_thrs, 'iou_thrs'), _eval_thresholds(area_rng, 'area_rng', 2)
+    D, T, A = es.pack['D'], len(thr), len(rng)
+    require_gpu(ious, 'eval_match')
+    if ious.dtype != torch.float64 or ious.numel() != es.pack['n_pairs'] or not ious.is_contiguous():
+        raise ValueError(f"eval_match: ious must be float64 [{es.pack['n_pairs']}], contiguous")
+    matched = torch.empty((A, D), dtype=torch.int32, device=es.device)         # the launch writes every row: each detection
+    ignored = torch.empty((A, D), dtype=torch.int32, device=es.device)         # belongs to a listed group
+    gt_row = torch.empty((A, T, D), dtype=torch.int32, device=es.device) if rows else None
+    with torch.cuda.device(es.device):
+        code = _lib.lib().mydet_eval_match_f64(ctypes.byref(es.c), _ptr(ious), thr.ctypes.data, T, rng.ctypes.data, A, _ptr(matched),
+                                               _ptr(ignored), _ptr(gt_row), _stream())
+    _lib.check(code, 'mydet_eval_match_f64')
+    return matched, ignored, gt_row
+
+
+def eval_accumulate(es, matched, ignored, n_thrs, area_rng, max_dets, rec_thrs):
+    """precision [T,R,K,A,M], recall [T,K,A,M], scores [T,R,K,A,M] (float64 tensors) from the masks of eval_match, one launch."""
+    rng, rec = _eval_thresholds(area_rng, 'area_rng', 2), _eval_thresholds(rec_thrs, 'rec_thrs')
+    md = np.ascontiguousarray(np.asarray(max_dets, dtype=np.int32))
+    T, A, M, R, K, D = int(n_thrs), len(rng), len(md), len(rec), es.pack['K'], es.pack['D']
+    for name, m in (('matched', matched), ('ignored', ignored)):
+        require_gpu(m, 'eval_accumulate')
+        if m.dtype != torch.int32 or tuple(m.shape) != (A, D) or not m.is_contiguous():
+            raise ValueError(f'eval_accumulate: {name} must be int32 [{A}, {D}], contiguous')
+    precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=es.device)
+    recall = torch.empty((T, K, A, M), dtype=torch.float64, device=es.device)
+    scores = torch.empty((T, R, K, A, M), dtype=torch.float64, device=es.device)
+    t = es.t
+    with torch.cuda.device(es.device):
+        code = _lib.lib().mydet_eval_accumulate_f64(ctypes.byref(es.c), _ptr(t['order']), _ptr(t['cat_start']), _ptr(t['dt_rank']),
+                                                    _ptr(matched), _ptr(ignored), T, rng.ctypes.data, A, md.ctypes.data, M, rec.ctypes.data,
+                                                    R, _ptr(precision), _ptr(recall), _ptr(scores), _stream())
+    _lib.check(code, 'mydet_eval_accumulate_f64')
+    return precision, recall, scores
+
+
+EVAL_SUMMARY_ROW = ' {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}'
+
+
+def eval_summarize(precision, recall, params):
+    """Host numpy: the 12 stats and the summary text of COCO's bbox evaluation from precision [T,R,K,A,M] and recall [T,K,A,M]
+    (numpy arrays) -- the reference's summarize(), its row format and selection rules: the mean over the entries > -1 of the
+    selected threshold, area label and maxDets, and -1 when there are none.  Like the reference it needs params.maxDets[2]."""
+    precision, recall = np.asarray(precision), np.asarray(recall)
+    iou_thrs = np.asarray(params.iouThrs)
+    lines = []
+
+    def row(ap, iou=None, area='all', max_dets=100):
+        a_sel = [n for n, lbl in enumerate(params.areaRngLbl) if lbl == area]
+        m_sel = [n for n, v in enumerate(params.maxDets) if v == max_dets]
+        s = precision if ap else recall
+        if iou is not None:
+            s = s[np.where(iou == iou_thrs)[0]]
+        s = s[..., a_sel, m_sel]
+        found = s[s > -1]
+        mean = -1 if len(found) == 0 else np.mean(found)
+        span = '{:0.2f}:{:0.2f}'.format(iou_thrs[0], iou_thrs[-1]) if iou is None else '{:0.2f}'.format(iou)
+        lines.append(EVAL_SUMMARY_ROW.format('Average Precision' if ap else 'Average Recall', '(AP)' if ap else '(AR)', span, area,
+                                             max_dets, mean))
+        return mean
+
+    top = params.maxDets[2]
+    stats = np.zeros((12,))
+    stats[0] = row(1)
+    stats[1] = row(1, iou=.5, max_dets=top)
+    stats[2] = row(1, iou=.75, max_dets=top)
+    for n, area in enumerate(('small', 'medium', 'large')):
+        stats[3 + n] = row(1, area=area, max_dets=top)
+    for n in range(3):
+        stats[6 + n] = row(0, max_dets=params.maxDets[n])
+    for n, area in enumerate(('small', 'medium', 'large')):
+        stats[9 + n] = row(0, area=area, max_dets=top)
+    return stats, ''.join(line + '\n' for line in lines)
