@@ -449,6 +449,63 @@ int mydet_postprocess_records_rotnms_f32(const float *bbox, const int64_t *class
                                          int B, int64_t N, float conf_thres, double nms_thres,
                                          int32_t *records, void *scratch, void *stream);
 
+/* NMS modes: class-agnostic suppression, Soft-NMS (Bodla et al. 2017) and box merging, inside the same one-workgroup-per-image
+ * launch.  No reference counterpart (ImageObjects.post_process has the class-aware hard NMS only).
+ * Filter, top-k, the NaN rule and the class-id check (MYDET_COUNT_BAD_CLASS) are those of mydet_postprocess_f32; call their
+ * result the SELECTED list.  A mode is (kind, agnostic, sigma, min_score):
+ *   Groups.  agnostic == 0: one group per class.  agnostic == 1: all selected boxes are one group.
+ *   Order P inside a group: score descending, candidate index ascending (-0 and +0 tie), as everywhere in this file.
+ *   Pair value o(i,j), for every kind: the axis-aligned float32 IoU of mydet_postprocess_f32 -- corners cx -/+ w/2, area
+ *     (x2-x1)*(y2-y1), inter / (a_i + a_j - inter), no contraction; 0/0 is NaN and never suppresses or decays.  Boxes of width 5
+ *     (cxcywhd) use columns 0-3 and the angle travels with its box, as in mydet_postprocess_rot_f32.
+ *   MYDET_NMS_HARD           greedy in order P; j is suppressed when (double)o > nms_thres.  With agnostic == 0 this IS
+ *                            mydet_postprocess_f32 (the same kernel instance, the same bits).
+ *   MYDET_NMS_SOFT_LINEAR /  a working score t_j = s_j per box.  Per group, repeat: pick the remaining box with the largest t
+ *   MYDET_NMS_SOFT_GAUSSIAN  (tie: lowest candidate index); stop the group -- the rest of it is dropped -- unless t >= min_score
+ *                            (float32); emit the box with score t; then for every remaining k
+ *                              linear:   if (double)o > nms_thres:  t_k = t_k * (1.0f - o)
+ *                              gaussian: t_k = t_k * (float)exp(-((double)o * (double)o) / sigma)   (exp in double, rounded once;
+ *                                        nms_thres is not used)
+ *                            A NaN o leaves t_k unchanged; a t_k that becomes NaN (inf * 0) drops box k.
+ *                            Requires conf_thres >= 0, min_score >= 0 and, for gaussian, sigma > 0: MYDET_E_BADARG otherwise.
+ *   MYDET_NMS_MERGE          HARD first.  Then for every kept box i: its cluster is i itself plus every box j of its group with
+ *                            (double)o(i,j) > nms_thres, kept or not.  In ascending position of P accumulate in float64
+ *                            W += s_j, X1 += s_j*x1_j, likewise Y1, X2, Y2 (the float32 corners, widened); x1' = X1/W, ...;
+ *                            the output row is ((float)((x1'+x2')*0.5), (float)((y1'+y2')*0.5), (float)(x2'-x1'), (float)(y2'-y1')).
+ *                            Score, class and index are those of i.  Requires conf_thres > 0 (so W > 0): MYDET_E_BADARG
+ *                            otherwise.  Box width 4 only: the _rot_ entry points return MYDET_E_UNSUPP (no mean of angles).
+ * Output order for every kind: class ascending, and inside a class the order of selection -- order P for HARD and MERGE, the
+ *   order of emission (non-increasing t) for the soft kinds.  Rows past the count are zero.  out_score holds t for the soft
+ *   kinds, out_index the candidate index.  Outputs, records, scratch and every other argument rule are those of the entry point
+ *   without _nms_.  A null mode, an unknown kind or an agnostic outside {0, 1} is MYDET_E_BADARG.  An error launches nothing.
+ * Not provided: the exact rotated pair test (mydet_postprocess_rotnms_f32) together with a mode -- there is no such entry
+ *   point, and mydet_merge_tile_records_nms_f32 returns MYDET_E_UNSUPP for rotated_nms with agnostic. */
+#define MYDET_NMS_HARD          0
+#define MYDET_NMS_SOFT_LINEAR   1
+#define MYDET_NMS_SOFT_GAUSSIAN 2
+#define MYDET_NMS_MERGE         3
+typedef struct mydet_nms_mode {
+    int kind;                         /* MYDET_NMS_* */
+    int agnostic;                     /* 0 | 1 */
+    double sigma;                     /* SOFT_GAUSSIAN only */
+    float min_score;                  /* the soft kinds only */
+    int reserved;                     /* 0 */
+} mydet_nms_mode;
+int mydet_postprocess_nms_f32(const float *bbox, const int64_t *class_idx, const float *score,
+                              int B, int64_t N, float conf_thres, double nms_thres, int topk, const mydet_nms_mode *mode,
+                              int32_t *count, float *out_bbox, int64_t *out_class, float *out_score,
+                              int32_t *out_index, void *scratch, void *stream);
+int mydet_postprocess_records_nms_f32(const float *bbox, const int64_t *class_idx, const float *score,
+                                      int B, int64_t N, float conf_thres, double nms_thres, const mydet_nms_mode *mode,
+                                      int32_t *records, void *scratch, void *stream);
+int mydet_postprocess_rot_nms_f32(const float *bbox, const int64_t *class_idx, const float *score,
+                                  int B, int64_t N, float conf_thres, double nms_thres, int topk, const mydet_nms_mode *mode,
+                                  int32_t *count, float *out_bbox, int64_t *out_class, float *out_score,
+                                  int32_t *out_index, void *scratch, void *stream);
+int mydet_postprocess_records_rot_nms_f32(const float *bbox, const int64_t *class_idx, const float *score,
+                                          int B, int64_t N, float conf_thres, double nms_thres, const mydet_nms_mode *mode,
+                                          int32_t *records, void *scratch, void *stream);
+
 /* Merge of tile records: tiled ("sliced") detection on large frames.  The detector ran on T windows of each of B frames
  * (overlapping tiles at native resolution, optionally the whole frame as one more window); this call turns the B x T
  * per-window records into B per-frame records with one more class-aware NMS in frame coordinates.  No reference counterpart.
@@ -486,6 +543,13 @@ int64_t mydet_merge_tile_records_scratch_bytes(int B, int T, int box_width);
 int mydet_merge_tile_records_f32(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words,
                                  int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
                                  int rotated_nms, int32_t *records, void *scratch, int64_t scratch_bytes, void *stream);
+/* The same merge with `agnostic` (0 | 1; MYDET_E_BADARG otherwise): with 1 the merge's hard NMS has ONE group of all candidates
+ * (NMS modes above: HARD with agnostic; output order class ascending, inside a class order P).  Both metrics apply.  agnostic
+ * with rotated_nms is MYDET_E_UNSUPP.  agnostic == 0 is mydet_merge_tile_records_f32. */
+int mydet_merge_tile_records_nms_f32(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words,
+                                     int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
+                                     int rotated_nms, int agnostic, int32_t *records, void *scratch, int64_t scratch_bytes,
+                                     void *stream);
 
 /* Tracking of detections across video frames on the device: persistent identities and Kalman-filtered boxes from the detection
  * records of consecutive frames.  The state model is the reference's KFTracklet (utils/structures.py:445-529) over

@@ -69,9 +69,17 @@ SIGNATURES = {
     'mydet_postprocess_rotnms_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
                                      c_ptr, c_ptr, c_ptr],
     'mydet_postprocess_records_rotnms_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_ptr, c_ptr, c_ptr],
+    'mydet_postprocess_nms_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                  c_ptr, c_ptr, c_ptr],
+    'mydet_postprocess_records_nms_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_postprocess_rot_nms_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                      c_ptr, c_ptr, c_ptr],
+    'mydet_postprocess_records_rot_nms_f32': [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_f32, c_f64, c_ptr, c_ptr, c_ptr, c_ptr],
     'mydet_rotated_iou_f32': [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr],
     'mydet_merge_tile_records_scratch_bytes': [c_int, c_int, c_int],
     'mydet_merge_tile_records_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_f64, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr],
+    'mydet_merge_tile_records_nms_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_f64, c_int, c_int, c_int, c_ptr, c_ptr, c_i64,
+                                         c_ptr],
     'mydet_track_state_words': [c_int],
     'mydet_track_reset': [c_ptr, c_int, c_int, c_ptr],
     'mydet_track_frames_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
@@ -127,6 +135,8 @@ REC_ROT_WORDS = REC_WORDS + REC_TOPK
 # merge of tile records (mydet_merge_tile_records_f32): MYDET_TILES_MAX windows per frame, MYDET_MERGE_* pair tests
 TILES_MAX = 64
 MERGE_IOU, MERGE_IOS = 0, 1
+# NMS modes (mydet_postprocess_*nms_f32): MYDET_NMS_* of include/mydet.h
+NMS_HARD, NMS_SOFT_LINEAR, NMS_SOFT_GAUSSIAN, NMS_MERGE = range(4)
 # tracking (mydet_track_frames_f32): MYDET_TRACK_* of include/mydet.h
 TRACK_MAX_TRACKS = 512
 TRACK_STATE_HEADER, TRACK_SLOT_WORDS = 8, 31
@@ -147,6 +157,11 @@ class DecodeLevel(ctypes.Structure):
     """mydet_decode_level (include/mydet.h)."""
     _fields_ = [('box', c_ptr), ('ldbox', c_i64), ('cls', c_ptr), ('ldcls', c_i64), ('anchors_wh', c_ptr),
                 ('H', c_int), ('W', c_int), ('stride', c_f32), ('n_off', c_i64)]
+
+
+class NmsMode(ctypes.Structure):
+    """mydet_nms_mode (include/mydet.h)."""
+    _fields_ = [('kind', c_int), ('agnostic', c_int), ('sigma', c_f64), ('min_score', c_f32), ('reserved', c_int)]
 
 
 class SeTail(ctypes.Structure):

@@ -11,6 +11,7 @@ import PIL.Image
 import torch
 
 from .. import ops
+from ..ops import Nms
 
 from ..models.general import name_to_model
 from ..utils import image_ops as imgUtils
@@ -102,7 +103,7 @@ class Chips:
 
 
 # what the keyword arguments of a frame method say (Detector._call_settings reads them, nothing else does)
-_Call = collections.namedtuple('_Call', 'preprocessing input_size conf_thres nms_thres rotated_nms tiles whole')
+_Call = collections.namedtuple('_Call', 'preprocessing input_size conf_thres nms_thres rotated_nms nms tiles whole')
 
 
 class _Frames:
@@ -225,9 +226,10 @@ class Detector():
         model_and_cfg: (model, cfg) built elsewhere
         weights_path: checkpoint with a 'model' state_dict (reference key names)
         cpu: must be False -- this package has no CPU path
+        nms: None, or an Nms: how the post-process suppresses in every call that does not say otherwise (`nms=` per call)
     '''
     def __init__(self, model_name: str = None, model_and_cfg: tuple = None,
-                 weights_path: str = None, cpu=False):
+                 weights_path: str = None, cpu=False, nms=None):
         if cpu:
             raise RuntimeError('mydetection_amd.Detector(cpu=True): there is no CPU path; '
                                'use the reference for CPU inference')
@@ -240,6 +242,7 @@ class Detector():
 
         self._init_preprocess(cfg)
         self._init_postprocess(cfg)
+        self.nms = self._nms_setting(nms, self.conf_thres, self.rotated_nms)
 
         n_params = sum(p.numel() for p in self.model.parameters() if p.requires_grad)
         print('Number of parameters:', n_params)
@@ -263,6 +266,12 @@ class Detector():
         # opt-in: NMS on the rotated rectangles of a 'cxcywhd' model (no shipped config sets the key: the default is the
         # axis-aligned NMS the reference runs); the `rotated_nms` keyword of the predict methods overrides it per call
         self.rotated_nms = bool(cfg.get('test.rotated_nms', False))
+
+    def _nms_setting(self, nms, conf_thres, rotated_nms):
+        """An `nms=` argument checked against this model and the thresholds it will run with (ops.nms_mode has the rules;
+        no device is touched).  Returns it."""
+        ops.nms_mode('Detector', nms, conf_thres, 5 if self.model.bb_format == 'cxcywhd' else 4, rotated_nms)
+        return nms
 
     def evaluation_predict(self, eval_info: dict, **kwargs):
         '''
@@ -334,7 +343,8 @@ class Detector():
     def _predict_pil(self, pil_img, **kwargs):
         '''
         Args:
-            pil_img, preprocessing (str), input_size (int), conf_thres (float), nms_thres (float), rotated_nms (bool)
+            pil_img, preprocessing (str), input_size (int), conf_thres (float), nms_thres (float), rotated_nms (bool),
+            nms (an Nms or None: class-agnostic suppression, Soft-NMS or box merging; the detector's own by default)
         '''
         assert isinstance(pil_img, PIL.Image.Image), 'input must be a PIL.Image'
         return self.predict_batch([pil_img], **kwargs)[0]
@@ -393,8 +403,9 @@ class Detector():
         rotated_nms = bool(kwargs.get('rotated_nms', self.rotated_nms))
         if rotated_nms and self.model.bb_format != 'cxcywhd':
             raise ValueError(f"rotated_nms needs a 'cxcywhd' model; this one predicts {self.model.bb_format!r}")
+        nms = self._nms_setting(kwargs.get('nms', self.nms), conf_thres, rotated_nms)
         for idxs, x, pads, hws in self.preprocess_batch(pil_imgs, **kwargs):
-            rec = self._records(x, conf_thres, nms_thres, rotated_nms)
+            rec = self._records(x, conf_thres, nms_thres, rotated_nms, nms)
             if any(p is not None for p in pads):
                 ops.records_to_original_(rec, pads)
             rec['img_hw'] = hws
@@ -406,11 +417,13 @@ class Detector():
         """Forget every captured hipGraph (after editing parameters in place, or to release the graphs' activation pools)."""
         self._graphs.clear()
 
-    def _records(self, x, conf_thres, nms_thres, rotated_nms=False):
+    def _records(self, x, conf_thres, nms_thres, rotated_nms=False, nms=None):
         """Detection records of one network input batch (boxes in network-input coordinates): a hipGraph replay when
-        this (shape, thresholds, kind of NMS) has been seen before, the eager launch sequence otherwise."""
+        this (shape, thresholds, kind of NMS, NMS mode) has been seen before, the eager launch sequence otherwise."""
         from ..utils.structures import batched_post_process
         key = (tuple(x.shape), float(conf_thres), float(nms_thres), bool(rotated_nms))
+        if nms is not None:                                          # an Nms hashes by value; without one the key is what it was
+            key += (nms,)
         if self.use_graph:
             cache = self._graphs
             g = cache.lookup(key)                                    # LRU; drops a graph captured before a weight change
@@ -418,7 +431,7 @@ class Detector():
                 from ..graph import GraphedPath
                 # each graph owns its activations; the lane count is the detector's (below), not a timing decision
                 g = cache.insert(key, GraphedPath(self.model, x, conf_thres, nms_thres, lanes=self.batch_lanes(x.shape[0]),
-                                                      rotated_nms=rotated_nms))
+                                                      rotated_nms=rotated_nms, nms=nms))
             if g is not None:
                 return {k: v.clone() for k, v in g(x).items()}       # the graph's own record buffers are overwritten by the next replay
             cache.note_eager(key)
@@ -426,14 +439,15 @@ class Detector():
             lanes = self.batch_lanes(x.shape[0])
             if lanes == 1:
                 bb, ci, sc = self.model.forward_candidates(x)
-                return batched_post_process(bb, ci, sc, conf_thres, nms_thres, rotated_nms=rotated_nms)
+                return batched_post_process(bb, ci, sc, conf_thres, nms_thres, rotated_nms=rotated_nms, nms=nms)
             # the eager form of a laned graph: the same parts of the batch, one after the other -- bit-identical to the replay
             words = ops.record_words(getattr(self.model, 'bbox_param', 4))
             records = torch.empty((x.shape[0], words), dtype=torch.int32, device=x.device)
             lo = 0
             for part in x.tensor_split(lanes):
                 bb, ci, sc = self.model.forward_candidates(part)
-                batched_post_process(bb, ci, sc, conf_thres, nms_thres, records=records[lo:lo + part.shape[0]], rotated_nms=rotated_nms)
+                batched_post_process(bb, ci, sc, conf_thres, nms_thres, records=records[lo:lo + part.shape[0]], rotated_nms=rotated_nms,
+                                     nms=nms)
                 lo += part.shape[0]
             return ops.record_views(records)
 
@@ -502,8 +516,10 @@ class Detector():
             raise ValueError("tiles: metric 'ios' is defined for the axis-aligned test only, not with rotated_nms")
         if rotated_nms and self.model.bb_format != 'cxcywhd':
             raise ValueError(f"rotated_nms needs a 'cxcywhd' model; this one predicts {self.model.bb_format!r}")
+        conf_thres = kwargs.get('conf_thres', self.conf_thres)
+        nms = self._nms_setting(kwargs.get('nms', self.nms), conf_thres, rotated_nms)
         return _Call(kwargs.get('preprocessing', self.preprocess), kwargs.get('input_size', self.input_size),
-                     kwargs.get('conf_thres', self.conf_thres), kwargs.get('nms_thres', self.nms_thres), rotated_nms, tiles,
+                     conf_thres, kwargs.get('nms_thres', self.nms_thres), rotated_nms, nms, tiles,
                      bool(whole or kwargs.get('_whole_records')))
 
     def _frame_records(self, frames, **kwargs):
@@ -537,7 +553,7 @@ class Detector():
                 order = sorted(range(len(idxs)), key=idxs.__getitem__)
                 x = torch.cat(xs)[torch.tensor(order, device=x.device)]
                 idxs, pads, hws = [idxs[k] for k in order], [pads[k] for k in order], [hws[k] for k in order]
-            rec = self._records(x, call.conf_thres, call.nms_thres, call.rotated_nms)
+            rec = self._records(x, call.conf_thres, call.nms_thres, call.rotated_nms, call.nms)
             if call.whole:                                           # the views of ONE buffer (a graph replay hands out copies)
                 rec = ops.record_views(rec['records'])
             if any(p is not None for p in pads):
@@ -551,7 +567,7 @@ class Detector():
         network input size are one [n*B,3,Hp,Wp] batch, window-major, built in place; the full-frame window joins the tiles'
         batch when its input size equals theirs and is a second batch otherwise.  Forward and post-process are self._records
         (graph capture by shape as everywhere), then the boxes go back to window pixels and ONE merge launch pair makes the B
-        frame records."""
+        frame records.  With an Nms the windows run the whole mode; the merge stays a hard NMS and takes the mode's `agnostic`."""
         tiles, B = call.tiles, src.n
         windows = ops.tile_windows(src.hw[0], src.hw[1], tiles.size, tiles.overlap, tiles.full_frame, src.align(tiles))
         dev = next(self.model.parameters()).device
@@ -566,7 +582,7 @@ class Detector():
             for n, (i, geo) in enumerate(members):
                 src.input(geo, out=x[n * B:(n + 1) * B], window=windows[i])
             # the views of ONE buffer (a graph replay hands out the fields as separate copies)
-            rec = ops.record_views(self._records(x, call.conf_thres, call.nms_thres, call.rotated_nms)['records'])
+            rec = ops.record_views(self._records(x, call.conf_thres, call.nms_thres, call.rotated_nms, call.nms)['records'])
             pads = [geo[3] for _, geo in members for _ in range(B)]
             if any(p is not None for p in pads):
                 ops.records_to_original_(rec, pads)
@@ -577,7 +593,8 @@ class Detector():
             for idx, r in batches:
                 tile_records[idx] = r.view(len(idx), B, -1)
         merged = ops.merge_tile_records(tile_records, B, T, [(x0, y0) for y0, x0, _, _ in windows],
-                                        call.nms_thres if tiles.nms_thres is None else tiles.nms_thres, tiles.metric, call.rotated_nms)
+                                        call.nms_thres if tiles.nms_thres is None else tiles.nms_thres, tiles.metric, call.rotated_nms,
+                                        agnostic=call.nms is not None and call.nms.agnostic)
         merged['img_hw'] = [src.hw] * B
         return [(list(range(B)), merged)]
 

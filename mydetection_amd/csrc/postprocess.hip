@@ -30,6 +30,11 @@
 // is shared, so the order, the tie rule and the record layout are those of the <5, false> instance.
 // The third template parameter IOS (axis-aligned pair test only; the merge of tile records below) divides the intersection
 // by the smaller of the two areas instead of by the union.
+// The fourth template parameter MODE (axis-aligned pair test only; the mydet_postprocess_*nms_f32 entry points, include/mydet.h
+// "NMS modes") keeps steps 1-3 and replaces what follows them: MODE_GROUPS is steps 4-5 with ONE group of all selected boxes
+// (class-agnostic hard NMS), MODE_SOFT is Soft-NMS (no matrix: a wave owns a group, a pick is one wave reduction), MODE_MERGE is
+// steps 4-5 and then the score-weighted mean of every kept box's cluster.  All three end in emit_ranked() instead of step 6.
+// MODE 0 is the shipped kernel: every `if constexpr (MODE != 0)` below is discarded from it.
 #include "common.h"
 #include "rot_iou.h"
 
@@ -61,6 +66,18 @@ struct PPArgs {
     unsigned long long *scratch;
 };
 
+// The kernel argument of the MODE != 0 instances: the shipped instances keep PPArgs as it is
+struct PPModeArgs : PPArgs {
+    int kind;                         // MYDET_NMS_*
+    int agn;                          // one group of all selected boxes
+    double sigma;
+    float min_score;
+};
+
+constexpr int MODE_GROUPS = 1, MODE_SOFT = 2, MODE_MERGE = 3;
+template <int MODE> struct ArgsOf { using type = PPModeArgs; };
+template <> struct ArgsOf<0> { using type = PPArgs; };
+
 // Order-preserving map of the float32 scores that pass the filter (never a NaN) to unsigned.  -0.0f takes the key of +0.0f:
 // the two compare equal, so between them the candidate index decides, as it does for any other tie.
 __device__ __forceinline__ unsigned sortable(float f) {
@@ -69,10 +86,227 @@ __device__ __forceinline__ unsigned sortable(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-template <int BW, bool ROT, bool IOS = false>
-__global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
+// ---- NMS modes (MODE != 0 of the kernel below) ----
+// The four helpers here restate lines of the kernel (the pair test of step 4, the sort of step 3, the row stores of step 6)
+// for the code the modes add.  The kernel's own lines do not call them: routing the shipped instances through helpers changed
+// their register allocation, and they are held to the instruction stream they had (profiles/nms_modes.md).
+
+// The axis-aligned IoU of boxes i and j from their corners and areas, in the float32 operation order of step 4 (torchvision's
+// CPU nms kernel).  0/0 (two boxes without area) is NaN.
+__device__ __forceinline__ float pair_iou(float ix1, float iy1, float ix2, float iy2, float ia,
+                                          float jx1, float jy1, float jx2, float jy2, float ja) {
+    const float xx1 = fmaxf(ix1, jx1), yy1 = fmaxf(iy1, jy1);
+    const float xx2 = fminf(ix2, jx2), yy2 = fminf(iy2, jy2);
+    const float ww = fmaxf(0.0f, xx2 - xx1), hh = fmaxf(0.0f, yy2 - yy1);
+    const float inter = ww * hh;
+    return inter / (ia + ja - inter);
+}
+
+// ascending bitonic sort of KMAX keys in LDS by the first KMAX threads of the workgroup; every thread takes the barriers
+__device__ __forceinline__ void bitonic_sort_kmax(unsigned long long *a, int tid) {
+    for (int k = 2; k <= KMAX; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            if (tid < KMAX) {
+                const int ixj = tid ^ j;
+                if (ixj > tid) {
+                    const unsigned long long x = a[tid], c = a[ixj];
+                    const bool up = (tid & k) == 0;
+                    if ((x > c) == up) { a[tid] = c; a[ixj] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// one output row `pos` of image b: box columns 0-3, the angle (BW = 5), class, score and candidate index
+template <int BW>
+__device__ __forceinline__ void write_row(const PPArgs &p, int b, int pos, f32x4 v, float ang, int64_t cls, float score, unsigned idx) {
+    if constexpr (BW == 4) {
+        *reinterpret_cast<f32x4 *>(p.obox + b * p.obox_st + pos * 4) = v;
+    } else if (p.oang) {                    // rotated record: the 512 x 4 box plane + the angle plane
+        *reinterpret_cast<f32x4 *>(p.obox + b * p.obox_st + pos * 4) = v;
+        p.oang[b * p.oang_st + pos] = ang;
+    } else {
+        float *d = p.obox + b * p.obox_st + pos * BW;
+        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3]; d[4] = ang;
+    }
+    p.ocls[b * p.ocls_st + pos] = cls;
+    p.oscore[b * p.oscore_st + pos] = score;
+    p.oidx[b * p.oidx_st + pos] = (int32_t)idx;
+}
+
+// zero rows from `total` to topk, then the count word (and the record header's padding behind it)
+template <int BW>
+__device__ __forceinline__ void finish_rows(const PPArgs &p, int b, int total, bool bad, int tid) {
+    for (int r = total + tid; r < p.topk; r += NT) {
+        if constexpr (BW == 4) {
+            *reinterpret_cast<f32x4 *>(p.obox + b * p.obox_st + r * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else if (p.oang) {
+            *reinterpret_cast<f32x4 *>(p.obox + b * p.obox_st + r * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+            p.oang[b * p.oang_st + r] = 0.f;
+        } else {
+#pragma unroll
+            for (int c = 0; c < BW; ++c) p.obox[b * p.obox_st + r * BW + c] = 0.f;
+        }
+        p.ocls[b * p.ocls_st + r] = 0;
+        p.oscore[b * p.oscore_st + r] = 0.f;
+        p.oidx[b * p.oidx_st + r] = 0;
+    }
+    if (tid <= p.count_pad) p.count[b * p.count_st + tid] = tid == 0 ? (bad ? MYDET_COUNT_BAD_CLASS : total) : 0;
+}
+
+// What the modes keep per selected box, in the 32 KiB of the suppression matrix (free in MODE_SOFT, and behind step 5 in the
+// other two).  Position = place in the sorted selected list: groups are contiguous there and in order P.
+struct ModeLds {
+    unsigned long long *okey;         // [KMAX] output order keys
+    float *t;                         // [KMAX] the score a box is emitted with (soft kinds: the working score at its pick)
+    float *mcx, *mcy, *mw, *mh;       // [KMAX] MODE_MERGE: the merged box
+    int *rank;                        // [KMAX] place in the group's selection order, -1 = not emitted
+    int *gbeg;                        // [KMAX] first positions of the groups, in any order
+    __device__ explicit ModeLds(unsigned long long *base) {
+        okey = base;
+        t = reinterpret_cast<float *>(base + KMAX);
+        mcx = t + KMAX; mcy = mcx + KMAX; mw = mcy + KMAX; mh = mw + KMAX;
+        rank = reinterpret_cast<int *>(mh + KMAX);
+        gbeg = rank + KMAX;
+    }
+};
+static_assert(KMAX * (8 + 4 * 7) <= KMAX * 8 * 8, "ModeLds fits the suppression matrix");
+
+struct SelLds {                       // the selected list after step 4's first half
+    const unsigned long long *key;
+    const float *x1, *y1, *x2, *y2, *area;
+    const int *cls, *segend;
+};
+
+// Soft-NMS (Bodla et al. 2017) of every group; include/mydet.h has the rules.  A wave owns a group: lane l holds its boxes
+// l, l + 64, ... (8 for a group of 512) with their working scores in registers.  A pick is a wave maximum over
+// (sortable(t), ~candidate index, position) and the decay that follows is 8 pair values per lane, so the 512 dependent picks of
+// the longest group need no workgroup barrier.  Writes t and rank of every emitted box.
+__device__ void soft_groups(const PPModeArgs &p, const float *sc, const SelLds &s, const ModeLds &m, int ngroups, int tid) {
+    constexpr int R = KMAX / 64;
+    const int wave = tid >> 6, lane = tid & 63;
+    const unsigned min_key = sortable(p.min_score);
+    const bool gaussian = p.kind == MYDET_NMS_SOFT_GAUSSIAN;
+    for (int g = wave; g < ngroups; g += NT / 64) {
+        const int g0 = m.gbeg[g], g1 = s.segend[g0];
+        float x1[R], y1[R], x2[R], y2[R], ar[R], t[R];
+        unsigned low[R];                                     // (~index) << 9 | position: the tie order, then where the box is
+        unsigned alive = 0u;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int pos = g0 + lane + 64 * r;
+            x1[r] = y1[r] = x2[r] = y2[r] = ar[r] = t[r] = 0.f;
+            low[r] = 0u;
+            if (pos < g1) {
+                const unsigned idx = (unsigned)(s.key[pos] & ((1ull << IDX_BITS) - 1));
+                x1[r] = s.x1[pos]; y1[r] = s.y1[pos]; x2[r] = s.x2[pos]; y2[r] = s.y2[pos]; ar[r] = s.area[pos];
+                t[r] = sc[idx];
+                low[r] = ((((1u << IDX_BITS) - 1u) - idx) << 9) | (unsigned)pos;
+                alive |= 1u << r;
+            }
+        }
+        for (int emitted = 0;; ++emitted) {
+            unsigned long long best = 0ull;                  // a live box has a key above 2^60: scores are >= 0 here
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const unsigned long long k = ((unsigned long long)sortable(t[r]) << 29) | low[r];
+                if (((alive >> r) & 1u) && k > best) best = k;
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const unsigned long long o = __shfl_xor(best, off);
+                best = o > best ? o : best;
+            }
+            if (best == 0ull || (unsigned)(best >> 29) < min_key) break;          // uniform: nothing left, or not t >= min_score
+            const int wpos = (int)(best & (KMAX - 1));
+            const float bx1 = s.x1[wpos], by1 = s.y1[wpos], bx2 = s.x2[wpos], by2 = s.y2[wpos], ba = s.area[wpos];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (!((alive >> r) & 1u)) continue;
+                if ((int)(low[r] & (KMAX - 1)) == wpos) {
+                    m.t[wpos] = t[r];
+                    m.rank[wpos] = emitted;
+                    alive &= ~(1u << r);
+                    continue;
+                }
+                const float o = pair_iou(bx1, by1, bx2, by2, ba, x1[r], y1[r], x2[r], y2[r], ar[r]);
+                if (gaussian) {
+                    // o == 0 gives the weight exp(-0) = 1 exactly: skipped; a NaN o leaves t as it is
+                    if (o == o && o != 0.0f) t[r] = t[r] * (float)exp(-((double)o * (double)o) / p.sigma);
+                } else if ((double)o > p.nms) {
+                    t[r] = t[r] * (1.0f - o);
+                }
+                if (t[r] != t[r]) alive &= ~(1u << r);       // inf * 0: a box without a score is dropped
+            }
+        }
+    }
+}
+
+// MODE_MERGE, one lane per kept box i: the score-weighted mean of the corners of i and of every box of its group that i's
+// pair value puts above the threshold, accumulated in float64 in ascending position (order P).
+__device__ void merge_clusters(const PPModeArgs &p, const SelLds &s, const ModeLds &m, const unsigned long long *removed, int nsel, int tid) {
+    if (tid >= nsel || ((removed[tid >> 6] >> (tid & 63)) & 1ull)) return;
+    const int ic = s.cls[tid];
+    int lo = 0, hi = tid;                                    // first position of my group: lower bound of my class
+    if (p.agn) hi = 0;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s.cls[mid] == ic) hi = mid; else lo = mid + 1;
+    }
+    const int e = s.segend[tid];
+    const float ix1 = s.x1[tid], iy1 = s.y1[tid], ix2 = s.x2[tid], iy2 = s.y2[tid], ia = s.area[tid];
+    double W = 0.0, X1 = 0.0, Y1 = 0.0, X2 = 0.0, Y2 = 0.0;
+    for (int j = lo; j < e; ++j) {
+        const float jx1 = s.x1[j], jy1 = s.y1[j], jx2 = s.x2[j], jy2 = s.y2[j];
+        const bool in = j == tid || (double)pair_iou(ix1, iy1, ix2, iy2, ia, jx1, jy1, jx2, jy2, s.area[j]) > p.nms;
+        if (in) {
+            const double w = (double)m.t[j];
+            W += w;
+            X1 += w * (double)jx1; Y1 += w * (double)jy1; X2 += w * (double)jx2; Y2 += w * (double)jy2;
+        }
+    }
+    const double x1 = X1 / W, y1 = Y1 / W, x2 = X2 / W, y2 = Y2 / W;
+    m.mcx[tid] = (float)((x1 + x2) * 0.5); m.mcy[tid] = (float)((y1 + y2) * 0.5);
+    m.mw[tid] = (float)(x2 - x1); m.mh[tid] = (float)(y2 - y1);
+}
+
+// The output of every mode: the emitted boxes by (class ascending, rank in the group's selection order), the rest zero.
+template <int BW, int MODE>
+__device__ void emit_ranked(const PPArgs &p, int b, const float *bb, const int64_t *ci, const SelLds &s, const ModeLds &m,
+                            int *s_total, int nsel, bool bad, int tid) {
+    if (tid < KMAX)
+        m.okey[tid] = tid < nsel && m.rank[tid] >= 0
+                          ? ((unsigned long long)s.cls[tid] << 20) | ((unsigned long long)m.rank[tid] << 10) | (unsigned long long)tid
+                          : ~0ull;
+    if (tid == 0) *s_total = 0;
+    __syncthreads();
+    bitonic_sort_kmax(m.okey, tid);
+    if (tid < KMAX && m.okey[tid] != ~0ull && (tid == KMAX - 1 || m.okey[tid + 1] == ~0ull)) *s_total = tid + 1;
+    __syncthreads();
+    const int total = bad ? 0 : *s_total;
+    if (tid < total) {
+        const int pos = (int)(m.okey[tid] & 1023ull);
+        const unsigned idx = (unsigned)(s.key[pos] & ((1ull << IDX_BITS) - 1));
+        const float *r = bb + (int64_t)idx * BW;
+        f32x4 v;
+        if constexpr (MODE == MODE_MERGE) v = f32x4{m.mcx[pos], m.mcy[pos], m.mw[pos], m.mh[pos]};
+        else if constexpr (BW == 4) v = *reinterpret_cast<const f32x4 *>(r);
+        else v = f32x4{r[0], r[1], r[2], r[3]};
+        float ang = 0.f;
+        if constexpr (BW == 5) ang = r[4];
+        write_row<BW>(p, b, tid, v, ang, ci[idx], m.t[pos], idx);
+    }
+    finish_rows<BW>(p, b, total, bad, tid);
+}
+
+template <int BW, bool ROT, bool IOS = false, int MODE = 0>
+__global__ __launch_bounds__(NT) void postprocess_kernel(const typename ArgsOf<MODE>::type p) {
     static_assert(!ROT || BW == 5, "the rotated IoU needs the angle column");
     static_assert(!(ROT && IOS), "intersection over smaller is defined for the axis-aligned test only");
+    static_assert(MODE == 0 || !ROT, "the NMS modes use the axis-aligned pair value");
+    static_assert(MODE != MODE_MERGE || BW == 4, "a mean of angles is not defined");
     __shared__ unsigned long long s_key[KMAX];
     __shared__ unsigned long long s_mask[KMAX * 8];
     // ROT: the seven planes of rotiou::Box -- s_x1, s_y1 = centre, s_x2, s_y2 = hori, s_vx, s_vy = verti, s_area
@@ -192,7 +426,8 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
                 }
                 s_sel[0] = 4 * tid + bsel;
                 s_sel[1] = a;
-                s_sel[2] = (int)c[bsel];
+                if constexpr (MODE == 0) s_sel[2] = (int)c[bsel];
+                else s_sel[2] = (int)(bsel == 3 ? c3 : bsel == 2 ? c2 : bsel == 1 ? c1 : c0);   // c[bsel], kept out of scratch
             }
             __syncthreads();
             prefix |= (unsigned long long)(unsigned)s_sel[0] << shift;
@@ -252,6 +487,9 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
                 const unsigned long long c = (unsigned long long)ci[idx];       // negative ids wrap to huge values
                 if (c > 0xFFFull) s_bad = 1;                                    // the sort key has 12 class bits
                 s_key[pos] = ((c & 0xFFFull) << CLS_SHIFT) | ((unsigned long long)(~su) << IDX_BITS) | (unsigned long long)idx;
+                if constexpr (MODE != 0) {                                      // one group: order P over all selected, no class bits
+                    if (p.agn) s_key[pos] = ((unsigned long long)(~su) << IDX_BITS) | (unsigned long long)idx;
+                }
             }
         }
     }
@@ -295,6 +533,7 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
             s_area[tid] = (x2 - x1) * (y2 - y1);
         }
         s_cls[tid] = (int)(k >> CLS_SHIFT);
+        if constexpr (MODE != 0) { if (p.agn) s_cls[tid] = (int)(ci[idx] & 0xFFF); }      // the key holds no class then
     }
     __syncthreads();
     // rows are zero except inside the row's own class segment (classes are contiguous after the sort).  
@@ -306,9 +545,26 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
             const int mid = (lo + hi) >> 1;
             if (s_cls[mid] == ic) lo = mid + 1; else hi = mid;
         }
+        if constexpr (MODE != 0) { if (p.agn) lo = nsel; }
         s_segend[tid] = lo;
     }
     __syncthreads();
+    if constexpr (MODE == MODE_SOFT) {
+        __shared__ int s_ng;
+        const SelLds sel{s_key, s_x1, s_y1, s_x2, s_y2, s_area, s_cls, s_segend};
+        const ModeLds m(s_mask);
+        if (tid == 0) s_ng = 0;
+        __syncthreads();                                    // and the zeroing of s_mask above is done
+        if (tid < nsel) {
+            m.rank[tid] = -1;
+            if (tid == 0 || (!p.agn && s_cls[tid - 1] != s_cls[tid])) m.gbeg[atomicAdd(&s_ng, 1)] = tid;
+        }
+        __syncthreads();
+        soft_groups(p, sc, sel, m, s_ng, tid);
+        __syncthreads();
+        emit_ranked<BW, MODE>(p, b, bb, ci, sel, m, &s_cnt[0], nsel, bad, tid);
+        return;
+    }
     // a wave owns rows i = wave, wave+16, ...; for each it walks only the 64-box words that overlap
     // [i+1, end of i's class segment): lane = one j, the word is the wave's ballot (no atomics, conflict-free LDS)
     {
@@ -434,6 +690,22 @@ __global__ __launch_bounds__(NT) void postprocess_kernel(const PPArgs p) {
             if (lane == w) s_removed[w] = removed[w];
     }
     __syncthreads();
+    if constexpr (MODE != 0) {                              // s_mask is free: the greedy result is s_removed
+        const SelLds sel{s_key, s_x1, s_y1, s_x2, s_y2, s_area, s_cls, s_segend};
+        const ModeLds m(s_mask);
+        if (tid < nsel) {
+            const unsigned idx = (unsigned)(s_key[tid] & ((1ull << IDX_BITS) - 1));
+            m.t[tid] = sc[idx];
+            m.rank[tid] = ((s_removed[tid >> 6] >> (tid & 63)) & 1ull) ? -1 : tid;
+        }
+        __syncthreads();
+        if constexpr (MODE == MODE_MERGE) {
+            merge_clusters(p, sel, m, s_removed, nsel, tid);
+            __syncthreads();
+        }
+        emit_ranked<BW, MODE>(p, b, bb, ci, sel, m, &s_cnt[0], nsel, bad, tid);
+        return;
+    }
 
     // 6. survivors, ranked by popcount, in sorted (class asc, score desc) order
     int total = 0;
@@ -506,8 +778,8 @@ static void record_outputs(PPArgs &p, int32_t *records, bool rot) {
     p.ocls_st = words / 2; p.oidx_st = words; p.oang_st = rot ? words : 0;
 }
 
-template <int BW, bool ROT = false, bool IOS = false>
-static int launch_postprocess(PPArgs &p, const float *bbox, const int64_t *class_idx, const float *score, int B, int64_t N,
+template <int BW, bool ROT = false, bool IOS = false, int MODE = 0>
+static int launch_postprocess(typename ArgsOf<MODE>::type &p, const float *bbox, const int64_t *class_idx, const float *score, int B, int64_t N,
                               float conf_thres, double nms_thres, int topk, void *scratch, void *stream) {
     if (B <= 0 || N < 0 || topk <= 0 || topk > KMAX) return MYDET_E_BADARG;
     if (N >= (1ll << IDX_BITS)) return MYDET_E_UNSUPP;
@@ -516,7 +788,7 @@ static int launch_postprocess(PPArgs &p, const float *bbox, const int64_t *class
     if (((uintptr_t)bbox & 15) || ((uintptr_t)p.obox & 15) || ((uintptr_t)scratch & 7) || ((uintptr_t)p.ocls & 7)) return MYDET_E_BADARG;
     p.bbox = bbox; p.cidx = class_idx; p.score = score; p.N = N; p.conf = conf_thres; p.nms = nms_thres;
     p.topk = topk; p.scratch = (unsigned long long *)scratch;
-    hipLaunchKernelGGL((postprocess_kernel<BW, ROT, IOS>), dim3(B), dim3(NT), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((postprocess_kernel<BW, ROT, IOS, MODE>), dim3(B), dim3(NT), 0, (hipStream_t)stream, p);
     return mydet_launch_status();
 }
 
@@ -585,6 +857,80 @@ extern "C" int mydet_postprocess_records_rotnms_f32(const float *bbox, const int
     return launch_postprocess<5, true>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream);
 }
 
+// ---- NMS modes (include/mydet.h): the four entry points above with a mydet_nms_mode ----
+// The argument rules of a mode, before any launch.  HARD without `agnostic` is the shipped instance itself.
+static int check_mode(const mydet_nms_mode *m, int box_width, float conf_thres) {
+    if (!m || m->kind < MYDET_NMS_HARD || m->kind > MYDET_NMS_MERGE || (m->agnostic != 0 && m->agnostic != 1)) return MYDET_E_BADARG;
+    if (m->kind == MYDET_NMS_SOFT_LINEAR || m->kind == MYDET_NMS_SOFT_GAUSSIAN) {
+        if (!(conf_thres >= 0.0f) || !(m->min_score >= 0.0f)) return MYDET_E_BADARG;
+        if (m->kind == MYDET_NMS_SOFT_GAUSSIAN && !(m->sigma > 0.0)) return MYDET_E_BADARG;
+    }
+    if (m->kind == MYDET_NMS_MERGE) {
+        if (!(conf_thres > 0.0f)) return MYDET_E_BADARG;
+        if (box_width != 4) return MYDET_E_UNSUPP;
+    }
+    return 0;
+}
+
+template <int BW>
+static int launch_mode(PPModeArgs &p, const mydet_nms_mode *m, const float *bbox, const int64_t *class_idx, const float *score, int B,
+                       int64_t N, float conf_thres, double nms_thres, int topk, void *scratch, void *stream) {
+    const int st = check_mode(m, BW, conf_thres);
+    if (st) return st;
+    p.kind = m->kind; p.agn = m->agnostic; p.sigma = m->sigma; p.min_score = m->min_score;
+    if (m->kind == MYDET_NMS_HARD)
+        return m->agnostic ? launch_postprocess<BW, false, false, MODE_GROUPS>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, topk, scratch, stream)
+                           : launch_postprocess<BW>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, topk, scratch, stream);
+    if constexpr (BW == 4) {
+        if (m->kind == MYDET_NMS_MERGE)
+            return launch_postprocess<4, false, false, MODE_MERGE>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, topk, scratch, stream);
+    }
+    return launch_postprocess<BW, false, false, MODE_SOFT>(p, bbox, class_idx, score, B, N, conf_thres, nms_thres, topk, scratch, stream);
+}
+
+static void dense_outputs(PPArgs &p, int box_width, int topk, int32_t *count, float *out_bbox, int64_t *out_class, float *out_score,
+                          int32_t *out_index) {
+    p.count = count; p.obox = out_bbox; p.ocls = out_class; p.oscore = out_score; p.oidx = out_index;
+    p.oang = nullptr; p.oang_st = 0;
+    p.count_pad = 0; p.count_st = 1; p.obox_st = (int64_t)topk * box_width; p.ocls_st = topk; p.oscore_st = topk; p.oidx_st = topk;
+}
+
+extern "C" int mydet_postprocess_nms_f32(const float *bbox, const int64_t *class_idx, const float *score, int B, int64_t N,
+                                         float conf_thres, double nms_thres, int topk, const mydet_nms_mode *mode, int32_t *count,
+                                         float *out_bbox, int64_t *out_class, float *out_score, int32_t *out_index,
+                                         void *scratch, void *stream) {
+    PPModeArgs p;
+    dense_outputs(p, 4, topk, count, out_bbox, out_class, out_score, out_index);
+    return launch_mode<4>(p, mode, bbox, class_idx, score, B, N, conf_thres, nms_thres, topk, scratch, stream);
+}
+
+extern "C" int mydet_postprocess_rot_nms_f32(const float *bbox, const int64_t *class_idx, const float *score, int B, int64_t N,
+                                             float conf_thres, double nms_thres, int topk, const mydet_nms_mode *mode, int32_t *count,
+                                             float *out_bbox, int64_t *out_class, float *out_score, int32_t *out_index,
+                                             void *scratch, void *stream) {
+    PPModeArgs p;
+    dense_outputs(p, 5, topk, count, out_bbox, out_class, out_score, out_index);
+    return launch_mode<5>(p, mode, bbox, class_idx, score, B, N, conf_thres, nms_thres, topk, scratch, stream);
+}
+
+extern "C" int mydet_postprocess_records_nms_f32(const float *bbox, const int64_t *class_idx, const float *score, int B, int64_t N,
+                                                 float conf_thres, double nms_thres, const mydet_nms_mode *mode, int32_t *records,
+                                                 void *scratch, void *stream) {
+    if (!records || ((uintptr_t)records & 15)) return MYDET_E_BADARG;
+    PPModeArgs p;
+    record_outputs(p, records, false);
+    return launch_mode<4>(p, mode, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream);
+}
+
+extern "C" int mydet_postprocess_records_rot_nms_f32(const float *bbox, const int64_t *class_idx, const float *score, int B,
+                                                     int64_t N, float conf_thres, double nms_thres, const mydet_nms_mode *mode,
+                                                     int32_t *records, void *scratch, void *stream) {
+    if (!records || ((uintptr_t)records & 15)) return MYDET_E_BADARG;
+    PPModeArgs p;
+    record_outputs(p, records, true);
+    return launch_mode<5>(p, mode, bbox, class_idx, score, B, N, conf_thres, nms_thres, MYDET_REC_TOPK, scratch, stream);
+}
+
 // ---- merge of tile records (tiled detection on large frames; include/mydet.h) ----
 // The detections of T windows of a frame, already in window pixel coordinates, become the candidates of ONE more run of the
 // kernel above: a gather launch writes the B x T*512 candidate arrays into scratch (box centres shifted by the window origin),
@@ -647,9 +993,11 @@ extern "C" int64_t mydet_merge_tile_records_scratch_bytes(int B, int T, int box_
     return (int64_t)B * T * KMAX * (4 * box_width + 8 + 4 + 8);
 }
 
-extern "C" int mydet_merge_tile_records_f32(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words,
-                                            int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
-                                            int rotated_nms, int32_t *records, void *scratch, int64_t scratch_bytes, void *stream) {
+// agnostic: the merge's NMS has one group of all candidates (mydet_merge_tile_records_nms_f32); 0 is the shipped call
+static int merge_tile_records(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words,
+                              int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
+                              int rotated_nms, int agnostic, int32_t *records, void *scratch, int64_t scratch_bytes, void *stream) {
+    if (agnostic != 0 && agnostic != 1) return MYDET_E_BADARG;
     if (B <= 0 || T < 1 || T > MYDET_TILES_MAX) return MYDET_E_BADARG;
     if (box_width != 4 && box_width != 5) return MYDET_E_BADARG;
     if (metric != MYDET_MERGE_IOU && metric != MYDET_MERGE_IOS) return MYDET_E_BADARG;
@@ -660,6 +1008,7 @@ extern "C" int mydet_merge_tile_records_f32(const int32_t *tile_records, int64_t
     if (tile_stride_words < 0 || frame_stride_words < 0 || (tile_stride_words & 3) || (frame_stride_words & 3)) return MYDET_E_BADARG;
     if (scratch_bytes < mydet_merge_tile_records_scratch_bytes(B, T, box_width)) return MYDET_E_BADARG;
     if (metric == MYDET_MERGE_IOS && rotated_nms) return MYDET_E_UNSUPP;
+    if (agnostic && rotated_nms) return MYDET_E_UNSUPP;
     const int64_t N = (int64_t)T * KMAX, BN = (int64_t)B * N;
     MergeArgs a;
     a.rec = tile_records; a.tile_st = tile_stride_words; a.frame_st = frame_stride_words; a.origins = origins; a.T = T;
@@ -672,9 +1021,19 @@ extern "C" int mydet_merge_tile_records_f32(const int32_t *tile_records, int64_t
     else hipLaunchKernelGGL((merge_gather_kernel<5>), grid, dim3(256), 0, (hipStream_t)stream, a);
     const int st = mydet_launch_status();
     if (st) return st;
-    PPArgs p;
+    PPModeArgs p;
     record_outputs(p, records, box_width == 5);
     const float conf = -__builtin_inff();
+    if (agnostic) {
+        p.kind = MYDET_NMS_HARD; p.agn = 1; p.sigma = 0.0; p.min_score = 0.f;
+        if (box_width == 4)
+            return metric == MYDET_MERGE_IOS
+                       ? launch_postprocess<4, false, true, MODE_GROUPS>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream)
+                       : launch_postprocess<4, false, false, MODE_GROUPS>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream);
+        return metric == MYDET_MERGE_IOS
+                   ? launch_postprocess<5, false, true, MODE_GROUPS>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream)
+                   : launch_postprocess<5, false, false, MODE_GROUPS>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream);
+    }
     if (box_width == 4)
         return metric == MYDET_MERGE_IOS
                    ? launch_postprocess<4, false, true>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream)
@@ -683,4 +1042,19 @@ extern "C" int mydet_merge_tile_records_f32(const int32_t *tile_records, int64_t
     return metric == MYDET_MERGE_IOS
                ? launch_postprocess<5, false, true>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream)
                : launch_postprocess<5>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream);
+}
+
+extern "C" int mydet_merge_tile_records_f32(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words,
+                                            int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
+                                            int rotated_nms, int32_t *records, void *scratch, int64_t scratch_bytes, void *stream) {
+    return merge_tile_records(tile_records, tile_stride_words, frame_stride_words, B, T, box_width, origins, nms_thres, metric,
+                              rotated_nms, 0, records, scratch, scratch_bytes, stream);
+}
+
+extern "C" int mydet_merge_tile_records_nms_f32(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words,
+                                                int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
+                                                int rotated_nms, int agnostic, int32_t *records, void *scratch,
+                                                int64_t scratch_bytes, void *stream) {
+    return merge_tile_records(tile_records, tile_stride_words, frame_stride_words, B, T, box_width, origins, nms_thres, metric,
+                              rotated_nms, agnostic, records, scratch, scratch_bytes, stream);
 }

@@ -41,7 +41,7 @@ def prepared_tensors(model):
 
 
 class GraphedPath:
-    """Captured `images -> detection records` for one (batch, H, W) and one (conf, nms, rotated_nms) setting.
+    """Captured `images -> detection records` for one (batch, H, W) and one (conf, nms, rotated_nms, NMS mode) setting.
 
     `lanes`: the images of a batch are independent, so the batch can be cut into equal parts that run the whole path on
     streams of their own (fork / join inside the capture -> parallel branches of the hipGraph).  The hardware
@@ -54,12 +54,14 @@ class GraphedPath:
     last bits (grid-size dependent K cuts, exactly as a solo image differs from the same image in a batch);
     `eager()` runs the same decomposition without the graph and is bit-identical to a replay."""
 
-    def __init__(self, model, example, conf_thres, nms_thres, warmup=2, lanes=None, rotated_nms=False):
+    def __init__(self, model, example, conf_thres, nms_thres, warmup=2, lanes=None, rotated_nms=False, nms=None):
         assert example.is_cuda and example.dim() == 4
         self.model = model
         self.static_in = example.clone()
         self.conf, self.nms = float(conf_thres), float(nms_thres)
         self.rotated_nms = bool(rotated_nms)            # which post-process kernel the capture records
+        self.nms_mode = nms                             # an ops.Nms or None: the mode that kernel runs in
+        ops.nms_mode('GraphedPath', nms, conf_thres, getattr(model, 'bbox_param', 4), rotated_nms)
         self.epoch = getattr(model, 'weights_epoch', 0)
         if lanes is None:
             lanes = os.environ.get('MYDET_LANES', 'auto')
@@ -112,7 +114,7 @@ class GraphedPath:
     def _run_eager(self):
         if self.lanes == 1:
             bb, ci, sc = self.model.forward_candidates(self.static_in)
-            return (bb, ci, sc), batched_post_process(bb, ci, sc, self.conf, self.nms, rotated_nms=self.rotated_nms)
+            return (bb, ci, sc), batched_post_process(bb, ci, sc, self.conf, self.nms, rotated_nms=self.rotated_nms, nms=self.nms_mode)
         main = torch.cuda.current_stream()
         parts = self.static_in.tensor_split(self.lanes)
         # every lane writes its rows of ONE record buffer (allocated on the joining stream); the candidates stay per lane
@@ -124,7 +126,7 @@ class GraphedPath:
             with torch.cuda.stream(st), ops.lane(i):
                 bb, ci, sc = self.model.forward_candidates(part)
                 batched_post_process(bb, ci, sc, self.conf, self.nms, records=records[lo:lo + part.shape[0]],
-                                     rotated_nms=self.rotated_nms)
+                                     rotated_nms=self.rotated_nms, nms=self.nms_mode)
                 cands.append((bb, ci, sc))
             lo += part.shape[0]
         for st in self._streams:

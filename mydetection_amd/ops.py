@@ -1209,7 +1209,83 @@ def _rot_entry(width, rotated_nms, plain, rot, rotnms):
     return plain if width == 4 else (rotnms if rotated_nms else rot)
 
 
-def postprocess(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, records=None, rotated_nms=False):
+NMS_KINDS = {'hard': _lib.NMS_HARD, 'soft-linear': _lib.NMS_SOFT_LINEAR, 'soft-gaussian': _lib.NMS_SOFT_GAUSSIAN,
+             'merge': _lib.NMS_MERGE}                                      # MYDET_NMS_* of include/mydet.h
+
+
+class Nms:
+    """How the post-process suppresses, the `nms=` argument of ops.postprocess, ImageObjects.post_process and the Detector
+    methods (include/mydet.h, "NMS modes", has the rules the kernel is held to).  kind: 'hard' (greedy, the default),
+    'soft-linear' or 'soft-gaussian' (Soft-NMS, Bodla et al. 2017: overlapped boxes lose score instead of being removed; the
+    output scores are the decayed ones) or 'merge' (hard NMS, then every kept box becomes the score-weighted mean of the
+    boxes it suppressed and itself).  agnostic: all classes are one group -- two classes on one box leave one box.  sigma:
+    the width of the Gaussian decay exp(-iou^2 / sigma).  min_score: a soft kind stops emitting a group at the first score
+    below it; None = the call's conf_thres.  Immutable; compares and hashes by value.  Touches no device."""
+    __slots__ = ('kind', 'agnostic', 'sigma', 'min_score')
+
+    def __init__(self, kind='hard', agnostic=False, sigma=0.5, min_score=None):
+        if not isinstance(kind, str) or kind not in NMS_KINDS:
+            raise ValueError(f'Nms: kind {kind!r} is not one of {sorted(NMS_KINDS)}')
+        if not isinstance(agnostic, (bool, int)) or agnostic not in (0, 1):
+            raise ValueError(f'Nms: agnostic is True or False, got {agnostic!r}')
+        try:
+            sigma = float(sigma)
+            min_score = None if min_score is None else float(min_score)
+        except (TypeError, ValueError):
+            raise ValueError(f'Nms: sigma and min_score are numbers, got {sigma!r} and {min_score!r}') from None
+        if not (0 < sigma < math.inf):
+            raise ValueError(f'Nms: sigma {sigma!r} is not a finite number above 0')
+        if min_score is not None and not (0 <= min_score < math.inf):
+            raise ValueError(f'Nms: min_score {min_score!r} is not a finite number >= 0 (or None: the conf_thres of the call)')
+        for name, v in zip(self.__slots__, (kind, bool(agnostic), sigma, min_score)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('Nms is immutable')
+
+    def _key(self):
+        return (self.kind, self.agnostic, self.sigma, self.min_score)
+
+    def __eq__(self, other):
+        return isinstance(other, Nms) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f'Nms({self.kind!r}, agnostic={self.agnostic}, sigma={self.sigma}, min_score={self.min_score})'
+
+    @property
+    def plain(self):
+        """The class-aware hard NMS: what a call without `nms=` runs."""
+        return self.kind == 'hard' and not self.agnostic
+
+
+def nms_mode(what, nms, conf_thres, box_width, rotated_nms=False):
+    """The _lib.NmsMode of an `nms=` argument for candidates of `box_width` floats, or None for today's call (nms None, or
+    the plain hard NMS together with rotated_nms).  Raises for what the library has no kernel for or rejects -- a TypeError
+    for anything but an Nms, a ValueError otherwise -- before any device is touched."""
+    if nms is None:
+        return None
+    if not isinstance(nms, Nms):
+        raise TypeError(f'{what}: nms is a mydetection_amd.api.Nms (or None), got {type(nms).__name__}')
+    if rotated_nms:
+        if nms.plain:
+            return None
+        raise ValueError(f'{what}: rotated_nms compares rotated rectangles under the class-aware hard NMS only, not with {nms!r}')
+    conf = float(conf_thres)
+    if nms.kind == 'merge':
+        if box_width != 4:
+            raise ValueError(f"{what}: Nms('merge') needs 'cxcywh' boxes; a mean of the angles of 'cxcywhd' boxes is not defined")
+        if not conf > 0:
+            raise ValueError(f"{what}: Nms('merge') weighs boxes by their scores and needs conf_thres > 0, got {conf_thres!r}")
+    if nms.kind in ('soft-linear', 'soft-gaussian') and not conf >= 0:
+        raise ValueError(f'{what}: Nms({nms.kind!r}) decays scores towards 0 and needs conf_thres >= 0, got {conf_thres!r}')
+    min_score = conf if nms.min_score is None else nms.min_score
+    return _lib.NmsMode(NMS_KINDS[nms.kind], int(nms.agnostic), nms.sigma, min_score, 0)
+
+
+def postprocess(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, records=None, rotated_nms=False, nms=None):
     """Batched filter/top-k/class-aware NMS.  bbox [B,N,4], class_idx [B,N] i64, score [B,N].  bbox [B,N,5]
     (cxcywhd) takes the rotated kernel: the same decisions on columns 0-3, rotated records ('angle' added).
     rotated_nms=True (cxcywhd only, ValueError otherwise): the NMS compares the rotated rectangles -- exact intersection
@@ -1219,9 +1295,14 @@ def postprocess(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, record
     index [B,512] i32 -- all views of 'records' (int32 [B, REC_WORDS]), which the kernel writes directly in the
     wire layout of the all-gather (parallel.gather_detections).  Class ids must lie in [0, 4096): an image whose
     selected candidates break that gets count = -1 (`check_counts` raises on it) instead of aliased classes.
+    nms: None, or an Nms -- class-agnostic suppression, Soft-NMS or box merging in the same launch (include/mydet.h, "NMS
+    modes": the mydet_postprocess_records_*nms_f32 entry points); not with rotated_nms (ValueError).
     """
     fn = _rot_entry(bbox.shape[-1], rotated_nms, 'mydet_postprocess_records_f32', 'mydet_postprocess_records_rot_f32',
                     'mydet_postprocess_records_rotnms_f32')
+    mode = nms_mode('postprocess', nms, conf_thres, bbox.shape[-1], rotated_nms)
+    if mode is not None:
+        fn = 'mydet_postprocess_records_nms_f32' if bbox.shape[-1] == 4 else 'mydet_postprocess_records_rot_nms_f32'
     require_gpu(bbox, 'postprocess')
     assert bbox.dtype == torch.float32 and score.dtype == torch.float32 and class_idx.dtype == torch.int64
     assert topk == TOPK
@@ -1234,19 +1315,22 @@ def postprocess(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, record
     assert records.dtype == torch.int32 and tuple(records.shape) == (B, words) and records.is_contiguous()
     scratch = torch.empty((B, max(N, 1)), dtype=torch.int64, device=dev)
     t0 = TIMER.start() if TIMER else None
-    code = getattr(_lib.lib(), fn)(_ptr(bbox), _ptr(class_idx), _ptr(score), B, N, float(conf_thres), float(nms_thres),
-                                   _ptr(records), _ptr(scratch), _stream())
+    args = (_ptr(bbox), _ptr(class_idx), _ptr(score), B, N, float(conf_thres), float(nms_thres))
+    code = getattr(_lib.lib(), fn)(*args, *(() if mode is None else (ctypes.byref(mode),)), _ptr(records), _ptr(scratch), _stream())
     if t0:
         TIMER.stop('postprocess', t0, float(B))
     _lib.check(code, fn)
     return record_views(records)
 
 
-def postprocess_dense(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, rotated_nms=False):
+def postprocess_dense(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, rotated_nms=False, nms=None):
     """The same filter/top-k/NMS into dense per-image arrays (mydet_postprocess_f32, or mydet_postprocess_rot_f32 for
     bbox [B,N,5], mydet_postprocess_rotnms_f32 with rotated_nms): count [B] i32, bbox [B,topk,4 or 5], class_idx [B,topk] i64,
-    score [B,topk], index [B,topk] i32."""
+    score [B,topk], index [B,topk] i32.  nms: as in postprocess (mydet_postprocess_nms_f32 / mydet_postprocess_rot_nms_f32)."""
     fn = _rot_entry(bbox.shape[-1], rotated_nms, 'mydet_postprocess_f32', 'mydet_postprocess_rot_f32', 'mydet_postprocess_rotnms_f32')
+    mode = nms_mode('postprocess_dense', nms, conf_thres, bbox.shape[-1], rotated_nms)
+    if mode is not None:
+        fn = 'mydet_postprocess_nms_f32' if bbox.shape[-1] == 4 else 'mydet_postprocess_rot_nms_f32'
     require_gpu(bbox, 'postprocess_dense')
     assert bbox.dtype == torch.float32 and score.dtype == torch.float32 and class_idx.dtype == torch.int64
     bbox, class_idx, score = bbox.contiguous(), class_idx.contiguous(), score.contiguous()
@@ -1260,9 +1344,9 @@ def postprocess_dense(bbox, class_idx, score, conf_thres, nms_thres, topk=TOPK, 
            'score': torch.empty((B, topk), dtype=torch.float32, device=dev),
            'index': torch.empty((B, topk), dtype=torch.int32, device=dev)}
     scratch = torch.empty((B, max(N, 1)), dtype=torch.int64, device=dev)
-    code = getattr(_lib.lib(), fn)(_ptr(bbox), _ptr(class_idx), _ptr(score), B, N, float(conf_thres), float(nms_thres),
-                                   int(topk), _ptr(out['count']), _ptr(out['bbox']), _ptr(out['class_idx']),
-                                   _ptr(out['score']), _ptr(out['index']), _ptr(scratch), _stream())
+    args = (_ptr(bbox), _ptr(class_idx), _ptr(score), B, N, float(conf_thres), float(nms_thres), int(topk))
+    code = getattr(_lib.lib(), fn)(*args, *(() if mode is None else (ctypes.byref(mode),)), _ptr(out['count']), _ptr(out['bbox']),
+                                   _ptr(out['class_idx']), _ptr(out['score']), _ptr(out['index']), _ptr(scratch), _stream())
     _lib.check(code, fn)
     return out
 
@@ -1317,16 +1401,19 @@ def merge_metric_id(metric):
     return MERGE_METRICS[metric]
 
 
-def merge_tile_records(rec, B, T, origins, nms_thres, metric='iou', rotated_nms=False, records=None):
+def merge_tile_records(rec, B, T, origins, nms_thres, metric='iou', rotated_nms=False, records=None, agnostic=False):
     """The records of T windows of each of B frames -> B records in frame coordinates, by one more class-aware NMS on the
     device (include/mydet.h: mydet_merge_tile_records_f32, where the candidate order, the tie rule and the pair tests are).
     rec: the window records, boxes in window pixel coordinates -- an int32 tensor [T*B, words] (tile-major: window t of
     frame b in row t*B + b) or [T, B, words] with any strides along T and B (a frame-major buffer is
     buf.view(B, T, words).transpose(0, 1)), or the record_views dict of such a [T*B, words] buffer.  origins: T pairs
     (x0, y0), or an int32 device tensor [T, 2].  metric: 'iou' or 'ios' (intersection over the smaller area); rotated_nms:
-    the rotated-IoU test (rotated records and 'iou' only).  records: optional int32 [B, words] buffer to write.  Returns the
-    record_views dict of the merged records; 'index' holds t*512 + k of every survivor."""
+    the rotated-IoU test (rotated records and 'iou' only).  records: optional int32 [B, words] buffer to write.  agnostic:
+    the merge's NMS has one group of all classes (mydet_merge_tile_records_nms_f32; both metrics, not with rotated_nms).
+    Returns the record_views dict of the merged records; 'index' holds t*512 + k of every survivor."""
     m = merge_metric_id(metric)
+    if agnostic and rotated_nms:
+        raise ValueError('merge_tile_records: agnostic is defined for the axis-aligned tests only, not with rotated_nms')
     if isinstance(rec, dict):
         rec = _record_buffer('merge_tile_records', rec)
     require_gpu(rec, 'merge_tile_records')
@@ -1361,11 +1448,12 @@ def merge_tile_records(rec, B, T, origins, nms_thres, metric='iou', rotated_nms=
     nbytes = _lib.lib().mydet_merge_tile_records_scratch_bytes(B, T, width)
     scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
     t0 = TIMER.start() if TIMER else None
-    code = _lib.lib().mydet_merge_tile_records_f32(_ptr(rec), rec.stride(0), rec.stride(1), B, T, width, _ptr(org), float(nms_thres), m,
-                                                   int(bool(rotated_nms)), _ptr(records), _ptr(scratch), nbytes, _stream())
+    head = (_ptr(rec), rec.stride(0), rec.stride(1), B, T, width, _ptr(org), float(nms_thres), m, int(bool(rotated_nms)))
+    fn = 'mydet_merge_tile_records_nms_f32' if agnostic else 'mydet_merge_tile_records_f32'
+    code = getattr(_lib.lib(), fn)(*head, *((1,) if agnostic else ()), _ptr(records), _ptr(scratch), nbytes, _stream())
     if t0:
         TIMER.stop('merge_tile_records', t0, float(B))
-    _lib.check(code, 'mydet_merge_tile_records_f32')
+    _lib.check(code, fn)
     return record_views(records)
 
 

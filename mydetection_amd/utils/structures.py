@@ -105,35 +105,41 @@ class ImageObjects():
         return ImageObjects(ops.record_boxes(rec, b, k), rec['class_idx'][b, :k], None, rec['score'][b, :k],
                             self._bb_format, img_hw=self.img_hw)
 
-    def post_process(self, conf_thres, nms_thres, rotated_nms=False):
+    def post_process(self, conf_thres, nms_thres, rotated_nms=False, nms=None):
         '''
         Confidence threshold + top-512 + class-aware NMS (reference: utils/structures.py:92-106),
         one HIP launch.  Returns a new ImageObjects whose tensors stay on the device.
         rotated_nms: compare the rotated rectangles ('cxcywhd' only; ValueError otherwise).
+        nms: None, or an ops.Nms (class-agnostic suppression, Soft-NMS, box merging; not with rotated_nms: ValueError).
         '''
         assert self.masks is None
         assert self.scores is not None
         _check_rotated(rotated_nms, self._bb_format)
         if self._bb_format not in _BOX_WIDTH:
             raise NotImplementedError()
+        ops.nms_mode('post_process', nms, conf_thres, _BOX_WIDTH[self._bb_format], rotated_nms)     # the rules, before any device
         bb, cats, sc = self._device_fields()
-        rec = ops.postprocess(bb[None], cats[None], sc[None], conf_thres, nms_thres, TOPK, rotated_nms=rotated_nms)
+        rec = ops.postprocess(bb[None], cats[None], sc[None], conf_thres, nms_thres, TOPK, rotated_nms=rotated_nms, nms=nms)
         return self._from_records(rec)
 
-    def nms(self, nms_thres=0.45, rotated=False):
-        return ImageObjects.non_max_suppression(self, nms_thres, rotated=rotated)
+    def nms(self, nms_thres=0.45, rotated=False, nms=None):
+        return ImageObjects.non_max_suppression(self, nms_thres, rotated=rotated, nms=nms)
 
     @staticmethod
-    def non_max_suppression(dts, nms_thres: float, rotated=False):
+    def non_max_suppression(dts, nms_thres: float, rotated=False, nms=None):
         '''
         Class-aware NMS (reference: utils/structures.py:111-173).  At most 512 boxes, as in the
         reference call chain (post_process caps at 512 before calling nms).
         rotated: compare the rotated rectangles ('cxcywhd' only; ValueError otherwise).
+        nms: None, or an ops.Nms with agnostic alone (every box is a candidate here, whatever its score; the soft kinds and
+        'merge' need a confidence threshold and raise ValueError: use post_process).
         '''
         assert isinstance(dts, ImageObjects)
         assert dts.masks is None, 'nms with masks is not currently supported'
         assert dts.scores is not None
         _check_rotated(rotated, dts._bb_format)
+        if dts._bb_format in _BOX_WIDTH:
+            ops.nms_mode('non_max_suppression', nms, float('-inf'), _BOX_WIDTH[dts._bb_format], rotated)
         if dts.bboxes.shape[0] == 0:
             return dts
         if dts._bb_format not in _BOX_WIDTH:
@@ -141,7 +147,7 @@ class ImageObjects():
         if len(dts) > TOPK:
             raise NotImplementedError(f'non_max_suppression handles at most {TOPK} boxes per image')
         bb, cats, sc = dts._device_fields()
-        rec = ops.postprocess(bb[None], cats[None], sc[None], float('-inf'), nms_thres, TOPK, rotated_nms=rotated)
+        rec = ops.postprocess(bb[None], cats[None], sc[None], float('-inf'), nms_thres, TOPK, rotated_nms=rotated, nms=nms)
         return dts._from_records(rec)
 
     def bboxes_to_original_(self, pad_info):
@@ -291,7 +297,7 @@ def batched_to_json(rec, img_ids, eval_type='x1y1wh', catIdx2id=None) -> list:
     return out
 
 
-def batched_post_process(bboxes, cats, scores, conf_thres, nms_thres, records=None, rotated_nms=False):
+def batched_post_process(bboxes, cats, scores, conf_thres, nms_thres, records=None, rotated_nms=False, nms=None):
     '''
     The batched form of `for d in dts: d.post_process(...)` (examples/train.py:229-232):
     bboxes [B,N,4], cats [B,N], scores [B,N] on the device -> fixed-size records
@@ -300,5 +306,6 @@ def batched_post_process(bboxes, cats, scores, conf_thres, nms_thres, records=No
     records: optional int32 [B, REC_WORDS] buffer (REC_ROT_WORDS for rotated boxes) to write (rows of a larger batch's
     record buffer).
     rotated_nms: the NMS compares the rotated rectangles (cxcywhd only; ValueError for [B,N,4]); same rotated records.
+    nms: None, or an ops.Nms (class-agnostic suppression, Soft-NMS, box merging in the same launch; not with rotated_nms).
     '''
-    return ops.postprocess(bboxes, cats, scores, conf_thres, nms_thres, TOPK, records=records, rotated_nms=rotated_nms)
+    return ops.postprocess(bboxes, cats, scores, conf_thres, nms_thres, TOPK, records=records, rotated_nms=rotated_nms, nms=nms)
