@@ -273,8 +273,8 @@ int mydet_conv_stem_p3_f32(const float *x, int64_t sxb, int64_t sxc, int64_t sxh
                            const float *shift1, int act1, float *y, int64_t ldy, int B, int H, int W, int C0, int Cout,
                            int stride0, int pad_t, int pad_l, int Hs, int Ws, int stride1, void *stream);
 int mydet_conv_stem_p3_lds_bytes(void);               /* dynamic LDS of that launch (one resident patch slab + the image patch) */
-/* Test hook: the split-bf16 launcher reads MYDET_B3_WIDE / MYDET_B3_WAVES once per process; this reads them again.
- * Returns the form bits (1 = wide 128 x 256 tiles from 192 output channels, 2 = 8-wave workgroups). */
+/* Test hook: the split-bf16 launcher reads MYDET_B3_WIDE / MYDET_B3_WAVES / MYDET_B3_HALF_TILES once per process; this reads them
+ * again.  Returns the form bits (1 = wide 128 x 256 tiles from 192 output channels, 2 = 8-wave workgroups). */
 int mydet_conv_b3_reload_tuning(void);
 
 /* Test / tuning hook: workgroups per CU the runtime reports (hipOccupancyMaxActiveBlocksPerMultiprocessor) for the
@@ -291,6 +291,15 @@ int mydet_conv_igemm_occupancy(int cfg, int *assumed);
  * No reference counterpart. */
 int mydet_conv_igemm_plan(int cfg, int B, int Ho, int Wo, int Cin, int Cout, int taps,
                           int64_t workspace_bytes, int cus, int32_t *out);
+/* Test hook (host only, no GPU call): the plan mydet_conv2d_igemm_b3_f32 uses for a layer on a chip of `cus` CUs, under the
+ * MYDET_B3_* switches as last read.  out[7] = {form (0 default, 1 wide, 2 8-wave), BM, BN, waves along N, workgroups of the main
+ * launch, tail tiles cut along K (0 = no tail), cuts per tail tile (1 = no tail)}.  taps = KH * KW; gated != 0: with a squeeze-excite
+ * gate (the opt-in forms have no gated instance: the default form runs); workspace_bytes <= 0 = no workspace (never a tail).
+ * It is the launcher's own arithmetic, not a copy: the form choice and the round / K-cut rule are the function the launch calls.
+ * Returns 0, MYDET_E_BADARG, or MYDET_E_UNSUPP for the channel counts the entry point refuses (Cin % 16 with more than one tap,
+ * Cin % 4, Cin % 16 under the wide form with Cout > 192).  No reference counterpart. */
+int mydet_conv_b3_plan(int B, int Ho, int Wo, int Cin, int Cout, int taps, int gated, int64_t workspace_bytes, int cus,
+                       int32_t *out);
 
 /* Focus.forward of the Ultralytics backbone (external/ultralytics/common.py:79-86): 2x2 space-to-depth,
  *   y[b, yo, xo, g*C + c] = x[b, c, 2*yo + dy, 2*xo + dx],  g = 0:(dy 0, dx 0) 1:(dy 1, dx 0) 2:(dy 0, dx 1) 3:(dy 1, dx 1)

@@ -29,6 +29,7 @@ SIGNATURES = {
     'mydet_conv_b3_reload_tuning': [],
     'mydet_conv_igemm_occupancy': [c_int, c_ptr],
     'mydet_conv_igemm_plan': [c_int] * 7 + [c_i64, c_int, c_ptr],
+    'mydet_conv_b3_plan': [c_int] * 7 + [c_i64, c_int, c_ptr],
     'mydet_split_bf16_elems': [c_int, c_int],
     'mydet_split_bf16_f32': [c_ptr, c_int, c_int, c_ptr, c_ptr],
     'mydet_conv2d_igemm_b3_f32': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64] + [c_int] * 13 + [c_ptr],

@@ -983,23 +983,85 @@ int launch_b3_inst(const ConvArgs &a, hipStream_t stream) {
     return mydet_launch_status();
 }
 
-template <int BM, int BN, int WN = 2>
-int launch_b3(const ConvArgs &a0, hipStream_t stream) {
-    ConvArgs a = a0;
-    const int slots = 2 * mydet_cu_count();
-    const int mtiles = (a.M + BM - 1) / BM;
-    a.ntiles = (a.Cout + BN - 1) / BN;
-    const int total = mtiles * a.ntiles;
-    const int nk = (a.K + 15) / 16;
+// The launch plan of the split-bf16 implicit GEMM (host only): one function for mydet_conv2d_igemm_b3_f32's launches and for
+// mydet_conv_b3_plan.  The tile form first, then the round / K-cut-tail rule of `plan_tiles` with this kernel's numbers: two
+// workgroups per CU (the wide form: one), 16-wide slabs, a tail only from 64 slabs, a small grid cut as a whole only from 32.
+struct B3Plan {
+    int form;               // 0 default (4-wave workgroups), 1 wide (128 x 256 tile, 8 waves), 2 8-wave 128 x 128
+    int BM, BN, WN;         // tile, waves along N
+    int ntiles, total;      // tiles along N, tiles in all
+    int rem, splits;        // tiles past the last whole round, K slices each of them would be cut into
+    bool split;             // the remainder runs as a K-cut tail
+};
+
+// The three switches of the form choice, read once per process; mydet_conv_b3_reload_tuning reads them again.
+int g_b3_form = -1;         // bit 0: MYDET_B3_WIDE=1, bit 1: MYDET_B3_WAVES=8
+bool g_b3_half_set = false; // MYDET_B3_HALF_TILES is set ...
+int g_b3_half = 0;          // ... to this (otherwise the limit is cus / 2)
+int b3_form() {
+    if (g_b3_form < 0) {
+        const char *w = getenv("MYDET_B3_WIDE"), *v = getenv("MYDET_B3_WAVES"), *h = getenv("MYDET_B3_HALF_TILES");
+        g_b3_half_set = h != nullptr;
+        g_b3_half = h ? atoi(h) : 0;
+        g_b3_form = ((w && *w == '1') ? 1 : 0) | ((v && atoi(v) == 8) ? 2 : 0);
+    }
+    return g_b3_form;
+}
+
+// Channel counts no form takes (MYDET_E_UNSUPP), 0 otherwise.  A 16-channel slab never straddles taps: Cin % 16 == 0, or ONE tap
+// (1x1) with Cin % 4 == 0 (the last slab's missing channels: zeros); the opt-in wide form has no padded-K instance.
+int b3_refuses(int Cin, int Cout, bool one_tap) {
+    if ((Cin & 15) && !(one_tap && !(Cin & 3))) return MYDET_E_UNSUPP;
+    if ((Cin & 15) && (Cout > 192 ? b3_form() & 1 : 0)) return MYDET_E_UNSUPP;
+    return 0;
+}
+
+B3Plan plan_b3(int64_t M64, int K, int Cout, bool gated, size_t ws_bytes, int cus) {
+    B3Plan pl;
+    const int tuned = b3_form();
+    pl.form = 0; pl.WN = 2;
+    if (Cout <= 64) {
+        pl.BM = 128; pl.BN = 64;
+    } else if (((M64 + 127) / 128) * ((Cout + 127) / 128) <= (g_b3_half_set ? g_b3_half : cus / 2)) {
+        // at most half as many 128-row tiles as CUs (the EfficientNet project convs on a lane of 8-16 images): 64-row tiles, twice the
+        // workgroups.  MYDET_B3_HALF_TILES overrides the limit (0 = never; tuning)
+        pl.BM = 64; pl.BN = 128;
+    } else {
+        // two other forms stay selectable, both correct and tested, neither faster:
+        //   MYDET_B3_WIDE=1  from 192 output channels a 128 x 256 tile, one 8-wave workgroup per CU, weights by LDS-DMA -- 0.66 / 0.75
+        //                    / 0.66 ms vs 0.65 / 0.69 / 0.69 on the three deep stride-2 layers, 1 538 vs 1 545 images/s in the model;
+        //   MYDET_B3_WAVES=8 8-wave workgroups (wave tile 64 x 32, four waves per SIMD) -- 5-10 % faster back to back, 0.7 % slower
+        //                    in the model (1 510 vs 1 520 images/s, twice each in one call)
+        const int form = gated ? 0 : tuned;             // (the opt-in forms have no gated instances)
+        pl.BM = 128; pl.BN = 128;
+        if ((form & 1) && Cout > 192) { pl.form = 1; pl.BN = 256; pl.WN = 4; }
+        else if (form & 2) { pl.form = 2; pl.WN = 4; }
+    }
+    // the wide form: one workgroup per CU, so a round is `cus` tiles (and Cin % 16 == 0: whole slabs)
+    const int slots = pl.form == 1 ? cus : 2 * cus;
+    const int nk = pl.form == 1 ? K / 16 : (K + 15) / 16;
+    const int mtiles = (int)((M64 + pl.BM - 1) / pl.BM);
+    pl.ntiles = (Cout + pl.BN - 1) / pl.BN;
+    const int total = pl.total = mtiles * pl.ntiles;
     const int rounds = total / slots;
-    const int rem = total % slots;
+    const int rem = pl.rem = total % slots;
     const bool small = rounds == 0 && total * 4 <= slots && nk >= 32;
     int splits = rem > 0 ? slots / rem : 0;
     if (splits > 16) splits = 16;
     if (splits > nk / 8) splits = nk / 8;
-    const size_t need = (size_t)rem * (splits > 0 ? splits : 0) * BM * BN * sizeof(float);
-    const bool split = rem > 0 && splits >= 2 && a0.ws && need <= a0.ws_bytes &&
-                       (small || (nk >= 64 && rounds >= 2 && rounds <= 4 && rem * 2 <= slots));
+    pl.splits = splits;
+    const size_t need = (size_t)rem * (splits > 0 ? splits : 0) * pl.BM * pl.BN * sizeof(float);
+    pl.split = rem > 0 && splits >= 2 && ws_bytes > 0 && need <= ws_bytes &&
+               (small || (nk >= 64 && rounds >= 2 && rounds <= 4 && rem * 2 <= slots));
+    return pl;
+}
+
+template <int BM, int BN, int WN = 2>
+int launch_b3(const ConvArgs &a0, const B3Plan &pl, hipStream_t stream) {
+    ConvArgs a = a0;
+    a.ntiles = pl.ntiles;
+    const int total = pl.total, rem = pl.rem, splits = pl.splits;
+    const bool split = pl.split;
     a.tile0 = 0; a.splits = 1;
     a.nblk = split ? total - rem : total;
     const bool res = a.res != nullptr;
@@ -1039,24 +1101,13 @@ int launch_b3w_inst(const ConvArgs &a, hipStream_t stream) {
     return mydet_launch_status();
 }
 
-// the wide form: one workgroup per CU, so a round is `cus` tiles; same split-K-tail rule otherwise
-int launch_b3w(const ConvArgs &a0, hipStream_t stream) {
+// the wide form (plan_b3: one workgroup per CU, so a round is `cus` tiles; same split-K-tail rule otherwise)
+int launch_b3w(const ConvArgs &a0, const B3Plan &pl, hipStream_t stream) {
     constexpr int BM = 128, BN = 256;
     ConvArgs a = a0;
-    const int slots = mydet_cu_count();
-    const int mtiles = (a.M + BM - 1) / BM;
-    a.ntiles = (a.Cout + BN - 1) / BN;
-    const int total = mtiles * a.ntiles;
-    const int nk = a.K / 16;
-    const int rounds = total / slots;
-    const int rem = total % slots;
-    const bool small = rounds == 0 && total * 4 <= slots && nk >= 32;
-    int splits = rem > 0 ? slots / rem : 0;
-    if (splits > 16) splits = 16;
-    if (splits > nk / 8) splits = nk / 8;
-    const size_t need = (size_t)rem * (splits > 0 ? splits : 0) * BM * BN * sizeof(float);
-    const bool split = rem > 0 && splits >= 2 && a0.ws && need <= a0.ws_bytes &&
-                       (small || (nk >= 64 && rounds >= 2 && rounds <= 4 && rem * 2 <= slots));
+    a.ntiles = pl.ntiles;
+    const int total = pl.total, rem = pl.rem, splits = pl.splits;
+    const bool split = pl.split;
     a.tile0 = 0; a.splits = 1;
     a.nblk = split ? total - rem : total;
     const bool res = a.res != nullptr;
@@ -1242,15 +1293,7 @@ extern "C" int mydet_split_bf16_f32(const float *w, int Cout, int K, uint16_t *p
     return mydet_launch_status();
 }
 
-static int g_b3_form = -1;
-static int b3_form() {
-    if (g_b3_form < 0) {
-        const char *w = getenv("MYDET_B3_WIDE"), *v = getenv("MYDET_B3_WAVES");
-        g_b3_form = ((w && *w == '1') ? 1 : 0) | ((v && atoi(v) == 8) ? 2 : 0);
-    }
-    return g_b3_form;
-}
-/* Test hook: read MYDET_B3_WIDE / MYDET_B3_WAVES again (they are read once per process otherwise). */
+/* Test hook: read MYDET_B3_WIDE / MYDET_B3_WAVES / MYDET_B3_HALF_TILES again (they are read once per process otherwise). */
 extern "C" int mydet_conv_b3_reload_tuning(void) {
     g_b3_form = -1;
     return b3_form();
@@ -1269,9 +1312,7 @@ extern "C" int mydet_conv2d_igemm_b3_f32(const float *x, int64_t ldx, const uint
         return MYDET_E_BADARG;
     if (act < 0 || act > 2) return MYDET_E_BADARG;
     if (a_gate && (KH != 1 || KW != 1 || ((uintptr_t)a_gate & 15))) return MYDET_E_BADARG;
-    // a 16-channel slab never straddles taps: Cin % 16 == 0, or ONE tap (1x1) with Cin % 4 == 0 (the last slab's missing channels: zeros)
-    if (((Cin & 15) && !(KH == 1 && KW == 1 && !(Cin & 3))) || (ldy & 3) || (residual && (ldr & 3))) return MYDET_E_UNSUPP;
-    if ((Cin & 15) && (Cout > 192 ? b3_form() & 1 : 0)) return MYDET_E_UNSUPP;          // (the opt-in wide form has no padded-K instance)
+    if (b3_refuses(Cin, Cout, KH == 1 && KW == 1) || (ldy & 3) || (residual && (ldr & 3))) return MYDET_E_UNSUPP;
     const int64_t M64 = (int64_t)B * Ho * Wo, K64 = (int64_t)KH * KW * Cin;
     if (M64 > (int64_t)1 << 30 || K64 > (int64_t)1 << 30) return MYDET_E_BADARG;
     const int64_t img_bytes = (int64_t)H * W * ldx * 4;
@@ -1288,20 +1329,31 @@ extern "C" int mydet_conv2d_igemm_b3_f32(const float *x, int64_t ldx, const uint
     a.x1 = nullptr; a.ldx1 = 0; a.C1 = 0; a.wsplit = w_planes;
     a.ws = ((uintptr_t)workspace & 15) ? nullptr : (float *)workspace;
     a.ws_bytes = workspace_bytes > 0 ? (size_t)workspace_bytes : 0;
-    if (Cout <= 64) return launch_b3<128, 64>(a, (hipStream_t)stream);
-    // two other forms stay selectable (read once; mydet_conv_b3_reload_tuning re-reads), both correct and tested, neither faster:
-    //   MYDET_B3_WIDE=1  from 192 output channels a 128 x 256 tile, one 8-wave workgroup per CU, weights by LDS-DMA -- 0.66 / 0.75
-    //                    / 0.66 ms vs 0.65 / 0.69 / 0.69 on the three deep stride-2 layers, 1 538 vs 1 545 images/s in the model;
-    //   MYDET_B3_WAVES=8 8-wave workgroups (wave tile 64 x 32, four waves per SIMD) -- 5-10 % faster back to back, 0.7 % slower
-    //                    in the model (1 510 vs 1 520 images/s, twice each in one call)
-    // at most half as many 128-row tiles as CUs (the EfficientNet project convs on a lane of 8-16 images): 64-row tiles, twice the
-    // workgroups.  MYDET_B3_HALF_TILES overrides the limit (0 = never; tuning)
-    static const int half_tiles = [] { const char *e = getenv("MYDET_B3_HALF_TILES"); return e ? atoi(e) : mydet_cu_count() / 2; }();
-    if (((M64 + 127) / 128) * ((Cout + 127) / 128) <= half_tiles) return launch_b3<64, 128>(a, (hipStream_t)stream);
-    const int form = a_gate ? 0 : b3_form();            // (the opt-in forms have no gated instances)
-    if ((form & 1) && Cout > 192) return launch_b3w(a, (hipStream_t)stream);
-    if (form & 2) return launch_b3<128, 128, 4>(a, (hipStream_t)stream);
-    return launch_b3<128, 128>(a, (hipStream_t)stream);
+    const B3Plan pl = plan_b3(M64, (int)K64, Cout, a_gate != nullptr, a.ws ? a.ws_bytes : 0, mydet_cu_count());
+    hipStream_t s = (hipStream_t)stream;
+    if (pl.form == 1) return launch_b3w(a, pl, s);
+    if (pl.form == 2) return launch_b3<128, 128, 4>(a, pl, s);
+    if (pl.BN == 64) return launch_b3<128, 64>(a, pl, s);
+    if (pl.BM == 64) return launch_b3<64, 128>(a, pl, s);
+    return launch_b3<128, 128>(a, pl, s);
+}
+
+/* Test hook (host only, no GPU call): the plan mydet_conv2d_igemm_b3_f32 uses for a layer on a chip of `cus` CUs (include/mydet.h). */
+extern "C" int mydet_conv_b3_plan(int B, int Ho, int Wo, int Cin, int Cout, int taps, int gated, int64_t workspace_bytes, int cus,
+                                  int32_t *out) {
+    if (!out || B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || taps <= 0 || cus <= 0 || cus > (1 << 20)) return MYDET_E_BADARG;
+    if (gated && taps != 1) return MYDET_E_BADARG;
+    if (b3_refuses(Cin, Cout, taps == 1)) return MYDET_E_UNSUPP;
+    const int64_t M64 = (int64_t)B * Ho * Wo, K64 = (int64_t)taps * Cin;
+    if (M64 > (int64_t)1 << 30 || K64 > (int64_t)1 << 30) return MYDET_E_BADARG;
+    // (the entry point's size limits that do not need the strides: the output at ldy = Cout -- which also keeps the tile count in an int)
+    if (M64 * Cout * 4 >= 0x7FFFFFF0ll || taps > 31 || mydet_split_bf16_elems(Cout, (int)K64) * 2 >= 0x7FFFFFF0ll) return MYDET_E_UNSUPP;
+    const B3Plan pl = plan_b3(M64, (int)K64, Cout, gated != 0, workspace_bytes > 0 ? (size_t)workspace_bytes : 0, cus);
+    out[0] = pl.form; out[1] = pl.BM; out[2] = pl.BN; out[3] = pl.WN;
+    out[4] = pl.split ? pl.total - pl.rem : pl.total;
+    out[5] = pl.split ? pl.rem : 0;
+    out[6] = pl.split ? pl.splits : 1;
+    return 0;
 }
 
 /* Test / tuning hook: workgroups per CU the runtime reports for the base instance of tile configuration `cfg`

@@ -321,6 +321,20 @@ def b3_takes(M, Cin, Cout, k, min_rows=None, min_cout=128):
     return M >= B3_MIN_ROWS and 2.0 * M * k * k * Cin * Cout >= B3_MIN_FLOP
 
 
+B3Plan = collections.namedtuple('B3Plan', 'form bm bn wn main tail cuts')
+B3_FORM_DEFAULT, B3_FORM_WIDE, B3_FORM_WAVES8 = 0, 1, 2
+
+
+def b3_plan(B, Ho, Wo, Cin, Cout, taps, gated=False, workspace_bytes=None, cus=256):
+    """The launch plan of mydet_conv2d_igemm_b3_f32 for a layer on a chip of `cus` CUs (mydet_conv_b3_plan: the launcher's own function,
+    host only, under the MYDET_B3_* switches as last read): tile form, BM x BN tile, waves along N, workgroups of the main launch,
+    tail tiles cut along K and cuts per tail tile (0 / 1: no tail).  A negative MYDET_E_* code for a shape the entry point refuses."""
+    out = (ctypes.c_int32 * 7)()
+    ws = WORKSPACE_BYTES if workspace_bytes is None else workspace_bytes
+    code = _lib.lib().mydet_conv_b3_plan(B, Ho, Wo, Cin, Cout, taps, int(bool(gated)), ws, cus, out)
+    return code if code else B3Plan(*out)
+
+
 # conv_p3_kernel (csrc/conv_p3.hip: 3x3 conv with the workgroup's input patch resident in LDS, split-bf16 operands) takes a 3x3 pad-1
 # layer when its 128-pixel tiles are mostly real pixels (P3_MIN_FILL; ragged 8 x 16 tiles waste their rows -- without strip tiles
 # 256->512 @80->40 ran 0.65 vs 0.61 ms, 512->1024 @40->20 0.92 vs 0.69), the launch fills the chip (P3_MIN_WGS workgroups) and

@@ -89,8 +89,8 @@ def test_conv_igemm_vs_fp64(dev, case):
     dict(B=12, Cin=256, Cout=320, k=1, s=1, H=27, W=29, act=2, form='wide'),     # ragged rows, a quarter-full second channel tile (320)
     dict(B=32, Cin=128, Cout=256, k=3, s=2, H=40, W=40, act=1, form='waves8'),   # 8-wave workgroups (wave tile 64 x 32)
     dict(B=9, Cin=512, Cout=255, k=1, s=1, H=31, W=33, act=0, bias_only=True, form='waves8'),
-    dict(B=16, Cin=1152, Cout=192, k=1, s=1, H=20, W=20, act=0, residual=True, gate=True),     # MBConv project conv: SE gate on the A operand, small grid cut along K
-    dict(B=16, Cin=672, Cout=112, k=1, s=1, H=40, W=40, act=0, gate=True),                     # ragged channel tile (112 of 128), gate, no skip
+    dict(B=16, Cin=1152, Cout=192, k=1, s=1, H=20, W=20, act=0, residual=True, gate=True),     # MBConv project conv: SE gate on the A operand; 100 tiles of 128 x 128 -> 200 tiles of 64 rows, not cut (mydet_conv_b3_plan; the cuts: tests/test_gpu_b3_branches.py)
+    dict(B=16, Cin=672, Cout=112, k=1, s=1, H=40, W=40, act=0, gate=True),                     # ragged channel tile (112 of 128), gate, no skip: 200 tiles of 128 rows
     dict(B=8, Cin=480, Cout=80, k=1, s=1, H=40, W=40, act=0, residual=True, gate=True),
     dict(B=5, Cin=96, Cout=64, k=1, s=1, H=33, W=31, act=0, gate=True),                        # 128 x 64 tile, ragged rows crossing image borders
     dict(B=16, Cin=256, Cout=128, k=1, s=1, H=40, W=40, act=1, residual=True, strided=True),      # input a channel slice of a wider map (ldx > Cin), output rows padded (ldy > Cout)
@@ -98,7 +98,7 @@ def test_conv_igemm_vs_fp64(dev, case):
     dict(B=8, Cin=40, Cout=240, k=1, s=1, H=80, W=80, act=2),                                    # Cin % 16 == 8: the last slab of a 1x1 layer zero-filled (EfficientNet 40 -> 240)
     dict(B=4, Cin=24, Cout=144, k=1, s=1, H=50, W=46, act=2, strided=True),                      # Cin % 16 == 8 again, a channel slice: what lies behind the 24 channels must not enter
     dict(B=8, Cin=192, Cout=1152, k=1, s=1, H=10, W=10, act=2),                                # 63 tiles of 128 rows: the 64-row tile without a gate, swish, ragged last row tile
-    dict(B=40, Cin=672, Cout=112, k=1, s=1, H=40, W=40, act=0, residual=True, gate=True),        # 500 tiles: the 128-row tile with the gate (the four above run 64-row tiles)
+    dict(B=40, Cin=672, Cout=112, k=1, s=1, H=40, W=40, act=0, residual=True, gate=True),        # 500 tiles: the 128-row tile with the gate (of the four above, 1152->192 and 480->80 run 64-row tiles, 96->64 the 128 x 64 tile)
 ])
 def test_conv_split_bf16_vs_fp64(dev, case, monkeypatch):
     """The implicit GEMM on the bfloat16 matrix instructions with float32-exact split operands (conv_igemm_b3_kernel;
@@ -119,7 +119,7 @@ def test_conv_split_bf16_vs_fp64(dev, case, monkeypatch):
 @pytest.mark.parametrize('case', [
     dict(B=4, Cin=32, Cout=64, s=2, H=64, W=64, act=1),                         # BN = 64 form, two slabs, whole tiles
     dict(B=3, Cin=64, Cout=128, s=2, H=80, W=96, act=1),                        # BN = 128 form (single weight buffer)
-    dict(B=2, Cin=128, Cout=256, s=2, H=40, W=40, act=1),                       # 20 x 20 outputs: ragged tiles in both directions, two channel tiles
+    dict(B=2, Cin=128, Cout=256, s=2, H=40, W=40, act=1),                       # 20 x 20 outputs: one 8 x 16 column (the third tile half empty) + one 32 x 4 strip tile per image, two channel tiles
     dict(B=3, Cin=48, Cout=192, s=2, H=37, W=53, act=0, bias_only=True),        # odd sizes, no activation, half-empty second channel tile
     dict(B=2, Cin=32, Cout=64, s=1, H=48, W=64, act=1, residual=True),          # stride 1 (the 32 -> 64 layer of the first DarkBlock) + residual
     dict(B=2, Cin=64, Cout=160, s=1, H=21, W=35, act=1, strided=True),          # stride 1, BN = 128, ragged, input a channel slice / padded output rows
