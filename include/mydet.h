@@ -560,6 +560,65 @@ int mydet_merge_tile_records_nms_f32(const int32_t *tile_records, int64_t tile_s
                                      int rotated_nms, int agnostic, int32_t *records, void *scratch, int64_t scratch_bytes,
                                      void *stream);
 
+/* Fusion of view records: test-time augmentation.  The detector ran on V views of each of B frames -- the frame mirrored by
+ * flips[v] (MYDET_VIEW_HFLIP | MYDET_VIEW_VFLIP bits, mydet_frames_to_input_flip_f32 below), at any network input size -- and
+ * this call turns the B x V per-view records into B per-frame records.  No reference counterpart; the view transform is the
+ * reference's hflip / vflip label rule (utils/augmentation.py) read backwards.
+ * In : the record of view v of frame b at view_records + v*view_stride_words + b*frame_stride_words, wire layout
+ *      (MYDET_REC_WORDS or MYDET_REC_ROT_WORDS words), its boxes in the pixel coordinates of the MIRRORED frame (the state after
+ *      mydet_bboxes_to_original_batched_f32).  Strides, alignment and the bad-class rule are those of
+ *      mydet_merge_tile_records_f32.  flips: HOST int32 [V], read during the call (it travels in the kernel arguments).
+ * Candidates: frame b has V*512.  Candidate v*512 + k, k < count[b,v], is slot k with
+ *      cx' = (float)frame_w - cx  when HFLIP (one float32 subtraction),  cy' = (float)frame_h - cy  when VFLIP,
+ *      angle' = -angle (box_width 5) when exactly ONE of the two bits is set, not wrapped; everything else unchanged.
+ * mode (kind, metric, rotated_nms, agnostic, min_score):
+ *   MYDET_FUSE_NMS  exactly what mydet_merge_tile_records_nms_f32 gives for these candidates with all origins zero (so cx' and
+ *                   cy' also take its + (float)0: a -0 centre becomes +0), with its metric / rotated_nms / agnostic and its
+ *                   MYDET_E_UNSUPP combinations; thres is its nms_thres.  Two launches: the merge's gather with the view
+ *                   transform, then the post-process kernel itself.  With every flip 0 the output equals that call's on the same
+ *                   buffer bit for bit.  min_score is not used.
+ *   MYDET_FUSE_WBF  Weighted Boxes Fusion (Solovyev et al. 2021).  box_width 4 only (5 is MYDET_E_UNSUPP: no mean of angles, as
+ *                   for MYDET_NMS_MERGE); metric must be MYDET_MERGE_IOU and rotated_nms 0 (MYDET_E_UNSUPP otherwise).
+ *                   A candidate whose score is not > 0 is skipped.  The others are visited in order P (score descending,
+ *                   candidate index ascending, -0 = +0).  Cluster j keeps, in creation order, float64 sums Wt, X1, Y1, X2, Y2, a
+ *                   member count n, the class and candidate index of its first member, and its fused row
+ *                     F_j = ((float)((x1'+x2')*0.5), (float)((y1'+y2')*0.5), (float)(x2'-x1'), (float)(y2'-y1')),  x1' = X1/Wt, ...
+ *                   (the formula of MYDET_NMS_MERGE, also for a cluster of one).  For candidate c of class q: eligible are the
+ *                   clusters of class q (agnostic: all); o_j is the axis-aligned float32 IoU of mydet_postprocess_f32 between
+ *                   F_j and c's row (corners cx -/+ w/2 of both in float32); c joins the eligible cluster with the largest o_j
+ *                   among those with (double)o_j > thres (tie: lowest j; NaN never matches):
+ *                     Wt += s; X1 += s*x1; Y1 += s*y1; X2 += s*x2; Y2 += s*y2 (c's float32 corners and score widened to
+ *                     double); n += 1; F_j recomputed.
+ *                   Without a match c founds cluster number (clusters so far) if that is < 512, and is dropped otherwise (it
+ *                   is among the lowest scores).  A cluster's score is f = (float)((Wt / n) * ((double)min(n, V) / (double)V));
+ *                   clusters with f < min_score (float32) are dropped.  Rows: class ascending, f descending, creation index
+ *                   ascending; each row is F_j, SCORE f, CLASS the first member's, INDEX the first member's v*512 + k; slots
+ *                   past the count zero.  A view with count == MYDET_COUNT_BAD_CLASS, or a candidate with score > 0 and a class
+ *                   outside [0, 4096), makes the frame's count MYDET_COUNT_BAD_CLASS.  Two launches: the gather, then one
+ *                   workgroup per frame (sort of the <= 4096 keys and the cluster table in LDS, 66 KiB).
+ *                   This is not the `ensemble-boxes` package bit for bit, on purpose: float32 IoU against the RUNNING fused box,
+ *                   the tie rules above, the 512-cluster cap.
+ * scratch: mydet_fuse_view_records_scratch_bytes(B, V, box_width, kind) bytes (0 for arguments the call rejects), 16-byte
+ *      aligned.  records must not overlap view_records.  Stream-ordered.
+ * MYDET_E_BADARG, nothing launched: V outside [1, MYDET_VIEWS_MAX]; a flip outside 0..3; frame_h or frame_w <= 0; a null mode or
+ *      an unknown kind; min_score negative or NaN; and the pointer, alignment, stride, box_width, metric, agnostic and scratch
+ *      rules of mydet_merge_tile_records_nms_f32.  `reserved` is ignored. */
+#define MYDET_VIEWS_MAX 8
+#define MYDET_FUSE_NMS 0
+#define MYDET_FUSE_WBF 1
+typedef struct mydet_fuse_mode {
+    int kind;                         /* MYDET_FUSE_* */
+    int metric;                       /* MYDET_MERGE_* */
+    int rotated_nms, agnostic;        /* 0 | 1 */
+    float min_score;                  /* WBF only */
+    int reserved;
+} mydet_fuse_mode;
+int64_t mydet_fuse_view_records_scratch_bytes(int B, int V, int box_width, int kind);
+int mydet_fuse_view_records_f32(const int32_t *view_records, int64_t view_stride_words, int64_t frame_stride_words,
+                                int B, int V, int box_width, const int32_t *flips, int frame_h, int frame_w,
+                                double thres, const mydet_fuse_mode *mode, int32_t *records,
+                                void *scratch, int64_t scratch_bytes, void *stream);
+
 /* Tracking of detections across video frames on the device: persistent identities and Kalman-filtered boxes from the detection
  * records of consecutive frames.  The state model is the reference's KFTracklet (utils/structures.py:445-529) over
  * RotBBoxKalmanFilter (utils/kalman_filter.py:77-142): constant velocity on (cx, cy, w, h, angle), diagonal P0 / Q / R with the
@@ -815,6 +874,20 @@ int mydet_frames_to_input_f32(const unsigned char *src, int B, int H, int W, int
                               const int32_t *bounds_y, const int32_t *ky, int ksy,
                               int norm, const float *mean3, const float *std3, void *stream);
 
+/* Mirrored views (test-time augmentation): mydet_frames_to_input_f32 with `flip`, a set of MYDET_VIEW_* bits.  The output is,
+ * bit for bit, what mydet_frames_to_input_f32 writes for a source whose pixel (y, x) is pixel (H-1-y if VFLIP else y,
+ * W-1-x if HFLIP else x) of `src`.  The frames are read in place through their strides -- the mirror is applied where a tap
+ * is addressed, and no mirrored copy exists; the tables are those of the unmirrored geometry (the two have one size).
+ * flip == 0 launches the kernel instance mydet_frames_to_input_f32 launches.  Any other bit is MYDET_E_BADARG; every other
+ * argument rule is that of mydet_frames_to_input_f32.  Symbols added under ABI version 2. */
+#define MYDET_VIEW_HFLIP 1
+#define MYDET_VIEW_VFLIP 2
+int mydet_frames_to_input_flip_f32(const unsigned char *src, int B, int H, int W, int64_t src_img_bytes, int64_t src_row_bytes,
+                                   float *out, int Hp, int Wp, int oh, int ow, int top, int left,
+                                   const int32_t *bounds_x, const int32_t *kx, int ksx,
+                                   const int32_t *bounds_y, const int32_t *ky, int ksy,
+                                   int norm, const float *mean3, const float *std3, int flip, void *stream);
+
 /* NV12 video frames (what hardware decoders produce): per frame a Y plane [H][W] and an interleaved chroma plane of
  * ceil(H/2) rows of ceil(W/2) (U, V) byte pairs; odd H and W are legal.  Frame b of a plane is at ptr + b*img_bytes, its
  * rows row_bytes apart (y_row_bytes >= W, uv_row_bytes >= 2*ceil(W/2); the planes may be separate allocations or the two
@@ -897,6 +970,18 @@ int mydet_yuv420_to_input_f32(const mydet_yuv420_src *src, int B, int H, int W,
                               const int32_t *bounds_x, const int32_t *kx, int ksx,
                               const int32_t *bounds_y, const int32_t *ky, int ksy,
                               int norm, const float *mean3, const float *std3, void *stream);
+
+/* mydet_yuv420_to_input_flip_f32: the mirrored views of mydet_frames_to_input_flip_f32 for every 4:2:0 layout.  The mirrored
+ * source is the mirrored RGB image of mydet_yuv420_to_rgb_u8: luma AND chroma are fetched for the pixel's position in the
+ * planes as they are (pixel (y, x) of the planes uses the pair (y >> 1, x >> 1)), so odd W and H stay legal and no
+ * "mirrored plane" is defined -- for odd sizes the result is NOT what the unmirrored call gives on planes mirrored by the
+ * caller, whose chroma pairing differs.  flip == 0 launches the instance mydet_yuv420_to_input_f32 launches; another bit
+ * than MYDET_VIEW_HFLIP | MYDET_VIEW_VFLIP is MYDET_E_BADARG. */
+int mydet_yuv420_to_input_flip_f32(const mydet_yuv420_src *src, int B, int H, int W,
+                                   float *out, int Hp, int Wp, int oh, int ow, int top, int left,
+                                   const int32_t *bounds_x, const int32_t *kx, int ksx,
+                                   const int32_t *bounds_y, const int32_t *ky, int ksy,
+                                   int norm, const float *mean3, const float *std3, int flip, void *stream);
 
 /* Overlay renderer: outlines of axis-aligned and rotated boxes, optional translucent fills and text labels, painted IN PLACE
  * into uint8 RGB frames or into the planes of the 8-bit 4:2:0 layouts, one launch per batch (csrc/draw.hip).  It stands where

@@ -81,6 +81,8 @@ SIGNATURES = {
     'mydet_merge_tile_records_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_f64, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr],
     'mydet_merge_tile_records_nms_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_f64, c_int, c_int, c_int, c_ptr, c_ptr, c_i64,
                                          c_ptr],
+    'mydet_fuse_view_records_scratch_bytes': [c_int, c_int, c_int, c_int],
+    'mydet_fuse_view_records_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_int, c_f64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr],
     'mydet_track_state_words': [c_int],
     'mydet_track_reset': [c_ptr, c_int, c_int, c_ptr],
     'mydet_track_frames_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
@@ -98,6 +100,8 @@ SIGNATURES = {
     'mydet_preprocess_u8_f32': [c_ptr, c_int, c_int, c_int, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_frames_to_input_f32': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
+    'mydet_frames_to_input_flip_f32': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_int, c_ptr],
     'mydet_nv12_to_rgb_u8': [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr],
     'mydet_nv12_to_input_f32': [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int,
                                 c_ptr, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -106,6 +110,9 @@ SIGNATURES = {
     'mydet_yuv420_to_input_f32': [c_ptr, c_int, c_int, c_int,
                                   c_ptr, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
+    'mydet_yuv420_to_input_flip_f32': [c_ptr, c_int, c_int, c_int,
+                                       c_ptr, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_int, c_ptr],
     'mydet_draw_boxes_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr],
     'mydet_draw_boxes_yuv420_u8': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_crop_boxes_rgb': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr],
@@ -121,7 +128,7 @@ SIGNATURES = {
 
 
 RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems',
-               'mydet_merge_tile_records_scratch_bytes', 'mydet_track_state_words'}
+               'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words'}
 
 # detection record layout (MYDET_REC_* of include/mydet.h), in int32 words
 REC_TOPK = 512
@@ -136,6 +143,10 @@ REC_ROT_WORDS = REC_WORDS + REC_TOPK
 # merge of tile records (mydet_merge_tile_records_f32): MYDET_TILES_MAX windows per frame, MYDET_MERGE_* pair tests
 TILES_MAX = 64
 MERGE_IOU, MERGE_IOS = 0, 1
+# mirrored views and their fusion (mydet_*_to_input_flip_f32, mydet_fuse_view_records_f32): MYDET_VIEW_*, MYDET_VIEWS_MAX, MYDET_FUSE_*
+VIEW_HFLIP, VIEW_VFLIP = 1, 2
+VIEWS_MAX = 8
+FUSE_NMS, FUSE_WBF = 0, 1
 # NMS modes (mydet_postprocess_*nms_f32): MYDET_NMS_* of include/mydet.h
 NMS_HARD, NMS_SOFT_LINEAR, NMS_SOFT_GAUSSIAN, NMS_MERGE = range(4)
 # tracking (mydet_track_frames_f32): MYDET_TRACK_* of include/mydet.h
@@ -163,6 +174,11 @@ class DecodeLevel(ctypes.Structure):
 class NmsMode(ctypes.Structure):
     """mydet_nms_mode (include/mydet.h)."""
     _fields_ = [('kind', c_int), ('agnostic', c_int), ('sigma', c_f64), ('min_score', c_f32), ('reserved', c_int)]
+
+
+class FuseMode(ctypes.Structure):
+    """mydet_fuse_mode (include/mydet.h)."""
+    _fields_ = [('kind', c_int), ('metric', c_int), ('rotated_nms', c_int), ('agnostic', c_int), ('min_score', c_f32), ('reserved', c_int)]
 
 
 class SeTail(ctypes.Structure):

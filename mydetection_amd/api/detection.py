@@ -43,6 +43,68 @@ class Tiles:
                 f'metric={self.metric!r})')
 
 
+class Augment:
+    """Test-time augmentation, the `augment=` argument of every Detector method that detects: the detector runs on mirrored and
+    rescaled views of each frame and ONE fusion on the device turns what the views find into the frame's detections
+    (ops.fuse_view_records; include/mydet.h: mydet_fuse_view_records_f32).  The views are the cross product of `scales` with
+    the flips '' , 'h' (hflip), 'v' (vflip) and 'hv' (both), in that order -- or `views` = ((scale, flip), ...) says them
+    one by one; YOLOv5's augment=True is ((1.0, ''), (0.83, 'h'), (0.67, '')).  At most 8 views, none twice, scales > 0.
+    A view of scale s runs at input_size_s = max(div, round(input_size * s / div) * div) with div the model's input
+    divisibility; scale 1.0 runs at the call's input_size itself.  A mirrored view is read in place by its input launch.
+    fuse: 'nms' -- one more NMS over the views' boxes, as Tiles merges windows (metric 'iou' or 'ios') -- or 'wbf', Weighted
+    Boxes Fusion ('cxcywh' models, metric 'iou'): the boxes of one object become their score-weighted mean, and a cluster
+    found by n of V views scores mean * min(n, V) / V; clusters below min_score (default 0) are dropped.  thres: the overlap
+    above which two boxes are one object (None: the call's nms_thres)."""
+
+    def __init__(self, hflip=True, vflip=False, scales=(1.0,), fuse='nms', thres=None, metric='iou', min_score=None, views=None):
+        if not isinstance(fuse, str) or fuse not in ops.FUSE_KINDS:
+            raise ValueError(f'Augment: fuse {fuse!r} is not one of {sorted(ops.FUSE_KINDS)}')
+        ops.merge_metric_id(metric)
+        if fuse == 'wbf' and metric != 'iou':
+            raise ValueError(f"Augment: fuse 'wbf' takes metric 'iou', not {metric!r}")
+        if views is None:
+            flips = [''] + (['h'] if hflip else []) + (['v'] if vflip else []) + (['hv'] if hflip and vflip else [])
+            views = [(s, f) for s in (scales if isinstance(scales, (tuple, list)) else (scales,)) for f in flips]
+        plan = []
+        for view in views:
+            try:
+                scale, flip = view
+                scale = float(scale)
+            except (TypeError, ValueError):
+                raise ValueError(f'Augment: a view is (scale, flip), got {view!r}') from None
+            if not 0.0 < scale < float('inf'):
+                raise ValueError(f'Augment: a positive finite scale expected, got {scale!r}')
+            plan.append((scale, ops.view_flip_bits(flip, 'Augment')))
+        if not 1 <= len(plan) <= ops.VIEWS_MAX:
+            raise ValueError(f'Augment: 1..{ops.VIEWS_MAX} views expected, got {len(plan)}')
+        if len(set(plan)) != len(plan):
+            raise ValueError(f'Augment: a view is given twice in {plan}')
+        if min_score is not None and not float(min_score) >= 0.0:
+            raise ValueError(f'Augment: min_score >= 0 expected, got {min_score!r}')
+        self.views = tuple(plan)                                     # ((scale, MYDET_VIEW_* bits), ...)
+        self.fuse, self.metric = fuse, metric
+        self.thres = None if thres is None else float(thres)
+        self.min_score = 0.0 if min_score is None else float(min_score)
+
+    def __repr__(self):
+        names = {0: '', 1: 'h', 2: 'v', 3: 'hv'}
+        return (f'Augment(views={tuple((s, names[f]) for s, f in self.views)}, fuse={self.fuse!r}, thres={self.thres}, '
+                f'metric={self.metric!r}, min_score={self.min_score})')
+
+    def plan(self, input_size, div, preprocessing):
+        """[(input size of the view, flip bits)] for a call with `input_size` under `preprocessing` and a model whose input
+        sizes are multiples of `div`.  'pad_divisible' has no input size: a scale other than 1.0 is a ValueError there."""
+        out = []
+        for scale, flip in self.views:
+            size = input_size
+            if scale != 1.0:
+                if preprocessing == 'pad_divisible' or input_size is None:
+                    raise ValueError(f"augment: a view of scale {scale} needs a preprocessing with an input_size, not {preprocessing!r}")
+                size = max(int(div), int(round(input_size * scale / div)) * int(div))
+            out.append((size, flip))
+        return out
+
+
 class Draw:
     """The settings of Detector.annotate_frames and its YUV forms: what the overlay renderer paints (ops.draw_boxes;
     include/mydet.h has the raster rules).  thickness: the outline's, 1..64 pixels; None = max(1, round(H / 360)) for frames
@@ -103,7 +165,7 @@ class Chips:
 
 
 # what the keyword arguments of a frame method say (Detector._call_settings reads them, nothing else does)
-_Call = collections.namedtuple('_Call', 'preprocessing input_size conf_thres nms_thres rotated_nms nms tiles whole')
+_Call = collections.namedtuple('_Call', 'preprocessing input_size conf_thres nms_thres rotated_nms nms tiles whole augment')
 
 
 class _Frames:
@@ -158,13 +220,14 @@ class _RgbFrames(_Frames):
                 self.frames = self.frames.contiguous()
         return self.frames
 
-    def input(self, geometry, out=None, window=None):
-        """The float32 network input of the frames, or of their crop view at window = (y0, x0, h, w): one launch."""
+    def input(self, geometry, out=None, window=None, flip=0):
+        """The float32 network input of the frames, or of their crop view at window = (y0, x0, h, w), or of their mirrored
+        view `flip` (ops.view_flip_bits): one launch."""
         fr = self.on_device()
         if window is not None:
             y0, x0, h, w = window
             fr = fr[:, y0:y0 + h, x0:x0 + w]
-        return ops.frames_to_input(fr, geometry, self.det.model.input_format, out=out)
+        return ops.frames_to_input(fr, geometry, self.det.model.input_format, out=out, flip=flip)
 
     def align(self, tiles):
         return tiles._align
@@ -200,13 +263,14 @@ class _Yuv420Frames(_Frames):
             self.planes = tuple(self.det._yuv_planes(given, self.yuv['layout'], device=dev))
         return self.planes
 
-    def input(self, geometry, out=None, window=None):
+    def input(self, geometry, out=None, window=None, flip=0):
         """As _RgbFrames.input; a window with even origin and size is itself a 4:2:0 frame."""
         ts = self.on_device()
         if window is not None:
             y0, x0, h, w = window
             ts = [ts[0][:, y0:y0 + h, x0:x0 + w]] + [t[:, y0 // 2:(y0 + h) // 2, x0 // 2:(x0 + w) // 2] for t in ts[1:]]
-        return ops.yuv420_to_input(ts, self.yuv['layout'], geometry, self.det.model.input_format, self.yuv['matrix'], self.yuv['full_range'], out=out)
+        return ops.yuv420_to_input(ts, self.yuv['layout'], geometry, self.det.model.input_format, self.yuv['matrix'], self.yuv['full_range'], out=out,
+                                   flip=flip)
 
     def align(self, tiles):
         return tiles._align * (2 if tiles._align % 2 else 1)
@@ -227,9 +291,10 @@ class Detector():
         weights_path: checkpoint with a 'model' state_dict (reference key names)
         cpu: must be False -- this package has no CPU path
         nms: None, or an Nms: how the post-process suppresses in every call that does not say otherwise (`nms=` per call)
+        augment: None, or an Augment: test-time augmentation in every call that does not say otherwise (`augment=` per call)
     '''
     def __init__(self, model_name: str = None, model_and_cfg: tuple = None,
-                 weights_path: str = None, cpu=False, nms=None):
+                 weights_path: str = None, cpu=False, nms=None, augment=None):
         if cpu:
             raise RuntimeError('mydetection_amd.Detector(cpu=True): there is no CPU path; '
                                'use the reference for CPU inference')
@@ -243,6 +308,7 @@ class Detector():
         self._init_preprocess(cfg)
         self._init_postprocess(cfg)
         self.nms = self._nms_setting(nms, self.conf_thres, self.rotated_nms)
+        self.augment = self._augment_setting(augment, None, self.rotated_nms, self.preprocess, self.input_size)
 
         n_params = sum(p.numel() for p in self.model.parameters() if p.requires_grad)
         print('Number of parameters:', n_params)
@@ -272,6 +338,23 @@ class Detector():
         no device is touched).  Returns it."""
         ops.nms_mode('Detector', nms, conf_thres, 5 if self.model.bb_format == 'cxcywhd' else 4, rotated_nms)
         return nms
+
+    def _augment_setting(self, augment, tiles, rotated_nms, preprocessing, input_size):
+        """An `augment=` argument checked against this model and the call it will run in; no device is touched.  Returns it."""
+        if augment is None:
+            return None
+        if not isinstance(augment, Augment):
+            raise TypeError(f'augment: a mydetection_amd.api.Augment (or None) expected, got {type(augment).__name__}')
+        if tiles is not None:
+            raise ValueError('augment: test-time augmentation of a tiled call is not provided; give tiles= or augment=')
+        if augment.fuse == 'wbf' and self.model.bb_format == 'cxcywhd':
+            raise ValueError("augment: fuse 'wbf' is defined for 'cxcywh' models only (no mean of angles); this one predicts 'cxcywhd'")
+        if augment.fuse == 'wbf' and rotated_nms:
+            raise ValueError("augment: fuse 'wbf' is not defined with rotated_nms")
+        if augment.metric == 'ios' and rotated_nms:
+            raise ValueError("augment: metric 'ios' is defined for the axis-aligned test only, not with rotated_nms")
+        augment.plan(input_size, self.divisibe, preprocessing)
+        return augment
 
     def evaluation_predict(self, eval_info: dict, **kwargs):
         '''
@@ -344,7 +427,9 @@ class Detector():
         '''
         Args:
             pil_img, preprocessing (str), input_size (int), conf_thres (float), nms_thres (float), rotated_nms (bool),
-            nms (an Nms or None: class-agnostic suppression, Soft-NMS or box merging; the detector's own by default)
+            nms (an Nms or None: class-agnostic suppression, Soft-NMS or box merging; the detector's own by default),
+            augment (an Augment or None: test-time augmentation; the detector's own by default.  The image's pixels then
+            take the frame path: predict_frames on np.asarray(img.convert('RGB')))
         '''
         assert isinstance(pil_img, PIL.Image.Image), 'input must be a PIL.Image'
         return self.predict_batch([pil_img], **kwargs)[0]
@@ -397,7 +482,11 @@ class Detector():
 
     def _records_by_size(self, pil_imgs, **kwargs):
         """Detection records of a list of PIL images, grouped by network input size: yields (indices, records) with the
-        boxes already in the coordinates of the original images."""
+        boxes already in the coordinates of the original images.  With augment= the pixels of the images take the frame
+        path (whose plain form equals this one): one augmented call per image size."""
+        if kwargs.get('augment', self.augment) is not None:
+            yield from self._frame_records([np.array(img.convert('RGB')) for img in pil_imgs], **kwargs)
+            return
         conf_thres = kwargs.get('conf_thres', self.conf_thres)
         nms_thres = kwargs.get('nms_thres', self.nms_thres)
         rotated_nms = bool(kwargs.get('rotated_nms', self.rotated_nms))
@@ -412,6 +501,7 @@ class Detector():
             yield idxs, rec
 
     _MAX_GRAPHS = 6
+    augment = None                    # the default of `augment=`; __init__ sets the detector's own
 
     def reset_graphs(self):
         """Forget every captured hipGraph (after editing parameters in place, or to release the graphs' activation pools)."""
@@ -518,9 +608,10 @@ class Detector():
             raise ValueError(f"rotated_nms needs a 'cxcywhd' model; this one predicts {self.model.bb_format!r}")
         conf_thres = kwargs.get('conf_thres', self.conf_thres)
         nms = self._nms_setting(kwargs.get('nms', self.nms), conf_thres, rotated_nms)
-        return _Call(kwargs.get('preprocessing', self.preprocess), kwargs.get('input_size', self.input_size),
-                     conf_thres, kwargs.get('nms_thres', self.nms_thres), rotated_nms, nms, tiles,
-                     bool(whole or kwargs.get('_whole_records')))
+        preprocessing, input_size = kwargs.get('preprocessing', self.preprocess), kwargs.get('input_size', self.input_size)
+        augment = self._augment_setting(kwargs.get('augment', self.augment), tiles, rotated_nms, preprocessing, input_size)
+        return _Call(preprocessing, input_size, conf_thres, kwargs.get('nms_thres', self.nms_thres), rotated_nms, nms, tiles,
+                     bool(whole or kwargs.get('_whole_records')), augment)
 
     def _frame_records(self, frames, **kwargs):
         """Detection records of uint8 frames: yields (indices, records) per network input size, like _records_by_size (same
@@ -529,7 +620,9 @@ class Detector():
 
     def _source_records(self, sources, call):
         """[(frame indices, records)] of frame sources, boxes in frame coordinates: per network input size, or, tiled, of the
-        one source's frames after the merge."""
+        one source's frames after the merge; augmented, of each source's frames after the fusion of its views."""
+        if call.augment is not None:
+            return [pair for src in sources for pair in self._records_of_views(src, call)]
         if call.tiles is None:
             return self._records_of_inputs(sources, call)
         return self._records_of_windows(self._one_source(sources, 'tiled'), call)
@@ -598,6 +691,44 @@ class Detector():
         merged['img_hw'] = [src.hw] * B
         return [(list(range(B)), merged)]
 
+    def _records_of_views(self, src, call):
+        """The augmented records, [(frame indices, fused records)] of the B frames of one source (one frame size).  Every view
+        of call.augment is the frames mirrored and resized: its input is one launch over the frames in place
+        (ops.frames_to_input / ops.yuv420_to_input with flip=).  The views of one network input size are one [n*B,3,Hp,Wp]
+        batch, view-major, through self._records (graph capture by shape as everywhere); then the boxes go back to the pixels
+        of the mirrored frame and ONE fusion launch pair (ops.fuse_view_records) makes the B frame records.  With an Nms every
+        view runs the whole mode; the fusion takes the mode's `agnostic`."""
+        aug, B = call.augment, src.n
+        plan = aug.plan(call.input_size, self.divisibe, call.preprocessing)
+        dev = next(self.model.parameters()).device
+        V = len(plan)
+        by_input, geos = {}, []
+        for v, (size, flip) in enumerate(plan):
+            geo = self._geometry(src.hw[0], src.hw[1], call.preprocessing, size)
+            geos.append(geo)
+            by_input.setdefault(geo[2], []).append((v, geo, flip))
+        batches = []
+        for (Hp, Wp), members in by_input.items():
+            x = torch.empty((len(members) * B, 3, Hp, Wp), dtype=torch.float32, device=dev)
+            for n, (_, geo, flip) in enumerate(members):
+                src.input(geo, out=x[n * B:(n + 1) * B], flip=flip)
+            # the views of ONE buffer (a graph replay hands out the fields as separate copies)
+            rec = ops.record_views(self._records(x, call.conf_thres, call.nms_thres, call.rotated_nms, call.nms)['records'])
+            pads = [geo[3] for _, geo, _ in members for _ in range(B)]
+            if any(p is not None for p in pads):
+                ops.records_to_original_(rec, pads)
+            batches.append(([v for v, _, _ in members], rec['records']))
+        view_records = batches[0][1]
+        if len(batches) > 1:                                         # view order again: records only, 16 KiB each
+            view_records = view_records.new_empty((V, B, view_records.shape[1]))
+            for idx, r in batches:
+                view_records[idx] = r.view(len(idx), B, -1)
+        fused = ops.fuse_view_records(view_records, B, V, [flip for _, flip in plan], src.hw,
+                                      call.nms_thres if aug.thres is None else aug.thres, aug.fuse, aug.metric,
+                                      call.rotated_nms and aug.fuse == 'nms', call.nms is not None and call.nms.agnostic, aug.min_score)
+        fused['img_hw'] = [src.hw if geos[0][3] is not None else geos[0][2]] * B
+        return [(list(src.idxs), fused)]
+
     def _detect(self, make_sources, kwargs, draw=None, chips=None):
         """The one path behind every frame method that returns objects.  make_sources(): the call's frame sources, built (and
         so checked) once the tracker's type is known to be right; draw: a Draw, or chips: a Chips, for the methods that go on
@@ -636,8 +767,9 @@ class Detector():
         RGB order, on the host or already on the device, or a list of such frames (grouped by size).  No PIL object and no
         per-frame copy or launch: resize, padding, /255 and normalisation of a whole group are one HIP launch that gives
         the bits of preprocess_batch, so the detections equal predict_batch on PIL.Image.fromarray of the same frames.
-        Keyword arguments as in _predict_pil, and tiles: None, or a Tiles for tiled detection on large frames (frames of one
-        size): every window's input is one launch over a crop view of all frames, the windows of one size are one forward
+        Keyword arguments as in _predict_pil (augment= included: an Augment runs mirrored and rescaled views of the frames,
+        each read in place by its input launch, and fuses them on the device; frames of any sizes, not with tiles), and
+        tiles: None, or a Tiles for tiled detection on large frames (frames of one size): every window's input is one launch over a crop view of all frames, the windows of one size are one forward
         batch, and one more NMS on the device merges their detections in frame coordinates (include/mydet.h:
         mydet_merge_tile_records_f32).  Returns a list of ImageObjects in original-frame coordinates.
         tracker: None, or a mydetection_amd.api.Tracker (frames of one size, a multiple of its `streams` of them: stream s owns

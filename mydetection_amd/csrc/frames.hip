@@ -20,11 +20,13 @@ struct FramesArgs {
     const unsigned char *src;
     int64_t src_img, src_row;                  // bytes between frames / rows
     int H, W;
+    int flip;                                  // MYDET_VIEW_* bits; read by the FLIP instances only
     FrOut o;
 };
 
-// N = pixels per thread along x of the vertical pass and the stores: 4 or 1 (frames_tile.h)
-template <int N>
+// N = pixels per thread along x of the vertical pass and the stores: 4 or 1 (frames_tile.h).  FLIP: the mirrored views
+// (frames_tile.h); the <N, false> instances are the ones mydet_frames_to_input_f32 has always launched.
+template <int N, bool FLIP>
 __global__ __launch_bounds__(256) void frames_to_input_kernel(const FramesArgs p) {
     extern __shared__ __align__(16) uint32_t fr_lds[];
     uint32_t *stage = fr_lds;                                           // [max_rows][FR_TW] packed pixels
@@ -45,10 +47,18 @@ __global__ __launch_bounds__(256) void frames_to_input_kernel(const FramesArgs p
         for (int r = tid >> 6; r < win.nrows; r += 256 / FR_TW) {
             uint32_t v = 0;
             if (c.inside) {
-                const unsigned char *px = src + (int64_t)(win.r0 + r) * p.src_row + c.x0 * 3;
+                // tap t is `step` * t bytes from the first one: backwards in a horizontally mirrored view
+                int64_t row = win.r0 + r;
+                int x = c.x0, step = 3;
+                if constexpr (FLIP) {
+                    row = fr_src_row(p.flip, p.H, win.r0 + r);
+                    x = fr_src_col(p.flip, p.W, c.x0);
+                    step = (p.flip & MYDET_VIEW_HFLIP) ? -3 : 3;
+                }
+                const unsigned char *px = src + row * p.src_row + x * 3;
                 if (p.o.bx) {
                     PxFilter f;
-                    for (int t = 0; t < c.nx; ++t) f.add(px[3 * t], px[3 * t + 1], px[3 * t + 2], wts[t * FR_TW + col]);
+                    for (int t = 0; t < c.nx; ++t) f.add(px[step * t], px[step * t + 1], px[step * t + 2], wts[t * FR_TW + col]);
                     v = f.pixel();
                 } else {
                     v = px_pack(px[0], px[1], px[2]);
@@ -63,23 +73,47 @@ __global__ __launch_bounds__(256) void frames_to_input_kernel(const FramesArgs p
 
 }  // namespace
 
-extern "C" int mydet_frames_to_input_f32(const unsigned char *src, int B, int H, int W, int64_t src_img_bytes,
-                                         int64_t src_row_bytes, float *out, int Hp, int Wp, int oh, int ow, int top, int left,
-                                         const int32_t *bounds_x, const int32_t *kx, int ksx, const int32_t *bounds_y,
-                                         const int32_t *ky, int ksy, int norm, const float *mean3, const float *std3,
-                                         void *stream) {
+// flip == 0 launches the <N, false> instances: the launch mydet_frames_to_input_f32 has always made
+static int frames_to_input(const unsigned char *src, int B, int H, int W, int64_t src_img_bytes, int64_t src_row_bytes, float *out,
+                           int Hp, int Wp, int oh, int ow, int top, int left, const int32_t *bounds_x, const int32_t *kx, int ksx,
+                           const int32_t *bounds_y, const int32_t *ky, int ksy, int norm, const float *mean3, const float *std3,
+                           int flip, void *stream) {
     if (!src || B <= 0 || H <= 0 || W <= 0 || src_row_bytes < (int64_t)W * 3 || src_img_bytes < 0) return MYDET_E_BADARG;
+    if (fr_flip_arg(flip)) return MYDET_E_BADARG;
     FramesArgs p;
     dim3 grid;
     const int code = fr_tile_setup(p.o, grid, B, H, W, out, Hp, Wp, oh, ow, top, left, bounds_x, kx, ksx, bounds_y, ky, ksy, norm,
                                    mean3, std3);
     if (code) return code;
-    p.src = src; p.src_img = src_img_bytes; p.src_row = src_row_bytes; p.H = H; p.W = W;
+    p.src = src; p.src_img = src_img_bytes; p.src_row = src_row_bytes; p.H = H; p.W = W; p.flip = flip;
     const size_t lds = fr_tile_lds_bytes(p.o);
     if (lds > 64 * 1024) return MYDET_E_UNSUPP;
-    if (fr_quad_stores(p.o))
-        hipLaunchKernelGGL(frames_to_input_kernel<4>, grid, dim3(256), lds, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(frames_to_input_kernel<1>, grid, dim3(256), lds, (hipStream_t)stream, p);
+    const bool quads = fr_quad_stores(p.o);
+    if (flip) {
+        if (quads) hipLaunchKernelGGL((frames_to_input_kernel<4, true>), grid, dim3(256), lds, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((frames_to_input_kernel<1, true>), grid, dim3(256), lds, (hipStream_t)stream, p);
+    } else if (quads) {
+        hipLaunchKernelGGL((frames_to_input_kernel<4, false>), grid, dim3(256), lds, (hipStream_t)stream, p);
+    } else {
+        hipLaunchKernelGGL((frames_to_input_kernel<1, false>), grid, dim3(256), lds, (hipStream_t)stream, p);
+    }
     return mydet_launch_status();
+}
+
+extern "C" int mydet_frames_to_input_f32(const unsigned char *src, int B, int H, int W, int64_t src_img_bytes,
+                                         int64_t src_row_bytes, float *out, int Hp, int Wp, int oh, int ow, int top, int left,
+                                         const int32_t *bounds_x, const int32_t *kx, int ksx, const int32_t *bounds_y,
+                                         const int32_t *ky, int ksy, int norm, const float *mean3, const float *std3,
+                                         void *stream) {
+    return frames_to_input(src, B, H, W, src_img_bytes, src_row_bytes, out, Hp, Wp, oh, ow, top, left, bounds_x, kx, ksx, bounds_y, ky,
+                           ksy, norm, mean3, std3, 0, stream);
+}
+
+extern "C" int mydet_frames_to_input_flip_f32(const unsigned char *src, int B, int H, int W, int64_t src_img_bytes,
+                                              int64_t src_row_bytes, float *out, int Hp, int Wp, int oh, int ow, int top, int left,
+                                              const int32_t *bounds_x, const int32_t *kx, int ksx, const int32_t *bounds_y,
+                                              const int32_t *ky, int ksy, int norm, const float *mean3, const float *std3,
+                                              int flip, void *stream) {
+    return frames_to_input(src, B, H, W, src_img_bytes, src_row_bytes, out, Hp, Wp, oh, ow, top, left, bounds_x, kx, ksx, bounds_y, ky,
+                           ksy, norm, mean3, std3, flip, stream);
 }

@@ -81,6 +81,15 @@ __device__ __forceinline__ FrColumn fr_column(const FrOut &p, int W, int tx0, in
     return c;
 }
 
+// Mirrored views (MYDET_VIEW_HFLIP / MYDET_VIEW_VFLIP, the *_flip_f32 entry points): the window, the tables and the stage are
+// those of the mirrored frame, and only the address of a tap changes -- row y of the mirrored frame is row H-1-y of the
+// frame in memory, column x is column W-1-x.  fr_window / fr_column give mirrored coordinates; the kernels pass every row
+// and column they read through these two.  FLIP = false instances never call them with a non-zero `flip`.
+__device__ __forceinline__ int fr_src_row(int flip, int H, int y) { return (flip & MYDET_VIEW_VFLIP) ? H - 1 - y : y; }
+__device__ __forceinline__ int fr_src_col(int flip, int W, int x) { return (flip & MYDET_VIEW_HFLIP) ? W - 1 - x : x; }
+
+inline int fr_flip_arg(int flip) { return (flip & ~(MYDET_VIEW_HFLIP | MYDET_VIEW_VFLIP)) ? MYDET_E_BADARG : 0; }
+
 template <int N>
 __device__ __forceinline__ void fr_stage_read(const uint32_t *stage, int rr, int xq, uint32_t (&h)[N]) {
     if constexpr (N == 4) {

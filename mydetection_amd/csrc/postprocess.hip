@@ -945,6 +945,10 @@ struct MergeArgs {
     float *bbox;                      // [B][T*512][BW]
     int64_t *cidx;                    // [B][T*512]
     float *score;                     // [B][T*512]
+    // VIEW instances (fusion of view records below): no origins; window t is view t, mirrored by bits 2t, 2t+1 of `flips`
+    unsigned flips;
+    float frame_w, frame_h;
+    int zero_origin;                  // add the (float)0 origin of a merge with zero origins: -0 becomes +0, as there
 };
 
 // One thread per candidate slot (b = blockIdx.y, t*512 + k = blockIdx.x * 256 + tid): lane k reads the 16-byte box row k of
@@ -953,7 +957,9 @@ struct MergeArgs {
 // arrays is defined.  A tile whose count is the bad-class sentinel plants ONE candidate with score +inf and class -1 in its
 // slot 0: it is among the top 512 whatever else the frame holds, and the kernel above then fails the frame the way it fails
 // any image with such a class (count = MYDET_COUNT_BAD_CLASS, zero rows).
-template <int BW>
+// VIEW: the candidates of mydet_fuse_view_records_f32 -- instead of the origin shift, the box is brought back from its
+// mirrored view: cx' = frame_w - cx (HFLIP), cy' = frame_h - cy (VFLIP), angle' = -angle when exactly one bit is set.
+template <int BW, bool VIEW = false>
 __global__ __launch_bounds__(256) void merge_gather_kernel(const MergeArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;          // grid.x * 256 == T * 512 exactly
     const int t = i >> 9, k = i & (KMAX - 1);
@@ -968,11 +974,19 @@ __global__ __launch_bounds__(256) void merge_gather_kernel(const MergeArgs a) {
         if (k == 0) { sc = __uint_as_float(0x7F800000u); c = -1; }
     } else if (k < count) {                                // a count above 512 cannot come from the kernel above; k < 512 anyway
         v = *reinterpret_cast<const f32x4 *>(r + MYDET_REC_BBOX + 4 * k);
-        v[0] = v[0] + (float)a.origins[2 * t];
-        v[1] = v[1] + (float)a.origins[2 * t + 1];
+        if constexpr (BW == 5) ang = reinterpret_cast<const float *>(r + MYDET_REC_ANGLE)[k];
+        if constexpr (VIEW) {
+            const unsigned f = (a.flips >> (2 * t)) & 3u;
+            if (f & MYDET_VIEW_HFLIP) v[0] = a.frame_w - v[0];
+            if (f & MYDET_VIEW_VFLIP) v[1] = a.frame_h - v[1];
+            if (f == MYDET_VIEW_HFLIP || f == MYDET_VIEW_VFLIP) ang = -ang;
+            if (a.zero_origin) { v[0] = v[0] + 0.0f; v[1] = v[1] + 0.0f; }
+        } else {
+            v[0] = v[0] + (float)a.origins[2 * t];
+            v[1] = v[1] + (float)a.origins[2 * t + 1];
+        }
         sc = reinterpret_cast<const float *>(r + MYDET_REC_SCORE)[k];
         c = reinterpret_cast<const int64_t *>(r + MYDET_REC_CLASS)[k];
-        if constexpr (BW == 5) ang = reinterpret_cast<const float *>(r + MYDET_REC_ANGLE)[k];
     }
     if constexpr (BW == 4) {
         *reinterpret_cast<f32x4 *>(a.bbox + o * 4) = v;
@@ -993,34 +1007,34 @@ extern "C" int64_t mydet_merge_tile_records_scratch_bytes(int B, int T, int box_
     return (int64_t)B * T * KMAX * (4 * box_width + 8 + 4 + 8);
 }
 
-// agnostic: the merge's NMS has one group of all candidates (mydet_merge_tile_records_nms_f32); 0 is the shipped call
-static int merge_tile_records(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words,
-                              int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
-                              int rotated_nms, int agnostic, int32_t *records, void *scratch, int64_t scratch_bytes, void *stream) {
+// The argument rules the merge and the fusion of view records share (T windows or views, at most `tmax`); `src` is the
+// origins (device) or the flips (host)
+static int merge_check_args(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words, int B, int T, int tmax,
+                            int box_width, const void *src, int metric, int rotated_nms, int agnostic, const int32_t *records,
+                            const void *scratch) {
     if (agnostic != 0 && agnostic != 1) return MYDET_E_BADARG;
-    if (B <= 0 || T < 1 || T > MYDET_TILES_MAX) return MYDET_E_BADARG;
+    if (B <= 0 || T < 1 || T > tmax) return MYDET_E_BADARG;
     if (box_width != 4 && box_width != 5) return MYDET_E_BADARG;
     if (metric != MYDET_MERGE_IOU && metric != MYDET_MERGE_IOS) return MYDET_E_BADARG;
     if (rotated_nms && box_width != 5) return MYDET_E_BADARG;
-    if (!tile_records || !origins || !records || !scratch) return MYDET_E_BADARG;
+    if (!tile_records || !src || !records || !scratch) return MYDET_E_BADARG;
     // a record is read with 16-byte loads: the base and both strides keep that alignment
-    if (((uintptr_t)tile_records & 15) || ((uintptr_t)records & 15) || ((uintptr_t)scratch & 15) || ((uintptr_t)origins & 3)) return MYDET_E_BADARG;
+    if (((uintptr_t)tile_records & 15) || ((uintptr_t)records & 15) || ((uintptr_t)scratch & 15) || ((uintptr_t)src & 3)) return MYDET_E_BADARG;
     if (tile_stride_words < 0 || frame_stride_words < 0 || (tile_stride_words & 3) || (frame_stride_words & 3)) return MYDET_E_BADARG;
-    if (scratch_bytes < mydet_merge_tile_records_scratch_bytes(B, T, box_width)) return MYDET_E_BADARG;
-    if (metric == MYDET_MERGE_IOS && rotated_nms) return MYDET_E_UNSUPP;
-    if (agnostic && rotated_nms) return MYDET_E_UNSUPP;
-    const int64_t N = (int64_t)T * KMAX, BN = (int64_t)B * N;
-    MergeArgs a;
-    a.rec = tile_records; a.tile_st = tile_stride_words; a.frame_st = frame_stride_words; a.origins = origins; a.T = T;
+    return 0;
+}
+
+// The candidate arrays in `scratch`; returns what follows them (the key strip of postprocess_kernel)
+static void *merge_layout(MergeArgs &a, void *scratch, int64_t BN, int box_width) {
     a.bbox = reinterpret_cast<float *>(scratch);
     a.cidx = reinterpret_cast<int64_t *>(a.bbox + BN * box_width);
     a.score = reinterpret_cast<float *>(a.cidx + BN);
-    void *keys = a.score + BN;
-    const dim3 grid((unsigned)(N / 256), (unsigned)B);
-    if (box_width == 4) hipLaunchKernelGGL((merge_gather_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((merge_gather_kernel<5>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    const int st = mydet_launch_status();
-    if (st) return st;
+    return a.score + BN;
+}
+
+// The second launch of the merge: postprocess_kernel on the gathered candidates with conf = -inf
+static int merge_nms(const MergeArgs &a, int B, int64_t N, int box_width, double nms_thres, int metric, int rotated_nms, int agnostic,
+                     int32_t *records, void *keys, void *stream) {
     PPModeArgs p;
     record_outputs(p, records, box_width == 5);
     const float conf = -__builtin_inff();
@@ -1044,6 +1058,28 @@ static int merge_tile_records(const int32_t *tile_records, int64_t tile_stride_w
                : launch_postprocess<5>(p, a.bbox, a.cidx, a.score, B, N, conf, nms_thres, MYDET_REC_TOPK, keys, stream);
 }
 
+// agnostic: the merge's NMS has one group of all candidates (mydet_merge_tile_records_nms_f32); 0 is the shipped call
+static int merge_tile_records(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words,
+                              int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
+                              int rotated_nms, int agnostic, int32_t *records, void *scratch, int64_t scratch_bytes, void *stream) {
+    const int bad = merge_check_args(tile_records, tile_stride_words, frame_stride_words, B, T, MYDET_TILES_MAX, box_width, origins, metric,
+                                     rotated_nms, agnostic, records, scratch);
+    if (bad) return bad;
+    if (scratch_bytes < mydet_merge_tile_records_scratch_bytes(B, T, box_width)) return MYDET_E_BADARG;
+    if (metric == MYDET_MERGE_IOS && rotated_nms) return MYDET_E_UNSUPP;
+    if (agnostic && rotated_nms) return MYDET_E_UNSUPP;
+    const int64_t N = (int64_t)T * KMAX;
+    MergeArgs a = {};
+    a.rec = tile_records; a.tile_st = tile_stride_words; a.frame_st = frame_stride_words; a.origins = origins; a.T = T;
+    void *keys = merge_layout(a, scratch, (int64_t)B * N, box_width);
+    const dim3 grid((unsigned)(N / 256), (unsigned)B);
+    if (box_width == 4) hipLaunchKernelGGL((merge_gather_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((merge_gather_kernel<5>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    const int st = mydet_launch_status();
+    if (st) return st;
+    return merge_nms(a, B, N, box_width, nms_thres, metric, rotated_nms, agnostic, records, keys, stream);
+}
+
 extern "C" int mydet_merge_tile_records_f32(const int32_t *tile_records, int64_t tile_stride_words, int64_t frame_stride_words,
                                             int B, int T, int box_width, const int32_t *origins, double nms_thres, int metric,
                                             int rotated_nms, int32_t *records, void *scratch, int64_t scratch_bytes, void *stream) {
@@ -1057,4 +1093,241 @@ extern "C" int mydet_merge_tile_records_nms_f32(const int32_t *tile_records, int
                                                 int64_t scratch_bytes, void *stream) {
     return merge_tile_records(tile_records, tile_stride_words, frame_stride_words, B, T, box_width, origins, nms_thres, metric,
                               rotated_nms, agnostic, records, scratch, scratch_bytes, stream);
+}
+
+// ---- fusion of view records (test-time augmentation; include/mydet.h) ----
+// The detector ran on V mirrored (and possibly rescaled) views of each frame; the records of the views, already in the pixel
+// coordinates of the mirrored frame, become one record per frame.  The gather above (VIEW instances) brings every box back from
+// its view and writes the B x V*512 candidate arrays.  MYDET_FUSE_NMS then runs postprocess_kernel on them exactly as the merge
+// of tile records does.  MYDET_FUSE_WBF runs wbf_kernel: Weighted Boxes Fusion (Solovyev et al. 2021) with the rules of the
+// header -- every candidate, in order P, joins the cluster whose running fused box it overlaps most, or founds one.
+namespace {
+
+constexpr int WBF_NMAX = MYDET_VIEWS_MAX * KMAX;
+
+struct WbfArgs {
+    PPArgs o;                         // the record outputs (write_row / finish_rows)
+    const float *bbox;                // the gathered candidates: [B][N][4], [B][N], [B][N]
+    const int64_t *cidx;
+    const float *score;
+    int N, V, agn;
+    double thres;
+    float min_score;
+};
+
+// LDS of wbf_kernel, dynamic (66 KiB + the scalars: above the 64 KiB a kernel gets without the opt-in)
+struct WbfLds {
+    unsigned long long key[WBF_NMAX];  // the candidates in order P; afterwards the first KMAX hold the output order keys
+    double sum[5][KMAX];               // Wt, X1, Y1, X2, Y2 of cluster j
+    float f[4][KMAX];                  // its fused row (cx, cy, w, h)
+    int n[KMAX], cls[KMAX], first[KMAX];
+    int nvalid, bad, ncl, total;
+};
+
+__device__ __forceinline__ float wbf_lane(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
+__device__ __forceinline__ unsigned long long wbf_lane64u(unsigned long long u, int lane) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), lane);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ double wbf_lane64(double v, int lane) {
+    return __longlong_as_double((long long)wbf_lane64u((unsigned long long)__double_as_longlong(v), lane));
+}
+
+// One workgroup per frame.  All 16 waves build and sort the keys and write the output; the clustering itself is one dependent
+// chain over the candidates (a candidate's match depends on every fused box before it, and the 512-cluster cap ties the classes
+// together), so wave 0 walks it alone: a lane owns clusters lane, lane + 64, ..., the match of a candidate is one wave maximum
+// over (IoU, lowest j), and lanes 0-4 update the five sums of the matched cluster (one division for the four means).  64 candidates at a time are fetched into registers and handed
+// round with v_readlane, so the chain waits for memory once per 64 steps.
+__global__ __launch_bounds__(NT) void wbf_kernel(const WbfArgs p) {
+    extern __shared__ __align__(16) unsigned char wbf_raw[];
+    WbfLds &s = *reinterpret_cast<WbfLds *>(wbf_raw);
+    const int tid = threadIdx.x, b = blockIdx.x, N = p.N;
+    const float *bb = p.bbox + (int64_t)b * N * 4;
+    const int64_t *ci = p.cidx + (int64_t)b * N;
+    const float *sc = p.score + (int64_t)b * N;
+    int npow = KMAX;                                        // keys sorted: the power of two that holds N
+    while (npow < N) npow <<= 1;
+
+    if (tid == 0) { s.nvalid = 0; s.bad = 0; s.ncl = 0; s.total = 0; }
+    __syncthreads();
+    // 1. keys of the candidates with a score > 0 (a NaN -- every slot past a view's count -- fails the test): ~score, then index
+    for (int i = tid; i < npow; i += NT) {
+        unsigned long long k = ~0ull;
+        if (i < N) {
+            const float v = sc[i];
+            if (v > 0.0f) {
+                if ((unsigned long long)ci[i] > 0xFFFull) s.bad = 1;       // the bad-class sentinel of a view, or a class the keys cannot hold
+                k = ((unsigned long long)(~sortable(v)) << 12) | (unsigned long long)i;
+                atomicAdd(&s.nvalid, 1);
+            }
+        }
+        s.key[i] = k;
+    }
+    __syncthreads();
+    for (int k = 2; k <= npow; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < npow; i += NT) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const unsigned long long x = s.key[i], c = s.key[ixj];
+                    const bool up = (i & k) == 0;
+                    if ((x > c) == up) { s.key[i] = c; s.key[ixj] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const int nvalid = s.nvalid;
+    const bool bad = s.bad != 0;
+
+    // 2. the chain
+    if (tid < 64 && !bad) {
+        const int lane = tid;
+        int ncl = 0;
+        for (int base = 0; base < nvalid; base += 64) {
+            float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, ar = 0.f, cs = 0.f;
+            int cq = 0, cidx = 0;
+            if (base + lane < nvalid) {
+                cidx = (int)(s.key[base + lane] & 4095ull);
+                const f32x4 v = *reinterpret_cast<const f32x4 *>(bb + (int64_t)cidx * 4);
+                const float hw = v[2] / 2.0f, hh = v[3] / 2.0f;
+                x1 = v[0] - hw; y1 = v[1] - hh; x2 = v[0] + hw; y2 = v[1] + hh;
+                ar = (x2 - x1) * (y2 - y1);
+                cs = sc[cidx];
+                cq = (int)ci[cidx];
+            }
+            const int nb = min(64, nvalid - base);
+            for (int i = 0; i < nb; ++i) {
+                const float bx1 = wbf_lane(x1, i), by1 = wbf_lane(y1, i), bx2 = wbf_lane(x2, i), by2 = wbf_lane(y2, i);
+                const float ba = wbf_lane(ar, i), bs = wbf_lane(cs, i);
+                const int q_cls = __builtin_amdgcn_readlane(cq, i), idx = __builtin_amdgcn_readlane(cidx, i);
+                unsigned long long best = 0ull;            // (sortable IoU, ~j) of the best eligible cluster above the threshold
+                for (int j = lane; j < ncl; j += 64) {
+                    if (!p.agn && s.cls[j] != q_cls) continue;
+                    const float fw = s.f[2][j] / 2.0f, fh = s.f[3][j] / 2.0f;
+                    const float jx1 = s.f[0][j] - fw, jy1 = s.f[1][j] - fh, jx2 = s.f[0][j] + fw, jy2 = s.f[1][j] + fh;
+                    const float o = pair_iou(jx1, jy1, jx2, jy2, (jx2 - jx1) * (jy2 - jy1), bx1, by1, bx2, by2, ba);
+                    if ((double)o > p.thres) {             // false for a NaN
+                        const unsigned long long k = ((unsigned long long)sortable(o) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)j);
+                        best = k > best ? k : best;
+                    }
+                }
+                // the wave maximum.  Most steps have no lane above the threshold (a founder) or exactly one (a box of an object
+                // the views agree on): those read the answer from the ballot, and only a contested step pays the six shuffle rounds
+                const unsigned long long hit = __ballot(best != 0ull);
+                if (hit != 0ull && (hit & (hit - 1ull)) == 0ull) {
+                    best = wbf_lane64u(best, __ffsll((long long)hit) - 1);
+                } else if (hit != 0ull) {
+#pragma unroll
+                    for (int off = 32; off >= 1; off >>= 1) {
+                        const unsigned long long o = __shfl_xor(best, off);
+                        best = o > best ? o : best;
+                    }
+                }
+                int j = -1;                                 // uniform from here on
+                if (best != 0ull) j = (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull));
+                else if (ncl < KMAX) j = ncl;
+                if (j >= 0) {
+                    // lane l < 5 owns sum l of the cluster (Wt, X1, Y1, X2, Y2), so the five updates are one instruction stream and
+                    // the four quotients one division; lane 0 then writes the fused row
+                    const bool found = best == 0ull;
+                    const float mine = lane == 1 ? bx1 : lane == 2 ? by1 : lane == 3 ? bx2 : lane == 4 ? by2 : 1.0f;
+                    double acc = 0.0;
+                    if (lane < 5) {
+                        acc = (found ? 0.0 : s.sum[lane][j]) + (double)bs * (double)mine;      // lane 0: s * 1 = s exactly
+                        s.sum[lane][j] = acc;
+                    }
+                    const double q = acc / wbf_lane64(acc, 0);
+                    const double mx1 = wbf_lane64(q, 1), my1 = wbf_lane64(q, 2), mx2 = wbf_lane64(q, 3), my2 = wbf_lane64(q, 4);
+                    if (lane == 0) {
+                        s.f[0][j] = (float)((mx1 + mx2) * 0.5); s.f[1][j] = (float)((my1 + my2) * 0.5);
+                        s.f[2][j] = (float)(mx2 - mx1); s.f[3][j] = (float)(my2 - my1);
+                        if (found) { s.n[j] = 1; s.cls[j] = q_cls; s.first[j] = idx; }
+                        else s.n[j] = s.n[j] + 1;
+                    }
+                }
+                if (best == 0ull && ncl < KMAX) ++ncl;
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");     // lane 0's cluster is what every lane reads next
+            }
+        }
+        if (lane == 0) s.ncl = ncl;
+    }
+    __syncthreads();
+
+    // 3. scores, the min_score cut, the output order (class ascending, score descending, creation order) and the rows
+    const int ncl = s.ncl;
+    float fs = 0.f;
+    unsigned long long ok = ~0ull;
+    if (tid < ncl) {
+        const int n = s.n[tid];
+        fs = (float)((s.sum[0][tid] / (double)n) * ((double)min(n, p.V) / (double)p.V));
+        if (!(fs < p.min_score))
+            ok = ((unsigned long long)s.cls[tid] << 41) | ((unsigned long long)(~sortable(fs)) << 9) | (unsigned long long)tid;
+    }
+    if (tid < KMAX) s.key[tid] = ok;                        // every candidate key has been read: the chain is over
+    __syncthreads();
+    bitonic_sort_kmax(s.key, tid);
+    if (tid < KMAX && s.key[tid] != ~0ull && (tid == KMAX - 1 || s.key[tid + 1] == ~0ull)) s.total = tid + 1;
+    __syncthreads();
+    const int total = bad ? 0 : s.total;
+    if (tid < total) {
+        const int j = (int)(s.key[tid] & (KMAX - 1));
+        const int n = s.n[j];
+        const float f = (float)((s.sum[0][j] / (double)n) * ((double)min(n, p.V) / (double)p.V));
+        write_row<4>(p.o, b, tid, f32x4{s.f[0][j], s.f[1][j], s.f[2][j], s.f[3][j]}, 0.f, (int64_t)s.cls[j], f, (unsigned)s.first[j]);
+    }
+    finish_rows<4>(p.o, b, total, bad, tid);
+}
+
+}  // namespace
+
+extern "C" int64_t mydet_fuse_view_records_scratch_bytes(int B, int V, int box_width, int kind) {
+    if (B <= 0 || V < 1 || V > MYDET_VIEWS_MAX || (box_width != 4 && box_width != 5)) return 0;
+    if (kind == MYDET_FUSE_NMS) return (int64_t)B * V * KMAX * (4 * box_width + 8 + 4 + 8);
+    if (kind == MYDET_FUSE_WBF && box_width == 4) return (int64_t)B * V * KMAX * (16 + 8 + 4);    // no key strip
+    return 0;
+}
+
+extern "C" int mydet_fuse_view_records_f32(const int32_t *view_records, int64_t view_stride_words, int64_t frame_stride_words,
+                                           int B, int V, int box_width, const int32_t *flips, int frame_h, int frame_w,
+                                           double thres, const mydet_fuse_mode *mode, int32_t *records,
+                                           void *scratch, int64_t scratch_bytes, void *stream) {
+    if (!mode || (mode->kind != MYDET_FUSE_NMS && mode->kind != MYDET_FUSE_WBF)) return MYDET_E_BADARG;
+    const int bad = merge_check_args(view_records, view_stride_words, frame_stride_words, B, V, MYDET_VIEWS_MAX, box_width, flips,
+                                     mode->metric, mode->rotated_nms, mode->agnostic, records, scratch);
+    if (bad) return bad;
+    if (frame_h <= 0 || frame_w <= 0 || !(mode->min_score >= 0.0f)) return MYDET_E_BADARG;
+    unsigned packed = 0u;
+    for (int v = 0; v < V; ++v) {
+        if (flips[v] < 0 || flips[v] > (MYDET_VIEW_HFLIP | MYDET_VIEW_VFLIP)) return MYDET_E_BADARG;
+        packed |= (unsigned)flips[v] << (2 * v);
+    }
+    const bool wbf = mode->kind == MYDET_FUSE_WBF;
+    if (wbf && (box_width != 4 || mode->metric != MYDET_MERGE_IOU || mode->rotated_nms)) return MYDET_E_UNSUPP;
+    if (!wbf && mode->rotated_nms && (mode->metric == MYDET_MERGE_IOS || mode->agnostic)) return MYDET_E_UNSUPP;
+    if (scratch_bytes < mydet_fuse_view_records_scratch_bytes(B, V, box_width, mode->kind)) return MYDET_E_BADARG;
+    const int64_t N = (int64_t)V * KMAX;
+    MergeArgs a = {};
+    a.rec = view_records; a.tile_st = view_stride_words; a.frame_st = frame_stride_words; a.origins = nullptr; a.T = V;
+    a.flips = packed; a.frame_w = (float)frame_w; a.frame_h = (float)frame_h; a.zero_origin = wbf ? 0 : 1;
+    void *keys = merge_layout(a, scratch, (int64_t)B * N, box_width);
+    static unsigned long long opted = 0ull;
+    if (wbf) {
+        const int st = mydet_lds_opt_in(opted, wbf_kernel, (int)sizeof(WbfLds));
+        if (st) return st;
+    }
+    const dim3 grid((unsigned)(N / 256), (unsigned)B);
+    if (box_width == 4) hipLaunchKernelGGL((merge_gather_kernel<4, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((merge_gather_kernel<5, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    const int st = mydet_launch_status();
+    if (st) return st;
+    if (!wbf)
+        return merge_nms(a, B, N, box_width, thres, mode->metric, mode->rotated_nms, mode->agnostic, records, keys, stream);
+    WbfArgs w = {};
+    record_outputs(w.o, records, false);
+    w.o.topk = MYDET_REC_TOPK;
+    w.bbox = a.bbox; w.cidx = a.cidx; w.score = a.score; w.N = (int)N; w.V = V; w.agn = mode->agnostic;
+    w.thres = thres; w.min_score = mode->min_score;
+    hipLaunchKernelGGL(wbf_kernel, dim3(B), dim3(NT), sizeof(WbfLds), (hipStream_t)stream, w);
+    return mydet_launch_status();
 }

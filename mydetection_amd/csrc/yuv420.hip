@@ -41,6 +41,7 @@ constexpr int YUV_ROWS = 8;                 // source rows converted per step
 struct YuvInputArgs {
     YuvSrc s;
     int max_cols;
+    int flip;                                  // MYDET_VIEW_* bits; read by the FLIP instances only
     FrOut o;
 };
 
@@ -73,8 +74,13 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const YuvRgbArgs p) {
     }
 }
 
-// N = pixels per thread along x of the vertical pass and the stores: 4 or 1 (frames_tile.h); BPS, PLANAR: the fetch (yuv_quad)
-template <int N, int BPS, bool PLANAR>
+// N = pixels per thread along x of the vertical pass and the stores: 4 or 1 (frames_tile.h); BPS, PLANAR: the fetch (yuv_quad).
+// FLIP: the mirrored views (frames_tile.h).  `raw` keeps the columns of the MIRRORED frame, so the horizontal pass is unchanged;
+// the fetch reads row fr_src_row and, when mirrored horizontally, the quad of the frame in memory that holds the four mirrored
+// columns and writes it reversed.  For that the window starts where W - c0 is a multiple of 4 (c0 >= -3: mirrored columns below 0
+// are columns >= W in memory, which yuv_quad gives as zero without reading), and a quad that would start below column 0 is
+// zero.  Luma and chroma are both fetched for the pixel's position in memory, so odd W and H need no rule of their own.
+template <int N, int BPS, bool PLANAR, bool FLIP>
 __global__ __launch_bounds__(256) void yuv_to_input_kernel(const YuvInputArgs p) {
     extern __shared__ __align__(16) uint32_t yuv_lds[];
     uint32_t *stage = yuv_lds;                                           // [max_rows][FR_TW] horizontally resampled pixels
@@ -86,7 +92,10 @@ __global__ __launch_bounds__(256) void yuv_to_input_kernel(const YuvInputArgs p)
     const FrWindow win = fr_window(p.o, p.s.H, tx0, ty0);
     if (win.live) {
         // first column of the window, on a quad: the first tap of the tile's first column (taps start in column order)
-        const int c0 = px_clamp(p.o.bx ? p.o.bx[2 * win.wx_lo] : win.wx_lo, 0, p.s.W - 1) & ~3;
+        int c0 = px_clamp(p.o.bx ? p.o.bx[2 * win.wx_lo] : win.wx_lo, 0, p.s.W - 1);
+        bool hflip = false;
+        if constexpr (FLIP) hflip = (p.flip & MYDET_VIEW_HFLIP) != 0;
+        c0 = hflip ? p.s.W - ((p.s.W - c0 + 3) & ~3) : c0 & ~3;
         if (p.o.bx) fr_stage_weights(p.o, wts, tx0, tid);               // read after the first barrier below
         // a thread owns one column of the tile: its taps are raw[xs, xs + nx)
         const int col = tid & (FR_TW - 1), wv = tid >> 6;
@@ -97,8 +106,25 @@ __global__ __launch_bounds__(256) void yuv_to_input_kernel(const YuvInputArgs p)
             const int nr = min(YUV_ROWS, win.nrows - rb);
             if (rb) __syncthreads();                                    // the previous step's taps have been read
             for (int r = wv; r < nr; r += 256 / FR_TW)                  // a wave converts a row of the window
-                for (int q = col; q < nq; q += FR_TW)
-                    *reinterpret_cast<uint4 *>(raw + r * p.max_cols + 4 * q) = yuv_quad<BPS, PLANAR>(p.s, b, win.r0 + rb + r, c0 + 4 * q);
+                for (int q = col; q < nq; q += FR_TW) {
+                    uint4 v;
+                    if constexpr (FLIP) {
+                        const int row = fr_src_row(p.flip, p.s.H, win.r0 + rb + r);
+                        if (hflip) {
+                            const int a = p.s.W - c0 - 4 * (q + 1);     // mirrored columns c0 + 4q + 3 .. c0 + 4q, a multiple of 4
+                            v = make_uint4(0u, 0u, 0u, 0u);
+                            if (a >= 0) {
+                                const uint4 t = yuv_quad<BPS, PLANAR>(p.s, b, row, a);
+                                v = make_uint4(t.w, t.z, t.y, t.x);
+                            }
+                        } else {
+                            v = yuv_quad<BPS, PLANAR>(p.s, b, row, c0 + 4 * q);
+                        }
+                    } else {
+                        v = yuv_quad<BPS, PLANAR>(p.s, b, win.r0 + rb + r, c0 + 4 * q);
+                    }
+                    *reinterpret_cast<uint4 *>(raw + r * p.max_cols + 4 * q) = v;
+                }
             __syncthreads();
             for (int r = wv; r < nr; r += 256 / FR_TW) {                // horizontal pass
                 uint32_t v = 0;
@@ -147,10 +173,11 @@ extern "C" int mydet_yuv420_to_rgb_u8(const mydet_yuv420_src *src, int B, int H,
     return mydet_launch_status();
 }
 
-extern "C" int mydet_yuv420_to_input_f32(const mydet_yuv420_src *src, int B, int H, int W, float *out, int Hp, int Wp, int oh, int ow,
-                                         int top, int left, const int32_t *bounds_x, const int32_t *kx, int ksx,
-                                         const int32_t *bounds_y, const int32_t *ky, int ksy, int norm, const float *mean3,
-                                         const float *std3, void *stream) {
+// flip == 0 launches the <N, BPS, PLANAR, false> instances: the launch mydet_yuv420_to_input_f32 has always made
+static int yuv420_to_input(const mydet_yuv420_src *src, int B, int H, int W, float *out, int Hp, int Wp, int oh, int ow, int top, int left,
+                           const int32_t *bounds_x, const int32_t *kx, int ksx, const int32_t *bounds_y, const int32_t *ky, int ksy,
+                           int norm, const float *mean3, const float *std3, int flip, void *stream) {
+    if (fr_flip_arg(flip)) return MYDET_E_BADARG;
     YuvInputArgs p;
     int bps;
     bool planar;
@@ -167,15 +194,36 @@ extern "C" int mydet_yuv420_to_input_f32(const mydet_yuv420_src *src, int B, int
     cols = (cols + 3 + 3) / 4 * 4;
     if (cols > ((int64_t)W + 3) / 4 * 4) cols = ((int64_t)W + 3) / 4 * 4;
     p.max_cols = (int)cols;
+    p.flip = flip;
     const size_t lds = fr_tile_lds_bytes(p.o) + (size_t)YUV_ROWS * p.max_cols * sizeof(uint32_t);
     if (lds > 64 * 1024) return MYDET_E_UNSUPP;
     const bool quads = fr_quad_stores(p.o);
-#define YUV_INPUT(BPS, PLANAR)                                                                                          \
-    if (quads) hipLaunchKernelGGL((yuv_to_input_kernel<4, BPS, PLANAR>), grid, dim3(256), lds, (hipStream_t)stream, p); \
-    else hipLaunchKernelGGL((yuv_to_input_kernel<1, BPS, PLANAR>), grid, dim3(256), lds, (hipStream_t)stream, p)
-    YUV_DISPATCH(bps, planar, YUV_INPUT);
+#define YUV_INPUT_F(BPS, PLANAR, FLIP)                                                                                        \
+    if (quads) hipLaunchKernelGGL((yuv_to_input_kernel<4, BPS, PLANAR, FLIP>), grid, dim3(256), lds, (hipStream_t)stream, p); \
+    else hipLaunchKernelGGL((yuv_to_input_kernel<1, BPS, PLANAR, FLIP>), grid, dim3(256), lds, (hipStream_t)stream, p)
+#define YUV_INPUT(BPS, PLANAR) YUV_INPUT_F(BPS, PLANAR, false)
+#define YUV_INPUT_FLIP(BPS, PLANAR) YUV_INPUT_F(BPS, PLANAR, true)
+    if (flip) YUV_DISPATCH(bps, planar, YUV_INPUT_FLIP);
+    else YUV_DISPATCH(bps, planar, YUV_INPUT);
+#undef YUV_INPUT_FLIP
 #undef YUV_INPUT
+#undef YUV_INPUT_F
     return mydet_launch_status();
+}
+
+extern "C" int mydet_yuv420_to_input_f32(const mydet_yuv420_src *src, int B, int H, int W, float *out, int Hp, int Wp, int oh, int ow,
+                                         int top, int left, const int32_t *bounds_x, const int32_t *kx, int ksx,
+                                         const int32_t *bounds_y, const int32_t *ky, int ksy, int norm, const float *mean3,
+                                         const float *std3, void *stream) {
+    return yuv420_to_input(src, B, H, W, out, Hp, Wp, oh, ow, top, left, bounds_x, kx, ksx, bounds_y, ky, ksy, norm, mean3, std3, 0, stream);
+}
+
+extern "C" int mydet_yuv420_to_input_flip_f32(const mydet_yuv420_src *src, int B, int H, int W, float *out, int Hp, int Wp, int oh,
+                                              int ow, int top, int left, const int32_t *bounds_x, const int32_t *kx, int ksx,
+                                              const int32_t *bounds_y, const int32_t *ky, int ksy, int norm, const float *mean3,
+                                              const float *std3, int flip, void *stream) {
+    return yuv420_to_input(src, B, H, W, out, Hp, Wp, oh, ow, top, left, bounds_x, kx, ksx, bounds_y, ky, ksy, norm, mean3, std3, flip,
+                           stream);
 }
 
 extern "C" int mydet_nv12_to_rgb_u8(const unsigned char *y, int64_t y_img_bytes, int64_t y_row_bytes, const unsigned char *uv,

@@ -1471,6 +1471,79 @@ def merge_tile_records(rec, B, T, origins, nms_thres, metric='iou', rotated_nms=
     return record_views(records)
 
 
+FUSE_KINDS = {'nms': _lib.FUSE_NMS, 'wbf': _lib.FUSE_WBF}              # MYDET_FUSE_* of include/mydet.h
+VIEWS_MAX = _lib.VIEWS_MAX
+
+
+def fuse_view_records(rec, B, V, flips, frame_hw, thres, kind='nms', metric='iou', rotated_nms=False, agnostic=False, min_score=0.0,
+                      records=None):
+    """The records of V mirrored views of each of B frames -> B records in frame coordinates: test-time augmentation
+    (include/mydet.h: mydet_fuse_view_records_f32, where the view transform, the candidate order and the WBF rules are).
+    rec: the view records, boxes in the pixel coordinates of the mirrored frame -- an int32 tensor [V*B, words] (view-major: view
+    v of frame b in row v*B + b) or [V, B, words] with any strides along V and B, or the record_views dict of a [V*B, words]
+    buffer.  flips: V views, each 0..3 or '', 'h', 'v', 'hv' (view_flip_bits).  frame_hw: (H, W) of the frames.  kind: 'nms' --
+    merge_tile_records at zero origins after the view transform, with its metric / rotated_nms / agnostic -- or 'wbf', Weighted
+    Boxes Fusion ('cxcywh' records, 'iou', no rotated_nms; clusters whose fused score is below min_score are dropped).  thres: the
+    overlap above which two boxes are one object.  records: optional int32 [B, words] buffer to write.  Every argument error
+    is a ValueError raised before any device is touched.  Returns the record_views dict; 'index' holds v*512 + k of a survivor
+    (kind 'nms') or of a cluster's first member ('wbf')."""
+    what = 'fuse_view_records'
+    if not isinstance(kind, str) or kind not in FUSE_KINDS:
+        raise ValueError(f'{what}: kind {kind!r} is not one of {sorted(FUSE_KINDS)}')
+    if not isinstance(metric, str) or metric not in MERGE_METRICS:
+        raise ValueError(f'{what}: metric {metric!r} is not one of {sorted(MERGE_METRICS)}')
+    m = MERGE_METRICS[metric]
+    B, V = int(B), int(V)
+    if not 1 <= V <= _lib.VIEWS_MAX or B < 1:
+        raise ValueError(f'{what}: B >= 1 and 1 <= V <= {_lib.VIEWS_MAX} expected, got B = {B}, V = {V}')
+    flips = [view_flip_bits(f, what) for f in flips]
+    if len(flips) != V:
+        raise ValueError(f'{what}: {V} flips expected, got {len(flips)}')
+    H, W = int(frame_hw[0]), int(frame_hw[1])
+    if H < 1 or W < 1:
+        raise ValueError(f'{what}: a positive frame size expected, got {H}x{W}')
+    min_score = float(min_score)
+    if not min_score >= 0.0:
+        raise ValueError(f'{what}: min_score >= 0 expected, got {min_score}')
+    if isinstance(rec, dict):
+        rec = _record_buffer(what, rec)
+    if not isinstance(rec, torch.Tensor) or rec.dtype != torch.int32 or rec.shape[-1] not in (_lib.REC_WORDS, _lib.REC_ROT_WORDS):
+        raise ValueError(f'{what}: int32 records of {_lib.REC_WORDS} or {_lib.REC_ROT_WORDS} words expected')
+    words = rec.shape[-1]
+    width = 4 if words == _lib.REC_WORDS else 5
+    if rotated_nms and width != 5:
+        raise ValueError(f"{what}: rotated_nms needs 'cxcywhd' records (the rotated record with its angle plane)")
+    if kind == 'wbf':
+        if width != 4:
+            raise ValueError(f"{what}: kind 'wbf' is defined for 'cxcywh' records only (no mean of angles)")
+        if m != _lib.MERGE_IOU or rotated_nms:
+            raise ValueError(f"{what}: kind 'wbf' takes metric 'iou' and no rotated_nms")
+    elif rotated_nms and (m == _lib.MERGE_IOS or agnostic):
+        raise ValueError(f"{what}: rotated_nms goes with metric 'iou' and without agnostic")
+    if rec.dim() == 2 and rec.shape[0] == V * B:
+        rec = rec.contiguous().view(V, B, words)
+    if tuple(rec.shape) != (V, B, words):
+        raise ValueError(f'{what}: records of shape [{V * B}, {words}] or [{V}, {B}, {words}] expected, got {tuple(rec.shape)}')
+    require_gpu(rec, what)
+    if rec.stride(2) != 1 or rec.stride(0) % 4 or rec.stride(1) % 4 or min(rec.stride(0), rec.stride(1)) < 0:
+        rec = rec.contiguous()
+    dev = rec.device
+    if records is None:
+        records = torch.empty((B, words), dtype=torch.int32, device=dev)
+    assert records.dtype == torch.int32 and tuple(records.shape) == (B, words) and records.is_contiguous() and records.device == dev
+    mode = _lib.FuseMode(FUSE_KINDS[kind], m, int(bool(rotated_nms)), int(bool(agnostic)), min_score, 0)
+    nbytes = _lib.lib().mydet_fuse_view_records_scratch_bytes(B, V, width, mode.kind)
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    host_flips = (ctypes.c_int32 * V)(*flips)
+    t0 = TIMER.start() if TIMER else None
+    code = _lib.lib().mydet_fuse_view_records_f32(_ptr(rec), rec.stride(0), rec.stride(1), B, V, width, host_flips, H, W, float(thres),
+                                                  ctypes.byref(mode), _ptr(records), _ptr(scratch), nbytes, _stream())
+    if t0:
+        TIMER.stop('fuse_view_records', t0, float(B))
+    _lib.check(code, 'mydet_fuse_view_records_f32')
+    return record_views(records)
+
+
 TRACK_MATCHES = {'iou': _lib.TRACK_MATCH_IOU, 'rotated': _lib.TRACK_MATCH_ROTATED}        # MYDET_TRACK_MATCH_* of include/mydet.h
 # KFTracklet's constants (reference utils/structures.py:457-460): standard deviations; the kernel takes their squares
 TRACK_P0 = (0.1, 0.1, 0.1, 0.1, 10, 0.1, 0.1, 0.1, 0.1, 10)
@@ -1747,13 +1820,36 @@ def packed_pixels(frames):
     return frames.stride(3) == 1 and frames.stride(2) == 3 and frames.stride(1) >= 3 * frames.shape[2] and frames.stride(0) >= 0
 
 
-def frames_to_input(frames_u8, geometry, input_format, out=None):
+VIEW_HFLIP, VIEW_VFLIP = _lib.VIEW_HFLIP, _lib.VIEW_VFLIP      # MYDET_VIEW_* of include/mydet.h
+
+
+def view_flip_bits(flip, what='flip'):
+    """The MYDET_VIEW_* bits of a mirrored view: an int 0..3, or '' / 'h' / 'v' / 'hv'.  A ValueError for anything else, raised
+    before any device is touched."""
+    if isinstance(flip, str):
+        if flip not in ('', 'h', 'v', 'hv', 'vh'):
+            raise ValueError(f"{what}: a flip is '', 'h', 'v' or 'hv', got {flip!r}")
+        return (VIEW_HFLIP if 'h' in flip else 0) | (VIEW_VFLIP if 'v' in flip else 0)
+    if isinstance(flip, bool) or not isinstance(flip, int) or not 0 <= flip <= (VIEW_HFLIP | VIEW_VFLIP):
+        raise ValueError(f'{what}: flip bits 0..3 (1 = horizontal, 2 = vertical) expected, got {flip!r}')
+    return flip
+
+
+def _flip_dims(flip, first):
+    """torch.flip dimensions of the view `flip` for a tensor whose rows are dimension `first`."""
+    return [d for d, bit in ((first, VIEW_VFLIP), (first + 1, VIEW_HFLIP)) if flip & bit]
+
+
+def frames_to_input(frames_u8, geometry, input_format, out=None, flip=0):
     """uint8 frames [B,H,W,3] (or [H,W,3]) of one size on the device -> the float32 network input [B,3,Hp,Wp] in ONE launch
     (include/mydet.h: mydet_frames_to_input_f32): PIL-exact resize, zero padding, /255 and normalisation, the bits
     resize_bilinear_u8 + preprocess_u8 give.  geometry: Detector._geometry's tuple (resize target (h, w) or None,
     (top, left), (Hp, Wp), pad_info).  The frames are read through their strides when pixels are packed (a crop of a
     larger buffer is used in place); a downscale whose filter has more taps than the kernel stages
-    (_lib.FRAMES_MAX_TAPS) goes through the two existing kernels instead.  out: optional float32 [B,3,Hp,Wp] view."""
+    (_lib.FRAMES_MAX_TAPS) goes through the two existing kernels instead.  out: optional float32 [B,3,Hp,Wp] view.
+    flip: the mirrored view (view_flip_bits: 1 = horizontal, 2 = vertical) -- the bits of this call on torch.flip of the frames,
+    read in place by the same launch (mydet_frames_to_input_flip_f32); only the fallback past the tap limit mirrors a copy."""
+    flip = view_flip_bits(flip, 'frames_to_input')
     require_gpu(frames_u8, 'frames_to_input')
     if frames_u8.dtype != torch.uint8:
         raise TypeError(f'frames_to_input: uint8 frames expected, got {frames_u8.dtype}')
@@ -1768,10 +1864,17 @@ def frames_to_input(frames_u8, geometry, input_format, out=None):
     if taps > _lib.FRAMES_MAX_TAPS:
         Hp, Wp = geometry[2]
         buf = torch.zeros((B, Hp, Wp, 3), dtype=torch.uint8, device=frames_u8.device)
+        if flip:
+            frames_u8 = torch.flip(frames_u8, _flip_dims(flip, 1))
         for n in range(B):
             resize_bilinear_u8(frames_u8[n].contiguous(), (oh, ow), buf[n], top, left)
         return out.copy_(preprocess_u8(buf, (Hp, Wp), input_format))
-    code = _lib.lib().mydet_frames_to_input_f32(_ptr(frames_u8), B, H, W, frames_u8.stride(0), frames_u8.stride(1), *tail, _stream())
+    head = (_ptr(frames_u8), B, H, W, frames_u8.stride(0), frames_u8.stride(1))
+    if flip:
+        code = _lib.lib().mydet_frames_to_input_flip_f32(*head, *tail, flip, _stream())
+        _lib.check(code, 'mydet_frames_to_input_flip_f32')
+        return out
+    code = _lib.lib().mydet_frames_to_input_f32(*head, *tail, _stream())
     _lib.check(code, 'mydet_frames_to_input_f32')
     return out
 
@@ -1900,20 +2003,26 @@ def yuv420_to_rgb(planes, layout, matrix='bt601', full_range=False, out=None):
     return dst[0] if single else dst
 
 
-def yuv420_to_input(planes, layout, geometry, input_format, matrix='bt601', full_range=False, out=None):
+def yuv420_to_input(planes, layout, geometry, input_format, matrix='bt601', full_range=False, out=None, flip=0):
     """4:2:0 frames of one size on the device -> the float32 network input [B,3,Hp,Wp] in ONE launch (include/mydet.h:
     mydet_yuv420_to_input_f32): the bits of frames_to_input(yuv420_to_rgb(planes, layout, matrix, full_range), geometry,
     input_format) without the RGB frames.  planes, layout, matrix, full_range as in yuv420_to_rgb; geometry, input_format,
     out and the tap limit as in frames_to_input -- past the limit the frames are converted and go through frames_to_input's
-    own fallback."""
+    own fallback.  flip: the mirrored view (view_flip_bits), by mydet_yuv420_to_input_flip_f32: the mirrored RGB frames of
+    yuv420_to_rgb, chroma fetched at the pixel's own position in the planes."""
+    flip = view_flip_bits(flip, 'yuv420_to_input')
     yuv420_layout(layout)
     m = yuv_matrix_id(matrix)
     checked, _ = _yuv420_planes(planes, layout, 'yuv420_to_input')
     B, H, W = checked[0].shape
     out, _, _, taps, tail = _input_window('yuv420_to_input', B, H, W, checked[0].device, geometry, input_format, out)
     if taps > _lib.FRAMES_MAX_TAPS:
-        return frames_to_input(yuv420_to_rgb(planes, layout, matrix, full_range), geometry, input_format, out)
+        return frames_to_input(yuv420_to_rgb(planes, layout, matrix, full_range), geometry, input_format, out, flip)
     src = _yuv420_src(checked, layout, m, full_range)
+    if flip:
+        code = _lib.lib().mydet_yuv420_to_input_flip_f32(ctypes.byref(src), B, H, W, *tail, flip, _stream())
+        _lib.check(code, 'mydet_yuv420_to_input_flip_f32')
+        return out
     code = _lib.lib().mydet_yuv420_to_input_f32(ctypes.byref(src), B, H, W, *tail, _stream())
     _lib.check(code, 'mydet_yuv420_to_input_f32')
     return out
