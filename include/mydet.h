@@ -1234,6 +1234,91 @@ int mydet_eval_accumulate_f64(const mydet_eval_set *set, const int32_t *order, c
                               const int32_t *max_dets, int M, const double *rec_thrs, int R, double *precision, double *recall,
                               double *scores, void *stream);
 
+/* Scoring tracks against ground truth: the CLEAR MOT counts (Bernardin & Stiefelhagen, applied as py-motmetrics applies them) and
+ * the identity counts behind IDF1 (Ristani et al.), in three stream-ordered launches (csrc/mot.hip) behind mydet_eval_ious_f64.
+ * The reference has no tracking loop and no track scorer; its CEPDOF / COSSY annotations carry a person_id per box, and tracked
+ * calls return ImageObjects.obj_ids: this is the scorer between them.  Agreement with py-motmetrics or TrackEval themselves is not
+ * claimed; what is claimed, and tested with ==, is the rules below.
+ *
+ * Data model.  The packed arrays of mydet_eval_set are reused as they are: an "image" is a frame, all sequences laid end to end
+ *   (I = the total number of frames); a group is a (frame, category) pair, g = k*I + f; dt_* are the tracker's boxes (the
+ *   hypotheses) and gt_* the annotated ones.  mydet_eval_ious_f64 is called unchanged and gives `ious` (axis-aligned float64, or
+ *   the exact rotated IoU).  gt_flags, the areas and the scores are not read here: every ground-truth row counts.
+ *   mydet_mot_set adds (DEVICE pointers; the scalars are what the host knows about them):
+ *     seq_start           int32 [S + 1], seq_start[0] = 0, seq_start[S] = I: sequence s is frames [seq_start[s], seq_start[s + 1])
+ *     a UNIT is one (sequence, category), u = k*S + s, U = S*K units, independent of each other
+ *     gt_id, dt_id        int32 [G], [D]: the dense identity index of every row inside its unit, 0 .. n - 1
+ *     gt_id_start, dt_id_start   int32 [U + 1]: unit u owns identities [start[u], start[u + 1]) of the Gids = gt_id_start[U]
+ *                         (Hids = dt_id_start[U]) global ones
+ *     ov_start            int64 [U + 1]: unit u owns nG_u * nH_u entries of an overlap matrix from ov_start[u]; n_ov = ov_start[U]
+ *   The packer (mydetection_amd.ops.mot_pack) guarantees that one identity appears at most once per frame on each side.
+ *
+ * Pair rules, every launch.  Rows are the ground truths of the group and columns its hypotheses, both in stored order.  A pair is
+ *   eligible when iou[r, c] >= thr[t], compared in float64; a NaN IoU is never eligible; the threshold is not clamped.  Costs are
+ *   integers so that no summation order can change a decision: q = (int64)floor(iou * 65536.0); an eligible pair costs 65536 - q,
+ *   an ineligible one BIG = 1 << 27, which exceeds any sum of 1024 eligible costs -- so the minimum-cost assignment first has the
+ *   most eligible pairs and then the least cost among those.  Sums are int64.
+ *
+ * The assignment routine (shared): the shortest-augmenting-path Hungarian method in its textbook u / v / p / way / minv form.
+ *   Rows are inserted in ascending order.  Inside an augmentation the next column is the unused column of least minv; a tie goes
+ *   to the lowest column index.  If there are more rows than columns the problem is transposed first (the routine's rows are then
+ *   the columns).  One wavefront: lanes own columns, a row step is one wave minimum over (minv, column), costs are formed on the fly.
+ *
+ * mydet_mot_clear_f64: one wavefront per (unit, threshold) walks the unit's frames in order.  State per ground-truth identity o:
+ *   last[o], the hypothesis identity of its most recent match (-1 at first; it persists over frames where o is unmatched or
+ *   absent); whether o was ever matched; whether o was matched in the previous frame in which it was present.  Per frame:
+ *   1. Keep.  Rows ascending: if last[o] >= 0, a column with that identity is in the frame, the pair is eligible and the column
+ *      is free, they are matched.
+ *   2. Assign.  The routine above on the remaining rows and columns, relative order kept; matches are the assigned pairs that are
+ *      eligible.
+ *   3. Count matches, rows ascending: TP += 1; SIOU += iou (float64, in this order); IDSW += 1 when last[o] >= 0 and differs from
+ *      the column's identity; FRAG += 1 when o was matched before but not in its previous present frame; last[o] = the column's
+ *      identity; matched[o] += 1.
+ *   4. FN += the unmatched rows; FP += the unmatched columns; present[o] += 1 for every row.
+ *   Outputs, every element written: counts int64 [U][T][5] = (TP, FP, FN, IDSW, FRAG); siou float64 [U][T]; present int32 [Gids];
+ *   matched int32 [T][Gids]; gt_match (may be NULL) int32 [T][G], the matched hypothesis row (an index into the D rows) or -1.
+ *
+ * mydet_mot_id_overlap: n[o][h], per unit and threshold, is the number of frames in which both identities are present and their
+ *   pair is eligible.  One thread per pair of `ious`; integer atomic adds into int32 matrices in caller scratch, [T][n_ov], which
+ *   the call zeroes first (stream-ordered); the result does not depend on order.  mydet_mot_scratch_bytes(mot, T) sizes it.
+ * mydet_mot_id_assign: IDTP[u][t] = the largest sum of n[o][h] over one-to-one pairings: the same routine with cost F_u - n, F_u
+ *   the unit's frame count, the smaller side on the rows.  Only the optimum value is an output (int64 [U][T]); it is unique even
+ *   when the pairing is not.  IDFN = nGT - IDTP and IDFP = nHyp - IDTP are the host's.
+ *
+ * iou_thrs is a HOST pointer, read before the launch.
+ * MYDET_E_BADARG, nothing launched: every mydet_eval_set rule above; a null mot; S < 1 or S > I; a negative count; n_gt_ids > G,
+ *   n_dt_ids > D, max_gt_ids > n_gt_ids, max_dt_ids > n_dt_ids, n_ov > n_gt_ids * n_dt_ids; a null seq_start, gt_id_start,
+ *   dt_id_start or ov_start; a null gt_id with G > 0 or dt_id with D > 0; T < 1; a null or NaN threshold (clear, overlap); null ious
+ *   with n_pairs > 0 (clear, overlap); a null output that would be written; scratch smaller than mydet_mot_scratch_bytes, or null
+ *   when that is not 0.
+ * MYDET_E_UNSUPP, nothing launched: max_gt > MYDET_EVAL_MAX_GT or max_dt > MYDET_EVAL_MAX_DT (rows of one group); max_gt_ids or
+ *   max_dt_ids > MYDET_MOT_MAX_IDS (identities of one unit and side); T > MYDET_EVAL_MAX_THRS.  A frame or a unit whose tables
+ *   hold more than was promised is left out by the kernels.
+ * Both wavefront kernels keep their state in dynamic LDS: 65 KiB for the CLEAR kernel, above the 64 KiB a kernel gets without the
+ *   opt-in and opted into once per device, and 32 KiB for the identity assignment.
+ * MYDET_MOT_MAX_IDS is 1024 and not 2048 because of the assignment's worst case, a matrix of ties, in which every inserted row walks
+ *   through the columns taken before it: measured on one MI355X (profiles/mot.md), the identity assignment of 2048 x 2048
+ *   identities whose overlaps are all 0 or 1 took 9.05 s in one wavefront, that of 1024 x 1024 0.75 s; a 2048 x 2048 problem with
+ *   spread overlaps took 32 ms. */
+#define MYDET_MOT_MAX_IDS 1024
+typedef struct mydet_mot_set {
+    int S;                           /* sequences */
+    int max_gt_ids, max_dt_ids;      /* the largest identity count of one unit, per side */
+    int64_t n_gt_ids, n_dt_ids;      /* Gids = gt_id_start[U], Hids = dt_id_start[U] */
+    int64_t n_ov;                    /* ov_start[U] */
+    const int32_t *seq_start;
+    const int32_t *gt_id, *dt_id;
+    const int32_t *gt_id_start, *dt_id_start;
+    const int64_t *ov_start;
+} mydet_mot_set;
+int mydet_mot_clear_f64(const mydet_eval_set *set, const mydet_mot_set *mot, const double *ious, const double *iou_thrs, int T,
+                        int64_t *counts, double *siou, int32_t *present, int32_t *matched, int32_t *gt_match, void *stream);
+int64_t mydet_mot_scratch_bytes(const mydet_mot_set *mot, int T);
+int mydet_mot_id_overlap(const mydet_eval_set *set, const mydet_mot_set *mot, const double *ious, const double *iou_thrs, int T,
+                         void *scratch, int64_t scratch_bytes, void *stream);
+int mydet_mot_id_assign(const mydet_eval_set *set, const mydet_mot_set *mot, int T, const void *scratch, int64_t scratch_bytes,
+                        int64_t *idtp, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

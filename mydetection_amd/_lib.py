@@ -121,6 +121,10 @@ SIGNATURES = {
     'mydet_eval_match_f64': [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr],
     'mydet_eval_accumulate_f64': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr,
                                   c_ptr, c_ptr],
+    'mydet_mot_clear_f64': [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_mot_scratch_bytes': [c_ptr, c_int],
+    'mydet_mot_id_overlap': [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr],
+    'mydet_mot_id_assign': [c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr],
     'mydet_cxcywh_to_x1y1x2y2_f32': [c_ptr, c_ptr, c_i64, c_int, c_ptr],
     'mydet_bboxes_to_original_f32': [c_ptr, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr],
 }
@@ -128,7 +132,7 @@ SIGNATURES = {
 
 
 RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems',
-               'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words'}
+               'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words', 'mydet_mot_scratch_bytes'}
 
 # detection record layout (MYDET_REC_* of include/mydet.h), in int32 words
 REC_TOPK = 512
@@ -163,6 +167,8 @@ CROP_U8, CROP_F32 = 0, 1
 # scoring (mydet_eval_*): MYDET_EVAL_* of include/mydet.h
 EVAL_MAX_GT, EVAL_MAX_DT, EVAL_MAX_THRS, EVAL_MAX_AREAS, EVAL_MAX_DETS, EVAL_MAX_RECS = 1024, 1024, 32, 8, 8, 128
 EVAL_GT_IGNORE, EVAL_GT_CROWD = 1, 2
+# track scoring (mydet_mot_*): MYDET_MOT_MAX_IDS of include/mydet.h
+MOT_MAX_IDS = 1024
 
 
 class DecodeLevel(ctypes.Structure):
@@ -260,6 +266,13 @@ class EvalSet(ctypes.Structure):
                 ('D', c_i64), ('G', c_i64), ('n_pairs', c_i64), ('groups', c_ptr), ('dt_start', c_ptr), ('gt_start', c_ptr),
                 ('pair_start', c_ptr), ('dt_box', c_ptr), ('gt_box', c_ptr), ('dt_score', c_ptr), ('dt_area', c_ptr), ('gt_area', c_ptr),
                 ('gt_flags', c_ptr)]
+
+
+class MotSet(ctypes.Structure):
+    """mydet_mot_set (include/mydet.h): sequences and identities beside a mydet_eval_set, device pointers."""
+    _fields_ = [('S', c_int), ('max_gt_ids', c_int), ('max_dt_ids', c_int), ('n_gt_ids', c_i64), ('n_dt_ids', c_i64), ('n_ov', c_i64),
+                ('seq_start', c_ptr), ('gt_id', c_ptr), ('dt_id', c_ptr), ('gt_id_start', c_ptr), ('dt_id_start', c_ptr),
+                ('ov_start', c_ptr)]
 
 
 # MYDET_YUV420_* of include/mydet.h

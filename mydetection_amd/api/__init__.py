@@ -2,10 +2,10 @@
 argument of its tiled detection on large frames, `Tracker`, the argument that turns its frame methods into a tracker,
 `Draw`, the settings of its annotate_frames methods, `Chips`, the settings of its crop_frames methods, `Nms`, how its
 post-process suppresses (class-agnostic, Soft-NMS, box merging), `Augment`, its test-time augmentation (mirrored and rescaled
-views fused on the device), and `Evaluator`, which scores what it returns against ground
-truth."""
+views fused on the device), `Evaluator`, which scores what it returns against ground
+truth, and `TrackEvaluator`, which scores its tracks against ground-truth identities."""
 from .detection import Augment, Chips, Detector, Draw, Nms, Tiles
-from .evaluation import Evaluator
+from .evaluation import Evaluator, TrackEvaluator
 from .tracking import Tracker
 
-__all__ = ['Augment', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Tiles', 'Tracker']
+__all__ = ['Augment', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Tiles', 'TrackEvaluator', 'Tracker']

@@ -10,6 +10,7 @@
 // (which ground truths a problem has used) is a bit set in LDS, column `lane` of a [word][64] array -- a lane touches only its
 // own column (no barrier) and lanes l, l + 32 share a bank without conflict.
 #include "common.h"
+#include "eval_set.h"
 #include "rot_iou.h"
 
 namespace {
@@ -248,21 +249,6 @@ __global__ __launch_bounds__(EV_WAVE) void eval_accumulate_kernel(const mydet_ev
             scores[p0 + r * pstep] = 0.0;
         }
     if (lane == 0) recall[(((int64_t)t * s.K + k) * q.A + a) * cv.M + mi] = nd ? rc_last : 0.0;
-}
-
-// The checks every entry point makes on the set.  Nothing is dereferenced: the pointers are device pointers.
-int eval_check_set(const mydet_eval_set *s) {
-    if (!s || (s->rotated != 0 && s->rotated != 1)) return MYDET_E_BADARG;
-    if (s->I < 1 || s->K < 1 || s->D < 0 || s->G < 0 || s->n_groups < 0 || s->n_pairs < 0 || s->max_dt < 0 || s->max_gt < 0) return MYDET_E_BADARG;
-    if (s->I > 0x7fffffff / s->K || s->n_groups > s->I * s->K || s->D > 0x7fffffff || s->G > 0x7fffffff) return MYDET_E_BADARG;
-    if (!s->dt_start || !s->gt_start) return MYDET_E_BADARG;
-    if (s->n_groups > 0 && (!s->groups || !s->pair_start)) return MYDET_E_BADARG;
-    if (s->D > 0 && (!s->dt_box || !s->dt_score || !s->dt_area)) return MYDET_E_BADARG;
-    if (s->G > 0 && (!s->gt_box || !s->gt_area || !s->gt_flags)) return MYDET_E_BADARG;
-    if (s->max_dt > s->D || s->max_gt > s->G || s->n_pairs > s->D * s->G) return MYDET_E_BADARG;
-    if ((s->D > 0 || s->G > 0) && s->n_groups == 0) return MYDET_E_BADARG;
-    if (s->max_gt > MYDET_EVAL_MAX_GT || s->max_dt > MYDET_EVAL_MAX_DT) return MYDET_E_UNSUPP;
-    return 0;
 }
 
 int eval_thresholds(EvalThresholds &q, const double *iou_thrs, int T, const double *area_rng, int A) {

@@ -2883,3 +2883,305 @@ def eval_summarize(precision, recall, params):
     for n, area in enumerate(('small', 'medium', 'large')):
         stats[9 + n] = row(0, area=area, max_dets=top)
     return stats, ''.join(line + '\n' for line in lines)
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# Scoring tracks against ground truth (include/mydet.h: mydet_mot_set and the three mydet_mot_* launches; the rules are there).
+# mot_pack and mot_summarize are host numpy; everything between them runs on the device.
+MOT_ID_KEYS = ('track_id', 'person_id')
+MOT_COUNTS = ('tp', 'fp', 'fn', 'idsw', 'frag')
+
+
+def mot_columns(rows, kind):
+    """JSON hypothesis rows that carry 'track_id' -> the columns mot_pack takes: image_id, category_id and track_id (lists),
+    bbox float64 [N, 4 | 5].  With kind 'cepdof' category_id defaults to 1."""
+    width = 5 if _eval_kind(kind) else 4
+    for r in rows:
+        if 'track_id' not in r:
+            raise ValueError("mot_columns: a hypothesis row without 'track_id'")
+        if len(r['bbox']) < width:
+            raise ValueError(f"mot_columns: kind {kind!r} scores {width}-wide boxes, got {len(r['bbox'])}")
+    return {'image_id': [r['image_id'] for r in rows],
+            'category_id': [r.get('category_id', 1) for r in rows] if width == 5 else [r['category_id'] for r in rows],
+            'track_id': [r['track_id'] for r in rows],
+            'bbox': np.array([r['bbox'][:width] for r in rows], dtype=np.float64).reshape(len(rows), width)}
+
+
+def mot_sequences(gt, sequences=None):
+    """(names, [image ids of each sequence in frame order]).  sequences: a dict {name: [img_id, ...]} gives them explicitly; None
+    groups the images by 'video_id' ordered by 'frame_id' when every image has both, and otherwise makes one sequence in
+    `images` order."""
+    images = gt['images']
+    if sequences is not None:
+        names = list(sequences)
+        frames = [list(sequences[n]) for n in names]
+        known = set(im['id'] for im in images)
+        for n, ids in zip(names, frames):
+            missing = [i for i in ids if i not in known]
+            if missing:
+                raise ValueError(f'sequence {n!r}: image id {missing[0]!r} is not in the ground truth')
+    elif images and all('video_id' in im and 'frame_id' in im for im in images):
+        by = {}
+        for im in images:
+            by.setdefault(im['video_id'], []).append((im['frame_id'], im['id']))
+        names = sorted(by)
+        frames = [[i for _, i in sorted(by[n])] for n in names]
+    else:
+        names, frames = ['all'], [[im['id'] for im in images]]
+    flat = [i for ids in frames for i in ids]
+    if len(set(flat)) != len(flat):
+        raise ValueError('mot_sequences: an image id appears in more than one frame')
+    if not flat:
+        raise ValueError('mot_sequences: no frames')
+    return names, frames
+
+
+def mot_id_key(gt, id_key=None):
+    """The identity key of the ground-truth annotations: id_key, or the first of 'track_id' and 'person_id' they carry."""
+    anns = gt['annotations']
+    keys = (id_key,) if id_key is not None else MOT_ID_KEYS
+    for key in keys:
+        if all(key in a for a in anns):
+            return key
+    raise ValueError(f'ground-truth annotations without an identity: one of {keys} expected in every annotation')
+
+
+def _mot_side(images, cats, ids, frame_of, cat_of, seq_of, I, S, what):
+    """The packed order of one side (stable by group), its groups, and its dense identities per unit."""
+    f = np.fromiter((frame_of.get(v, -1) for v in images), dtype=np.int64, count=len(images))
+    k = np.fromiter((cat_of(v) for v in cats), dtype=np.int64, count=len(cats))
+    keep = np.nonzero((f >= 0) & (k >= 0))[0]
+    g = k[keep] * I + f[keep]
+    o = np.argsort(g, kind='stable')
+    rows, g = keep[o], g[o]
+    unit = (g // I) * S + seq_of[g % I]
+    dense = np.zeros(len(rows), dtype=np.int32)
+    tables, seen = {}, set()
+    for n, (r, gg, u) in enumerate(zip(rows.tolist(), g.tolist(), unit.tolist())):
+        table = tables.setdefault(u, {})
+        dense[n] = table.setdefault(ids[r], len(table))
+        if (gg, dense[n]) in seen:
+            raise ValueError(f'mot_pack: {what} identity {ids[r]!r} appears twice in image {images[r]!r}')
+        seen.add((gg, dense[n]))
+    return rows, g, dense, tables
+
+
+def mot_pack(dts, gt, kind, sequences=None, id_key=None, use_cats=True):
+    """Host-only: hypotheses (JSON rows with 'track_id', or the columns of mot_columns) and a loaded ground-truth dict -> the dense
+    numpy arrays of mydet_eval_set and mydet_mot_set (include/mydet.h, 'Data model').  Frames are the images of the sequences laid
+    end to end (mot_sequences); categories are the sorted category ids, or one category with use_cats=False; rows keep input order
+    inside their group.  Beside the arrays the dict holds the scalars, seq_names, cat_ids, img_ids (frame order), dt_rows / gt_rows
+    and gt_ids / dt_ids: per unit, the identity of every dense index.  A duplicate identity in a frame is a ValueError."""
+    rotated = _eval_kind(kind)
+    width = 5 if rotated else 4
+    cols = dts if isinstance(dts, dict) else mot_columns(dts, kind)
+    names, frames = mot_sequences(gt, sequences)
+    img_ids = [i for ids in frames for i in ids]
+    cat_ids = sorted(set(c['id'] for c in gt['categories'])) if use_cats else [None]
+    I, S, K = len(img_ids), len(names), len(cat_ids)
+    if K < 1 or I * K >= 2 ** 31:
+        raise ValueError(f'mot_pack: {I} frames x {K} categories')
+    U = S * K
+    seq_start = np.zeros(S + 1, dtype=np.int64)
+    np.cumsum([len(ids) for ids in frames], out=seq_start[1:])
+    seq_of = np.repeat(np.arange(S), np.diff(seq_start))
+    frame_of = {v: n for n, v in enumerate(img_ids)}
+    cat_index = {v: n for n, v in enumerate(cat_ids)}
+    cat_of = (lambda v: cat_index.get(v, -1)) if use_cats else (lambda v: 0)
+
+    anns = gt['annotations']
+    key = mot_id_key(gt, id_key)
+    for a in anns:
+        if len(a['bbox']) < width:
+            raise ValueError(f"mot_pack: kind {kind!r} scores {width}-wide boxes, got {len(a['bbox'])} in the ground truth")
+    gt_rows, gt_g, gt_id, gt_tables = _mot_side([a['image_id'] for a in anns], [a.get('category_id', 1) for a in anns],
+                                                [a[key] for a in anns], frame_of, cat_of, seq_of, I, S, 'ground-truth')
+    dt_box_in = np.asarray(cols['bbox'], dtype=np.float64)
+    if dt_box_in.size and (dt_box_in.ndim != 2 or dt_box_in.shape[1] != width):
+        raise ValueError(f'mot_pack: kind {kind!r} scores {width}-wide boxes, got {dt_box_in.shape}')
+    dt_rows, dt_g, dt_id, dt_tables = _mot_side(cols['image_id'], cols['category_id'], cols['track_id'], frame_of, cat_of, seq_of,
+                                                I, S, 'hypothesis')
+    G, D = len(gt_rows), len(dt_rows)
+    gt_box = np.array([anns[r]['bbox'][:width] for r in gt_rows], dtype=np.float64).reshape(G, width)
+    dt_box = dt_box_in.reshape(-1, width)[dt_rows]
+    gt_start, dt_start = _eval_starts(gt_g, I * K), _eval_starts(dt_g, I * K)
+    nd, ng = np.diff(dt_start), np.diff(gt_start)
+    groups = np.nonzero((nd > 0) | (ng > 0))[0]
+    pair_start = np.zeros(len(groups) + 1, dtype=np.int64)
+    np.cumsum(nd[groups] * ng[groups], out=pair_start[1:])
+    n_gid = np.array([len(gt_tables.get(u, ())) for u in range(U)], dtype=np.int64)
+    n_hid = np.array([len(dt_tables.get(u, ())) for u in range(U)], dtype=np.int64)
+    gt_id_start, dt_id_start, ov_start = (np.zeros(U + 1, dtype=np.int64) for _ in range(3))
+    np.cumsum(n_gid, out=gt_id_start[1:])
+    np.cumsum(n_hid, out=dt_id_start[1:])
+    np.cumsum(n_gid * n_hid, out=ov_start[1:])
+    if gt_id_start[-1] >= 2 ** 31 or dt_id_start[-1] >= 2 ** 31:
+        raise ValueError('mot_pack: too many identities')
+    box_type = np.float32 if rotated else np.float64
+    return {'kind': kind, 'rotated': int(rotated), 'I': I, 'K': K, 'S': S, 'U': U, 'D': D, 'G': G, 'n_pairs': int(pair_start[-1]),
+            'max_dt': int(nd.max()) if D else 0, 'max_gt': int(ng.max()) if G else 0,
+            'max_gt_ids': int(n_gid.max()), 'max_dt_ids': int(n_hid.max()), 'n_gt_ids': int(gt_id_start[-1]),
+            'n_dt_ids': int(dt_id_start[-1]), 'n_ov': int(ov_start[-1]),
+            'img_ids': img_ids, 'cat_ids': cat_ids, 'seq_names': names, 'dt_rows': dt_rows, 'gt_rows': gt_rows,
+            'gt_ids': [list(gt_tables.get(u, ())) for u in range(U)], 'dt_ids': [list(dt_tables.get(u, ())) for u in range(U)],
+            'groups': groups.astype(np.int32), 'pair_start': pair_start,
+            'dt_start': dt_start.astype(np.int32), 'gt_start': gt_start.astype(np.int32),
+            'dt_box': np.ascontiguousarray(dt_box.astype(box_type)), 'gt_box': np.ascontiguousarray(gt_box.astype(box_type)),
+            'dt_score': np.ones(D), 'dt_area': dt_box[:, 2] * dt_box[:, 3], 'gt_area': gt_box[:, 2] * gt_box[:, 3],
+            'gt_flags': np.zeros(G, dtype=np.uint8),
+            'seq_start': seq_start.astype(np.int32), 'gt_id': gt_id, 'dt_id': dt_id,
+            'gt_id_start': gt_id_start.astype(np.int32), 'dt_id_start': dt_id_start.astype(np.int32), 'ov_start': ov_start}
+
+
+MOT_SET_ARRAYS = ('seq_start', 'gt_id', 'dt_id', 'gt_id_start', 'dt_id_start', 'ov_start')
+
+
+def mot_set_struct(pack, pointers):
+    """_lib.MotSet from the scalars of a pack and a name -> address mapping (a null pointer for an absent or empty array)."""
+    c = _lib.MotSet()
+    for k in ('S', 'max_gt_ids', 'max_dt_ids', 'n_gt_ids', 'n_dt_ids', 'n_ov'):
+        setattr(c, k, int(pack[k]))
+    for k in MOT_SET_ARRAYS:
+        setattr(c, k, pointers.get(k) if len(pack[k]) else None)
+    return c
+
+
+class MotSet:
+    """The arrays of mot_pack as tensors on one device (`.t`), with the mydet_eval_set (`.c`) and the mydet_mot_set (`.m`) that
+    point at them."""
+
+    def __init__(self, pack, device=None):
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError('MotSet: no GPU is visible; mydetection_amd scores on MI355X only (there is no CPU path in this package)')
+            device = 'cuda'
+        self.pack = pack
+        self.t = {k: torch.from_numpy(np.ascontiguousarray(pack[k])).to(device) for k in EVAL_SET_ARRAYS + MOT_SET_ARRAYS}
+        require_gpu(self.t['dt_start'], 'MotSet')
+        self.device = self.t['dt_start'].device
+        self.c = eval_set_struct(pack, {k: self.t[k].data_ptr() for k in EVAL_SET_ARRAYS})
+        self.m = mot_set_struct(pack, {k: self.t[k].data_ptr() for k in MOT_SET_ARRAYS})
+
+
+def mot_clear(ms, ious, iou_thrs, rows=False):
+    """mydet_mot_clear_f64, one launch: (counts int64 [U, T, 5] = (TP, FP, FN, IDSW, FRAG), siou float64 [U, T], present int32
+    [Gids], matched int32 [T, Gids], gt_match int32 [T, G] or None unless rows=True)."""
+    thr = _eval_thresholds(iou_thrs, 'iou_thrs')
+    p, T, dev = ms.pack, len(thr), ms.device
+    counts = torch.empty((p['U'], T, 5), dtype=torch.int64, device=dev)
+    siou = torch.empty((p['U'], T), dtype=torch.float64, device=dev)
+    present = torch.empty((p['n_gt_ids'],), dtype=torch.int32, device=dev)
+    matched = torch.empty((T, p['n_gt_ids']), dtype=torch.int32, device=dev)
+    gt_match = torch.empty((T, p['G']), dtype=torch.int32, device=dev) if rows else None
+    with torch.cuda.device(dev):
+        code = _lib.lib().mydet_mot_clear_f64(ctypes.byref(ms.c), ctypes.byref(ms.m), _ptr(ious), thr.ctypes.data, T, _ptr(counts),
+                                              _ptr(siou), _ptr(present), _ptr(matched), _ptr(gt_match), _stream())
+    _lib.check(code, 'mydet_mot_clear_f64')
+    return counts, siou, present, matched, gt_match
+
+
+def mot_id_overlap(ms, ious, iou_thrs):
+    """mydet_mot_id_overlap (a memset and one launch): int32 [T, n_ov], per threshold the identity-overlap matrix of every unit,
+    unit u's [nG_u, nH_u] block at ov_start[u].  The tensor is the scratch mydet_mot_scratch_bytes sizes."""
+    thr = _eval_thresholds(iou_thrs, 'iou_thrs')
+    T = len(thr)
+    overlap = torch.empty((T, ms.pack['n_ov']), dtype=torch.int32, device=ms.device)
+    with torch.cuda.device(ms.device):
+        nbytes = _lib.lib().mydet_mot_scratch_bytes(ctypes.byref(ms.m), T)
+        if T <= _lib.EVAL_MAX_THRS and nbytes != overlap.numel() * 4:
+            raise RuntimeError(f'mydet_mot_scratch_bytes: {nbytes} for [{T}, {ms.pack["n_ov"]}] int32')
+        code = _lib.lib().mydet_mot_id_overlap(ctypes.byref(ms.c), ctypes.byref(ms.m), _ptr(ious), thr.ctypes.data, T, _ptr(overlap),
+                                               nbytes, _stream())
+    _lib.check(code, 'mydet_mot_id_overlap')
+    return overlap
+
+
+def mot_id_assign(ms, overlap):
+    """mydet_mot_id_assign, one launch: IDTP int64 [U, T] from the matrices of mot_id_overlap."""
+    T = overlap.shape[0]
+    require_gpu(overlap, 'mot_id_assign')
+    if overlap.dtype != torch.int32 or tuple(overlap.shape) != (T, ms.pack['n_ov']) or not overlap.is_contiguous():
+        raise ValueError(f"mot_id_assign: overlap must be int32 [T, {ms.pack['n_ov']}], contiguous")
+    idtp = torch.empty((ms.pack['U'], T), dtype=torch.int64, device=ms.device)
+    with torch.cuda.device(ms.device):
+        code = _lib.lib().mydet_mot_id_assign(ctypes.byref(ms.c), ctypes.byref(ms.m), T, _ptr(overlap), overlap.numel() * 4, _ptr(idtp),
+                                              _stream())
+    _lib.check(code, 'mydet_mot_id_assign')
+    return idtp
+
+
+def mot_evaluate(ms, iou_thrs, rows=False, ious=None):
+    """The four launches on a MotSet (or a pack): mydet_eval_ious_f64, mydet_mot_clear_f64, mydet_mot_id_overlap and
+    mydet_mot_id_assign, stream-ordered, no synchronisation.  Returns the raw arrays as tensors: counts, siou, present, matched and
+    gt_match (mot_clear), idtp int64 [U, T], ious float64 [n_pairs] and overlap int32 [T, n_ov].  ious: a float64 [n_pairs] tensor
+    to score instead of the IoUs of the boxes."""
+    if isinstance(ms, dict):
+        ms = MotSet(ms)
+    if ious is None:
+        ious = eval_ious(ms)
+    else:
+        require_gpu(ious, 'mot_evaluate')
+        if ious.dtype != torch.float64 or ious.numel() != ms.pack['n_pairs'] or not ious.is_contiguous() or ious.device != ms.device:
+            raise ValueError(f"mot_evaluate: ious must be float64 [{ms.pack['n_pairs']}], contiguous, on {ms.device}")
+    counts, siou, present, matched, gt_match = mot_clear(ms, ious, iou_thrs, rows)
+    overlap = mot_id_overlap(ms, ious, iou_thrs)
+    idtp = mot_id_assign(ms, overlap)
+    return {'counts': counts, 'siou': siou, 'present': present, 'matched': matched, 'idtp': idtp, 'ious': ious, 'overlap': overlap,
+            'gt_match': gt_match}
+
+
+def _mot_ratio(num, den):
+    """One float64 division of two exact integers; nan without a denominator."""
+    return float(np.float64(num) / np.float64(den)) if den else float('nan')
+
+
+def mot_metrics(tp, fp, fn, idsw, frag, siou, idtp, present, matched):
+    """Host: the metrics of one row (a sequence or the total) at one threshold from its integer counts, SIOU and the present /
+    matched frame counts of its ground-truth identities.  motp is the mean IoU of the matches, not a distance.  Mostly tracked is
+    5 * matched >= 4 * present, mostly lost 5 * matched < present, both in integers."""
+    tp, fp, fn, idsw, frag, idtp = (int(v) for v in (tp, fp, fn, idsw, frag, idtp))
+    n_gt, n_hyp = tp + fn, tp + fp
+    present, matched = np.asarray(present, dtype=np.int64), np.asarray(matched, dtype=np.int64)
+    mt = int(np.count_nonzero(5 * matched >= 4 * present))
+    ml = int(np.count_nonzero(5 * matched < present))
+    mota = _mot_ratio(fn + fp + idsw, n_gt)
+    return {'tp': tp, 'fp': fp, 'fn': fn, 'idsw': idsw, 'frag': frag, 'n_gt': n_gt, 'n_hyp': n_hyp,
+            'idtp': idtp, 'idfp': n_hyp - idtp, 'idfn': n_gt - idtp,
+            'mota': 1.0 - mota, 'motp': _mot_ratio(siou, tp) if tp else float('nan'),
+            'precision': _mot_ratio(tp, n_hyp), 'recall': _mot_ratio(tp, n_gt),
+            'idf1': _mot_ratio(2 * idtp, n_gt + n_hyp), 'idp': _mot_ratio(idtp, n_hyp), 'idr': _mot_ratio(idtp, n_gt),
+            'n_ids': int(len(present)), 'mt': mt, 'pt': int(len(present)) - mt - ml, 'ml': ml}
+
+
+MOT_SUMMARY_COLUMNS = ('mota', 'motp', 'idf1', 'idp', 'idr', 'recall', 'precision')
+MOT_SUMMARY_COUNTS = ('n_ids', 'mt', 'pt', 'ml', 'tp', 'fp', 'fn', 'idsw', 'frag')
+
+
+def mot_summarize(raw, pack, iou_thrs):
+    """Host numpy: per sequence and overall, per threshold, the metrics of mot_metrics from the raw arrays of mot_evaluate (numpy).
+    A sequence sums its categories' units; SIOU is added unit by unit in unit order.  Returns (result, text): result is
+    {'iou_thrs', 'overall': [per threshold], 'sequences': {name: [per threshold]}}."""
+    S, K, T = pack['S'], pack['K'], len(iou_thrs)
+    counts, siou, idtp = np.asarray(raw['counts']), np.asarray(raw['siou']), np.asarray(raw['idtp'])
+    present, matched = np.asarray(raw['present']), np.asarray(raw['matched'])
+    ids = pack['gt_id_start']
+
+    def row(units, t):
+        c = sum((counts[u, t].astype(np.int64) for u in units), np.zeros(5, dtype=np.int64))
+        s = np.float64(0.0)
+        for u in units:
+            s = s + siou[u, t]
+        sel = np.concatenate([np.arange(ids[u], ids[u + 1]) for u in units]) if units else np.zeros(0, dtype=np.int64)
+        return mot_metrics(c[0], c[1], c[2], c[3], c[4], s, sum(int(idtp[u, t]) for u in units), present[sel], matched[t][sel])
+
+    result = {'iou_thrs': [float(v) for v in iou_thrs],
+              'sequences': {name: [row([k * S + s for k in range(K)], t) for t in range(T)] for s, name in enumerate(pack['seq_names'])},
+              'overall': [row(list(range(S * K)), t) for t in range(T)]}
+    head = ' {:<16} {:>5}'.format('sequence', 'IoU') + ''.join(' {:>9}'.format(c) for c in MOT_SUMMARY_COLUMNS) \
+        + ''.join(' {:>6}'.format(c) for c in MOT_SUMMARY_COUNTS)
+    lines = [head]
+    for name, rows in list(result['sequences'].items()) + [('OVERALL', result['overall'])]:
+        for t, r in enumerate(rows):
+            lines.append(' {:<16} {:>5.2f}'.format(str(name)[:16], result['iou_thrs'][t]) + ''.join(' {:>9.4f}'.format(r[c]) for c in MOT_SUMMARY_COLUMNS)
+                         + ''.join(' {:>6d}'.format(r[c]) for c in MOT_SUMMARY_COUNTS))
+    return result, ''.join(line + '\n' for line in lines)

@@ -2,3 +2,4 @@
 sets, `cepdof` for rotated CEPDOF-style sets.  Both are one evaluator, BboxEval (include/mydet.h: mydet_eval_*)."""
 from .coco import BboxEval, coco_evaluate_bbox, myCOCOeval  # noqa: F401
 from .cepdof import CEPDOFeval, evaluate_json  # noqa: F401
+from .mot import MOTeval  # noqa: F401
