@@ -682,6 +682,43 @@ int mydet_track_frames_f32(const int32_t *records, int64_t stream_stride_words, 
                            float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
                            int32_t *out_count, int32_t *out_dropped, void *stream);
 
+/* Association modes of the tracker.  mydet_track_frames_assoc_f32 is mydet_track_frames_f32 with one more argument, `assoc` (HOST
+ * pointer; the struct travels as a kernel argument); mydet_track_frames_f32 is it with {MYDET_TRACK_ASSIGN_GREEDY, bands 0}.
+ * Predict, update, retire, births and every output are as documented above; only the "associate" step has modes, through two
+ * independent settings.
+ * Score bands (bands = 1; with bands = 0 there is one band and the three thresholds are not read):
+ *   a detection with score >= high_thres is HIGH, one with low_thres <= score < high_thres is LOW, one below low_thres is
+ *   ignored: neither matched nor born.  Births come only from unmatched HIGH detections with score >= new_thres, in the same
+ *   order as before.  Stage 1 associates the HIGH detections with every live track at params->match_thres.  Stage 2 associates
+ *   the LOW detections, at low_match_thres, with the live tracks that no stage-1 detection took AND whose missed == 1 after
+ *   this frame's predict: the tracks matched or born in the previous frame (ByteTrack's rule).  A track matched in stage 2
+ *   takes the normal update, score momentum included.
+ * Assignment inside a stage:
+ *   MYDET_TRACK_ASSIGN_GREEDY   the walk documented above.  With bands one walk in rank order is stage 1 and then stage 2 (every
+ *             HIGH detection precedes every LOW one); the threshold and the eligibility change at the boundary.
+ *   MYDET_TRACK_ASSIGN_OPTIMAL  rows: the stage's detections in rank order (score descending, record slot ascending); columns: the
+ *             track slots 0 .. max_tracks-1 in order, then one dummy column per row.  With iou the float32 IoU of the greedy
+ *             mode and q = (int)floorf(iou * 65536.0f): cost = 65536 - q for an eligible pair -- the track is live, not taken
+ *             by an earlier stage, of the detection's class, passes the stage-2 missed rule, and iou > the stage's threshold (a
+ *             NaN IoU is never eligible); cost = 131072 for an ineligible pair on a real column; cost = 65536 on a dummy
+ *             column.  The result is the minimum-cost assignment as the shortest-augmenting-path method finds it (the solver
+ *             of mydet_mot_clear_f64): rows inserted in ascending order, the next column the unused one of least reduced
+ *             cost, the lowest column index on a tie.  A row that ends on a dummy column is unmatched.
+ * MYDET_E_BADARG: as mydet_track_frames_f32, and a null assoc; an unknown assign; bands not 0 or 1; with bands a non-finite
+ *      threshold or low_thres >= high_thres.  reserved is not read. */
+#define MYDET_TRACK_ASSIGN_GREEDY  0
+#define MYDET_TRACK_ASSIGN_OPTIMAL 1
+typedef struct mydet_track_assoc {
+    int assign;                          /* MYDET_TRACK_ASSIGN_GREEDY 0 | _OPTIMAL 1 */
+    int bands;                           /* 0 | 1 */
+    float high_thres, low_thres, low_match_thres;
+    int reserved[3];
+} mydet_track_assoc;
+int mydet_track_frames_assoc_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                 int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                 float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                 int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, void *stream);
+
 /* Winograd F(4x4,3x3) form of the same 3x3 stride-1 pad-1 conv + BN + act (+ residual) as mydet_conv2d_wino_f32
  * (4x fewer multiplies than the direct form; used for the deep layers with chip-filling grids).  `u` = the
  * transform-domain weights made by mydet_wino4_weights_f32 from the OHWI weight (mydet_wino4_weights_floats(Cout, Cin)

@@ -86,6 +86,8 @@ SIGNATURES = {
     'mydet_track_state_words': [c_int],
     'mydet_track_reset': [c_ptr, c_int, c_int, c_ptr],
     'mydet_track_frames_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_track_frames_assoc_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                     c_ptr, c_ptr],
     'mydet_mbconv_tiles': [c_int, c_int, c_int],
     'mydet_mbconv_expand_dw_f32': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64] + [c_int] * 11 + [c_ptr, c_int, c_ptr, c_ptr],
     'mydet_sepconv_nodes_f32': [c_int, c_ptr, c_int, c_int, c_ptr],
@@ -157,6 +159,7 @@ NMS_HARD, NMS_SOFT_LINEAR, NMS_SOFT_GAUSSIAN, NMS_MERGE = range(4)
 TRACK_MAX_TRACKS = 512
 TRACK_STATE_HEADER, TRACK_SLOT_WORDS = 8, 31
 TRACK_MATCH_IOU, TRACK_MATCH_ROTATED = 0, 1
+TRACK_ASSIGN_GREEDY, TRACK_ASSIGN_OPTIMAL = 0, 1
 # overlay renderer (mydet_draw_boxes_*): MYDET_DRAW_* of include/mydet.h
 DRAW_MAX_BOXES, DRAW_MAX_THICKNESS, DRAW_MAX_GLYPHS, DRAW_NAME_BYTES = 512, 64, 33, 16
 DRAW_COLOR_CLASS, DRAW_COLOR_ID, DRAW_COLOR_FIXED = 0, 1, 2
@@ -234,6 +237,12 @@ class TrackParams(ctypes.Structure):
     _fields_ = [('p0', c_f32 * 10), ('q', c_f32 * 10), ('r', c_f32 * 5), ('momentum', c_f32), ('min_score', c_f32),
                 ('new_thres', c_f32), ('match_thres', c_f32), ('img_h', c_f32), ('img_w', c_f32), ('max_missed', c_int),
                 ('match', c_int)]
+
+
+class TrackAssoc(ctypes.Structure):
+    """mydet_track_assoc (include/mydet.h): the association mode of mydet_track_frames_assoc_f32."""
+    _fields_ = [('assign', c_int), ('bands', c_int), ('high_thres', c_f32), ('low_thres', c_f32), ('low_match_thres', c_f32),
+                ('reserved', c_int * 3)]
 
 
 class DrawList(ctypes.Structure):

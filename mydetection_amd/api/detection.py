@@ -745,9 +745,15 @@ class Detector():
         elif used:
             src, = sources                                           # a plain call alone takes any number of sizes, none included
         call = self._call_settings(kwargs, whole=tracker is not None or used)
+        conf_thres = call.conf_thres
+        if tracker is not None and tracker.low_thres is not None:
+            # the second stage needs the low band in the records: every post-process of this call (the windows of tiles=
+            # and the views of augment= included) runs at the lower threshold; the tracker keeps the call's own as high_thres
+            tracker.assoc(conf_thres)
+            call = self._call_settings(dict(kwargs, conf_thres=min(conf_thres, tracker.low_thres)), whole=True)
         records = self._source_records(sources, call)
         if tracker is not None:
-            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, call.conf_thres)
+            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres)
         elif used:
             records = list(records)
             (idxs, found), = records                                 # one frame size: one group, in frame order
@@ -806,7 +812,7 @@ class Detector():
         width = 5 if 'angle' in rec else 4
         state = tracker.bind(frame_hw, width, rec['records'].device)
         params = tracker.params(frame_hw, tracker.resolve_match(self.model.bb_format), conf_thres)
-        out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks)
+        out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks, assoc=tracker.assoc(conf_thres))
         B, mt = len(idxs), tracker.max_tracks
         missed = out['missed'].view(B, mt)
         keep = (missed >= 0) if coasting else (missed == 0)

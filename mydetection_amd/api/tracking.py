@@ -13,12 +13,19 @@ class Tracker:
     class when their IoU is > match_thres; an unmatched detection with score >= new_thres (None: the call's conf_thres) starts
     one; a track is dropped after max_missed frames without a match, when its score (momentum) falls below min_score, or when
     its box leaves the frame.  p0, q, r: the filter's standard deviations (KFTracklet's constants by default).
+    assign: 'greedy' (detections in score order, each takes the free track of largest IoU) or 'optimal' (the one-to-one
+    assignment of largest total IoU).  low_thres: None, or the score from which a detection below the call's conf_thres may
+    still CONTINUE a track that was matched or born in the previous frame (ByteTrack's second stage; it never starts one): the
+    call's post-process then runs at min(conf_thres, low_thres).  high_thres: where the high band begins (None: the call's
+    conf_thres); low_match_thres: the IoU threshold of the second stage (None: match_thres).  low_thres must be below
+    high_thres: a call whose conf_thres is not above it is a ValueError.  include/mydet.h (mydet_track_assoc) has the rules.
     The first call binds the tracker to that call's frame size (H, W), box format and device; `state` is then the int32
     [streams, words] device buffer (ops.track_state_views names its fields) and reset() empties it (ids start at 1 again).
     A batch of B frames is `streams` runs of B / streams consecutive frames: frame f of stream s is frame s * (B / streams) + f."""
 
     def __init__(self, streams=1, max_tracks=256, match=None, match_thres=0.3, new_thres=None, max_missed=30, momentum=0.8,
-                 min_score=0.1, p0=ops.TRACK_P0, q=ops.TRACK_Q, r=ops.TRACK_R):
+                 min_score=0.1, p0=ops.TRACK_P0, q=ops.TRACK_Q, r=ops.TRACK_R, assign='greedy', low_thres=None, high_thres=None,
+                 low_match_thres=None):
         self.streams, self.max_tracks = int(streams), int(max_tracks)
         if self.streams < 1:
             raise ValueError(f'Tracker: streams >= 1 expected, got {streams!r}')
@@ -29,19 +36,33 @@ class Tracker:
         self.match_thres, self.new_thres = float(match_thres), None if new_thres is None else float(new_thres)
         self.max_missed, self.momentum, self.min_score = int(max_missed), float(momentum), float(min_score)
         self.p0, self.q, self.r = tuple(p0), tuple(q), tuple(r)
+        self.assign = assign
+        self.low_thres, self.high_thres, self.low_match_thres = (None if v is None else float(v) for v in (low_thres, high_thres, low_match_thres))
         self.params((1, 1), 'iou', 0.0)                              # the range checks, before any device is touched
+        self.assoc(float('nan') if self.low_thres is None else self.low_thres + 1.0)       # a conf_thres above low_thres
         self.state = None
         self.img_hw = None
         self.box_width = None
 
     def __repr__(self):
         return (f'Tracker(streams={self.streams}, max_tracks={self.max_tracks}, match={self.match!r}, match_thres={self.match_thres}, '
-                f'new_thres={self.new_thres}, max_missed={self.max_missed}, momentum={self.momentum}, min_score={self.min_score})')
+                f'new_thres={self.new_thres}, max_missed={self.max_missed}, momentum={self.momentum}, min_score={self.min_score}, '
+                f'assign={self.assign!r}, low_thres={self.low_thres}, high_thres={self.high_thres}, low_match_thres={self.low_match_thres})')
 
     def params(self, img_hw, match, conf_thres):
         """The kernel's parameter struct for a frame size, a resolved pair test and the call's conf_thres."""
         return ops.track_params(img_hw, match, self.match_thres, conf_thres if self.new_thres is None else self.new_thres,
                                 self.max_missed, self.momentum, self.min_score, self.p0, self.q, self.r)
+
+    def assoc(self, conf_thres):
+        """The association mode for a call's conf_thres: None for the default (greedy, one band: the entry point of old), else
+        the struct of ops.track_assoc.  A ValueError when the call's conf_thres is not above low_thres."""
+        if self.low_thres is None:
+            if self.assign == 'greedy' and self.high_thres is None and self.low_match_thres is None:
+                return None
+            return ops.track_assoc(self.assign, None, self.high_thres, self.low_match_thres)
+        return ops.track_assoc(self.assign, self.low_thres, conf_thres if self.high_thres is None else self.high_thres,
+                               self.match_thres if self.low_match_thres is None else self.low_match_thres)
 
     def resolve_match(self, bb_format):
         """The pair test for a model's box format; a ValueError for 'rotated' on a model without angles."""

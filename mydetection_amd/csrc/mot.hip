@@ -4,112 +4,20 @@
 //   mydet_mot_clear_f64    one wavefront per (unit, threshold): walks the unit's frames in order (keep, assign, count)
 //   mydet_mot_id_overlap   one thread per IoU pair: integer atomic adds into the identity-overlap matrices
 //   mydet_mot_id_assign    one wavefront per (unit, threshold): the largest one-to-one sum of overlaps
-// Both wavefront kernels share hung_solve, the shortest-augmenting-path Hungarian method on integer costs: lanes own columns
+// Both wavefront kernels share hung_solve (hung.h), the shortest-augmenting-path Hungarian method on integer costs: lanes own columns
 // (column j is lane j % 64), a row step is one wave minimum over (minv, column), and the costs are formed from the IoU buffer or
 // the overlap matrix on the fly.  Every decision is an integer or a float64 comparison, so no order of evaluation can change it;
 // the only float64 sum (SIOU) is added in ascending row order by readlane.  Built with -ffp-contract=off like evalmatch.hip.
 #include "common.h"
 #include "eval_set.h"
+#include "hung.h"
 
 namespace {
-
-constexpr int MOT_WAVE = 64;
-constexpr int64_t MOT_ONE = 65536, MOT_BIG = 1ll << 27, MOT_INF = 1ll << 60;
 
 struct MotThresholds {                           // host array, copied into the launch
     double iou[MYDET_EVAL_MAX_THRS];
     int T;
 };
-
-template <int N>
-struct HungLds {
-    static_assert(N <= 2048, "a lane's used columns are one 32-bit mask");
-    int64_t u[N], v[N], minv[N];                 // row and column potentials, the reduced cost of the best way into a column
-    int32_t way[N], p[N];                        // the column before it on that way (-1: the inserted row); the row of a column
-};
-
-__device__ __forceinline__ int64_t wave_min(int64_t x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int64_t o = __shfl_xor(x, off);
-        x = o < x ? o : x;
-    }
-    return x;
-}
-
-__device__ __forceinline__ int wave_min(int x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = min(x, __shfl_xor(x, off));
-    return x;
-}
-
-__device__ __forceinline__ int64_t wave_sum(int64_t x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
-// The minimum-cost assignment of n rows to m columns, n <= m <= N, cost(i, j) >= 0 an int64: afterwards s.p[j] is the row of
-// column j or -1.  Rows are inserted in ascending order; inside an augmentation the next column is the unused column of least
-// minv, the lowest index on a tie.  One wavefront; every branch is wave-uniform (the barriers are those of a one-wave block).
-template <int N, typename Cost>
-__device__ void hung_solve(HungLds<N> &s, int n, int m, const Cost &cost, int lane) {
-    for (int j = lane; j < m; j += MOT_WAVE) {
-        s.v[j] = 0;
-        s.p[j] = -1;
-    }
-    for (int i = lane; i < n; i += MOT_WAVE) s.u[i] = 0;
-    __syncthreads();
-    for (int i = 0; i < n; ++i) {
-        for (int j = lane; j < m; j += MOT_WAVE) s.minv[j] = MOT_INF;
-        uint32_t used = 0;                                             // bit k: column lane + 64k
-        int j0 = -1;
-        for (;;) {
-            if (j0 >= 0 && (j0 & 63) == lane) used |= 1u << (j0 >> 6);
-            const int i0 = j0 < 0 ? i : s.p[j0];
-            const int64_t ui = s.u[i0];
-            int64_t best = MOT_INF;
-            int best_j = 0x7fffffff;
-            for (int j = lane, k = 0; j < m; j += MOT_WAVE, ++k) {
-                if ((used >> k) & 1u) continue;
-                const int64_t cur = cost(i0, j) - ui - s.v[j];
-                int64_t mv = s.minv[j];
-                if (cur < mv) {
-                    mv = cur;
-                    s.minv[j] = cur;
-                    s.way[j] = j0;
-                }
-                if (mv < best) {
-                    best = mv;
-                    best_j = j;
-                }
-            }
-            const int64_t delta = wave_min(best);
-            const int j1 = wave_min(best == delta ? best_j : 0x7fffffff);
-            for (int j = lane, k = 0; j < m; j += MOT_WAVE, ++k) {
-                if ((used >> k) & 1u) {
-                    s.u[s.p[j]] += delta;                              // p is one-to-one: every lane its own row
-                    s.v[j] -= delta;
-                } else {
-                    s.minv[j] -= delta;
-                }
-            }
-            if (lane == 0) s.u[i] += delta;                            // the inserted row: not in p yet
-            __syncthreads();
-            if (j1 >= m) return;                                       // n <= m leaves an unused column: never taken
-            j0 = j1;
-            if (s.p[j0] < 0) break;
-        }
-        if (lane == 0) {
-            do {
-                const int j1 = s.way[j0];
-                s.p[j0] = j1 < 0 ? i : s.p[j1];
-                j0 = j1;
-            } while (j0 >= 0);
-        }
-        __syncthreads();
-    }
-}
 
 // The listed position of group g, or -1.
 __device__ __forceinline__ int mot_listed(const mydet_eval_set &s, int g) {

@@ -14,12 +14,16 @@
 //   2. predict every live track;
 //   3. greedy association: the walk over the ranked detections is sequential, its body is lane-per-track -- every thread
 //      computes the IoU of its own predicted box with the detection, a 64-bit key (IoU bits, ~slot) is maximised over the wave
-//      by shuffles and over the waves through LDS: one barrier per detection;
+//      by shuffles and over the waves through LDS: one barrier per detection.  With score bands (mydet_track_assoc) the same
+//      walk is stage 1 and then stage 2, because every high detection is ranked before every low one: only the threshold and
+//      the track's eligibility change at the boundary.  The optimal assignment instead publishes every predicted track's side
+//      of the pair test in LDS and lets wavefront 0 run hung_solve (hung.h) once per stage, the costs formed on the fly;
 //   4. matched tracks take the Kalman update; 5. infeasible and long-missed tracks are retired; 6. the unmatched detections
 //      above new_thres are born into the lowest free slots -- ranks by ballot and popcount, no serial loop.
 // Built with -ffp-contract=off: the float32 operation order below IS the definition (tests/_track_ref.py restates it in numpy
 // and is held to the reference's float64 on tests/golden/kf_tracklet.npz).
 #include "common.h"
+#include "hung.h"
 #include "rot_iou.h"
 
 namespace {
@@ -27,6 +31,9 @@ namespace {
 constexpr int KMAX = MYDET_REC_TOPK;
 constexpr int TMAX = MYDET_TRACK_MAX_TRACKS;
 constexpr int NWMAX = TMAX / 64;
+// the instances of track_kernel: today's walk, the walk with score bands, the optimal assignment (bands a launch argument)
+constexpr int ASSOC_GREEDY = 0, ASSOC_GREEDY_BANDS = 1, ASSOC_OPTIMAL = 2;
+constexpr int64_t ASSOC_INELIGIBLE = 2 * MOT_ONE;
 
 struct TrackArgs {
     const int32_t *rec;               // record of frame f of stream s at rec + s*stream_st + f*frame_st (words)
@@ -38,6 +45,51 @@ struct TrackArgs {
     float *obox, *oscore;
     int64_t *ocls, *oid;
     int32_t *omissed, *ocount, *odropped;
+    mydet_track_assoc as;             // read by the instances with bands or the optimal assignment only
+};
+
+// LDS of the optimal assignment, dynamic: with the kernel's static arrays it is above the 64 KiB a kernel gets without the opt-in
+struct AssocLds {
+    HungLds<TMAX + KMAX> h;           // columns: the track slots, then one dummy per row
+    float t[7][TMAX];                 // every track's side of the pair test after predict
+    int64_t tcls[TMAX];
+    int32_t tmissed[TMAX];            // missed after predict (>= 1), or -1 for a slot that is not live
+    int32_t tmd[TMAX];                // the record slot a track took, or -1
+    int32_t rowd[KMAX], rowp[KMAX];   // a stage's rows: record slot and rank
+};
+// An upper bound of track_kernel's static arrays (33 - 37 KiB).  The opt-in asks for the dynamic part plus this, so the request
+// covers the kernel's whole LDS whether the runtime holds the limit against the dynamic part alone or against the sum.
+constexpr int ASSOC_STATIC_LDS = 40 * 1024;
+
+// The cost of (row i, column j) of one stage (include/mydet.h: mydet_track_assoc).  The IoU is the float32 expression of the
+// greedy walk, operation for operation.
+template <bool ROT>
+struct AssocCost {
+    const float (*g)[KMAX];           // the detections' pair-test planes
+    const int64_t *dcl;
+    const AssocLds *A;
+    int MT;
+    bool second;                      // stage 2: only the tracks matched or born in the previous frame
+    float thr;
+    __device__ __forceinline__ int64_t operator()(int i, int j) const {
+        if (j >= MT) return MOT_ONE;
+        const int d = A->rowd[i], tm = A->tmissed[j];
+        if (tm < 0 || A->tmd[j] >= 0 || A->tcls[j] != dcl[d] || (second && tm != 1)) return ASSOC_INELIGIBLE;
+        float iou;
+        if constexpr (ROT) {
+            const rotiou::Box bi{g[0][d], g[1][d], g[2][d], g[3][d], g[4][d], g[5][d], g[6][d]};
+            const rotiou::Box bj{A->t[0][j], A->t[1][j], A->t[2][j], A->t[3][j], A->t[4][j], A->t[5][j], A->t[6][j]};
+            iou = rotiou::rot_iou(bi, bj);
+        } else {
+            const float xx1 = fmaxf(g[0][d], A->t[0][j]), yy1 = fmaxf(g[1][d], A->t[1][j]);
+            const float xx2 = fminf(g[2][d], A->t[2][j]), yy2 = fminf(g[3][d], A->t[3][j]);
+            const float ww = fmaxf(0.0f, xx2 - xx1), hh = fmaxf(0.0f, yy2 - yy1);
+            const float inter = ww * hh;
+            iou = inter / (g[4][d] + A->t[4][j] - inter);
+        }
+        if (!(iou > thr)) return ASSOC_INELIGIBLE;                 // a NaN (0/0) is never eligible
+        return MOT_ONE - (int64_t)(int)floorf(iou * 65536.0f);
+    }
 };
 
 __device__ __forceinline__ unsigned sortable(float f) {
@@ -67,9 +119,10 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
     return v;
 }
 
-template <int BW, bool ROT>
+template <int BW, bool ROT, int MODE>
 __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
     static_assert(!ROT || BW == 5, "the rotated IoU needs the angle column");
+    extern __shared__ __align__(16) unsigned char track_dyn[];     // AssocLds (ASSOC_OPTIMAL only)
     __shared__ float s_z[5][KMAX];                    // the frame's detections: cx, cy, w, h, angle (0 for BW = 4)
     __shared__ float s_g[ROT ? 7 : 5][KMAX];          // pair-test planes: x1, y1, x2, y2, area | the seven fields of rotiou::Box
     __shared__ float s_sc[KMAX];
@@ -191,13 +244,75 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
         }
         const int any_live = __syncthreads_or(live ? 1 : 0);      // also: s_order is complete
 
-        // 3. greedy association
+        // 3. association
         int md = -1;                                               // the record slot this track took
-        if (any_live) {
+        if constexpr (MODE == ASSOC_OPTIMAL) {
+            // Wavefront 0 solves, the others wait at the barrier below; every branch around a barrier is workgroup-uniform
+            // (any_live, a.as.bands), and inside the wavefront the solver orders its LDS traffic with HungWaveSync.  No row
+            // is skipped and no column compacted: the solver sees the matrix the rule text defines.
+            AssocLds &A = *reinterpret_cast<AssocLds *>(track_dyn);
+            for (int p = tid; p < n; p += nthr) s_dmatch[p] = -1;
+            if (any_live) {
+                A.t[0][tid] = t0; A.t[1][tid] = t1; A.t[2][tid] = t2; A.t[3][tid] = t3; A.t[4][tid] = t4; A.t[5][tid] = t5; A.t[6][tid] = t6;
+                A.tcls[tid] = cls; A.tmissed[tid] = live ? missed : -1; A.tmd[tid] = -1;
+                __syncthreads();
+                if (wave == 0) {
+                    const HungWaveSync wsync;
+                    const bool bands = a.as.bands != 0;
+                    const unsigned long long before = (1ull << lane) - 1ull;
+                    for (int stage = 0; stage < (bands ? 2 : 1); ++stage) {
+                        int nr = 0;                                // the stage's rows, in rank order
+                        for (int p0 = 0; p0 < n; p0 += 64) {
+                            const int p = p0 + lane;
+                            int d = 0;
+                            bool in = false;
+                            if (p < n) {
+                                d = s_order[p];
+                                const float sc = s_sc[d];
+                                const bool high = sc >= a.as.high_thres;
+                                in = !bands ? true : stage == 0 ? high : (!high && sc >= a.as.low_thres && sc < a.as.high_thres);
+                            }
+                            const unsigned long long bal = __ballot(in);
+                            if (in) {
+                                const int k = nr + __popcll(bal & before);
+                                A.rowd[k] = d; A.rowp[k] = p;
+                            }
+                            nr += __popcll(bal);
+                        }
+                        wsync();
+                        if (nr > 0) {
+                            const AssocCost<ROT> cost = {s_g, s_cl, &A, MT, stage == 1, stage == 1 ? a.as.low_match_thres : P.match_thres};
+                            hung_solve(A.h, nr, MT + nr, cost, lane, wsync);
+                            for (int j = lane; j < MT; j += 64) {  // a row on a real column; the costs first: they read tmd
+                                const int i = A.h.p[j];
+                                A.h.way[j] = i >= 0 && cost(i, j) != ASSOC_INELIGIBLE ? i : -1;
+                            }
+                            wsync();
+                            for (int j = lane; j < MT; j += 64) {
+                                const int i = A.h.way[j];
+                                if (i >= 0) { A.tmd[j] = A.rowd[i]; s_dmatch[A.rowp[i]] = j; }
+                            }
+                            wsync();
+                        }
+                    }
+                }
+                __syncthreads();
+                md = A.tmd[tid];
+            }
+        } else if (any_live) {
             for (int p = 0; p < n; ++p) {
                 const int d = s_order[p];
                 unsigned long long key = 0ull;
-                if (live && md < 0 && cls == s_cl[d]) {
+                bool offered = live && md < 0 && cls == s_cl[d];
+                float thres = P.match_thres;
+                if constexpr (MODE == ASSOC_GREEDY_BANDS) {
+                    const float sc = s_sc[d];
+                    if (!(sc >= a.as.high_thres)) {                // stage 2, or a detection that is ignored
+                        offered = offered && missed == 1 && sc >= a.as.low_thres && sc < a.as.high_thres;
+                        thres = a.as.low_match_thres;
+                    }
+                }
+                if (offered) {
                     float iou;
                     if constexpr (ROT) {
                         const rotiou::Box bi{s_g[0][d], s_g[1][d], s_g[2][d], s_g[3][d], s_g[4][d], s_g[5][d], s_g[6][d]};
@@ -210,7 +325,7 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
                         const float inter = ww * hh;
                         iou = inter / (s_g[4][d] + t4 - inter);
                     }
-                    if (iou > P.match_thres)                       // a NaN (0/0) never matches
+                    if (iou > thres)                               // a NaN (0/0) never matches
                         key = ((unsigned long long)__float_as_uint(fmaxf(iou, 0.0f)) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)tid);
                 }
                 key = wave_max(key);
@@ -273,7 +388,9 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
         // 6. births: the k-th unmatched detection above new_thres (in rank order) goes to the k-th lowest free slot
         for (int p0 = 0; p0 < n64; p0 += nthr) {
             const int p = p0 + tid;
-            const bool flag = p < n && s_dmatch[p] < 0 && s_sc[s_order[p]] >= P.new_thres;
+            bool flag = p < n && s_dmatch[p] < 0 && s_sc[s_order[p]] >= P.new_thres;
+            if constexpr (MODE != ASSOC_GREEDY)                    // with bands only a high detection starts a track
+                if (a.as.bands) flag = flag && s_sc[s_order[p]] >= a.as.high_thres;
             const unsigned long long bits = __ballot(flag);
             if (lane == 0 && p < KMAX) s_bmask[p >> 6] = bits;
         }
@@ -354,16 +471,50 @@ extern "C" int mydet_track_reset(int32_t *state, int S, int max_tracks, void *st
     return mydet_launch_status();
 }
 
-extern "C" int mydet_track_frames_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
-                                      int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
-                                      float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
-                                      int32_t *out_count, int32_t *out_dropped, void *stream) {
+namespace {
+
+inline bool track_finite(float v) { return v - v == 0.0f; }            // false for a NaN and for an infinity
+
+// One instance: the > 64 KiB LDS opt-in of the optimal assignment is per kernel and per device (common.h)
+template <int BW, bool ROT, int MODE>
+int track_launch(const TrackArgs &a, dim3 grid, dim3 block, hipStream_t stream) {
+    size_t dyn = 0;
+    if constexpr (MODE == ASSOC_OPTIMAL) {
+        static unsigned long long opted = 0ull;                    // one bit per device ordinal
+        dyn = sizeof(AssocLds);
+        const int st = mydet_lds_opt_in(opted, track_kernel<BW, ROT, MODE>, (int)sizeof(AssocLds) + ASSOC_STATIC_LDS);
+        if (st) return st;
+    }
+    hipLaunchKernelGGL((track_kernel<BW, ROT, MODE>), grid, block, dyn, stream, a);
+    return mydet_launch_status();
+}
+
+template <int MODE>
+int track_launch_mode(const TrackArgs &a, int box_width, dim3 grid, dim3 block, hipStream_t stream) {
+    if (box_width == 4) return track_launch<4, false, MODE>(a, grid, block, stream);
+    if (a.p.match == MYDET_TRACK_MATCH_ROTATED) return track_launch<5, true, MODE>(a, grid, block, stream);
+    return track_launch<5, false, MODE>(a, grid, block, stream);
+}
+
+}  // namespace
+
+extern "C" int mydet_track_frames_assoc_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                            int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                            float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                            int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, void *stream) {
     if (S <= 0 || F <= 0 || max_tracks < 1) return MYDET_E_BADARG;
     if (box_width != 4 && box_width != 5) return MYDET_E_BADARG;
     if (!records || !params || !state || !out_box || !out_score || !out_class || !out_id || !out_missed || !out_count || !out_dropped)
         return MYDET_E_BADARG;
     if (params->match != MYDET_TRACK_MATCH_IOU && params->match != MYDET_TRACK_MATCH_ROTATED) return MYDET_E_BADARG;
     if (params->match == MYDET_TRACK_MATCH_ROTATED && box_width != 5) return MYDET_E_BADARG;
+    if (!assoc) return MYDET_E_BADARG;
+    if (assoc->assign != MYDET_TRACK_ASSIGN_GREEDY && assoc->assign != MYDET_TRACK_ASSIGN_OPTIMAL) return MYDET_E_BADARG;
+    if (assoc->bands != 0 && assoc->bands != 1) return MYDET_E_BADARG;
+    if (assoc->bands) {
+        if (!track_finite(assoc->high_thres) || !track_finite(assoc->low_thres) || !track_finite(assoc->low_match_thres)) return MYDET_E_BADARG;
+        if (assoc->low_thres >= assoc->high_thres) return MYDET_E_BADARG;
+    }
     // a record's box plane is read with 16-byte loads: the base and both strides keep that alignment
     if (((uintptr_t)records & 15) || ((uintptr_t)state & 15)) return MYDET_E_BADARG;
     if (stream_stride_words < 0 || frame_stride_words < 0 || (stream_stride_words & 3) || (frame_stride_words & 3)) return MYDET_E_BADARG;
@@ -377,9 +528,18 @@ extern "C" int mydet_track_frames_f32(const int32_t *records, int64_t stream_str
     a.state = state; a.state_words = mydet_track_state_words(max_tracks);
     a.obox = out_box; a.oscore = out_score; a.ocls = out_class; a.oid = out_id; a.omissed = out_missed; a.ocount = out_count;
     a.odropped = out_dropped;
+    a.as = *assoc;
     const dim3 grid((unsigned)S), block((unsigned)((max_tracks + 63) / 64 * 64));
-    if (box_width == 4) hipLaunchKernelGGL((track_kernel<4, false>), grid, block, 0, (hipStream_t)stream, a);
-    else if (params->match == MYDET_TRACK_MATCH_ROTATED) hipLaunchKernelGGL((track_kernel<5, true>), grid, block, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((track_kernel<5, false>), grid, block, 0, (hipStream_t)stream, a);
-    return mydet_launch_status();
+    if (assoc->assign == MYDET_TRACK_ASSIGN_OPTIMAL) return track_launch_mode<ASSOC_OPTIMAL>(a, box_width, grid, block, (hipStream_t)stream);
+    if (assoc->bands) return track_launch_mode<ASSOC_GREEDY_BANDS>(a, box_width, grid, block, (hipStream_t)stream);
+    return track_launch_mode<ASSOC_GREEDY>(a, box_width, grid, block, (hipStream_t)stream);
+}
+
+extern "C" int mydet_track_frames_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                      int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                      float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                      int32_t *out_count, int32_t *out_dropped, void *stream) {
+    const mydet_track_assoc assoc = {MYDET_TRACK_ASSIGN_GREEDY, 0, 0.0f, 0.0f, 0.0f, {0, 0, 0}};
+    return mydet_track_frames_assoc_f32(records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
+                                        out_score, out_class, out_id, out_missed, out_count, out_dropped, &assoc, stream);
 }

@@ -1545,6 +1545,7 @@ def fuse_view_records(rec, B, V, flips, frame_hw, thres, kind='nms', metric='iou
 
 
 TRACK_MATCHES = {'iou': _lib.TRACK_MATCH_IOU, 'rotated': _lib.TRACK_MATCH_ROTATED}        # MYDET_TRACK_MATCH_* of include/mydet.h
+TRACK_ASSIGNS = {'greedy': _lib.TRACK_ASSIGN_GREEDY, 'optimal': _lib.TRACK_ASSIGN_OPTIMAL}   # MYDET_TRACK_ASSIGN_*
 # KFTracklet's constants (reference utils/structures.py:457-460): standard deviations; the kernel takes their squares
 TRACK_P0 = (0.1, 0.1, 0.1, 0.1, 10, 0.1, 0.1, 0.1, 0.1, 10)
 TRACK_Q = (0.049, 0.032, 0.052, 0.097, 13.62, 0.01, 0.01, 0.01, 0.01, 1)
@@ -1592,6 +1593,30 @@ def track_params(img_hw, match='iou', match_thres=0.3, new_thres=0.3, max_missed
     p.momentum, p.min_score, p.new_thres, p.match_thres = float(momentum), float(min_score), float(new_thres), float(match_thres)
     p.img_h, p.img_w, p.max_missed, p.match = h, w, max_missed, m
     return p
+
+
+def track_assoc(assign='greedy', low_thres=None, high_thres=None, low_match_thres=None):
+    """The association mode of mydet_track_frames_assoc_f32 (a _lib.TrackAssoc; include/mydet.h has the rules).  assign: 'greedy'
+    or 'optimal'.  low_thres: None for one score band; else the second stage is on and high_thres and low_match_thres are
+    required (Tracker fills them from the call's conf_thres and its match_thres).  ValueError for anything out of range;
+    touches no device."""
+    if not isinstance(assign, str) or assign not in TRACK_ASSIGNS:
+        raise ValueError(f'tracker: assign {assign!r} is not one of {sorted(TRACK_ASSIGNS)}')
+    a = _lib.TrackAssoc()
+    a.assign = TRACK_ASSIGNS[assign]
+    if low_thres is None:
+        if high_thres is not None or low_match_thres is not None:
+            raise ValueError('tracker: high_thres and low_match_thres belong to the second stage; set low_thres to turn it on')
+        return a
+    if high_thres is None or low_match_thres is None:
+        raise ValueError('tracker: with low_thres, high_thres and low_match_thres are required')
+    low, high, lm = float(low_thres), float(high_thres), float(low_match_thres)
+    if not (np.isfinite(low) and np.isfinite(high) and np.isfinite(lm)):
+        raise ValueError(f'tracker: finite low_thres, high_thres and low_match_thres expected, got {low_thres!r}, {high_thres!r}, {low_match_thres!r}')
+    a.bands, a.high_thres, a.low_thres, a.low_match_thres = 1, high, low, lm
+    if not a.low_thres < a.high_thres:                               # as the kernel compares them: in float32
+        raise ValueError(f'tracker: low_thres < high_thres expected, got {low_thres!r} and {high_thres!r}')
+    return a
 
 
 def track_state(streams, max_tracks, device):
@@ -1647,7 +1672,7 @@ def track_state_views(state, max_tracks=None):
     return out
 
 
-def track_frames(records, tracker_state, params, frames_per_stream=None, max_tracks=None, out=None):
+def track_frames(records, tracker_state, params, frames_per_stream=None, max_tracks=None, out=None, assoc=None):
     """Advance S streams by F frames each in ONE launch (include/mydet.h: mydet_track_frames_f32, where the rules are).
     records: the detection records in frame coordinates -- an int32 tensor [S*F, words] (frame f of stream s in row s*F + f) or
     [S, F, words] with any strides along S and F that are multiples of 4 words, or the record_views dict of a [S*F, words]
@@ -1655,9 +1680,12 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     from track_state, updated in place.  params: track_params(...).  frames_per_stream: F for 2-d records (default: rows / S).
     Returns a dict of device tensors: box [S,F,MT,5], score [S,F,MT], cls, id int64 [S,F,MT] (id 0 = a free slot), missed int32
     [S,F,MT] (0 = matched or born in this frame, -1 = a free slot), count int32 [S,F] (live tracks; MYDET_COUNT_BAD_CLASS for
-    a bad-class frame, which leaves the state alone), dropped int32 [S,F].  out: such a dict to write into."""
+    a bad-class frame, which leaves the state alone), dropped int32 [S,F].  out: such a dict to write into.  assoc: None for the
+    greedy single-band association of mydet_track_frames_f32, or a track_assoc(...) (mydet_track_frames_assoc_f32)."""
     if not isinstance(params, _lib.TrackParams):
         raise TypeError(f'track_frames: params is a _lib.TrackParams (ops.track_params), got {type(params).__name__}')
+    if assoc is not None and not isinstance(assoc, _lib.TrackAssoc):
+        raise TypeError(f'track_frames: assoc is a _lib.TrackAssoc (ops.track_assoc) or None, got {type(assoc).__name__}')
     if isinstance(records, dict):
         records = _record_buffer('track_frames', records)
     if not isinstance(tracker_state, torch.Tensor) or tracker_state.dim() != 2:
@@ -1698,12 +1726,15 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
         if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
             raise ValueError(f'track_frames: out[{k!r}] must be a contiguous {dt} tensor {shape} on {dev}')
     t0 = TIMER.start() if TIMER else None
-    code = _lib.lib().mydet_track_frames_f32(_ptr(records), records.stride(0), records.stride(1), S, F, width, ctypes.byref(params), mt,
-                                             _ptr(tracker_state), _ptr(out['box']), _ptr(out['score']), _ptr(out['cls']),
-                                             _ptr(out['id']), _ptr(out['missed']), _ptr(out['count']), _ptr(out['dropped']), _stream())
+    args = (_ptr(records), records.stride(0), records.stride(1), S, F, width, ctypes.byref(params), mt, _ptr(tracker_state), _ptr(out['box']),
+            _ptr(out['score']), _ptr(out['cls']), _ptr(out['id']), _ptr(out['missed']), _ptr(out['count']), _ptr(out['dropped']))
+    if assoc is None:
+        code = _lib.lib().mydet_track_frames_f32(*args, _stream())
+    else:
+        code = _lib.lib().mydet_track_frames_assoc_f32(*args, ctypes.byref(assoc), _stream())
     if t0:
         TIMER.stop('track_frames', t0, float(S * F))
-    _lib.check(code, 'mydet_track_frames_f32')
+    _lib.check(code, 'mydet_track_frames_f32' if assoc is None else 'mydet_track_frames_assoc_f32')
     return out
 
 
