@@ -1356,6 +1356,63 @@ int mydet_mot_id_overlap(const mydet_eval_set *set, const mydet_mot_set *mot, co
 int mydet_mot_id_assign(const mydet_eval_set *set, const mydet_mot_set *mot, int T, const void *scratch, int64_t scratch_bytes,
                         int64_t *idtp, void *stream);
 
+/* HOTA (Luiten et al., IJCV 2021): detection accuracy (DetA), association accuracy (AssA) and localisation (LocA) per localisation
+ * threshold alpha, in three stream-ordered launches (csrc/hota.hip) behind mydet_eval_ious_f64.  The rules are those of TrackEval's
+ * hota.py with three changes, made so that no order of evaluation can change a decision: the accumulations are in fixed point,
+ * the costs are integers, and the tie rules are stated.  Agreement with TrackEval itself is not claimed; what is claimed, and tested
+ * with ==, is the rules below.
+ *
+ * Data model: exactly that of mydet_mot_set above.  A unit u is one (sequence, category); a group is one frame of one category;
+ *   rows are ground truths, columns are hypotheses; a group's IoU block is stored [column][row].  `ious` is the unchanged output of
+ *   mydet_eval_ious_f64.  A NaN IoU counts as 0 everywhere below.  Pair values are IoUs, in [0, 1]; a pair whose alignment score
+ *   (rule 1) or pair score (rule 2) leaves its range because they are not adds nothing and scores 0.
+ *   alphas: a HOST array of T float64 values, each > 0, <= 1 and not NaN.
+ *   A frame's assignment carries no state from frame to frame and does not depend on alpha: one assignment per group, every group
+ *   of every sequence at once.
+ *
+ * 1. Alignment (mydet_hota_align_f64).  Per group, in float64, uncontracted: rowsum[r] = the sum of iou over the columns, added
+ *    in ascending column order; colsum[c] = the sum of iou over the rows, added in ascending row order.  For a pair,
+ *    den = rowsum[r] + colsum[c] - iou, in that order; s = iou / den when iou > 0, else 0.
+ *    P[o][h] += (int64)floor(s * 2^30): an int64 atomic add into `pot`, int64 [n_ov], unit u's [nG_u][nH_u] block at ov_start[u]
+ *    (o, h: the identities of the row and the column).  gt_count[o] and dt_count[h], int32 [Gids] and [Hids], are the numbers of
+ *    frames an identity is present in.  The launch zeroes all three arrays first.  With at most 2^22 frames every integer below
+ *    stays under 2^53.
+ * 2. Pair score (mydet_hota_match).  A = (double)P / (double)((gt_count[o] + dt_count[h]) * 2^30 - P): one division of two exactly
+ *    representable integers; 0 when P is 0.  q = (int32)floor(A * iou * 1048576.0), the product in that order.  score_q, int32
+ *    [n_pairs] in the layout of `ious`, is an output.  q is formed once per pair, before the assignment runs.
+ * 3. Match (mydet_hota_match).  Per group with both sides non-empty: the minimum-cost assignment with cost 1048576 - q, by the
+ *    assignment routine above as it stands: all rows inserted in ascending order, a tie goes to the lowest column, the problem
+ *    transposed when rows > columns.  The smaller side is fully assigned.  hota_match int32 [G]: the assigned hypothesis row (an
+ *    index into the D rows) or -1; every element is written.
+ * 4. Score (mydet_hota_score_f64), per unit and alpha.  A row with hota_match >= 0 and iou >= alpha (float64, no epsilon) is a TP
+ *    of that alpha.  counts int64 [U][T][3] = (TP, FN, FP), FN = the unit's rows - TP and FP = the unit's columns - TP.  matches
+ *    int32 [T][n_ov]: M[a][o][h] += 1 per TP (the launch zeroes it first).  loc_sum float64 [U][T]: the sum of the TPs' IoUs.
+ *    ass_sum float64 [U][T][3], summed over the unit's pairs with M > 0: M * (M / max(1, gt_count + dt_count - M)),
+ *    M * (M / max(1, gt_count)), M * (M / max(1, dt_count)): one int-to-double conversion per operand, one division and one
+ *    multiplication a term.  The order of the two float64 sums is not part of the rules (the kernel adds per thread in index
+ *    order and then by a fixed tree, so a result repeats from run to run); every term is >= 0, so any order is within
+ *    (n - 1) * 2^-53 of the exact sum, relatively.
+ * The host (mydetection_amd.ops.hota_summarize) sums units into sequence rows and one overall row, as the CLEAR rows are -- not
+ *   TrackEval's averaging over classes -- and forms, per alpha, DetA = TP / (TP + FN + FP), DetRe, DetPr, AssA = ass_sum0 /
+ *   max(1, TP), AssRe, AssPr, LocA = loc_sum / TP (1 without a TP) and HOTA = sqrt(DetA * AssA).
+ *
+ * What takes part.  A group with rows and columns that `groups` does not list, a group whose table holds more than the caps, and
+ *   every group of a unit whose identity tables hold more than MYDET_MOT_MAX_IDS or reach past n_gt_ids, n_dt_ids or n_ov, is
+ *   left out of all four rules: its rows and columns are counted nowhere and its rows keep hota_match -1.  A group with one empty
+ *   side needs no listing, as in mydet_mot_clear_f64.
+ * MYDET_E_BADARG and MYDET_E_UNSUPP, nothing launched: every rule of the mydet_mot_* launches above, in the same order; null ious
+ *   or score_q with n_pairs > 0; a null array that would be read or written; T < 1, a null alphas or an alpha that is not > 0 and
+ *   <= 1 (BADARG); T > MYDET_EVAL_MAX_THRS (UNSUPP); I > 2^22 frames (UNSUPP: seq_start is a device array, so the bound on a
+ *   sequence is checked on the total).
+ * mydet_hota_match keeps the solver's state in 32 KiB of dynamic LDS, which needs no opt-in.  No launch needs scratch memory. */
+int mydet_hota_align_f64(const mydet_eval_set *set, const mydet_mot_set *mot, const double *ious, int64_t *pot, int32_t *gt_count,
+                         int32_t *dt_count, void *stream);
+int mydet_hota_match(const mydet_eval_set *set, const mydet_mot_set *mot, const double *ious, const int64_t *pot,
+                     const int32_t *gt_count, const int32_t *dt_count, int32_t *score_q, int32_t *hota_match, void *stream);
+int mydet_hota_score_f64(const mydet_eval_set *set, const mydet_mot_set *mot, const double *ious, const int32_t *hota_match,
+                         const int32_t *gt_count, const int32_t *dt_count, const double *alphas, int T, int64_t *counts,
+                         int32_t *matches, double *loc_sum, double *ass_sum, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,9 @@ SIGNATURES = {
     'mydet_mot_scratch_bytes': [c_ptr, c_int],
     'mydet_mot_id_overlap': [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr],
     'mydet_mot_id_assign': [c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr],
+    'mydet_hota_align_f64': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_hota_match': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_hota_score_f64': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
     'mydet_cxcywh_to_x1y1x2y2_f32': [c_ptr, c_ptr, c_i64, c_int, c_ptr],
     'mydet_bboxes_to_original_f32': [c_ptr, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr],
 }
@@ -172,6 +175,8 @@ EVAL_MAX_GT, EVAL_MAX_DT, EVAL_MAX_THRS, EVAL_MAX_AREAS, EVAL_MAX_DETS, EVAL_MAX
 EVAL_GT_IGNORE, EVAL_GT_CROWD = 1, 2
 # track scoring (mydet_mot_*): MYDET_MOT_MAX_IDS of include/mydet.h
 MOT_MAX_IDS = 1024
+# HOTA (mydet_hota_*): the frame bound of include/mydet.h, and the fixed-point units of a potential and of a pair score
+HOTA_MAX_FRAMES, HOTA_P_ONE, HOTA_Q_ONE = 1 << 22, 1 << 30, 1 << 20
 
 
 class DecodeLevel(ctypes.Structure):

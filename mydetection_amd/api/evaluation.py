@@ -92,9 +92,14 @@ class TrackEvaluator:
     result() -> {'iou_thrs', 'overall': [per threshold], 'sequences': {name: [per threshold]}, 'summary'}; every entry holds the
     integer counts (tp, fp, fn, idsw, frag, n_gt, n_hyp, idtp, idfp, idfn, n_ids, mt, pt, ml) and mota = 1 - (FN + FP + IDSW) / nGT,
     motp = SIOU / TP, precision, recall, idf1 = 2 IDTP / (nGT + nHyp), idp, idr.  motp is the MEAN IoU of the matches, not the
-    distance of the CLEAR MOT paper: larger is better.  Every other ratio is one float64 division of exact integers."""
+    distance of the CLEAR MOT paper: larger is better.  Every other ratio is one float64 division of exact integers.
+    hota: False, True (alphas 0.05 .. 0.95) or a sequence of alphas, each > 0 and <= 1: result()['hota'] = {'alphas', 'overall',
+    'sequences'} then holds HOTA, DetA, AssA, DetRe, DetPr, AssRe, AssPr and LocA per alpha and as means over the alphas
+    (mydet_hota_*; units summed as the CLEAR rows are, not averaged over classes as TrackEval does), and the summary gains their
+    table.  With hota=False the result is what it was."""
 
-    def __init__(self, gt, kind='coco', iou_thrs=(0.5,), sequences=None, id_key=None, use_cats=True, catIdx2id=None, device=None):
+    def __init__(self, gt, kind='coco', iou_thrs=(0.5,), sequences=None, id_key=None, use_cats=True, catIdx2id=None, device=None,
+                 hota=False):
         self.rotated = ops._eval_kind(kind)
         self.kind, self.gt, self.device = kind, _loaded(gt), device
         self.iou_thrs = ops._eval_thresholds(iou_thrs, 'iou_thrs')
@@ -103,6 +108,7 @@ class TrackEvaluator:
         if sequences is not None and not isinstance(sequences, dict):
             raise ValueError('TrackEvaluator: sequences is None or a dict {name: [img_id, ...]}')
         self.sequences, self.id_key, self.use_cats = sequences, id_key, bool(use_cats)
+        self.hota = False if hota is False or hota is None else ops.hota_alphas(hota)
         ops.mot_sequences(self.gt, sequences)                        # the argument errors, before anything is added
         ops.mot_id_key(self.gt, id_key)
         self.cat_table = COCO_CATEGORY_IDS if catIdx2id is None else catIdx2id
@@ -149,7 +155,7 @@ class TrackEvaluator:
     def evaluator(self, **kwargs):
         """The MOTeval over what was added, before evaluate()."""
         return MOTeval(self.gt, self.columns(), self.kind, self.iou_thrs, self.sequences, self.id_key, self.use_cats, False, self.device,
-                       **kwargs)
+                       hota=self.hota, **kwargs)
 
     def result(self):
         e = self.evaluator()

@@ -257,20 +257,6 @@ __global__ __launch_bounds__(MOT_WAVE) void mot_id_assign_kernel(const mydet_mot
     if (lane == 0) idtp[(int64_t)u * T + t] = sum;
 }
 
-int mot_check(const mydet_eval_set *s, const mydet_mot_set *m) {
-    const int code = eval_check_set(s);
-    if (code == MYDET_E_BADARG) return code;
-    if (!m || m->S < 1 || m->S > s->I) return MYDET_E_BADARG;
-    if (m->max_gt_ids < 0 || m->max_dt_ids < 0 || m->n_gt_ids < 0 || m->n_dt_ids < 0 || m->n_ov < 0) return MYDET_E_BADARG;
-    if (m->n_gt_ids > s->G || m->n_dt_ids > s->D || m->max_gt_ids > m->n_gt_ids || m->max_dt_ids > m->n_dt_ids) return MYDET_E_BADARG;
-    if ((double)m->n_ov > (double)m->n_gt_ids * (double)m->n_dt_ids) return MYDET_E_BADARG;
-    if (!m->seq_start || !m->gt_id_start || !m->dt_id_start || !m->ov_start) return MYDET_E_BADARG;
-    if ((s->G > 0 && !m->gt_id) || (s->D > 0 && !m->dt_id)) return MYDET_E_BADARG;
-    if (code) return code;
-    if (m->max_gt_ids > MYDET_MOT_MAX_IDS || m->max_dt_ids > MYDET_MOT_MAX_IDS) return MYDET_E_UNSUPP;
-    return 0;
-}
-
 int mot_thresholds(MotThresholds &q, const double *iou_thrs, int T) {
     if (!iou_thrs || T < 1) return MYDET_E_BADARG;
     if (T > MYDET_EVAL_MAX_THRS) return MYDET_E_UNSUPP;

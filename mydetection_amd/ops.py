@@ -3216,3 +3216,152 @@ def mot_summarize(raw, pack, iou_thrs):
             lines.append(' {:<16} {:>5.2f}'.format(str(name)[:16], result['iou_thrs'][t]) + ''.join(' {:>9.4f}'.format(r[c]) for c in MOT_SUMMARY_COLUMNS)
                          + ''.join(' {:>6d}'.format(r[c]) for c in MOT_SUMMARY_COUNTS))
     return result, ''.join(line + '\n' for line in lines)
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# HOTA on the same packed arrays (include/mydet.h, "HOTA": the three mydet_hota_* launches; the rules are there).  Everything up to
+# hota_summarize runs on the device; hota_summarize is host numpy.
+HOTA_DEFAULT_ALPHAS = tuple((np.arange(1, 20) / 20.0).tolist())
+HOTA_COUNTS = ('tp', 'fn', 'fp')
+HOTA_PER_ALPHA = ('hota', 'deta', 'assa', 'detre', 'detpr', 'assre', 'asspr', 'loca')
+
+
+def hota_alphas(alphas=True):
+    """The float64 array of localisation thresholds: True (or None) gives 0.05 .. 0.95; a sequence gives its values, 1 to
+    EVAL_MAX_THRS of them, each > 0, <= 1 and not NaN (ValueError otherwise)."""
+    a = np.array(HOTA_DEFAULT_ALPHAS) if alphas is True or alphas is None else _eval_thresholds(alphas, 'alphas')
+    if not 1 <= len(a) <= _lib.EVAL_MAX_THRS:
+        raise ValueError(f'hota: 1 to {_lib.EVAL_MAX_THRS} alphas expected, got {len(a)}')
+    if not bool(np.all((a > 0) & (a <= 1))):                         # NaN fails both
+        raise ValueError('hota: every alpha must be > 0 and <= 1, none of them NaN')
+    return a
+
+
+def _hota_tensor(what, t, dtype, n, dev, name):
+    require_gpu(t, what)
+    if t.dtype != dtype or t.numel() != n or not t.is_contiguous() or t.device != dev:
+        raise ValueError(f'{what}: {name} must be {dtype} with {n} elements, contiguous, on {dev}')
+    return t
+
+
+def hota_align(ms, ious):
+    """mydet_hota_align_f64 (three memsets and two launches): (pot int64 [n_ov], gt_count int32 [Gids], dt_count int32 [Hids]):
+    the fixed-point alignment potentials of every identity pair, unit u's [nG_u, nH_u] block at ov_start[u], and the number of
+    frames every identity is present in."""
+    p, dev = ms.pack, ms.device
+    _hota_tensor('hota_align', ious, torch.float64, p['n_pairs'], dev, 'ious')
+    pot = torch.empty((p['n_ov'],), dtype=torch.int64, device=dev)
+    gt_count = torch.empty((p['n_gt_ids'],), dtype=torch.int32, device=dev)
+    dt_count = torch.empty((p['n_dt_ids'],), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        code = _lib.lib().mydet_hota_align_f64(ctypes.byref(ms.c), ctypes.byref(ms.m), _ptr(ious), _ptr(pot), _ptr(gt_count),
+                                               _ptr(dt_count), _stream())
+    _lib.check(code, 'mydet_hota_align_f64')
+    return pot, gt_count, dt_count
+
+
+def hota_match(ms, ious, pot, gt_count, dt_count):
+    """mydet_hota_match (two memsets and one launch, one wavefront per listed group): (score_q int32 [n_pairs], the pair scores in
+    the layout of ious; hota_match int32 [G], the assigned hypothesis row of every ground truth or -1).  Independent of alpha."""
+    p, dev = ms.pack, ms.device
+    _hota_tensor('hota_match', ious, torch.float64, p['n_pairs'], dev, 'ious')
+    _hota_tensor('hota_match', pot, torch.int64, p['n_ov'], dev, 'pot')
+    _hota_tensor('hota_match', gt_count, torch.int32, p['n_gt_ids'], dev, 'gt_count')
+    _hota_tensor('hota_match', dt_count, torch.int32, p['n_dt_ids'], dev, 'dt_count')
+    score_q = torch.empty((p['n_pairs'],), dtype=torch.int32, device=dev)
+    match = torch.empty((p['G'],), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        code = _lib.lib().mydet_hota_match(ctypes.byref(ms.c), ctypes.byref(ms.m), _ptr(ious), _ptr(pot), _ptr(gt_count), _ptr(dt_count),
+                                           _ptr(score_q), _ptr(match), _stream())
+    _lib.check(code, 'mydet_hota_match')
+    return score_q, match
+
+
+def hota_score(ms, ious, match, gt_count, dt_count, alphas):
+    """mydet_hota_score_f64 (a memset and two launches): (counts int64 [U, T, 3] = (TP, FN, FP), matches int32 [T, n_ov], loc_sum
+    float64 [U, T], ass_sum float64 [U, T, 3])."""
+    a = hota_alphas(alphas)
+    p, T, dev = ms.pack, len(a), ms.device
+    _hota_tensor('hota_score', ious, torch.float64, p['n_pairs'], dev, 'ious')
+    _hota_tensor('hota_score', match, torch.int32, p['G'], dev, 'hota_match')
+    _hota_tensor('hota_score', gt_count, torch.int32, p['n_gt_ids'], dev, 'gt_count')
+    _hota_tensor('hota_score', dt_count, torch.int32, p['n_dt_ids'], dev, 'dt_count')
+    counts = torch.empty((p['U'], T, 3), dtype=torch.int64, device=dev)
+    matches = torch.empty((T, p['n_ov']), dtype=torch.int32, device=dev)
+    loc_sum = torch.empty((p['U'], T), dtype=torch.float64, device=dev)
+    ass_sum = torch.empty((p['U'], T, 3), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        code = _lib.lib().mydet_hota_score_f64(ctypes.byref(ms.c), ctypes.byref(ms.m), _ptr(ious), _ptr(match), _ptr(gt_count),
+                                               _ptr(dt_count), a.ctypes.data, T, _ptr(counts), _ptr(matches), _ptr(loc_sum),
+                                               _ptr(ass_sum), _stream())
+    _lib.check(code, 'mydet_hota_score_f64')
+    return counts, matches, loc_sum, ass_sum
+
+
+def hota_evaluate(ms, alphas=True, ious=None):
+    """mydet_eval_ious_f64 and the three HOTA launches on a MotSet (or a pack), stream-ordered, no synchronisation.  Returns the
+    raw arrays as tensors: ious, pot, gt_count, dt_count, score_q, hota_match, counts, matches, loc_sum, ass_sum.  ious: a float64
+    [n_pairs] tensor to score instead of the IoUs of the boxes (mot_evaluate's, for one)."""
+    a = hota_alphas(alphas)
+    if isinstance(ms, dict):
+        ms = MotSet(ms)
+    if ious is None:
+        ious = eval_ious(ms)
+    pot, gt_count, dt_count = hota_align(ms, ious)
+    score_q, match = hota_match(ms, ious, pot, gt_count, dt_count)
+    counts, matches, loc_sum, ass_sum = hota_score(ms, ious, match, gt_count, dt_count, a)
+    return {'ious': ious, 'pot': pot, 'gt_count': gt_count, 'dt_count': dt_count, 'score_q': score_q, 'hota_match': match,
+            'counts': counts, 'matches': matches, 'loc_sum': loc_sum, 'ass_sum': ass_sum}
+
+
+def _hota_ratio(num, den):
+    """One float64 division; 0.0 without a denominator."""
+    return float(np.float64(num) / np.float64(den)) if den else 0.0
+
+
+def hota_metrics(tp, fn, fp, loc_sum, ass_sum):
+    """Host: the metrics of one row (a sequence or the total) at one alpha from its integer counts and the two float64 sums."""
+    tp, fn, fp = int(tp), int(fn), int(fp)
+    deta = _hota_ratio(tp, tp + fn + fp)
+    assa, assre, asspr = (_hota_ratio(v, max(1, tp)) for v in ass_sum)
+    return {'tp': tp, 'fn': fn, 'fp': fp, 'deta': deta, 'detre': _hota_ratio(tp, tp + fn), 'detpr': _hota_ratio(tp, tp + fp),
+            'assa': assa, 'assre': assre, 'asspr': asspr, 'loca': _hota_ratio(loc_sum, tp) if tp else 1.0,
+            'hota': float(np.sqrt(np.float64(deta) * np.float64(assa)))}
+
+
+HOTA_SUMMARY_COLUMNS = ('hota', 'deta', 'assa', 'detre', 'detpr', 'assre', 'asspr', 'loca', 'hota0', 'loca0', 'hota_loca0')
+
+
+def hota_summarize(raw, pack, alphas):
+    """Host numpy: per sequence and overall, the HOTA family from the raw arrays of hota_evaluate (numpy).  A sequence row sums its
+    categories' units and the overall row sums all units, as the CLEAR rows do (not TrackEval's averaging over classes); the float64
+    sums are added unit by unit in unit order.  Returns (result, text): result is {'alphas', 'overall': entry, 'sequences':
+    {name: entry}}; an entry holds 'per_alpha', the lists tp, fn, fp, hota, deta, assa, detre, detpr, assre, asspr and loca over
+    the alphas, and as scalars under the same names the means of the ratios over the alphas, plus hota0, loca0 and hota_loca0 =
+    hota0 * loca0 at the first alpha."""
+    S, K, T = pack['S'], pack['K'], len(alphas)
+    counts, loc_sum, ass_sum = np.asarray(raw['counts']), np.asarray(raw['loc_sum']), np.asarray(raw['ass_sum'])
+
+    def entry(units):
+        rows = []
+        for t in range(T):
+            c = sum((counts[u, t].astype(np.int64) for u in units), np.zeros(3, dtype=np.int64))
+            loc, ass = np.float64(0.0), np.zeros(3, dtype=np.float64)
+            for u in units:
+                loc = loc + loc_sum[u, t]
+                ass = ass + ass_sum[u, t]
+            rows.append(hota_metrics(c[0], c[1], c[2], loc, ass))
+        out = {'per_alpha': {k: [r[k] for r in rows] for k in HOTA_COUNTS + HOTA_PER_ALPHA}}
+        for k in HOTA_PER_ALPHA:
+            out[k] = float(np.mean(np.array(out['per_alpha'][k], dtype=np.float64)))
+        out['hota0'], out['loca0'] = rows[0]['hota'], rows[0]['loca']
+        out['hota_loca0'] = float(np.float64(out['hota0']) * np.float64(out['loca0']))
+        return out
+
+    result = {'alphas': [float(v) for v in alphas],
+              'sequences': {name: entry([k * S + s for k in range(K)]) for s, name in enumerate(pack['seq_names'])},
+              'overall': entry(list(range(S * K)))}
+    lines = [' {:<16}'.format('sequence') + ''.join(' {:>10}'.format(c) for c in HOTA_SUMMARY_COLUMNS)]
+    for name, e in list(result['sequences'].items()) + [('OVERALL', result['overall'])]:
+        lines.append(' {:<16}'.format(str(name)[:16]) + ''.join(' {:>10.4f}'.format(e[c]) for c in HOTA_SUMMARY_COLUMNS))
+    return result, ''.join(line + '\n' for line in lines)
