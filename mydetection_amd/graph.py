@@ -30,14 +30,9 @@ from .utils.structures import batched_post_process
 
 def prepared_tensors(model):
     """Every kernel-ready parameter copy cached on the model's modules at this moment (models.modules.prepare_conv
-    and friends keep them in `_prep_cache` / `_w2t` dicts): the tensors a captured launch sequence reads."""
-    held = []
-    for m in model.modules():
-        for slot in ('_prep_cache', '_w2t'):
-            cache = m.__dict__.get(slot)
-            if cache:
-                held.append(dict(cache))        # shallow copy: keeps the current values alive when a slot is rebuilt
-    return held
+    and `derived` keep them in `_prep_cache`): the tensors a captured launch sequence reads."""
+    # shallow copies: they keep the current values alive when a slot is rebuilt
+    return [dict(m.__dict__['_prep_cache']) for m in model.modules() if m.__dict__.get('_prep_cache')]
 
 
 class GraphedPath:

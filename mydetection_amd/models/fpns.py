@@ -3,7 +3,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .modules import ConvBn, ConvBnLeaky, SpconvBn, prepare_conv
+from .modules import NO_FORMS, ConvBn, ConvBnLeaky, SpconvBn, conv_prepared, derived, prepare_conv
 
 
 class YOLOv3FPN(nn.Module):
@@ -120,14 +120,10 @@ def conv1x1_bn_pair(a, b, x):
     if a is _identity:
         return x, x
     pa, pb = prepare_conv(a, 'main', a[0], a[1]), prepare_conv(b, 'main', b[0], b[1])
-    cache = a.__dict__.setdefault('_prep_cache', {})
-    hit = cache.get('pair')
-    if hit is None or hit[0][0] is not pa[0] or hit[0][1] is not pb[0]:
+    def cat(_):
         with torch.no_grad():
-            hit = ((pa[0], pb[0]), tuple(torch.cat([u, v]).contiguous() for u, v in zip(pa, pb)))
-        cache['pair'] = hit
-    w, scale, shift = hit[1]
-    y = ops.conv2d(x, w, scale, shift, 1, 1, (0, 0, 0, 0), ops.ACT_NONE)
+            return tuple(torch.cat([u, v]).contiguous() for u, v in zip(pa, pb))
+    y = conv_prepared(a, 'pair', x, derived(a, 'pair', (pa[0], pb[0]), cat), 1, (0, 0, 0, 0), ops.ACT_NONE, forms=NO_FORMS)
     na = pa[0].shape[0]
     return y[:, :na], y[:, na:]
 

@@ -49,41 +49,52 @@ def prepare_conv(owner, slot, conv, bn, depthwise=False):
     return hit[1]
 
 
-def prepare_wino(owner, slot, w_ohwi):
-    """Transform-domain copies of a prepared 3x3 OHWI weight: (ops.wino_weights, ops.wino4_weights), each None when
-    its fused Winograd kernel does not cover the shape (F(4x4) only from ops.WINO4_MIN_CIN input channels up).
-    Cached on `owner` next to the weight they were made from."""
+def derived(owner, slot, source, make):
+    """`make(source)`, cached on `owner` under `slot` next to what it was made from and rebuilt when that is replaced.  source: a
+    prepared tensor or a tuple of them (prepare_conv hands out new tensors whenever a parameter changes); compared by identity, so
+    module switches (True / False) may ride along in the tuple."""
     cache = owner.__dict__.setdefault('_prep_cache', {})
     hit = cache.get(slot)
-    if hit is None or hit[0] is not w_ohwi:
-        u = ops.wino_weights(w_ohwi) if ops.WINOGRAD else None
-        u4 = ops.wino4_weights(w_ohwi) if ops.WINOGRAD and ops.WINOGRAD4 and w_ohwi.shape[3] >= ops.WINO4_MIN_CIN else None
-        hit = (w_ohwi, (u, u4))
+    src = source if isinstance(source, tuple) else (source,)
+    if hit is None or len(hit[0]) != len(src) or any(a is not b for a, b in zip(hit[0], src)):
+        hit = (src, make(source))
         cache[slot] = hit
     return hit[1]
 
 
-def prepare_b3(owner, slot, w_ohwi):
-    """Three-plane bfloat16 copy of a prepared OHWI weight for the split-bf16 implicit GEMM (ops.split_bf16; cached on `owner`
-    next to the weight it was made from), or None when no shape of the layer can take that kernel (Cin % 16; 1x1 layers: Cin % 4)."""
-    if not ops.SPLIT_BF16 or (w_ohwi.shape[3] % 16 and not (w_ohwi.shape[1] == 1 and w_ohwi.shape[2] == 1 and w_ohwi.shape[3] % 4 == 0)):
-        return None
-    cache = owner.__dict__.setdefault('_prep_cache', {})
-    hit = cache.get(slot)
-    if hit is None or hit[0] is not w_ohwi:
-        hit = (w_ohwi, ops.split_bf16(w_ohwi))
-        cache[slot] = hit
-    return hit[1]
+# The weight forms a call site lets its layers take (ops.CONV_FORMS): exactly those each site handed to ops.conv2d before the routes were
+# tabulated in ops.conv_route.  Widening a site's set is a tuning change that has to be measured -- every form is a copy of the weight
+# that each captured graph holds, split-bf16 planes 1.5 x its size -- not a clean-up.
+ALL_FORMS = ops.CONV_FORMS
+WINOGRAD_FORMS = frozenset(('wino', 'wino4'))
+B3_FORM = frozenset(('b3',))
+NO_FORMS = frozenset()
 
 
-class FusedConvMixin:
-    """Caches kernel-ready parameters (OHWI weights, per-channel scale/shift)."""
+def conv_operands(owner, slot, w, stride, pad, act, forms, gated=False):
+    """{form: tensor} of the forms among `forms` that ops.conv_forms finds worth preparing for the prepared OHWI weight `w`: keyword
+    arguments of ops.conv2d.  Cached on `owner` next to the weight; made again when a switch that conv_forms reads is flipped."""
+    def make(_):
+        made = ((f, ops.CONV_FORM_WEIGHTS[f](w)) for f in sorted(ops.conv_forms(w.shape[0], w.shape[3], w.shape[1], stride, pad, gated, act, forms)))
+        return {f: t for f, t in made if t is not None}
+    return derived(owner, (slot, forms), (w, ops.WINOGRAD, ops.WINOGRAD4, ops.SPLIT_BF16), make)
 
-    def _prepared(self, conv, bn):
-        return prepare_conv(self, 'main', conv, bn)
+
+def conv_prepared(owner, slot, x, params, stride, pad, act, *, forms, gate=None, **kw):
+    """ops.conv2d of the prepared (OHWI weight, scale, shift) `params` with the forms of `forms` that the layer can use (conv_operands);
+    kw: residual, out, interior, b3_min_rows."""
+    held = conv_operands(owner, slot, params[0], stride, pad, act, forms, gate is not None) if forms else {}
+    return ops.conv2d(x, *params, params[0].shape[1], stride, pad, act, gate=gate, **kw, **held)
 
 
-class ConvBnLeaky(nn.Module, FusedConvMixin):
+def fused_conv(owner, slot, x, conv, bn, act, *, forms, **kw):
+    """act(bn(conv(x * gate))) + residual as one launch: prepare_conv, the weight forms the call site allows, ops.conv2d.
+    kw: residual, gate, out, interior, b3_min_rows."""
+    p = conv.padding
+    return conv_prepared(owner, slot, x, prepare_conv(owner, slot, conv, bn), conv.stride[0], (p[0], p[1], p[0], p[1]), act, forms=forms, **kw)
+
+
+class ConvBnLeaky(nn.Module):
     '''
     Conv2d + BatchNorm + LeakyReLU(0.1) as one kernel  (reference: models/modules.py:76-95)
 
@@ -103,7 +114,7 @@ class ConvBnLeaky(nn.Module, FusedConvMixin):
         either path."""
         if self.training:
             raise NotImplementedError('mydetection_amd implements the inference path only; call model.eval()')
-        w, scale, shift = self._prepared(self.conv, self.bn)
+        w, scale, shift = prepare_conv(self, 'main', self.conv, self.bn)
         p = (self.k - 1) // 2
         if upcat_lo is not None:
             assert residual is None
@@ -114,11 +125,7 @@ class ConvBnLeaky(nn.Module, FusedConvMixin):
             x = ops.upsample_concat(upcat_lo, tuple(x.shape[2:4]), x)        # cat((up(lo), x), dim=1), then the plain layer
         if w.shape[3] == 3 and self.k == 3 and w.shape[0] == 32 and residual is None:
             return ops.conv2d_stem(x, w, scale, shift, self.s, (p, p, p, p), ops.ACT_LEAKY)
-        u, u4 = prepare_wino(self, 'wino', w) if self.k == 3 and self.s == 1 else (None, None)
-        # the layers that stay on the direct implicit GEMM (1x1, stride-2 3x3) take its split-bf16 form where ops.b3_takes says so
-        # ... and the 3x3 layers their patch-resident form where ops.p3_takes says so (stride 2; stride 1 below F(4x4)'s channel limit)
-        b3 = prepare_b3(self, 'b3', w) if (u is None and u4 is None) or (self.k == 3 and w.shape[3] <= ops.P3_S1_MAX_CIN) else None
-        return ops.conv2d(x, w, scale, shift, self.k, self.s, (p, p, p, p), ops.ACT_LEAKY, residual=residual, wino=u, wino4=u4, b3=b3)
+        return conv_prepared(self, 'main', x, (w, scale, shift), self.s, (p, p, p, p), ops.ACT_LEAKY, forms=ALL_FORMS, residual=residual)
 
 
 def stem_p3(cbl_0, cbl_1, x):
@@ -132,14 +139,11 @@ def stem_p3(cbl_0, cbl_1, x):
     B, _, H, W = x.shape
     if not (ops.SPLIT_BF16 and ops.stem_p3_takes(B, H, W, cbl_1.conv.out_channels, (1, 1, 1, 1))):
         return None
-    w0, scale0, shift0 = cbl_0._prepared(cbl_0.conv, cbl_0.bn)
-    w1, scale1, shift1 = cbl_1._prepared(cbl_1.conv, cbl_1.bn)
-    cache = cbl_0.__dict__.setdefault('_prep_cache', {})
-    hit = cache.get('stem_p3')
-    if hit is None or hit[0] is not w0:
-        hit = (w0, ops.stem_p3_weights(w0))
-        cache['stem_p3'] = hit
-    return ops.conv_stem_p3(x, hit[1], scale0, shift0, (1, 1, 1, 1), prepare_b3(cbl_1, 'b3', w1), scale1, shift1)
+    w0, scale0, shift0 = prepare_conv(cbl_0, 'main', cbl_0.conv, cbl_0.bn)
+    w1, scale1, shift1 = prepare_conv(cbl_1, 'main', cbl_1.conv, cbl_1.bn)
+    # the second layer's planes are the ones its own forward holds: one copy whichever launch runs
+    b3 = conv_operands(cbl_1, 'main', w1, 2, (1, 1, 1, 1), ops.ACT_LEAKY, ALL_FORMS).get('b3')
+    return ops.conv_stem_p3(x, derived(cbl_0, 'stem_p3', w0, ops.stem_p3_weights), scale0, shift0, (1, 1, 1, 1), b3, scale1, shift1)
 
 
 class DarkBlock(nn.Module):
@@ -186,12 +190,8 @@ class SeparableConv2d(nn.Module):
             raise NotImplementedError('mydetection_amd implements the inference path only; call model.eval()')
         wd, _, _ = prepare_conv(self, 'dw', self.depthwise, None, depthwise=True)
         wp, scale, shift = prepare_conv(self, ('pw', id(bn)), self.pointwise, bn)
-        cache = self.__dict__.setdefault('_prep_cache', {})
-        hit = cache.get(('pwk', id(bn)))
-        if hit is None or hit[0] is not wp:
-            hit = (wp, ops.pack_pointwise(wp))
-            cache[('pwk', id(bn))] = hit
-        return dict(inputs=list(inputs), modes=modes, fuse_weights=fuse_weights, w_dw=wd, w_pw=hit[1], scale=scale,
+        return dict(inputs=list(inputs), modes=modes, fuse_weights=fuse_weights, w_dw=wd,
+                    w_pw=derived(self, ('pwk', id(bn)), wp, ops.pack_pointwise), scale=scale,
                     shift=shift, cout=self.pointwise.out_channels, act=act, out=out)
 
     def node_per_anchor(self, inputs, A, n_cls):
@@ -199,12 +199,7 @@ class SeparableConv2d(nn.Module):
         weights / bias with every anchor's n_cls rows padded to whole 16-channel blocks (cached)."""
         nd = self.node(inputs)
         wp, _, shift = prepare_conv(self, ('pw', id(None)), self.pointwise, None)
-        cache = self.__dict__.setdefault('_prep_cache', {})
-        hit = cache.get(('pwk_anchor', A, n_cls))
-        if hit is None or hit[0] is not wp:
-            hit = (wp, ops.pack_pointwise_per_anchor(wp, shift, A, n_cls))
-            cache[('pwk_anchor', A, n_cls)] = hit
-        nd['w_pw'], nd['shift'] = hit[1]
+        nd['w_pw'], nd['shift'] = derived(self, ('pwk_anchor', A, n_cls), wp, lambda wp: ops.pack_pointwise_per_anchor(wp, shift, A, n_cls))
         return nd
 
     def forward(self, x, bn=None, act=ops.ACT_NONE):
@@ -214,8 +209,7 @@ class SeparableConv2d(nn.Module):
             return ops.sepconv_nodes([self.node([x], bn=bn, act=act)])[0]
         wd, _, _ = prepare_conv(self, 'dw', self.depthwise, None, depthwise=True)
         x = ops.dwconv(x, wd, None, None, self.k, self.s, (self.p,) * 4, ops.ACT_NONE)
-        wp, scale, shift = prepare_conv(self, ('pw', id(bn)), self.pointwise, bn)
-        return ops.conv2d(x, wp, scale, shift, 1, 1, (0, 0, 0, 0), act)
+        return fused_conv(self, ('pw', id(bn)), x, self.pointwise, bn, act, forms=NO_FORMS)
 
 
 class ConvBn(nn.Sequential):
@@ -227,10 +221,8 @@ class ConvBn(nn.Sequential):
         self.k, self.p = k, padding
 
     def forward(self, x):
-        w, scale, shift = prepare_conv(self, 'main', self[0], self[1])
         # the 3x3 C6 / C7 convs (320->88 @20^2, 88->88 @10^2) take the Winograd kernels like every other 3x3 stride-1 layer
-        u, u4 = prepare_wino(self, 'wino', w) if self.k == 3 and self.p == 1 else (None, None)
-        return ops.conv2d(x, w, scale, shift, self.k, 1, (self.p,) * 4, ops.ACT_NONE, wino=u, wino4=u4)
+        return fused_conv(self, 'main', x, self[0], self[1], ops.ACT_NONE, forms=WINOGRAD_FORMS)
 
 
 class SpconvBn(nn.Sequential):

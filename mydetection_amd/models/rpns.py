@@ -5,7 +5,8 @@ from .. import ops
 import numpy as np
 import torch
 
-from .modules import prepare_wino, prepare_b3, FusedConvMixin, SeparableConv2d, SpconvBn, prepare_conv, _versions
+from .modules import (B3_FORM, NO_FORMS, WINOGRAD_FORMS, SeparableConv2d, SpconvBn, conv_prepared, derived, fused_conv,
+                      prepare_conv, _versions)
 
 
 class RawPreds(dict):
@@ -13,10 +14,6 @@ class RawPreds(dict):
     pixel-major head tensor the views alias, so the decode kernel can read it in place."""
     packed = None        # dict(box=(tensor, ld, astride, c0), cls=(tensor, ld, astride, c0, conf_c0)); tensors are
                          # logical [B,ch,H,W] stored channels-last with pixel stride ld
-
-
-class _HeadConv(nn.Conv2d, FusedConvMixin):
-    pass
 
 
 class YOLOHead(nn.Module):
@@ -35,14 +32,13 @@ class YOLOHead(nn.Module):
         self.heads = nn.ModuleList()
         out_ch = (self.bb_param + 1 + self.n_cls) * self.n_anch
         for i, ch in enumerate(cfg['model.fpn.out_channels']):
-            self.heads.add_module(name=f'conv_{i}', module=_HeadConv(ch, out_ch, 1, stride=1, padding=0))
+            self.heads.add_module(name=f'conv_{i}', module=nn.Conv2d(ch, out_ch, 1, stride=1, padding=0))
 
     def forward(self, features):
         nBp = self.bb_param
         all_level_preds = []
         for module, P in zip(self.heads, features):
-            w, scale, shift = module._prepared(module, None)
-            preds = ops.conv2d(P, w, scale, shift, 1, 1, (0, 0, 0, 0), ops.ACT_NONE, b3=prepare_b3(module, 'b3', w))
+            preds = fused_conv(module, 'main', P, module, None, ops.ACT_NONE, forms=B3_FORM)
             nB, _, nH, nW = preds.shape
             per = nBp + 1 + self.n_cls
             raw = RawPreds()
@@ -75,11 +71,10 @@ class _LastConv(nn.Conv2d):
         w, scale, shift = prepare_conv(self, 'main', self, None)
         cout = w.shape[0]
         if out is not None or cout % 4 == 0:
-            u, u4 = prepare_wino(self, 'wino', w) if out is None and cout >= 32 else (None, None)
-            return ops.conv2d(x, w, scale, shift, 3, 1, (1, 1, 1, 1), ops.ACT_NONE, out=out, wino=u, wino4=u4)
-        cache = self.__dict__.setdefault('_prep_cache', {})
-        hit = cache.get('padded')
-        if hit is None or hit[0] is not w:
+            return conv_prepared(self, 'main', x, (w, scale, shift), 1, (1, 1, 1, 1), ops.ACT_NONE, out=out,
+                                 forms=WINOGRAD_FORMS if out is None and cout >= 32 else NO_FORMS)
+
+        def pad_rows(w):
             cp = (cout + 3) // 4 * 4
             wp = w.new_zeros((cp,) + tuple(w.shape[1:]))
             wp[:cout] = w
@@ -89,11 +84,8 @@ class _LastConv(nn.Conv2d):
             if scale is not None:
                 sc = scale.new_ones(cp)
                 sc[:cout] = scale
-            hit = (w, (wp, sc, sp))
-            cache['padded'] = hit
-        wp, sc, sp = hit[1]
-        u, u4 = prepare_wino(self, 'wino_padded', wp)
-        y = ops.conv2d(x, wp, sc, sp, 3, 1, (1, 1, 1, 1), ops.ACT_NONE, wino=u, wino4=u4)
+            return wp, sc, sp
+        y = conv_prepared(self, 'padded', x, derived(self, 'padded', w, pad_rows), 1, (1, 1, 1, 1), ops.ACT_NONE, forms=WINOGRAD_FORMS)
         return y[:, :cout]
 
 

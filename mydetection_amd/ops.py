@@ -432,6 +432,132 @@ def _check_conv(code, entry, family, *shape):
     _lib.check(code, entry)
 
 
+CONV_FORM_WEIGHTS = {'wino': wino_weights, 'wino4': wino4_weights, 'b3': split_bf16}      # the weight operands derived from the OHWI weight
+CONV_FORMS = frozenset(CONV_FORM_WEIGHTS)
+
+
+def _wino_shape(k, stride, pad, gated):
+    return not gated and k == 3 and stride == 1 and tuple(pad) == (1, 1, 1, 1)
+
+
+def conv_route(B, H, W, Cin, Cout, k, stride, pad, act, *, gated, ldy, ldr, forms, b3_min_rows=None):
+    """The launchers `conv2d` tries for a layer, in order, as KernelTimer family names (the keys of CONV_LAUNCHERS): every one but the
+    last may answer MYDET_E_UNSUPP.  forms: the weight forms the caller holds (of CONV_FORMS); gated: a squeeze-excite gate multiplies the
+    input; ldy / ldr: pixel strides of output and residual (0: none); b3_min_rows: the caller's own row threshold for the split-bf16
+    implicit GEMM.  Host code only -- no tensors, no launch -- under the module switches as they are at the call."""
+    return _conv_route(_route_switches(), B, H, W, Cin, Cout, k, stride, tuple(pad), act, bool(gated), ldy, ldr,
+                       'wino' in forms, 'wino4' in forms, 'b3' in forms, b3_min_rows)
+
+
+def _route_switches():      # every switch the route reads (p3_takes, b3_takes included): in the memo key, so that a flipped one is obeyed
+    return (WINOGRAD, WINOGRAD4, WINO4_MIN_ITEMS, SPLIT_BF16, B3_MIN_ROWS, B3_MIN_FLOP, B3_KPAD, B3_GATED_MIN_COUT, CONV_P3, P3_MIN_WGS,
+            P3_S1_MAX_CIN, P3_MIN_FILL)
+
+
+@functools.lru_cache(maxsize=1 << 14)       # the eager path asks per layer and call
+def _conv_route(switches, B, H, W, Cin, Cout, k, stride, pad, act, gated, ldy, ldr, wino, wino4, b3, b3_min_rows):
+    Ho, Wo = conv_out_size(H, k, stride, pad[0], pad[2]), conv_out_size(W, k, stride, pad[1], pad[3])
+    route = ()
+    if b3 and not gated and act in (ACT_NONE, ACT_LEAKY) and p3_takes(B, Ho, Wo, Cin, Cout, k, stride, pad):
+        route = ('conv_p3',)
+    if WINOGRAD and _wino_shape(k, stride, pad, gated) and ldy % 4 == 0 and ldr % 4 == 0:
+        # F(4x4) when the grid fills the chip, or when it is the only Winograd form held
+        if wino4 and WINOGRAD4 and (not wino or wino4_items(B, H, W, Cout) >= WINO4_MIN_ITEMS):
+            return route + ('conv_wino4',)
+        if wino:
+            return route + ('conv_wino',)
+    if b3 and (not gated or (k == 1 and act == ACT_NONE)) and b3_takes(B * Ho * Wo, Cin, Cout, k, b3_min_rows, B3_GATED_MIN_COUT if gated else 128):
+        route += ('conv_igemm_b3',)
+    return route + ('conv_igemm',)
+
+
+def conv_forms(Cout, Cin, k, stride, pad, gated, act, among=CONV_FORMS):
+    """The weight forms worth preparing for a layer whose caller may hold the forms `among`: those `conv_route` can name at some batch and
+    map size (the row / channel / grid thresholds left open).  The Winograd forms where their weight transforms cover the shape (F(4x4)
+    from WINO4_MIN_CIN input channels up); split-bf16 planes under split_bf16's Cin rule -- where a Winograd form takes the layer at
+    every size, only up to the channel limit below which conv_p3 comes first."""
+    forms = set()
+    if WINOGRAD and _wino_shape(k, stride, pad, gated) and Cout % 4 == 0:
+        if 'wino' in among and _lib.lib().mydet_wino_weights_floats(Cout, Cin) > 0:
+            forms.add('wino')
+        if 'wino4' in among and WINOGRAD4 and Cin >= WINO4_MIN_CIN and _lib.lib().mydet_wino4_weights_floats(Cout, Cin) > 0:
+            forms.add('wino4')
+    if ('b3' in among and SPLIT_BF16 and (Cin % 16 == 0 or (k == 1 and Cin % 4 == 0)) and (not gated or (k == 1 and act == ACT_NONE))
+            and (not forms or (k == 3 and Cin <= P3_S1_MAX_CIN and act in (ACT_NONE, ACT_LEAKY)))):
+        forms.add('b3')
+    return forms
+
+
+def conv_price(family, B, H, W, Ho, Wo, Cin, Cout, k, residual, interior):
+    """(work, nbytes, fused) of one conv launch for KernelTimer.stop: the direct form's FLOPs -- the algorithmic work of the layer, whatever
+    the kernel -- and input + output + weights (+ residual) read or written once."""
+    b_in, b_out = 4.0 * B * H * W * Cin, 4.0 * B * Ho * Wo * Cout
+    b_rest = 4.0 * (k * k * Cin * Cout) + (b_out if residual else 0.0)
+    # only conv_igemm discounts a block-interior tensor (fused = None: nbytes); the other families never have: a reported metric, kept
+    fused = (0.0 if interior == 'in' else b_in) + (0.0 if interior == 'out' else b_out) + b_rest if family == 'conv_igemm' else None
+    return 2.0 * B * Ho * Wo * Cout * k * k * Cin, b_in + b_out + b_rest, fused
+
+
+# One row per conv kernel family -- a new form is a row here, its predicate in conv_route and its weight rule in conv_forms:
+# family (the KernelTimer name): (C entry point, its argument layout, weight form it reads (None: the OHWI weight),
+#                                 conv_size_refusals family whose limits explain a refusal)
+CONV_LAUNCHERS = {
+    'conv_p3': ('mydet_conv3x3_p3_f32', 'p3', 'b3', None),
+    'conv_wino4': ('mydet_conv2d_wino4_f32', 'wino', 'wino4', 'wino4'),
+    'conv_wino': ('mydet_conv2d_wino_f32', 'wino', 'wino', 'wino'),
+    'conv_igemm_b3': ('mydet_conv2d_igemm_b3_f32', 'igemm', 'b3', None),
+    'conv_igemm': ('mydet_conv2d_igemm_f32', 'igemm', None, 'igemm'),
+}
+
+
+def _conv_launch(route, c, weights, interior=None, may_refuse=False):
+    """Walk `route` through CONV_LAUNCHERS: the first launcher that does not answer MYDET_E_UNSUPP has run the layer (priced for TIMER,
+    any other code raised).  The last one's refusal raises too -- unless may_refuse, then None is returned."""
+    x, ldx, scale, shift, residual, ldr, gate, out, ldy, B, H, W, Cin, Cout, k, stride, pad, Ho, Wo, act = c
+    L = _lib.lib()
+    for family in route:
+        entry, layout, form, sizes = CONV_LAUNCHERS[family]
+        head = (_ptr(x), ldx, _ptr(weights[form]), _ptr(scale), _ptr(shift), _ptr(residual), ldr)
+        if layout != 'p3':      # the scratch buffer: F(4x4)'s transform-domain input, or the K-cut tails' partial tiles
+            ws = wino4_workspace(x.device, L.mydet_wino4_workspace_bytes(B, H, W, Cin, Cout)) if form == 'wino4' else conv_workspace(x.device)
+        t0 = TIMER.start() if TIMER else None
+        if layout == 'igemm':
+            code = getattr(L, entry)(*head, _ptr(gate), _ptr(ws), ws.numel() * 4, _ptr(out), ldy, B, H, W, Cin, Cout, k, k, stride, pad[0], pad[1],
+                                     Ho, Wo, act, _stream())
+        elif layout == 'wino':
+            code = getattr(L, entry)(*head, _ptr(ws), ws.numel() * 4, _ptr(out), ldy, B, H, W, Cin, Cout, act, _stream())
+        else:
+            code = getattr(L, entry)(*head, _ptr(out), ldy, B, H, W, Cin, Cout, stride, act, _stream())
+        if code == -2 and (may_refuse or family != route[-1]):          # MYDET_E_UNSUPP: the next launcher
+            continue
+        if t0:
+            name = f'{family} {Cin}->{Cout} k{k}s{stride} {H}x{W}' if TIMER_DETAIL else family
+            TIMER.stop(name, t0, *conv_price(family, B, H, W, Ho, Wo, Cin, Cout, k, residual is not None, interior))
+        if sizes:
+            _check_conv(code, entry, sizes, B, H, W, Ho, Wo, ldx, ldy, ldr)
+        else:
+            _lib.check(code, entry)
+        return out
+    return None
+
+
+def _conv_call(x, Cout, scale, shift, k, stride, pad, act, residual, out, out_ld, gate):
+    """The tensors of a conv launch in kernel-readable layouts, the output allocated, and its shape: the tuple the launchers unpack."""
+    x, ldx = to_nhwc(x)
+    B, Cin, H, W = x.shape
+    Ho, Wo = conv_out_size(H, k, stride, pad[0], pad[2]), conv_out_size(W, k, stride, pad[1], pad[3])
+    if out is None:
+        out, ldy = empty_nhwc(B, Cout, Ho, Wo, x.device, out_ld)
+    else:
+        ldy = nhwc_ld(out)
+        assert ldy is not None and out.shape == (B, Cout, Ho, Wo)
+    ldr = 0
+    if residual is not None:
+        residual, ldr = to_nhwc(residual)
+        assert residual.shape == out.shape
+    return x, ldx, scale, shift, residual, ldr, gate, out, ldy, B, H, W, Cin, Cout, k, stride, pad, Ho, Wo, act
+
+
 def conv2d(x, w_ohwi, scale, shift, k, stride, pad, act, residual=None, out=None, out_ld=None, gate=None, wino=None,
            wino4=None, interior=None, b3=None, b3_min_rows=None):
     """y = act(conv(x * gate)*scale + shift) + residual.  x logical [B,Cin,H,W]; pad=(top,left,bottom,right);
@@ -442,83 +568,18 @@ def conv2d(x, w_ohwi, scale, shift, k, stride, pad, act, residual=None, out=None
     fused-minimum byte count of KernelTimer; no effect on the launch).
     b3: optional `split_bf16(w_ohwi)`: a layer that stays on the direct implicit GEMM then runs it on the bfloat16 matrix
     instructions with float32-exact split operands (include/mydet.h: mydet_conv2d_igemm_b3_f32; Cin % 16 == 0; with a gate: 1x1 layers
-    without activation), from
-    B3_MIN_ROWS output pixels up (`b3_min_rows` overrides)."""
+    without activation), from B3_MIN_ROWS output pixels up (`b3_min_rows` overrides).  Which launcher runs: `conv_route`."""
     require_gpu(x, 'conv2d')
     if x.shape[1] % 4:
         raise ValueError(f'conv2d: Cin = {x.shape[1]} is not a multiple of 4 (the implicit-GEMM kernel reads channels in '
                          'float4; the 3-channel image layer goes through conv2d_stem)')
-    x, ldx = to_nhwc(x)
-    B, Cin, H, W = x.shape
-    Cout = w_ohwi.shape[0]
-    Ho = conv_out_size(H, k, stride, pad[0], pad[2])
-    Wo = conv_out_size(W, k, stride, pad[1], pad[3])
-    if out is None:
-        out, ldy = empty_nhwc(B, Cout, Ho, Wo, x.device, out_ld)
-    else:
-        ldy = nhwc_ld(out)
-        assert ldy is not None and out.shape == (B, Cout, Ho, Wo)
-    ldr = 0
-    if residual is not None:
-        residual, ldr = to_nhwc(residual)
-        assert residual.shape == out.shape
-    if b3 is not None and gate is None and act in (ACT_NONE, ACT_LEAKY) and p3_takes(B, Ho, Wo, Cin, Cout, k, stride, pad):
-        y = conv3x3_p3(x, b3, scale, shift, stride, act, residual=residual, out=out, cout=Cout)
-        if y is not None:
-            return y
-    if (wino4 is not None and WINOGRAD and WINOGRAD4 and gate is None and k == 3 and stride == 1 and tuple(pad) == (1, 1, 1, 1)
-            and ldy % 4 == 0 and ldr % 4 == 0 and (wino is None or wino4_items(B, H, W, Cout) >= WINO4_MIN_ITEMS)):
-        ws = wino4_workspace(x.device, _lib.lib().mydet_wino4_workspace_bytes(B, H, W, Cin, Cout))
-        t0 = TIMER.start() if TIMER else None
-        code = _lib.lib().mydet_conv2d_wino4_f32(_ptr(x), ldx, _ptr(wino4), _ptr(scale), _ptr(shift), _ptr(residual), ldr,
-                                                 _ptr(ws), ws.numel() * 4, _ptr(out), ldy, B, H, W, Cin, Cout, act, _stream())
-        if t0:      # priced with the direct form's flops: the algorithmic work of the layer
-            name = f'conv_wino4 {Cin}->{Cout} k3s1 {H}x{W}' if TIMER_DETAIL else 'conv_wino4'
-            TIMER.stop(name, t0, 2.0 * B * Ho * Wo * Cout * 9 * Cin,
-                       4.0 * (B * H * W * Cin + B * Ho * Wo * Cout * (2 if residual is not None else 1) + 9 * Cin * Cout))
-        _check_conv(code, 'mydet_conv2d_wino4_f32', 'wino4', B, H, W, Ho, Wo, ldx, ldy, ldr)
-        return out
-    if (wino is not None and WINOGRAD and gate is None and k == 3 and stride == 1 and tuple(pad) == (1, 1, 1, 1)
-            and ldy % 4 == 0 and ldr % 4 == 0):
-        ws = conv_workspace(x.device)
-        t0 = TIMER.start() if TIMER else None
-        code = _lib.lib().mydet_conv2d_wino_f32(_ptr(x), ldx, _ptr(wino), _ptr(scale), _ptr(shift), _ptr(residual), ldr,
-                                                _ptr(ws), ws.numel() * 4, _ptr(out), ldy, B, H, W, Cin, Cout, act,
-                                                _stream())
-        if t0:      # priced with the direct form's flops: the algorithmic work of the layer
-            name = f'conv_wino {Cin}->{Cout} k3s1 {H}x{W}' if TIMER_DETAIL else 'conv_wino'
-            TIMER.stop(name, t0, 2.0 * B * Ho * Wo * Cout * 9 * Cin,
-                       4.0 * (B * H * W * Cin + B * Ho * Wo * Cout * (2 if residual is not None else 1) + 9 * Cin * Cout))
-        _check_conv(code, 'mydet_conv2d_wino_f32', 'wino', B, H, W, Ho, Wo, ldx, ldy, ldr)
-        return out
-    ws = conv_workspace(x.device)
-    if (b3 is not None and b3_takes(B * Ho * Wo, Cin, Cout, k, b3_min_rows, min_cout=B3_GATED_MIN_COUT if gate is not None else 128)
-            and (gate is None or (k == 1 and act == ACT_NONE))):
-        t0 = TIMER.start() if TIMER else None
-        code = _lib.lib().mydet_conv2d_igemm_b3_f32(
-            _ptr(x), ldx, _ptr(b3), _ptr(scale), _ptr(shift), _ptr(residual), ldr, _ptr(gate), _ptr(ws), ws.numel() * 4, _ptr(out), ldy,
-            B, H, W, Cin, Cout, k, k, stride, pad[0], pad[1], Ho, Wo, act, _stream())
-        if code != -2:                              # MYDET_E_UNSUPP: the float32 kernel below
-            if t0:
-                name = f'conv_igemm_b3 {Cin}->{Cout} k{k}s{stride} {H}x{W}' if TIMER_DETAIL else 'conv_igemm_b3'
-                b_in, b_out = 4.0 * B * H * W * Cin, 4.0 * B * Ho * Wo * Cout
-                b_rest = 4.0 * (k * k * Cin * Cout) + (b_out if residual is not None else 0.0)
-                TIMER.stop(name, t0, 2.0 * B * Ho * Wo * Cout * k * k * Cin, b_in + b_out + b_rest)
-            _lib.check(code, 'mydet_conv2d_igemm_b3_f32')
-            return out
-    t0 = TIMER.start() if TIMER else None
-    code = _lib.lib().mydet_conv2d_igemm_f32(
-        _ptr(x), ldx, _ptr(w_ohwi), _ptr(scale), _ptr(shift), _ptr(residual), ldr, _ptr(gate),
-        _ptr(ws), ws.numel() * 4 if ws is not None else 0, _ptr(out), ldy,
-        B, H, W, Cin, Cout, k, k, stride, pad[0], pad[1], Ho, Wo, act, _stream())
-    if t0:
-        name = f'conv_igemm {Cin}->{Cout} k{k}s{stride} {H}x{W}' if TIMER_DETAIL else 'conv_igemm'
-        b_in, b_out = 4.0 * B * H * W * Cin, 4.0 * B * Ho * Wo * Cout
-        b_rest = 4.0 * (k * k * Cin * Cout) + (b_out if residual is not None else 0.0)
-        TIMER.stop(name, t0, 2.0 * B * Ho * Wo * Cout * k * k * Cin, b_in + b_out + b_rest,
-                   (0.0 if interior == 'in' else b_in) + (0.0 if interior == 'out' else b_out) + b_rest)
-    _check_conv(code, 'mydet_conv2d_igemm_f32', 'igemm', B, H, W, Ho, Wo, ldx, ldy, ldr)
-    return out
+    c = _conv_call(x, w_ohwi.shape[0], scale, shift, k, stride, pad, act, residual, out, out_ld, gate)
+    weights = {None: w_ohwi, 'wino': wino, 'wino4': wino4, 'b3': b3}
+    # conv_route, with the forms held as its memoised core takes them
+    ldr, ldy, (B, H, W, Cin, Cout) = c[5], c[8], c[9:14]
+    route = _conv_route(_route_switches(), B, H, W, Cin, Cout, k, stride, tuple(pad), act, gate is not None, ldy, ldr,
+                        wino is not None, wino4 is not None, b3 is not None, b3_min_rows)
+    return _conv_launch(route, c, weights, interior)
 
 
 def conv3x3_p3(x, b3, scale, shift, stride, act, residual=None, out=None, out_ld=None, cout=None):
@@ -526,32 +587,11 @@ def conv3x3_p3(x, b3, scale, shift, stride, act, residual=None, out=None, out_ld
     include/mydet.h: mydet_conv3x3_p3_f32).  b3 = split_bf16(w_ohwi) of the [Cout, 3, 3, Cin] weight; cout = Cout (default: len(shift)).
     Returns None when the kernel does not cover the shape (Cin % 16, activation): the caller then uses conv2d."""
     require_gpu(x, 'conv3x3_p3')
-    x, ldx = to_nhwc(x)
-    B, Cin, H, W = x.shape
+    if x.shape[1] % 16 or stride not in (1, 2) or act not in (ACT_NONE, ACT_LEAKY) or b3 is None:
+        return None
     Cout = int(cout if cout is not None else (shift if shift is not None else scale).shape[0])
-    if Cin % 16 or stride not in (1, 2) or act not in (ACT_NONE, ACT_LEAKY) or b3 is None:
-        return None
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if out is None:
-        out, ldy = empty_nhwc(B, Cout, Ho, Wo, x.device, out_ld)
-    else:
-        ldy = nhwc_ld(out)
-        assert ldy is not None and out.shape == (B, Cout, Ho, Wo)
-    ldr = 0
-    if residual is not None:
-        residual, ldr = to_nhwc(residual)
-        assert residual.shape == out.shape
-    t0 = TIMER.start() if TIMER else None
-    code = _lib.lib().mydet_conv3x3_p3_f32(_ptr(x), ldx, _ptr(b3), _ptr(scale), _ptr(shift), _ptr(residual), ldr, _ptr(out), ldy,
-                                           B, H, W, Cin, Cout, stride, act, _stream())
-    if code == -2:
-        return None
-    if t0:
-        name = f'conv_p3 {Cin}->{Cout} k3s{stride} {H}x{W}' if TIMER_DETAIL else 'conv_p3'
-        b_in, b_out = 4.0 * B * H * W * Cin, 4.0 * B * Ho * Wo * Cout
-        TIMER.stop(name, t0, 2.0 * B * Ho * Wo * Cout * 9 * Cin, b_in + b_out + 4.0 * 9 * Cin * Cout + (b_out if residual is not None else 0.0))
-    _lib.check(code, 'mydet_conv3x3_p3_f32')
-    return out
+    c = _conv_call(x, Cout, scale, shift, 3, stride, (1, 1, 1, 1), act, residual, out, out_ld, None)
+    return _conv_launch(('conv_p3',), c, {'b3': b3}, may_refuse=True)
 
 
 def conv2d_stem(x, w_ohwi, scale, shift, stride, pad, act):
@@ -1050,7 +1090,8 @@ def conv1x1_upcat(a, b, w_ohwi, scale, shift, act):
         return None
     if t0:
         name = f'conv_igemm {C1}^+{C2}->{Cout} k1s1 {H}x{W}' if TIMER_DETAIL else 'conv_igemm'
-        TIMER.stop(name, t0, 2.0 * B * H * W * Cout * (C1 + C2), 4.0 * (B * (Ha * Wa * C1 + H * W * C2) + B * H * W * Cout + (C1 + C2) * Cout))
+        work, nbytes, _ = conv_price('conv_igemm', B, H, W, H, W, C1 + C2, Cout, 1, False, None)
+        TIMER.stop(name, t0, work, nbytes - 4.0 * B * 3 * Ha * Wa * C1)      # `a` is read once at half resolution, not as its 2x copy
     _lib.check(code, 'mydet_conv1x1_upcat_f32')
     return out
 
