@@ -719,6 +719,93 @@ int mydet_track_frames_assoc_f32(const int32_t *records, int64_t stream_stride_w
                                  float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
                                  int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, void *stream);
 
+/* Counting tracks in zones and across lines on the device: one launch behind the tracker launch reads the tracker's dense outputs
+ * (a track keeps its slot for life) and keeps, per stream, who is inside which polygon, who went through which directed line,
+ * for how long, and where the anchors fell.  Every decision is an integer comparison; tests/_zones_ref.py restates the rules and
+ * the kernel (csrc/zones.hip) equals it with ==.  The reference project counts people per frame only (draw_bboxes_on_np prints
+ * `Count: N`); the rules below are this library's.
+ *
+ * Geometry: fixed point, 1/16 pixel.  q(v) = (int32) floorf(min(max(v * 16.0f, -1048576.0f), 1048576.0f)) in float32; the caller
+ *   quantises polygon vertices and line end points with the same formula (mydet_zone_set holds the quantised values).  A track's
+ *   anchor is (cx, cy) of its out_box (MYDET_ZONE_ANCHOR_CENTER) or (cx, cy + h / 2.0f) (MYDET_ZONE_ANCHOR_BOTTOM), in float32;
+ *   a track whose anchor has a non-finite coordinate is unobserved in that frame; p = (q(x), q(y)) otherwise.  Frame sizes up to
+ *   32768; cross products in int64.
+ * Limits: at most MYDET_ZONES_MAX polygons of 3 .. MYDET_ZONE_MAX_VERTICES vertices and at most MYDET_ZONES_MAX directed lines A -> B.
+ * Inside (even-odd, half-open): the edge (a, b) -- consecutive vertices, the last with the first -- toggles when
+ *   (a.y > p.y) != (b.y > p.y) and, with d = b.y - a.y: (p.x - a.x) * d < (b.x - a.x) * (p.y - a.y) for d > 0, > for d < 0.
+ *   A point on the shared edge of two adjacent polygons is inside exactly one of them.
+ * Side of a line: side(p) = sign((B.x - A.x) * (p.y - A.y) - (B.y - A.y) * (p.x - A.x)).
+ * Per stream, per frame, per track slot t, in this order (now = the stream's frame counter, kept in the state):
+ *   1. bad-class frame (out_count < 0): the slot state stands; inside = 0, crossed = 0, dwell = -1 for every slot; the per-frame
+ *      rows are written from the state; now still advances.
+ *   2. close   if the state holds an id for t and the tracker's id of t differs (track gone, or slot reused): for every zone z
+ *      whose bit is set lost[z] += 1, visits[z] += 1, dwell_sum[z] += now - entered[t][z], dwell_max[z] = max(dwell_max[z],
+ *      now - entered[t][z]); then the slot state is cleared (all zero).
+ *   3. observe when id != 0, the class passes the filter (n_classes == 0, or cls is one of classes[0 .. n_classes)), missed == 0
+ *      (coasting = 1: missed >= 0) and the anchor is finite.  A live but unobserved track keeps its state and its dwell goes on.
+ *      Observed, with p the quantised anchor: the slot adopts the id if its state is empty.  Every polygon z: outside -> inside
+ *      gives entries[z] += 1, entered[t][z] = now, bit z set (a track born inside is an entry); inside -> outside gives
+ *      exits[z] += 1, visits[z] += 1, now - entered[t][z] added to dwell_sum[z] and maxed into dwell_max[z], bit z cleared,
+ *      entered[t][z] = 0.  Every line l, s = side(p): if s != 0 and a remembered side exists and differs from s, the segment test
+ *      decides -- A and B must not lie strictly on the same side of the line through the previously observed anchor p' and p:
+ *      sign(cross(p - p', A - p')) * sign(cross(p - p', B - p')) <= 0, cross(u, v) = u.x * v.y - u.y * v.x -- and if it passes
+ *      pos[l] += 1 (s > 0) or neg[l] += 1 (s < 0) and bit 2l (pos) or 2l + 1 (neg) of the slot's `crossed` is set; a track that
+ *      passes around a line's end is not counted.  Whenever s != 0 the remembered side becomes s; with s == 0 it stays (a track
+ *      that sits on the line and goes back is not counted, one that continues is counted once).  Finally p' = p.
+ *   4. outputs (frame o = s*F + f, Z = n_polygons, L = n_lines): out_inside i32 [S*F][MT] the zone bits of the slot, 0 unless
+ *      the slot state's id equals the tracker's id; out_crossed i32 [S*F][MT] the frame's crossing bits; out_dwell i32
+ *      [S*F][MT][Z] now - entered[t][z] where out_inside has bit z, else -1; out_occupancy i32 [S*F][Z] the slots whose state has
+ *      bit z after the frame (unobserved live tracks included); cumulative after the frame out_zone_counts i32 [S*F][Z][4]
+ *      (entries, exits, lost, visits) and out_line_counts i32 [S*F][L][2] (pos, neg).
+ *   5. heat map (heat_h > 0): every observed anchor with missed == 0, 0 <= p.x < 16 img_w and 0 <= p.y < 16 img_h adds 1 to cell
+ *      (p.y * heat_h / (16 img_h), p.x * heat_w / (16 img_w)) (integer division) of heat i32 [S][heat_h][heat_w], which
+ *      accumulates across launches (the caller zeroes it).
+ *   6. now += 1.
+ * Two launches of F1 and F2 frames leave exactly the state and the outputs of one launch of F1 + F2 frames.
+ * One workgroup per stream, thread = track slot, the frames in order.  In: the tracker's out_box [S*F][MT][5], out_id, out_class
+ * (i64), out_missed, out_count of the SAME S, F and max_tracks.  zs: HOST pointer; the struct travels as a kernel argument.
+ * state: S * mydet_zones_state_words(max_tracks) int32 words, 16-byte aligned, caller-owned, persistent between launches and
+ *      initialised (all zero) by mydet_zones_reset.  Per stream, in words, MT = max_tracks:
+ *        [0] now   [1, 4) zero   [4, 68) zone counts [16][4] (entries, exits, lost, visits)   [68, 100) line counts [16][2]
+ *        [100, 116) dwell_max [16]   [116, 148) dwell_sum (int64 [16])
+ *        [148, 148 + 2 MT) id (int64 [MT]; 0 = an empty slot)   then i32 planes [MT] each: inside (zone bits), sides (2 bits per
+ *        line l at 2l: 0 none, 1 positive, 2 negative), px, py (the previously observed anchor)   then entered [16][MT];
+ *        zero padding to a multiple of 4 words.
+ * MYDET_E_BADARG: S, F or max_tracks < 1; a null pointer (out_dwell, out_occupancy, out_zone_counts may be null with no polygon,
+ *      out_line_counts with no line, heat with heat_h == 0); a misaligned pointer; no polygon and no line; more than
+ *      MYDET_ZONES_MAX of either; a vertex count outside 3 .. 16; a coordinate outside +-1048576; a polygon whose doubled area is 0;
+ *      a line with A == B; n_classes outside 0 .. 16; anchor or coasting not 0 or 1; img_h or img_w outside 1 .. 32768; heat_h,
+ *      heat_w not both 0 or both in 1 .. MYDET_ZONE_MAX_HEAT.  MYDET_E_UNSUPP: max_tracks > MYDET_TRACK_MAX_TRACKS
+ *      (mydet_zones_state_words is 0 for such a max_tracks). */
+#define MYDET_ZONES_MAX            16
+#define MYDET_ZONE_MAX_VERTICES    16
+#define MYDET_ZONE_MAX_CLASSES     16
+#define MYDET_ZONE_MAX_HEAT        1024
+#define MYDET_ZONE_MAX_FRAME       32768
+#define MYDET_ZONE_COORD_MAX       1048576  /* |q(v)| <= this */
+#define MYDET_ZONE_ANCHOR_CENTER   0
+#define MYDET_ZONE_ANCHOR_BOTTOM   1
+#define MYDET_ZONES_STATE_HEADER   148      /* words before the slot planes */
+#define MYDET_ZONES_SLOT_WORDS     22       /* words per slot: 2 + 4 + 16 */
+typedef struct mydet_zone_set {
+    int n_polygons, n_lines, n_classes;
+    int anchor;                          /* MYDET_ZONE_ANCHOR_* */
+    int coasting;                        /* 0 | 1 */
+    int img_h, img_w;
+    int heat_h, heat_w;                  /* 0, 0: no heat map */
+    int reserved[3];
+    int n_vertices[MYDET_ZONES_MAX];
+    int polygon[MYDET_ZONES_MAX][MYDET_ZONE_MAX_VERTICES][2];      /* quantised (x, y) */
+    int line[MYDET_ZONES_MAX][4];        /* quantised A.x, A.y, B.x, B.y */
+    int classes[MYDET_ZONE_MAX_CLASSES];
+} mydet_zone_set;
+int64_t mydet_zones_state_words(int max_tracks);
+int mydet_zones_reset(int32_t *state, int S, int max_tracks, void *stream);
+int mydet_zones_frames(const float *box, const int64_t *id, const int64_t *cls, const int32_t *missed, const int32_t *count,
+                       int S, int F, int max_tracks, const mydet_zone_set *zs, int32_t *state, int32_t *heat,
+                       int32_t *out_inside, int32_t *out_crossed, int32_t *out_dwell, int32_t *out_occupancy,
+                       int32_t *out_zone_counts, int32_t *out_line_counts, void *stream);
+
 /* Winograd F(4x4,3x3) form of the same 3x3 stride-1 pad-1 conv + BN + act (+ residual) as mydet_conv2d_wino_f32
  * (4x fewer multiplies than the direct form; used for the deep layers with chip-filling grids).  `u` = the
  * transform-domain weights made by mydet_wino4_weights_f32 from the OHWI weight (mydet_wino4_weights_floats(Cout, Cin)

@@ -88,6 +88,10 @@ SIGNATURES = {
     'mydet_track_frames_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
     'mydet_track_frames_assoc_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                      c_ptr, c_ptr],
+    'mydet_zones_state_words': [c_int],
+    'mydet_zones_reset': [c_ptr, c_int, c_int, c_ptr],
+    'mydet_zones_frames': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                           c_ptr],
     'mydet_mbconv_tiles': [c_int, c_int, c_int],
     'mydet_mbconv_expand_dw_f32': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64] + [c_int] * 11 + [c_ptr, c_int, c_ptr, c_ptr],
     'mydet_sepconv_nodes_f32': [c_int, c_ptr, c_int, c_int, c_ptr],
@@ -137,7 +141,7 @@ SIGNATURES = {
 
 
 RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems',
-               'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words', 'mydet_mot_scratch_bytes'}
+               'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words', 'mydet_mot_scratch_bytes', 'mydet_zones_state_words'}
 
 # detection record layout (MYDET_REC_* of include/mydet.h), in int32 words
 REC_TOPK = 512
@@ -163,6 +167,10 @@ TRACK_MAX_TRACKS = 512
 TRACK_STATE_HEADER, TRACK_SLOT_WORDS = 8, 31
 TRACK_MATCH_IOU, TRACK_MATCH_ROTATED = 0, 1
 TRACK_ASSIGN_GREEDY, TRACK_ASSIGN_OPTIMAL = 0, 1
+# zones and lines (mydet_zones_frames): MYDET_ZONE* of include/mydet.h
+ZONES_MAX, ZONE_MAX_VERTICES, ZONE_MAX_CLASSES, ZONE_MAX_HEAT, ZONE_MAX_FRAME, ZONE_COORD_MAX = 16, 16, 16, 1024, 32768, 1 << 20
+ZONE_ANCHOR_CENTER, ZONE_ANCHOR_BOTTOM = 0, 1
+ZONES_STATE_HEADER, ZONES_SLOT_WORDS = 148, 22
 # overlay renderer (mydet_draw_boxes_*): MYDET_DRAW_* of include/mydet.h
 DRAW_MAX_BOXES, DRAW_MAX_THICKNESS, DRAW_MAX_GLYPHS, DRAW_NAME_BYTES = 512, 64, 33, 16
 DRAW_COLOR_CLASS, DRAW_COLOR_ID, DRAW_COLOR_FIXED = 0, 1, 2
@@ -248,6 +256,13 @@ class TrackAssoc(ctypes.Structure):
     """mydet_track_assoc (include/mydet.h): the association mode of mydet_track_frames_assoc_f32."""
     _fields_ = [('assign', c_int), ('bands', c_int), ('high_thres', c_f32), ('low_thres', c_f32), ('low_match_thres', c_f32),
                 ('reserved', c_int * 3)]
+
+
+class ZoneSet(ctypes.Structure):
+    """mydet_zone_set (include/mydet.h): quantised polygons and lines, the anchor, the class filter, the heat grid."""
+    _fields_ = [('n_polygons', c_int), ('n_lines', c_int), ('n_classes', c_int), ('anchor', c_int), ('coasting', c_int),
+                ('img_h', c_int), ('img_w', c_int), ('heat_h', c_int), ('heat_w', c_int), ('reserved', c_int * 3),
+                ('n_vertices', c_int * 16), ('polygon', ((c_int * 2) * 16) * 16), ('line', (c_int * 4) * 16), ('classes', c_int * 16)]
 
 
 class DrawList(ctypes.Structure):

@@ -3,9 +3,11 @@ argument of its tiled detection on large frames, `Tracker`, the argument that tu
 `Draw`, the settings of its annotate_frames methods, `Chips`, the settings of its crop_frames methods, `Nms`, how its
 post-process suppresses (class-agnostic, Soft-NMS, box merging), `Augment`, its test-time augmentation (mirrored and rescaled
 views fused on the device), `Evaluator`, which scores what it returns against ground
-truth, and `TrackEvaluator`, which scores its tracks against ground-truth identities."""
+truth, `TrackEvaluator`, which scores its tracks against ground-truth identities, and `Zones`, which counts its tracks in
+polygons and across lines on the device."""
 from .detection import Augment, Chips, Detector, Draw, Nms, Tiles
 from .evaluation import Evaluator, TrackEvaluator
 from .tracking import Tracker
+from .zones import Zones
 
-__all__ = ['Augment', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Tiles', 'TrackEvaluator', 'Tracker']
+__all__ = ['Augment', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Tiles', 'TrackEvaluator', 'Tracker', 'Zones']

@@ -737,11 +737,14 @@ class Detector():
         draw or crop launch before any host synchronisation; a tracked call hands it to the tracker (_tracked_objects) and
         paints or cuts out the returned tracks."""
         tracker, coasting = self._pop_tracker(kwargs)
+        zones = self._pop_zones(kwargs, tracker)
         sources = make_sources()
         used = draw is not None or chips is not None
         if tracker is not None:
             src = self._one_source(sources, 'tracked')
             tracker.check_call(src.n, src.hw, self.model.bb_format)
+            if zones is not None:
+                zones.check_call(tracker, src.hw, self.model.bb_format)
         elif used:
             src, = sources                                           # a plain call alone takes any number of sizes, none included
         call = self._call_settings(kwargs, whole=tracker is not None or used)
@@ -753,7 +756,7 @@ class Detector():
             call = self._call_settings(dict(kwargs, conf_thres=min(conf_thres, tracker.low_thres)), whole=True)
         records = self._source_records(sources, call)
         if tracker is not None:
-            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres)
+            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres, zones)
         elif used:
             records = list(records)
             (idxs, found), = records                                 # one frame size: one group, in frame order
@@ -782,7 +785,12 @@ class Detector():
         the consecutive frames s*F .. s*F + F-1).  One more launch on the device (include/mydet.h: mydet_track_frames_f32)
         associates the call's detections with the tracker's tracks, and each ImageObjects then holds the tracks matched or born
         in its frame -- bboxes the Kalman-filtered state, scores the track scores, cats the classes, obj_ids (int64) the
-        persistent identities -- and, with coasting=True, the live tracks without a detection in that frame as well."""
+        persistent identities -- and, with coasting=True, the live tracks without a detection in that frame as well.
+        zones: None, or a mydetection_amd.api.Zones (with tracker= only: ValueError otherwise).  One more launch right behind the
+        tracker's (include/mydet.h: mydet_zones_frames) counts the tracks in its polygons and across its lines; the objects are
+        bit for bit those of the call without zones= and carry zone_mask (int32: bit z = inside polygon z) and line_events
+        (int32: bit 2l / 2l+1 = went through line l in its positive / negative direction in this frame); zones.last,
+        zones.counts() and zones.heat have the rest.  Every frame method that takes tracker= takes zones=."""
         return self._detect(lambda: self._rgb_sources(frames), kwargs)
 
     @staticmethod
@@ -795,14 +803,27 @@ class Detector():
         return tracker, coasting
 
     @staticmethod
+    def _pop_zones(kwargs, tracker):
+        """zones out of a frame method's keyword arguments: a TypeError for anything but a Zones, a ValueError without a
+        tracker (the zones count tracks), both before any launch."""
+        from .zones import Zones
+        zones = kwargs.pop('zones', None)
+        if zones is not None and not isinstance(zones, Zones):
+            raise TypeError(f'zones: a mydetection_amd.api.Zones (or None) expected, got {type(zones).__name__}')
+        if zones is not None and tracker is None:
+            raise ValueError('zones: zones= counts tracks and needs tracker= in the same call')
+        return zones
+
+    @staticmethod
     def _no_tracker(kwargs, what):
-        if 'tracker' in kwargs or 'coasting' in kwargs:
+        if 'tracker' in kwargs or 'coasting' in kwargs or 'zones' in kwargs:
             raise TypeError(f'{what}: track ids in the json rows are not built; use the predict_frames form with tracker=')
 
-    def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres):
+    def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres, zones=None):
         """The tracked form of _objects_of_records: one eager tracker launch on the call's records (frame coordinates, one
         buffer), then per frame the ImageObjects of the tracks with missed == 0 (coasting: of every live track).  Two host
-        synchronisations: the frame counts, and the indices of the selected slots."""
+        synchronisations: the frame counts, and the indices of the selected slots.  zones: a Zones whose launch follows the
+        tracker's at once (no synchronisation in between); the objects then carry zone_mask and line_events."""
         from ..utils.structures import ImageObjects
         records = list(records)
         assert len(records) == 1, 'one frame size gives one network input size'
@@ -813,6 +834,7 @@ class Detector():
         state = tracker.bind(frame_hw, width, rec['records'].device)
         params = tracker.params(frame_hw, tracker.resolve_match(self.model.bb_format), conf_thres)
         out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks, assoc=tracker.assoc(conf_thres))
+        zout = None if zones is None else zones.run(out, tracker, frame_hw)
         B, mt = len(idxs), tracker.max_tracks
         missed = out['missed'].view(B, mt)
         keep = (missed >= 0) if coasting else (missed == 0)
@@ -821,11 +843,14 @@ class Detector():
         per_frame = torch.bincount(sel[:, 0], minlength=B).cpu().tolist()
         box, score, cls, ids = out['box'].view(B * mt, 5), out['score'].view(-1), out['cls'].view(-1), out['id'].view(-1)
         flat = sel[:, 0] * mt + sel[:, 1]
+        inside, crossed = (None, None) if zout is None else (zout['inside'].view(-1), zout['crossed'].view(-1))
         objs, lo = [], 0
         for k in per_frame:
             rows = flat[lo:lo + k]
             lo += k
-            objs.append(ImageObjects(box[rows][:, :width], cls[rows], None, score[rows], self.model.bb_format, hw, obj_ids=ids[rows]))
+            objs.append(ImageObjects(box[rows][:, :width], cls[rows], None, score[rows], self.model.bb_format, hw, obj_ids=ids[rows],
+                                     zone_mask=None if inside is None else inside[rows],
+                                     line_events=None if crossed is None else crossed[rows]))
         return objs
 
     def _objects_of_records(self, records):

@@ -1779,6 +1779,201 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     return out
 
 
+ZONE_ANCHORS = {'center': _lib.ZONE_ANCHOR_CENTER, 'bottom': _lib.ZONE_ANCHOR_BOTTOM}
+
+
+def zone_quantise(v):
+    """q(v) of include/mydet.h (mydet_zones_frames) in numpy float32: 1/16 pixel, floor, clamped to +-2^20."""
+    v = np.asarray(v, dtype=np.float32)
+    lo, hi = np.float32(-_lib.ZONE_COORD_MAX), np.float32(_lib.ZONE_COORD_MAX)
+    return np.floor(np.minimum(np.maximum(v * np.float32(16.0), lo), hi)).astype(np.int32)
+
+
+def _zone_points(what, pts, n_lo, n_hi):
+    try:
+        with np.errstate(over='ignore'):                             # too large for float32: an infinity, refused below
+            a = np.asarray(pts, dtype=np.float32)
+    except (TypeError, ValueError):
+        a = None
+    if a is None or a.ndim != 2 or a.shape[1] != 2 or not n_lo <= a.shape[0] <= n_hi:
+        raise ValueError(f'zone_set: {what} is {n_lo} .. {n_hi} points (x, y), got {pts!r}' if n_lo != n_hi else
+                         f'zone_set: {what} is {n_lo} points (x, y), got {pts!r}')
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f'zone_set: {what} has a non-finite coordinate: {pts!r}')
+    return zone_quantise(a)
+
+
+def zone_set(img_hw, polygons=(), lines=(), anchor='center', classes=None, coasting=False, heat=None):
+    """The parameter struct of mydet_zones_frames (a _lib.ZoneSet; include/mydet.h has the rules).  img_hw: the frame size
+    (H, W), each 1 .. 32768.  polygons: at most 16 sequences of 3 .. 16 points (x, y) in frame pixels; lines: at most 16 pairs
+    ((ax, ay), (bx, by)), directed A -> B.  Coordinates are quantised to 1/16 pixel here, by the formula the kernel applies to
+    the anchors.  anchor: 'center' (cx, cy) or 'bottom' (cx, cy + h/2).  classes: None, or 1 .. 16 class indices to count.
+    coasting: also observe live tracks without a detection in the frame, at their predicted boxes.  heat: None, or (gh, gw),
+    each 1 .. 1024.  ValueError for anything out of range, a polygon of zero area or a line of zero length after quantisation,
+    non-finite coordinates, or neither polygons nor lines; touches no device."""
+    if not isinstance(anchor, str) or anchor not in ZONE_ANCHORS:
+        raise ValueError(f'zone_set: anchor {anchor!r} is not one of {sorted(ZONE_ANCHORS)}')
+    try:
+        h, w = (int(v) for v in img_hw)
+    except (TypeError, ValueError):
+        raise ValueError(f'zone_set: a frame size (H, W) expected, got {img_hw!r}') from None
+    if not (1 <= h <= _lib.ZONE_MAX_FRAME and 1 <= w <= _lib.ZONE_MAX_FRAME):
+        raise ValueError(f'zone_set: a frame size (H, W) of 1 .. {_lib.ZONE_MAX_FRAME} each expected, got {img_hw!r}')
+    polygons, lines = list(polygons), list(lines)
+    if not polygons and not lines:
+        raise ValueError('zone_set: neither polygons nor lines given')
+    if len(polygons) > _lib.ZONES_MAX or len(lines) > _lib.ZONES_MAX:
+        raise ValueError(f'zone_set: at most {_lib.ZONES_MAX} polygons and {_lib.ZONES_MAX} lines, got {len(polygons)} and {len(lines)}')
+    z = _lib.ZoneSet()
+    z.n_polygons, z.n_lines, z.anchor, z.coasting, z.img_h, z.img_w = len(polygons), len(lines), ZONE_ANCHORS[anchor], int(bool(coasting)), h, w
+    for p, poly in enumerate(polygons):
+        q = _zone_points(f'polygon {p}', poly, 3, _lib.ZONE_MAX_VERTICES).astype(np.int64)
+        nxt = np.roll(q, -1, axis=0)
+        if int(np.sum(q[:, 0] * nxt[:, 1] - nxt[:, 0] * q[:, 1])) == 0:
+            raise ValueError(f'zone_set: polygon {p} has no area at 1/16 pixel: {poly!r}')
+        z.n_vertices[p] = len(q)
+        for i, (x, y) in enumerate(q.tolist()):
+            z.polygon[p][i][0], z.polygon[p][i][1] = x, y
+    for l, line in enumerate(lines):
+        q = _zone_points(f'line {l}', line, 2, 2)
+        if np.array_equal(q[0], q[1]):
+            raise ValueError(f'zone_set: line {l} has no length at 1/16 pixel: {line!r}')
+        z.line[l][:] = q.reshape(-1).tolist()
+    if classes is not None:
+        cl = [int(c) for c in classes]
+        if not 1 <= len(cl) <= _lib.ZONE_MAX_CLASSES or any(c < 0 or c >= 1 << 31 for c in cl):
+            raise ValueError(f'zone_set: classes is None or 1 .. {_lib.ZONE_MAX_CLASSES} class indices, got {classes!r}')
+        z.n_classes = len(cl)
+        z.classes[:len(cl)] = cl
+    if heat is not None:
+        try:
+            gh, gw = (int(v) for v in heat)
+        except (TypeError, ValueError):
+            raise ValueError(f'zone_set: heat is None or (gh, gw), got {heat!r}') from None
+        if not (1 <= gh <= _lib.ZONE_MAX_HEAT and 1 <= gw <= _lib.ZONE_MAX_HEAT):
+            raise ValueError(f'zone_set: heat (gh, gw) of 1 .. {_lib.ZONE_MAX_HEAT} each expected, got {heat!r}')
+        z.heat_h, z.heat_w = gh, gw
+    return z
+
+
+def zones_state_words(max_tracks):
+    """int32 words of one stream's zone state (include/mydet.h: mydet_zones_state_words); host arithmetic only."""
+    max_tracks = int(max_tracks)
+    if not 1 <= max_tracks <= _lib.TRACK_MAX_TRACKS:
+        raise ValueError(f'zones: 1 <= max_tracks <= {_lib.TRACK_MAX_TRACKS} expected, got {max_tracks}')
+    return (_lib.ZONES_STATE_HEADER + _lib.ZONES_SLOT_WORDS * max_tracks + 3) // 4 * 4
+
+
+def zones_state(streams, max_tracks, device):
+    """A reset zone state: int32 [streams, zones_state_words(max_tracks)] (include/mydet.h has the layout)."""
+    words = zones_state_words(max_tracks)
+    streams = int(streams)
+    if streams < 1:
+        raise ValueError(f'zones: streams >= 1 expected, got {streams}')
+    state = torch.empty((streams, words), dtype=torch.int32, device=device)
+    return zones_reset_(state, max_tracks)
+
+
+def _check_zones_state(state, max_tracks, what):
+    words = zones_state_words(max_tracks)
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != words or not state.is_contiguous():
+        got = f'{state.dtype} {tuple(state.shape)}' if isinstance(state, torch.Tensor) else type(state).__name__
+        raise ValueError(f'{what}: a contiguous int32 state [streams, {words}] for max_tracks = {max_tracks} expected, got {got}')
+    require_gpu(state, what)
+    return words
+
+
+def zones_reset_(state, max_tracks):
+    """Reset a zone state in place (mydet_zones_reset): nobody inside, every counter and the frame counter 0."""
+    _check_zones_state(state, max_tracks, 'zones_reset_')
+    code = _lib.lib().mydet_zones_reset(_ptr(state), state.shape[0], int(max_tracks), _stream())
+    _lib.check(code, 'mydet_zones_reset')
+    return state
+
+
+def zones_heat(streams, zone_set, device):
+    """A zeroed heat map int32 [streams, gh, gw] for a zone_set with heat=(gh, gw)."""
+    if not isinstance(zone_set, _lib.ZoneSet) or zone_set.heat_h < 1:
+        raise ValueError('zones_heat: a zone_set(..., heat=(gh, gw)) expected')
+    return torch.zeros((int(streams), zone_set.heat_h, zone_set.heat_w), dtype=torch.int32, device=device)
+
+
+def zones_state_views(state, max_tracks=None):
+    """Field views of a zone state int32 [S, words] (include/mydet.h: mydet_zones_frames), nothing copied: a dict of now int32
+    [S], zone_counts int32 [S,16,4] (entries, exits, lost, visits), line_counts int32 [S,16,2] (pos, neg), dwell_max int32
+    [S,16], dwell_sum int64 [S,16], id int64 [S,MT] (0 = an empty slot), inside, sides, px, py int32 [S,MT], entered int32
+    [S,16,MT].  max_tracks: taken from the row length when None.  Works on any device (tests read a host copy)."""
+    if state.dtype != torch.int32 or state.dim() != 2 or not state.is_contiguous():
+        raise ValueError(f'zones_state_views: a contiguous int32 state [streams, words] expected, got {state.dtype} {tuple(state.shape)}')
+    S, words = state.shape
+    if max_tracks is None:
+        max_tracks = (words - _lib.ZONES_STATE_HEADER) // _lib.ZONES_SLOT_WORDS
+    mt = int(max_tracks)
+    if words != zones_state_words(mt):
+        raise ValueError(f'zones_state_views: {words} words per stream is not the state of max_tracks = {mt}')
+    Z = _lib.ZONES_MAX
+    out = {'now': state[:, 0], 'zone_counts': state[:, 4:4 + 4 * Z].view(S, Z, 4), 'line_counts': state[:, 4 + 4 * Z:4 + 6 * Z].view(S, Z, 2),
+           'dwell_max': state[:, 4 + 6 * Z:4 + 7 * Z], 'dwell_sum': state[:, 4 + 7 * Z:4 + 9 * Z].view(torch.int64)}
+    o = _lib.ZONES_STATE_HEADER
+    out['id'] = state[:, o:o + 2 * mt].view(torch.int64)
+    o += 2 * mt
+    for name in ('inside', 'sides', 'px', 'py'):
+        out[name] = state[:, o:o + mt]
+        o += mt
+    out['entered'] = state[:, o:o + Z * mt].view(S, Z, mt)
+    return out
+
+
+def zones_frames(track_out, state, zone_set, heat=None, out=None):
+    """Count the tracks of S streams x F frames in zones and across lines in ONE launch (include/mydet.h: mydet_zones_frames,
+    where the rules are).  track_out: the dict ops.track_frames returned (box [S,F,MT,5], id, cls, missed, count are read).
+    state: int32 [S, zones_state_words(MT)] from zones_state, updated in place.  zone_set: zone_set(...).  heat: the int32
+    [S,gh,gw] buffer of a zone_set with heat= (zones_heat), added to in place; None otherwise.  Returns a dict of int32 device
+    tensors, Z polygons and L lines: inside, crossed [S,F,MT], dwell [S,F,MT,Z], occupancy [S,F,Z], zone_counts [S,F,Z,4]
+    (entries, exits, lost, visits; cumulative), line_counts [S,F,L,2] (pos, neg; cumulative).  out: such a dict to write into."""
+    if not isinstance(zone_set, _lib.ZoneSet):
+        raise TypeError(f'zones_frames: zone_set is a _lib.ZoneSet (ops.zone_set), got {type(zone_set).__name__}')
+    box = track_out['box']
+    if not isinstance(box, torch.Tensor) or box.dim() != 4 or box.shape[3] != 5:
+        raise ValueError('zones_frames: track_out is the dict of ops.track_frames (box [S,F,MT,5], id, cls, missed, count)')
+    S, F, mt, _ = box.shape
+    dev = box.device
+    shapes = {'box': ((S, F, mt, 5), torch.float32), 'id': ((S, F, mt), torch.int64), 'cls': ((S, F, mt), torch.int64),
+              'missed': ((S, F, mt), torch.int32), 'count': ((S, F), torch.int32)}
+    for k, (shape, dt) in shapes.items():
+        t = track_out[k]
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f'zones_frames: track_out[{k!r}] must be a contiguous {dt} tensor {shape} on {dev}')
+    _check_zones_state(state, mt, 'zones_frames')
+    if state.shape[0] != S or state.device != dev:
+        raise ValueError(f'zones_frames: a state of {S} streams on {dev} expected, got {state.shape[0]} on {state.device}')
+    require_gpu(box, 'zones_frames')
+    if zone_set.heat_h > 0:
+        want = (S, zone_set.heat_h, zone_set.heat_w)
+        if not isinstance(heat, torch.Tensor) or tuple(heat.shape) != want or heat.dtype != torch.int32 or heat.device != dev or not heat.is_contiguous():
+            raise ValueError(f'zones_frames: heat must be a contiguous int32 tensor {want} on {dev} (ops.zones_heat)')
+    elif heat is not None:
+        raise ValueError('zones_frames: heat given, but the zone_set has no heat grid')
+    Z, L = zone_set.n_polygons, zone_set.n_lines
+    oshapes = {'inside': (S, F, mt), 'crossed': (S, F, mt), 'dwell': (S, F, mt, Z), 'occupancy': (S, F, Z), 'zone_counts': (S, F, Z, 4),
+               'line_counts': (S, F, L, 2)}
+    if out is None:
+        out = {k: torch.empty(shape, dtype=torch.int32, device=dev) for k, shape in oshapes.items()}
+    for k, shape in oshapes.items():
+        t = out[k]
+        if tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f'zones_frames: out[{k!r}] must be a contiguous int32 tensor {shape} on {dev}')
+    t0 = TIMER.start() if TIMER else None
+    code = _lib.lib().mydet_zones_frames(_ptr(box), _ptr(track_out['id']), _ptr(track_out['cls']), _ptr(track_out['missed']),
+                                         _ptr(track_out['count']), S, F, mt, ctypes.byref(zone_set), _ptr(state), _ptr(heat),
+                                         _ptr(out['inside']), _ptr(out['crossed']), _ptr(out['dwell']), _ptr(out['occupancy']),
+                                         _ptr(out['zone_counts']), _ptr(out['line_counts']), _stream())
+    if t0:
+        TIMER.stop('zones_frames', t0, float(S * F))
+    _lib.check(code, 'mydet_zones_frames')
+    return out
+
+
 def bboxes_iou(a, b, xyxy=False):
     require_gpu(a, 'bboxes_iou')
     a, b = a.contiguous().float(), b.contiguous().float()

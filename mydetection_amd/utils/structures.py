@@ -28,9 +28,16 @@ class ImageObjects():
         bb_format (optional): 'cxcywh', or 'cxcywhd' (rotated boxes: cx, cy, w, h, angle in degrees)
         img_hw: tuple-like, image (height, width)
         obj_ids (optional): 1-d tensor, torch.int64, persistent track identities (Detector.predict_frames(tracker=)); else None
+        zone_mask, line_events (optional): 1-d tensors, torch.int32, per object: the polygons it is inside (bit z) and the lines
+            it went through in this frame (bit 2l positive, 2l+1 negative) (Detector.predict_frames(tracker=, zones=)); else None
     '''
-    def __init__(self, bboxes, cats, masks=None, scores=None, bb_format='cxcywh', img_hw=None, obj_ids=None):
+    _PER_OBJECT = ('obj_ids', 'zone_mask', 'line_events')            # optional 1-d fields that follow every selection of rows
+
+    def __init__(self, bboxes, cats, masks=None, scores=None, bb_format='cxcywh', img_hw=None, obj_ids=None, zone_mask=None,
+                 line_events=None):
         self.obj_ids: torch.LongTensor = obj_ids
+        self.zone_mask: torch.IntTensor = zone_mask
+        self.line_events: torch.IntTensor = line_events
         self.bboxes: torch.FloatTensor = bboxes
         self.cats: torch.LongTensor = cats
         self.masks: torch.BoolTensor = masks
@@ -46,7 +53,15 @@ class ImageObjects():
         c = self.cats[idx]
         m = self.masks[idx, :, :] if self.masks is not None else None
         s = self.scores[idx] if self.scores is not None else None
-        return ImageObjects(b, c, m, s, self._bb_format, self.img_hw, None if self.obj_ids is None else self.obj_ids[idx])
+        return ImageObjects(b, c, m, s, self._bb_format, self.img_hw, **self._per_object(lambda t: t[idx]))
+
+    def _per_object(self, fn):
+        """fn applied to each optional per-object field that is set, as keyword arguments of the constructor."""
+        return {k: None if getattr(self, k) is None else fn(getattr(self, k)) for k in self._PER_OBJECT}
+
+    def _per_object_(self, fn):
+        for k, v in self._per_object(fn).items():
+            setattr(self, k, v)
 
     def __len__(self):
         return self.bboxes.shape[0]
@@ -57,7 +72,7 @@ class ImageObjects():
         self.cats = self.cats.cpu()
         self.scores = self.scores.cpu() if self.scores is not None else None
         self.masks = self.masks.cpu() if self.masks is not None else None
-        self.obj_ids = self.obj_ids.cpu() if self.obj_ids is not None else None
+        self._per_object_(lambda t: t.cpu())
 
     def cuda_(self, device='cuda'):
         '''Move all attributes to the GPU in-place (the kernels need them there)'''
@@ -65,7 +80,7 @@ class ImageObjects():
         self.cats = self.cats.to(device)
         self.scores = self.scores.to(device) if self.scores is not None else None
         self.masks = self.masks.to(device) if self.masks is not None else None
-        self.obj_ids = self.obj_ids.to(device) if self.obj_ids is not None else None
+        self._per_object_(lambda t: t.to(device))
 
     def sort_by_score_(self, descending=True):
         '''Sort the bounding boxes by scores in-place'''
@@ -75,8 +90,7 @@ class ImageObjects():
         self.bboxes = self.bboxes[idxs, :]
         self.cats = self.cats[idxs]
         self.scores = self.scores[idxs]
-        if self.obj_ids is not None:
-            self.obj_ids = self.obj_ids[idxs]
+        self._per_object_(lambda t: t[idxs])
 
     def category_filter_(self, categories) -> None:
         '''Keep the objects in the given category set and discard others in-place.'''
@@ -88,8 +102,7 @@ class ImageObjects():
         self.cats = self.cats[keep_mask]
         if self.scores is not None:
             self.scores = self.scores[keep_mask]
-        if self.obj_ids is not None:
-            self.obj_ids = self.obj_ids[keep_mask]
+        self._per_object_(lambda t: t[keep_mask])
 
     # ------------------------------------------------------------------ post-processing
     def _device_fields(self):
@@ -194,6 +207,9 @@ class ImageObjects():
         if self.scores is not None:
             assert self.scores.shape[0] == self.bboxes.shape[0]
         assert self.img_hw is None or len(self.img_hw) == 2
+        for k in ('zone_mask', 'line_events'):
+            t = getattr(self, k)
+            assert t is None or (t.dtype == torch.int32 and t.dim() == 1 and t.shape[0] == self.bboxes.shape[0]), k
 
     def to_json(self, img_id, eval_type='x1y1wh', catIdx2id=None) -> list:
         '''
