@@ -12,6 +12,16 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static inline int mydet_launch_status() { return (int)hipGetLastError(); }
 
+// 16-byte alignment of an operand that is read or written with 16-byte accesses (entry-point checks)
+static inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// Grid of a 256-thread grid-stride kernel over `total` items: one thread each, at most 32 workgroups per CU of a 256-CU chip
+static inline unsigned grid_for(int64_t total) {
+    int64_t blocks = (total + 255) / 256;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
 // Compute units of the current device (256 on MI355X), read once.
 static inline int mydet_cu_count() {
     static int n = 0;

@@ -21,84 +21,19 @@
 // Each lane reads 4 consecutive k of its row with one ds_read_b128; lane half h owns
 // k = 8*kc + 4*h + t at MFMA step t -- a permutation of k applied to A and B alike.
 //
+// The frame the three kernels of this file share -- tile origin, row addresses, K range and tap cursor, K loop, end of tile --
+// is igemm_tile.h; a kernel body here is its staging layout, its compute lambda and calls into that header.
+//
 // Replaces the ATen conv2d/batch_norm/leaky_relu chain under models/modules.py:94-95,
 // the residual add of models/modules.py:69-73 and the head convs models/rpns.py:24-25.
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
+#include "igemm_tile.h"
 #include "split_bf16.h"
 
 namespace {
-
-constexpr unsigned OOB = 0xFFFFFFFFu;
-
-struct ConvArgs {
-    const float *x, *w, *scale, *shift, *res, *gate;
-    float *y;
-    int64_t ldx, ldr, ldy;
-    int B, H, W, Cin, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo, act;
-    int M, K, ntiles, nblk;
-    int tile0, splits;        // split-K tail: first logical tile of this launch, K slices per tile (1 = whole K)
-    float *ws;                // split-K partial accumulators
-    size_t ws_bytes;
-    // CAT (1x1 only): channels [0, C1) of A come from x1 = a [B, H/2, W/2, ldx1] map read through nearest 2x upsampling, the
-    // remaining Cin - C1 from x -- conv1x1(cat((up2x(x1), x), 1)) without the concatenated tensor
-    const float *x1;
-    int64_t ldx1;
-    int C1;
-    // split-bf16 form (conv_igemm_b3_kernel): the weights as three bfloat16 planes [3][Cout][K] with w = p0 + p1 + p2
-    const unsigned short *wsplit;
-};
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
-}
-
-// Epilogue: lane = output channel, register = output pixel.  Stores (and residual loads) are
-// buffer ops whose per-lane offset is fixed and whose row term is a scalar: one v_add per element.
-// Ragged tiles route out-of-range elements to offset 0xFFFFFFFF, which the range check drops.
-template <int ACT, bool RES, bool FULL, int TM, int TN>
-__device__ __forceinline__ void epilogue(const ConvArgs &p, f32x16 (&acc)[TM][TN], int m_base, int n_base,
-                                         int fr, int fh, const float (&pscl)[TN], const float (&psft)[TN]) {
-    const __amdgpu_buffer_rsrc_t yr = mydet_rsrc(p.y, (int64_t)p.M * p.ldy * 4);
-    const __amdgpu_buffer_rsrc_t rr = mydet_rsrc(RES ? p.res : p.y, (int64_t)p.M * (RES ? p.ldr : p.ldy) * 4);
-    const unsigned ldy4 = (unsigned)p.ldy * 4u, ldr4 = (unsigned)p.ldr * 4u;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n_base + j * 32 + fr;
-        const bool nok = FULL || n < p.Cout;
-        const float scl = pscl[j], sft = psft[j];      // requested before the K loop (a round trip per workgroup otherwise)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int mrow = m_base + i * 32 + 4 * fh;          // + (r&3) + 8*(r>>2)
-            const unsigned ybase = (unsigned)mrow * ldy4 + (unsigned)n * 4u;
-            const unsigned rbase = (unsigned)mrow * ldr4 + (unsigned)n * 4u;
-            float rv[16];
-            if (RES) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int dr = (r & 3) + 8 * (r >> 2);
-                    const bool ok = FULL || (nok && mrow + dr < p.M);
-                    rv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                          rr, ok ? rbase + (unsigned)dr * ldr4 : OOB, 0, 0));
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int dr = (r & 3) + 8 * (r >> 2);
-                float v = acc[i][j][r] * scl + sft;
-                if (ACT == MYDET_ACT_LEAKY) v = v > 0.0f ? v : v * 0.1f;
-                if (ACT == MYDET_ACT_SWISH) v = v * mydet_sigmoid_fast(v);
-                if (RES) v += rv[r];
-                const bool ok = FULL || (nok && mrow + dr < p.M);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yr,
-                                                      ok ? ybase + (unsigned)dr * ldy4 : OOB, 0, 0);
-            }
-        }
-    }
-}
 
 template <int BM, int BN, int WM, int WN, int BK, bool CIN32, int ACT, bool RES, bool GATE, bool SPLIT = false, bool CAT = false>
 __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs p) {
@@ -118,16 +53,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
     float *Bs = smem + 2 * BM * LDS_LD;             // [2][BN][LDS_LD]
 
     const int tid = threadIdx.x;
-    // SPLIT: block = (tail tile, K slice); otherwise one block per tile, XCD-grouped
-    const int lid = SPLIT ? p.tile0 + (int)blockIdx.x / p.splits : mydet_xcd_remap(blockIdx.x, p.nblk);
-    const int m0 = (lid / p.ntiles) * BM;
-    const int n0 = (lid % p.ntiles) * BN;
-
-    // ---- descriptors: A window starts at the image holding the tile's first row
-    const int hwo = p.Ho * p.Wo;
-    const int b0 = m0 / hwo;
-    const int64_t img = (int64_t)p.H * p.W * p.ldx;
-    const __amdgpu_buffer_rsrc_t xr = mydet_rsrc(p.x + b0 * img, (p.B - b0) * img * 4);
+    const IgTile t = ig_tile<SPLIT, BM, BN>(p);
+    const int m0 = t.m0, n0 = t.n0, b0 = t.b0;
+    const __amdgpu_buffer_rsrc_t xr = t.xr;
     const __amdgpu_buffer_rsrc_t wr = mydet_rsrc(p.w, (int64_t)p.Cout * p.K * 4);
     const int64_t img1 = (int64_t)(p.H >> 1) * (p.W >> 1) * p.ldx1;      // CAT: the half-resolution source
     const __amdgpu_buffer_rsrc_t xr1 = mydet_rsrc(CAT ? p.x1 + b0 * img1 : p.w, CAT ? (p.B - b0) * img1 * 4 : 16);
@@ -136,36 +64,18 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
 
     // ---- staging role: chunk (4 floats) `sc` of rows sr + RP*i
     const int sc = tid % CH, sr = tid / CH;
-    const int ntaps = p.KH * p.KW;
     int aoff[AI];                                   // byte offset of tap (0,0), channel 4*sc, from the window base
     unsigned amask[AI];                             // bit t: tap t of this row is inside the image
     unsigned gbase[AI];                             // GATE: byte offset of the row's image in gate[B][Cin]
     unsigned aoff1[AI];                             // CAT: byte offset of the row's pixel (oh / 2, ow / 2) in x1, channel 4*sc
-    // pointwise, stride 1, unpadded (uniform): input pixel == output pixel, no index arithmetic beyond the row number (the
-    // three divisions per row below are pure latency in a small-grid launch)
-    const bool flat = !CAT && ntaps == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.Ho == p.H && p.Wo == p.W;
+    const bool flat = !CAT && ig_flat(p);
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
-        const int m = m0 + sr + RP * i;
-        const int mm = m < p.M ? m : p.M - 1;
-        if (flat) {
-            aoff[i] = (int)(((int64_t)(mm - b0 * hwo) * p.ldx + sc * 4) * 4);
-            amask[i] = m < p.M ? 1u : 0u;
-            if (GATE) gbase[i] = (unsigned)((mm / hwo) * p.Cin) * 4u;
-            continue;
-        }
-        const int ow = mm % p.Wo, t = mm / p.Wo;
-        const int oh = t % p.Ho, b = t / p.Ho;
-        const int ih0 = oh * p.stride - p.pad_t, iw0 = ow * p.stride - p.pad_l;
-        aoff[i] = (int)((((int64_t)(b - b0) * p.H + ih0) * p.W + iw0) * p.ldx + sc * 4) * 4;
-        unsigned mask = 0;
-        for (int tp = 0; tp < ntaps; ++tp) {
-            const int kh = tp / p.KW, kw = tp - kh * p.KW;
-            if ((unsigned)(ih0 + kh) < (unsigned)p.H && (unsigned)(iw0 + kw) < (unsigned)p.W) mask |= 1u << tp;
-        }
-        amask[i] = m < p.M ? mask : 0u;
-        if (GATE) gbase[i] = (unsigned)(b * p.Cin) * 4u;
-        if (CAT) aoff1[i] = (unsigned)((((int64_t)(b - b0) * (p.H >> 1) + (oh >> 1)) * (p.W >> 1) + (ow >> 1)) * p.ldx1 + sc * 4) * 4u;
+        const IgRow r = ig_row(p, t, flat, m0 + sr + RP * i, sc);
+        aoff[i] = r.aoff;
+        amask[i] = r.amask;
+        if (GATE) gbase[i] = (unsigned)(r.b * p.Cin) * 4u;
+        if (CAT) aoff1[i] = (unsigned)((((int64_t)(r.b - b0) * (p.H >> 1) + (r.oh >> 1)) * (p.W >> 1) + (r.ow >> 1)) * p.ldx1 + sc * 4) * 4u;
     }
     unsigned boff[BI];
 #pragma unroll
@@ -175,41 +85,24 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
         boff[i] = (unsigned)(n * p.K + sc * 4) * 4u;
     }
 
-    f32x4 areg[PF][AI], breg[PF][BI];                // PF slabs in flight (see the K loop)
-    const int nk_all = (p.K + BK - 1) / BK;
-    int kt0 = 0, nk = nk_all;                        // this block's slab range [kt0, nk)
-    if (SPLIT) {
-        const int sp = (int)blockIdx.x % p.splits;
-        kt0 = (int)((unsigned)(nk_all * sp) / (unsigned)p.splits);          // (nk_all * splits < 2^31: no 64-bit division)
-        nk = (int)((unsigned)(nk_all * (sp + 1)) / (unsigned)p.splits);
-    }
-    int tap = 0, c0 = 0, tapoff = 0;                 // CIN32 path: uniform tap / channel base / byte offset
-    if (SPLIT && CIN32) {
-        const int k0 = kt0 * BK;
-        tap = k0 / p.Cin;
-        c0 = k0 - tap * p.Cin;
-        const int kh = tap / p.KW, kw = tap - kh * p.KW;
-        tapoff = (int)(((int64_t)kh * p.W + kw) * p.ldx) * 4;
-    }
+    int kt0, nk;                                     // this block's slab range [kt0, nk)
+    ig_k_range<SPLIT>(p, (p.K + BK - 1) / BK, kt0, nk);
+    IgTapCursor cur;                                 // CIN32 path only
+    if (SPLIT && CIN32) cur.seek(p, kt0 * BK);
 
     auto load_slab = [&](int kt, f32x4 (&areg)[AI], f32x4 (&breg)[BI]) {
         if (CIN32) {
+            const int c0 = cur.c0;
             const bool lo = CAT && c0 < p.C1;              // uniform: this slab's channels come from the upsampled map
-            const unsigned uoff = (unsigned)(tapoff + (c0 - (CAT ? p.C1 : 0)) * 4);
+            const unsigned uoff = (unsigned)(cur.tapoff + (c0 - (CAT ? p.C1 : 0)) * 4);
 #pragma unroll
             for (int i = 0; i < AI; ++i) {
-                const bool ok = (amask[i] >> tap) & 1u;
+                const bool ok = (amask[i] >> cur.tap) & 1u;
                 if (lo) areg[i] = buf_load16(xr1, ok ? aoff1[i] + (unsigned)(c0 * 4) : OOB);
                 else areg[i] = buf_load16(xr, ok ? (unsigned)aoff[i] + uoff : OOB);
                 if (GATE) areg[i] *= buf_load16(gr, gbase[i] + (unsigned)(c0 + sc * 4) * 4u);
             }
-            c0 += BK;
-            if (c0 == p.Cin) {                        // uniform: next tap
-                c0 = 0;
-                ++tap;
-                const int kh = tap / p.KW, kw = tap - kh * p.KW;
-                tapoff = (int)(((int64_t)kh * p.W + kw) * p.ldx) * 4;
-            }
+            cur.advance(p, BK);
         } else {
             const int k = kt * BK + sc * 4;          // Cin % 4 == 0: a chunk never straddles taps
             const int tp = k / p.Cin;
@@ -224,6 +117,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
                 if (GATE) areg[i] *= buf_load16(gr, kok ? gbase[i] + (unsigned)cc * 4u : OOB);
             }
         }
+        // (a look-ahead past the last slab: the weight rows run into the next row or the range check)
         const unsigned koff = (unsigned)kt * (BK * 4);
 #pragma unroll
         for (int i = 0; i < BI; ++i) breg[i] = buf_load16(wr, boff[i] + koff);
@@ -242,24 +136,13 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
     const int wave = tid >> 6, lane = tid & 63;
     const int wm = wave / WN, wn = wave % WN;
     const int fr = lane & 31, fh = lane >> 5;
+    const int m_base = m0 + wm * TM * 32, n_base = n0 + wn * TN * 32;
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
+    ig_zero(acc);
     const int a_off = (wm * TM * 32 + fr) * LDS_LD + fh * 4;
     const int b_off = (wn * TN * 32 + fr) * LDS_LD + fh * 4;
-    float pscl[TN], psft[TN];                          // this lane's output channels' scale / shift: in flight under the K loop
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * TN * 32 + j * 32 + fr;
-        const int nc = n < p.Cout ? n : 0;
-        pscl[j] = (!SPLIT && p.scale) ? p.scale[nc] : 1.0f;
-        psft[j] = (!SPLIT && p.shift) ? p.shift[nc] : 0.0f;
-    }
+    float pscl[TN], psft[TN];
+    ig_scale_shift<SPLIT>(p, n_base, fr, pscl, psft);
 
     auto compute = [&](int buf) {
         const float *a = As + buf * BM * LDS_LD + a_off;
@@ -281,48 +164,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
         }
     };
 
-    // K loop.  LDS holds two slabs (the one being multiplied, the next one), registers PF more: the loads of slabs kt+2 ..
-    // kt+1+PF are in flight while slab kt is multiplied, so a workgroup alone on its CU (small grids: batch-1 layers, the
-    // MBConv 1x1 convs of one batch lane) has two MFMA phases to cover a load round trip instead of one -- with one slab
-    // in flight those loops ran at the L2 latency (0.67 us per slab against 0.43 us of MFMA work).
-    // Prefetches past the last slab are unconditional: the taps are masked off (A) and the weight rows run into the next row
-    // or the range check (B) -- harmless, never consumed.
-    load_slab(kt0, areg[0], breg[0]);
-    store_slab(0, areg[0], breg[0]);
-#pragma unroll
-    for (int d = 0; d < PF; ++d) load_slab(kt0 + 1 + d, areg[d], breg[d]);
-    __syncthreads();
-    int buf = 0;
-    for (int kt = kt0; kt < nk; kt += PF) {
-#pragma unroll
-        for (int d = 0; d < PF; ++d) {               // register set d holds slab kt + d + 1
-            if (kt + d >= nk) break;
-            compute(buf);
-            store_slab(buf ^ 1, areg[d], breg[d]);
-            load_slab(kt + d + 1 + PF, areg[d], breg[d]);
-            __syncthreads();
-            buf ^= 1;
-        }
-    }
-
-    if (SPLIT) {     // raw partial tile, [vec4][thread] so lanes store contiguously; summed by conv_fixup_kernel
-        constexpr int NV4 = TM * TN * 4;
-        f32x4 *dst = reinterpret_cast<f32x4 *>(p.ws) + (int64_t)blockIdx.x * NV4 * NT + tid;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int v = 0; v < 4; ++v)
-                    dst[((i * TN + j) * 4 + v) * NT] =
-                        f32x4{acc[i][j][4 * v], acc[i][j][4 * v + 1], acc[i][j][4 * v + 2], acc[i][j][4 * v + 3]};
-        return;
-    }
-    const int m_base = m0 + wm * TM * 32, n_base = n0 + wn * TN * 32;
-    if ((m0 + BM <= p.M) && (n0 + BN <= p.Cout))
-        epilogue<ACT, RES, true, TM, TN>(p, acc, m_base, n_base, fr, fh, pscl, psft);
-    else
-        epilogue<ACT, RES, false, TM, TN>(p, acc, m_base, n_base, fr, fh, pscl, psft);
+    ig_k_loop<PF, f32x4[AI], f32x4[BI]>(kt0, nk, load_slab, store_slab, compute);
+    ig_finish<ACT, RES, SPLIT, BM, BN, NT>(p, acc, m0, n0, m_base, n_base, tid, fr, fh, pscl, psft);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -371,45 +214,26 @@ __global__ __launch_bounds__(128 * WN, 2) void conv_igemm_b3_kernel(const ConvAr
     extern __shared__ __attribute__((aligned(16))) char smem_b3[];
 
     const int tid = threadIdx.x;
-    const int lid = SPLIT ? p.tile0 + (int)blockIdx.x / p.splits : mydet_xcd_remap(blockIdx.x, p.nblk);
-    const int m0 = (lid / p.ntiles) * BM;
-    const int n0 = (lid % p.ntiles) * BN;
-    const int hwo = p.Ho * p.Wo;
-    const int b0 = m0 / hwo;
-    const int64_t img = (int64_t)p.H * p.W * p.ldx;
-    const __amdgpu_buffer_rsrc_t xr = mydet_rsrc(p.x + b0 * img, (p.B - b0) * img * 4);
+    const IgTile t = ig_tile<SPLIT, BM, BN>(p);
+    const int m0 = t.m0, n0 = t.n0;
+    const __amdgpu_buffer_rsrc_t xr = t.xr;
     const int CoutP = (p.Cout + B3_COUT_PAD - 1) / B3_COUT_PAD * B3_COUT_PAD;
     const __amdgpu_buffer_rsrc_t wr = mydet_rsrc(p.wsplit, (int64_t)((p.K + 15) >> 4) * 3 * CoutP * 32);
 
     // ---- staging roles.  A: chunk (4 floats) sc of rows sr + RP i.  B: chunk (8 bf16) bh of row br, all three planes.
     constexpr int RP = NT / 4;
     const int sc = tid & 3, sr = tid >> 2;
-    const int ntaps = p.KH * p.KW;
     int aoff[AI];
     unsigned amask[AI];
     unsigned goff[AI];                               // GATE: byte offset of the row's image (+ this thread's channel quad) in gate[B][Cin]
     const __amdgpu_buffer_rsrc_t gr = mydet_rsrc(GATE ? p.gate : p.x, (int64_t)p.B * p.Cin * 4);
-    const bool flat = ntaps == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.Ho == p.H && p.Wo == p.W;
+    const bool flat = ig_flat(p);
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
-        const int m = m0 + sr + RP * i;
-        const int mm = m < p.M ? m : p.M - 1;
-        goff[i] = GATE ? (unsigned)((mm / hwo) * p.Cin + sc * 4) * 4u : 0u;
-        if (flat) {
-            aoff[i] = (int)(((int64_t)(mm - b0 * hwo) * p.ldx + sc * 4) * 4);
-            amask[i] = m < p.M ? 1u : 0u;
-            continue;
-        }
-        const int ow = mm % p.Wo, t = mm / p.Wo;
-        const int oh = t % p.Ho, b = t / p.Ho;
-        const int ih0 = oh * p.stride - p.pad_t, iw0 = ow * p.stride - p.pad_l;
-        aoff[i] = (int)((((int64_t)(b - b0) * p.H + ih0) * p.W + iw0) * p.ldx + sc * 4) * 4;
-        unsigned mask = 0;
-        for (int tp = 0; tp < ntaps; ++tp) {
-            const int kh = tp / p.KW, kw = tp - kh * p.KW;
-            if ((unsigned)(ih0 + kh) < (unsigned)p.H && (unsigned)(iw0 + kw) < (unsigned)p.W) mask |= 1u << tp;
-        }
-        amask[i] = m < p.M ? mask : 0u;
+        const IgRow r = ig_row(p, t, flat, m0 + sr + RP * i, sc);
+        aoff[i] = r.aoff;
+        amask[i] = r.amask;
+        goff[i] = GATE ? (unsigned)(r.b * p.Cin + sc * 4) * 4u : 0u;
     }
     // B: 16-byte unit `tid` of the tile's plane-slab (BN rows x 32 bytes, contiguous in the slab-major layout); the unit's
     // (row, k-half) follow from the layout's swizzle (split_bf16_kernel); rows past Cout are zeros there
@@ -419,28 +243,17 @@ __global__ __launch_bounds__(128 * WN, 2) void conv_igemm_b3_kernel(const ConvAr
     const unsigned boff = bact ? (unsigned)(n0 * 32 + tid * 16) : OOB;
     const unsigned plane_bytes = (unsigned)CoutP * 32u, slab_bytes = 3u * plane_bytes;
 
-    f32x4 areg[PF][AI];
-    u32x4 breg[PF][3];
     const int nk_all = (p.K + BK - 1) / BK;          // (1x1 layers may have Cin % 16 == 4, 8, 12: the last slab's missing channels are zeros)
-    int kt0 = 0, nk = nk_all;
-    if (SPLIT) {
-        const int sp = (int)blockIdx.x % p.splits;
-        kt0 = (int)((unsigned)(nk_all * sp) / (unsigned)p.splits);
-        nk = (int)((unsigned)(nk_all * (sp + 1)) / (unsigned)p.splits);
-    }
-    int tap = 0, c0 = 0, tapoff = 0;                 // uniform tap / channel base / byte offset of the slab being requested
-    if (SPLIT) {
-        const int k0 = kt0 * BK;
-        tap = k0 / p.Cin;
-        c0 = k0 - tap * p.Cin;
-        const int kh = tap / p.KW, kw = tap - kh * p.KW;
-        tapoff = (int)(((int64_t)kh * p.W + kw) * p.ldx) * 4;
-    }
+    int kt0, nk;
+    ig_k_range<SPLIT>(p, nk_all, kt0, nk);
+    IgTapCursor cur;
+    if (SPLIT) cur.seek(p, kt0 * BK);
     auto load_slab = [&](int kt, f32x4 (&ar)[AI], u32x4 (&brg)[3]) {
-        const unsigned uoff = (unsigned)(tapoff + c0 * 4);
+        const int c0 = cur.c0;
+        const unsigned uoff = (unsigned)(cur.tapoff + c0 * 4);
 #pragma unroll
         for (int i = 0; i < AI; ++i) {
-            bool ok = ((amask[i] >> tap) & 1u) && c0 + sc * 4 < p.Cin;
+            bool ok = ((amask[i] >> cur.tap) & 1u) && c0 + sc * 4 < p.Cin;
             ar[i] = buf_load16(xr, ok ? (unsigned)aoff[i] + uoff : OOB);
             if (GATE) {                               // (1x1: one tap, c0 is the slab's first channel)
                 const f32x4 gv = buf_load16(gr, ok ? goff[i] + (unsigned)c0 * 4u : OOB);
@@ -448,13 +261,7 @@ __global__ __launch_bounds__(128 * WN, 2) void conv_igemm_b3_kernel(const ConvAr
                 for (int e = 0; e < 4; ++e) ar[i][e] *= gv[e];
             }
         }
-        c0 += BK;
-        if (c0 == p.Cin) {                            // uniform: next tap
-            c0 = 0;
-            ++tap;
-            const int kh = tap / p.KW, kw = tap - kh * p.KW;
-            tapoff = (int)(((int64_t)kh * p.W + kw) * p.ldx) * 4;
-        }
+        cur.advance(p, BK);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
             brg[pl] = __builtin_amdgcn_raw_buffer_load_b128(wr, kt < nk_all ? boff : OOB,      // (the range check sees the voffset only: the
@@ -482,24 +289,14 @@ __global__ __launch_bounds__(128 * WN, 2) void conv_igemm_b3_kernel(const ConvAr
     const int wave = tid >> 6, lane = tid & 63;
     const int wm = wave / WN, wn = wave % WN;
     const int fr = lane & 31, fh = lane >> 5;
+    const int m_base = m0 + wm * TM * 32, n_base = n0 + wn * TN * 32;
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    ig_zero(acc);
     const int fsw = (fh ^ ((fr >> 3) & 1)) * 16;           // (block rows start at multiples of 32: bit 3 of the row is bit 3 of fr)
     const int a_off = (wm * TM * 32 + fr) * ROWB + fsw;
     const int b_off = 3 * PLANE_A + (wn * TN * 32 + fr) * ROWB + fsw;
     float pscl[TN], psft[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * TN * 32 + j * 32 + fr;
-        const int nc = n < p.Cout ? n : 0;
-        pscl[j] = (!SPLIT && p.scale) ? p.scale[nc] : 1.0f;
-        psft[j] = (!SPLIT && p.shift) ? p.shift[nc] : 0.0f;
-    }
+    ig_scale_shift<SPLIT>(p, n_base, fr, pscl, psft);
     auto compute = [&](int buf) {
         const char *a = smem_b3 + buf * BUF + a_off;
         const char *b = smem_b3 + buf * BUF + b_off;
@@ -512,53 +309,11 @@ __global__ __launch_bounds__(128 * WN, 2) void conv_igemm_b3_kernel(const ConvAr
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) bf[j][pl] = *reinterpret_cast<const bf16x8 *>(b + pl * PLANE_B + j * 32 * ROWB);
-        // the six piece products, small ones first (the running sum absorbs them at its own rounding either way); a piece pair
-        // sweeps all blocks of the wave tile before the next pair, so MFMAs on one accumulator are TM * TN instructions apart
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][SPLIT_PA[t]], bf[j][SPLIT_PB[t]], acc[i][j], 0, 0, 0);
+        split_mfma6(af, bf, acc);
     };
 
-    load_slab(kt0, areg[0], breg[0]);
-    store_slab(0, areg[0], breg[0]);
-#pragma unroll
-    for (int d = 0; d < PF; ++d) load_slab(kt0 + 1 + d, areg[d], breg[d]);
-    __syncthreads();
-    int buf = 0;
-    for (int kt = kt0; kt < nk; kt += PF) {
-#pragma unroll
-        for (int d = 0; d < PF; ++d) {               // register set d holds slab kt + d + 1
-            if (kt + d >= nk) break;
-            compute(buf);
-            store_slab(buf ^ 1, areg[d], breg[d]);
-            load_slab(kt + d + 1 + PF, areg[d], breg[d]);
-            __syncthreads();
-            buf ^= 1;
-        }
-    }
-
-    if (SPLIT) {     // raw partial tile in conv_fixup_kernel's layout
-        constexpr int NV4 = TM * TN * 4;
-        f32x4 *dst = reinterpret_cast<f32x4 *>(p.ws) + (int64_t)blockIdx.x * NV4 * NT + tid;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int v = 0; v < 4; ++v)
-                    dst[((i * TN + j) * 4 + v) * NT] =
-                        f32x4{acc[i][j][4 * v], acc[i][j][4 * v + 1], acc[i][j][4 * v + 2], acc[i][j][4 * v + 3]};
-        return;
-    }
-    const int m_base = m0 + wm * TM * 32, n_base = n0 + wn * TN * 32;
-    if ((m0 + BM <= p.M) && (n0 + BN <= p.Cout))
-        epilogue<ACT, RES, true, TM, TN>(p, acc, m_base, n_base, fr, fh, pscl, psft);
-    else
-        epilogue<ACT, RES, false, TM, TN>(p, acc, m_base, n_base, fr, fh, pscl, psft);
+    ig_k_loop<PF, f32x4[AI], u32x4[3]>(kt0, nk, load_slab, store_slab, compute);
+    ig_finish<ACT, RES, SPLIT, BM, BN, NT>(p, acc, m0, n0, m_base, n_base, tid, fr, fh, pscl, psft);
 }
 
 // ---- wide form: tile 128 x 256 on 8 waves (wave tile 64 x 64), ONE workgroup per CU.
@@ -581,67 +336,27 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_b3w_kernel(const ConvArgs p
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int lid = SPLIT ? p.tile0 + (int)blockIdx.x / p.splits : mydet_xcd_remap(blockIdx.x, p.nblk);
-    const int m0 = (lid / p.ntiles) * BM;
-    const int n0 = (lid % p.ntiles) * BN;
-    const int hwo = p.Ho * p.Wo;
-    const int b0 = m0 / hwo;
-    const int64_t img = (int64_t)p.H * p.W * p.ldx;
-    const __amdgpu_buffer_rsrc_t xr = mydet_rsrc(p.x + b0 * img, (p.B - b0) * img * 4);
+    const IgTile t = ig_tile<SPLIT, BM, BN>(p);
+    const int m0 = t.m0, n0 = t.n0;
+    const __amdgpu_buffer_rsrc_t xr = t.xr;
     const int CoutP = (p.Cout + B3_COUT_PAD - 1) / B3_COUT_PAD * B3_COUT_PAD;
     const __amdgpu_buffer_rsrc_t wr = mydet_rsrc(p.wsplit, (int64_t)(p.K >> 4) * 3 * CoutP * 32);
     const unsigned plane_bytes = (unsigned)CoutP * 32u, slab_bytes = 3u * plane_bytes;
 
     // ---- activation staging role: chunk (4 floats) sc of row sr
     const int sc = tid & 3, sr = tid >> 2;
-    const int ntaps = p.KH * p.KW;
-    int aoff;
-    unsigned amask;
-    {
-        const bool flat = ntaps == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.Ho == p.H && p.Wo == p.W;
-        const int m = m0 + sr;
-        const int mm = m < p.M ? m : p.M - 1;
-        if (flat) {
-            aoff = (int)(((int64_t)(mm - b0 * hwo) * p.ldx + sc * 4) * 4);
-            amask = m < p.M ? 1u : 0u;
-        } else {
-            const int ow = mm % p.Wo, t = mm / p.Wo;
-            const int oh = t % p.Ho, b = t / p.Ho;
-            const int ih0 = oh * p.stride - p.pad_t, iw0 = ow * p.stride - p.pad_l;
-            aoff = (int)((((int64_t)(b - b0) * p.H + ih0) * p.W + iw0) * p.ldx + sc * 4) * 4;
-            unsigned mask = 0;
-            for (int tp = 0; tp < ntaps; ++tp) {
-                const int kh = tp / p.KW, kw = tp - kh * p.KW;
-                if ((unsigned)(ih0 + kh) < (unsigned)p.H && (unsigned)(iw0 + kw) < (unsigned)p.W) mask |= 1u << tp;
-            }
-            amask = m < p.M ? mask : 0u;
-        }
-    }
+    const IgRow row = ig_row(p, t, ig_flat(p), m0 + sr, sc);
+    const int aoff = row.aoff;
+    const unsigned amask = row.amask;
     const int nk_all = p.K / BK;
-    int kt0 = 0, nk = nk_all;
-    if (SPLIT) {
-        const int sp = (int)blockIdx.x % p.splits;
-        kt0 = (int)((unsigned)(nk_all * sp) / (unsigned)p.splits);
-        nk = (int)((unsigned)(nk_all * (sp + 1)) / (unsigned)p.splits);
-    }
-    int tap = 0, c0 = 0, tapoff = 0;                 // uniform tap / channel base / byte offset of the activation slab being requested
-    if (SPLIT) {
-        const int k0 = kt0 * BK;
-        tap = k0 / p.Cin;
-        c0 = k0 - tap * p.Cin;
-        const int kh = tap / p.KW, kw = tap - kh * p.KW;
-        tapoff = (int)(((int64_t)kh * p.W + kw) * p.ldx) * 4;
-    }
+    int kt0, nk;
+    ig_k_range<SPLIT>(p, nk_all, kt0, nk);
+    IgTapCursor cur;                                 // of the activation slab being requested
+    if (SPLIT) cur.seek(p, kt0 * BK);
     auto load_a = [&](f32x4 &ar) {                   // requests past the last slab run into masked taps: harmless, never consumed
-        const bool ok = (amask >> tap) & 1u;
-        ar = buf_load16(xr, ok ? (unsigned)aoff + (unsigned)(tapoff + c0 * 4) : OOB);
-        c0 += BK;
-        if (c0 == p.Cin) {                            // uniform: next tap
-            c0 = 0;
-            ++tap;
-            const int kh = tap / p.KW, kw = tap - kh * p.KW;
-            tapoff = (int)(((int64_t)kh * p.W + kw) * p.ldx) * 4;
-        }
+        const bool ok = (amask >> cur.tap) & 1u;
+        ar = buf_load16(xr, ok ? (unsigned)aoff + (unsigned)(cur.tapoff + cur.c0 * 4) : OOB);
+        cur.advance(p, BK);
     };
     auto store_a = [&](int buf, const f32x4 &ar) {
         bf16x4 q0, q1, q2;
@@ -668,23 +383,13 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_b3w_kernel(const ConvArgs p
     // ---- compute role
     const int wm = wave / WN, wn = wave % WN;
     const int fr = lane & 31, fh = lane >> 5;
+    const int m_base = m0 + wm * 64, n_base = n0 + wn * 64;
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    ig_zero(acc);
     const int a_off = (wm * 64 + fr) * ROWB + fh * 16;
     const int b_off = (wn * 2) * 1024 + b3_unit(fr, fh) * 16;            // + j * 1024 + plane * PLANE_B
     float pscl[TN], psft[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + fr;
-        const int nc = n < p.Cout ? n : 0;
-        pscl[j] = (!SPLIT && p.scale) ? p.scale[nc] : 1.0f;
-        psft[j] = (!SPLIT && p.shift) ? p.shift[nc] : 0.0f;
-    }
+    ig_scale_shift<SPLIT>(p, n_base, fr, pscl, psft);
     auto compute = [&](int buf, int slot) {
         const char *a = As + buf * ABUF + a_off;
         const char *b = Bs + slot * BSLOT + b_off;
@@ -697,13 +402,7 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_b3w_kernel(const ConvArgs p
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) bf[j][pl] = *reinterpret_cast<const bf16x8 *>(b + pl * PLANE_B + j * 1024);
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][SPLIT_PA[t]], bf[j][SPLIT_PB[t]], acc[i][j], 0, 0, 0);
+        split_mfma6(af, bf, acc);
     };
 
     // prologue.  Requests, oldest first: B(kt0), B(kt0+1), A(kt0), A(kt0+1), A(kt0+2)
@@ -736,25 +435,7 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_b3w_kernel(const ConvArgs p
             slot = slot == RING - 1 ? 0 : slot + 1;
         }
     }
-
-    if (SPLIT) {     // raw partial tile in conv_fixup_kernel's layout
-        constexpr int NV4 = TM * TN * 4;
-        f32x4 *dst = reinterpret_cast<f32x4 *>(p.ws) + (int64_t)blockIdx.x * NV4 * NT + tid;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int v = 0; v < 4; ++v)
-                    dst[((i * TN + j) * 4 + v) * NT] =
-                        f32x4{acc[i][j][4 * v], acc[i][j][4 * v + 1], acc[i][j][4 * v + 2], acc[i][j][4 * v + 3]};
-        return;
-    }
-    const int m_base = m0 + wm * 64, n_base = n0 + wn * 64;
-    if ((m0 + BM <= p.M) && (n0 + BN <= p.Cout))
-        epilogue<ACT, RES, true, TM, TN>(p, acc, m_base, n_base, fr, fh, pscl, psft);
-    else
-        epilogue<ACT, RES, false, TM, TN>(p, acc, m_base, n_base, fr, fh, pscl, psft);
+    ig_finish<ACT, RES, SPLIT, BM, BN, NT>(p, acc, m0, n0, m_base, n_base, tid, fr, fh, pscl, psft);
 }
 
 // float32 OHWI weight [Cout][K] -> the split-bf16 kernels' operand: three bfloat16 planes (w = p0 + p1 + p2), SLAB-MAJOR so that
@@ -804,12 +485,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fixup_kernel(const ConvArgs
     f32x4 cur[NV4], nxt[NV4];
 #pragma unroll
     for (int q = 0; q < NV4; ++q) cur[q] = src[(int64_t)q * NT];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    ig_zero(acc);
     for (int sp = 0; sp < p.splits; ++sp) {
         const bool more = sp + 1 < p.splits;          // uniform
         if (more) {
@@ -834,17 +510,94 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_fixup_kernel(const ConvArgs
     }
     const int m_base = m0 + wm * TM * 32, n_base = n0 + wn * TN * 32;
     float pscl[TN], psft[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n_base + j * 32 + fr;
-        const int nc = n < p.Cout ? n : 0;
-        pscl[j] = p.scale ? p.scale[nc] : 1.0f;
-        psft[j] = p.shift ? p.shift[nc] : 0.0f;
+    ig_scale_shift<false>(p, n_base, fr, pscl, psft);
+    ig_finish<ACT, RES, false, BM, BN, NT>(p, acc, m0, n0, m_base, n_base, tid, fr, fh, pscl, psft);
+}
+
+// ---- host half.  The activation x residual instances of an epilogue, chosen once: f(ACT, RES) as integral constants.
+template <int ACT> using ActC = std::integral_constant<int, ACT>;
+template <class F>
+int with_act_res(int act, bool res, F &&f) {
+    switch (act) {
+        case MYDET_ACT_LEAKY: return res ? f(ActC<MYDET_ACT_LEAKY>{}, std::true_type{}) : f(ActC<MYDET_ACT_LEAKY>{}, std::false_type{});
+        case MYDET_ACT_SWISH: return res ? f(ActC<MYDET_ACT_SWISH>{}, std::true_type{}) : f(ActC<MYDET_ACT_SWISH>{}, std::false_type{});
+        default: return res ? f(ActC<MYDET_ACT_NONE>{}, std::true_type{}) : f(ActC<MYDET_ACT_NONE>{}, std::false_type{});
     }
-    if ((m0 + BM <= p.M) && (n0 + BN <= p.Cout))
-        epilogue<ACT, RES, true, TM, TN>(p, acc, m_base, n_base, fr, fh, pscl, psft);
-    else
-        epilogue<ACT, RES, false, TM, TN>(p, acc, m_base, n_base, fr, fh, pscl, psft);
+}
+
+// `slots` = workgroups of a configuration the chip holds at once (256 CUs x workgroups per CU).  Workgroups
+// are equal-sized, so a grid of R full rounds plus a small remainder pays a whole extra round for the
+// remainder.  When that happens (and the caller gave workspace) the remainder tiles are instead cut along K into
+// `splits` slices that together fill the chip once, their partial tiles go to the workspace, and a small fixup
+// launch sums them in slice order and applies the epilogue: deterministic, no atomics.
+struct TilePlan {
+    int ntiles, total;      // tiles along N, tiles in all
+    int rem, splits;        // tiles past the last whole round, K slices each of them would be cut into
+    bool split;             // the remainder runs as a K-cut tail (rem tiles x splits slices + the fixup launch)
+};
+
+// What the rule leaves to a kernel family, in K slabs of that family
+struct TailRule {
+    int small_nk;           // a small grid is cut as a whole from this many slabs
+    int slice_nk;           // a slice is at least this many slabs
+    int tail_nk;            // a tail behind whole rounds needs this many slabs
+};
+constexpr TailRule TAIL_F32 = {16, 4, 32};      // (32-wide slabs; 16-wide ones in configuration 6)
+constexpr TailRule TAIL_B3 = {32, 8, 64};       // (16-wide slabs)
+
+// The round / K-cut-tail rule (host only), once, for every launch and plan hook of this file.  nk: K in slabs; ws_bytes = 0: no workspace.
+TilePlan plan_tail(int64_t M, int Cout, int BM, int BN, int nk, int slots, size_t ws_bytes, const TailRule &r) {
+    TilePlan pl;
+    const int mtiles = (int)((M + BM - 1) / BM);
+    pl.ntiles = (Cout + BN - 1) / BN;
+    const int total = pl.total = mtiles * pl.ntiles;
+    const int rounds = total / slots;
+    const int rem = pl.rem = total % slots;
+    // a grid that fills less than a quarter of one round (batch-1 / small-map layers: M = Ho*Wo is a few tiles) is cut along K
+    // as a whole, so the chip is busy instead of a handful of CUs walking all of K
+    // (a quarter, not half: between the two the K slices and the fixup launch cost more than the idle CUs -- round 4: batch 1
+    // 643 -> 654 images/s, EfficientDet-D1 +1.3 %, D1-FCOS2-ATSS +1.0 %; an eighth is worse again)
+    const bool small = rounds == 0 && total * 4 <= slots && nk >= r.small_nk;
+    int splits = rem > 0 ? slots / rem : 0;
+    if (splits > 16) splits = 16;
+    if (splits > nk / r.slice_nk) splits = nk / r.slice_nk;
+    pl.splits = splits;
+    const size_t need = (size_t)rem * (splits > 0 ? splits : 0) * BM * BN * sizeof(float);
+    // only long-K layers: on short ones the two extra launches cost more than the spared round
+    // (shorter K -- 8 or 16 slabs, the 256->128 / 512->256 1x1 layers of YOLOv3 -- measured 1-3 % SLOWER with the tail cut)
+    // and at most four whole rounds: after more, the workgroups no longer finish together and the partial last round is cheap
+    // already (128->256 stride 2 @160^2, 6.25 rounds: headline 1 454 -> 1 459 images/s without its tail; the same holds for F(4x4))
+    pl.split = rem > 0 && splits >= 2 && ws_bytes > 0 && need <= ws_bytes &&
+               (small || (nk >= r.tail_nk && rounds >= 2 && rounds <= 4 && rem * 2 <= slots));
+    return pl;
+}
+
+// The launches of a plan: main(args) over the whole rounds (all tiles without a tail), then the tail's K slices tail(args) into the
+// workspace and fixup(args, tail tiles).  Each takes the ConvArgs of its launch; the first failure is returned.
+template <class Main, class Tail, class Fixup>
+int launch_with_tail(const ConvArgs &a0, const TilePlan &pl, Main &&main, Tail &&tail, Fixup &&fixup) {
+    ConvArgs a = a0;
+    a.ntiles = pl.ntiles;
+    a.tile0 = 0; a.splits = 1;
+    a.nblk = pl.split ? pl.total - pl.rem : pl.total;
+    int rc = a.nblk > 0 ? main(a) : 0;
+    if (rc || !pl.split) return rc;
+    a.tile0 = pl.total - pl.rem; a.splits = pl.splits; a.nblk = pl.rem * pl.splits;
+    if ((rc = tail(a))) return rc;
+    return fixup(a, pl.rem);
+}
+
+template <int BM, int BN, int WM, int WN, int ACT, bool RES>
+int launch_fixup(const ConvArgs &a, int ntail, hipStream_t stream) {
+    hipLaunchKernelGGL((conv_fixup_kernel<BM, BN, WM, WN, ACT, RES>), dim3(ntail), dim3(WM * WN * 64), 0, stream, a);
+    return mydet_launch_status();
+}
+
+template <int BM, int BN, int WM, int WN>
+int launch_fixup_act(const ConvArgs &a, int ntail, hipStream_t stream) {
+    return with_act_res(a.act, a.res != nullptr, [&](auto act, auto res) {
+        return launch_fixup<BM, BN, WM, WN, decltype(act)::value, decltype(res)::value>(a, ntail, stream);
+    });
 }
 
 template <int BM, int BN, int WM, int WN, int BK, bool CIN32, int ACT, bool RES, bool GATE = false, bool SPLIT = false, bool CAT = false>
@@ -858,118 +611,44 @@ int launch_inst(const ConvArgs &a, size_t lds, hipStream_t stream) {
 
 template <int BM, int BN, int WM, int WN, int BK, bool CIN32>
 int launch_act(const ConvArgs &a, size_t lds, hipStream_t stream) {
-    const bool res = a.res != nullptr;
     if (a.gate)         // only the MBConv project conv is gated: no activation (checked by the caller)
-        return res ? launch_inst<BM, BN, WM, WN, BK, CIN32, MYDET_ACT_NONE, true, true>(a, lds, stream)
-                   : launch_inst<BM, BN, WM, WN, BK, CIN32, MYDET_ACT_NONE, false, true>(a, lds, stream);
-    switch (a.act) {
-        case MYDET_ACT_LEAKY:
-            return res ? launch_inst<BM, BN, WM, WN, BK, CIN32, MYDET_ACT_LEAKY, true>(a, lds, stream)
-                       : launch_inst<BM, BN, WM, WN, BK, CIN32, MYDET_ACT_LEAKY, false>(a, lds, stream);
-        case MYDET_ACT_SWISH:
-            return res ? launch_inst<BM, BN, WM, WN, BK, CIN32, MYDET_ACT_SWISH, true>(a, lds, stream)
-                       : launch_inst<BM, BN, WM, WN, BK, CIN32, MYDET_ACT_SWISH, false>(a, lds, stream);
-        default:
-            return res ? launch_inst<BM, BN, WM, WN, BK, CIN32, MYDET_ACT_NONE, true>(a, lds, stream)
-                       : launch_inst<BM, BN, WM, WN, BK, CIN32, MYDET_ACT_NONE, false>(a, lds, stream);
-    }
+        return a.res ? launch_inst<BM, BN, WM, WN, BK, CIN32, MYDET_ACT_NONE, true, true>(a, lds, stream)
+                     : launch_inst<BM, BN, WM, WN, BK, CIN32, MYDET_ACT_NONE, false, true>(a, lds, stream);
+    return with_act_res(a.act, a.res != nullptr, [&](auto act, auto res) {
+        return launch_inst<BM, BN, WM, WN, BK, CIN32, decltype(act)::value, decltype(res)::value>(a, lds, stream);
+    });
 }
 
-template <int BM, int BN, int WM, int WN, int ACT, bool RES>
-int launch_fixup(const ConvArgs &a, int ntail, hipStream_t stream) {
-    hipLaunchKernelGGL((conv_fixup_kernel<BM, BN, WM, WN, ACT, RES>), dim3(ntail), dim3(WM * WN * 64), 0, stream, a);
-    return mydet_launch_status();
-}
-
-template <int BM, int BN, int WM, int WN>
-int launch_fixup_act(const ConvArgs &a, int ntail, hipStream_t stream) {
-    const bool res = a.res != nullptr;
-    switch (a.act) {
-        case MYDET_ACT_LEAKY:
-            return res ? launch_fixup<BM, BN, WM, WN, MYDET_ACT_LEAKY, true>(a, ntail, stream)
-                       : launch_fixup<BM, BN, WM, WN, MYDET_ACT_LEAKY, false>(a, ntail, stream);
-        case MYDET_ACT_SWISH:
-            return res ? launch_fixup<BM, BN, WM, WN, MYDET_ACT_SWISH, true>(a, ntail, stream)
-                       : launch_fixup<BM, BN, WM, WN, MYDET_ACT_SWISH, false>(a, ntail, stream);
-        default:
-            return res ? launch_fixup<BM, BN, WM, WN, MYDET_ACT_NONE, true>(a, ntail, stream)
-                       : launch_fixup<BM, BN, WM, WN, MYDET_ACT_NONE, false>(a, ntail, stream);
-    }
-}
-
-// `slots` = workgroups of this configuration the chip holds at once (256 CUs x workgroups per CU).  Workgroups
-// are equal-sized, so a grid of R full rounds plus a small remainder pays a whole extra round for the
-// remainder.  When that happens (and the caller gave workspace) the remainder tiles are instead cut along K into
-// `splits` slices that together fill the chip once, their partial tiles go to the workspace, and a small fixup
-// launch sums them in slice order and applies the epilogue: deterministic, no atomics.
-struct TilePlan {
-    int ntiles, total;      // tiles along N, tiles in all
-    int rem, splits;        // tiles past the last whole round, K slices each of them would be cut into
-    bool split;             // the remainder runs as a K-cut tail (rem tiles x splits slices + the fixup launch)
-};
-
-// The arithmetic of `launch` (host only): one function for the launch and for mydet_conv_igemm_plan.  ws_bytes = 0: no workspace.
+// The arithmetic of `launch` (host only): one function for the launch and for mydet_conv_igemm_plan.
 TilePlan plan_tiles(int M, int Cout, int K, int BM, int BN, int BK, int slots, size_t ws_bytes) {
-    TilePlan pl;
-    const int mtiles = (M + BM - 1) / BM;
-    pl.ntiles = (Cout + BN - 1) / BN;
-    const int total = pl.total = mtiles * pl.ntiles;
-    const int nk = (K + BK - 1) / BK;
-    const int rounds = total / slots;
-    const int rem = pl.rem = total % slots;
-    // a grid that fills less than a quarter of one round (batch-1 / small-map layers: M = Ho*Wo is a few tiles) is cut along K
-    // as a whole, so the chip is busy instead of a handful of CUs walking all of K
-    // (a quarter, not half: between the two the K slices and the fixup launch cost more than the idle CUs -- round 4: batch 1
-    // 643 -> 654 images/s, EfficientDet-D1 +1.3 %, D1-FCOS2-ATSS +1.0 %; an eighth is worse again)
-    const bool small = rounds == 0 && total * 4 <= slots && nk >= 16;
-    int splits = rem > 0 ? slots / rem : 0;
-    if (splits > 16) splits = 16;
-    if (splits > nk / 4) splits = nk / 4;
-    pl.splits = splits;
-    const size_t need = (size_t)rem * (splits > 0 ? splits : 0) * BM * BN * sizeof(float);
-    // only long-K layers: on short ones the two extra launches cost more than the spared round
-    // (shorter K -- 8 or 16 slabs, the 256->128 / 512->256 1x1 layers of YOLOv3 -- measured 1-3 % SLOWER with the tail cut)
-    // and at most four whole rounds: after more, the workgroups no longer finish together and the partial last round is cheap
-    // already (128->256 stride 2 @160^2, 6.25 rounds: headline 1 454 -> 1 459 images/s without its tail; the same holds for F(4x4))
-    pl.split = rem > 0 && splits >= 2 && ws_bytes > 0 && need <= ws_bytes &&
-               (small || (nk >= 32 && rounds >= 2 && rounds <= 4 && rem * 2 <= slots));
-    return pl;
+    return plan_tail(M, Cout, BM, BN, (K + BK - 1) / BK, slots, ws_bytes, TAIL_F32);
 }
 
 template <int BM, int BN, int WM, int WN, int BK>
-int launch(const ConvArgs &a0, int slots, hipStream_t stream) {
-    ConvArgs a = a0;
-    const TilePlan pl = plan_tiles(a.M, a.Cout, a.K, BM, BN, BK, slots, a0.ws ? a0.ws_bytes : 0);
-    a.ntiles = pl.ntiles;
-    const int total = pl.total, rem = pl.rem, splits = pl.splits;
-    const bool split = pl.split;
+int launch(const ConvArgs &a, int slots, hipStream_t stream) {
+    const TilePlan pl = plan_tiles(a.M, a.Cout, a.K, BM, BN, BK, slots, a.ws ? a.ws_bytes : 0);
     const size_t lds = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float);
     const bool cin = (a.Cin % BK) == 0;
-    a.tile0 = 0; a.splits = 1;
-    a.nblk = split ? total - rem : total;
-    int rc = 0;
+    auto fixup = [&](const ConvArgs &t, int rem) { return launch_fixup_act<BM, BN, WM, WN>(t, rem, stream); };
     if (a.x1) {         // upsample + concat read on the fly: instantiated for the YOLOv3 pyramid's use (64 x 64 tile, LeakyReLU)
         if (!(BM == 64 && BN == 64 && BK == 32) || !cin || a.act != MYDET_ACT_LEAKY || a.res || a.gate) return MYDET_E_UNSUPP;
-        if (a.nblk > 0) rc = launch_inst<64, 64, 2, 2, 32, true, MYDET_ACT_LEAKY, false, false, false, true>(a, lds, stream);
-        if (rc || !split) return rc;
-        a.tile0 = total - rem; a.splits = splits; a.nblk = rem * splits;
-        rc = launch_inst<64, 64, 2, 2, 32, true, MYDET_ACT_NONE, false, false, true, true>(a, lds, stream);
-        if (rc) return rc;
-        return launch_fixup_act<BM, BN, WM, WN>(a, rem, stream);
+        return launch_with_tail(
+            a, pl, [&](const ConvArgs &m) { return launch_inst<64, 64, 2, 2, 32, true, MYDET_ACT_LEAKY, false, false, false, true>(m, lds, stream); },
+            [&](const ConvArgs &t) { return launch_inst<64, 64, 2, 2, 32, true, MYDET_ACT_NONE, false, false, true, true>(t, lds, stream); }, fixup);
     }
-    if (a.nblk > 0)
-        rc = cin ? launch_act<BM, BN, WM, WN, BK, true>(a, lds, stream) : launch_act<BM, BN, WM, WN, BK, false>(a, lds, stream);
-    if (rc || !split) return rc;
-    a.tile0 = total - rem; a.splits = splits; a.nblk = rem * splits;
-    if (a.gate) {       // SE-gated project conv: the gate rides on the A operand, so the K slices sum like any others
-        if (cin) rc = launch_inst<BM, BN, WM, WN, BK, true, MYDET_ACT_NONE, false, true, true>(a, lds, stream);
-        else rc = launch_inst<BM, BN, WM, WN, BK, false, MYDET_ACT_NONE, false, true, true>(a, lds, stream);
-    } else {
-        if (cin) rc = launch_inst<BM, BN, WM, WN, BK, true, MYDET_ACT_NONE, false, false, true>(a, lds, stream);
-        else rc = launch_inst<BM, BN, WM, WN, BK, false, MYDET_ACT_NONE, false, false, true>(a, lds, stream);
-    }
-    if (rc) return rc;
-    return launch_fixup_act<BM, BN, WM, WN>(a, rem, stream);
+    return launch_with_tail(
+        a, pl,
+        [&](const ConvArgs &m) {
+            return cin ? launch_act<BM, BN, WM, WN, BK, true>(m, lds, stream) : launch_act<BM, BN, WM, WN, BK, false>(m, lds, stream);
+        },
+        [&](const ConvArgs &t) {
+            if (t.gate)     // SE-gated project conv: the gate rides on the A operand, so the K slices sum like any others
+                return cin ? launch_inst<BM, BN, WM, WN, BK, true, MYDET_ACT_NONE, false, true, true>(t, lds, stream)
+                           : launch_inst<BM, BN, WM, WN, BK, false, MYDET_ACT_NONE, false, true, true>(t, lds, stream);
+            return cin ? launch_inst<BM, BN, WM, WN, BK, true, MYDET_ACT_NONE, false, false, true>(t, lds, stream)
+                       : launch_inst<BM, BN, WM, WN, BK, false, MYDET_ACT_NONE, false, false, true>(t, lds, stream);
+        },
+        fixup);
 }
 
 // ---- split-bf16 launches (conv_igemm_b3_kernel): the same round / split-K-tail rule as `launch`, two workgroups per CU
@@ -984,14 +663,11 @@ int launch_b3_inst(const ConvArgs &a, hipStream_t stream) {
 }
 
 // The launch plan of the split-bf16 implicit GEMM (host only): one function for mydet_conv2d_igemm_b3_f32's launches and for
-// mydet_conv_b3_plan.  The tile form first, then the round / K-cut-tail rule of `plan_tiles` with this kernel's numbers: two
-// workgroups per CU (the wide form: one), 16-wide slabs, a tail only from 64 slabs, a small grid cut as a whole only from 32.
-struct B3Plan {
+// mydet_conv_b3_plan.  The tile form first, then the round / K-cut-tail rule with this kernel's numbers (TAIL_B3): two
+// workgroups per CU (the wide form: one), 16-wide slabs.
+struct B3Plan : TilePlan {
     int form;               // 0 default (4-wave workgroups), 1 wide (128 x 256 tile, 8 waves), 2 8-wave 128 x 128
     int BM, BN, WN;         // tile, waves along N
-    int ntiles, total;      // tiles along N, tiles in all
-    int rem, splits;        // tiles past the last whole round, K slices each of them would be cut into
-    bool split;             // the remainder runs as a K-cut tail
 };
 
 // The three switches of the form choice, read once per process; mydet_conv_b3_reload_tuning reads them again.
@@ -1017,78 +693,55 @@ int b3_refuses(int Cin, int Cout, bool one_tap) {
 }
 
 B3Plan plan_b3(int64_t M64, int K, int Cout, bool gated, size_t ws_bytes, int cus) {
-    B3Plan pl;
     const int tuned = b3_form();
-    pl.form = 0; pl.WN = 2;
+    int form = 0, BM = 128, BN = 128, WN = 2;
     if (Cout <= 64) {
-        pl.BM = 128; pl.BN = 64;
+        BN = 64;
     } else if (((M64 + 127) / 128) * ((Cout + 127) / 128) <= (g_b3_half_set ? g_b3_half : cus / 2)) {
         // at most half as many 128-row tiles as CUs (the EfficientNet project convs on a lane of 8-16 images): 64-row tiles, twice the
         // workgroups.  MYDET_B3_HALF_TILES overrides the limit (0 = never; tuning)
-        pl.BM = 64; pl.BN = 128;
+        BM = 64;
     } else {
         // two other forms stay selectable, both correct and tested, neither faster:
         //   MYDET_B3_WIDE=1  from 192 output channels a 128 x 256 tile, one 8-wave workgroup per CU, weights by LDS-DMA -- 0.66 / 0.75
         //                    / 0.66 ms vs 0.65 / 0.69 / 0.69 on the three deep stride-2 layers, 1 538 vs 1 545 images/s in the model;
         //   MYDET_B3_WAVES=8 8-wave workgroups (wave tile 64 x 32, four waves per SIMD) -- 5-10 % faster back to back, 0.7 % slower
         //                    in the model (1 510 vs 1 520 images/s, twice each in one call)
-        const int form = gated ? 0 : tuned;             // (the opt-in forms have no gated instances)
-        pl.BM = 128; pl.BN = 128;
-        if ((form & 1) && Cout > 192) { pl.form = 1; pl.BN = 256; pl.WN = 4; }
-        else if (form & 2) { pl.form = 2; pl.WN = 4; }
+        const int opt = gated ? 0 : tuned;              // (the opt-in forms have no gated instances)
+        if ((opt & 1) && Cout > 192) { form = 1; BN = 256; WN = 4; }
+        else if (opt & 2) { form = 2; WN = 4; }
     }
     // the wide form: one workgroup per CU, so a round is `cus` tiles (and Cin % 16 == 0: whole slabs)
-    const int slots = pl.form == 1 ? cus : 2 * cus;
-    const int nk = pl.form == 1 ? K / 16 : (K + 15) / 16;
-    const int mtiles = (int)((M64 + pl.BM - 1) / pl.BM);
-    pl.ntiles = (Cout + pl.BN - 1) / pl.BN;
-    const int total = pl.total = mtiles * pl.ntiles;
-    const int rounds = total / slots;
-    const int rem = pl.rem = total % slots;
-    const bool small = rounds == 0 && total * 4 <= slots && nk >= 32;
-    int splits = rem > 0 ? slots / rem : 0;
-    if (splits > 16) splits = 16;
-    if (splits > nk / 8) splits = nk / 8;
-    pl.splits = splits;
-    const size_t need = (size_t)rem * (splits > 0 ? splits : 0) * pl.BM * pl.BN * sizeof(float);
-    pl.split = rem > 0 && splits >= 2 && ws_bytes > 0 && need <= ws_bytes &&
-               (small || (nk >= 64 && rounds >= 2 && rounds <= 4 && rem * 2 <= slots));
+    B3Plan pl;
+    static_cast<TilePlan &>(pl) =
+        plan_tail(M64, Cout, BM, BN, form == 1 ? K / 16 : (K + 15) / 16, form == 1 ? cus : 2 * cus, ws_bytes, TAIL_B3);
+    pl.form = form; pl.BM = BM; pl.BN = BN; pl.WN = WN;
     return pl;
 }
 
 template <int BM, int BN, int WN = 2>
-int launch_b3(const ConvArgs &a0, const B3Plan &pl, hipStream_t stream) {
-    ConvArgs a = a0;
-    a.ntiles = pl.ntiles;
-    const int total = pl.total, rem = pl.rem, splits = pl.splits;
-    const bool split = pl.split;
-    a.tile0 = 0; a.splits = 1;
-    a.nblk = split ? total - rem : total;
+int launch_b3(const ConvArgs &a, const B3Plan &pl, hipStream_t stream) {
+    constexpr int PF = WN == 4 ? 2 : B3_PF;
     const bool res = a.res != nullptr;
-    int rc = 0;
+    auto fixup = [&](const ConvArgs &t, int rem) { return launch_fixup_act<BM, BN, 2, WN>(t, rem, stream); };
     if (a.gate) {           // squeeze-excite project convs: no activation (MYDET_E_UNSUPP otherwise: the caller's float32 kernel takes it)
         if (a.act != MYDET_ACT_NONE || WN != 2) return MYDET_E_UNSUPP;
-        if (a.nblk > 0)
-            rc = res ? launch_b3_inst<BM, BN, MYDET_ACT_NONE, true, false, B3_PF, 2, true>(a, stream)
-                     : launch_b3_inst<BM, BN, MYDET_ACT_NONE, false, false, B3_PF, 2, true>(a, stream);
-        if (rc || !split) return rc;
-        a.tile0 = total - rem; a.splits = splits; a.nblk = rem * splits;
-        rc = launch_b3_inst<BM, BN, MYDET_ACT_NONE, false, true, B3_PF, 2, true>(a, stream);
-        if (rc) return rc;
-        return launch_fixup_act<BM, BN, 2, WN>(a, rem, stream);
+        return launch_with_tail(
+            a, pl,
+            [&](const ConvArgs &m) {
+                return res ? launch_b3_inst<BM, BN, MYDET_ACT_NONE, true, false, B3_PF, 2, true>(m, stream)
+                           : launch_b3_inst<BM, BN, MYDET_ACT_NONE, false, false, B3_PF, 2, true>(m, stream);
+            },
+            [&](const ConvArgs &t) { return launch_b3_inst<BM, BN, MYDET_ACT_NONE, false, true, B3_PF, 2, true>(t, stream); }, fixup);
     }
-    if (a.nblk > 0) {
-        switch (a.act) {
-            case MYDET_ACT_LEAKY: rc = res ? launch_b3_inst<BM, BN, MYDET_ACT_LEAKY, true, false, (WN == 4 ? 2 : B3_PF), WN>(a, stream) : launch_b3_inst<BM, BN, MYDET_ACT_LEAKY, false, false, (WN == 4 ? 2 : B3_PF), WN>(a, stream); break;
-            case MYDET_ACT_SWISH: rc = res ? launch_b3_inst<BM, BN, MYDET_ACT_SWISH, true, false, (WN == 4 ? 2 : B3_PF), WN>(a, stream) : launch_b3_inst<BM, BN, MYDET_ACT_SWISH, false, false, (WN == 4 ? 2 : B3_PF), WN>(a, stream); break;
-            default: rc = res ? launch_b3_inst<BM, BN, MYDET_ACT_NONE, true, false, (WN == 4 ? 2 : B3_PF), WN>(a, stream) : launch_b3_inst<BM, BN, MYDET_ACT_NONE, false, false, (WN == 4 ? 2 : B3_PF), WN>(a, stream); break;
-        }
-    }
-    if (rc || !split) return rc;
-    a.tile0 = total - rem; a.splits = splits; a.nblk = rem * splits;
-    rc = launch_b3_inst<BM, BN, MYDET_ACT_NONE, false, true, (WN == 4 ? 2 : B3_PF), WN>(a, stream);
-    if (rc) return rc;
-    return launch_fixup_act<BM, BN, 2, WN>(a, rem, stream);
+    return launch_with_tail(
+        a, pl,
+        [&](const ConvArgs &m) {
+            return with_act_res(m.act, res, [&](auto act, auto r) {
+                return launch_b3_inst<BM, BN, decltype(act)::value, decltype(r)::value, false, PF, WN>(m, stream);
+            });
+        },
+        [&](const ConvArgs &t) { return launch_b3_inst<BM, BN, MYDET_ACT_NONE, false, true, PF, WN>(t, stream); }, fixup);
 }
 
 template <int ACT, bool RES, bool SPLIT>
@@ -1102,28 +755,16 @@ int launch_b3w_inst(const ConvArgs &a, hipStream_t stream) {
 }
 
 // the wide form (plan_b3: one workgroup per CU, so a round is `cus` tiles; same split-K-tail rule otherwise)
-int launch_b3w(const ConvArgs &a0, const B3Plan &pl, hipStream_t stream) {
-    constexpr int BM = 128, BN = 256;
-    ConvArgs a = a0;
-    a.ntiles = pl.ntiles;
-    const int total = pl.total, rem = pl.rem, splits = pl.splits;
-    const bool split = pl.split;
-    a.tile0 = 0; a.splits = 1;
-    a.nblk = split ? total - rem : total;
-    const bool res = a.res != nullptr;
-    int rc = 0;
-    if (a.nblk > 0) {
-        switch (a.act) {
-            case MYDET_ACT_LEAKY: rc = res ? launch_b3w_inst<MYDET_ACT_LEAKY, true, false>(a, stream) : launch_b3w_inst<MYDET_ACT_LEAKY, false, false>(a, stream); break;
-            case MYDET_ACT_SWISH: rc = res ? launch_b3w_inst<MYDET_ACT_SWISH, true, false>(a, stream) : launch_b3w_inst<MYDET_ACT_SWISH, false, false>(a, stream); break;
-            default: rc = res ? launch_b3w_inst<MYDET_ACT_NONE, true, false>(a, stream) : launch_b3w_inst<MYDET_ACT_NONE, false, false>(a, stream); break;
-        }
-    }
-    if (rc || !split) return rc;
-    a.tile0 = total - rem; a.splits = splits; a.nblk = rem * splits;
-    rc = launch_b3w_inst<MYDET_ACT_NONE, false, true>(a, stream);
-    if (rc) return rc;
-    return launch_fixup_act<BM, BN, 2, 4>(a, rem, stream);
+int launch_b3w(const ConvArgs &a, const B3Plan &pl, hipStream_t stream) {
+    return launch_with_tail(
+        a, pl,
+        [&](const ConvArgs &m) {
+            return with_act_res(m.act, m.res != nullptr, [&](auto act, auto r) {
+                return launch_b3w_inst<decltype(act)::value, decltype(r)::value, false>(m, stream);
+            });
+        },
+        [&](const ConvArgs &t) { return launch_b3w_inst<MYDET_ACT_NONE, false, true>(t, stream); },
+        [&](const ConvArgs &t, int rem) { return launch_fixup_act<128, 256, 2, 4>(t, rem, stream); });
 }
 
 // Workgroups per CU assumed for tile configuration 6: the runtime reports 4 (mydet_conv_igemm_occupancy; the two-slab
@@ -1207,6 +848,29 @@ int choose_cfg(int64_t M64, int Cin, int Cout, int taps) {
     return 8;
 }
 
+// 32-bit byte offsets: what one buffer descriptor covers (an output, the weights, a block's A window) stays below this
+constexpr int64_t LIM32 = 0x7FFFFFF0ll;
+// Bytes of a block's A window on an H x W x ld map: the images its rows touch (tiles are at most 256 rows of Ho x Wo outputs), +1
+int64_t window_bytes(int H, int W, int64_t ld, int Ho, int Wo) { return (int64_t)H * W * ld * 4 * (256 / ((int64_t)Ho * Wo) + 2); }
+
+// The argument block of an entry point (its checks done: M and K fit an int) but for the weight operand (w | wsplit) and the CAT
+// source, which the caller adds.  A workspace that is not 16-byte aligned is no workspace.
+ConvArgs conv_args(const float *x, int64_t ldx, const float *scale, const float *shift, const float *residual, int64_t ldr,
+                   const float *a_gate, void *workspace, int64_t workspace_bytes, float *y, int64_t ldy, int B, int H, int W, int Cin,
+                   int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, int act) {
+    ConvArgs a;
+    a.x = x; a.w = nullptr; a.scale = scale; a.shift = shift; a.res = residual; a.gate = a_gate; a.y = y;
+    a.ldx = ldx; a.ldr = ldr; a.ldy = ldy;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride;
+    a.pad_t = pad_t; a.pad_l = pad_l; a.Ho = Ho; a.Wo = Wo; a.act = act;
+    a.M = B * Ho * Wo; a.K = KH * KW * Cin; a.ntiles = 0; a.nblk = 0;
+    a.tile0 = 0; a.splits = 1;
+    a.x1 = nullptr; a.ldx1 = 0; a.C1 = 0; a.wsplit = nullptr;
+    a.ws = ((uintptr_t)workspace & 15) ? nullptr : (float *)workspace;
+    a.ws_bytes = workspace_bytes > 0 ? (size_t)workspace_bytes : 0;
+    return a;
+}
+
 }  // namespace
 
 extern "C" int mydet_conv2d_igemm_f32(const float *x, int64_t ldx, const float *w, const float *scale,
@@ -1224,27 +888,16 @@ extern "C" int mydet_conv2d_igemm_f32(const float *x, int64_t ldx, const float *
     if ((ldy & 3) || (residual && (ldr & 3))) return MYDET_E_UNSUPP;
     const int64_t M64 = (int64_t)B * Ho * Wo;
     if (M64 > (int64_t)1 << 30 || (int64_t)KH * KW * Cin > (int64_t)1 << 30) return MYDET_E_BADARG;
-    // 32-bit byte offsets inside a block's window (the images its 128 rows touch, +1) and the weights
-    const int64_t img_bytes = (int64_t)H * W * ldx * 4;
-    const int64_t span_imgs = 256 / ((int64_t)Ho * Wo) + 2;      // tiles are at most 256 rows
-    if ((int64_t)M64 * ldy * 4 >= 0x7FFFFFF0ll || (residual && (int64_t)M64 * ldr * 4 >= 0x7FFFFFF0ll))
-        return MYDET_E_UNSUPP;
+    // 32-bit byte offsets: the output, a block's window and the weights
+    if (M64 * ldy * 4 >= LIM32 || (residual && M64 * ldr * 4 >= LIM32)) return MYDET_E_UNSUPP;
     if (act < 0 || act > 2) return MYDET_E_BADARG;
-    if (KH * KW > 31 || img_bytes * span_imgs >= 0x7FFFFFF0ll || (int64_t)Cout * KH * KW * Cin * 4 >= 0x7FFFFFF0ll)
-        return MYDET_E_UNSUPP;
-    ConvArgs a;
+    if (KH * KW > 31 || window_bytes(H, W, ldx, Ho, Wo) >= LIM32 || (int64_t)Cout * KH * KW * Cin * 4 >= LIM32) return MYDET_E_UNSUPP;
     if (a_gate && (KH != 1 || KW != 1 || stride != 1 || act != MYDET_ACT_NONE || ((uintptr_t)a_gate & 15)))
         return MYDET_E_UNSUPP;
-    if (a_gate && (int64_t)B * Cin * 4 >= 0x7FFFFFF0ll) return MYDET_E_UNSUPP;      // gate[B][Cin] is read through one descriptor
-    a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.res = residual; a.gate = a_gate; a.y = y;
-    a.ldx = ldx; a.ldr = ldr; a.ldy = ldy;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride;
-    a.pad_t = pad_t; a.pad_l = pad_l; a.Ho = Ho; a.Wo = Wo; a.act = act;
-    a.M = (int)M64; a.K = KH * KW * Cin; a.ntiles = 0; a.nblk = 0;
-    a.tile0 = 0; a.splits = 1;
-    a.x1 = nullptr; a.ldx1 = 0; a.C1 = 0; a.wsplit = nullptr;
-    a.ws = ((uintptr_t)workspace & 15) ? nullptr : (float *)workspace;
-    a.ws_bytes = workspace_bytes > 0 ? (size_t)workspace_bytes : 0;
+    if (a_gate && (int64_t)B * Cin * 4 >= LIM32) return MYDET_E_UNSUPP;      // gate[B][Cin] is read through one descriptor
+    ConvArgs a = conv_args(x, ldx, scale, shift, residual, ldr, a_gate, workspace, workspace_bytes, y, ldy, B, H, W, Cin, Cout, KH, KW,
+                           stride, pad_t, pad_l, Ho, Wo, act);
+    a.w = w;
     hipStream_t s = (hipStream_t)stream;
     if (forced_cfg() >= 0) return launch_cfg(forced_cfg(), a, s);
     // few output channels behind a big map (MBConv project convs of the high-resolution stages): the LDS-free skinny
@@ -1315,20 +968,12 @@ extern "C" int mydet_conv2d_igemm_b3_f32(const float *x, int64_t ldx, const uint
     if (b3_refuses(Cin, Cout, KH == 1 && KW == 1) || (ldy & 3) || (residual && (ldr & 3))) return MYDET_E_UNSUPP;
     const int64_t M64 = (int64_t)B * Ho * Wo, K64 = (int64_t)KH * KW * Cin;
     if (M64 > (int64_t)1 << 30 || K64 > (int64_t)1 << 30) return MYDET_E_BADARG;
-    const int64_t img_bytes = (int64_t)H * W * ldx * 4;
-    const int64_t span_imgs = 256 / ((int64_t)Ho * Wo) + 2;
-    if (M64 * ldy * 4 >= 0x7FFFFFF0ll || (residual && M64 * ldr * 4 >= 0x7FFFFFF0ll)) return MYDET_E_UNSUPP;
-    if (KH * KW > 31 || img_bytes * span_imgs >= 0x7FFFFFF0ll || mydet_split_bf16_elems(Cout, (int)K64) * 2 >= 0x7FFFFFF0ll) return MYDET_E_UNSUPP;
-    if (a_gate && (int64_t)B * Cin * 4 >= 0x7FFFFFF0ll) return MYDET_E_UNSUPP;      // gate[B][Cin] is read through one descriptor
-    ConvArgs a;
-    a.x = x; a.w = nullptr; a.scale = scale; a.shift = shift; a.res = residual; a.gate = a_gate; a.y = y;
-    a.ldx = ldx; a.ldr = ldr; a.ldy = ldy;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride;
-    a.pad_t = pad_t; a.pad_l = pad_l; a.Ho = Ho; a.Wo = Wo; a.act = act;
-    a.M = (int)M64; a.K = (int)K64; a.ntiles = 0; a.nblk = 0; a.tile0 = 0; a.splits = 1;
-    a.x1 = nullptr; a.ldx1 = 0; a.C1 = 0; a.wsplit = w_planes;
-    a.ws = ((uintptr_t)workspace & 15) ? nullptr : (float *)workspace;
-    a.ws_bytes = workspace_bytes > 0 ? (size_t)workspace_bytes : 0;
+    if (M64 * ldy * 4 >= LIM32 || (residual && M64 * ldr * 4 >= LIM32)) return MYDET_E_UNSUPP;
+    if (KH * KW > 31 || window_bytes(H, W, ldx, Ho, Wo) >= LIM32 || mydet_split_bf16_elems(Cout, (int)K64) * 2 >= LIM32) return MYDET_E_UNSUPP;
+    if (a_gate && (int64_t)B * Cin * 4 >= LIM32) return MYDET_E_UNSUPP;      // gate[B][Cin] is read through one descriptor
+    ConvArgs a = conv_args(x, ldx, scale, shift, residual, ldr, a_gate, workspace, workspace_bytes, y, ldy, B, H, W, Cin, Cout, KH, KW,
+                           stride, pad_t, pad_l, Ho, Wo, act);
+    a.wsplit = w_planes;
     const B3Plan pl = plan_b3(M64, (int)K64, Cout, a_gate != nullptr, a.ws ? a.ws_bytes : 0, mydet_cu_count());
     hipStream_t s = (hipStream_t)stream;
     if (pl.form == 1) return launch_b3w(a, pl, s);
@@ -1347,7 +992,7 @@ extern "C" int mydet_conv_b3_plan(int B, int Ho, int Wo, int Cin, int Cout, int 
     const int64_t M64 = (int64_t)B * Ho * Wo, K64 = (int64_t)taps * Cin;
     if (M64 > (int64_t)1 << 30 || K64 > (int64_t)1 << 30) return MYDET_E_BADARG;
     // (the entry point's size limits that do not need the strides: the output at ldy = Cout -- which also keeps the tile count in an int)
-    if (M64 * Cout * 4 >= 0x7FFFFFF0ll || taps > 31 || mydet_split_bf16_elems(Cout, (int)K64) * 2 >= 0x7FFFFFF0ll) return MYDET_E_UNSUPP;
+    if (M64 * Cout * 4 >= LIM32 || taps > 31 || mydet_split_bf16_elems(Cout, (int)K64) * 2 >= LIM32) return MYDET_E_UNSUPP;
     const B3Plan pl = plan_b3(M64, (int)K64, Cout, gated != 0, workspace_bytes > 0 ? (size_t)workspace_bytes : 0, cus);
     out[0] = pl.form; out[1] = pl.BM; out[2] = pl.BN; out[3] = pl.WN;
     out[4] = pl.split ? pl.total - pl.rem : pl.total;
@@ -1401,20 +1046,12 @@ extern "C" int mydet_conv1x1_upcat_f32(const float *x_lo, int64_t ld_lo, int C_l
     // a shape the regular rule sends to another tile -- or to the skinny kernel -- is the caller's two launches
     if (forced_cfg() >= 0 ? forced_cfg() != 3 : (choose_cfg(M64, Cin, Cout, 1) != 3 || (Cout <= 48 && M64 >= 65536 && pw_skinny_on())))
         return MYDET_E_UNSUPP;
-    if (M64 > (int64_t)1 << 30 || M64 * ldy * 4 >= 0x7FFFFFF0ll) return MYDET_E_UNSUPP;
-    const int64_t span_imgs = 256 / ((int64_t)H * W) + 2;
-    if ((int64_t)H * W * ld_hi * 4 * span_imgs >= 0x7FFFFFF0ll || (int64_t)(H >> 1) * (W >> 1) * ld_lo * 4 * span_imgs >= 0x7FFFFFF0ll ||
-        (int64_t)Cout * Cin * 4 >= 0x7FFFFFF0ll)
+    if (M64 > (int64_t)1 << 30 || M64 * ldy * 4 >= LIM32) return MYDET_E_UNSUPP;
+    if (window_bytes(H, W, ld_hi, H, W) >= LIM32 || window_bytes(H >> 1, W >> 1, ld_lo, H, W) >= LIM32 || (int64_t)Cout * Cin * 4 >= LIM32)
         return MYDET_E_UNSUPP;
-    ConvArgs a;
-    a.x = x_hi; a.w = w; a.scale = scale; a.shift = shift; a.res = nullptr; a.gate = nullptr; a.y = y;
-    a.ldx = ld_hi; a.ldr = 0; a.ldy = ldy;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = 1; a.KW = 1; a.stride = 1;
-    a.pad_t = 0; a.pad_l = 0; a.Ho = H; a.Wo = W; a.act = act;
-    a.M = (int)M64; a.K = Cin; a.ntiles = 0; a.nblk = 0;
-    a.tile0 = 0; a.splits = 1;
-    a.x1 = x_lo; a.ldx1 = ld_lo; a.C1 = C_lo; a.wsplit = nullptr;
-    a.ws = ((uintptr_t)workspace & 15) ? nullptr : (float *)workspace;
-    a.ws_bytes = workspace_bytes > 0 ? (size_t)workspace_bytes : 0;
+    ConvArgs a = conv_args(x_hi, ld_hi, scale, shift, nullptr, 0, nullptr, workspace, workspace_bytes, y, ldy, B, H, W, Cin, Cout, 1, 1, 1,
+                           0, 0, H, W, act);
+    a.w = w;
+    a.x1 = x_lo; a.ldx1 = ld_lo; a.C1 = C_lo;
     return launch_cfg(3, a, (hipStream_t)stream);          // the tile the 1x1 layers of this shape take anyway (same k order)
 }

@@ -209,8 +209,6 @@ __global__ __launch_bounds__(256) void lr_tb_kernel(const LtArgs a) {
     }
 }
 
-bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int mydet_lr_tb_levels_f32(int n, const mydet_lr_tb_level *levels, int B, int C, void *stream) {

@@ -738,14 +738,6 @@ __global__ __launch_bounds__(256) void bifpn_fuse_kernel(const FuseArgs p) {
     }
 }
 
-inline unsigned grid_for(int64_t total) {
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
-}
-
-inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 inline bool dw_tiled() {      // MYDET_DW_TILED=0: the register-blocked kernels for stride 1 too (tuning / A-B)
     static int v = -1;
     if (v < 0) {

@@ -243,8 +243,6 @@ __global__ __launch_bounds__(256, 2) void mbconv_expand_dw_kernel(const MbArgs p
     }
 }
 
-inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 template <int K, int ST, int CIN>
 int launch(MbArgs &p, int B, hipStream_t stream) {
     using G = MbGeom<K, ST>;

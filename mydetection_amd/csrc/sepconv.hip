@@ -554,8 +554,6 @@ __global__ __launch_bounds__(256, 4) void sepconv_decode_kernel(const SpDecArgs 
 }
 
 
-inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int mydet_sepconv_nodes_f32(int n, const mydet_sepconv_node *nodes, int B, int C, void *stream) {

@@ -26,3 +26,17 @@ __device__ __forceinline__ void split3(const f32x4 v, bf16x4 &p0, bf16x4 &p1, bf
 // Piece product t of a k-step is (piece SPLIT_PA[t] of one operand) x (piece SPLIT_PB[t] of the other): small products first (the
 // running sum absorbs them at its own rounding either way)
 constexpr int SPLIT_PA[6] = {2, 1, 0, 1, 0, 0}, SPLIT_PB[6] = {0, 1, 2, 0, 1, 0};
+
+// The six piece products of one 16-wide k-step on a wave tile of TM x TN 32 x 32 blocks (af / bf: the three pieces of each block row's
+// fragment).  A piece pair sweeps all blocks of the wave tile before the next pair, so MFMAs on one accumulator are TM * TN
+// instructions apart.
+template <int TM, int TN>
+__device__ __forceinline__ void split_mfma6(const bf16x8 (&af)[TM][3], const bf16x8 (&bf)[TN][3], f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int t = 0; t < 6; ++t)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][SPLIT_PA[t]], bf[j][SPLIT_PB[t]], acc[i][j], 0, 0, 0);
+}

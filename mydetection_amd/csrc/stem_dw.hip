@@ -190,8 +190,6 @@ __global__ __launch_bounds__(256, 2) void stem_dw_kernel(const SdArgs p) {
     }
 }
 
-inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int mydet_stem_dw_f32(const float *x, int64_t sxb, int64_t sxc, int64_t sxh, int64_t sxw, const float *w_stem,
