@@ -1199,6 +1199,73 @@ int mydet_draw_boxes_rgb_u8(unsigned char *dst, int B, int H, int W, int64_t dst
 int mydet_draw_boxes_yuv420_u8(const mydet_yuv420_src *planes, int B, int H, int W, const mydet_draw_list *list,
                                const mydet_draw_style *style, void *stream);
 
+/* Redaction: the detections of a list are hidden -- pixelated, blurred or painted over -- IN PLACE in uint8 RGB frames or in the
+ * planes of the 8-bit 4:2:0 layouts, before a frame leaves the device for an encoder, a screen or a disk (csrc/redact.hip).  No
+ * reference counterpart: the rules are this library's own, integer-exact, and they are these.
+ *
+ * List.  The renderer's mydet_draw_list, read in place: a record buffer's planes or a dense [B,K,5] array.  The renderer's skip
+ *   rules hold unchanged: a row with a non-finite cx, cy, w, h or angle, or with w <= 0 or h <= 0, is skipped; a frame with
+ *   count <= 0 is skipped; a count above K means K; a NULL count means K.  Nothing outside the H x W view is read or written.
+ * Class filter.  n_classes == 0: every row is redacted.  n_classes in 1..MYDET_REDACT_MAX_CLASSES: only rows whose class is one
+ *   of classes[0..n_classes) (the shape of mydet_zone_set's filter); the list then needs its cls plane.
+ * Coverage.  The renderer's geometry: pixel centre (j + 0.5, i + 0.5); a, b, c and s exactly those of the overlay renderer
+ *   above (csrc/box_rot.h; angle == 0 makes no trigonometric call); float32, uncontracted.  With ra = (w * 0.5f) * pad and
+ *   rb = (h * 0.5f) * pad:
+ *       MYDET_REDACT_BOX      covered iff a <= ra && b <= rb
+ *       MYDET_REDACT_ELLIPSE  covered iff (a*rb)*(a*rb) + (b*ra)*(b*ra) <= (ra*rb)*(ra*rb)
+ *   A pixel is redacted iff some row of its frame covers it.  Row order and overlaps do not matter: every new value is a function
+ *   of the ORIGINAL frame and of the pixel's position only.
+ * Cells.  The cell grid is anchored at the frame origin; cell = c is even, MYDET_REDACT_MIN_CELL..MYDET_REDACT_MAX_CELL.  Cell
+ *   (I, J) holds rows [I*c, min(H, (I+1)*c)) and the matching columns; its mean, per channel and in integers, is
+ *   (2*S + n) / (2*n) (round half up) with S the channel's sum and n the number of the cell's pixels inside the frame.
+ * Modes.
+ *   MYDET_REDACT_MOSAIC  a redacted pixel becomes the mean of its cell.
+ *   MYDET_REDACT_SMOOTH  a redacted pixel becomes the bilinear interpolation of the cell means, each mean placed at its cell's
+ *       nominal centre, all in integers: u = 2*j + 1 - c, J0 = floor(u / (2c)), fx = u - 2c*J0 (in [0, 2c)), Ja = clamp(J0, 0,
+ *       nJ-1), Jb = clamp(J0+1, 0, nJ-1); v, I0, fy, Ia, Ib the same from i;
+ *           value = ((2c-fy)*((2c-fx)*M[Ia][Ja] + fx*M[Ia][Jb]) + fy*((2c-fx)*M[Ib][Ja] + fx*M[Ib][Jb]) + 2c^2) / (4c^2)
+ *       (fits int32 for c <= 64).  A strong blur whose cost does not depend on its radius.
+ *   MYDET_REDACT_SOLID   a redacted pixel becomes `color`; in 4:2:0 the colour goes through the renderer's RGB -> Y'CbCr table above.
+ * 4:2:0 targets (NV12, NV21, I420; YV12 = I420 with the planes exchanged by the caller; odd H and W legal; the 10-bit layouts are
+ *   MYDET_E_BADARG).  Luma is redacted per pixel with the luma cell means.  A chroma sample is redacted iff any luma pixel of its
+ *   quad is.  Chroma cells are c/2 x c/2 chroma samples anchored at the origin (c/2 may be odd); their means and the smooth
+ *   formula use c/2 in place of c on the chroma sample grid of ceil(H/2) x ceil(W/2).
+ * Launches.  The frames are written in place, a cell's mean must come from original pixels, and in `smooth` a pixel reads the
+ *   means of cells that another workgroup repaints.  So the entry point issues two kernels on the stream: the first reads the
+ *   frames and writes the mean of every cell the second may read (every cell that a non-skipped row's padded bounding box
+ *   reaches, one cell further in `smooth`) into `workspace`, mydet_redact_workspace_bytes(B, H, W, cell) bytes (one dword per
+ *   cell and frame; 4-byte aligned; its contents after the call are not part of the contract); the second reads the list and
+ *   the workspace only and stores the redacted pixels.  MYDET_REDACT_SOLID issues the second alone and takes a NULL workspace.
+ *   No host synchronisation, no allocation, no memset, no atomics on global memory: the pair can be captured in a graph and its
+ *   result is deterministic.  A block of cells or a tile (64 x 16 pixels RGB, 128 x 16 for 4:2:0) that no padded box reaches is
+ *   neither read nor written; in the others only covered pixels are stored -- with the renderer's dword accesses under the
+ *   renderer's alignment conditions where a whole pixel group is covered, byte by byte otherwise, with the same result.
+ * MYDET_E_BADARG, with nothing launched: what the renderer refuses for the list and the target; cell odd or outside
+ *   MYDET_REDACT_MIN_CELL..MYDET_REDACT_MAX_CELL; pad not finite or <= 0; an unknown mode or shape; n_classes outside
+ *   0..MYDET_REDACT_MAX_CLASSES; a class filter with a NULL cls plane; a NULL workspace when the mode needs one.
+ *   mydet_redact_workspace_bytes returns MYDET_E_BADARG for non-positive B, H, W or such a cell.
+ * MYDET_E_UNSUPP: B or ceil(H / 16) above 65535 (the renderer's grid limits), or H or W of 2^22 or more. */
+#define MYDET_REDACT_MOSAIC      0
+#define MYDET_REDACT_SMOOTH      1
+#define MYDET_REDACT_SOLID       2
+#define MYDET_REDACT_BOX         0
+#define MYDET_REDACT_ELLIPSE     1
+#define MYDET_REDACT_MIN_CELL    4
+#define MYDET_REDACT_MAX_CELL    64
+#define MYDET_REDACT_MAX_CLASSES 16
+typedef struct mydet_redact_style {
+    int mode, shape, cell;                   /* MYDET_REDACT_MOSAIC | _SMOOTH | _SOLID; MYDET_REDACT_BOX | _ELLIPSE; cell size */
+    float pad;                               /* the box is scaled by this before it is covered */
+    unsigned char color[4];                  /* R, G, B of MYDET_REDACT_SOLID; [3] ignored */
+    int n_classes;
+    int classes[MYDET_REDACT_MAX_CLASSES];
+} mydet_redact_style;
+int64_t mydet_redact_workspace_bytes(int B, int H, int W, int cell);
+int mydet_redact_boxes_rgb_u8(unsigned char *dst, int B, int H, int W, int64_t img_bytes, int64_t row_bytes,
+                              const mydet_draw_list *list, const mydet_redact_style *style, void *workspace, void *stream);
+int mydet_redact_boxes_yuv420_u8(const mydet_yuv420_src *planes, int B, int H, int W,
+                                 const mydet_draw_list *list, const mydet_redact_style *style, void *workspace, void *stream);
+
 /* Object chips: the image of every box of a list, cut out of uint8 RGB frames or of 4:2:0 planes, turned upright and resampled
  * to one fixed size ch x cw, one launch per batch (csrc/crop.hip).  What attribute and re-identification classifiers, plate and
  * face recognisers and thumbnails take.  No reference counterpart: the sampling rules are this library's own, and they are these.

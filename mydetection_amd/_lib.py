@@ -121,6 +121,9 @@ SIGNATURES = {
                                        c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_int, c_ptr],
     'mydet_draw_boxes_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr],
     'mydet_draw_boxes_yuv420_u8': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
+    'mydet_redact_workspace_bytes': [c_int, c_int, c_int, c_int],
+    'mydet_redact_boxes_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_redact_boxes_yuv420_u8': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr],
     'mydet_crop_boxes_rgb': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr],
     'mydet_crop_boxes_yuv420': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_eval_ious_f64': [c_ptr, c_ptr, c_ptr],
@@ -141,7 +144,8 @@ SIGNATURES = {
 
 
 RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems',
-               'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words', 'mydet_mot_scratch_bytes', 'mydet_zones_state_words'}
+               'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words', 'mydet_mot_scratch_bytes', 'mydet_zones_state_words',
+               'mydet_redact_workspace_bytes'}
 
 # detection record layout (MYDET_REC_* of include/mydet.h), in int32 words
 REC_TOPK = 512
@@ -175,6 +179,10 @@ ZONES_STATE_HEADER, ZONES_SLOT_WORDS = 148, 22
 DRAW_MAX_BOXES, DRAW_MAX_THICKNESS, DRAW_MAX_GLYPHS, DRAW_NAME_BYTES = 512, 64, 33, 16
 DRAW_COLOR_CLASS, DRAW_COLOR_ID, DRAW_COLOR_FIXED = 0, 1, 2
 DRAW_LABEL_CLASS, DRAW_LABEL_SCORE, DRAW_LABEL_ID = 1, 2, 4
+# redaction (mydet_redact_boxes_*): MYDET_REDACT_* of include/mydet.h
+REDACT_MOSAIC, REDACT_SMOOTH, REDACT_SOLID = 0, 1, 2
+REDACT_BOX, REDACT_ELLIPSE = 0, 1
+REDACT_MIN_CELL, REDACT_MAX_CELL, REDACT_MAX_CLASSES = 4, 64, 16
 # object chips (mydet_crop_boxes_*): MYDET_CROP_* of include/mydet.h
 CROP_MAX_SIDE, CROP_MAX_SLOTS = 256, 512
 CROP_U8, CROP_F32 = 0, 1
@@ -280,6 +288,12 @@ class DrawStyle(ctypes.Structure):
     _fields_ = [('thickness', c_int), ('fill_alpha', c_int), ('color_mode', c_int), ('label_flags', c_int),
                 ('color', ctypes.c_ubyte * 4), ('n_palette', c_int), ('ch', c_int), ('cw', c_int), ('n_names', c_int),
                 ('palette', c_ptr), ('atlas', c_ptr), ('names', c_ptr)]
+
+
+class RedactStyle(ctypes.Structure):
+    """mydet_redact_style (include/mydet.h)."""
+    _fields_ = [('mode', c_int), ('shape', c_int), ('cell', c_int), ('pad', c_f32), ('color', ctypes.c_ubyte * 4), ('n_classes', c_int),
+                ('classes', c_int * 16)]
 
 
 class CropOut(ctypes.Structure):

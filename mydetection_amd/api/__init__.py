@@ -1,13 +1,14 @@
 """Inference entry point of the package: `Detector` (mirror of the reference's api.detection.Detector), `Tiles`, the
 argument of its tiled detection on large frames, `Tracker`, the argument that turns its frame methods into a tracker,
-`Draw`, the settings of its annotate_frames methods, `Chips`, the settings of its crop_frames methods, `Nms`, how its
+`Draw`, the settings of its annotate_frames methods, `Redact`, the settings of its redact_frames methods (mosaic, blur or one
+colour over every detection, on the device), `Chips`, the settings of its crop_frames methods, `Nms`, how its
 post-process suppresses (class-agnostic, Soft-NMS, box merging), `Augment`, its test-time augmentation (mirrored and rescaled
 views fused on the device), `Evaluator`, which scores what it returns against ground
 truth, `TrackEvaluator`, which scores its tracks against ground-truth identities, and `Zones`, which counts its tracks in
 polygons and across lines on the device."""
-from .detection import Augment, Chips, Detector, Draw, Nms, Tiles
+from .detection import Augment, Chips, Detector, Draw, Nms, Redact, Tiles
 from .evaluation import Evaluator, TrackEvaluator
 from .tracking import Tracker
 from .zones import Zones
 
-__all__ = ['Augment', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Tiles', 'TrackEvaluator', 'Tracker', 'Zones']
+__all__ = ['Augment', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Redact', 'Tiles', 'TrackEvaluator', 'Tracker', 'Zones']

@@ -142,6 +142,38 @@ class Draw:
         return self._styles[key]
 
 
+class Redact:
+    """The settings of Detector.redact_frames and its YUV forms, and the `redact=` argument of annotate_frames*: how the detections
+    are hidden in the frames before they leave the device (ops.redact_boxes; include/mydet.h has the rules).  mode: 'mosaic'
+    (pixelate: a covered pixel becomes the mean of its cell), 'smooth' (the bilinear interpolation of the cell means: a strong
+    blur whose cost does not depend on its radius) or 'solid' (`color`).  cell: the cell size, even, 4..64; None =
+    min(64, max(4, 2 * ((min(H, W) + 48) // 96))) for frames of H x W (22 at 1080p).  shape: 'box' or 'ellipse'.  pad: the box is
+    scaled by it first (1.25 = a quarter more), finite and > 0.  classes: None = every detection, or 1..16 class indices = only
+    those (people but not cars).  color: the (r, g, b) of 'solid'."""
+
+    def __init__(self, mode='mosaic', cell=None, shape='box', pad=1.0, classes=None, color=(0, 0, 0)):
+        # ops.redact_style has the rules; a None cell is checked with a stand-in and resolved per frame size
+        checked = ops.redact_style(mode, 16 if cell is None else cell, shape, pad, classes, color)
+        self.mode, self.cell, self.shape, self.pad, self.classes, self.color = mode, cell, shape, checked.pad, checked.classes, checked.color
+        self._styles = {}
+
+    def __repr__(self):
+        return (f'Redact(mode={self.mode!r}, cell={self.cell}, shape={self.shape!r}, pad={self.pad}, classes={self.classes}, '
+                f'color={self.color})')
+
+    @staticmethod
+    def default_cell(frame_hw):
+        """The cell size of cell=None for frames of size frame_hw: about 1 / 48 of the shorter side, even, inside 4..64."""
+        return min(64, max(4, 2 * ((min(int(frame_hw[0]), int(frame_hw[1])) + 48) // 96)))
+
+    def style(self, frame_hw):
+        """The ops.RedactStyle for frames of size frame_hw (cached)."""
+        cell = self.default_cell(frame_hw) if self.cell is None else self.cell
+        if cell not in self._styles:
+            self._styles[cell] = ops.redact_style(self.mode, cell, self.shape, self.pad, self.classes, self.color)
+        return self._styles[cell]
+
+
 class Chips:
     """The settings of Detector.crop_frames and its YUV forms: the image of every detected object, cut out of the frame, turned
     upright and resampled to one size on the device (ops.crop_boxes; include/mydet.h has the sampling rules).  size: (height,
@@ -189,6 +221,17 @@ class _Frames:
             boxes, counts, scores, classes, ids = objects_to_rows(found, self.device())
             (ops.draw_boxes_yuv420 if yuv else ops.draw_boxes)(image, boxes=boxes, style=style, counts=counts, scores=scores, classes=classes,
                                                                ids=ids, **yuv)
+        return self.drawn()
+
+    def redact(self, found, style):
+        """Hide `found` (as in draw) in the frames; returns what redact_frames* returns as `redacted`."""
+        from ..utils.visualization import objects_to_rows
+        image, yuv = self.image()
+        if isinstance(found, dict):
+            ops.redact_records(image, found, style, **yuv)
+        else:
+            boxes, counts, _, classes, _ = objects_to_rows(found, self.device())
+            (ops.redact_boxes_yuv420 if yuv else ops.redact_boxes)(image, boxes=boxes, style=style, counts=counts, classes=classes, **yuv)
         return self.drawn()
 
     def crop(self, found, chip_kwargs):
@@ -729,17 +772,18 @@ class Detector():
         fused['img_hw'] = [src.hw if geos[0][3] is not None else geos[0][2]] * B
         return [(list(src.idxs), fused)]
 
-    def _detect(self, make_sources, kwargs, draw=None, chips=None):
+    def _detect(self, make_sources, kwargs, draw=None, chips=None, redact=None):
         """The one path behind every frame method that returns objects.  make_sources(): the call's frame sources, built (and
         so checked) once the tracker's type is known to be right; draw: a Draw, or chips: a Chips, for the methods that go on
-        to paint or cut out what was found (one source).  Returns the ImageObjects in frame order -- with draw, (objects,
-        what the source calls drawn); with chips, (objects, chip views).  An untracked call hands the records buffer to the
+        to paint or cut out what was found (one source); redact: a Redact, for those that hide it in the frames, before anything
+        is painted.  Returns the ImageObjects in frame order -- with draw or redact, (objects, what the source calls drawn); with
+        chips, (objects, chip views).  An untracked call hands the records buffer to the
         draw or crop launch before any host synchronisation; a tracked call hands it to the tracker (_tracked_objects) and
         paints or cuts out the returned tracks."""
         tracker, coasting = self._pop_tracker(kwargs)
         zones = self._pop_zones(kwargs, tracker)
         sources = make_sources()
-        used = draw is not None or chips is not None
+        used = draw is not None or chips is not None or redact is not None
         if tracker is not None:
             src = self._one_source(sources, 'tracked')
             tracker.check_call(src.n, src.hw, self.model.bb_format)
@@ -761,6 +805,8 @@ class Detector():
             records = list(records)
             (idxs, found), = records                                 # one frame size: one group, in frame order
             assert idxs == list(range(src.n))
+        if redact is not None:
+            made = src.redact(found, redact.style(src.hw))
         if draw is not None:
             made = src.draw(found, draw.style(src.hw, tracker is not None))
         elif chips is not None:
@@ -969,28 +1015,65 @@ class Detector():
             raise TypeError(f'{what}: {kind.__name__.lower()} is a mydetection_amd.api.{kind.__name__}, got {type(given).__name__}')
         return kind() if given is None else given
 
-    def annotate_frames(self, frames, draw=None, **kwargs):
+    def annotate_frames(self, frames, draw=None, redact=None, **kwargs):
         """predict_frames plus the overlay: returns (objects, drawn).  objects is exactly what predict_frames(frames, **kwargs)
         returns; drawn is the uint8 batch [B,H,W,3] on the device with boxes, fills and labels painted by ONE more launch
         (include/mydet.h: mydet_draw_boxes_rgb_u8) -- the input itself, drawn in place, when it is a single device tensor with
         packed pixels, else the device batch the call had to build anyway.  Frames of one size (ValueError otherwise).  draw: a
         Draw (default Draw()).  tiles=, tracker= and coasting= as in predict_frames.  An untracked call draws straight from the
-        records buffer, before any host synchronisation; a tracked call draws the returned tracks, with their ids."""
+        records buffer, before any host synchronisation; a tracked call draws the returned tracks, with their ids.  redact: None,
+        or a Redact: the detections are hidden first (as redact_frames does) and the overlay is painted on top."""
         draw = self._setting(draw, Draw, 'annotate_frames')
-        return self._detect(lambda: self._rgb_sources(frames, 'annotate_frames'), kwargs, draw=draw)
+        redact = self._redact_setting(redact, 'annotate_frames')
+        return self._detect(lambda: self._rgb_sources(frames, 'annotate_frames'), kwargs, draw=draw, redact=redact)
 
-    def annotate_frames_yuv(self, planes, layout, draw=None, *, matrix='bt601', full_range=False, **kwargs):
+    def annotate_frames_yuv(self, planes, layout, draw=None, redact=None, *, matrix='bt601', full_range=False, **kwargs):
         """predict_frames_yuv plus the overlay, painted into the planes (include/mydet.h: mydet_draw_boxes_yuv420_u8): returns
         (objects, drawn).  layout: 'nv12', 'nv21', 'i420' or 'yv12'; the 10-bit layouts are not drawn into (ValueError).  drawn:
         the planes on the device, in the order given -- the input tensors themselves when they are device tensors -- or, for a
-        single surface, the surface.  matrix and full_range also say how the colours become Y'CbCr.  Otherwise as annotate_frames."""
+        single surface, the surface.  matrix and full_range also say how the colours become Y'CbCr.  Otherwise as annotate_frames
+        (redact= included)."""
         draw = self._setting(draw, Draw, 'annotate_frames_yuv')
+        redact = self._redact_setting(redact, 'annotate_frames_yuv')
         return self._detect(lambda: [_Yuv420Frames(self, planes, layout, matrix, full_range, drawn_by='annotate_frames_yuv')], kwargs,
-                            draw=draw)
+                            draw=draw, redact=redact)
 
-    def annotate_frames_nv12(self, y, uv=None, draw=None, *, matrix='bt601', full_range=False, **kwargs):
+    def annotate_frames_nv12(self, y, uv=None, draw=None, redact=None, *, matrix='bt601', full_range=False, **kwargs):
         """annotate_frames_yuv for NV12: (y, uv) planes, or with uv=None the single surface [B,H*3/2,W] (see predict_frames_nv12)."""
-        return self.annotate_frames_yuv(y if uv is None else (y, uv), 'nv12', draw, matrix=matrix, full_range=full_range, **kwargs)
+        return self.annotate_frames_yuv(y if uv is None else (y, uv), 'nv12', draw, redact, matrix=matrix, full_range=full_range, **kwargs)
+
+    @staticmethod
+    def _redact_setting(given, what):
+        """The `redact=` of an annotate_frames* call: None, or a Redact (a TypeError for anything else)."""
+        if given is not None and not isinstance(given, Redact):
+            raise TypeError(f'{what}: redact is a mydetection_amd.api.Redact (or None), got {type(given).__name__}')
+        return given
+
+    def redact_frames(self, frames, redact=None, **kwargs):
+        """predict_frames plus the privacy step: returns (objects, redacted).  objects is exactly what predict_frames(frames,
+        **kwargs) returns (tiles=, augment=, nms=, tracker=, coasting= and zones= included); redacted is the uint8 batch
+        [B,H,W,3] on the device in which every detection is pixelated, blurred or painted over (include/mydet.h:
+        mydet_redact_boxes_rgb_u8) -- the input itself, redacted in place, when it is a single device tensor with packed
+        pixels, else the device batch the call had to build anyway.  Frames of one size (ValueError otherwise).  redact: a
+        Redact (default Redact(): a mosaic of every detection).  An untracked call launches straight from the records buffer,
+        before any host synchronisation.  A tracked call redacts the returned tracks: with coasting=True a person stays hidden
+        through the frames in which the detector misses them, as long as the track lives."""
+        redact = self._setting(redact, Redact, 'redact_frames')
+        return self._detect(lambda: self._rgb_sources(frames, 'redact_frames'), kwargs, redact=redact)
+
+    def redact_frames_yuv(self, planes, layout, redact=None, *, matrix='bt601', full_range=False, **kwargs):
+        """predict_frames_yuv plus the privacy step, in the planes (include/mydet.h: mydet_redact_boxes_yuv420_u8): returns
+        (objects, redacted).  layout: 'nv12', 'nv21', 'i420' or 'yv12'; the 10-bit layouts are not written into (ValueError).
+        redacted: the planes on the device, in the order given -- the input tensors themselves when they are device tensors -- or,
+        for a single surface, the surface.  matrix and full_range also say how the colour of 'solid' becomes Y'CbCr.  Otherwise
+        as redact_frames."""
+        redact = self._setting(redact, Redact, 'redact_frames_yuv')
+        return self._detect(lambda: [_Yuv420Frames(self, planes, layout, matrix, full_range, drawn_by='redact_frames_yuv')], kwargs,
+                            redact=redact)
+
+    def redact_frames_nv12(self, y, uv=None, redact=None, *, matrix='bt601', full_range=False, **kwargs):
+        """redact_frames_yuv for NV12: (y, uv) planes, or with uv=None the single surface [B,H*3/2,W] (see predict_frames_nv12)."""
+        return self.redact_frames_yuv(y if uv is None else (y, uv), 'nv12', redact, matrix=matrix, full_range=full_range, **kwargs)
 
     @staticmethod
     def _chip_views(buf, objs):

@@ -12,6 +12,7 @@
 // any chunk reads and writes no pixel.  The others load their pixels once, walk the short list per pixel and store the pixel
 // groups that changed: with dword stores when address, pitch and frame stride allow (see the header), byte by byte otherwise.
 #include "box_rot.h"
+#include "draw_yuv.h"
 #include "pixel_math.h"
 
 namespace {
@@ -20,12 +21,6 @@ constexpr int DR_THREADS = 256;
 constexpr int DR_TEXT = 36;                  // bytes of label text kept per hit (MYDET_DRAW_MAX_GLYPHS = 33 used)
 constexpr int DR_GLYPHS = 33;
 constexpr int DR_NAME = 16;                  // MYDET_DRAW_NAME_BYTES
-
-// RGB -> Y'CbCr rows, 8 fraction bits: [matrix: 0 = BT.601, 1 = BT.709][range: 0 = limited, 1 = full]; the only copy of the table
-struct DrawYuvK { int y[3], u[3], v[3], yoff; };
-constexpr DrawYuvK DRAW_YUV[2][2] = {
-    {{{66, 129, 25}, {-38, -74, 112}, {112, -94, -18}, 16}, {{77, 150, 29}, {-43, -85, 128}, {128, -107, -21}, 0}},
-    {{{47, 157, 16}, {-26, -86, 112}, {112, -102, -10}, 16}, {{54, 183, 18}, {-29, -99, 128}, {128, -116, -12}, 0}}};
 
 struct DrawHit {
     float cx, cy, hw, hh, c, s;              // centre, half sizes, cos, sin
@@ -44,14 +39,6 @@ struct DrawArgs {
     int v_first;                             // NV21: the pair is (V, U)
     DrawYuvK k;
 };
-
-__device__ __forceinline__ uint32_t draw_yuv_of(const DrawYuvK &k, uint32_t rgb) {
-    const int r = px_chan(rgb, 0), g = px_chan(rgb, 1), b = px_chan(rgb, 2);
-    const int y = ((k.y[0] * r + k.y[1] * g + k.y[2] * b + 128) >> 8) + k.yoff;
-    const int u = ((k.u[0] * r + k.u[1] * g + k.u[2] * b + 128) >> 8) + 128;
-    const int v = ((k.v[0] * r + k.v[1] * g + k.v[2] * b + 128) >> 8) + 128;
-    return px_pack(px_clamp(y, 0, 255), px_clamp(u, 0, 255), px_clamp(v, 0, 255));
-}
 
 // (colour * alpha + old * (255 - alpha) + 127) / 255 on one 8-bit value
 __device__ __forceinline__ int draw_blend1(int old, int col, int alpha) { return (col * alpha + old * (255 - alpha) + 127) / 255; }

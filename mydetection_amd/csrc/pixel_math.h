@@ -3,11 +3,11 @@
 #pragma once
 #include "common.h"
 
-__device__ __forceinline__ int px_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__host__ __device__ __forceinline__ int px_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // A pixel as one dword: r | g << 8 | b << 16
-__device__ __forceinline__ uint32_t px_pack(int r, int g, int b) { return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16); }
-__device__ __forceinline__ int px_chan(uint32_t v, int c) { return (int)((v >> (8 * c)) & 255u); }
+__host__ __device__ __forceinline__ uint32_t px_pack(int r, int g, int b) { return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16); }
+__host__ __device__ __forceinline__ int px_chan(uint32_t v, int c) { return (int)((v >> (8 * c)) & 255u); }
 
 // One output of Pillow's 8-bit fixed-point filter, three channels: clip8((2^21 + sum in * w) >> 22), w 22-bit integers
 struct PxFilter {

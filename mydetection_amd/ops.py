@@ -2784,6 +2784,144 @@ def draw_records(target, rec, style, layout=None, matrix='bt601', full_range=Fal
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# Redaction (include/mydet.h: mydet_redact_boxes_rgb_u8 / mydet_redact_boxes_yuv420_u8, where the rules are).
+
+REDACT_MODES = {'mosaic': _lib.REDACT_MOSAIC, 'smooth': _lib.REDACT_SMOOTH, 'solid': _lib.REDACT_SOLID}
+REDACT_SHAPES = {'box': _lib.REDACT_BOX, 'ellipse': _lib.REDACT_ELLIPSE}
+_REDACT_WS = {}
+
+
+class RedactStyle:
+    """What ops.redact_style returns: the checked settings of a redaction, on the host."""
+
+    def __init__(self, mode, cell, shape, pad, classes, color):
+        self.mode, self.cell, self.shape, self.pad, self.classes, self.color = mode, cell, shape, pad, classes, color
+
+    def __repr__(self):
+        return (f'RedactStyle(mode={self.mode!r}, cell={self.cell}, shape={self.shape!r}, pad={self.pad}, classes={self.classes}, '
+                f'color={self.color})')
+
+    def struct(self):
+        """The mydet_redact_style."""
+        s = _lib.RedactStyle()
+        s.mode, s.shape, s.cell, s.pad = REDACT_MODES[self.mode], REDACT_SHAPES[self.shape], self.cell, self.pad
+        s.color[0], s.color[1], s.color[2] = self.color
+        s.n_classes = len(self.classes or ())
+        for k, c in enumerate(self.classes or ()):
+            s.classes[k] = c
+        return s
+
+
+def redact_style(mode='mosaic', cell=16, shape='box', pad=1.0, classes=None, color=(0, 0, 0)):
+    """The settings of a redaction, checked here and touching no device (a RedactStyle; include/mydet.h has the rules).  mode:
+    'mosaic' (a covered pixel becomes the mean of its cell), 'smooth' (the bilinear interpolation of the cell means: a strong
+    blur) or 'solid' (`color`).  cell: the cell size, even, 4..64.  shape: 'box' or 'ellipse', what of a row is covered.  pad:
+    the row is scaled by it first, finite and > 0.  classes: None = every row, or 1..16 class indices = only rows of these.
+    color: the (r, g, b) of 'solid'."""
+    if not isinstance(mode, str) or mode not in REDACT_MODES:
+        raise ValueError(f'redact_style: mode {mode!r} is not one of {sorted(REDACT_MODES)}')
+    if not isinstance(shape, str) or shape not in REDACT_SHAPES:
+        raise ValueError(f'redact_style: shape {shape!r} is not one of {sorted(REDACT_SHAPES)}')
+    if isinstance(cell, bool) or not isinstance(cell, int) or not _lib.REDACT_MIN_CELL <= cell <= _lib.REDACT_MAX_CELL or cell % 2:
+        raise ValueError(f'redact_style: an even integer cell in {_lib.REDACT_MIN_CELL}..{_lib.REDACT_MAX_CELL} expected, got {cell!r}')
+    try:
+        pad = float(pad)
+    except (TypeError, ValueError):
+        raise ValueError(f'redact_style: pad is a finite number > 0, got {pad!r}') from None
+    if not (math.isfinite(pad) and pad > 0) or float(np.float32(pad)) <= 0 or not math.isfinite(float(np.float32(pad))):
+        raise ValueError(f'redact_style: pad is a finite number > 0, got {pad!r}')
+    if classes is not None:
+        try:
+            ok = all(isinstance(c, (int, np.integer)) and not isinstance(c, bool) for c in classes)
+            classes = tuple(int(c) for c in classes) if ok else None
+        except TypeError:
+            classes = None
+        if classes is None or not 1 <= len(classes) <= _lib.REDACT_MAX_CLASSES or any(not -2 ** 31 <= c < 2 ** 31 for c in classes):
+            raise ValueError(f'redact_style: classes is None or 1..{_lib.REDACT_MAX_CLASSES} class indices')
+    try:
+        color = tuple(int(v) for v in color)
+    except (TypeError, ValueError):
+        raise ValueError(f'redact_style: color = (r, g, b) expected, got {color!r}') from None
+    if len(color) != 3 or min(color) < 0 or max(color) > 255:
+        raise ValueError(f'redact_style: color = (r, g, b) with entries in 0..255 expected, got {color!r}')
+    return RedactStyle(mode, cell, shape, pad, classes, color)
+
+
+def _redact_check_style(style, what):
+    if not isinstance(style, RedactStyle):
+        raise TypeError(f'{what}: style is an ops.RedactStyle (ops.redact_style), got {type(style).__name__}')
+
+
+def _redact_launch(image, yuv, lst, style, dev):
+    """The two kernels of one redaction, one TIMER span; the means workspace is kept per (device, B, H, W, cell)."""
+    B, H, W = (image.shape if yuv is None else image[0].shape)[:3]
+    ws = None
+    if style.mode != 'solid':
+        key = (dev, B, H, W, style.cell)
+        if key not in _REDACT_WS:
+            _REDACT_WS[key] = torch.empty(_lib.lib().mydet_redact_workspace_bytes(B, H, W, style.cell) // 4, dtype=torch.int32, device=dev)
+        ws = _REDACT_WS[key]
+    s = style.struct()
+    _launch_on_image('redact_boxes', image, yuv, 'mydet_redact_boxes_rgb_u8', 'mydet_redact_boxes_yuv420_u8', ctypes.byref(lst), ctypes.byref(s),
+                     _ptr(ws))
+
+
+def _redact_dense(what, image, yuv, B, boxes, style, counts, classes):
+    _redact_check_style(style, what)
+    boxes, counts, planes = _box_rows(what, B, boxes, counts, None, classes, None)
+    if style.classes is not None and planes['classes'] is None:
+        raise ValueError(f'{what}: a style with a class filter needs classes')
+    K = boxes.shape[1]
+    if K > _lib.DRAW_MAX_BOXES:
+        raise ValueError(f'{what}: at most {_lib.DRAW_MAX_BOXES} rows per frame are redacted in one call (every new value comes from the '
+                         f'original frame), got {K}')
+    dev = _same_device(what, image, [boxes, counts, planes['classes']])
+    if K == 0:
+        return
+    boxes = boxes.contiguous()
+    counts = None if counts is None else counts.contiguous()
+    cls = planes['classes'].contiguous() if style.classes is not None else None
+    _redact_launch(image, yuv, _list_of_rows(boxes, 0, K, counts, {'cls': cls}), style, dev)
+
+
+def redact_boxes(frames, boxes, style, counts=None, classes=None):
+    """Hide boxes in uint8 RGB frames on the device, IN PLACE: mosaic, smooth blur or one colour (include/mydet.h:
+    mydet_redact_boxes_rgb_u8, where the rules are).  frames: [B,H,W,3] or [H,W,3] with packed pixels, any row and frame
+    strides (a crop view is redacted in place).  boxes: float32 [B,K,4|5] or [K,4|5], rows (cx, cy, w, h[, degrees]), K <= 512.
+    counts: int32 [B], the rows of each frame that are boxes (None: all K; above K means K).  classes: int64 [B,K], what a
+    style with a class filter reads.  Every new value is a function of the original frame: row order and overlaps do not
+    matter.  style: ops.redact_style(...).  Returns `frames`."""
+    what = 'redact_boxes'
+    _redact_dense(what, *_image(what, frames, None, None, None, True), boxes, style, counts, classes)
+    return frames
+
+
+def redact_boxes_yuv420(planes, layout, boxes, style, counts=None, classes=None, matrix='bt601', full_range=False):
+    """redact_boxes in the planes of 4:2:0 frames, IN PLACE (include/mydet.h: mydet_redact_boxes_yuv420_u8): planes, layout as
+    in draw_boxes_yuv420 ('nv12', 'nv21', 'i420', 'yv12'; odd H and W are legal; 'p010' / 'i010' give a ValueError).  matrix,
+    full_range: how the colour of 'solid' becomes Y'CbCr (ops.rgb_to_yuv).  Returns `planes`."""
+    what = 'redact_boxes_yuv420'
+    _redact_dense(what, *_image(what, planes, layout, matrix, full_range, True), boxes, style, counts, classes)
+    return planes
+
+
+def redact_records(target, rec, style, layout=None, matrix='bt601', full_range=False):
+    """Hide the detections of a record dict (ops.record_views; plain or rotated) in `target`, IN PLACE, reading the record's
+    planes through their strides -- nothing is copied or synchronised.  target: uint8 RGB frames [B,H,W,3] (layout None) or
+    the planes of `layout` as in redact_boxes_yuv420.  The dict must hold views of its 'records' buffer (a ValueError for
+    copies, as in draw_records).  Returns `target`."""
+    what = 'redact_records'
+    _redact_check_style(style, what)
+    records = _record_buffer(what, rec)
+    image, yuv, B = _image(what, target, layout, matrix, full_range, True)
+    if B != records.shape[0]:
+        raise ValueError(f'{what}: {B} frames and {records.shape[0]} records')
+    dev = _same_device(what, image, [records])
+    _redact_launch(image, yuv, _list_of_records(what, records, style.classes is not None, None), style, dev)
+    return target
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Object chips (include/mydet.h: mydet_crop_boxes_rgb / mydet_crop_boxes_yuv420, where the sampling rules are).
 
 CROP_OUTPUTS = ('uint8', 'input')
