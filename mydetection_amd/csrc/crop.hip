@@ -10,7 +10,7 @@
 // reading the count: such a slot is not written.  Source taps are plain global loads (the taps of a chip overlap and hit L2); a
 // tap is tested against the H x W view before it addresses anything, and reads the fill colour outside it.  The 4:2:0 form
 // converts every tap with yuv_pixel (yuv_fetch.h): the table, the formula and the 10-bit rule of yuv420.hip.
-#include "box_rot.h"
+#include "paint_tile.h"
 #include "yuv_fetch.h"
 
 namespace {
@@ -174,12 +174,7 @@ __global__ __launch_bounds__(CR_THREADS) void crop_kernel(const CropArgs p) {
 
 // The checks both entry points share; fills everything of `p` but the source
 int crop_setup(CropArgs &p, dim3 &grid, const mydet_draw_list *l, const mydet_crop_out *o, int B, int H, int W) {
-    if (!l || !o || B <= 0 || H <= 0 || W <= 0) return MYDET_E_BADARG;
-    if (!l->box || l->K < 1 || l->K > MYDET_DRAW_MAX_BOXES) return MYDET_E_BADARG;
-    const int64_t strides[] = {l->box_frame_stride, l->box_row_stride, l->angle_frame_stride, l->angle_row_stride, l->count_stride,
-                               o->frame_stride};
-    for (int64_t v : strides)
-        if (v < 0) return MYDET_E_BADARG;
+    if (!o || B <= 0 || H <= 0 || W <= 0 || paint_list_check(l, false) || o->frame_stride < 0) return MYDET_E_BADARG;
     if (!o->out || o->ch < 1 || o->ch > MYDET_CROP_MAX_SIDE || o->cw < 1 || o->cw > MYDET_CROP_MAX_SIDE) return MYDET_E_BADARG;
     if (o->M < 1 || o->M > MYDET_CROP_MAX_SLOTS) return MYDET_E_BADARG;
     if (!(o->pad > 0.0f) || !(o->pad <= 3.402823466e38f)) return MYDET_E_BADARG;          // NaN, infinity, <= 0

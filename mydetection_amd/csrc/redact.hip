@@ -5,22 +5,20 @@
 // A redacted pixel is a function of the ORIGINAL frame, and in `smooth` of cells that other workgroups repaint, so the entry
 // point issues two kernels on the stream:
 //   means  one workgroup of 256 lanes per block of whole cells, at least 64 x 16 pixels and a multiple of 4 pixels wide, so a
-//          lane owns the renderer's pixel group (4 pixels of a row; 4 x 2 luma pixels + 2 chroma samples in 4:2:0) and takes the
-//          renderer's dword loads.  A block that no padded box reaches (one cell further in `smooth`) reads nothing.  The others
-//          sum their pixels per cell with integer LDS atomics into 16 copies of the block's sums (lanes of a wave that hit one
-//          cell spread over them), add the copies up and write every cell's mean as one dword r | g << 8 | b << 16 (y | u << 8 |
-//          v << 16: the chroma cells of c/2 samples lie on the luma cells) into the workspace [B][nI][nJ].  Integer sums: any
-//          order gives the same bytes.  No global atomics, nothing to clear.
-//   paint  the renderer's tiles (64 x 16 RGB, 128 x 16 for 4:2:0) and its hit collection; it reads the list and the workspace
-//          only and stores the covered pixels: dwords where a whole group is covered and the alignment allows, bytes otherwise.
+//          lane owns a pixel group of paint_tile.h and takes its loads.  A block that no padded box reaches (one cell further
+//          in `smooth`) reads nothing.  The others sum their pixels per cell with integer LDS atomics into 16 copies of the
+//          block's sums (lanes of a wave that hit one cell spread over them), add the copies up and write every cell's mean as
+//          one dword r | g << 8 | b << 16 (y | u << 8 | v << 16: the chroma cells of c/2 samples lie on the luma cells) into the
+//          workspace [B][nI][nJ].  Integer sums: any order gives the same bytes.  No global atomics, nothing to clear.
+//   paint  the tiles, the hit compaction and the store of paint_tile.h; it reads the list and the workspace only and stores the
+//          covered pixels.
 // `solid` needs the second kernel alone.
-#include "box_rot.h"
 #include "draw_yuv.h"
-#include "pixel_math.h"
+#include "paint_tile.h"
 
 namespace {
 
-constexpr int RD_THREADS = 256;
+constexpr int RD_THREADS = PT_THREADS;
 constexpr int RD_COPIES = 16;                // copies of a block's cell sums in LDS
 constexpr int RD_CELLS = 64;                 // cells of a means block at most (cell 4: 4 x 16)
 
@@ -43,124 +41,27 @@ struct RedactArgs {
     int GI, GJ;                              // cells of a means block
     RedactDiv by_cell[2], by_two[2], by_whole[2];   // / cc, / (2 cc), / (4 cc^2) for cc = cell [0] and cell / 2 [1] (the chroma grid)
     RedactDiv by_groups;                     // / (pixel groups of a means block's row)
-    unsigned char *p[3];                     // RGB: p[0] = the frames.  4:2:0: Y; interleaved chroma or U; V
-    int64_t img[3], row[3];                  // bytes between frames / rows
-    int wide[3];                             // the plane takes the dword (planar chroma: 16-bit) accesses
-    int v_first;                             // NV21: the pair is (V, U)
+    PaintPlanes t;
     uint32_t color;                          // solid: r | g << 8 | b << 16, or y | u << 8 | v << 16
     uint32_t *means;                         // [B][nI][nJ]
 };
 
-// FMT: 0 = RGB, 1 = interleaved chroma (NV12 / NV21), 2 = planar chroma (I420).
-// The pixels one lane owns: RGB 4 pixels of row i0 from column j0; 4:2:0 rows i0, i0 + 1 (i0 even), columns j0 .. j0 + 3 and
-// their two chroma samples.  nr x nc of them lie inside the frame.
-struct RedactUnit {
-    int nr, nc, nq;
-    unsigned char *yo, *uo, *vo;
-    bool ywords, cwords;
-};
-
-template <int FMT>
-__device__ __forceinline__ RedactUnit redact_unit(const RedactArgs &p, int b, int i0, int j0) {
-    RedactUnit u;
-    u.nr = px_clamp(p.H - i0, 0, FMT == 0 ? 1 : 2);
-    u.nc = u.nr ? px_clamp(p.W - j0, 0, 4) : 0;
-    u.nq = (u.nc + 1) >> 1;
-    u.uo = u.vo = nullptr;
-    u.cwords = false;
-    if (FMT == 0) {
-        u.yo = p.p[0] + (int64_t)b * p.img[0] + (int64_t)i0 * p.row[0] + (int64_t)j0 * 3;
-    } else {
-        u.yo = p.p[0] + (int64_t)b * p.img[0] + (int64_t)i0 * p.row[0] + j0;
-        const int cw = (p.W + 1) >> 1;
-        if (FMT == 2) {
-            u.uo = p.p[1] + (int64_t)b * p.img[1] + (int64_t)(i0 >> 1) * p.row[1] + (j0 >> 1);
-            u.vo = p.p[2] + (int64_t)b * p.img[2] + (int64_t)(i0 >> 1) * p.row[2] + (j0 >> 1);
-        } else {
-            u.uo = p.p[1] + (int64_t)b * p.img[1] + (int64_t)(i0 >> 1) * p.row[1] + j0;
-        }
-        u.cwords = u.nq == 2 && (j0 >> 1) + 2 <= cw && (FMT == 2 ? (p.wide[1] && p.wide[2]) : p.wide[1]);
-    }
-    u.ywords = p.wide[0] && u.nc == 4;
-    return u;
-}
-
-// The sums of the unit's two halves (columns j0, j0 + 1 and j0 + 2, j0 + 3) over the pixels inside the frame: s[h] = (R, G, B)
-// or (Y, U, V) -- one chroma sample per half --; have[h]: the half has a pixel
-template <int FMT>
-__device__ __forceinline__ void redact_load(const RedactArgs &p, const RedactUnit &u, int s[2][3], bool have[2]) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) { s[h][0] = s[h][1] = s[h][2] = 0; have[h] = u.nc > 2 * h; }
-    if (!u.nc) return;
-    if (FMT == 0) {
-        uint32_t px[4] = {0, 0, 0, 0};
-        if (u.ywords) {
-            const uint32_t *o4 = reinterpret_cast<const uint32_t *>(u.yo);
-            const uint32_t w0 = o4[0], w1 = o4[1], w2 = o4[2];
-            px[0] = w0 & 0xffffffu; px[1] = (w0 >> 24) | ((w1 & 0xffffu) << 8); px[2] = (w1 >> 16) | ((w2 & 0xffu) << 16); px[3] = w2 >> 8;
-        } else {
-            for (int k = 0; k < u.nc; ++k) px[k] = px_pack(u.yo[3 * k], u.yo[3 * k + 1], u.yo[3 * k + 2]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)                                       // pixels past nc are 0
-#pragma unroll
-            for (int c = 0; c < 3; ++c) s[k >> 1][c] += px_chan(px[k], c);
-    } else {
-        for (int r = 0; r < u.nr; ++r) {
-            const unsigned char *yr = u.yo + (int64_t)r * p.row[0];
-            if (u.ywords) {
-                const uint32_t w = *reinterpret_cast<const uint32_t *>(yr);
-                s[0][0] += (int)(w & 255u) + (int)((w >> 8) & 255u);
-                s[1][0] += (int)((w >> 16) & 255u) + (int)(w >> 24);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) if (k < u.nc) s[k >> 1][0] += yr[k];
-            }
-        }
-        const int su = p.v_first ? 1 : 0;                                // byte of U inside an interleaved pair
-        if (FMT == 2) {
-            if (u.cwords) {
-                const uint32_t a = *reinterpret_cast<const uint16_t *>(u.uo), v = *reinterpret_cast<const uint16_t *>(u.vo);
-                s[0][1] = a & 255u; s[1][1] = a >> 8; s[0][2] = v & 255u; s[1][2] = v >> 8;
-            } else {
-                for (int q = 0; q < u.nq; ++q) { s[q][1] = u.uo[q]; s[q][2] = u.vo[q]; }
-            }
-        } else {
-            if (u.cwords) {
-                const uint32_t w = *reinterpret_cast<const uint32_t *>(u.uo);
-                s[0][1] = (w >> (8 * su)) & 255u; s[0][2] = (w >> (8 * (1 - su))) & 255u;
-                s[1][1] = (w >> (16 + 8 * su)) & 255u; s[1][2] = (w >> (16 + 8 * (1 - su))) & 255u;
-            } else {
-                for (int q = 0; q < u.nq; ++q) { s[q][1] = u.uo[2 * q + su]; s[q][2] = u.uo[2 * q + 1 - su]; }
-            }
-        }
-    }
-}
-
 // Row r of frame b: false when the rules skip it or the class filter leaves it out; else its geometry and (ex, ey), the half
-// extents of the padded shape's bounding box, one pixel wider (the renderer's margin for float32 rounding)
+// extents of the padded shape's bounding box
 __device__ __forceinline__ bool redact_row(const RedactArgs &p, int b, int r, RedactHit &o, float &ex, float &ey) {
     const mydet_draw_list &l = p.l;
-    const float *bx = l.box + (int64_t)b * l.box_frame_stride + (int64_t)r * l.box_row_stride;
-    const float cx = bx[0], cy = bx[1], w = bx[2], h = bx[3];
-    const float ang = l.angle ? l.angle[(int64_t)b * l.angle_frame_stride + (int64_t)r * l.angle_row_stride] : 0.0f;
-    if (!(isfinite(cx) && isfinite(cy) && isfinite(w) && isfinite(h) && isfinite(ang) && w > 0.0f && h > 0.0f)) return false;
     if (p.s.n_classes > 0) {
         const int64_t cls = l.cls[(int64_t)b * l.cls_frame_stride + (int64_t)r * l.cls_row_stride];
         bool in = false;
         for (int k = 0; k < p.s.n_classes; ++k) in = in || cls == (int64_t)p.s.classes[k];
         if (!in) return false;
     }
-    o.cx = cx; o.cy = cy;
-    o.ra = (w * 0.5f) * p.s.pad; o.rb = (h * 0.5f) * p.s.pad;
-    box_rotation<false>(ang, o.c, o.s);
-    ex = fabsf(o.c) * o.ra + fabsf(o.s) * o.rb + 1.0f;
-    ey = fabsf(o.s) * o.ra + fabsf(o.c) * o.rb + 1.0f;
+    PaintRow g;
+    if (!paint_row(l, b, r, g)) return false;
+    o.cx = g.cx; o.cy = g.cy; o.c = g.c; o.s = g.s;
+    o.ra = (g.w * 0.5f) * p.s.pad; o.rb = (g.h * 0.5f) * p.s.pad;
+    paint_extents(o.c, o.s, o.ra, o.rb, ex, ey);
     return true;
-}
-
-__device__ __forceinline__ bool redact_reaches(const RedactHit &h, float ex, float ey, float x0, float y0, float x1, float y1) {
-    return !(h.cx - ex > x1 || h.cx + ex < x0 || h.cy - ey > y1 || h.cy + ey < y0);
 }
 
 __device__ __forceinline__ bool redact_covers(const RedactHit &h, int shape, int i, int j) {
@@ -169,11 +70,6 @@ __device__ __forceinline__ bool redact_covers(const RedactHit &h, int shape, int
     if (shape == MYDET_REDACT_BOX) return a <= h.ra && b <= h.rb;
     const float u = a * h.rb, v = b * h.ra, w = h.ra * h.rb;
     return u * u + v * v <= w * w;
-}
-
-__device__ __forceinline__ int redact_count(const RedactArgs &p, int b) {
-    const int cnt = p.l.count ? p.l.count[(int64_t)b * p.l.count_stride] : p.l.K;
-    return min(cnt, p.l.K);
 }
 
 __device__ __forceinline__ int redact_mean(int S, int n) { return (2 * S + n) / (2 * n); }
@@ -185,7 +81,7 @@ __global__ __launch_bounds__(RD_THREADS) void redact_means_kernel(const RedactAr
     const int c = p.s.cell;
     const int I0 = blockIdx.y * p.GI, J0 = blockIdx.x * p.GJ;
     const int y0 = I0 * c, x0 = J0 * c;
-    const int cnt = redact_count(p, b);
+    const int cnt = paint_count(p.l, b);
     if (cnt <= 0) return;
     {                                                                     // does a padded box reach the block, or (smooth) its neighbours?
         const float d = p.s.mode == MYDET_REDACT_SMOOTH ? (float)c : 0.0f;
@@ -194,22 +90,22 @@ __global__ __launch_bounds__(RD_THREADS) void redact_means_kernel(const RedactAr
         for (int r = tid; r < cnt; r += RD_THREADS) {
             RedactHit h;
             float ex, ey;
-            if (redact_row(p, b, r, h, ex, ey) && redact_reaches(h, ex, ey, bx0, by0, bx1, by1)) hit = 1;
+            if (redact_row(p, b, r, h, ex, ey) && paint_reaches(h.cx, h.cy, ex, ey, bx0, by0, bx1, by1)) hit = 1;
         }
         if (!__syncthreads_or(hit)) return;
     }
     for (int e = tid; e < RD_COPIES * RD_CELLS * 3; e += RD_THREADS) (&sums[0][0][0])[e] = 0;
     __syncthreads();
-    constexpr int UH = FMT == 0 ? 1 : 2;                                  // rows of a lane's unit
+    constexpr int UH = FMT == 0 ? 1 : 2;                                  // rows of a lane's group
     const int ng = (p.GJ * c) >> 2, units = ng * ((p.GI * c) / UH);
     const int copy = tid & (RD_COPIES - 1);
     for (int idx = tid; idx < units; idx += RD_THREADS) {
         const int ur = redact_div(idx, p.by_groups), g = idx - ur * ng;
         const int i0 = y0 + ur * UH, j0 = x0 + 4 * g;
-        const RedactUnit u = redact_unit<FMT>(p, b, i0, j0);
+        const PaintGroup u = paint_group<FMT>(p.t, p.H, p.W, b, i0, j0);
         int s[2][3];
         bool have[2];
-        redact_load<FMT>(p, u, s, have);
+        paint_load_halves<FMT>(p.t, u, s, have);
         const int ci = redact_div(ur * UH, p.by_cell[0]);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -232,26 +128,14 @@ __global__ __launch_bounds__(RD_THREADS) void redact_means_kernel(const RedactAr
 }
 
 // Rows lo, lo + 1, ... (one per lane, below cnt) of frame b against the tile [tx0, tx0 + TW) x [ty0, ty0 + TH): the hits into
-// `hits`; returns their number.  Every lane of the workgroup calls it (two barriers inside).  The renderer's draw_collect
-// without colours, labels and paint order.
+// `hits`; returns their number.  Every lane of the workgroup calls it (two barriers inside).
 __device__ int redact_collect(const RedactArgs &p, int b, int lo, int cnt, int tx0, int ty0, int TW, int TH, RedactHit *hits, int *wave_cnt) {
-    const int tid = threadIdx.x, r = lo + tid;
+    const int r = lo + (int)threadIdx.x;
     RedactHit h;
     float ex, ey;
-    const bool hit = r < cnt && redact_row(p, b, r, h, ex, ey) && redact_reaches(h, ex, ey, (float)tx0, (float)ty0, (float)(tx0 + TW), (float)(ty0 + TH));
-    const unsigned long long m = __ballot(hit);
-    const int lane = tid & 63, wv = tid >> 6;
-    if (lane == 0) wave_cnt[wv] = __popcll(m);
-    __syncthreads();
-    int base = 0, total = 0;
-    for (int k = 0; k < RD_THREADS / 64; ++k) {
-        const int n = wave_cnt[k];
-        if (k < wv) base += n;
-        total += n;
-    }
-    if (hit) hits[base + __popcll(m & ((1ull << lane) - 1ull))] = h;
-    __syncthreads();
-    return total;
+    const bool hit = r < cnt && redact_row(p, b, r, h, ex, ey) &&
+                     paint_reaches(h.cx, h.cy, ex, ey, (float)tx0, (float)ty0, (float)(tx0 + TW), (float)(ty0 + TH));
+    return paint_compact(hit, wave_cnt, [&](int slot) { hits[slot] = h; });
 }
 
 // The new value at sample (i, j) of the luma / RGB grid (G = 0: cells of c x c samples) or of the chroma grid (G = 1: c/2 x c/2):
@@ -284,12 +168,12 @@ __global__ __launch_bounds__(RD_THREADS) void redact_paint_kernel(const RedactAr
     constexpr int TW = FMT == 0 ? 64 : 128;
     const int tid = threadIdx.x, b = blockIdx.z;
     const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * 16;
-    const int cnt = redact_count(p, b);
+    const int cnt = paint_count(p.l, b);
     if (cnt <= 0) return;
     const int i0 = FMT == 0 ? ty0 + (tid >> 4) : ty0 + 2 * (tid >> 5);
     const int j0 = FMT == 0 ? tx0 + 4 * (tid & 15) : tx0 + 4 * (tid & 31);
-    const RedactUnit u = redact_unit<FMT>(p, b, i0, j0);
-    const unsigned rowbits = (1u << u.nc) - 1u, all = u.nr == 2 ? (rowbits | (rowbits << 4)) : (u.nr ? rowbits : 0u);
+    const PaintGroup u = paint_group<FMT>(p.t, p.H, p.W, b, i0, j0);
+    const unsigned all = paint_inside(u);
     unsigned cov = 0;                                                     // bit 4 * r + k: pixel (i0 + r, j0 + k) is redacted
     for (int lo = 0; lo < cnt; lo += RD_THREADS) {
         const int n = redact_collect(p, b, lo, cnt, tx0, ty0, TW, 16, hits, wave_cnt);
@@ -307,67 +191,26 @@ __global__ __launch_bounds__(RD_THREADS) void redact_paint_kernel(const RedactAr
     }
     if (!cov) return;
     const uint32_t *M = p.means + (int64_t)b * p.nI * p.nJ;
-    if (FMT == 0) {
+    if constexpr (FMT == 0) {
         uint32_t px[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int k = 0; k < 4; ++k) if (cov & (1u << k)) px[k] = redact_value<0>(p, M, i0, j0 + k, 0, 3);
-        if (u.ywords && cov == 0xfu) {
-            uint32_t *o4 = reinterpret_cast<uint32_t *>(u.yo);
-            o4[0] = px[0] | (px[1] << 24);
-            o4[1] = (px[1] >> 8) | (px[2] << 16);
-            o4[2] = (px[2] >> 16) | (px[3] << 8);
-        } else {
+        paint_store(u, px, cov);
+    } else {
+        int Y[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, U[2] = {0, 0}, V[2] = {0, 0};
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (cov & (1u << k)) {
-                    u.yo[3 * k] = (unsigned char)px[k]; u.yo[3 * k + 1] = (unsigned char)(px[k] >> 8); u.yo[3 * k + 2] = (unsigned char)(px[k] >> 16);
-                }
-        }
-        return;
-    }
+                if (cov & (1u << (4 * r + k))) Y[r][k] = px_chan(redact_value<0>(p, M, i0 + r, j0 + k, 0, 1), 0);
+        const unsigned cq = paint_quads(cov);                             // a chroma sample is redacted iff a pixel of its quad is
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const unsigned m = (cov >> (4 * r)) & 15u;
-        if (!m) continue;
-        unsigned char *yr = u.yo + (int64_t)r * p.row[0];
-        uint32_t Y[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) if (m & (1u << k)) Y[k] = redact_value<0>(p, M, i0 + r, j0 + k, 0, 1) & 255u;
-        if (u.ywords && m == 15u) {
-            *reinterpret_cast<uint32_t *>(yr) = Y[0] | (Y[1] << 8) | (Y[2] << 16) | (Y[3] << 24);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (m & (1u << k)) yr[k] = (unsigned char)Y[k];
-        }
-    }
-    bool cq[2];                                                           // a chroma sample is redacted iff a pixel of its quad is
-    int U[2] = {0, 0}, V[2] = {0, 0};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        cq[q] = (cov & (0x33u << (2 * q))) != 0;
-        if (cq[q]) {
-            const uint32_t v = redact_value<1>(p, M, i0 >> 1, (j0 >> 1) + q, 1, 3);
-            U[q] = px_chan(v, 1); V[q] = px_chan(v, 2);
-        }
-    }
-    const int su = p.v_first ? 1 : 0;
-    if (FMT == 2) {
-        if (u.cwords && cq[0] && cq[1]) {
-            *reinterpret_cast<uint16_t *>(u.uo) = (uint16_t)(U[0] | (U[1] << 8));
-            *reinterpret_cast<uint16_t *>(u.vo) = (uint16_t)(V[0] | (V[1] << 8));
-        } else {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) if (cq[q]) { u.uo[q] = (unsigned char)U[q]; u.vo[q] = (unsigned char)V[q]; }
-        }
-    } else {
-        if (u.cwords && cq[0] && cq[1]) {
-            const uint32_t p0 = (uint32_t)(su ? (V[0] | (U[0] << 8)) : (U[0] | (V[0] << 8)));
-            const uint32_t p1 = (uint32_t)(su ? (V[1] | (U[1] << 8)) : (U[1] | (V[1] << 8)));
-            *reinterpret_cast<uint32_t *>(u.uo) = p0 | (p1 << 16);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) if (cq[q]) { u.uo[2 * q + su] = (unsigned char)U[q]; u.uo[2 * q + 1 - su] = (unsigned char)V[q]; }
-        }
+        for (int q = 0; q < 2; ++q)
+            if (cq & (1u << q)) {
+                const uint32_t v = redact_value<1>(p, M, i0 >> 1, (j0 >> 1) + q, 1, 3);
+                U[q] = px_chan(v, 1); V[q] = px_chan(v, 2);
+            }
+        paint_store<FMT>(p.t, u, Y, U, V, cov, cq);
     }
 }
 
@@ -375,13 +218,7 @@ bool redact_cell_ok(int cell) { return cell >= MYDET_REDACT_MIN_CELL && cell <= 
 
 // The checks both entry points share; fills the list, the style, the view, the cell grid and the means block of `p`
 int redact_check(const mydet_draw_list *l, const mydet_redact_style *s, int B, int H, int W, void *workspace, RedactArgs &p) {
-    if (!l || !s || B <= 0 || H <= 0 || W <= 0) return MYDET_E_BADARG;
-    if (!l->box || l->K < 1 || l->K > MYDET_DRAW_MAX_BOXES) return MYDET_E_BADARG;
-    const int64_t strides[] = {l->box_frame_stride, l->box_row_stride, l->angle_frame_stride, l->angle_row_stride, l->score_frame_stride,
-                               l->score_row_stride, l->cls_frame_stride, l->cls_row_stride, l->id_frame_stride, l->id_row_stride,
-                               l->count_stride};
-    for (int64_t v : strides)
-        if (v < 0) return MYDET_E_BADARG;
+    if (!s || B <= 0 || H <= 0 || W <= 0 || paint_list_check(l, true)) return MYDET_E_BADARG;
     if (s->mode != MYDET_REDACT_MOSAIC && s->mode != MYDET_REDACT_SMOOTH && s->mode != MYDET_REDACT_SOLID) return MYDET_E_BADARG;
     if (s->shape != MYDET_REDACT_BOX && s->shape != MYDET_REDACT_ELLIPSE) return MYDET_E_BADARG;
     if (!redact_cell_ok(s->cell) || !(s->pad > 0.0f) || !(s->pad <= 3.402823466e38f)) return MYDET_E_BADARG;
@@ -429,11 +266,9 @@ extern "C" int64_t mydet_redact_workspace_bytes(int B, int H, int W, int cell) {
 extern "C" int mydet_redact_boxes_rgb_u8(unsigned char *dst, int B, int H, int W, int64_t img_bytes, int64_t row_bytes,
                                          const mydet_draw_list *list, const mydet_redact_style *style, void *workspace, void *stream) {
     RedactArgs p = {};
-    const int code = redact_check(list, style, B, H, W, workspace, p);
+    int code = redact_check(list, style, B, H, W, workspace, p);
+    if (!code) code = paint_planes_rgb(p.t, dst, img_bytes, row_bytes, W);
     if (code) return code;
-    if (!dst || row_bytes < (int64_t)W * 3 || img_bytes < 0) return MYDET_E_BADARG;
-    p.p[0] = dst; p.img[0] = img_bytes; p.row[0] = row_bytes;
-    p.wide[0] = (((uintptr_t)dst | (uintptr_t)img_bytes | (uintptr_t)row_bytes) & 3) == 0;
     p.color = px_pack(style->color[0], style->color[1], style->color[2]);
     return redact_launch<0>(p, B, (hipStream_t)stream);
 }
@@ -441,25 +276,9 @@ extern "C" int mydet_redact_boxes_rgb_u8(unsigned char *dst, int B, int H, int W
 extern "C" int mydet_redact_boxes_yuv420_u8(const mydet_yuv420_src *planes, int B, int H, int W, const mydet_draw_list *list,
                                             const mydet_redact_style *style, void *workspace, void *stream) {
     RedactArgs p = {};
-    const int code = redact_check(list, style, B, H, W, workspace, p);
+    int code = redact_check(list, style, B, H, W, workspace, p);
+    if (!code) code = paint_planes_yuv420(p.t, planes, W);
     if (code) return code;
-    if (!planes || !planes->plane[0] || !planes->plane[1]) return MYDET_E_BADARG;
-    if (planes->layout != MYDET_YUV420_NV12 && planes->layout != MYDET_YUV420_NV21 && planes->layout != MYDET_YUV420_I420)
-        return MYDET_E_BADARG;                                            // unknown, or a 10-bit layout
-    if (planes->matrix < 0 || planes->matrix > 1 || planes->full_range < 0 || planes->full_range > 1) return MYDET_E_BADARG;
-    const bool planar = planes->layout == MYDET_YUV420_I420;
-    if ((planes->plane[2] != nullptr) != planar) return MYDET_E_BADARG;
-    const int64_t cw = ((int64_t)W + 1) / 2;
-    const int64_t need[3] = {(int64_t)W, planar ? cw : 2 * cw, cw};
-    const int wide[3] = {4, planar ? 2 : 4, 2};
-    for (int i = 0; i < (planar ? 3 : 2); ++i) {
-        if (planes->row_bytes[i] < need[i] || planes->img_bytes[i] < 0) return MYDET_E_BADARG;
-        const uintptr_t bits = (uintptr_t)planes->plane[i] | (uintptr_t)planes->row_bytes[i] | (uintptr_t)planes->img_bytes[i];
-        p.p[i] = static_cast<unsigned char *>(const_cast<void *>(planes->plane[i]));
-        p.img[i] = planes->img_bytes[i]; p.row[i] = planes->row_bytes[i];
-        p.wide[i] = (bits & (uintptr_t)(wide[i] - 1)) == 0;
-    }
-    p.v_first = planes->layout == MYDET_YUV420_NV21;
     p.color = draw_yuv_of(DRAW_YUV[planes->matrix][planes->full_range], px_pack(style->color[0], style->color[1], style->color[2]));
-    return planar ? redact_launch<2>(p, B, (hipStream_t)stream) : redact_launch<1>(p, B, (hipStream_t)stream);
+    return planes->layout == MYDET_YUV420_I420 ? redact_launch<2>(p, B, (hipStream_t)stream) : redact_launch<1>(p, B, (hipStream_t)stream);
 }

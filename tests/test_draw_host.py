@@ -262,6 +262,53 @@ def test_draw_entry_points_report_bad_arguments_before_launch():
     s.thickness = 0
     assert yuv(s=s) == -1
 
+    # The same rows to the six entry points that take a list: draw, redact and crop, each rgb and yuv420.  A row changes one
+    # thing of a call that is in order and names, per entry point, the code at B = 1 and at B = 65536 -- a batch every entry
+    # point refuses with MYDET_E_UNSUPP (-2) once the checks before that one have passed, so -2 says "accepted so far" and
+    # pins where each entry point puts that check.  None at B = 1: the call is in order and would launch; it is not sent.
+    rst, out = _lib.RedactStyle(), _lib.CropOut()
+    rst.mode, rst.shape, rst.cell, rst.pad = _lib.REDACT_MOSAIC, _lib.REDACT_BOX, 4, 1.0
+    out.ch, out.cw, out.M, out.kind, out.pad, out.out, out.slot_stride, out.frame_stride = 8, 8, 1, _lib.CROP_U8, 1.0, 4096, 192, 192
+
+    def six(B, l=True, row=24, layout=_lib.YUV420_NV12, planes=(4096, 8192, None), rows=(8, 8, 0), **fields):
+        """The six calls, not yet made."""
+        gl, gs = good()
+        for k, v in fields.items():
+            setattr(gl, k, v)
+        lp = ctypes.byref(gl) if l else null
+        d = _lib.Yuv420Src()
+        for i, p in enumerate(planes):
+            d.plane[i], d.img_bytes[i], d.row_bytes[i] = p, 64, rows[i]
+        d.layout = layout
+        return (lambda: lib.mydet_draw_boxes_rgb_u8(one, B, 8, 8, 192, row, lp, ctypes.byref(gs), null),
+                lambda: lib.mydet_draw_boxes_yuv420_u8(ctypes.byref(d), B, 8, 8, lp, ctypes.byref(gs), null),
+                lambda: lib.mydet_redact_boxes_rgb_u8(one, B, 8, 8, 192, row, lp, ctypes.byref(rst), one, null),
+                lambda: lib.mydet_redact_boxes_yuv420_u8(ctypes.byref(d), B, 8, 8, lp, ctypes.byref(rst), one, null),
+                lambda: lib.mydet_crop_boxes_rgb(one, B, 8, 8, 192, row, lp, ctypes.byref(out), null),
+                lambda: lib.mydet_crop_boxes_yuv420(ctypes.byref(d), B, 8, 8, lp, ctypes.byref(out), null))
+
+    N = None
+    #      the row                                             draw rgb, yuv; redact rgb, yuv; crop rgb, yuv: at B = 1, at B = 65536
+    table = ((dict(),                                          (N, N, N, N, N, N), (-2, -2, -2, -2, -2, -2)),
+             (dict(l=False),                                   (-1,) * 6, (-1,) * 6),
+             (dict(K=0),                                       (-1,) * 6, (-1,) * 6),
+             (dict(K=513),                                     (-1,) * 6, (-1,) * 6),
+             (dict(box_row_stride=-1),                         (-1,) * 6, (-1,) * 6),
+             (dict(angle_frame_stride=-1),                     (-1,) * 6, (-1,) * 6),
+             (dict(count_stride=-1),                           (-1,) * 6, (-1,) * 6),
+             # planes that crop does not read: their strides are nothing to it
+             (dict(score_row_stride=-1),                       (-1, -1, -1, -1, N, N), (-1, -1, -1, -1, -2, -2)),
+             (dict(cls_frame_stride=-8),                       (-1, -1, -1, -1, N, N), (-1, -1, -1, -1, -2, -2)),
+             (dict(id_row_stride=-1),                          (-1, -1, -1, -1, N, N), (-1, -1, -1, -1, -2, -2)),
+             # a 10-bit layout: the painters refuse it, crops read it; redact checks the batch before the planes
+             (dict(layout=_lib.YUV420_P010, rows=(16, 16, 0)), (N, -1, N, -1, N, N), (-2, -1, -2, -2, -2, -2)),
+             (dict(planes=(4096, 8192, 12288)),                (N, -1, N, -1, N, -1), (-2, -1, -2, -2, -2, -1)),      # plane[2] for NV12
+             (dict(row=23, rows=(7, 8, 0)),                    (-1,) * 6, (-1, -1, -2, -2, -2, -1)),                  # row_bytes one short
+             (dict(row=24, rows=(8, 7, 0)),                    (N, -1, N, -1, N, -1), (-2, -1, -2, -2, -2, -1)))
+    for row, small, large in table:
+        assert tuple(call() for call in six(65536, **row)) == large, row
+        assert tuple(N if want is N else call() for call, want in zip(six(1, **row), small)) == small, row
+
 
 def test_unsettled_pixels_of_the_rotated_cases_stay_under_the_cap():
     """What tests/test_gpu_draw.py relies on: float32 error in (a, b) is below 1e-3 px for |coordinates| <= 512 (ulp 6e-5, a

@@ -1,7 +1,10 @@
 """Host only: the kernels of csrc/conv_igemm.hip in two builds of libmydet_hip.so, side by side -- names, registers, scratch, static
 LDS (code object metadata) and whether the instruction streams are the same.
 
-    python tools/igemm_resources.py OLD.so NEW.so [--out FILE.json]
+    python tools/igemm_resources.py OLD.so NEW.so [--out FILE.json] [--mark KERNEL ...]
+
+--mark names a kernel of another source file instead: the kernels of every code object that holds one of the marks are compared
+(profiles/paint_tile.md: --mark draw_rgb_kernel --mark redact_paint_kernel).
 
 Exit code 1 when the kernel lists differ or a kernel without scratch gained some.  Used for profiles/igemm_frame.md.
 """
@@ -19,10 +22,11 @@ FIELDS = ('vgpr_count', 'agpr_count', 'sgpr_count', 'private_segment_fixed_size'
 MARK = 'conv_igemm_b3w_kernel'            # a kernel only conv_igemm.hip has: finds its code object
 
 
-def kernels(lib):
-    """{kernel name: {field: value, 'isa': digest of its instructions}} of the code object that holds conv_igemm.hip."""
+def kernels(lib, marks=(MARK,)):
+    """{kernel name: {field: value, 'isa': digest of its instructions}} of the code objects that hold a kernel of `marks`."""
+    found = {}
     for (_, notes), (_, dis) in zip(code_objects(lib, notes=True), code_objects(lib)):
-        if MARK not in notes:
+        if not any(m in notes for m in marks):
             continue
         out, cur = {}, None
         for line in notes.splitlines():
@@ -41,8 +45,10 @@ def kernels(lib):
             isa.setdefault(fn, hashlib.sha1()).update((re.sub(r'\b(0x)?[0-9a-f]{4,}\b|<[^>]*>', '', ins) + '\n').encode())
         for name, rec in out.items():
             rec['isa'] = isa[name].hexdigest() if name in isa else None
-        return out
-    raise SystemExit(f'{lib}: no code object with {MARK}')
+        found.update(out)
+    if not found:
+        raise SystemExit(f'{lib}: no code object with {marks}')
+    return found
 
 
 def main():
@@ -50,8 +56,10 @@ def main():
     ap.add_argument('old')
     ap.add_argument('new')
     ap.add_argument('--out')
+    ap.add_argument('--mark', action='append', help='a kernel name that finds a code object (default: the one of conv_igemm.hip)')
     args = ap.parse_args()
-    old, new = kernels(args.old), kernels(args.new)
+    marks = tuple(args.mark or (MARK,))
+    old, new = kernels(args.old, marks), kernels(args.new, marks)
     res = {'only_old': sorted(set(old) - set(new)), 'only_new': sorted(set(new) - set(old)), 'kernels': len(old), 'differ': {},
            'same_isa': 0, 'gained_scratch': []}
     for name in sorted(set(old) & set(new)):
