@@ -806,6 +806,42 @@ int mydet_zones_frames(const float *box, const int64_t *id, const int64_t *cls, 
                        int32_t *out_inside, int32_t *out_crossed, int32_t *out_dwell, int32_t *out_occupancy,
                        int32_t *out_zone_counts, int32_t *out_line_counts, void *stream);
 
+/* Track trails: where each track's anchor was in its last frames, kept on the device by one launch behind the tracker launch
+ * (csrc/overlay.hip), for the overlay painter below.  It has the shape of mydet_zones_frames: one workgroup per stream, thread =
+ * track slot, the frames in order, the tracker's dense out_box / out_id / out_class / out_missed / out_count of the SAME S, F and
+ * max_tracks as input; q(v) and the anchors are those of mydet_zones_frames.  tests/_overlay_ref.py restates the rules and the
+ * kernel equals it with ==.
+ * Per stream, per frame, per track slot t, in this order (L = max_points, 2 .. MYDET_TRAIL_MAX_POINTS):
+ *   1. bad-class frame (out_count < 0): the state stands; the outputs come from the state.
+ *   2. clear   if the state holds an id for t and the tracker's id of t differs: id = 0, fill = 0, head = 0, the ring all zero.
+ *   3. push    when id != 0, missed == 0, the class passes the filter (n_classes == 0, or cls is one of classes[0 .. n_classes))
+ *      and the anchor is finite: the slot adopts the id if its state is empty; ring[head] = p = (q(x), q(y)); head = (head + 1)
+ *      mod L; fill = min(fill + 1, L).  (A coasting track pushes nothing: its trail ends at its last matched anchor.)
+ *   4. outputs (frame o = s*F + f): out_points i32 [S*F][MT][L][2] the ring newest first -- entry k is ring[(head - 1 - k) mod L]
+ *      for k < fill, zero beyond --; out_len i32 [S*F][MT] the fill, 0 unless the state's id equals the tracker's id; out_bbox i32
+ *      [S*F][MT][4] (min x, min y, max x, max y) of those fill points, zeros with fill == 0.
+ * Two launches of F1 and F2 frames leave exactly the state and the outputs of one launch of F1 + F2 frames.
+ * ts: HOST pointer.  state: S * mydet_trails_state_words(max_tracks, max_points) int32 words, 16-byte aligned, caller-owned,
+ *      persistent, initialised (all zero) by mydet_trails_reset.  Per stream, in words, MT = max_tracks:
+ *        [0, 2 MT) id (int64 [MT]; 0 = an empty slot)   [2 MT, 3 MT) fill   [3 MT, 4 MT) head   then ring i32 [MT][L][2];
+ *        zero padding to a multiple of 4 words.
+ * MYDET_E_BADARG, with nothing launched: S, F or max_tracks < 1; a null or misaligned pointer; max_points outside
+ *      2 .. MYDET_TRAIL_MAX_POINTS; anchor not MYDET_ZONE_ANCHOR_*; n_classes outside 0 .. MYDET_ZONE_MAX_CLASSES.
+ *      MYDET_E_UNSUPP: max_tracks > MYDET_TRACK_MAX_TRACKS (mydet_trails_state_words is 0 for such a max_tracks, and for a
+ *      max_points outside its range). */
+#define MYDET_TRAIL_MAX_POINTS     32
+typedef struct mydet_trail_set {
+    int max_points;                      /* L */
+    int anchor;                          /* MYDET_ZONE_ANCHOR_* */
+    int n_classes, reserved;
+    int classes[MYDET_ZONE_MAX_CLASSES];
+} mydet_trail_set;
+int64_t mydet_trails_state_words(int max_tracks, int max_points);
+int mydet_trails_reset(int32_t *state, int S, int max_tracks, int max_points, void *stream);
+int mydet_trails_frames(const float *box, const int64_t *id, const int64_t *cls, const int32_t *missed, const int32_t *count,
+                        int S, int F, int max_tracks, const mydet_trail_set *ts, int32_t *state, int32_t *out_points,
+                        int32_t *out_len, int32_t *out_bbox, void *stream);
+
 /* Winograd F(4x4,3x3) form of the same 3x3 stride-1 pad-1 conv + BN + act (+ residual) as mydet_conv2d_wino_f32
  * (4x fewer multiplies than the direct form; used for the deep layers with chip-filling grids).  `u` = the
  * transform-domain weights made by mydet_wino4_weights_f32 from the OHWI weight (mydet_wino4_weights_floats(Cout, Cin)
@@ -1198,6 +1234,89 @@ int mydet_draw_boxes_rgb_u8(unsigned char *dst, int B, int H, int W, int64_t dst
                             const mydet_draw_list *list, const mydet_draw_style *style, void *stream);
 int mydet_draw_boxes_yuv420_u8(const mydet_yuv420_src *planes, int B, int H, int W, const mydet_draw_list *list,
                                const mydet_draw_style *style, void *stream);
+
+/* Counting overlay: the zones, the directed lines with a tick on their positive side, their running counters and the trails of
+ * the tracks, painted IN PLACE into the frames the renderer above draws into, by one launch that runs before it (csrc/overlay.hip),
+ * so that boxes and their labels stay on top.  The counters are read from the outputs of mydet_zones_frames on the device and
+ * formatted by the kernel.  All geometry is in the zones' fixed point: q(v) as in mydet_zones_frames, |q| <= MYDET_ZONE_COORD_MAX,
+ * frames at most MYDET_ZONE_MAX_FRAME on a side; the centre of pixel (row i, column j) is p = (16 j + 8, 16 i + 8).  Every
+ * decision is an integer comparison; tests/_overlay_ref.py restates the rules with Python ints and the kernel equals it with ==.
+ *
+ * Zone fill.  Pixel (i, j) belongs to polygon z iff p is inside by the even-odd, half-open "Inside" rule of mydet_zones_frames,
+ *   verbatim (two zones that share an edge paint disjoint pixel sets).  It blends with the renderer's formula (colour * alpha +
+ *   old * (255 - alpha) + 127) / 255; alpha = zone_alpha when out_occupancy[o][z] == 0 in this frame, occupied_alpha otherwise
+ *   (alpha 0 paints nothing); polygons in order z = 0 .. Z-1; colour palette[z mod n_palette].
+ * Stroke (zone outlines, lines, direction ticks, trail segments).  A segment a -> b of thickness t (1..MYDET_DRAW_MAX_THICKNESS)
+ *   paints every pixel whose centre lies within t/2 pixels of the segment (a capsule; a == b gives a dot), opaque.  In integers,
+ *   with d = b - a, v = p - a, len2 = d.d, u = v.d and r = 8 t:   u <= 0: v.v <= r^2;   else u >= len2: (p-b).(p-b) <= r^2;   else
+ *   cross(d, v)^2 <= r^2 * len2.  The components of d are at most 2^21 and those of v below 2^21, so |cross| < 2^43, len2 <= 2^43
+ *   and r^2 * len2 <= 2^61 fit int64; cross^2 need not: the kernel first rejects |cross| >= 2^31, which is then certainly outside (r^2 * len2 < 2^62).
+ * Direction tick of line A -> B, computed on the host with integers alone when the geometry is built: M = ((A + B) >> 1) per
+ *   coordinate, n = (-(B.y - A.y), B.x - A.x) (the positive side of mydet_zones_frames), Lh = floor(sqrt(len2)), the tick goes
+ *   from M to M + trunc(n * 16 * tick_px / Lh) per coordinate (truncated toward zero), tick_px = 4 * thickness: one more segment
+ *   of the line's colour and thickness.  (Its end may pass MYDET_ZONE_COORD_MAX by 16 * tick_px <= 4096; the bounds above hold.)
+ * Counter labels.  Zone z: its name, then for each requested part a space and its text -- MYDET_OVERLAY_COUNT_OCCUPANCY `N`,
+ *   _ENTRIES `+E`, _VISITS `-V` (the finished visits: exits + lost) --; line l: `name +pos -neg`.  A number is the decimal of
+ *   min(value, 999999) (a negative value, which the counters never are, shows 0); a name shows at most MYDET_DRAW_NAME_BYTES
+ *   characters; a label has at most MYDET_OVERLAY_MAX_GLYPHS glyphs.  The label is the renderer's (same atlas; background the
+ *   zone's or line's colour palette[z or l mod n_palette]; text colour by the renderer's rule) and is placed by the renderer's rule
+ *   at an anchor point (x, y) in fixed point: left column clamp(x >> 4, 0, max(0, W - n*cw)), top row clamp((y >> 4) - ch, 0,
+ *   max(0, H - ch)), ch rows x n*cw columns, clipped to the frame.  Zone: the vertex least in (y, x); line: M.  Values are those
+ *   of out_occupancy, out_zone_counts and out_line_counts of frame o = s*F + f = the frame's index in the batch.
+ * Trails (mydet_trails_frames).  In frame o every slot with out_len >= 2 whose track the call shows -- missed == 0, or with
+ *   coasting missed >= 0 -- paints the segments between consecutive points with trail_thickness in palette[id mod n_palette]
+ *   (non-negative mod: the renderer's MYDET_DRAW_COLOR_ID colour).
+ * Paint order, per pixel: fills z ascending; zone outlines z ascending; lines l ascending, each followed by its tick; trails by
+ *   slot ascending; labels of zones, then of lines.  The last opaque operation wins.
+ * 4:2:0 targets follow the renderer's chroma rule unchanged: a chroma sample takes, in paint order and once each, every operation
+ *   (a fill, a segment, a label) that hits a pixel of its quad, a label with its colour at the first pixel of the quad it hits.
+ *   NV12, NV21, I420 (YV12 through exchanged planes); the 10-bit layouts are refused.
+ * Skipping.  A tile no operation reaches is neither read nor written; in the others only pixel groups some operation hit are
+ *   stored; nothing outside the H x W view is touched.
+ *
+ * mydet_overlay (HOST struct; it travels as a kernel argument, well below the 4 KB limit, because the static geometry --
+ *   polygons, lines, ticks, anchors and names, 3.4 KB -- sits in a DEVICE buffer made once: mydet_overlay_geometry).  The
+ *   kernel reads n_polygons and n_lines from the host struct and never more than MYDET_ZONE_MAX_VERTICES vertices.  flags says
+ *   what is painted; the pointers a part does not need may be NULL: ZONES reads geometry and occupancy, LINES geometry, either
+ *   with counters != 0 zone_counts (ZONES) / line_counts (LINES) and the style's atlas; TRAILS the trail outputs with id and
+ *   missed [S*F][max_tracks] of the tracker.  style: palette, n_palette, atlas, ch, cw are read, the rest is ignored.
+ * MYDET_E_BADARG, with nothing launched: a null overlay, style, palette or target, or a null pointer a painted part reads;
+ *   n_palette < 1; non-positive B, H, W or H, W above MYDET_ZONE_MAX_FRAME; B != S * F; flags 0 or with unknown bits; unknown
+ *   counter bits; an alpha outside 0..255; a thickness outside 1..MYDET_DRAW_MAX_THICKNESS; n_polygons or n_lines outside
+ *   0..MYDET_ZONES_MAX; counters without an atlas, ch outside 8..64 or cw outside 1..64; max_tracks < 1; max_points outside
+ *   2..MYDET_TRAIL_MAX_POINTS; coasting not 0 or 1; the target's rules of mydet_draw_boxes_*.  MYDET_E_UNSUPP: max_tracks >
+ *   MYDET_TRACK_MAX_TRACKS, B or ceil(H / 16) above 65535. */
+#define MYDET_OVERLAY_MAX_GLYPHS      40
+#define MYDET_OVERLAY_ZONES           1
+#define MYDET_OVERLAY_LINES           2
+#define MYDET_OVERLAY_TRAILS          4
+#define MYDET_OVERLAY_COUNT_OCCUPANCY 1
+#define MYDET_OVERLAY_COUNT_ENTRIES   2
+#define MYDET_OVERLAY_COUNT_VISITS    4
+typedef struct mydet_overlay_geometry {
+    int n_vertices[MYDET_ZONES_MAX];
+    int polygon[MYDET_ZONES_MAX][MYDET_ZONE_MAX_VERTICES][2];      /* quantised (x, y), as in mydet_zone_set */
+    int line[MYDET_ZONES_MAX][4];                                  /* A.x, A.y, B.x, B.y */
+    int tick[MYDET_ZONES_MAX][4];                                  /* M.x, M.y, the tick's end */
+    int anchor[2 * MYDET_ZONES_MAX][2];                            /* label anchors: zone z at z, line l at MYDET_ZONES_MAX + l */
+    unsigned char name[2 * MYDET_ZONES_MAX][MYDET_DRAW_NAME_BYTES]; /* ASCII, NUL-terminated when shorter; same order */
+} mydet_overlay_geometry;
+typedef struct mydet_overlay {
+    const mydet_overlay_geometry *geometry;                        /* DEVICE */
+    int flags, counters;                                           /* MYDET_OVERLAY_*, MYDET_OVERLAY_COUNT_* */
+    int n_polygons, n_lines;
+    int zone_alpha, occupied_alpha, thickness, trail_thickness;
+    int S, F, max_tracks, max_points;
+    int coasting, reserved;
+    const int32_t *occupancy, *zone_counts, *line_counts;          /* DEVICE: outputs of mydet_zones_frames of the same S, F */
+    const int32_t *trail_points, *trail_len, *trail_bbox;          /* DEVICE: outputs of mydet_trails_frames */
+    const int64_t *id;                                             /* DEVICE: the tracker's out_id */
+    const int32_t *missed;                                         /* DEVICE: the tracker's out_missed */
+} mydet_overlay;
+int mydet_draw_overlay_rgb_u8(unsigned char *dst, int B, int H, int W, int64_t dst_img_bytes, int64_t dst_row_bytes,
+                              const mydet_overlay *overlay, const mydet_draw_style *style, void *stream);
+int mydet_draw_overlay_yuv420_u8(const mydet_yuv420_src *planes, int B, int H, int W, const mydet_overlay *overlay,
+                                 const mydet_draw_style *style, void *stream);
 
 /* Redaction: the detections of a list are hidden -- pixelated, blurred or painted over -- IN PLACE in uint8 RGB frames or in the
  * planes of the 8-bit 4:2:0 layouts, before a frame leaves the device for an encoder, a screen or a disk (csrc/redact.hip).  No

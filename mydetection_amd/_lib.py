@@ -92,6 +92,11 @@ SIGNATURES = {
     'mydet_zones_reset': [c_ptr, c_int, c_int, c_ptr],
     'mydet_zones_frames': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                            c_ptr],
+    'mydet_trails_state_words': [c_int, c_int],
+    'mydet_trails_reset': [c_ptr, c_int, c_int, c_int, c_ptr],
+    'mydet_trails_frames': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_draw_overlay_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr],
+    'mydet_draw_overlay_yuv420_u8': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
     'mydet_mbconv_tiles': [c_int, c_int, c_int],
     'mydet_mbconv_expand_dw_f32': [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64] + [c_int] * 11 + [c_ptr, c_int, c_ptr, c_ptr],
     'mydet_sepconv_nodes_f32': [c_int, c_ptr, c_int, c_int, c_ptr],
@@ -145,7 +150,7 @@ SIGNATURES = {
 
 RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems',
                'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words', 'mydet_mot_scratch_bytes', 'mydet_zones_state_words',
-               'mydet_redact_workspace_bytes'}
+               'mydet_redact_workspace_bytes', 'mydet_trails_state_words'}
 
 # detection record layout (MYDET_REC_* of include/mydet.h), in int32 words
 REC_TOPK = 512
@@ -179,6 +184,10 @@ ZONES_STATE_HEADER, ZONES_SLOT_WORDS = 148, 22
 DRAW_MAX_BOXES, DRAW_MAX_THICKNESS, DRAW_MAX_GLYPHS, DRAW_NAME_BYTES = 512, 64, 33, 16
 DRAW_COLOR_CLASS, DRAW_COLOR_ID, DRAW_COLOR_FIXED = 0, 1, 2
 DRAW_LABEL_CLASS, DRAW_LABEL_SCORE, DRAW_LABEL_ID = 1, 2, 4
+# counting overlay and trails (mydet_draw_overlay_*, mydet_trails_frames): MYDET_OVERLAY_*, MYDET_TRAIL_MAX_POINTS of include/mydet.h
+OVERLAY_MAX_GLYPHS, TRAIL_MAX_POINTS = 40, 32
+OVERLAY_ZONES, OVERLAY_LINES, OVERLAY_TRAILS = 1, 2, 4
+OVERLAY_COUNT_OCCUPANCY, OVERLAY_COUNT_ENTRIES, OVERLAY_COUNT_VISITS = 1, 2, 4
 # redaction (mydet_redact_boxes_*): MYDET_REDACT_* of include/mydet.h
 REDACT_MOSAIC, REDACT_SMOOTH, REDACT_SOLID = 0, 1, 2
 REDACT_BOX, REDACT_ELLIPSE = 0, 1
@@ -288,6 +297,26 @@ class DrawStyle(ctypes.Structure):
     _fields_ = [('thickness', c_int), ('fill_alpha', c_int), ('color_mode', c_int), ('label_flags', c_int),
                 ('color', ctypes.c_ubyte * 4), ('n_palette', c_int), ('ch', c_int), ('cw', c_int), ('n_names', c_int),
                 ('palette', c_ptr), ('atlas', c_ptr), ('names', c_ptr)]
+
+
+class TrailSet(ctypes.Structure):
+    """mydet_trail_set (include/mydet.h): the ring length, the anchor and the class filter of mydet_trails_frames."""
+    _fields_ = [('max_points', c_int), ('anchor', c_int), ('n_classes', c_int), ('reserved', c_int), ('classes', c_int * 16)]
+
+
+class OverlayGeometry(ctypes.Structure):
+    """mydet_overlay_geometry (include/mydet.h): what the overlay painter reads from a DEVICE buffer."""
+    _fields_ = [('n_vertices', c_int * 16), ('polygon', ((c_int * 2) * 16) * 16), ('line', (c_int * 4) * 16), ('tick', (c_int * 4) * 16),
+                ('anchor', (c_int * 2) * 32), ('name', (ctypes.c_ubyte * 16) * 32)]
+
+
+class Overlay(ctypes.Structure):
+    """mydet_overlay (include/mydet.h): device pointers and the settings of one overlay launch."""
+    _fields_ = [('geometry', c_ptr), ('flags', c_int), ('counters', c_int), ('n_polygons', c_int), ('n_lines', c_int),
+                ('zone_alpha', c_int), ('occupied_alpha', c_int), ('thickness', c_int), ('trail_thickness', c_int),
+                ('S', c_int), ('F', c_int), ('max_tracks', c_int), ('max_points', c_int), ('coasting', c_int), ('reserved', c_int),
+                ('occupancy', c_ptr), ('zone_counts', c_ptr), ('line_counts', c_ptr),
+                ('trail_points', c_ptr), ('trail_len', c_ptr), ('trail_bbox', c_ptr), ('id', c_ptr), ('missed', c_ptr)]
 
 
 class RedactStyle(ctypes.Structure):

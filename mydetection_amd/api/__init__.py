@@ -4,11 +4,13 @@ argument of its tiled detection on large frames, `Tracker`, the argument that tu
 colour over every detection, on the device), `Chips`, the settings of its crop_frames methods, `Nms`, how its
 post-process suppresses (class-agnostic, Soft-NMS, box merging), `Augment`, its test-time augmentation (mirrored and rescaled
 views fused on the device), `Evaluator`, which scores what it returns against ground
-truth, `TrackEvaluator`, which scores its tracks against ground-truth identities, and `Zones`, which counts its tracks in
-polygons and across lines on the device."""
+truth, `TrackEvaluator`, which scores its tracks against ground-truth identities, `Zones`, which counts its tracks in
+polygons and across lines on the device, and `Overlay`, which paints those zones, lines, counters and the tracks' trails into
+the annotated frames."""
 from .detection import Augment, Chips, Detector, Draw, Nms, Redact, Tiles
 from .evaluation import Evaluator, TrackEvaluator
+from .overlay import Overlay
 from .tracking import Tracker
 from .zones import Zones
 
-__all__ = ['Augment', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Redact', 'Tiles', 'TrackEvaluator', 'Tracker', 'Zones']
+__all__ = ['Augment', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Overlay', 'Redact', 'Tiles', 'TrackEvaluator', 'Tracker', 'Zones']

@@ -782,6 +782,7 @@ class Detector():
         paints or cuts out the returned tracks."""
         tracker, coasting = self._pop_tracker(kwargs)
         zones = self._pop_zones(kwargs, tracker)
+        overlay = self._pop_overlay(kwargs, tracker, zones, draw)
         sources = make_sources()
         used = draw is not None or chips is not None or redact is not None
         if tracker is not None:
@@ -789,6 +790,8 @@ class Detector():
             tracker.check_call(src.n, src.hw, self.model.bb_format)
             if zones is not None:
                 zones.check_call(tracker, src.hw, self.model.bb_format)
+            if overlay is not None:
+                overlay.check_call(tracker, zones, src.hw)
         elif used:
             src, = sources                                           # a plain call alone takes any number of sizes, none included
         call = self._call_settings(kwargs, whole=tracker is not None or used)
@@ -800,13 +803,15 @@ class Detector():
             call = self._call_settings(dict(kwargs, conf_thres=min(conf_thres, tracker.low_thres)), whole=True)
         records = self._source_records(sources, call)
         if tracker is not None:
-            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres, zones)
+            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres, zones, overlay)
         elif used:
             records = list(records)
             (idxs, found), = records                                 # one frame size: one group, in frame order
             assert idxs == list(range(src.n))
         if redact is not None:
             made = src.redact(found, redact.style(src.hw))
+        if overlay is not None:                                      # under the boxes and their labels, over the redaction
+            overlay.paint(*src.image(), zones, src.hw, coasting)
         if draw is not None:
             made = src.draw(found, draw.style(src.hw, tracker is not None))
         elif chips is not None:
@@ -861,15 +866,33 @@ class Detector():
         return zones
 
     @staticmethod
+    def _pop_overlay(kwargs, tracker, zones, draw):
+        """overlay out of a frame method's keyword arguments: a TypeError for anything but an Overlay and in a method that does not
+        draw, a ValueError without a tracker or, for the zone parts, without zones=, all before any launch."""
+        from .overlay import Overlay
+        if 'overlay' not in kwargs:
+            return None
+        overlay = kwargs.pop('overlay')
+        if overlay is None:
+            return None
+        if not isinstance(overlay, Overlay):
+            raise TypeError(f'overlay: a mydetection_amd.api.Overlay (or None) expected, got {type(overlay).__name__}')
+        if draw is None:
+            raise TypeError('overlay: overlay= is an argument of annotate_frames and its YUV forms')
+        overlay.check_call(tracker, zones, (1, 1) if overlay.img_hw is None else overlay.img_hw)
+        return overlay
+
+    @staticmethod
     def _no_tracker(kwargs, what):
         if 'tracker' in kwargs or 'coasting' in kwargs or 'zones' in kwargs:
             raise TypeError(f'{what}: track ids in the json rows are not built; use the predict_frames form with tracker=')
 
-    def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres, zones=None):
+    def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres, zones=None, overlay=None):
         """The tracked form of _objects_of_records: one eager tracker launch on the call's records (frame coordinates, one
         buffer), then per frame the ImageObjects of the tracks with missed == 0 (coasting: of every live track).  Two host
         synchronisations: the frame counts, and the indices of the selected slots.  zones: a Zones whose launch follows the
-        tracker's at once (no synchronisation in between); the objects then carry zone_mask and line_events."""
+        tracker's at once (no synchronisation in between); the objects then carry zone_mask and line_events.  overlay: an
+        Overlay, whose trails launch follows them and which keeps the tracker's outputs for its paint launch."""
         from ..utils.structures import ImageObjects
         records = list(records)
         assert len(records) == 1, 'one frame size gives one network input size'
@@ -881,6 +904,8 @@ class Detector():
         params = tracker.params(frame_hw, tracker.resolve_match(self.model.bb_format), conf_thres)
         out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks, assoc=tracker.assoc(conf_thres))
         zout = None if zones is None else zones.run(out, tracker, frame_hw)
+        if overlay is not None:                                      # the trails launch, behind the tracker's (and the zones')
+            overlay.run_trails(out, tracker, zones, frame_hw)
         B, mt = len(idxs), tracker.max_tracks
         missed = out['missed'].view(B, mt)
         keep = (missed >= 0) if coasting else (missed == 0)
@@ -1022,7 +1047,12 @@ class Detector():
         packed pixels, else the device batch the call had to build anyway.  Frames of one size (ValueError otherwise).  draw: a
         Draw (default Draw()).  tiles=, tracker= and coasting= as in predict_frames.  An untracked call draws straight from the
         records buffer, before any host synchronisation; a tracked call draws the returned tracks, with their ids.  redact: None,
-        or a Redact: the detections are hidden first (as redact_frames does) and the overlay is painted on top."""
+        or a Redact: the detections are hidden first (as redact_frames does) and the overlay is painted on top.
+        overlay: None, or a mydetection_amd.api.Overlay (with tracker=; its zone parts with zones=: ValueError otherwise): the
+        zones and lines of the call's Zones, their counters as they stand after each frame and the trails of the tracks are
+        painted by one more launch before the boxes (include/mydet.h: mydet_draw_overlay_rgb_u8), the trails kept by one launch
+        behind the tracker's (mydet_trails_frames); no host synchronisation is added and the objects are bit for bit those of
+        the call without overlay=.  Paint order: redact, overlay, boxes.  annotate_frames_yuv and _nv12 take it too."""
         draw = self._setting(draw, Draw, 'annotate_frames')
         redact = self._redact_setting(redact, 'annotate_frames')
         return self._detect(lambda: self._rgb_sources(frames, 'annotate_frames'), kwargs, draw=draw, redact=redact)

@@ -1924,6 +1924,22 @@ def zones_state_views(state, max_tracks=None):
     return out
 
 
+def _track_planes(what, track_out):
+    """(S, F, MT, device) of the dict ops.track_frames returned, its box, id, cls, missed and count planes checked."""
+    box = track_out['box']
+    if not isinstance(box, torch.Tensor) or box.dim() != 4 or box.shape[3] != 5:
+        raise ValueError(f'{what}: track_out is the dict of ops.track_frames (box [S,F,MT,5], id, cls, missed, count)')
+    S, F, mt, _ = box.shape
+    dev = box.device
+    shapes = {'box': ((S, F, mt, 5), torch.float32), 'id': ((S, F, mt), torch.int64), 'cls': ((S, F, mt), torch.int64),
+              'missed': ((S, F, mt), torch.int32), 'count': ((S, F), torch.int32)}
+    for k, (shape, dt) in shapes.items():
+        t = track_out[k]
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f'{what}: track_out[{k!r}] must be a contiguous {dt} tensor {shape} on {dev}')
+    return S, F, mt, dev
+
+
 def zones_frames(track_out, state, zone_set, heat=None, out=None):
     """Count the tracks of S streams x F frames in zones and across lines in ONE launch (include/mydet.h: mydet_zones_frames,
     where the rules are).  track_out: the dict ops.track_frames returned (box [S,F,MT,5], id, cls, missed, count are read).
@@ -1933,17 +1949,8 @@ def zones_frames(track_out, state, zone_set, heat=None, out=None):
     (entries, exits, lost, visits; cumulative), line_counts [S,F,L,2] (pos, neg; cumulative).  out: such a dict to write into."""
     if not isinstance(zone_set, _lib.ZoneSet):
         raise TypeError(f'zones_frames: zone_set is a _lib.ZoneSet (ops.zone_set), got {type(zone_set).__name__}')
+    S, F, mt, dev = _track_planes('zones_frames', track_out)
     box = track_out['box']
-    if not isinstance(box, torch.Tensor) or box.dim() != 4 or box.shape[3] != 5:
-        raise ValueError('zones_frames: track_out is the dict of ops.track_frames (box [S,F,MT,5], id, cls, missed, count)')
-    S, F, mt, _ = box.shape
-    dev = box.device
-    shapes = {'box': ((S, F, mt, 5), torch.float32), 'id': ((S, F, mt), torch.int64), 'cls': ((S, F, mt), torch.int64),
-              'missed': ((S, F, mt), torch.int32), 'count': ((S, F), torch.int32)}
-    for k, (shape, dt) in shapes.items():
-        t = track_out[k]
-        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            raise ValueError(f'zones_frames: track_out[{k!r}] must be a contiguous {dt} tensor {shape} on {dev}')
     _check_zones_state(state, mt, 'zones_frames')
     if state.shape[0] != S or state.device != dev:
         raise ValueError(f'zones_frames: a state of {S} streams on {dev} expected, got {state.shape[0]} on {state.device}')
@@ -2781,6 +2788,326 @@ def draw_records(target, rec, style, layout=None, matrix='bt601', full_range=Fal
     ids = None if ids is None else ids.contiguous()
     _draw_launch(image, yuv, _list_of_records(what, records, True, ids), style, dev)
     return target
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Counting overlay and trails (include/mydet.h: mydet_trails_frames, mydet_draw_overlay_rgb_u8 / _yuv420_u8, where the rules are).
+# overlay_geometry and overlay_label_text are host functions and ARE the documented rules for ticks, anchors and texts.
+
+OVERLAY_COUNTERS = {'occupancy': _lib.OVERLAY_COUNT_OCCUPANCY, 'entries': _lib.OVERLAY_COUNT_ENTRIES, 'visits': _lib.OVERLAY_COUNT_VISITS}
+
+
+def trail_set(max_points, anchor='center', classes=None):
+    """The parameter struct of mydet_trails_frames (a _lib.TrailSet): max_points 2 .. 32 ring entries per track; anchor 'center'
+    or 'bottom' and classes None or 1 .. 16 class indices, as in zone_set.  A ValueError otherwise; touches no device."""
+    if isinstance(max_points, bool) or not isinstance(max_points, (int, np.integer)) or not 2 <= max_points <= _lib.TRAIL_MAX_POINTS:
+        raise ValueError(f'trail_set: an integer max_points in 2 .. {_lib.TRAIL_MAX_POINTS} expected, got {max_points!r}')
+    if not isinstance(anchor, str) or anchor not in ZONE_ANCHORS:
+        raise ValueError(f'trail_set: anchor {anchor!r} is not one of {sorted(ZONE_ANCHORS)}')
+    t = _lib.TrailSet()
+    t.max_points, t.anchor = int(max_points), ZONE_ANCHORS[anchor]
+    if classes is not None:
+        cl = [int(c) for c in classes]
+        if not 1 <= len(cl) <= _lib.ZONE_MAX_CLASSES or any(c < 0 or c >= 1 << 31 for c in cl):
+            raise ValueError(f'trail_set: classes is None or 1 .. {_lib.ZONE_MAX_CLASSES} class indices, got {classes!r}')
+        t.n_classes = len(cl)
+        t.classes[:len(cl)] = cl
+    return t
+
+
+def trails_state_words(max_tracks, max_points):
+    """int32 words of one stream's trail state (include/mydet.h: mydet_trails_state_words); host arithmetic only."""
+    max_tracks, max_points = int(max_tracks), int(max_points)
+    if not 1 <= max_tracks <= _lib.TRACK_MAX_TRACKS:
+        raise ValueError(f'trails: 1 <= max_tracks <= {_lib.TRACK_MAX_TRACKS} expected, got {max_tracks}')
+    if not 2 <= max_points <= _lib.TRAIL_MAX_POINTS:
+        raise ValueError(f'trails: 2 <= max_points <= {_lib.TRAIL_MAX_POINTS} expected, got {max_points}')
+    return (max_tracks * (4 + 2 * max_points) + 3) // 4 * 4
+
+
+def _check_trails_state(state, max_tracks, max_points, what):
+    words = trails_state_words(max_tracks, max_points)
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != words or not state.is_contiguous():
+        got = f'{state.dtype} {tuple(state.shape)}' if isinstance(state, torch.Tensor) else type(state).__name__
+        raise ValueError(f'{what}: a contiguous int32 state [streams, {words}] for max_tracks = {max_tracks}, max_points = {max_points} expected, '
+                         f'got {got}')
+    require_gpu(state, what)
+    return words
+
+
+def trails_state(streams, max_tracks, max_points, device):
+    """A reset trail state: int32 [streams, trails_state_words(max_tracks, max_points)] (include/mydet.h has the layout)."""
+    words = trails_state_words(max_tracks, max_points)
+    streams = int(streams)
+    if streams < 1:
+        raise ValueError(f'trails: streams >= 1 expected, got {streams}')
+    state = torch.empty((streams, words), dtype=torch.int32, device=device)
+    return trails_reset_(state, max_tracks, max_points)
+
+
+def trails_reset_(state, max_tracks, max_points):
+    """Reset a trail state in place (mydet_trails_reset): every ring empty."""
+    _check_trails_state(state, max_tracks, max_points, 'trails_reset_')
+    code = _lib.lib().mydet_trails_reset(_ptr(state), state.shape[0], int(max_tracks), int(max_points), _stream())
+    _lib.check(code, 'mydet_trails_reset')
+    return state
+
+
+def trails_state_views(state, max_tracks, max_points):
+    """Field views of a trail state int32 [S, words] (include/mydet.h: mydet_trails_frames), nothing copied: id int64 [S,MT]
+    (0 = an empty slot), fill, head int32 [S,MT], ring int32 [S,MT,L,2].  Works on any device (tests read a host copy)."""
+    if state.dtype != torch.int32 or state.dim() != 2 or not state.is_contiguous():
+        raise ValueError(f'trails_state_views: a contiguous int32 state [streams, words] expected, got {state.dtype} {tuple(state.shape)}')
+    mt, L = int(max_tracks), int(max_points)
+    S, words = state.shape
+    if words != trails_state_words(mt, L):
+        raise ValueError(f'trails_state_views: {words} words per stream is not the state of max_tracks = {mt}, max_points = {L}')
+    return {'id': state[:, :2 * mt].view(torch.int64), 'fill': state[:, 2 * mt:3 * mt], 'head': state[:, 3 * mt:4 * mt],
+            'ring': state[:, 4 * mt:4 * mt + 2 * L * mt].view(S, mt, L, 2)}
+
+
+def trails_frames(track_out, state, trail_set, out=None):
+    """Keep the trails of the tracks of S streams x F frames in ONE launch (include/mydet.h: mydet_trails_frames, where the rules
+    are).  track_out: the dict ops.track_frames returned.  state: int32 [S, trails_state_words(MT, L)] from trails_state, updated
+    in place.  trail_set: trail_set(...).  Returns a dict of int32 device tensors: points [S,F,MT,L,2] (newest first, zeros beyond
+    the fill), len [S,F,MT], bbox [S,F,MT,4] (min x, min y, max x, max y), all in 1/16 pixel.  out: such a dict to write into."""
+    what = 'trails_frames'
+    if not isinstance(trail_set, _lib.TrailSet):
+        raise TypeError(f'{what}: trail_set is a _lib.TrailSet (ops.trail_set), got {type(trail_set).__name__}')
+    S, F, mt, dev = _track_planes(what, track_out)
+    L = trail_set.max_points
+    _check_trails_state(state, mt, L, what)
+    if state.shape[0] != S or state.device != dev:
+        raise ValueError(f'{what}: a state of {S} streams on {dev} expected, got {state.shape[0]} on {state.device}')
+    require_gpu(track_out['box'], what)
+    oshapes = {'points': (S, F, mt, L, 2), 'len': (S, F, mt), 'bbox': (S, F, mt, 4)}
+    if out is None:
+        out = {k: torch.empty(shape, dtype=torch.int32, device=dev) for k, shape in oshapes.items()}
+    for k, shape in oshapes.items():
+        t = out[k]
+        if tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f'{what}: out[{k!r}] must be a contiguous int32 tensor {shape} on {dev}')
+    t0 = TIMER.start() if TIMER else None
+    code = _lib.lib().mydet_trails_frames(_ptr(track_out['box']), _ptr(track_out['id']), _ptr(track_out['cls']), _ptr(track_out['missed']),
+                                          _ptr(track_out['count']), S, F, mt, ctypes.byref(trail_set), _ptr(state), _ptr(out['points']),
+                                          _ptr(out['len']), _ptr(out['bbox']), _stream())
+    if t0:
+        TIMER.stop('trails_frames', t0, float(S * F))
+    _lib.check(code, 'mydet_trails_frames')
+    return out
+
+
+def overlay_counter_flags(counters):
+    """The C counter flags of an iterable of 'occupancy' / 'entries' / 'visits' (None or empty: 0 = no labels); a ValueError otherwise."""
+    if counters is None:
+        return 0
+    if isinstance(counters, str):
+        counters = (counters,)
+    flags = 0
+    for name in counters:
+        if not isinstance(name, str) or name not in OVERLAY_COUNTERS:
+            raise ValueError(f'overlay: counter {name!r} is not one of {sorted(OVERLAY_COUNTERS)}')
+        flags |= OVERLAY_COUNTERS[name]
+    return flags
+
+
+def overlay_label_text(name, counters=('occupancy', 'entries'), occupancy=0, entries=0, visits=0, line=None):
+    """The text of a counter label (the rule of include/mydet.h as host code).  A zone: `name`, then for each part of `counters`,
+    in the order occupancy, entries, visits, a space and `N`, `+E` or `-V`.  A line (line = (pos, neg)): `name +pos -neg`.  A
+    number is the decimal of min(value, 999999); the name is cut to 16 characters, the label to 40 glyphs."""
+    def num(v):
+        return str(min(max(int(v), 0), 999999))
+    text = str(name)[:_lib.DRAW_NAME_BYTES]
+    if line is not None:
+        text += f' +{num(line[0])} -{num(line[1])}'
+    else:
+        flags = overlay_counter_flags(counters)
+        if flags & _lib.OVERLAY_COUNT_OCCUPANCY:
+            text += f' {num(occupancy)}'
+        if flags & _lib.OVERLAY_COUNT_ENTRIES:
+            text += f' +{num(entries)}'
+        if flags & _lib.OVERLAY_COUNT_VISITS:
+            text += f' -{num(visits)}'
+    return text[:_lib.OVERLAY_MAX_GLYPHS]
+
+
+def overlay_tick(line, thickness):
+    """The direction tick (M.x, M.y, E.x, E.y) of a quantised line (A.x, A.y, B.x, B.y), by integers alone (include/mydet.h):
+    M = (A + B) >> 1; n = (-(B.y - A.y), B.x - A.x); E = M + trunc(n * 16 * 4 * thickness / isqrt(len2))."""
+    ax, ay, bx, by = (int(v) for v in line)
+    mx, my = (ax + bx) >> 1, (ay + by) >> 1
+    nx, ny = -(by - ay), bx - ax
+    lh = math.isqrt(nx * nx + ny * ny)
+    k = 16 * 4 * int(thickness)
+
+    def trunc_div(v):
+        return (abs(v) // lh) * (1 if v >= 0 else -1)
+    return mx, my, mx + trunc_div(nx * k), my + trunc_div(ny * k)
+
+
+class OverlayGeometry:
+    """What ops.overlay_geometry returns: the static geometry of the overlay on the host (`struct`, a _lib.OverlayGeometry, with
+    n_polygons, n_lines and thickness); its device buffer is made the first time a device paints with it."""
+
+    def __init__(self, struct, n_polygons, n_lines, thickness):
+        self.struct, self.n_polygons, self.n_lines, self.thickness = struct, n_polygons, n_lines, thickness
+        self._buffers = {}
+
+    def __repr__(self):
+        return f'OverlayGeometry({self.n_polygons} polygons, {self.n_lines} lines, thickness={self.thickness})'
+
+    def buffer(self, device):
+        key = str(torch.device(device))
+        if key not in self._buffers:
+            raw = np.frombuffer(bytes(self.struct), dtype=np.uint8).copy()
+            self._buffers[key] = torch.from_numpy(raw).to(device)
+        return self._buffers[key]
+
+
+def overlay_geometry(zone_set, names=None, thickness=2):
+    """The host part of the overlay painter (include/mydet.h: mydet_overlay_geometry): the quantised polygons and lines of a
+    zone_set(...), the direction tick of every line (overlay_tick; it depends on `thickness`, 1 .. 64, the thickness of outlines,
+    lines and ticks), the label anchors -- a zone's vertex least in (y, x), a line's midpoint -- and the names (one per polygon
+    followed by one per line, 16 ASCII characters are shown; None: zone0 .. and line0 ..).  Touches no device."""
+    if not isinstance(zone_set, _lib.ZoneSet):
+        raise TypeError(f'overlay_geometry: zone_set is a _lib.ZoneSet (ops.zone_set), got {type(zone_set).__name__}')
+    if isinstance(thickness, bool) or not isinstance(thickness, (int, np.integer)) or not 1 <= thickness <= _lib.DRAW_MAX_THICKNESS:
+        raise ValueError(f'overlay_geometry: an integer thickness in 1..{_lib.DRAW_MAX_THICKNESS} expected, got {thickness!r}')
+    Z, L = zone_set.n_polygons, zone_set.n_lines
+    if names is None:
+        names = [f'zone{z}' for z in range(Z)] + [f'line{l}' for l in range(L)]
+    names = list(names)
+    if len(names) != Z + L or not all(isinstance(n, str) for n in names):
+        raise ValueError(f'overlay_geometry: names is one str per polygon followed by one per line ({Z + L}), got {names!r}')
+    g = _lib.OverlayGeometry()
+    for z in range(Z):
+        n = zone_set.n_vertices[z]
+        g.n_vertices[z] = n
+        pts = [(zone_set.polygon[z][i][0], zone_set.polygon[z][i][1]) for i in range(n)]
+        for i, (x, y) in enumerate(pts):
+            g.polygon[z][i][0], g.polygon[z][i][1] = x, y
+        y, x = min((y, x) for x, y in pts)
+        g.anchor[z][0], g.anchor[z][1] = x, y
+    for l in range(L):
+        line = list(zone_set.line[l])
+        g.line[l][:] = line
+        tick = overlay_tick(line, thickness)
+        g.tick[l][:] = list(tick)
+        g.anchor[_lib.ZONES_MAX + l][0], g.anchor[_lib.ZONES_MAX + l][1] = tick[0], tick[1]
+    for k, name in enumerate(names):
+        raw = name.encode('ascii', 'replace')[:_lib.DRAW_NAME_BYTES]
+        slot = k if k < Z else _lib.ZONES_MAX + k - Z
+        g.name[slot][:len(raw)] = list(raw)
+    return OverlayGeometry(g, Z, L, int(thickness))
+
+
+def _overlay_alpha(what, name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 255:
+        raise ValueError(f'{what}: an integer {name} in 0..255 expected, got {v!r}')
+    return int(v)
+
+
+def _overlay_struct(what, B, geometry, zones_out, trails_out, track_out, zones, lines, counters, zone_alpha, occupied_alpha,
+                    trail_thickness, coasting):
+    """The checked _lib.Overlay of a draw_overlay call and the tensors it points to."""
+    o = _lib.Overlay()
+    o.zone_alpha, o.occupied_alpha = _overlay_alpha(what, 'zone_alpha', zone_alpha), _overlay_alpha(what, 'occupied_alpha', occupied_alpha)
+    if isinstance(trail_thickness, bool) or not isinstance(trail_thickness, (int, np.integer)) or not 1 <= trail_thickness <= _lib.DRAW_MAX_THICKNESS:
+        raise ValueError(f'{what}: an integer trail_thickness in 1..{_lib.DRAW_MAX_THICKNESS} expected, got {trail_thickness!r}')
+    o.trail_thickness, o.thickness, o.coasting = int(trail_thickness), 1, int(bool(coasting))
+    keep, shape = [], None
+    if geometry is not None:
+        if not isinstance(geometry, OverlayGeometry):
+            raise TypeError(f'{what}: geometry is an ops.OverlayGeometry (ops.overlay_geometry), got {type(geometry).__name__}')
+        Z, L = geometry.n_polygons, geometry.n_lines
+        paint_z, paint_l = bool(zones) and Z > 0, bool(lines) and L > 0
+        o.counters = overlay_counter_flags(counters)
+        if paint_z or paint_l:
+            if not isinstance(zones_out, dict):
+                raise ValueError(f'{what}: zones_out, the dict of ops.zones_frames on the same zone_set, is needed to paint zones or lines')
+            S, F = zones_out['occupancy'].shape[:2] if Z else zones_out['line_counts'].shape[:2]
+            shape = (int(S), int(F))
+            for k, want in (('occupancy', (S, F, Z)), ('zone_counts', (S, F, Z, 4)), ('line_counts', (S, F, L, 2))):
+                t = zones_out[k]
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != want or t.dtype != torch.int32 or not t.is_contiguous():
+                    raise ValueError(f'{what}: zones_out[{k!r}] must be a contiguous int32 tensor {want}')
+                keep.append(t)
+            o.flags |= (_lib.OVERLAY_ZONES if paint_z else 0) | (_lib.OVERLAY_LINES if paint_l else 0)
+            o.n_polygons, o.n_lines, o.thickness = Z, L, geometry.thickness
+            o.occupancy, o.zone_counts, o.line_counts = (_ptr(t) if t.numel() else None for t in keep)
+    if trails_out is not None:
+        if not isinstance(trails_out, dict) or not isinstance(track_out, dict):
+            raise ValueError(f'{what}: trails_out is the dict of ops.trails_frames and needs track_out, the dict of ops.track_frames it was made from')
+        pts = trails_out['points']
+        if not isinstance(pts, torch.Tensor) or pts.dim() != 5 or pts.shape[4] != 2:
+            raise ValueError(f'{what}: trails_out is the dict of ops.trails_frames (points [S,F,MT,L,2], len, bbox)')
+        S, F, mt, L = (int(v) for v in pts.shape[:4])
+        if shape is not None and shape != (S, F):
+            raise ValueError(f'{what}: zones_out is of {shape[0]} x {shape[1]} frames, trails_out of {S} x {F}')
+        shape = (S, F)
+        wants = (('points', trails_out, (S, F, mt, L, 2), torch.int32), ('len', trails_out, (S, F, mt), torch.int32),
+                 ('bbox', trails_out, (S, F, mt, 4), torch.int32), ('id', track_out, (S, F, mt), torch.int64),
+                 ('missed', track_out, (S, F, mt), torch.int32))
+        for k, src, want, dt in wants:
+            t = src[k]
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != want or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f'{what}: {k!r} must be a contiguous {dt} tensor {want}')
+            keep.append(t)
+        if not (1 <= mt <= _lib.TRACK_MAX_TRACKS and 2 <= L <= _lib.TRAIL_MAX_POINTS):
+            raise ValueError(f'{what}: trails of 1..{_lib.TRACK_MAX_TRACKS} tracks and 2..{_lib.TRAIL_MAX_POINTS} points expected, got {mt} and {L}')
+        o.flags |= _lib.OVERLAY_TRAILS
+        o.max_tracks, o.max_points = mt, L
+        o.trail_points, o.trail_len, o.trail_bbox, o.id, o.missed = (_ptr(t) for t in keep[-5:])
+    if not o.flags:
+        raise ValueError(f'{what}: nothing to paint: neither zones or lines of a geometry nor trails')
+    if shape[0] * shape[1] != B:
+        raise ValueError(f'{what}: {B} frames, but the counting outputs are of {shape[0]} streams x {shape[1]} frames')
+    o.S, o.F = shape
+    return o, keep
+
+
+def _draw_overlay(what, image, yuv, B, style, kwargs):
+    _draw_check_style(style, what)
+    o, keep = _overlay_struct(what, B, **kwargs)                     # every argument rule, before a device is touched
+    dev = _same_device(what, image, keep)
+    if o.flags & (_lib.OVERLAY_ZONES | _lib.OVERLAY_LINES):
+        keep.append(kwargs['geometry'].buffer(dev))
+        o.geometry = _ptr(keep[-1])
+    s, keep_style = style.struct(dev)
+    if o.counters and (o.flags & (_lib.OVERLAY_ZONES | _lib.OVERLAY_LINES)) and not s.atlas:
+        atlas = glyph_atlas(style.label_height, dev)
+        s.atlas, s.ch, s.cw = _ptr(atlas), atlas.shape[1], atlas.shape[2]
+    _launch_on_image('draw_overlay', image, yuv, 'mydet_draw_overlay_rgb_u8', 'mydet_draw_overlay_yuv420_u8', ctypes.byref(o), ctypes.byref(s))
+    del keep, keep_style
+
+
+def draw_overlay(frames, style, geometry=None, zones_out=None, trails_out=None, track_out=None, zones=True, lines=True,
+                 counters=('occupancy', 'entries'), zone_alpha=48, occupied_alpha=96, trail_thickness=2, coasting=False):
+    """Paint the counting overlay into uint8 RGB frames on the device, IN PLACE, in one launch (include/mydet.h:
+    mydet_draw_overlay_rgb_u8, where the raster rules are).  frames: as in draw_boxes, [S*F,H,W,3] in the frame order of the
+    counting outputs.  style: ops.draw_style(...): its palette and, for the counter labels, its label_height are used.
+    geometry: overlay_geometry(...) of the zone_set that made zones_out, the dict of ops.zones_frames (occupancy, zone_counts,
+    line_counts are read on the device); zones / lines: paint the polygons (fill, outline) / the lines with their ticks;
+    counters: the parts of a zone's label, any of 'occupancy', 'entries', 'visits' (empty: no labels, of lines neither).
+    trails_out: the dict of ops.trails_frames, painted with trail_thickness for the tracks of track_out (the dict of
+    ops.track_frames both were made from) that the call shows: missed == 0, with coasting=True every live track.  Returns `frames`."""
+    what = 'draw_overlay'
+    kwargs = dict(geometry=geometry, zones_out=zones_out, trails_out=trails_out, track_out=track_out, zones=zones, lines=lines, counters=counters,
+                  zone_alpha=zone_alpha, occupied_alpha=occupied_alpha, trail_thickness=trail_thickness, coasting=coasting)
+    _draw_overlay(what, *_image(what, frames, None, None, None, True), style, kwargs)
+    return frames
+
+
+def draw_overlay_yuv420(planes, layout, style, geometry=None, zones_out=None, trails_out=None, track_out=None, zones=True, lines=True,
+                        counters=('occupancy', 'entries'), zone_alpha=48, occupied_alpha=96, trail_thickness=2, coasting=False,
+                        matrix='bt601', full_range=False):
+    """draw_overlay into the planes of 4:2:0 frames, IN PLACE (include/mydet.h: mydet_draw_overlay_yuv420_u8); planes, layout,
+    matrix and full_range as in draw_boxes_yuv420 ('p010' / 'i010' are not drawn into: ValueError).  Returns `planes`."""
+    what = 'draw_overlay_yuv420'
+    kwargs = dict(geometry=geometry, zones_out=zones_out, trails_out=trails_out, track_out=track_out, zones=zones, lines=lines, counters=counters,
+                  zone_alpha=zone_alpha, occupied_alpha=occupied_alpha, trail_thickness=trail_thickness, coasting=coasting)
+    _draw_overlay(what, *_image(what, planes, layout, matrix, full_range, True), style, kwargs)
+    return planes
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
