@@ -842,6 +842,82 @@ int mydet_trails_frames(const float *box, const int64_t *id, const int64_t *cls,
                         int S, int F, int max_tracks, const mydet_trail_set *ts, int32_t *state, int32_t *out_points,
                         int32_t *out_len, int32_t *out_bbox, void *stream);
 
+/* Camera motion: one global integer shift (dx, dy) per frame, estimated from the frames themselves on the device
+ * (csrc/motion.hip), for the tracker's predict step (mydet_track_frames_motion_f32 below).  On a pan, a shake or a drone every
+ * box jumps together and the IoU with the constant-velocity prediction fails for all tracks at once; the information is in the
+ * pixels, not in the boxes (BoT-SORT's camera-motion compensation; the reference project has nothing like it).  Everything
+ * is an integer; tests/_motion_ref.py restates the rules and the kernels equal it with == on every output and on the state.
+ *
+ * The estimator runs per stream: frame f of stream s is frame o = s*F + f of the B = S*F frames of the call.  The previous frame of
+ * frame f is frame f-1 of the call; for f = 0 it is the last frame of the previous call, of which the state keeps what is needed.
+ * Luma L(y, x), 0 .. 255: RGB frames (77 R + 150 G + 29 B + 128) >> 8; 4:2:0 planes the Y sample as 8 bits (the 10-bit rule of
+ *   mydet_yuv420_src: s8 = min(255, (v10 + 2) >> 2)); matrix, range and chroma play no part.
+ * Reduced luma, k = `reduce` in {2, 4, 8} (0: the smallest k with max(H, W) <= 512 k, else 8 -- mydet_motion_default_reduce):
+ *   hr = H / k, wr = W / k (integer division), r(i, j) = (sum of the k x k lumas at (i k, j k) + k*k/2) >> log2(k*k).  Rows and columns from
+ *   hr k, wr k on are not read.
+ * Blocks, R = `search` in MYDET_MOTION_MIN_SEARCH .. MYDET_MOTION_MAX_SEARCH reduced pixels: nby = (hr - 2R) / 16, nbx = (wr - 2R) / 16,
+ *   nb = nby nbx; block b = by nbx + bx is 16 x 16 with its origin (y0, x0) = (R + 16 by, R + 16 bx) in the PREVIOUS reduced luma.
+ * Coarse stage, per block: for every (dy, dx) in [-R, R]^2 the SAD of the previous block against the current reduced luma at
+ *   (y0 + dy, x0 + dx).  The best candidate is the smallest (SAD, dy*dy + dx*dx, dy, dx), compared lexicographically: a tie
+ *   goes to the smaller motion.  smin = its SAD, smax = the largest SAD of the block.  The block is VALID when
+ *   smax - smin >= min_texture (a flat block fails) and 2 smin <= smax (a block whose content is gone fails).  With fewer
+ *   than min_blocks valid blocks (0: max(2, ceil(nb / 8))) the frame's result is (0, 0, valid 0).  Otherwise D = the
+ *   component-wise LOWER MEDIAN of (cdx, cdy) over the valid blocks: the element at index (n - 1) / 2 of the ascending sort.
+ * Refine stage, at full resolution, valid blocks only: P = min(32, 8 k); the P x P patch of the previous luma has its origin at
+ *   (py, px) = ((y0 + 8) k - P/2, (x0 + 8) k - P/2).  For every (ey, ex) in [-k, k]^2 the SAD against the current luma at
+ *   (py + D.y k + ey, px + D.x k + ex); the best by (SAD, ey*ey + ex*ex, ey, ex); the block's vector is D k + e.  The geometry
+ *   keeps every read inside the frame.
+ * Result: (dx, dy) = the component-wise lower median of the block vectors, in whole pixels: content at p in the previous frame
+ *   is at p + d in this one; valid = 1; n_valid = the number of valid blocks.  The first frame of a stream after a reset is
+ *   (0, 0, 0, 0).  Not part of the rules: sub-pixel precision, rotation or zoom, masking detections out, motion beyond R k.
+ * Out: out_shift int32 [S*F][4] = (dx, dy, valid, n_valid); out_blocks (may be NULL) int32 [S*F][nb][6] = (cdx, cdy, smin, smax,
+ *   fdx, fdy), the block vector in (fdx, fdy); fields are zero where they are undefined (everything in a stream's first frame
+ *   after a reset; fdx, fdy of an invalid block and of a frame without enough valid blocks).
+ * state: S * mydet_motion_state_words(H, W, k, R) int32 words, 16-byte aligned, caller-owned, persistent, initialised (all zero)
+ *   by mydet_motion_reset.  Per stream, with wrp = wr rounded up to a multiple of 4:
+ *        [0] seen (0 | 1)   [1, 4) zero   then the reduced luma of the last frame, bytes [hr][wrp] (the padding columns zero)
+ *        then its nb patches, bytes [nb][P][P]; zero padding to a multiple of 4 words.
+ *   Two calls of F1 and F2 frames leave exactly the outputs and the state of one call of F1 + F2.
+ * ws: device scratch of at least mydet_motion_workspace_bytes(S*F, H, W, k, R) bytes, 16-byte aligned, stream-ordered.
+ * Frames are read in place: RGB packed pixels with any row and frame stride (as mydet_frames_to_input_f32); 4:2:0 through
+ *   mydet_yuv420_src, every layout.  set: HOST pointer.
+ * MYDET_E_BADARG, with nothing launched: B or S < 1 or B no multiple of S; a null or misaligned pointer; reduce not 0, 2, 4, 8;
+ *   search out of range; H / k or W / k below 2R + 16; a negative min_texture or min_blocks; a workspace too small; a frame
+ *   side above 32768; the source errors of the pixel format.  MYDET_E_UNSUPP: more than MYDET_MOTION_MAX_BLOCKS blocks
+ *   (mydet_motion_state_words and _workspace_bytes are 0 for every refused geometry). */
+#define MYDET_MOTION_MIN_SEARCH    4
+#define MYDET_MOTION_MAX_SEARCH    16
+#define MYDET_MOTION_MAX_BLOCKS    1024
+#define MYDET_MOTION_STATE_HEADER  4        /* words before the reduced luma */
+typedef struct mydet_motion_set {
+    int reduce;                          /* k: 2 | 4 | 8, or 0 for the default of the frame size */
+    int search;                          /* R, reduced pixels */
+    int min_texture, min_blocks;         /* min_blocks 0: max(2, ceil(nb / 8)) */
+    int reserved[4];
+} mydet_motion_set;
+int mydet_motion_default_reduce(int H, int W);
+int64_t mydet_motion_state_words(int H, int W, int k, int R);
+int64_t mydet_motion_workspace_bytes(int frames, int H, int W, int k, int R);
+int mydet_motion_reset(int32_t *state, int S, int H, int W, int k, int R, void *stream);
+int mydet_motion_frames_rgb_u8(const unsigned char *src, int B, int H, int W, int64_t src_img_bytes, int64_t src_row_bytes, int S,
+                               const mydet_motion_set *set, int32_t *state, void *ws, int64_t ws_bytes, int32_t *out_shift,
+                               int32_t *out_blocks, void *stream);
+int mydet_motion_frames_yuv420(const struct mydet_yuv420_src *src, int B, int H, int W, int S, const mydet_motion_set *set, int32_t *state,
+                               void *ws, int64_t ws_bytes, int32_t *out_shift, int32_t *out_blocks, void *stream);
+
+/* The tracker with camera motion: mydet_track_frames_assoc_f32 with one more argument, `shift` (DEVICE, int32 [S*F][4] = (dx, dy,
+ * valid, n_valid): out_shift of the estimator above for the same S and F; 4-byte aligned).  mydet_track_frames_assoc_f32 and
+ * mydet_track_frames_f32 are this entry point with shift = NULL and give the bits they always gave.
+ * Rule: in a frame whose valid == 1, every live track takes x[0] = x[0] + (float)dx, x[1] = x[1] + (float)dy inside `predict`,
+ * after x += v and before the frame's predicted box is taken: the association sees the moved prediction, a coasting track's
+ * output moves with the camera, and the leave-the-frame rule of `retire` sees the moved box.  Velocities and covariances are
+ * untouched; a bad-class frame leaves the state alone whatever its shift. */
+int mydet_track_frames_motion_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                  int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                  float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                  int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
+                                  void *stream);
+
 /* Winograd F(4x4,3x3) form of the same 3x3 stride-1 pad-1 conv + BN + act (+ residual) as mydet_conv2d_wino_f32
  * (4x fewer multiplies than the direct form; used for the deep layers with chip-filling grids).  `u` = the
  * transform-domain weights made by mydet_wino4_weights_f32 from the OHWI weight (mydet_wino4_weights_floats(Cout, Cin)

@@ -88,6 +88,14 @@ SIGNATURES = {
     'mydet_track_frames_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
     'mydet_track_frames_assoc_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                      c_ptr, c_ptr],
+    'mydet_track_frames_motion_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                      c_ptr, c_ptr, c_ptr],
+    'mydet_motion_default_reduce': [c_int, c_int],
+    'mydet_motion_state_words': [c_int, c_int, c_int, c_int],
+    'mydet_motion_workspace_bytes': [c_int, c_int, c_int, c_int, c_int],
+    'mydet_motion_reset': [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr],
+    'mydet_motion_frames_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
+    'mydet_motion_frames_yuv420': [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
     'mydet_zones_state_words': [c_int],
     'mydet_zones_reset': [c_ptr, c_int, c_int, c_ptr],
     'mydet_zones_frames': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
@@ -150,7 +158,7 @@ SIGNATURES = {
 
 RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems',
                'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words', 'mydet_mot_scratch_bytes', 'mydet_zones_state_words',
-               'mydet_redact_workspace_bytes', 'mydet_trails_state_words'}
+               'mydet_redact_workspace_bytes', 'mydet_trails_state_words', 'mydet_motion_state_words', 'mydet_motion_workspace_bytes'}
 
 # detection record layout (MYDET_REC_* of include/mydet.h), in int32 words
 REC_TOPK = 512
@@ -180,6 +188,8 @@ TRACK_ASSIGN_GREEDY, TRACK_ASSIGN_OPTIMAL = 0, 1
 ZONES_MAX, ZONE_MAX_VERTICES, ZONE_MAX_CLASSES, ZONE_MAX_HEAT, ZONE_MAX_FRAME, ZONE_COORD_MAX = 16, 16, 16, 1024, 32768, 1 << 20
 ZONE_ANCHOR_CENTER, ZONE_ANCHOR_BOTTOM = 0, 1
 ZONES_STATE_HEADER, ZONES_SLOT_WORDS = 148, 22
+# camera motion (mydet_motion_frames_*): MYDET_MOTION_* of include/mydet.h
+MOTION_MIN_SEARCH, MOTION_MAX_SEARCH, MOTION_MAX_BLOCKS, MOTION_STATE_HEADER = 4, 16, 1024, 4
 # overlay renderer (mydet_draw_boxes_*): MYDET_DRAW_* of include/mydet.h
 DRAW_MAX_BOXES, DRAW_MAX_THICKNESS, DRAW_MAX_GLYPHS, DRAW_NAME_BYTES = 512, 64, 33, 16
 DRAW_COLOR_CLASS, DRAW_COLOR_ID, DRAW_COLOR_FIXED = 0, 1, 2
@@ -273,6 +283,11 @@ class TrackAssoc(ctypes.Structure):
     """mydet_track_assoc (include/mydet.h): the association mode of mydet_track_frames_assoc_f32."""
     _fields_ = [('assign', c_int), ('bands', c_int), ('high_thres', c_f32), ('low_thres', c_f32), ('low_match_thres', c_f32),
                 ('reserved', c_int * 3)]
+
+
+class MotionSet(ctypes.Structure):
+    """mydet_motion_set (include/mydet.h): the settings of the camera-motion estimator; 0 = the default of the frame size."""
+    _fields_ = [('reduce', c_int), ('search', c_int), ('min_texture', c_int), ('min_blocks', c_int), ('reserved', c_int * 4)]
 
 
 class ZoneSet(ctypes.Structure):

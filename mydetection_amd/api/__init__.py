@@ -6,11 +6,13 @@ post-process suppresses (class-agnostic, Soft-NMS, box merging), `Augment`, its 
 views fused on the device), `Evaluator`, which scores what it returns against ground
 truth, `TrackEvaluator`, which scores its tracks against ground-truth identities, `Zones`, which counts its tracks in
 polygons and across lines on the device, and `Overlay`, which paints those zones, lines, counters and the tracks' trails into
-the annotated frames."""
+the annotated frames, and `CameraMotion`, which estimates the global image shift of every frame on the device and moves the
+tracker's predictions by it."""
 from .detection import Augment, Chips, Detector, Draw, Nms, Redact, Tiles
 from .evaluation import Evaluator, TrackEvaluator
+from .motion import CameraMotion
 from .overlay import Overlay
 from .tracking import Tracker
 from .zones import Zones
 
-__all__ = ['Augment', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Overlay', 'Redact', 'Tiles', 'TrackEvaluator', 'Tracker', 'Zones']
+__all__ = ['Augment', 'CameraMotion', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Overlay', 'Redact', 'Tiles', 'TrackEvaluator', 'Tracker', 'Zones']

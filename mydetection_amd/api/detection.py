@@ -783,6 +783,7 @@ class Detector():
         tracker, coasting = self._pop_tracker(kwargs)
         zones = self._pop_zones(kwargs, tracker)
         overlay = self._pop_overlay(kwargs, tracker, zones, draw)
+        motion = self._pop_motion(kwargs, tracker)
         sources = make_sources()
         used = draw is not None or chips is not None or redact is not None
         if tracker is not None:
@@ -792,6 +793,8 @@ class Detector():
                 zones.check_call(tracker, src.hw, self.model.bb_format)
             if overlay is not None:
                 overlay.check_call(tracker, zones, src.hw)
+            if motion is not None:
+                motion.check_call(tracker, src.hw)
         elif used:
             src, = sources                                           # a plain call alone takes any number of sizes, none included
         call = self._call_settings(kwargs, whole=tracker is not None or used)
@@ -803,7 +806,9 @@ class Detector():
             call = self._call_settings(dict(kwargs, conf_thres=min(conf_thres, tracker.low_thres)), whole=True)
         records = self._source_records(sources, call)
         if tracker is not None:
-            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres, zones, overlay)
+            # the camera motion of the whole original frames (whatever tiles= and augment= fed the network), ahead of the tracker
+            shift = None if motion is None else motion.run(*src.image(), tracker, src.hw)['shift']
+            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres, zones, overlay, shift)
         elif used:
             records = list(records)
             (idxs, found), = records                                 # one frame size: one group, in frame order
@@ -841,7 +846,13 @@ class Detector():
         tracker's (include/mydet.h: mydet_zones_frames) counts the tracks in its polygons and across its lines; the objects are
         bit for bit those of the call without zones= and carry zone_mask (int32: bit z = inside polygon z) and line_events
         (int32: bit 2l / 2l+1 = went through line l in its positive / negative direction in this frame); zones.last,
-        zones.counts() and zones.heat have the rest.  Every frame method that takes tracker= takes zones=."""
+        zones.counts() and zones.heat have the rest.  Every frame method that takes tracker= takes zones=.
+        motion: None, or a mydetection_amd.api.CameraMotion (with tracker= only: ValueError otherwise) for a camera that moves.
+        Its launches run on the call's whole original frames before the tracker's (include/mydet.h: mydet_motion_frames_rgb_u8),
+        give one integer shift (dx, dy) per frame against the frame before it, and the tracker moves every prediction by it
+        before the association (mydet_track_frames_motion_f32); no host synchronisation is added, motion.last has the shifts.
+        Zones, trails and the heat map stay in frame pixels and assume a fixed camera.  Every frame method that takes tracker=
+        takes motion=; without it every call is bit for bit what it was."""
         return self._detect(lambda: self._rgb_sources(frames), kwargs)
 
     @staticmethod
@@ -866,6 +877,18 @@ class Detector():
         return zones
 
     @staticmethod
+    def _pop_motion(kwargs, tracker):
+        """motion out of a frame method's keyword arguments: a TypeError for anything but a CameraMotion, a ValueError without
+        a tracker (the shift moves the tracker's predictions), both before any launch."""
+        from .motion import CameraMotion
+        motion = kwargs.pop('motion', None)
+        if motion is not None and not isinstance(motion, CameraMotion):
+            raise TypeError(f'motion: a mydetection_amd.api.CameraMotion (or None) expected, got {type(motion).__name__}')
+        if motion is not None and tracker is None:
+            raise ValueError('motion: motion= moves the predictions of a tracker and needs tracker= in the same call')
+        return motion
+
+    @staticmethod
     def _pop_overlay(kwargs, tracker, zones, draw):
         """overlay out of a frame method's keyword arguments: a TypeError for anything but an Overlay and in a method that does not
         draw, a ValueError without a tracker or, for the zone parts, without zones=, all before any launch."""
@@ -884,15 +907,16 @@ class Detector():
 
     @staticmethod
     def _no_tracker(kwargs, what):
-        if 'tracker' in kwargs or 'coasting' in kwargs or 'zones' in kwargs:
+        if 'tracker' in kwargs or 'coasting' in kwargs or 'zones' in kwargs or 'motion' in kwargs:
             raise TypeError(f'{what}: track ids in the json rows are not built; use the predict_frames form with tracker=')
 
-    def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres, zones=None, overlay=None):
+    def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres, zones=None, overlay=None, shift=None):
         """The tracked form of _objects_of_records: one eager tracker launch on the call's records (frame coordinates, one
         buffer), then per frame the ImageObjects of the tracks with missed == 0 (coasting: of every live track).  Two host
         synchronisations: the frame counts, and the indices of the selected slots.  zones: a Zones whose launch follows the
         tracker's at once (no synchronisation in between); the objects then carry zone_mask and line_events.  overlay: an
-        Overlay, whose trails launch follows them and which keeps the tracker's outputs for its paint launch."""
+        Overlay, whose trails launch follows them and which keeps the tracker's outputs for its paint launch.  shift: the
+        camera motion of the call's frames (CameraMotion.run), on the device."""
         from ..utils.structures import ImageObjects
         records = list(records)
         assert len(records) == 1, 'one frame size gives one network input size'
@@ -902,7 +926,7 @@ class Detector():
         width = 5 if 'angle' in rec else 4
         state = tracker.bind(frame_hw, width, rec['records'].device)
         params = tracker.params(frame_hw, tracker.resolve_match(self.model.bb_format), conf_thres)
-        out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks, assoc=tracker.assoc(conf_thres))
+        out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks, assoc=tracker.assoc(conf_thres), shift=shift)
         zout = None if zones is None else zones.run(out, tracker, frame_hw)
         if overlay is not None:                                      # the trails launch, behind the tracker's (and the zones')
             overlay.run_trails(out, tracker, zones, frame_hw)

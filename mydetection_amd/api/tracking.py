@@ -93,6 +93,7 @@ class Tracker:
         return self.state
 
     def reset(self):
-        """Forget every track; the next id of every stream is 1 again.  The frame size stays bound."""
+        """Forget every track; the next id of every stream is 1 again.  The frame size stays bound.  A CameraMotion used with
+        this tracker is not touched: it has its own reset()."""
         if self.state is not None:
             ops.track_reset_(self.state, self.max_tracks)

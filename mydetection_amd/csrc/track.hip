@@ -46,6 +46,7 @@ struct TrackArgs {
     int64_t *ocls, *oid;
     int32_t *omissed, *ocount, *odropped;
     mydet_track_assoc as;             // read by the instances with bands or the optimal assignment only
+    const int32_t *shift;             // null, or the camera motion of frame o at shift + 4 o: (dx, dy, valid, n_valid)
 };
 
 // LDS of the optimal assignment, dynamic: with the kernel's static arrays it is above the 64 KiB a kernel gets without the opt-in
@@ -226,6 +227,10 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
                 pxv[i] = t;
                 pvv[i] = pvv[i] + qv;
                 x[i] = x[i] + v[i];
+            }
+            if (a.shift) {                                         // camera motion: the prediction moves with the image
+                const int32_t *sh = a.shift + o * 4;
+                if (sh[2] == 1) { x[0] = x[0] + (float)sh[0]; x[1] = x[1] + (float)sh[1]; }
             }
             x[4] = mod180(x[4]);
             if (missed >= 1) score = P.momentum * score;
@@ -498,10 +503,11 @@ int track_launch_mode(const TrackArgs &a, int box_width, dim3 grid, dim3 block, 
 
 }  // namespace
 
-extern "C" int mydet_track_frames_assoc_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
-                                            int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
-                                            float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
-                                            int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, void *stream) {
+extern "C" int mydet_track_frames_motion_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                             int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                             float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                             int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
+                                             void *stream) {
     if (S <= 0 || F <= 0 || max_tracks < 1) return MYDET_E_BADARG;
     if (box_width != 4 && box_width != 5) return MYDET_E_BADARG;
     if (!records || !params || !state || !out_box || !out_score || !out_class || !out_id || !out_missed || !out_count || !out_dropped)
@@ -519,7 +525,7 @@ extern "C" int mydet_track_frames_assoc_f32(const int32_t *records, int64_t stre
     if (((uintptr_t)records & 15) || ((uintptr_t)state & 15)) return MYDET_E_BADARG;
     if (stream_stride_words < 0 || frame_stride_words < 0 || (stream_stride_words & 3) || (frame_stride_words & 3)) return MYDET_E_BADARG;
     if (((uintptr_t)out_box & 3) || ((uintptr_t)out_score & 3) || ((uintptr_t)out_class & 7) || ((uintptr_t)out_id & 7) ||
-        ((uintptr_t)out_missed & 3) || ((uintptr_t)out_count & 3) || ((uintptr_t)out_dropped & 3))
+        ((uintptr_t)out_missed & 3) || ((uintptr_t)out_count & 3) || ((uintptr_t)out_dropped & 3) || ((uintptr_t)shift & 3))
         return MYDET_E_BADARG;
     if (max_tracks > MYDET_TRACK_MAX_TRACKS) return MYDET_E_UNSUPP;
     TrackArgs a;
@@ -529,10 +535,19 @@ extern "C" int mydet_track_frames_assoc_f32(const int32_t *records, int64_t stre
     a.obox = out_box; a.oscore = out_score; a.ocls = out_class; a.oid = out_id; a.omissed = out_missed; a.ocount = out_count;
     a.odropped = out_dropped;
     a.as = *assoc;
+    a.shift = shift;
     const dim3 grid((unsigned)S), block((unsigned)((max_tracks + 63) / 64 * 64));
     if (assoc->assign == MYDET_TRACK_ASSIGN_OPTIMAL) return track_launch_mode<ASSOC_OPTIMAL>(a, box_width, grid, block, (hipStream_t)stream);
     if (assoc->bands) return track_launch_mode<ASSOC_GREEDY_BANDS>(a, box_width, grid, block, (hipStream_t)stream);
     return track_launch_mode<ASSOC_GREEDY>(a, box_width, grid, block, (hipStream_t)stream);
+}
+
+extern "C" int mydet_track_frames_assoc_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                            int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                            float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                            int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, void *stream) {
+    return mydet_track_frames_motion_f32(records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
+                                         out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, nullptr, stream);
 }
 
 extern "C" int mydet_track_frames_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,

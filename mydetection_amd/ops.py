@@ -1713,7 +1713,7 @@ def track_state_views(state, max_tracks=None):
     return out
 
 
-def track_frames(records, tracker_state, params, frames_per_stream=None, max_tracks=None, out=None, assoc=None):
+def track_frames(records, tracker_state, params, frames_per_stream=None, max_tracks=None, out=None, assoc=None, shift=None):
     """Advance S streams by F frames each in ONE launch (include/mydet.h: mydet_track_frames_f32, where the rules are).
     records: the detection records in frame coordinates -- an int32 tensor [S*F, words] (frame f of stream s in row s*F + f) or
     [S, F, words] with any strides along S and F that are multiples of 4 words, or the record_views dict of a [S*F, words]
@@ -1722,7 +1722,10 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     Returns a dict of device tensors: box [S,F,MT,5], score [S,F,MT], cls, id int64 [S,F,MT] (id 0 = a free slot), missed int32
     [S,F,MT] (0 = matched or born in this frame, -1 = a free slot), count int32 [S,F] (live tracks; MYDET_COUNT_BAD_CLASS for
     a bad-class frame, which leaves the state alone), dropped int32 [S,F].  out: such a dict to write into.  assoc: None for the
-    greedy single-band association of mydet_track_frames_f32, or a track_assoc(...) (mydet_track_frames_assoc_f32)."""
+    greedy single-band association of mydet_track_frames_f32, or a track_assoc(...) (mydet_track_frames_assoc_f32).  shift:
+    None, or the camera motion of the same frames -- motion_frames(...)['shift'], int32 [S,F,4] or [S*F,4] on the records'
+    device: in a frame with valid == 1 every prediction moves by (dx, dy) before the association
+    (mydet_track_frames_motion_f32)."""
     if not isinstance(params, _lib.TrackParams):
         raise TypeError(f'track_frames: params is a _lib.TrackParams (ops.track_params), got {type(params).__name__}')
     if assoc is not None and not isinstance(assoc, _lib.TrackAssoc):
@@ -1766,16 +1769,25 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
         t = out[k]
         if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
             raise ValueError(f'track_frames: out[{k!r}] must be a contiguous {dt} tensor {shape} on {dev}')
+    if shift is not None:
+        if (not isinstance(shift, torch.Tensor) or shift.dtype != torch.int32 or shift.numel() != S * F * 4 or shift.shape[-1] != 4 or
+                shift.device != dev or not shift.is_contiguous()):
+            raise ValueError(f'track_frames: shift must be a contiguous int32 tensor [{S},{F},4] on {dev} (ops.motion_frames)')
     t0 = TIMER.start() if TIMER else None
     args = (_ptr(records), records.stride(0), records.stride(1), S, F, width, ctypes.byref(params), mt, _ptr(tracker_state), _ptr(out['box']),
             _ptr(out['score']), _ptr(out['cls']), _ptr(out['id']), _ptr(out['missed']), _ptr(out['count']), _ptr(out['dropped']))
-    if assoc is None:
+    if shift is not None:
+        name = 'mydet_track_frames_motion_f32'
+        code = _lib.lib().mydet_track_frames_motion_f32(*args, ctypes.byref(track_assoc() if assoc is None else assoc), _ptr(shift), _stream())
+    elif assoc is None:
+        name = 'mydet_track_frames_f32'
         code = _lib.lib().mydet_track_frames_f32(*args, _stream())
     else:
+        name = 'mydet_track_frames_assoc_f32'
         code = _lib.lib().mydet_track_frames_assoc_f32(*args, ctypes.byref(assoc), _stream())
     if t0:
         TIMER.stop('track_frames', t0, float(S * F))
-    _lib.check(code, 'mydet_track_frames_f32' if assoc is None else 'mydet_track_frames_assoc_f32')
+    _lib.check(code, name)
     return out
 
 
@@ -1978,6 +1990,136 @@ def zones_frames(track_out, state, zone_set, heat=None, out=None):
     if t0:
         TIMER.stop('zones_frames', t0, float(S * F))
     _lib.check(code, 'mydet_zones_frames')
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Camera motion (include/mydet.h: mydet_motion_frames_rgb_u8, where the rules are; csrc/motion.hip)
+
+def motion_set(reduce=None, search=8, min_texture=1024, min_blocks=None):
+    """The settings of the camera-motion estimator (a _lib.MotionSet; include/mydet.h has the rules).  reduce: None (by frame
+    size: the smallest of 2, 4, 8 with max(H, W) <= 512 * reduce, else 8) or 2, 4, 8; search: 4 .. 16 reduced pixels;
+    min_texture: the least SAD range of a block that counts; min_blocks: None (max(2, ceil(blocks / 8))) or the least number of
+    valid blocks of a frame.  ValueError for anything out of range; touches no device."""
+    def whole(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f'motion_set: {name} is an integer, got {v!r}')
+        return int(v)
+    m = _lib.MotionSet()
+    if reduce is not None:
+        m.reduce = whole('reduce', reduce)
+        if m.reduce not in (2, 4, 8):
+            raise ValueError(f'motion_set: reduce is None, 2, 4 or 8, got {reduce!r}')
+    m.search = whole('search', search)
+    if not _lib.MOTION_MIN_SEARCH <= m.search <= _lib.MOTION_MAX_SEARCH:
+        raise ValueError(f'motion_set: search of {_lib.MOTION_MIN_SEARCH} .. {_lib.MOTION_MAX_SEARCH} reduced pixels expected, got {search!r}')
+    m.min_texture = whole('min_texture', min_texture)
+    if not 0 <= m.min_texture < 1 << 24:
+        raise ValueError(f'motion_set: 0 <= min_texture < 2^24 expected, got {min_texture!r}')
+    if min_blocks is not None:
+        m.min_blocks = whole('min_blocks', min_blocks)
+        if not 1 <= m.min_blocks <= _lib.MOTION_MAX_BLOCKS:
+            raise ValueError(f'motion_set: min_blocks is None or 1 .. {_lib.MOTION_MAX_BLOCKS}, got {min_blocks!r}')
+    return m
+
+
+def motion_geometry(frame_hw, set):
+    """The geometry the rules give a frame size (H, W) under a motion_set, host arithmetic only: a dict of k, R, hr, wr, wrp (wr
+    rounded up to a multiple of 4), nby, nbx, nb, P, min_blocks, state_words.  A ValueError for a frame that is too small for
+    2R + 16 reduced pixels per side, too large (32768), or has more than 1024 blocks."""
+    if not isinstance(set, _lib.MotionSet):
+        raise TypeError(f'motion: set is a _lib.MotionSet (ops.motion_set), got {type(set).__name__}')
+    try:
+        H, W = (int(v) for v in frame_hw)
+    except (TypeError, ValueError):
+        raise ValueError(f'motion: a frame size (H, W) expected, got {frame_hw!r}') from None
+    if not (1 <= H <= _lib.ZONE_MAX_FRAME and 1 <= W <= _lib.ZONE_MAX_FRAME):
+        raise ValueError(f'motion: a frame size (H, W) of 1 .. {_lib.ZONE_MAX_FRAME} each expected, got {frame_hw!r}')
+    R = set.search
+    k = set.reduce or next((c for c in (2, 4) if max(H, W) <= 512 * c), 8)
+    hr, wr = H // k, W // k
+    if min(hr, wr) < 2 * R + 16:
+        raise ValueError(f'motion: {H}x{W} frames reduced by {k} are {hr}x{wr}, below the 2 * search + 16 = {2 * R + 16} a block and its search window need')
+    nby, nbx = (hr - 2 * R) // 16, (wr - 2 * R) // 16
+    nb, P, wrp = nby * nbx, min(32, 8 * k), (wr + 3) // 4 * 4
+    if nb > _lib.MOTION_MAX_BLOCKS:
+        raise ValueError(f'motion: {H}x{W} frames reduced by {k} have {nb} blocks, above {_lib.MOTION_MAX_BLOCKS}; use a larger reduce')
+    words = (_lib.MOTION_STATE_HEADER + hr * wrp // 4 + nb * P * P // 4 + 3) // 4 * 4
+    return dict(H=H, W=W, k=k, R=R, hr=hr, wr=wr, wrp=wrp, nby=nby, nbx=nbx, nb=nb, P=P,
+                min_blocks=set.min_blocks or max(2, (nb + 7) // 8), state_words=words)
+
+
+def _check_motion_state(state, geo, what):
+    words = geo['state_words']
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != words or not state.is_contiguous():
+        got = f'{state.dtype} {tuple(state.shape)}' if isinstance(state, torch.Tensor) else type(state).__name__
+        raise ValueError(f"{what}: a contiguous int32 state [streams, {words}] for {geo['H']}x{geo['W']} frames expected, got {got}")
+    require_gpu(state, what)
+
+
+def motion_state(streams, frame_hw, set, device):
+    """A reset estimator state: int32 [streams, words] for frames of frame_hw under `set` (include/mydet.h has the layout)."""
+    geo = motion_geometry(frame_hw, set)
+    streams = int(streams)
+    if streams < 1:
+        raise ValueError(f'motion: streams >= 1 expected, got {streams}')
+    state = torch.empty((streams, geo['state_words']), dtype=torch.int32, device=device)
+    return motion_reset_(state, frame_hw, set)
+
+
+def motion_reset_(state, frame_hw, set):
+    """Reset an estimator state in place (mydet_motion_reset): the next frame of every stream has no previous one."""
+    geo = motion_geometry(frame_hw, set)
+    _check_motion_state(state, geo, 'motion_reset_')
+    code = _lib.lib().mydet_motion_reset(_ptr(state), state.shape[0], geo['H'], geo['W'], geo['k'], geo['R'], _stream())
+    _lib.check(code, 'mydet_motion_reset')
+    return state
+
+
+def motion_state_views(state, frame_hw, set):
+    """Field views of an estimator state int32 [S, words], nothing copied: seen int32 [S], reduced uint8 [S,hr,wr] (the last
+    frame's reduced luma), patches uint8 [S,nb,P,P].  Works on any device (tests read a host copy)."""
+    geo = motion_geometry(frame_hw, set)
+    if state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != geo['state_words'] or not state.is_contiguous():
+        raise ValueError(f"motion_state_views: a contiguous int32 state [streams, {geo['state_words']}] expected, got {state.dtype} {tuple(state.shape)}")
+    S, o = state.shape[0], _lib.MOTION_STATE_HEADER
+    nred, npat = geo['hr'] * geo['wrp'] // 4, geo['nb'] * geo['P'] ** 2 // 4
+    return {'seen': state[:, 0],
+            'reduced': state[:, o:o + nred].view(torch.uint8).view(S, geo['hr'], geo['wrp'])[:, :, :geo['wr']],
+            'patches': state[:, o + nred:o + nred + npat].view(torch.uint8).view(S, geo['nb'], geo['P'], geo['P'])}
+
+
+def motion_frames(image, state, set, frames_per_stream=None, layout=None, out=None):
+    """The camera motion of S streams x F frames (include/mydet.h: mydet_motion_frames_rgb_u8, where the rules are): per frame
+    one integer shift against the frame before it, which for a stream's first frame is the last frame of the previous call
+    (kept in `state`).  image: what the ops.draw_* functions take first, read only -- uint8 RGB frames [S*F,H,W,3] with
+    packed pixels and any row and frame strides (layout None), or the planes of `layout` ('nv12', 'nv21', 'i420', 'yv12', 'p010',
+    'i010') as in yuv420_to_rgb; frame f of stream s is frame s*F + f.  state: motion_state(...), updated in place; its row
+    count is S.  frames_per_stream: F, checked against the batch when given.  Returns {'shift': int32 [S,F,4] (dx, dy, valid,
+    n_valid), 'blocks': int32 [S,F,nb,6] (cdx, cdy, smin, smax, fdx, fdy)} on the device; out: such a dict to write into."""
+    what = 'motion_frames'
+    if not isinstance(set, _lib.MotionSet):
+        raise TypeError(f'{what}: set is a _lib.MotionSet (ops.motion_set), got {type(set).__name__}')
+    img, yuv, B = _image(what, image, layout, 'bt601', False, False)
+    H, W = (img.shape[1:3] if yuv is None else img[0].shape[1:3])
+    geo = motion_geometry((H, W), set)
+    _check_motion_state(state, geo, what)
+    S = state.shape[0]
+    if B % S or (frames_per_stream is not None and int(frames_per_stream) * S != B):
+        raise ValueError(f'{what}: {B} frames are not F frames of each of {S} streams')
+    F = B // S
+    dev = _same_device(what, img, [state])
+    shapes = {'shift': (S, F, 4), 'blocks': (S, F, geo['nb'], 6)}
+    if out is None:
+        out = {k: torch.empty(shape, dtype=torch.int32, device=dev) for k, shape in shapes.items()}
+    for k, shape in shapes.items():
+        t = out[k]
+        if tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f'{what}: out[{k!r}] must be a contiguous int32 tensor {shape} on {dev}')
+    nbytes = _lib.lib().mydet_motion_workspace_bytes(B, geo['H'], geo['W'], geo['k'], geo['R'])
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    _launch_on_image(what, img, yuv, 'mydet_motion_frames_rgb_u8', 'mydet_motion_frames_yuv420', S, ctypes.byref(set), _ptr(state),
+                     _ptr(ws), nbytes, _ptr(out['shift']), _ptr(out['blocks']))
     return out
 
 
