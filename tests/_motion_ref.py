@@ -78,6 +78,20 @@ def best(sads, r):
     return (key[2], key[3]), key[0], max(sads.values())
 
 
+def coarse_sads(prev_red, cur_red, g, b):
+    """sads[(dy, dx)] of block b of the previous reduced luma against the current one, every (dy, dx) in [-R, R]^2."""
+    y0, x0 = g.origin(b)
+    tpl = prev_red[y0:y0 + 16, x0:x0 + 16]
+    return {(dy, dx): int(np.abs(tpl - cur_red[y0 + dy:y0 + dy + 16, x0 + dx:x0 + dx + 16]).sum())
+            for dy in range(-g.R, g.R + 1) for dx in range(-g.R, g.R + 1)}
+
+
+def block_valid(row, g):
+    """Whether a block row (cdx, cdy, smin, smax, ...) is VALID under g.min_texture."""
+    smin, smax = int(row[2]), int(row[3])
+    return smax - smin >= g.min_texture and 2 * smin <= smax
+
+
 def estimate(prev_red, prev_patches, cur_L, g):
     """One frame against its predecessor: (shift [4], blocks [nb][6])."""
     blocks = np.zeros((g.nb, 6), np.int64)
@@ -85,13 +99,9 @@ def estimate(prev_red, prev_patches, cur_L, g):
     R, k, P = g.R, g.k, g.P
     valid = []
     for b in range(g.nb):
-        y0, x0 = g.origin(b)
-        tpl = prev_red[y0:y0 + 16, x0:x0 + 16]
-        sads = {(dy, dx): int(np.abs(tpl - cur_red[y0 + dy:y0 + dy + 16, x0 + dx:x0 + dx + 16]).sum())
-                for dy in range(-R, R + 1) for dx in range(-R, R + 1)}
-        (dy, dx), smin, smax = best(sads, R)
+        (dy, dx), smin, smax = best(coarse_sads(prev_red, cur_red, g, b), R)
         blocks[b, :4] = dx, dy, smin, smax
-        if smax - smin >= g.min_texture and 2 * smin <= smax:
+        if block_valid(blocks[b], g):
             valid.append(b)
     n = len(valid)
     if n < g.min_blocks:
@@ -142,15 +152,28 @@ def run(streams, lumas):
 
 # ---- test textures ----
 
-def texture(h, w, seed, smooth=5):
-    """Uniform noise smoothed by a smooth x smooth box mean, uint8 [h, w] (raw noise aliases in the reduced images)."""
-    rng = np.random.default_rng(seed)
-    raw = rng.integers(0, 256, (h + smooth - 1, w + smooth - 1)).astype(np.int64)
+def _box_mean(raw, h, w, smooth):
     acc = np.zeros((h, w), np.int64)
     for i in range(smooth):
         for j in range(smooth):
             acc += raw[i:i + h, j:j + w]
     return ((acc + smooth * smooth // 2) // (smooth * smooth)).astype(np.uint8)
+
+
+def texture(h, w, seed, smooth=5):
+    """Uniform noise smoothed by a smooth x smooth box mean, uint8 [h, w] (raw noise aliases in the reduced images)."""
+    rng = np.random.default_rng(seed)
+    return _box_mean(rng.integers(0, 256, (h + smooth - 1, w + smooth - 1)).astype(np.int64), h, w, smooth)
+
+
+def coarse_texture(h, w, seed, cell=12, smooth=5, saturate=0):
+    """Uniform noise replicated in cell x cell cells, then the box mean: texture() is too fine for k = 8 (a block's SAD range
+    stays below the default min_texture), this is not.  saturate: cell values are drawn from 0 .. 255 + saturate and clipped,
+    so that about saturate / 256 of the cells are 255, and stay 255 inside the cell (cell > smooth)."""
+    rng = np.random.default_rng(seed)
+    hh, ww = h + smooth - 1, w + smooth - 1
+    cells = np.minimum(255, rng.integers(0, 256 + saturate, (-(-hh // cell), -(-ww // cell))))
+    return _box_mean(cells.repeat(cell, axis=0).repeat(cell, axis=1)[:hh, :ww].astype(np.int64), h, w, smooth)
 
 
 def crops(tex, hw, offsets):
@@ -167,6 +190,68 @@ def offsets_of_shifts(shifts, margin):
         oy, ox = oy - dy, ox - dx
         out.append((oy, ox))
     return out
+
+
+# ---- test scenes whose blocks disagree ----
+
+def two_motions(tex_a, tex_b, hw, shifts_a, shifts_b, mask, margin):
+    """Frames uint8 [len(shifts) + 1, H, W] of two regions: where `mask` (bool [H, W]) is False crops of tex_a that move by
+    shifts_a, where it is True crops of tex_b that move by shifts_b.  The regions stay where they are; their content moves."""
+    a = crops(tex_a, hw, offsets_of_shifts(shifts_a, margin))
+    b = crops(tex_b, hw, offsets_of_shifts(shifts_b, margin))
+    return np.where(mask[None], b, a)
+
+
+def partly_flat(frames, mask, value=90):
+    """The frames with the region `mask` (bool [H, W]) at one constant luma: blocks that see nothing else are invalid."""
+    out = frames.copy()
+    out[..., mask] = value
+    return out
+
+
+def periodic(hw, period_yx, shift, seed, margin=32):
+    """Two frames uint8 [2, H, W] of a texture that repeats every period_yx[0] rows and period_yx[1] columns (None: does not
+    repeat along that axis), the second moved by shift = (dx, dy): candidates a whole period apart have equal SADs."""
+    H, W = hw
+    py, px = period_yx
+    tile = texture(py or H + 2 * margin, px or W + 2 * margin, seed)
+    big = np.tile(tile, (-(-(H + 2 * margin) // tile.shape[0]), -(-(W + 2 * margin) // tile.shape[1])))
+    return crops(big, hw, offsets_of_shifts([shift], margin))
+
+
+def diagonal(hw, period, shift, seed, margin=32):
+    """Two frames uint8 [2, H, W] of a texture that repeats only under the translation (dx, dy) = (period / 2, -period / 2) and
+    its multiples, the second moved by shift = (dx, dy): with shift = (period / 4, -period / 4) the candidates (dx, dy) and
+    (-dx, -dy) tie at the same distance, and the order of dy and dx in the comparison decides."""
+    H, W = hw
+    yy, xx = np.mgrid[:H + 2 * margin, :W + 2 * margin]
+    along = texture(H + W + 4 * margin, period, seed)
+    return crops(along[xx + yy, (xx - yy) % period], hw, offsets_of_shifts([shift], margin))
+
+
+def store_y(y8, layout, rng):
+    """The 8-bit luma y8 as the Y plane of `layout` stores it: uint8, or int16 words of ten live bits v10 = clip(4 y + j, 0,
+    1023) with a random j in [-2, 1] (up to +3 where y = 255: the clamp of the 10-bit rule) and six random ignored bits."""
+    if layout not in ('p010', 'i010'):
+        return y8.astype(np.uint8)
+    y = y8.astype(np.int64)
+    j = rng.integers(-2, 2, y.shape)
+    j = np.where(y == 255, rng.integers(-2, 4, y.shape), j)
+    v10 = np.clip(4 * y + j, 0, 1023).astype(np.uint16)
+    junk = rng.integers(0, 64, y.shape).astype(np.uint16)
+    return ((v10 << 6) | junk if layout == 'p010' else v10 | (junk << 10)).view(np.int16)
+
+
+def live_bits(stored, layout):
+    """The ten live bits of 16-bit words as the layout stores them, int64."""
+    w = np.asarray(stored).view(np.uint16).astype(np.int64)
+    return (w >> 6) if layout == 'p010' else (w & 1023)
+
+
+def medians(values):
+    """(lower, upper) median of a list of integers."""
+    v = sorted(int(x) for x in values)
+    return v[(len(v) - 1) // 2], v[len(v) // 2]
 
 
 # ---- the tracker with the shift ----

@@ -36,19 +36,28 @@ def _grey_crops(hw, shifts, seed=0):
     return ref.crops(_textures()[seed], hw, ref.offsets_of_shifts(shifts, MARGIN))
 
 
-def _run(image_of, lumas, hw, S, splits=None, layout=None, **set_kw):
+def _run(image_of, lumas, hw, S, splits=None, layout=None, want=None, fill=None, **set_kw):
     """The kernels on S streams x F frames, in one call or in the calls `splits` names, against the restatement's one call.
-    image_of(f0, n): what ops.motion_frames takes first for frames f0 .. f0 + n - 1 of every stream.  lumas: int64 [S, F, H, W]."""
+    image_of(f0, n): what ops.motion_frames takes first for frames f0 .. f0 + n - 1 of every stream.  lumas: int64 [S, F, H, W].
+    want: (shift, blocks, streams) of the restatement where the caller has them already (lumas is not read then).  fill: the
+    outputs are passed in as out=, every word `fill` beforehand: what the kernels leave unwritten shows."""
     from mydetection_amd import ops
-    F = lumas.shape[1]
-    g = ref.Geometry(hw, set_kw.get('reduce'), set_kw.get('search', 8), set_kw.get('min_texture', 1024), set_kw.get('min_blocks'))
-    streams = [ref.Stream(g) for _ in range(S)]
-    want_shift, want_blocks = ref.run(streams, lumas)
+    if want is None:
+        g = ref.Geometry(hw, set_kw.get('reduce'), set_kw.get('search', 8), set_kw.get('min_texture', 1024), set_kw.get('min_blocks'))
+        streams = [ref.Stream(g) for _ in range(S)]
+        want_shift, want_blocks = ref.run(streams, lumas)
+    else:
+        want_shift, want_blocks, streams = want
+    F = want_shift.shape[1]
     mset = ops.motion_set(**set_kw)
     state = ops.motion_state(S, hw, mset, 'cuda')
     parts, lo = [], 0
     for n in splits or [F]:
-        parts.append(ops.motion_frames(image_of(lo, n), state, mset, frames_per_stream=n, layout=layout))
+        out = None
+        if fill is not None:
+            out = {'shift': torch.full((S, n, 4), fill, dtype=torch.int32, device='cuda'),
+                   'blocks': torch.full((S, n, want_blocks.shape[2], 6), fill, dtype=torch.int32, device='cuda')}
+        parts.append(ops.motion_frames(image_of(lo, n), state, mset, frames_per_stream=n, layout=layout, out=out))
         lo += n
     assert lo == F
     shift = torch.cat([p['shift'] for p in parts], dim=1).cpu().numpy()
