@@ -1527,6 +1527,80 @@ int mydet_crop_boxes_rgb(const unsigned char *src, int B, int H, int W, int64_t 
 int mydet_crop_boxes_yuv420(const mydet_yuv420_src *src, int B, int H, int W,
                             const mydet_draw_list *list, const mydet_crop_out *out, void *stream);
 
+/* Appearance: a colour descriptor per box (csrc/appear.hip) and a tracker that matches by it too (csrc/track.hip), DeepSORT's and
+ * BoT-SORT's appearance branch with a colour histogram in place of a ReID network (the library ships no weights).  The tracker
+ * side takes ANY array of 128 uint16 bins per detection whose bins sum to at most 512 (not checked; S below is then <= 131072
+ * and cannot overflow), so a learned embedding can be quantised into it.  No reference counterpart: the rules are this library's.
+ *
+ * Descriptor (mydet_appear_boxes_rgb_u8 / _yuv420).  Arguments as the crop entry points: the frames or a mydet_yuv420_src, B, H,
+ *   W, and a mydet_draw_list read in place (box and angle planes, count; score, cls, id ignored).  Out: desc, uint16
+ *   [B][K][128], frame b at desc + b*desc_frame_stride (elements).  EVERY row k < K of every frame is written: a row at or beyond
+ *   the frame's count (NULL count: K; a negative count -- MYDET_COUNT_BAD_CLASS -- is 0) is 128 zeros.
+ *   Geometry, float32 and uncontracted, in the order written.  (c, s) by the Rotation rule of the object chips above (angle 0
+ *   without an angle plane).  32 rows x 16 columns of samples over the central 0.75 of the box:
+ *       sx = w * 0.75f / 16,  sy = h * 0.75f / 32
+ *       lx = ((float)j + 0.5f - 8.0f) * sx,  ly = ((float)i + 0.5f - 16.0f) * sy      (0 <= i < 32, 0 <= j < 16)
+ *       X  = cx + lx*c - ly*s,  Y = cy + lx*s + ly*c
+ *   Sampling.  A sample whose X or Y is NaN or has |.| > 2^29 is not counted (only a non-finite or absurd box has such samples).
+ *   Every other sample reads the nearest pixel x = clamp((int)floorf(X), 0, W-1), y = clamp((int)floorf(Y), 0, H-1): a box
+ *   outside the frame reads edge pixels, nothing outside the view is addressed.
+ *   Bin of a sample with pixel (R, G, B): (i >> 4)*64 + (R >> 6)*16 + (G >> 6)*4 + (B >> 6) -- the upper and the lower half of
+ *   the object each get a joint 4 x 4 x 4 colour histogram.  desc[b][k][bin] = the number of samples; a row sums to at most 512.
+ *   4:2:0 sources: every layout of mydet_crop_boxes_yuv420, every tap converted as there, so the descriptors are bit for bit
+ *   those of the RGB frames mydet_yuv420_to_rgb_u8 gives, which are never built.
+ *   MYDET_E_BADARG, nothing launched: a null list, box plane, source or desc; non-positive B, H, W; a source pitch below the row's
+ *   bytes; a negative stride; K outside 1..MYDET_DRAW_MAX_BOXES; desc not 4-byte aligned; desc_frame_stride odd or < K*128; and
+ *   what mydet_yuv420_src refuses.  MYDET_E_UNSUPP: B > 65535, H or W > 2^24.
+ *
+ * Tracker (mydet_track_frames_appear_f32): mydet_track_frames_motion_f32 (shift may be NULL) with
+ *   appear        HOST pointer to the settings below;
+ *   desc          DEVICE uint16, the descriptors of frame o = s*F + f at desc + o*512*128, row = record slot; 16-byte aligned;
+ *   appear_state  DEVICE int32, S * mydet_track_appear_state_words(max_tracks) words, 16-byte aligned, caller-owned, persistent,
+ *                 all zero at the start.  Per stream, MT = max_tracks: has [MT] (1: the slot's track has a template), then
+ *                 tmpl [128][MT] in units of 1/256 sample (bin-major), zero padding to a multiple of 4 words;
+ *   out_sim, out_how   int32 [S*F][max_tracks].
+ *   Similarity: S(j, d) = sum over the 128 bins of min(tmpl[b][j], 256 * desc[d][b]), an int32 in 0..MYDET_APPEAR_SIM_MAX.
+ *   Per frame, beside the rules of mydet_track_frames_f32 and mydet_track_assoc (greedy; one band or two):
+ *   gate      in the walk, a pair that passes every test of today's walk and iou > the threshold is offered only if gate == 0,
+ *             or has[j] == 0, or S(j, d) >= gate.  The key stays IoU-major with the same tie rule.
+ *   re-identification   after the walk, before the update, if reid > 0.  In rank order, every detection that is still unmatched and
+ *             would be born (score >= new_thres; with bands also >= high_thres) is offered to every live track j that is
+ *             unmatched, of its class, has[j] == 1, missed >= 2 after predict, and within reach: with m = max(x[2], x[3], z_w,
+ *             z_h), fabsf(z_cx - x[0]) <= reach*m and fabsf(z_cy - x[1]) <= reach*m (float32; x the prediction after the
+ *             camera shift), and S(j, d) >= reid.  The largest S wins, the lowest slot on a tie; the winner takes the detection
+ *             exactly as a matched track does (update, score, missed = 0).
+ *   template  a track matched in any stage to a detection with score >= update_thres: t += ((256*d - t) * alpha) >> 8 per bin
+ *             (arithmetic shift, alpha in 1..256), or t = 256*d when has == 0, which sets has.  A birth writes t = 256*d,
+ *             has = 1.  A retired slot clears both.  A bad-class frame leaves everything alone.
+ *   out_how   -1 a free slot, 0 live and unmatched, 1 / 2 matched in the high / low band, 3 re-identified, 4 born.
+ *   out_sim   S of the pair that matched, with the template as it was before the update (0 for has == 0), else -1.
+ *   With gate == 0 and reid == 0 every other output and the tracker state are those of mydet_track_frames_motion_f32.
+ *   MYDET_E_BADARG: as mydet_track_frames_motion_f32, and a null or misaligned appear, desc, appear_state, out_sim or out_how;
+ *   gate or reid outside 0..MYDET_APPEAR_SIM_MAX; alpha outside 1..256; reach negative or not finite; update_thres NaN.
+ *   MYDET_E_UNSUPP: MYDET_TRACK_ASSIGN_OPTIMAL (the solver forms its costs on the fly and would recompute S inside its inner
+ *   loop).  mydet_track_appear_state_words is 0 for a max_tracks the tracker refuses. */
+#define MYDET_APPEAR_BINS    128
+#define MYDET_APPEAR_SAMPLES 512
+#define MYDET_APPEAR_SIM_MAX 131072      /* 256 * MYDET_APPEAR_SAMPLES */
+typedef struct mydet_track_appear {
+    int gate, reid;                      /* on the scale of S; 0 = off */
+    int alpha;                           /* 1..256: the template moves by alpha/256 of the difference */
+    float reach;                         /* re-identification: centre distance per axis, in units of the larger box side */
+    float update_thres;                  /* the detection score from which a match moves the template */
+    int reserved[3];
+} mydet_track_appear;
+int mydet_appear_boxes_rgb_u8(const unsigned char *src, int B, int H, int W, int64_t src_img_bytes, int64_t src_row_bytes,
+                              const mydet_draw_list *list, uint16_t *desc, int64_t desc_frame_stride, void *stream);
+int mydet_appear_boxes_yuv420(const mydet_yuv420_src *src, int B, int H, int W, const mydet_draw_list *list, uint16_t *desc,
+                              int64_t desc_frame_stride, void *stream);
+int64_t mydet_track_appear_state_words(int max_tracks);
+int mydet_track_frames_appear_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                  int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                  float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                  int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
+                                  const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
+                                  int32_t *out_sim, int32_t *out_how, void *stream);
+
 /* Scoring detections against ground truth: COCO's bbox evaluation with useCats = 1, in three stream-ordered launches
  * (csrc/evalmatch.hip).  Replaces utils/evaluation/coco.py (coco_evaluate_bbox, myCOCOeval) and utils/evaluation/cepdof.py
  * (evaluate_json, CEPDOFeval) of the reference, which sit on pycocotools: its computeIoU, evaluateImg and accumulate.  The

@@ -90,6 +90,11 @@ SIGNATURES = {
                                      c_ptr, c_ptr],
     'mydet_track_frames_motion_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_ptr, c_ptr],
+    'mydet_track_appear_state_words': [c_int],
+    'mydet_track_frames_appear_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                      c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_appear_boxes_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr],
+    'mydet_appear_boxes_yuv420': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr],
     'mydet_motion_default_reduce': [c_int, c_int],
     'mydet_motion_state_words': [c_int, c_int, c_int, c_int],
     'mydet_motion_workspace_bytes': [c_int, c_int, c_int, c_int, c_int],
@@ -158,7 +163,8 @@ SIGNATURES = {
 
 RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems',
                'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words', 'mydet_mot_scratch_bytes', 'mydet_zones_state_words',
-               'mydet_redact_workspace_bytes', 'mydet_trails_state_words', 'mydet_motion_state_words', 'mydet_motion_workspace_bytes'}
+               'mydet_redact_workspace_bytes', 'mydet_trails_state_words', 'mydet_motion_state_words', 'mydet_motion_workspace_bytes',
+               'mydet_track_appear_state_words'}
 
 # detection record layout (MYDET_REC_* of include/mydet.h), in int32 words
 REC_TOPK = 512
@@ -184,6 +190,8 @@ TRACK_MAX_TRACKS = 512
 TRACK_STATE_HEADER, TRACK_SLOT_WORDS = 8, 31
 TRACK_MATCH_IOU, TRACK_MATCH_ROTATED = 0, 1
 TRACK_ASSIGN_GREEDY, TRACK_ASSIGN_OPTIMAL = 0, 1
+# appearance (mydet_appear_boxes_*, mydet_track_frames_appear_f32): MYDET_APPEAR_* of include/mydet.h
+APPEAR_BINS, APPEAR_SAMPLES, APPEAR_SIM_MAX = 128, 512, 131072
 # zones and lines (mydet_zones_frames): MYDET_ZONE* of include/mydet.h
 ZONES_MAX, ZONE_MAX_VERTICES, ZONE_MAX_CLASSES, ZONE_MAX_HEAT, ZONE_MAX_FRAME, ZONE_COORD_MAX = 16, 16, 16, 1024, 32768, 1 << 20
 ZONE_ANCHOR_CENTER, ZONE_ANCHOR_BOTTOM = 0, 1
@@ -283,6 +291,11 @@ class TrackAssoc(ctypes.Structure):
     """mydet_track_assoc (include/mydet.h): the association mode of mydet_track_frames_assoc_f32."""
     _fields_ = [('assign', c_int), ('bands', c_int), ('high_thres', c_f32), ('low_thres', c_f32), ('low_match_thres', c_f32),
                 ('reserved', c_int * 3)]
+
+
+class TrackAppear(ctypes.Structure):
+    """mydet_track_appear (include/mydet.h): the appearance settings of mydet_track_frames_appear_f32; gate and reid on the scale of S."""
+    _fields_ = [('gate', c_int), ('reid', c_int), ('alpha', c_int), ('reach', c_f32), ('update_thres', c_f32), ('reserved', c_int * 3)]
 
 
 class MotionSet(ctypes.Structure):

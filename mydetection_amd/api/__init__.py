@@ -7,7 +7,9 @@ views fused on the device), `Evaluator`, which scores what it returns against gr
 truth, `TrackEvaluator`, which scores its tracks against ground-truth identities, `Zones`, which counts its tracks in
 polygons and across lines on the device, and `Overlay`, which paints those zones, lines, counters and the tracks' trails into
 the annotated frames, and `CameraMotion`, which estimates the global image shift of every frame on the device and moves the
-tracker's predictions by it."""
+tracker's predictions by it, and `Appearance`, which gives every detection a colour descriptor on the device and lets the
+tracker gate its matches and re-identify lost tracks by it."""
+from .appearance import Appearance
 from .detection import Augment, Chips, Detector, Draw, Nms, Redact, Tiles
 from .evaluation import Evaluator, TrackEvaluator
 from .motion import CameraMotion
@@ -15,4 +17,4 @@ from .overlay import Overlay
 from .tracking import Tracker
 from .zones import Zones
 
-__all__ = ['Augment', 'CameraMotion', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Overlay', 'Redact', 'Tiles', 'TrackEvaluator', 'Tracker', 'Zones']
+__all__ = ['Appearance', 'Augment', 'CameraMotion', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Overlay', 'Redact', 'Tiles', 'TrackEvaluator', 'Tracker', 'Zones']

@@ -1,0 +1,79 @@
+"""`Appearance`: the `appearance=` argument of Detector's tracked frame methods -- the tracker matches by what an object looks
+like as well as by where it is.  One launch on the call's frames gives every detection a 128-bin colour descriptor
+(ops.appear_records; include/mydet.h: mydet_appear_boxes_rgb_u8 has the rule), and the tracker launch keeps a template per
+track, gates its IoU matches by it and re-identifies lost tracks (mydet_track_frames_appear_f32).  The reference project has
+no tracker loop and nothing like it; the step is the appearance branch of DeepSORT / BoT-SORT with a colour histogram in place
+of a ReID network: the package ships no weights."""
+from .. import ops
+
+
+class Appearance:
+    """The appearance settings and the templates of every track slot of the tracker it is used with.
+
+    gate: None (off) or a fraction in (0, 1] of the largest similarity -- an IoU match of a track that has a template is
+    offered only when the histogram intersection of template and detection reaches it; reid: None (off) or such a fraction --
+    a detection that would start a track is instead given to the most similar lost track (not matched in the previous frame)
+    of its class within `reach` times the larger box side of its predicted centre, when the similarity reaches it; momentum:
+    the share of its old template a matched track keeps; update_thres: the detection score from which a match moves the
+    template (None: the tracker's birth threshold, so a low-band match never does).  The defaults are starting points, not
+    tuned values: there is no dataset behind them.  Greedy assignment only: a Tracker with assign='optimal' is a ValueError.
+    The first call binds the object to the tracker's streams and max_tracks, the frame size and the device; a later call with
+    another is a ValueError.  `state` is then the int32 [streams, words] device buffer (ops.appear_state_views names its
+    fields) and `last` the latest call's outputs on the device: 'desc' uint16 [B,512,128] (row = record slot of the call's
+    final records), 'sim' and 'how' int32 [streams, F, max_tracks].
+    reset() clears every template; Tracker.reset() does NOT touch this object, and need not: a slot's template is read only
+    while its `has` flag is set, and a birth into a slot overwrites both."""
+
+    def __init__(self, gate=0.3, reid=0.6, momentum=0.9, reach=2.0, update_thres=None):
+        ops.appear_set(gate, reid, momentum, reach, 0.0 if update_thres is None else update_thres)     # the range checks, before any device
+        self.gate, self.reid, self.momentum, self.reach = gate, reid, float(momentum), float(reach)
+        self.update_thres = None if update_thres is None else float(update_thres)
+        self.state = self.last = None
+        self.streams = self.max_tracks = self.img_hw = None
+
+    def __repr__(self):
+        return (f'Appearance(gate={self.gate}, reid={self.reid}, momentum={self.momentum}, reach={self.reach}, '
+                f'update_thres={self.update_thres})')
+
+    def set(self, birth_thres):
+        """The kernel's settings struct for a call whose tracker starts tracks at `birth_thres`."""
+        return ops.appear_set(self.gate, self.reid, self.momentum, self.reach, birth_thres if self.update_thres is None else self.update_thres)
+
+    def check_call(self, tracker, img_hw):
+        """The argument rules of a call that need no device: a greedy tracker, and the tracker's streams and max_tracks and the
+        frame size are those of the first call."""
+        if tracker.assign != 'greedy':
+            raise ValueError(f"appearance: runs with a Tracker of assign='greedy' only, got assign={tracker.assign!r}")
+        hw = (int(img_hw[0]), int(img_hw[1]))
+        if self.img_hw is not None and (tracker.streams, tracker.max_tracks, hw) != (self.streams, self.max_tracks, self.img_hw):
+            raise ValueError(f'appearance: bound to {self.streams} streams of {self.max_tracks} tracks on {self.img_hw[0]}x{self.img_hw[1]} frames '
+                             f'by its first call, got {tracker.streams} streams of {tracker.max_tracks} tracks on {hw[0]}x{hw[1]} frames')
+
+    def bind(self, tracker, img_hw, device):
+        """First call: take the tracker's streams and max_tracks and the frame size, allocate the state on the device."""
+        if self.state is None:
+            self.streams, self.max_tracks, self.img_hw = tracker.streams, tracker.max_tracks, (int(img_hw[0]), int(img_hw[1]))
+            self.state = ops.appear_state(self.streams, self.max_tracks, device)
+        elif self.state.device != device:
+            raise ValueError(f'appearance: its state lives on {self.state.device}, this call runs on {device}')
+        return self.state
+
+    def run(self, image, yuv, rec, tracker, img_hw, birth_thres):
+        """The descriptor launch on the frames of a call (image, yuv: what a frame source's image() returns) and its final
+        records; no host synchronisation.  Returns what ops.track_frames takes as appear= and keeps the descriptors in `last`."""
+        self.check_call(tracker, img_hw)
+        first = image if not isinstance(image, (tuple, list)) else image[0]
+        state = self.bind(tracker, img_hw, first.device)
+        desc = ops.appear_records(image, rec, **yuv)
+        self.last = {'desc': desc}
+        return self.set(birth_thres), desc, state
+
+    def took(self, track_out):
+        """Keep the tracker launch's sim and how beside the descriptors."""
+        self.last.update(sim=track_out['sim'], how=track_out['how'])
+
+    def reset(self):
+        """Clear every template.  The binding stays; the tracker is not touched."""
+        if self.state is not None:
+            ops.appear_reset_(self.state, self.max_tracks)
+        self.last = None

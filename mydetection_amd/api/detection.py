@@ -784,6 +784,7 @@ class Detector():
         zones = self._pop_zones(kwargs, tracker)
         overlay = self._pop_overlay(kwargs, tracker, zones, draw)
         motion = self._pop_motion(kwargs, tracker)
+        appearance = self._pop_appearance(kwargs, tracker)
         sources = make_sources()
         used = draw is not None or chips is not None or redact is not None
         if tracker is not None:
@@ -795,6 +796,8 @@ class Detector():
                 overlay.check_call(tracker, zones, src.hw)
             if motion is not None:
                 motion.check_call(tracker, src.hw)
+            if appearance is not None:
+                appearance.check_call(tracker, src.hw)
         elif used:
             src, = sources                                           # a plain call alone takes any number of sizes, none included
         call = self._call_settings(kwargs, whole=tracker is not None or used)
@@ -808,7 +811,9 @@ class Detector():
         if tracker is not None:
             # the camera motion of the whole original frames (whatever tiles= and augment= fed the network), ahead of the tracker
             shift = None if motion is None else motion.run(*src.image(), tracker, src.hw)['shift']
-            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres, zones, overlay, shift)
+            # the descriptors come from the whole original frames too, at the call's final records: behind the motion launches
+            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres, zones, overlay, shift,
+                                                 None if appearance is None else (appearance, src))
         elif used:
             records = list(records)
             (idxs, found), = records                                 # one frame size: one group, in frame order
@@ -852,7 +857,16 @@ class Detector():
         give one integer shift (dx, dy) per frame against the frame before it, and the tracker moves every prediction by it
         before the association (mydet_track_frames_motion_f32); no host synchronisation is added, motion.last has the shifts.
         Zones, trails and the heat map stay in frame pixels and assume a fixed camera.  Every frame method that takes tracker=
-        takes motion=; without it every call is bit for bit what it was."""
+        takes motion=; without it every call is bit for bit what it was.
+        appearance: None, or a mydetection_amd.api.Appearance (with tracker= only, and only with its assign='greedy': ValueError
+        otherwise) to match by what an object looks like too.  One launch on the call's whole original frames and its final
+        records (after the tile merge or the view fusion, behind the motion launches; include/mydet.h:
+        mydet_appear_boxes_rgb_u8) gives every detection a 128-bin colour descriptor -- 32 x 16 nearest-pixel samples over the
+        central 0.75 of the box, a 4 x 4 x 4 colour histogram for its upper and one for its lower half --, and the tracker launch
+        (mydet_track_frames_appear_f32) keeps a template per track, offers an IoU match only when the histogram intersection
+        reaches `gate`, and gives a detection that would start a track to the most similar lost track within `reach` instead
+        when it reaches `reid`.  No host synchronisation is added; appearance.last has desc, sim and how.  Every frame method
+        that takes tracker= takes appearance=; without it every call is bit for bit what it was."""
         return self._detect(lambda: self._rgb_sources(frames), kwargs)
 
     @staticmethod
@@ -889,6 +903,20 @@ class Detector():
         return motion
 
     @staticmethod
+    def _pop_appearance(kwargs, tracker):
+        """appearance out of a frame method's keyword arguments: a TypeError for anything but an Appearance, a ValueError without
+        a tracker (the templates belong to its tracks) or with one whose assignment is 'optimal', all before any launch."""
+        from .appearance import Appearance
+        appearance = kwargs.pop('appearance', None)
+        if appearance is not None and not isinstance(appearance, Appearance):
+            raise TypeError(f'appearance: a mydetection_amd.api.Appearance (or None) expected, got {type(appearance).__name__}')
+        if appearance is not None and tracker is None:
+            raise ValueError('appearance: appearance= gates and re-identifies the tracks of a tracker and needs tracker= in the same call')
+        if appearance is not None and tracker.assign != 'greedy':
+            raise ValueError(f"appearance: runs with a Tracker of assign='greedy' only, got assign={tracker.assign!r}")
+        return appearance
+
+    @staticmethod
     def _pop_overlay(kwargs, tracker, zones, draw):
         """overlay out of a frame method's keyword arguments: a TypeError for anything but an Overlay and in a method that does not
         draw, a ValueError without a tracker or, for the zone parts, without zones=, all before any launch."""
@@ -907,16 +935,17 @@ class Detector():
 
     @staticmethod
     def _no_tracker(kwargs, what):
-        if 'tracker' in kwargs or 'coasting' in kwargs or 'zones' in kwargs or 'motion' in kwargs:
+        if 'tracker' in kwargs or 'coasting' in kwargs or 'zones' in kwargs or 'motion' in kwargs or 'appearance' in kwargs:
             raise TypeError(f'{what}: track ids in the json rows are not built; use the predict_frames form with tracker=')
 
-    def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres, zones=None, overlay=None, shift=None):
+    def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres, zones=None, overlay=None, shift=None, appearance=None):
         """The tracked form of _objects_of_records: one eager tracker launch on the call's records (frame coordinates, one
         buffer), then per frame the ImageObjects of the tracks with missed == 0 (coasting: of every live track).  Two host
         synchronisations: the frame counts, and the indices of the selected slots.  zones: a Zones whose launch follows the
         tracker's at once (no synchronisation in between); the objects then carry zone_mask and line_events.  overlay: an
         Overlay, whose trails launch follows them and which keeps the tracker's outputs for its paint launch.  shift: the
-        camera motion of the call's frames (CameraMotion.run), on the device."""
+        camera motion of the call's frames (CameraMotion.run), on the device.  appearance: (an Appearance, the call's frame
+        source): its descriptor launch on these records runs right ahead of the tracker's."""
         from ..utils.structures import ImageObjects
         records = list(records)
         assert len(records) == 1, 'one frame size gives one network input size'
@@ -926,7 +955,13 @@ class Detector():
         width = 5 if 'angle' in rec else 4
         state = tracker.bind(frame_hw, width, rec['records'].device)
         params = tracker.params(frame_hw, tracker.resolve_match(self.model.bb_format), conf_thres)
-        out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks, assoc=tracker.assoc(conf_thres), shift=shift)
+        assoc, appear = tracker.assoc(conf_thres), None
+        if appearance is not None:
+            birth = max(params.new_thres, assoc.high_thres) if assoc is not None and assoc.bands else params.new_thres
+            appear = appearance[0].run(*appearance[1].image(), rec, tracker, frame_hw, birth)
+        out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks, assoc=assoc, shift=shift, appear=appear)
+        if appearance is not None:
+            appearance[0].took(out)
         zout = None if zones is None else zones.run(out, tracker, frame_hw)
         if overlay is not None:                                      # the trails launch, behind the tracker's (and the zones')
             overlay.run_trails(out, tracker, zones, frame_hw)

@@ -94,6 +94,8 @@ class Tracker:
 
     def reset(self):
         """Forget every track; the next id of every stream is 1 again.  The frame size stays bound.  A CameraMotion used with
-        this tracker is not touched: it has its own reset()."""
+        this tracker is not touched: it has its own reset().  Neither is an Appearance: a slot's template is read only while its
+        `has` flag is set, a reset tracker matches nothing (so no template moves), and a birth into a slot overwrites both; call
+        Appearance.reset() as well to clear them at once."""
         if self.state is not None:
             ops.track_reset_(self.state, self.max_tracks)

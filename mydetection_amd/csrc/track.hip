@@ -22,6 +22,8 @@
 //      above new_thres are born into the lowest free slots -- ranks by ballot and popcount, no serial loop.
 // Built with -ffp-contract=off: the float32 operation order below IS the definition (tests/_track_ref.py restates it in numpy
 // and is held to the reference's float64 on tests/golden/kf_tracklet.npz).
+#include <type_traits>
+
 #include "common.h"
 #include "hung.h"
 #include "rot_iou.h"
@@ -48,6 +50,17 @@ struct TrackArgs {
     mydet_track_assoc as;             // read by the instances with bands or the optimal assignment only
     const int32_t *shift;             // null, or the camera motion of frame o at shift + 4 o: (dx, dy, valid, n_valid)
 };
+// The arguments of the instances with an appearance (mydet_track_frames_appear_f32): the others keep TrackArgs as it was
+struct TrackAppearArgs : TrackArgs {
+    mydet_track_appear ap;
+    const uint16_t *desc;             // the descriptors of frame o at desc + o * KMAX * 128, row = record slot
+    int32_t *astate;                  // per stream: has [MT], then tmpl [128][MT] (bin-major: the lanes of a wave read adjacent words)
+    int64_t astate_words;
+    int32_t *osim, *ohow;
+};
+template <bool APPEAR>
+using TrackKernelArgs = std::conditional_t<APPEAR, TrackAppearArgs, TrackArgs>;
+constexpr int ABINS = MYDET_APPEAR_BINS;
 
 // LDS of the optimal assignment, dynamic: with the kernel's static arrays it is above the 64 KiB a kernel gets without the opt-in
 struct AssocLds {
@@ -120,9 +133,26 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
     return v;
 }
 
-template <int BW, bool ROT, int MODE>
-__global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
+// S(j, d) = sum over the bins of min(tmpl[b][j], 256 * desc[d][b]); tm = the track's column of the template, dr = the row
+__device__ __forceinline__ int appear_sim(const int32_t *tm, int MT, const uint16_t *dr) {
+    int s = 0;
+#pragma unroll 4                                                       // 32 template words in flight: the sum is latency-bound
+    for (int g = 0; g < ABINS / 8; ++g) {
+        const uint4 q = reinterpret_cast<const uint4 *>(dr)[g];
+        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            s += min(tm[(int64_t)(g * 8 + 2 * k) * MT], (int)((w[k] & 0xffffu) << 8));
+            s += min(tm[(int64_t)(g * 8 + 2 * k + 1) * MT], (int)((w[k] >> 16) << 8));
+        }
+    }
+    return s;
+}
+
+template <int BW, bool ROT, int MODE, bool APPEAR>
+__global__ __launch_bounds__(TMAX) void track_kernel(const TrackKernelArgs<APPEAR> a) {
     static_assert(!ROT || BW == 5, "the rotated IoU needs the angle column");
+    static_assert(!APPEAR || MODE != ASSOC_OPTIMAL, "the appearance runs with the greedy walk only");
     extern __shared__ __align__(16) unsigned char track_dyn[];     // AssocLds (ASSOC_OPTIMAL only)
     __shared__ float s_z[5][KMAX];                    // the frame's detections: cx, cy, w, h, angle (0 for BW = 4)
     __shared__ float s_g[ROT ? 7 : 5][KMAX];          // pair-test planes: x1, y1, x2, y2, area | the seven fields of rotiou::Box
@@ -164,6 +194,14 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
     }
     int64_t next_id = *reinterpret_cast<const int64_t *>(st);
     int nlive = st[2];
+    // the appearance state: `has` lives in a register, the template column stays in memory (only this thread touches it)
+    [[maybe_unused]] int has = 0;
+    [[maybe_unused]] int32_t *tm = nullptr;
+    if constexpr (APPEAR) {
+        int32_t *as = a.astate + (int64_t)s * a.astate_words;
+        tm = as + MT + tid;
+        if (slot_ok) has = as[tid];
+    }
     const float one_minus_m = 1.0f - P.momentum;
 
     for (int f = 0; f < a.F; ++f) {
@@ -176,6 +214,8 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
                 ob[0] = 0.0f; ob[1] = 0.0f; ob[2] = 0.0f; ob[3] = 0.0f; ob[4] = 0.0f;
                 a.oscore[o * MT + tid] = 0.0f; a.ocls[o * MT + tid] = 0; a.oid[o * MT + tid] = 0; a.omissed[o * MT + tid] = -1;
             }
+            if constexpr (APPEAR)
+                if (slot_ok) { a.osim[o * MT + tid] = -1; a.ohow[o * MT + tid] = -1; }
             if (tid == 0) { a.ocount[o] = MYDET_COUNT_BAD_CLASS; a.odropped[o] = 0; }
             continue;
         }
@@ -251,6 +291,9 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
 
         // 3. association
         int md = -1;                                               // the record slot this track took
+        [[maybe_unused]] int how = 0, simv = -1;                   // APPEAR: the stage that matched, S of the matched pair
+        [[maybe_unused]] const uint16_t *dframe = nullptr;
+        if constexpr (APPEAR) dframe = a.desc + o * ((int64_t)KMAX * ABINS);
         if constexpr (MODE == ASSOC_OPTIMAL) {
             // Wavefront 0 solves, the others wait at the barrier below; every branch around a barrier is workgroup-uniform
             // (any_live, a.as.bands), and inside the wavefront the solver orders its LDS traffic with HungWaveSync.  No row
@@ -330,8 +373,15 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
                         const float inter = ww * hh;
                         iou = inter / (s_g[4][d] + t4 - inter);
                     }
-                    if (iou > thres)                               // a NaN (0/0) never matches
-                        key = ((unsigned long long)__float_as_uint(fmaxf(iou, 0.0f)) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)tid);
+                    if constexpr (APPEAR) {                        // the gate: S only for a pair that passed the IoU test
+                        bool pass = iou > thres;
+                        if (pass && a.ap.gate > 0 && has) pass = appear_sim(tm, MT, dframe + (int64_t)d * ABINS) >= a.ap.gate;
+                        if (pass)
+                            key = ((unsigned long long)__float_as_uint(fmaxf(iou, 0.0f)) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)tid);
+                    } else {
+                        if (iou > thres)                           // a NaN (0/0) never matches
+                            key = ((unsigned long long)__float_as_uint(fmaxf(iou, 0.0f)) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)tid);
+                    }
                 }
                 key = wave_max(key);
                 if (lane == 0) s_red[p & 1][wave] = key;
@@ -341,9 +391,64 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
                 const int win = best ? (int)(0xFFFFFFFFu - (unsigned)best) : -1;
                 if (win == tid) md = d;
                 if (tid == 0) s_dmatch[p] = win;
+                if constexpr (APPEAR) {
+                    if (win == tid) {
+                        how = 1;
+                        if constexpr (MODE == ASSOC_GREEDY_BANDS)
+                            if (!(s_sc[d] >= a.as.high_thres)) how = 2;
+                    }
+                }
             }
         } else {
             for (int p = tid; p < n; p += nthr) s_dmatch[p] = -1;
+        }
+
+        // 3b. re-identification: a detection that would be born is offered to the lost tracks of its class within reach, the
+        // largest S wins (the lowest slot on a tie).  One barrier per candidate; skipped uniformly without one or without a track.
+        if constexpr (APPEAR) {
+            if (a.ap.reid > 0) {
+                __syncthreads();                                   // s_dmatch is complete
+                for (int p0 = 0; p0 < n64; p0 += nthr) {
+                    const int p = p0 + tid;
+                    bool flag = p < n && s_dmatch[p] < 0 && s_sc[s_order[p]] >= P.new_thres;
+                    if constexpr (MODE != ASSOC_GREEDY) flag = flag && s_sc[s_order[p]] >= a.as.high_thres;
+                    const unsigned long long bits = __ballot(flag);
+                    if (lane == 0 && p < KMAX) s_bmask[p >> 6] = bits;
+                }
+                const bool elig = live && md < 0 && has && missed >= 2;
+                const int any_elig = __syncthreads_or(elig ? 1 : 0);          // also: s_bmask is complete
+                int ncand = 0;
+#pragma unroll
+                for (int w = 0; w < KMAX / 64; ++w) ncand += __popcll(s_bmask[w]);
+                if (any_elig && ncand) {
+                    int rc = 0;
+                    for (int p = 0; p < n; ++p) {
+                        if (!((s_bmask[p >> 6] >> (p & 63)) & 1ull)) continue;
+                        const int d = s_order[p];
+                        unsigned long long key = 0ull;
+                        if (live && md < 0 && has && missed >= 2 && cls == s_cl[d]) {
+                            const float zw = s_z[2][d], zh = s_z[3][d];
+                            const float m = fmaxf(fmaxf(x[2], x[3]), fmaxf(zw, zh));
+                            const float lim = a.ap.reach * m;
+                            if (fabsf(s_z[0][d] - x[0]) <= lim && fabsf(s_z[1][d] - x[1]) <= lim) {
+                                const int sv = appear_sim(tm, MT, dframe + (int64_t)d * ABINS);
+                                if (sv >= a.ap.reid) key = ((unsigned long long)(unsigned)sv << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)tid);
+                            }
+                        }
+                        key = wave_max(key);
+                        if (lane == 0) s_red[rc & 1][wave] = key;
+                        __syncthreads();
+                        unsigned long long best = 0ull;
+                        for (int w = 0; w < nwave; ++w) { const unsigned long long k = s_red[rc & 1][w]; best = k > best ? k : best; }
+                        const int win = best ? (int)(0xFFFFFFFFu - (unsigned)best) : -1;
+                        if (win == tid) { md = d; how = 3; }
+                        if (tid == 0) s_dmatch[p] = win;
+                        ++rc;
+                    }
+                }
+            }
+            // S of the matched pair, before the template moves (0 for a track without an appearance: its template is zero)
+            if (md >= 0) simv = appear_sim(tm, MT, dframe + (int64_t)md * ABINS);
         }
 
         // 4. update the matched tracks (KFTracklet.update)
@@ -373,6 +478,16 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
                 pvv[i] = pvv[i] - kv * oxv;
             }
             x[4] = mod180(x[4]);
+            if constexpr (APPEAR) {                                // the template follows a detection that could have been born
+                if (s_sc[md] >= a.ap.update_thres) {
+                    const uint16_t *dr = dframe + (int64_t)md * ABINS;
+                    for (int b = 0; b < ABINS; ++b) {
+                        const int dv = (int)dr[b] << 8, t = tm[(int64_t)b * MT];
+                        tm[(int64_t)b * MT] = has ? t + (((dv - t) * a.ap.alpha) >> 8) : dv;
+                    }
+                    has = 1;
+                }
+            }
             score = P.momentum * score + one_minus_m * s_sc[md];
             missed = 0;
         }
@@ -386,6 +501,10 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
 #pragma unroll
                 for (int i = 0; i < 5; ++i) { x[i] = v[i] = pxx[i] = pxv[i] = pvv[i] = 0.0f; }
                 score = 0.0f; missed = 0; cls = 0; id = 0;
+                if constexpr (APPEAR) {
+                    for (int b = 0; b < ABINS; ++b) tm[(int64_t)b * MT] = 0;
+                    has = 0;
+                }
             }
         }
         __syncthreads();                                           // s_dmatch is complete
@@ -430,6 +549,11 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
                 }
                 score = s_sc[d]; missed = 0; cls = s_cl[d]; id = next_id + fr;
                 live = true;
+                if constexpr (APPEAR) {
+                    const uint16_t *dr = dframe + (int64_t)d * ABINS;
+                    for (int b = 0; b < ABINS; ++b) tm[(int64_t)b * MT] = (int)dr[b] << 8;
+                    has = 1; how = 4; simv = -1;
+                }
             }
         }
         next_id += born;
@@ -441,6 +565,7 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
             ob[0] = x[0]; ob[1] = x[1]; ob[2] = x[2]; ob[3] = x[3]; ob[4] = x[4];
             a.oscore[o * MT + tid] = score; a.ocls[o * MT + tid] = cls; a.oid[o * MT + tid] = id;
             a.omissed[o * MT + tid] = live ? missed : -1;
+            if constexpr (APPEAR) { a.osim[o * MT + tid] = live ? simv : -1; a.ohow[o * MT + tid] = live ? how : -1; }
         }
         if (tid == 0) { a.ocount[o] = nlive; a.odropped[o] = nbirth - born; }
     }
@@ -453,17 +578,25 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackArgs a) {
             g_pxx[i * MT + tid] = pxx[i]; g_pxv[i * MT + tid] = pxv[i]; g_pvv[i * MT + tid] = pvv[i];
         }
         g_score[tid] = score; g_missed[tid] = missed;
+        if constexpr (APPEAR) a.astate[(int64_t)s * a.astate_words + tid] = has;
     }
     if (tid == 0) { *reinterpret_cast<int64_t *>(st) = next_id; st[2] = nlive; }
 }
 
+#ifndef MYDET_TRACK_APPEAR
 __global__ __launch_bounds__(256) void track_reset_kernel(int32_t *state, int64_t words) {
     int32_t *st = state + (int64_t)blockIdx.x * words;
     for (int64_t i = threadIdx.x; i < words; i += 256) st[i] = i == 0 ? 1 : 0;      // next id 1, everything else 0
 }
+#endif
 
 }  // namespace
 
+// This file is two translation units (the Makefile builds track_appear.hip, which is this file under MYDET_TRACK_APPEAR): the
+// instances and entry points without an appearance here, the ones with it there.  One unit would do for the language, but
+// the compiler's inlining choices inside an instance depend on how many instances share its helpers, and the instances that
+// were here before the appearance must stay the code they were (profiles/appearance.md has both builds side by side).
+#ifndef MYDET_TRACK_APPEAR
 extern "C" int64_t mydet_track_state_words(int max_tracks) {
     if (max_tracks < 1 || max_tracks > MYDET_TRACK_MAX_TRACKS) return 0;
     return ((int64_t)MYDET_TRACK_STATE_HEADER + (int64_t)MYDET_TRACK_SLOT_WORDS * max_tracks + 3) / 4 * 4;
@@ -475,39 +608,38 @@ extern "C" int mydet_track_reset(int32_t *state, int S, int max_tracks, void *st
     hipLaunchKernelGGL(track_reset_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, state, mydet_track_state_words(max_tracks));
     return mydet_launch_status();
 }
+#endif
 
 namespace {
 
 inline bool track_finite(float v) { return v - v == 0.0f; }            // false for a NaN and for an infinity
 
 // One instance: the > 64 KiB LDS opt-in of the optimal assignment is per kernel and per device (common.h)
-template <int BW, bool ROT, int MODE>
-int track_launch(const TrackArgs &a, dim3 grid, dim3 block, hipStream_t stream) {
+template <int BW, bool ROT, int MODE, bool APPEAR>
+int track_launch(const TrackKernelArgs<APPEAR> &a, dim3 grid, dim3 block, hipStream_t stream) {
     size_t dyn = 0;
     if constexpr (MODE == ASSOC_OPTIMAL) {
         static unsigned long long opted = 0ull;                    // one bit per device ordinal
         dyn = sizeof(AssocLds);
-        const int st = mydet_lds_opt_in(opted, track_kernel<BW, ROT, MODE>, (int)sizeof(AssocLds) + ASSOC_STATIC_LDS);
+        const int st = mydet_lds_opt_in(opted, track_kernel<BW, ROT, MODE, APPEAR>, (int)sizeof(AssocLds) + ASSOC_STATIC_LDS);
         if (st) return st;
     }
-    hipLaunchKernelGGL((track_kernel<BW, ROT, MODE>), grid, block, dyn, stream, a);
+    hipLaunchKernelGGL((track_kernel<BW, ROT, MODE, APPEAR>), grid, block, dyn, stream, a);
     return mydet_launch_status();
 }
 
-template <int MODE>
-int track_launch_mode(const TrackArgs &a, int box_width, dim3 grid, dim3 block, hipStream_t stream) {
-    if (box_width == 4) return track_launch<4, false, MODE>(a, grid, block, stream);
-    if (a.p.match == MYDET_TRACK_MATCH_ROTATED) return track_launch<5, true, MODE>(a, grid, block, stream);
-    return track_launch<5, false, MODE>(a, grid, block, stream);
+template <int MODE, bool APPEAR = false>
+int track_launch_mode(const TrackKernelArgs<APPEAR> &a, int box_width, dim3 grid, dim3 block, hipStream_t stream) {
+    if (box_width == 4) return track_launch<4, false, MODE, APPEAR>(a, grid, block, stream);
+    if (a.p.match == MYDET_TRACK_MATCH_ROTATED) return track_launch<5, true, MODE, APPEAR>(a, grid, block, stream);
+    return track_launch<5, false, MODE, APPEAR>(a, grid, block, stream);
 }
 
-}  // namespace
-
-extern "C" int mydet_track_frames_motion_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
-                                             int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
-                                             float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
-                                             int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
-                                             void *stream) {
+// The argument rules every tracker entry point shares; fills `a`
+int track_setup(TrackArgs &a, const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F, int box_width,
+                const mydet_track_params *params, int max_tracks, int32_t *state, float *out_box, float *out_score, int64_t *out_class,
+                int64_t *out_id, int32_t *out_missed, int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc,
+                const int32_t *shift) {
     if (S <= 0 || F <= 0 || max_tracks < 1) return MYDET_E_BADARG;
     if (box_width != 4 && box_width != 5) return MYDET_E_BADARG;
     if (!records || !params || !state || !out_box || !out_score || !out_class || !out_id || !out_missed || !out_count || !out_dropped)
@@ -528,7 +660,6 @@ extern "C" int mydet_track_frames_motion_f32(const int32_t *records, int64_t str
         ((uintptr_t)out_missed & 3) || ((uintptr_t)out_count & 3) || ((uintptr_t)out_dropped & 3) || ((uintptr_t)shift & 3))
         return MYDET_E_BADARG;
     if (max_tracks > MYDET_TRACK_MAX_TRACKS) return MYDET_E_UNSUPP;
-    TrackArgs a;
     a.rec = records; a.stream_st = stream_stride_words; a.frame_st = frame_stride_words; a.F = F; a.MT = max_tracks;
     a.p = *params;
     a.state = state; a.state_words = mydet_track_state_words(max_tracks);
@@ -536,12 +667,59 @@ extern "C" int mydet_track_frames_motion_f32(const int32_t *records, int64_t str
     a.odropped = out_dropped;
     a.as = *assoc;
     a.shift = shift;
+    return 0;
+}
+
+}  // namespace
+
+#ifndef MYDET_TRACK_APPEAR
+extern "C" int mydet_track_frames_motion_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                             int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                             float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                             int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
+                                             void *stream) {
+    TrackArgs a;
+    const int code = track_setup(a, records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
+                                 out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift);
+    if (code) return code;
     const dim3 grid((unsigned)S), block((unsigned)((max_tracks + 63) / 64 * 64));
     if (assoc->assign == MYDET_TRACK_ASSIGN_OPTIMAL) return track_launch_mode<ASSOC_OPTIMAL>(a, box_width, grid, block, (hipStream_t)stream);
     if (assoc->bands) return track_launch_mode<ASSOC_GREEDY_BANDS>(a, box_width, grid, block, (hipStream_t)stream);
     return track_launch_mode<ASSOC_GREEDY>(a, box_width, grid, block, (hipStream_t)stream);
 }
 
+#else
+extern "C" int64_t mydet_track_appear_state_words(int max_tracks) {
+    if (max_tracks < 1 || max_tracks > MYDET_TRACK_MAX_TRACKS) return 0;
+    return ((int64_t)(1 + MYDET_APPEAR_BINS) * max_tracks + 3) / 4 * 4;
+}
+
+extern "C" int mydet_track_frames_appear_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                             int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                             float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                             int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
+                                             const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
+                                             int32_t *out_sim, int32_t *out_how, void *stream) {
+    TrackAppearArgs a;
+    const int code = track_setup(a, records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
+                                 out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift);
+    if (code) return code;
+    if (!appear || !desc || !appear_state || !out_sim || !out_how) return MYDET_E_BADARG;
+    if (((uintptr_t)desc & 15) || ((uintptr_t)appear_state & 15) || ((uintptr_t)out_sim & 3) || ((uintptr_t)out_how & 3)) return MYDET_E_BADARG;
+    if (appear->gate < 0 || appear->gate > MYDET_APPEAR_SIM_MAX || appear->reid < 0 || appear->reid > MYDET_APPEAR_SIM_MAX) return MYDET_E_BADARG;
+    if (appear->alpha < 1 || appear->alpha > 256) return MYDET_E_BADARG;
+    if (!track_finite(appear->reach) || appear->reach < 0.0f || appear->update_thres != appear->update_thres) return MYDET_E_BADARG;
+    if (assoc->assign != MYDET_TRACK_ASSIGN_GREEDY) return MYDET_E_UNSUPP;          // the solver forms its costs on the fly
+    a.ap = *appear; a.desc = desc; a.astate = appear_state; a.astate_words = mydet_track_appear_state_words(max_tracks);
+    a.osim = out_sim; a.ohow = out_how;
+    const dim3 grid((unsigned)S), block((unsigned)((max_tracks + 63) / 64 * 64));
+    if (assoc->bands) return track_launch_mode<ASSOC_GREEDY_BANDS, true>(a, box_width, grid, block, (hipStream_t)stream);
+    return track_launch_mode<ASSOC_GREEDY, true>(a, box_width, grid, block, (hipStream_t)stream);
+}
+
+#endif
+
+#ifndef MYDET_TRACK_APPEAR
 extern "C" int mydet_track_frames_assoc_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
                                             int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
                                             float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
@@ -558,3 +736,4 @@ extern "C" int mydet_track_frames_f32(const int32_t *records, int64_t stream_str
     return mydet_track_frames_assoc_f32(records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
                                         out_score, out_class, out_id, out_missed, out_count, out_dropped, &assoc, stream);
 }
+#endif

@@ -1713,7 +1713,7 @@ def track_state_views(state, max_tracks=None):
     return out
 
 
-def track_frames(records, tracker_state, params, frames_per_stream=None, max_tracks=None, out=None, assoc=None, shift=None):
+def track_frames(records, tracker_state, params, frames_per_stream=None, max_tracks=None, out=None, assoc=None, shift=None, appear=None):
     """Advance S streams by F frames each in ONE launch (include/mydet.h: mydet_track_frames_f32, where the rules are).
     records: the detection records in frame coordinates -- an int32 tensor [S*F, words] (frame f of stream s in row s*F + f) or
     [S, F, words] with any strides along S and F that are multiples of 4 words, or the record_views dict of a [S*F, words]
@@ -1725,7 +1725,11 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     greedy single-band association of mydet_track_frames_f32, or a track_assoc(...) (mydet_track_frames_assoc_f32).  shift:
     None, or the camera motion of the same frames -- motion_frames(...)['shift'], int32 [S,F,4] or [S*F,4] on the records'
     device: in a frame with valid == 1 every prediction moves by (dx, dy) before the association
-    (mydet_track_frames_motion_f32)."""
+    (mydet_track_frames_motion_f32).  appear: None, or (appear_set(...), desc, appear_state) -- the descriptors of the same
+    frames, uint16 [S*F,512,128] or [S,F,512,128] (appear_records, or any 128 bins that sum to at most 512 per row), and the
+    int32 [S, words] state of appear_state, updated in place: the gate, the re-identification and the templates of
+    mydet_track_frames_appear_f32 (greedy assignment only: a ValueError with assign 'optimal', before any launch).  The dict
+    then also holds sim and how, int32 [S,F,MT]."""
     if not isinstance(params, _lib.TrackParams):
         raise TypeError(f'track_frames: params is a _lib.TrackParams (ops.track_params), got {type(params).__name__}')
     if assoc is not None and not isinstance(assoc, _lib.TrackAssoc):
@@ -1743,6 +1747,11 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
         raise ValueError(f'track_frames: int32 records of {_lib.REC_WORDS} or {_lib.REC_ROT_WORDS} words expected, got '
                          f'{records.dtype} {tuple(records.shape)}')
     width = 4 if words == _lib.REC_WORDS else 5
+    if appear is not None:
+        if not isinstance(appear, (tuple, list)) or len(appear) != 3 or not isinstance(appear[0], _lib.TrackAppear):
+            raise TypeError('track_frames: appear is (ops.appear_set(...), desc, appear_state) or None')
+        if assoc is not None and assoc.assign != _lib.TRACK_ASSIGN_GREEDY:
+            raise ValueError("track_frames: the appearance runs with assign 'greedy' only (the optimal assignment forms its costs on the fly)")
     if params.match == _lib.TRACK_MATCH_ROTATED and width != 5:
         raise ValueError("track_frames: match 'rotated' needs 'cxcywhd' records (the rotated record with its angle plane)")
     if records.dim() == 2:
@@ -1763,6 +1772,15 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     shapes = {'box': ((S, F, mt, 5), torch.float32), 'score': ((S, F, mt), torch.float32), 'cls': ((S, F, mt), torch.int64),
               'id': ((S, F, mt), torch.int64), 'missed': ((S, F, mt), torch.int32), 'count': ((S, F), torch.int32),
               'dropped': ((S, F), torch.int32)}
+    if appear is not None:
+        shapes.update(sim=((S, F, mt), torch.int32), how=((S, F, mt), torch.int32))
+        aset, desc, astate = appear
+        if (not isinstance(desc, torch.Tensor) or desc.dtype != torch.uint16 or desc.numel() != S * F * _lib.REC_TOPK * _lib.APPEAR_BINS or
+                tuple(desc.shape[-2:]) != (_lib.REC_TOPK, _lib.APPEAR_BINS) or desc.device != dev or not desc.is_contiguous()):
+            raise ValueError(f'track_frames: desc must be a contiguous uint16 tensor [{S * F},{_lib.REC_TOPK},{_lib.APPEAR_BINS}] on {dev}')
+        _check_appear_state(astate, mt, 'track_frames')
+        if astate.shape[0] != S or astate.device != dev:
+            raise ValueError(f'track_frames: the appearance state must be [{S}, words] on {dev}')
     if out is None:
         out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
     for k, (shape, dt) in shapes.items():
@@ -1776,7 +1794,12 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     t0 = TIMER.start() if TIMER else None
     args = (_ptr(records), records.stride(0), records.stride(1), S, F, width, ctypes.byref(params), mt, _ptr(tracker_state), _ptr(out['box']),
             _ptr(out['score']), _ptr(out['cls']), _ptr(out['id']), _ptr(out['missed']), _ptr(out['count']), _ptr(out['dropped']))
-    if shift is not None:
+    if appear is not None:
+        name = 'mydet_track_frames_appear_f32'
+        code = _lib.lib().mydet_track_frames_appear_f32(*args, ctypes.byref(track_assoc() if assoc is None else assoc),
+                                                        None if shift is None else _ptr(shift), ctypes.byref(aset), _ptr(desc), _ptr(astate),
+                                                        _ptr(out['sim']), _ptr(out['how']), _stream())
+    elif shift is not None:
         name = 'mydet_track_frames_motion_f32'
         code = _lib.lib().mydet_track_frames_motion_f32(*args, ctypes.byref(track_assoc() if assoc is None else assoc), _ptr(shift), _stream())
     elif assoc is None:
@@ -3513,6 +3536,145 @@ def crop_records(source, rec, size, layout=None, max_per_frame=None, pad=1.0, fi
     dst = _crop_dst(what, dst, B, M, settings[0], settings[4], dev)
     _crop_launch(image, yuv, _list_of_records(what, records, False, None), settings, M, dst)
     return dst
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# Appearance (include/mydet.h: mydet_appear_boxes_rgb_u8 and mydet_track_frames_appear_f32 have the rules): a 128-bin colour
+# descriptor per box, and the settings and state of the tracker's gate, re-identification and templates.
+
+def _appear_level(what, name, v):
+    """A fraction of the largest similarity -> the integer scale of S: floor(v * 131072 + 0.5); None and 0 are 0 = off."""
+    if v is None:
+        return 0
+    v = float(v)
+    if not 0 <= v <= 1:                                                # false for a NaN
+        raise ValueError(f'{what}: {name} is None (off) or a fraction in [0, 1] of the largest similarity, got {v!r}')
+    return int(math.floor(v * _lib.APPEAR_SIM_MAX + 0.5))
+
+
+def appear_set(gate=0.3, reid=0.6, momentum=0.9, reach=2.0, update_thres=0.3):
+    """The appearance settings of mydet_track_frames_appear_f32 (a _lib.TrackAppear).  gate, reid: None or 0 (off), or a fraction
+    in (0, 1] of the largest similarity, converted to the integer scale of S by floor(v * 131072 + 0.5).  momentum in [0, 1): the
+    share of the old template a match keeps; alpha = floor((1 - momentum) * 256 + 0.5) must land in 1..256.  reach: finite, >= 0.
+    update_thres: the detection score from which a match moves the template (not NaN).  ValueError for anything out of range;
+    touches no device."""
+    what = 'appear_set'
+    a = _lib.TrackAppear()
+    a.gate, a.reid = _appear_level(what, 'gate', gate), _appear_level(what, 'reid', reid)
+    m = float(momentum)
+    alpha = int(math.floor((1.0 - m) * 256 + 0.5)) if 0 <= m <= 1 else 0
+    if not 1 <= alpha <= 256:
+        raise ValueError(f'{what}: momentum in [0, 1) with (1 - momentum) * 256 rounding to 1..256 expected, got {momentum!r}')
+    a.alpha = alpha
+    r, u = float(reach), float(update_thres)
+    if not (math.isfinite(r) and r >= 0 and math.isfinite(float(np.float32(r)))):
+        raise ValueError(f'{what}: reach is a finite number >= 0, got {reach!r}')
+    if math.isnan(u):
+        raise ValueError(f'{what}: update_thres is a number, got {update_thres!r}')
+    a.reach, a.update_thres = r, u
+    return a
+
+
+def appear_state_words(max_tracks):
+    """int32 words of one stream's appearance state (mydet_track_appear_state_words); host arithmetic only."""
+    track_state_words(max_tracks)                                      # the range check
+    return ((1 + _lib.APPEAR_BINS) * int(max_tracks) + 3) // 4 * 4
+
+
+def _check_appear_state(state, max_tracks, what):
+    words = appear_state_words(max_tracks)
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != words or not state.is_contiguous():
+        got = f'{state.dtype} {tuple(state.shape)}' if isinstance(state, torch.Tensor) else type(state).__name__
+        raise ValueError(f'{what}: a contiguous int32 appearance state [streams, {words}] for max_tracks = {max_tracks} expected, got {got}')
+    return words
+
+
+def appear_state(streams, max_tracks, device):
+    """A cleared appearance state: int32 zeros [streams, appear_state_words(max_tracks)] -- no slot has a template."""
+    words = appear_state_words(max_tracks)
+    streams = int(streams)
+    if streams < 1:
+        raise ValueError(f'appear_state: streams >= 1 expected, got {streams}')
+    return torch.zeros((streams, words), dtype=torch.int32, device=device)
+
+
+def appear_reset_(state, max_tracks):
+    """Clear an appearance state in place: every `has` flag and every template bin is 0 (the state's initial value)."""
+    _check_appear_state(state, max_tracks, 'appear_reset_')
+    return state.zero_()
+
+
+def appear_state_views(state, max_tracks):
+    """Field views of an appearance state int32 [S, words], nothing copied: has int32 [S,MT], tmpl int32 [S,128,MT] in units of
+    1/256 sample (bin-major).  Works on any device."""
+    _check_appear_state(state, max_tracks, 'appear_state_views')
+    mt = int(max_tracks)
+    return {'has': state[:, :mt], 'tmpl': state[:, mt:mt + _lib.APPEAR_BINS * mt].view(state.shape[0], _lib.APPEAR_BINS, mt)}
+
+
+def _appear_out(what, out, B, K, dev):
+    shape = (B, K, _lib.APPEAR_BINS)
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint16, device=dev)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.uint16:
+        raise TypeError(f'{what}: out is a uint16 tensor, got {out.dtype if isinstance(out, torch.Tensor) else type(out).__name__}')
+    if tuple(out.shape) != shape or out.device != dev:
+        raise ValueError(f'{what}: out of shape {shape} on {dev} expected, got {tuple(out.shape)} on {out.device}')
+    if K and (not out[0].is_contiguous() or out.stride(0) % 2 or out.stride(0) < K * _lib.APPEAR_BINS or out.data_ptr() % 4):
+        raise ValueError(f'{what}: out needs contiguous frames, an even frame stride and a 4-byte aligned base (strides {tuple(out.stride())})')
+    return out
+
+
+def _appear_launch(image, yuv, lst, desc):
+    _launch_on_image('appear_boxes', image, yuv, 'mydet_appear_boxes_rgb_u8', 'mydet_appear_boxes_yuv420', ctypes.byref(lst), desc.data_ptr(),
+                     desc.stride(0))
+
+
+def _appear_dense(what, image, yuv, B, boxes, counts, out):
+    boxes, counts, _ = _box_rows(what, B, boxes, counts, None, None, None)
+    if boxes.shape[1] > _lib.DRAW_MAX_BOXES:
+        raise ValueError(f'{what}: at most {_lib.DRAW_MAX_BOXES} rows per frame and launch, got {boxes.shape[1]}')
+    dev = _same_device(what, image, [boxes, counts])
+    K = boxes.shape[1]
+    desc = _appear_out(what, out, B, K, dev)
+    if K == 0:
+        return desc
+    boxes = boxes.contiguous()
+    counts = None if counts is None else counts.contiguous()
+    _appear_launch(image, yuv, _list_of_rows(boxes, 0, K, counts, {}), desc)
+    return desc
+
+
+def appear_boxes(frames, boxes, counts=None, out=None):
+    """The appearance descriptors of boxes: a 128-bin colour histogram of 32 x 16 nearest-pixel samples over the central 0.75 of
+    every box, in ONE launch (include/mydet.h: mydet_appear_boxes_rgb_u8, where the rule is).  frames: uint8 [B,H,W,3] or
+    [H,W,3], read in place through their strides when pixels are packed.  boxes: float32 [B,K,4|5] or [K,4|5], K <= 512, rows (cx,
+    cy, w, h[, degrees]) in frame pixels.  counts: int32 [B] (None: all K).  Returns uint16 [B,K,128]; every row is written, rows
+    at or beyond the count are zeros.  out: such a tensor to write into (contiguous frames, any even frame stride)."""
+    what = 'appear_boxes'
+    return _appear_dense(what, *_image(what, frames, None, None, None, False), boxes, counts, out)
+
+
+def appear_boxes_yuv420(planes, layout, boxes, counts=None, out=None, matrix='bt601', full_range=False):
+    """appear_boxes out of 4:2:0 frames (mydet_appear_boxes_yuv420): the bits of appear_boxes on yuv420_to_rgb(planes, layout,
+    matrix, full_range), which is never built.  Every layout, the 10-bit ones included."""
+    what = 'appear_boxes_yuv420'
+    return _appear_dense(what, *_image(what, planes, layout, matrix, full_range, False), boxes, counts, out)
+
+
+def appear_records(source, rec, layout=None, out=None, matrix='bt601', full_range=False):
+    """The descriptors of the detections of a record dict (ops.record_views; plain or rotated) in ONE launch that reads the
+    record's planes in place -- nothing is copied or synchronised.  source: uint8 RGB frames [B,H,W,3] (layout None) or the
+    planes of `layout`.  Returns uint16 [B,512,128], row = record slot: what track_frames takes as desc."""
+    what = 'appear_records'
+    records = _record_buffer(what, rec)
+    image, yuv, B = _image(what, source, layout, matrix, full_range, False)
+    if B != records.shape[0]:
+        raise ValueError(f'{what}: {B} frames and {records.shape[0]} records')
+    dev = _same_device(what, image, [records])
+    desc = _appear_out(what, out, B, _lib.REC_TOPK, dev)
+    _appear_launch(image, yuv, _list_of_records(what, records, False, None), desc)
+    return desc
 
 
 # --------------------------------------------------------------------------------------------------------------------------
