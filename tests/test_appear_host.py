@@ -1,10 +1,13 @@
 """CPU-only: the host side of the appearance -- properties of the restatement (tests/_appear_ref.py), the template arithmetic at
 its edges, the settled conditions on the cases of tests/_appear_cases.py that keep the comparison of tests/test_gpu_appear.py from
-being hollow, the C ABI (declared, exported, bound, constants, the ABI version unchanged, argument checks before any launch) and
+being hollow, the same for every case of tests/test_gpu_appear_branches.py (the outcome it is for occurs, the margins hold, and the
+restatement with that one rule altered gives other outputs), the C ABI (declared, exported, bound, constants, the ABI version unchanged, argument checks before any launch) and
 the argument rules of ops.appear_* and api.Appearance."""
 import ctypes
+import inspect
 import os
 import re
+import textwrap
 
 import numpy as np
 import pytest
@@ -136,6 +139,236 @@ def test_the_busy_scene_uses_every_rule():
     assert {-1, 0, 1, 2, 3, 4} <= hows, hows
     assert outs[3]['count'] == -1 and s.margins['iou_thres'] >= 0.02 and s.margins['band'] >= 1e-3 and s.margins['score'] >= 1e-3
     assert any(len(np.unique(a['tmpl'][:, 0])) > 3 for a in arrays)  # templates blend
+
+
+# ---- the cases of tests/test_gpu_appear_branches.py, on the restatement alone ----
+
+def _altered(old, new):
+    """_appear_ref.Stream with ONE rule altered: the text `old`, which must occur exactly once in step, replaced by `new`."""
+    src = textwrap.dedent(inspect.getsource(ref.Stream.step))
+    assert src.count(old) == 1, old
+    ns = {}
+    exec(compile(src.replace(old, new), '<altered step>', 'exec'), vars(ref), ns)
+    return type('Altered', (ref.Stream,), {'step': ns['step']})
+
+
+_M = 'm = max(x[2], x[3], boxes[d][2], boxes[d][3])'
+_CAND = 'if d in match.values() or stage[d] != 1 or not scores[d] >= new32:'
+ALTERED = {
+    'gate >': ('if s < self.gate:', 'if s <= self.gate:'),
+    'reid >': ('if s >= self.reid and', 'if s > self.reid and'),
+    'missed >= 1': ('t.missed < 2', 't.missed < 1'),
+    'reach <': ('<= lim and abs(boxes[d][1] - x[1]) <= lim', '< lim and abs(boxes[d][1] - x[1]) < lim'),
+    'm of the detection': (_M, 'm = max(boxes[d][2], boxes[d][3])'),
+    'm of the track': (_M, 'm = max(x[2], x[3])'),
+    'm without track_w': (_M, 'm = max(x[3], boxes[d][2], boxes[d][3])'),
+    'm without track_h': (_M, 'm = max(x[2], boxes[d][2], boxes[d][3])'),
+    'm without det_w': (_M, 'm = max(x[2], x[3], boxes[d][3])'),
+    'm without det_h': (_M, 'm = max(x[2], x[3], boxes[d][2])'),
+    'x alone': (' and abs(boxes[d][1] - x[1]) <= lim', ''),
+    'y alone': ('abs(boxes[d][0] - x[0]) <= lim and ', ''),
+    'any class': ('if k in match or t.cls != cats[d] or not self.has[k]', 'if k in match or not self.has[k]'),
+    'below new_thres': (_CAND, 'if d in match.values() or stage[d] != 1:'),
+    'low band': (_CAND, 'if d in match.values() or stage[d] == 0 or not scores[d] >= new32:'),
+}
+
+
+class _RoundingTake(ref.Stream):
+    """The template blend with a rounding shift in place of the floor."""
+
+    def _take(self, k, d):
+        if self.has[k]:
+            self.tmpl[:, k] = [int(t) + (((256 * int(v) - int(t)) * self.alpha + 128) >> 8) for t, v in zip(self.tmpl[:, k], d)]
+        else:
+            super()._take(k, d)
+
+
+def _summary(outs, arrays):
+    return [(o['how'], o['id'], o['sim'], o['dropped']) for o in outs], [a['tmpl'].tolist() for a in arrays]
+
+
+def _proves(c, what=None, **over):
+    """The case gives what it expects on the restatement, with the margins of the suite; with the rule `what` altered (or the
+    settings `over` replaced) the outputs differ."""
+    stream, outs, arrays = cases.restate(c)
+    for f, k, h in c['expect']:
+        assert outs[f]['how'][k] == h, (f, k, h, outs[f]['how'][k])
+    m = stream.margins
+    assert m['iou_thres'] >= 0.02 and m['iou_gap'] >= 0.02 and m['score'] >= 1e-3 and m['band'] >= 1e-3 and stream.ties == 0, m
+    if what is not None or over:
+        cls = None if what is None else what if isinstance(what, type) else _altered(*ALTERED[what])
+        _, o2, a2 = cases.restate(c, cls, **over)
+        assert _summary(o2, a2) != _summary(outs, arrays), (what, over)
+    return stream, outs, arrays
+
+
+def test_branch_cases_streams_and_odd_slot_counts():
+    from mydetection_amd import ops
+    assert ops.appear_state_words(65) == 8388 != 129 * 65 and all(ops.appear_state_words(mt) == 129 * mt for mt in (64, 100, 128, 512))
+    assert ops.appear_state_words(1) == 132 and ops.appear_state_words(63) == 8128 and ops.appear_state_words(130) == 16772
+    assert [mt % 64 for mt in (1, 63, 65, 100, 130)].count(0) == 0                  # none fills its last wave
+    for width, low, rot in ((4, False, False), (5, True, True)):
+        scenes = cases.stream_scenes(width, low=low, rot=rot)
+        assert len(scenes) == 3 and {len(fr) for fr, _ in scenes} == {11} and {ds.shape for _, ds in scenes} == {(11, 512, 128)}
+        hows = {}
+        for mt in (65, 1):
+            for s, (fr, ds) in enumerate(scenes):
+                stream, outs, _ = ref.run(fr, ds, width, cases.TRACK_HW, mt, params=dict(match='rotated' if rot else 'iou'),
+                                          appear=dict(gate=ref.level(0.3), reid=ref.level(0.5), alpha=ref.alpha_of(0.8), update_thres=0.5),
+                                          assoc=cases.BANDS if low else None)
+                m = stream.margins
+                assert m['iou_thres'] >= 0.02 and m['iou_gap'] >= 0.02 and m['score'] >= 1e-3 and m['band'] >= 1e-3, m
+                hows[mt, s] = {h for o in outs for h in o['how']}
+                if mt == 1:                                          # one slot: whoever else could be born is dropped
+                    two = [f for f, r in enumerate(fr) if r is not None and (r[1] >= 0.5).sum() >= 2]
+                    assert len(two) == (6, 0, 4)[s] and all(outs[f]['dropped'] >= 1 for f in two), (s, two)
+                    assert all(o['count'] in (-1, 0, 1) for o in outs)
+        assert hows[65, 0] >= {-1, 0, 1, 3, 4} and 3 in hows[65, 1] and hows[65, 2] >= {1, 4}, hows          # the three scenes differ
+
+
+def test_branch_case_many_detections():
+    for mt in (192, 64):
+        c = cases.many(mt)
+        stream, outs, arrays = _proves(c)
+        f = cases.MANY_FRAME
+        assert all(len(fr[1]) > 64 for fr in c['frames'])                             # n > nthr at MT = 64: the ballot loop goes round
+        if mt == 192:
+            assert outs[1]['id'][:150] == list(range(1, 151)) and outs[0]['how'][:150] == [4] * 150       # born into slots 0 .. 149 in order
+            assert [outs[f]['id'][k] for k in cases.MANY_LOST] == [k + 1 for k in cases.MANY_LOST]
+            assert [outs[f]['missed'][k] for k in cases.MANY_LOST] == [0, 0, 0] and [outs[f - 1]['missed'][k] for k in cases.MANY_LOST] == [2, 2, 2]
+            assert outs[f]['how'].count(3) == 3 and outs[f]['how'].count(4) == 3 and all(o['dropped'] == 0 for o in outs)
+            assert len({k // 64 for k in cases.MANY_LOST}) == 3                       # the winners' slots: three different waves
+            # the candidates of the re-identification (unmatched, above new_thres) by rank: three different words of the mask,
+            # the returning objects at or beyond rank 128
+            scores = c['frames'][f][1]
+            rank = {int(d): p for p, d in enumerate(np.lexsort((np.arange(len(scores)), -scores.astype(np.float64))))}
+            back = [rank[d] for d in range(146, 150)]
+            assert min(back) >= 128 and {rank[d] >> 6 for d in range(146, 152)} == {0, 1, 2}, rank
+            # the stranger: S below reid against its old track, which stays lost
+            assert ref.similarity(arrays[f - 1]['tmpl'][:, cases.MANY_STRANGER], c['descs'][f][149]) < c['appear']['reid']
+            assert outs[f]['missed'][cases.MANY_STRANGER] == 3
+        else:
+            assert all(o['dropped'] > 0 for o in outs) and outs[0]['how'] == [4] * 64 and outs[f]['how'].count(3) == 1
+            assert np.array_equal(arrays[0]['tmpl'].T, 256 * c['descs'][0][:64].astype(np.int32))   # the born slots' templates
+    _proves(cases.many(192), reid=0)                                  # without the re-identification the three are born anew
+
+
+def test_branch_cases_integer_levels_at_equality():
+    t = cases.threshold_cases()
+    assert ref.similarity(256 * cases.RED.astype(np.int64), cases.MIXED) == 65536
+    for name, c in t.items():
+        stream, outs, _ = _proves(c, 'gate >' if name.startswith('gate') else 'reid >') if name.endswith('65536') else _proves(c)
+        assert stream.margins['sim'] == 0.5, name                     # S - level + 0.5: S == level, or one below it
+        f = len(c['frames']) - 1
+        assert (outs[f]['sim'][0] == 65536) == name.endswith('65536'), name
+    # the low band: its own threshold and how = 2
+    assert t['gate_low_65536']['expect'][0] == (1, 0, 2) and t['gate_low_65536']['assoc']['low_match_thres'] == 0.3
+
+
+def test_branch_cases_gate_changes_the_outcome():
+    g = cases.gate_cases()
+    _, outs, _ = _proves(g['second_takes'], gate=0)
+    assert outs[3]['match'][:2] == [-1, 0] and cases.restate(g['second_takes'], gate=0)[1][3]['match'][:2] == [0, -1]
+    _, outs, _ = _proves(g['all_refuse'], gate=0)
+    assert outs[3]['id'][:3] == [1, 2, 3]
+    c = g['walk_refuses_reid_takes']
+    stream, outs, _ = _proves(c, reid=0)
+    assert c['appear']['reid'] <= 65536 < c['appear']['gate'] and outs[4]['sim'][0] == 65536 and outs[3]['missed'][0] == 2
+    assert cases.restate(c, gate=0)[1][4]['how'][0] == 1            # the IoU passes: without the gate the walk takes it
+
+
+def test_branch_cases_reid_guards():
+    g = cases.guard_cases()
+    _proves(g['base'], reid=0)
+    _proves(g['bands_base'], reid=0)
+    for name, what in (('gap_0', 'missed >= 1'), ('other_class', 'any class'), ('below_new_thres', 'below new_thres'), ('low_band', 'low band')):
+        stream, outs, _ = _proves(g[name], what)
+        assert 3 not in outs[-1]['how']
+        assert 3 in cases.restate(g[name], _altered(*ALTERED[what]))[1][-1]['how'], name
+    assert g['base']['frames'][2][1].size == 0 and len(g['gap_0']['frames']) == len(g['base']['frames']) - 1       # a gap of 1 frame, of 0
+
+
+def test_branch_cases_reach():
+    r = cases.reach_cases()
+    for name, c in r.items():
+        if name.endswith('_at'):
+            _proves(c, 'reach <')
+            _proves(r[name[:-3] + '_past'])
+    for arg in cases.REACH_SIZES:                                    # each argument of the max decides its case
+        _proves(r[arg + '_at'], 'm without ' + arg)
+        for other in cases.REACH_SIZES:
+            if other != arg:
+                assert cases.restate(r[arg + '_at'], _altered(*ALTERED['m without ' + other]))[1][4]['how'][0] == 3
+    _proves(r['track_w_at'], 'm of the detection')
+    _proves(r['det_w_at'], 'm of the track')
+    _proves(r['y_only_past'], 'x alone')
+    _proves(r['track_w_past'], 'y alone')
+    stream, outs, arrays = _proves(r['shift_at'])
+    assert arrays[3]['x'][:2, 0].tolist() == [200.0, 200.0]          # the prediction is exact, and moves by (7, -3)
+    c = dict(r['shift_at'], shifts=None)
+    assert cases.restate(c)[1][4]['how'][:2] == [0, 4]
+    assert cases.restate(dict(r['shift_past'], shifts=None))[1][4]['how'][:2] == [0, 4]
+    assert r['reach_0_at']['appear']['reach'] == 0.0 and r['reach_0_past']['frames'][4][0][0, 0] == np.nextafter(np.float32(200), np.float32(201))
+
+
+def test_branch_cases_templates_and_rebirth():
+    t = cases.template_cases()
+    _, _, a1 = _proves(t['alpha_1'], _RoundingTake)
+    _, _, a256 = _proves(t['alpha_256'], alpha=255)
+    assert cases.ONE[5] == 512 and cases.ONE.sum() == 512 and not cases.ZERO.any()
+    seq = cases.TEMPLATE_SEQ
+    for f in range(12):
+        assert np.array_equal(a256[f]['tmpl'][:, 0], 256 * seq[f].astype(np.int32))            # alpha 256: the descriptor itself
+    col = [a['tmpl'][:, 0].astype(np.int64) for a in a1]
+    assert col[0][5] == ref.SIM_MAX and col[1][5] == ref.SIM_MAX - 512 and col[2][5] == ref.SIM_MAX - 510
+    steps = np.array([b - a for a, b in zip(col, col[1:])])
+    want = np.array([256 * seq[f + 1].astype(np.int64) - col[f] for f in range(11)])
+    assert ((steps == -1) & (want > -256)).any()                      # falls by less than a unit's worth: the floor
+    assert ((steps == 0) & (want > 0)).any()
+    assert not ((steps > 0) & (want < 256)).any()                     # and never rises by it
+    _, outs, arrays = _proves(t['zero_refused'], gate=0)
+    assert arrays[1]['has'][:2].tolist() == [1, 1] and not arrays[1]['tmpl'][:, 1].any() and outs[1]['sim'][:2] == [-1, -1]
+    c = cases.retire_rebirth()
+    _, outs, arrays = _proves(c)
+    assert outs[1]['id'][0] == 2 and outs[1]['sim'][0] == -1 and outs[1]['count'] == 1 and outs[1]['missed'][0] == 0
+    assert np.array_equal(arrays[1]['tmpl'][:, 0], 256 * cases.BLUE.astype(np.int32)) and arrays[1]['has'][0] == 1
+    # the match did happen, and it is what retired the track: without the second detection the slot is empty after the frame
+    alone = dict(c, frames=[c['frames'][0], cases._fr([((650.0, 200.0, 40.0, 60.0, 0.0), 0.9, 0)], 4)])
+    _, o2, a2 = cases.restate(alone)
+    assert o2[1]['count'] == 0 and not a2[1]['tmpl'].any() and not a2[1]['has'].any()
+
+
+def test_branch_cases_descriptor_rows_are_settled():
+    """Every row the GPU test compares with == has u == 0, and the named rows are what their names say."""
+    frames = cases.frames()
+    names = [n for n, _ in cases.bound_rows()]
+    boxes = cases.bound_boxes()
+    desc, info = ref.descriptors(frames, boxes)
+    assert all(i is not None and i['u'] == 0 for row in info for i in row)
+    for k, name in enumerate(names):
+        for b, kk in ((0, k), (1, len(names) - 1 - k)):
+            d = desc[b, kk].astype(np.int64)
+            if name.startswith(('zero_size', 'at_')):
+                assert d.sum() == 512 and sorted(d[d > 0].tolist()) == [256, 256] and (d[:64] > 0).sum() == 1, name
+            elif name.startswith('past_'):
+                assert d.sum() == 0, name
+            else:
+                assert d.sum() == 256 and d[:64].sum() == (0 if name == 'half_-y' else 128), (name, d.sum())       # half the taps count
+    x, y = np.clip([cases.W, -1, 30, 30], 0, cases.W - 1), np.clip([20, 20, cases.H, -1], 0, cases.H - 1)
+    for k, (xx, yy) in enumerate(zip(x, y)):                         # the border pixel the clamp picks
+        px = frames[0, yy, xx].astype(np.int64)
+        assert desc[0, 2 + k, (px[0] >> 6) * 16 + (px[1] >> 6) * 4 + (px[2] >> 6)] == 256, names[2 + k]
+    assert float(np.float32(cases.up(cases.P29))) == cases.P29 + 64
+    for name, fr in cases.edge_frames().items():
+        _, info = ref.descriptors(fr, cases.edge_boxes())
+        assert all(i is not None and i['u'] == 0 for row in info for i in row), name
+        assert fr.shape[1:3] == {'h1': (1, cases.W), 'w1': (cases.H, 1), '1x1': (1, 1)}[name]
+    one, _ = ref.descriptors(cases.edge_frames()['1x1'], cases.edge_boxes())
+    assert all(np.array_equal(one[b, k], one[b, 0]) and one[b, k].sum() == 512 for b in range(2) for k in range(6))
+    for k in (1, 2, 3, 5, 7):
+        assert k % 4 and (k * 128 + 130) % 2 == 0
+        d, info = ref.descriptors(cases.frames(2, 48, 66), cases.ragged_boxes(k))
+        assert all(i['u'] == 0 for row in info for i in row) and (d.sum(axis=2) == 512).all()
 
 
 def _header():
