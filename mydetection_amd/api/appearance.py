@@ -5,9 +5,10 @@ track, gates its IoU matches by it and re-identifies lost tracks (mydet_track_fr
 no tracker loop and nothing like it; the step is the appearance branch of DeepSORT / BoT-SORT with a colour histogram in place
 of a ReID network: the package ships no weights."""
 from .. import ops
+from .bound import Bound
 
 
-class Appearance:
+class Appearance(Bound):
     """The appearance settings and the templates of every track slot of the tracker it is used with.
 
     gate: None (off) or a fraction in (0, 1] of the largest similarity -- an IoU match of a track that has a template is
@@ -23,13 +24,13 @@ class Appearance:
     final records), 'sim' and 'how' int32 [streams, F, max_tracks].
     reset() clears every template; Tracker.reset() does NOT touch this object, and need not: a slot's template is read only
     while its `has` flag is set, and a birth into a slot overwrites both."""
+    what = 'appearance'
 
     def __init__(self, gate=0.3, reid=0.6, momentum=0.9, reach=2.0, update_thres=None):
+        super().__init__()
         ops.appear_set(gate, reid, momentum, reach, 0.0 if update_thres is None else update_thres)     # the range checks, before any device
         self.gate, self.reid, self.momentum, self.reach = gate, reid, float(momentum), float(reach)
         self.update_thres = None if update_thres is None else float(update_thres)
-        self.state = self.last = None
-        self.streams = self.max_tracks = self.img_hw = None
 
     def __repr__(self):
         return (f'Appearance(gate={self.gate}, reid={self.reid}, momentum={self.momentum}, reach={self.reach}, '
@@ -39,31 +40,29 @@ class Appearance:
         """The kernel's settings struct for a call whose tracker starts tracks at `birth_thres`."""
         return ops.appear_set(self.gate, self.reid, self.momentum, self.reach, birth_thres if self.update_thres is None else self.update_thres)
 
+    @staticmethod
+    def check_tracker(tracker):
+        """The greedy rule: the optimal assignment forms its costs on the fly and has no place for the gate."""
+        if tracker.assign != 'greedy':
+            raise ValueError(f"appearance: runs with a Tracker of assign='greedy' only, got assign={tracker.assign!r}")
+
     def check_call(self, tracker, img_hw):
         """The argument rules of a call that need no device: a greedy tracker, and the tracker's streams and max_tracks and the
         frame size are those of the first call."""
-        if tracker.assign != 'greedy':
-            raise ValueError(f"appearance: runs with a Tracker of assign='greedy' only, got assign={tracker.assign!r}")
-        hw = (int(img_hw[0]), int(img_hw[1]))
-        if self.img_hw is not None and (tracker.streams, tracker.max_tracks, hw) != (self.streams, self.max_tracks, self.img_hw):
-            raise ValueError(f'appearance: bound to {self.streams} streams of {self.max_tracks} tracks on {self.img_hw[0]}x{self.img_hw[1]} frames '
-                             f'by its first call, got {tracker.streams} streams of {tracker.max_tracks} tracks on {hw[0]}x{hw[1]} frames')
+        self.check_tracker(tracker)
+        self._key(tracker, img_hw)
 
-    def bind(self, tracker, img_hw, device):
-        """First call: take the tracker's streams and max_tracks and the frame size, allocate the state on the device."""
-        if self.state is None:
-            self.streams, self.max_tracks, self.img_hw = tracker.streams, tracker.max_tracks, (int(img_hw[0]), int(img_hw[1]))
-            self.state = ops.appear_state(self.streams, self.max_tracks, device)
-        elif self.state.device != device:
-            raise ValueError(f'appearance: its state lives on {self.state.device}, this call runs on {device}')
-        return self.state
+    def _allocate(self, device):
+        self.state = ops.appear_state(self.streams, self.max_tracks, device)
+
+    def _reset_state(self):
+        ops.appear_reset_(self.state, self.max_tracks)
 
     def run(self, image, yuv, rec, tracker, img_hw, birth_thres):
         """The descriptor launch on the frames of a call (image, yuv: what a frame source's image() returns) and its final
         records; no host synchronisation.  Returns what ops.track_frames takes as appear= and keeps the descriptors in `last`."""
         self.check_call(tracker, img_hw)
-        first = image if not isinstance(image, (tuple, list)) else image[0]
-        state = self.bind(tracker, img_hw, first.device)
+        state = self.bind(tracker, img_hw, self._image_device(image))
         desc = ops.appear_records(image, rec, **yuv)
         self.last = {'desc': desc}
         return self.set(birth_thres), desc, state
@@ -71,9 +70,3 @@ class Appearance:
     def took(self, track_out):
         """Keep the tracker launch's sim and how beside the descriptors."""
         self.last.update(sim=track_out['sim'], how=track_out['how'])
-
-    def reset(self):
-        """Clear every template.  The binding stays; the tracker is not touched."""
-        if self.state is not None:
-            ops.appear_reset_(self.state, self.max_tracks)
-        self.last = None

@@ -16,6 +16,10 @@ from ..ops import Nms
 from ..models.general import name_to_model
 from ..utils import image_ops as imgUtils
 from ..utils.structures import ImageObjects
+from .appearance import Appearance
+from .motion import CameraMotion
+from .overlay import Overlay
+from .zones import Zones
 
 
 class Tiles:
@@ -783,21 +787,17 @@ class Detector():
         tracker, coasting = self._pop_tracker(kwargs)
         zones = self._pop_zones(kwargs, tracker)
         overlay = self._pop_overlay(kwargs, tracker, zones, draw)
-        motion = self._pop_motion(kwargs, tracker)
+        motion = self._pop_companion(kwargs, 'motion', tracker)
         appearance = self._pop_appearance(kwargs, tracker)
         sources = make_sources()
         used = draw is not None or chips is not None or redact is not None
         if tracker is not None:
             src = self._one_source(sources, 'tracked')
             tracker.check_call(src.n, src.hw, self.model.bb_format)
-            if zones is not None:
-                zones.check_call(tracker, src.hw, self.model.bb_format)
-            if overlay is not None:
-                overlay.check_call(tracker, zones, src.hw)
-            if motion is not None:
-                motion.check_call(tracker, src.hw)
-            if appearance is not None:
-                appearance.check_call(tracker, src.hw)
+            for companion, args in ((zones, (src.hw, self.model.bb_format)), (overlay, (zones, src.hw)), (motion, (src.hw,)),
+                                    (appearance, (src.hw,))):
+                if companion is not None:
+                    companion.check_call(tracker, *args)
         elif used:
             src, = sources                                           # a plain call alone takes any number of sizes, none included
         call = self._call_settings(kwargs, whole=tracker is not None or used)
@@ -878,59 +878,46 @@ class Detector():
             raise TypeError(f'tracker: a mydetection_amd.api.Tracker (or None) expected, got {type(tracker).__name__}')
         return tracker, coasting
 
-    @staticmethod
-    def _pop_zones(kwargs, tracker):
-        """zones out of a frame method's keyword arguments: a TypeError for anything but a Zones, a ValueError without a
-        tracker (the zones count tracks), both before any launch."""
-        from .zones import Zones
-        zones = kwargs.pop('zones', None)
-        if zones is not None and not isinstance(zones, Zones):
-            raise TypeError(f'zones: a mydetection_amd.api.Zones (or None) expected, got {type(zones).__name__}')
-        if zones is not None and tracker is None:
-            raise ValueError('zones: zones= counts tracks and needs tracker= in the same call')
-        return zones
+    # the objects that sit behind the tracker in a tracked call: keyword -> (class, why it needs a tracker; None for the overlay,
+    # whose check_call has that rule, behind the TypeError of a method that does not draw)
+    _COMPANIONS = {'zones': (Zones, 'zones= counts tracks'),
+                   'overlay': (Overlay, None),
+                   'motion': (CameraMotion, 'motion= moves the predictions of a tracker'),
+                   'appearance': (Appearance, 'appearance= gates and re-identifies the tracks of a tracker')}
 
     @staticmethod
-    def _pop_motion(kwargs, tracker):
-        """motion out of a frame method's keyword arguments: a TypeError for anything but a CameraMotion, a ValueError without
-        a tracker (the shift moves the tracker's predictions), both before any launch."""
-        from .motion import CameraMotion
-        motion = kwargs.pop('motion', None)
-        if motion is not None and not isinstance(motion, CameraMotion):
-            raise TypeError(f'motion: a mydetection_amd.api.CameraMotion (or None) expected, got {type(motion).__name__}')
-        if motion is not None and tracker is None:
-            raise ValueError('motion: motion= moves the predictions of a tracker and needs tracker= in the same call')
-        return motion
+    def _pop_companion(kwargs, key, tracker):
+        """The `key` entry out of a frame method's keyword arguments: a TypeError for anything but None or an object of its
+        class, a ValueError without a tracker, both before any launch."""
+        cls, why = Detector._COMPANIONS[key]
+        obj = kwargs.pop(key, None)
+        if obj is not None and not isinstance(obj, cls):
+            raise TypeError(f'{key}: a mydetection_amd.api.{cls.__name__} (or None) expected, got {type(obj).__name__}')
+        if obj is not None and tracker is None and why:
+            raise ValueError(f'{key}: {why} and needs tracker= in the same call')
+        return obj
+
+    @staticmethod
+    def _pop_zones(kwargs, tracker):
+        """zones out of a frame method's keyword arguments, by _pop_companion's rules."""
+        return Detector._pop_companion(kwargs, 'zones', tracker)
 
     @staticmethod
     def _pop_appearance(kwargs, tracker):
-        """appearance out of a frame method's keyword arguments: a TypeError for anything but an Appearance, a ValueError without
-        a tracker (the templates belong to its tracks) or with one whose assignment is 'optimal', all before any launch."""
-        from .appearance import Appearance
-        appearance = kwargs.pop('appearance', None)
-        if appearance is not None and not isinstance(appearance, Appearance):
-            raise TypeError(f'appearance: a mydetection_amd.api.Appearance (or None) expected, got {type(appearance).__name__}')
-        if appearance is not None and tracker is None:
-            raise ValueError('appearance: appearance= gates and re-identifies the tracks of a tracker and needs tracker= in the same call')
-        if appearance is not None and tracker.assign != 'greedy':
-            raise ValueError(f"appearance: runs with a Tracker of assign='greedy' only, got assign={tracker.assign!r}")
+        """As _pop_companion, and a ValueError with a tracker whose assignment is 'optimal'."""
+        appearance = Detector._pop_companion(kwargs, 'appearance', tracker)
+        if appearance is not None:
+            appearance.check_tracker(tracker)
         return appearance
 
     @staticmethod
     def _pop_overlay(kwargs, tracker, zones, draw):
-        """overlay out of a frame method's keyword arguments: a TypeError for anything but an Overlay and in a method that does not
-        draw, a ValueError without a tracker or, for the zone parts, without zones=, all before any launch."""
-        from .overlay import Overlay
-        if 'overlay' not in kwargs:
-            return None
-        overlay = kwargs.pop('overlay')
-        if overlay is None:
-            return None
-        if not isinstance(overlay, Overlay):
-            raise TypeError(f'overlay: a mydetection_amd.api.Overlay (or None) expected, got {type(overlay).__name__}')
-        if draw is None:
-            raise TypeError('overlay: overlay= is an argument of annotate_frames and its YUV forms')
-        overlay.check_call(tracker, zones, (1, 1) if overlay.img_hw is None else overlay.img_hw)
+        """As _pop_companion, and a TypeError in a method that does not draw, a ValueError for the zone parts without zones=."""
+        overlay = Detector._pop_companion(kwargs, 'overlay', tracker)
+        if overlay is not None:
+            if draw is None:
+                raise TypeError('overlay: overlay= is an argument of annotate_frames and its YUV forms')
+            overlay.check_call(tracker, zones, (1, 1) if overlay.img_hw is None else overlay.img_hw)
         return overlay
 
     @staticmethod

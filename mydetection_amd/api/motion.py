@@ -4,9 +4,10 @@ handed to the tracker, whose predictions move with the camera before they are as
 The reference project has no tracker loop and nothing like it; the step is BoT-SORT's camera-motion compensation with a pure
 translation."""
 from .. import ops
+from .bound import Bound
 
 
-class CameraMotion:
+class CameraMotion(Bound):
     """The estimator's settings and its state for every stream of the tracker it is used with.
 
     reduce: None (by frame size) or 2, 4, 8 -- the luma is reduced by k x k box means before the coarse search; search: the
@@ -20,12 +21,12 @@ class CameraMotion:
     reset() forgets the last frame of every stream, so that the next frame reports (0, 0, 0, 0); Tracker.reset() does NOT
     touch this object, and reset() does not touch the tracker.
     Zones, trails and the heat map stay in frame pixels: they assume a fixed camera."""
+    what = 'motion'
 
     def __init__(self, reduce=None, search=8, min_texture=1024, min_blocks=None):
+        super().__init__()
         self.set = ops.motion_set(reduce, search, min_texture, min_blocks)       # the range checks, before any device is touched
         self.reduce, self.search, self.min_texture, self.min_blocks = reduce, int(search), int(min_texture), min_blocks
-        self.state = self.last = None
-        self.streams = self.img_hw = None
 
     def __repr__(self):
         return f'CameraMotion(reduce={self.reduce}, search={self.search}, min_texture={self.min_texture}, min_blocks={self.min_blocks})'
@@ -33,33 +34,23 @@ class CameraMotion:
     def check_call(self, tracker, img_hw):
         """The argument rules of a call that need no device: the frame is large enough for a block and its search window, and
         the tracker's streams and the frame size are those of the first call."""
-        hw = (int(img_hw[0]), int(img_hw[1]))
         if self.img_hw is None:
-            ops.motion_geometry(hw, self.set)                        # the frame-size rule
-        elif (tracker.streams, hw) != (self.streams, self.img_hw):
-            raise ValueError(f'motion: bound to {self.streams} streams of {self.img_hw[0]}x{self.img_hw[1]} frames by its first call, '
-                             f'got {tracker.streams} streams of {hw[0]}x{hw[1]} frames')
+            ops.motion_geometry((int(img_hw[0]), int(img_hw[1])), self.set)      # the frame-size rule
+        self._key(tracker, img_hw)
 
-    def bind(self, tracker, img_hw, device):
-        """First call: take the tracker's streams and the frame size, allocate the state on the device."""
-        if self.state is None:
-            self.streams, self.img_hw = tracker.streams, (int(img_hw[0]), int(img_hw[1]))
-            self.state = ops.motion_state(self.streams, self.img_hw, self.set, device)
-        elif self.state.device != device:
-            raise ValueError(f'motion: its state lives on {self.state.device}, this call runs on {device}')
-        return self.state
+    def _key(self, tracker, img_hw):
+        return self._check_bound(tracker.streams, None, img_hw)      # no track slots in this state: max_tracks is not bound
+
+    def _allocate(self, device):
+        self.state = ops.motion_state(self.streams, self.img_hw, self.set, device)
+
+    def _reset_state(self):
+        ops.motion_reset_(self.state, self.img_hw, self.set)
 
     def run(self, image, yuv, tracker, img_hw):
         """The estimator's launches on the frames of a call (image, yuv: what a frame source's image() returns); no host
         synchronisation.  Returns (and keeps in `last`) the dict of ops.motion_frames."""
         self.check_call(tracker, img_hw)
-        first = image if not isinstance(image, (tuple, list)) else image[0]
-        state = self.bind(tracker, img_hw, first.device)
+        state = self.bind(tracker, img_hw, self._image_device(image))
         self.last = ops.motion_frames(image, state, self.set, layout=yuv.get('layout') if yuv else None)
         return self.last
-
-    def reset(self):
-        """Forget the last frame of every stream.  The binding stays; the tracker is not touched."""
-        if self.state is not None:
-            ops.motion_reset_(self.state, self.img_hw, self.set)
-        self.last = None

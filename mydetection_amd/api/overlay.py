@@ -3,9 +3,10 @@ their running counters and the trails of the tracks, painted into the frames on 
 include/mydet.h: mydet_draw_overlay_rgb_u8 has the raster rules, mydet_trails_frames those of the trails).  The reference prints
 `Count: N` into its frame (utils/visualization.py: draw_bboxes_on_np); everything else here is this package's."""
 from .. import _lib, ops
+from .bound import Bound
 
 
-class Overlay:
+class Overlay(Bound):
     """What the counting overlay paints.  zones: the polygons of the call's Zones, filled (zone_alpha while nobody is inside,
     occupied_alpha otherwise; 0..255) and outlined; lines: its directed lines, each with a tick on its positive side;
     counters: the parts of a zone's label, any of 'occupancy' (`N`), 'entries' (`+E`), 'visits' (`-V`, the finished visits) -- a
@@ -15,10 +16,13 @@ class Overlay:
     frames of H rows, as Draw's; label_height: 8..64, None = as Draw's.
     Like Zones, the first call binds the object to the tracker's streams and max_tracks, the frame size and the device; it then
     holds the trail state (`state`, ops.trails_state_views names its fields; `last`: the output dict of the latest call,
-    ops.trails_frames).  A later call with another shape is a ValueError.  reset() forgets the trails."""
+    ops.trails_frames).  A later call with another shape is a ValueError.  reset() forgets the trails; the binding stays."""
+    what = 'overlay'
+    extra = ('_anchor', 'anchor')
 
     def __init__(self, zones=True, lines=True, counters=('occupancy', 'entries'), trails=0, zone_alpha=48, occupied_alpha=96,
                  thickness=None, trail_thickness=None, label_height=None, classes=None):
+        super().__init__()
         self.zones, self.lines = bool(zones), bool(lines)
         self.counters = (counters,) if isinstance(counters, str) else tuple(counters or ())
         ops.overlay_counter_flags(self.counters)
@@ -37,8 +41,6 @@ class Overlay:
         self.thickness, self.trail_thickness, self.label_height = thickness, trail_thickness, label_height
         self.classes = None if classes is None else tuple(int(c) for c in classes)
         ops.trail_set(2, 'center', self.classes)
-        self.state = self.last = None
-        self.streams = self.max_tracks = self.img_hw = None
         self._anchor = self._trail_set = self._track_out = None
         self._styles, self._geometry = {}, None
 
@@ -76,25 +78,24 @@ class Overlay:
                              '(trails alone: Overlay(zones=False, lines=False, trails=N))')
         if not (self.trails or (self.zones and zones.polygons) or (self.lines and zones.lines)):
             raise ValueError(f'overlay: nothing to paint: {self!r} with {zones!r}')
-        hw = (int(img_hw[0]), int(img_hw[1]))
-        anchor = 'center' if zones is None else zones.anchor
-        if self.img_hw is not None and (tracker.streams, tracker.max_tracks, hw, anchor) != (self.streams, self.max_tracks, self.img_hw, self._anchor):
-            raise ValueError(f'overlay: bound to {self.streams} streams of {self.max_tracks} tracks on {self.img_hw[0]}x{self.img_hw[1]} frames '
-                             f'(anchor {self._anchor!r}) by its first call, got {tracker.streams} streams of {tracker.max_tracks} tracks on '
-                             f'{hw[0]}x{hw[1]} frames (anchor {anchor!r})')
+        hw = self._call_key(tracker, zones, img_hw)[2]
         if max(hw) > _lib.ZONE_MAX_FRAME:
             raise ValueError(f'overlay: frames of at most {_lib.ZONE_MAX_FRAME} on a side, got {hw[0]}x{hw[1]}')
 
+    def _call_key(self, tracker, zones, img_hw):
+        return self._check_bound(tracker.streams, tracker.max_tracks, img_hw, 'center' if zones is None else zones.anchor)
+
+    def _allocate(self, device):
+        if self.trails:
+            self._trail_set = ops.trail_set(self.trails, self._anchor, self.classes)
+            self.state = ops.trails_state(self.streams, self.max_tracks, self.trails, device)
+
+    def _reset_state(self):
+        ops.trails_reset_(self.state, self.max_tracks, self.trails)
+
     def bind(self, tracker, zones, img_hw, device):
         """First call: take the tracker's shape, the frame size and the zones' anchor; allocate the trail state on the device."""
-        if self.img_hw is None:
-            self.streams, self.max_tracks, self.img_hw = tracker.streams, tracker.max_tracks, (int(img_hw[0]), int(img_hw[1]))
-            self._anchor = 'center' if zones is None else zones.anchor
-            if self.trails:
-                self._trail_set = ops.trail_set(self.trails, self._anchor, self.classes)
-                self.state = ops.trails_state(self.streams, self.max_tracks, self.trails, device)
-        elif self.state is not None and self.state.device != device:
-            raise ValueError(f'overlay: its state lives on {self.state.device}, this call runs on {device}')
+        self._bind_key(self._call_key(tracker, zones, img_hw), device)
 
     def run_trails(self, track_out, tracker, zones, img_hw):
         """The trails launch on a tracker launch's outputs (right behind it: no host synchronisation); keeps the result as `last`."""
@@ -122,9 +123,3 @@ class Overlay:
             ops.draw_overlay_yuv420(image, style=self.style(img_hw), **yuv, **kwargs)
         else:
             ops.draw_overlay(image, self.style(img_hw), **kwargs)
-
-    def reset(self):
-        """Forget every trail.  The binding stays."""
-        if self.state is not None:
-            ops.trails_reset_(self.state, self.max_tracks, self.trails)
-        self.last = None

@@ -3,9 +3,10 @@ frame and Kalman-filtered boxes, computed on the device from the call's own dete
 include/mydet.h: mydet_track_frames_f32 has the rules).  The state model is the reference's KFTracklet
 (utils/structures.py:445-529); the reference has no loop around it, the association is this package's."""
 from .. import ops
+from .bound import Bound
 
 
-class Tracker:
+class Tracker(Bound):
     """State and parameters of `streams` independent video streams, at most `max_tracks` (<= 512) live tracks each.
 
     match: the pair test of the association, 'iou' (axis-aligned, on cx, cy, w, h) or 'rotated' (the exact rotated IoU;
@@ -22,13 +23,15 @@ class Tracker:
     The first call binds the tracker to that call's frame size (H, W), box format and device; `state` is then the int32
     [streams, words] device buffer (ops.track_state_views names its fields) and reset() empties it (ids start at 1 again).
     A batch of B frames is `streams` runs of B / streams consecutive frames: frame f of stream s is frame s * (B / streams) + f."""
+    what = 'tracker'
+    extra = ('box_width', 'box width')
+    hint = ' (one frame size per tracker)'
 
     def __init__(self, streams=1, max_tracks=256, match=None, match_thres=0.3, new_thres=None, max_missed=30, momentum=0.8,
                  min_score=0.1, p0=ops.TRACK_P0, q=ops.TRACK_Q, r=ops.TRACK_R, assign='greedy', low_thres=None, high_thres=None,
                  low_match_thres=None):
-        self.streams, self.max_tracks = int(streams), int(max_tracks)
-        if self.streams < 1:
-            raise ValueError(f'Tracker: streams >= 1 expected, got {streams!r}')
+        super().__init__()
+        self.streams, self.max_tracks = ops.check_streams('Tracker', streams), int(max_tracks)
         ops.track_state_words(self.max_tracks)
         if match is not None:
             ops.track_match_id(match)
@@ -40,8 +43,6 @@ class Tracker:
         self.low_thres, self.high_thres, self.low_match_thres = (None if v is None else float(v) for v in (low_thres, high_thres, low_match_thres))
         self.params((1, 1), 'iou', 0.0)                              # the range checks, before any device is touched
         self.assoc(float('nan') if self.low_thres is None else self.low_thres + 1.0)       # a conf_thres above low_thres
-        self.state = None
-        self.img_hw = None
         self.box_width = None
 
     def __repr__(self):
@@ -74,28 +75,22 @@ class Tracker:
 
     def check_call(self, n_frames, img_hw, bb_format):
         """The argument rules of a tracked call that need no device: the batch is whole runs of every stream, and the frame
-        size and box format are those the tracker was bound to."""
+        size and box format are those of the first call."""
         self.resolve_match(bb_format)
         if n_frames < 1 or n_frames % self.streams:
             raise ValueError(f'tracker: a batch of {n_frames} frames is not a multiple of streams = {self.streams}')
-        width = 5 if bb_format == 'cxcywhd' else 4
-        if self.img_hw is not None and (tuple(img_hw) != self.img_hw or width != self.box_width):
-            raise ValueError(f'tracker: bound to {self.img_hw[0]}x{self.img_hw[1]} frames with {self.box_width}-wide boxes by its first call, '
-                             f'got {img_hw[0]}x{img_hw[1]} with {width}-wide boxes (one frame size per tracker)')
+        self._check_bound(self.streams, self.max_tracks, img_hw, 5 if bb_format == 'cxcywhd' else 4)
+
+    def _allocate(self, device):
+        self.state = ops.track_state(self.streams, self.max_tracks, device)
+
+    def _reset_state(self):
+        """reset(): forget every track; the next id of every stream is 1 again.  The frame size stays bound.  A CameraMotion used
+        with this tracker is not touched: it has its own reset().  Neither is an Appearance: a slot's template is read only while
+        its `has` flag is set, a reset tracker matches nothing (so no template moves), and a birth into a slot overwrites both;
+        call Appearance.reset() as well to clear them at once."""
+        ops.track_reset_(self.state, self.max_tracks)
 
     def bind(self, img_hw, box_width, device):
         """First call: take the frame size and allocate the state on the records' device."""
-        if self.state is None:
-            self.state = ops.track_state(self.streams, self.max_tracks, device)
-            self.img_hw, self.box_width = (int(img_hw[0]), int(img_hw[1])), int(box_width)
-        elif self.state.device != device:
-            raise ValueError(f'tracker: its state lives on {self.state.device}, this call runs on {device}')
-        return self.state
-
-    def reset(self):
-        """Forget every track; the next id of every stream is 1 again.  The frame size stays bound.  A CameraMotion used with
-        this tracker is not touched: it has its own reset().  Neither is an Appearance: a slot's template is read only while its
-        `has` flag is set, a reset tracker matches nothing (so no template moves), and a birth into a slot overwrites both; call
-        Appearance.reset() as well to clear them at once."""
-        if self.state is not None:
-            ops.track_reset_(self.state, self.max_tracks)
+        return self._bind_key(self._check_bound(self.streams, self.max_tracks, img_hw, int(box_width)), device)

@@ -3,9 +3,10 @@ through each directed line, and for how long they stayed, counted on the device 
 (ops.zones_frames; include/mydet.h: mydet_zones_frames has the rules).  The reference project counts the people of one frame
 (utils/visualization.py: draw_bboxes_on_np prints `Count: N`); the bookkeeping across frames is this package's."""
 from .. import _lib, ops
+from .bound import Bound
 
 
-class Zones:
+class Zones(Bound):
     """Polygons and directed lines in frame pixels, and the counters of every stream of the tracker they are used with.
 
     polygons: at most 16 sequences of 3 .. 16 points (x, y); lines: at most 16 pairs ((ax, ay), (bx, by)), A -> B: a crossing
@@ -20,9 +21,11 @@ class Zones:
     The first call binds the object to the tracker's streams and max_tracks, the frame size and the device; a later call with
     another is a ValueError.  `state` is then the int32 [streams, words] device buffer (ops.zones_state_views names its fields),
     `last` the output dict of the latest call on the device (ops.zones_frames), `heat` the heat map (None without heat=).
-    reset() zeroes the counters, the frame counter, the heat map and forgets who is inside."""
+    reset() zeroes the counters, the frame counter, the heat map and forgets who is inside; the binding stays."""
+    what = 'zones'
 
     def __init__(self, polygons=(), lines=(), anchor='center', classes=None, coasting=False, heat=None, names=None):
+        super().__init__()
         self.polygons = [[(float(x), float(y)) for x, y in poly] for poly in self._rows(polygons, 'polygons')]
         self.lines = [[(float(x), float(y)) for x, y in line] for line in self._rows(lines, 'lines')]
         self.anchor, self.coasting = anchor, bool(coasting)
@@ -36,9 +39,7 @@ class Zones:
         if len(names) != n:
             raise ValueError(f'Zones: names is one name per polygon followed by one per line ({n}), got {len(names)}')
         self.names = names
-        self.state = self.heat = self.last = None
-        self.streams = self.max_tracks = self.img_hw = None
-        self._set = None
+        self.heat = self._set = None
 
     @staticmethod
     def _rows(rows, what):
@@ -60,24 +61,20 @@ class Zones:
         frame size are those of the first call."""
         if self.anchor == 'bottom' and bb_format != 'cxcywh':
             raise ValueError(f"zones: anchor 'bottom' is for 'cxcywh' models; this one predicts {bb_format!r}")
-        hw = (int(img_hw[0]), int(img_hw[1]))
         if self.img_hw is None:
-            self.zone_set(hw)                                        # the frame-size rule
-        elif (tracker.streams, tracker.max_tracks, hw) != (self.streams, self.max_tracks, self.img_hw):
-            raise ValueError(f'zones: bound to {self.streams} streams of {self.max_tracks} tracks on {self.img_hw[0]}x{self.img_hw[1]} frames by '
-                             f'its first call, got {tracker.streams} streams of {tracker.max_tracks} tracks on {hw[0]}x{hw[1]} frames')
+            self.zone_set(img_hw)                                    # the frame-size rule
+        self._key(tracker, img_hw)
 
-    def bind(self, tracker, img_hw, device):
-        """First call: take the tracker's shape and the frame size, allocate the state (and the heat map) on the device."""
-        if self.state is None:
-            self._set = self.zone_set(img_hw)
-            self.streams, self.max_tracks, self.img_hw = tracker.streams, tracker.max_tracks, (int(img_hw[0]), int(img_hw[1]))
-            self.state = ops.zones_state(self.streams, self.max_tracks, device)
-            if self.heat_hw is not None:
-                self.heat = ops.zones_heat(self.streams, self._set, device)
-        elif self.state.device != device:
-            raise ValueError(f'zones: its state lives on {self.state.device}, this call runs on {device}')
-        return self.state
+    def _allocate(self, device):
+        self._set = self.zone_set(self.img_hw)
+        self.state = ops.zones_state(self.streams, self.max_tracks, device)
+        if self.heat_hw is not None:
+            self.heat = ops.zones_heat(self.streams, self._set, device)
+
+    def _reset_state(self):
+        ops.zones_reset_(self.state, self.max_tracks)
+        if self.heat is not None:
+            self.heat.zero_()
 
     def run(self, track_out, tracker, img_hw):
         """The zone launch on a tracker launch's outputs; no host synchronisation.  Returns (and keeps as `last`) the dict of
@@ -86,14 +83,6 @@ class Zones:
         state = self.bind(tracker, img_hw, track_out['box'].device)
         self.last = ops.zones_frames(track_out, state, self._set, heat=self.heat)
         return self.last
-
-    def reset(self):
-        """Zero every counter, the frame counter and the heat map, and forget who is inside.  The binding stays."""
-        if self.state is not None:
-            ops.zones_reset_(self.state, self.max_tracks)
-            if self.heat is not None:
-                self.heat.zero_()
-        self.last = None
 
     def counts(self):
         """The cumulative numbers, one host synchronisation (the state crosses once): a list with one dict per stream --

@@ -1585,6 +1585,83 @@ def fuse_view_records(rec, B, V, flips, frame_hw, thres, kind='nms', metric='iou
     return record_views(records)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# Per-stream state: the tracker and what sits behind it (zones, trails, camera motion, appearance) each keep an int32
+# [streams, words] buffer.  The rules of such a buffer are stated once here; a family is one record of what differs: the name
+# of its functions (`<name>_reset_`), the prefix of its messages, words(*args): the row length, what_for: the format of what that
+# length belongs to, reset: the C entry that fills the rows (None: zeros) and reset_args(*args): its arguments between the stream
+# count and the HIP stream, gpu: whether a host tensor is refused.
+_StateFamily = collections.namedtuple('_StateFamily', 'name prefix words what_for reset reset_args gpu')
+
+
+def check_streams(prefix, streams):
+    streams = int(streams)
+    if streams < 1:
+        raise ValueError(f'{prefix}: streams >= 1 expected, got {streams}')
+    return streams
+
+
+def _max_tracks(prefix, max_tracks):
+    max_tracks = int(max_tracks)
+    if not 1 <= max_tracks <= _lib.TRACK_MAX_TRACKS:
+        raise ValueError(f'{prefix}: 1 <= max_tracks <= {_lib.TRACK_MAX_TRACKS} expected, got {max_tracks}')
+    return max_tracks
+
+
+def _row_slots(state, header, slot_words):
+    """max_tracks by the row length of a slot family's state, for the views that take None; 1 for what is no state at all."""
+    if not isinstance(state, torch.Tensor) or state.dim() != 2:
+        return 1
+    return max((state.shape[1] - header) // slot_words, 1)
+
+
+def _state_check(fam, state, args, what, views=False):
+    """The state rule: a contiguous int32 [streams, fam.words(*args)] tensor, on a GPU unless the family or the caller
+    (views: the field views work on a host copy) says otherwise."""
+    words = fam.words(*args)
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != words or not state.is_contiguous():
+        got = f'{state.dtype} {tuple(state.shape)}' if isinstance(state, torch.Tensor) else type(state).__name__
+        raise ValueError(f'{what}: a contiguous int32 state [streams, {words} words] for {fam.what_for.format(*args)} expected, got {got}')
+    if fam.gpu and not views:
+        require_gpu(state, what)
+
+
+def _state_reset(fam, state, args):
+    _state_check(fam, state, args, f'{fam.name}_reset_')
+    if fam.reset is None:
+        return state.zero_()
+    code = getattr(_lib.lib(), fam.reset)(_ptr(state), state.shape[0], *fam.reset_args(*args), _stream())
+    _lib.check(code, fam.reset)
+    return state
+
+
+def _state_new(fam, streams, args, device):
+    """Allocate [streams, words] and reset it."""
+    words = fam.words(*args)                                         # the rules of `args` first, then that of `streams`
+    return _state_reset(fam, torch.empty((check_streams(fam.prefix, streams), words), dtype=torch.int32, device=device), args)
+
+
+def _check_planes(what, name, planes, shapes, dev):
+    """The check-only half of out_planes, for a dict that another call made (`name`: what the message calls it)."""
+    for k, (shape, dt) in shapes.items():
+        t = planes[k]
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f'{what}: {name}[{k!r}] must be a contiguous {dt} tensor {shape} on {dev}')
+    return planes
+
+
+def out_planes(what, out, shapes, dev):
+    """The output dict of a *_frames call.  shapes: name -> (shape, dtype).  out None: allocated on `dev`; else every named entry
+    of `out` must be a contiguous tensor of that shape and dtype on `dev` (a ValueError that names the entry), and `out` is returned."""
+    if out is None:
+        return {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+    return _check_planes(what, 'out', out, shapes, dev)
+
+
+def _ints(*args):
+    return tuple(int(a) for a in args)
+
+
 TRACK_MATCHES = {'iou': _lib.TRACK_MATCH_IOU, 'rotated': _lib.TRACK_MATCH_ROTATED}        # MYDET_TRACK_MATCH_* of include/mydet.h
 TRACK_ASSIGNS = {'greedy': _lib.TRACK_ASSIGN_GREEDY, 'optimal': _lib.TRACK_ASSIGN_OPTIMAL}   # MYDET_TRACK_ASSIGN_*
 # KFTracklet's constants (reference utils/structures.py:457-460): standard deviations; the kernel takes their squares
@@ -1602,10 +1679,10 @@ def track_match_id(match):
 
 def track_state_words(max_tracks):
     """int32 words of one stream's tracker state (include/mydet.h: mydet_track_state_words); host arithmetic only."""
-    max_tracks = int(max_tracks)
-    if not 1 <= max_tracks <= _lib.TRACK_MAX_TRACKS:
-        raise ValueError(f'tracker: 1 <= max_tracks <= {_lib.TRACK_MAX_TRACKS} expected, got {max_tracks}')
-    return (_lib.TRACK_STATE_HEADER + _lib.TRACK_SLOT_WORDS * max_tracks + 3) // 4 * 4
+    return (_lib.TRACK_STATE_HEADER + _lib.TRACK_SLOT_WORDS * _max_tracks('tracker', max_tracks) + 3) // 4 * 4
+
+
+_TRACK_STATE = _StateFamily('track', 'tracker', track_state_words, 'max_tracks = {}', 'mydet_track_reset', _ints, True)
 
 
 def track_variances(std, n, what):
@@ -1662,29 +1739,12 @@ def track_assoc(assign='greedy', low_thres=None, high_thres=None, low_match_thre
 
 def track_state(streams, max_tracks, device):
     """A reset tracker state: int32 [streams, track_state_words(max_tracks)] (include/mydet.h has the layout)."""
-    words = track_state_words(max_tracks)
-    streams = int(streams)
-    if streams < 1:
-        raise ValueError(f'tracker: streams >= 1 expected, got {streams}')
-    state = torch.empty((streams, words), dtype=torch.int32, device=device)
-    return track_reset_(state, max_tracks)
-
-
-def _check_track_state(state, max_tracks, what):
-    words = track_state_words(max_tracks)
-    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != words or not state.is_contiguous():
-        got = f'{state.dtype} {tuple(state.shape)}' if isinstance(state, torch.Tensor) else type(state).__name__
-        raise ValueError(f'{what}: a contiguous int32 state [streams, {words}] for max_tracks = {max_tracks} expected, got {got}')
-    require_gpu(state, what)
-    return words
+    return _state_new(_TRACK_STATE, streams, (max_tracks,), device)
 
 
 def track_reset_(state, max_tracks):
     """Reset a tracker state in place (mydet_track_reset): no tracks, the next id of every stream is 1."""
-    _check_track_state(state, max_tracks, 'track_reset_')
-    code = _lib.lib().mydet_track_reset(_ptr(state), state.shape[0], int(max_tracks), _stream())
-    _lib.check(code, 'mydet_track_reset')
-    return state
+    return _state_reset(_TRACK_STATE, state, (max_tracks,))
 
 
 def track_state_views(state, max_tracks=None):
@@ -1692,15 +1752,9 @@ def track_state_views(state, max_tracks=None):
     x, v, pxx, pxv, pvv float32 [S,5,MT] (rows cx, cy, w, h, angle), score float32 [S,MT], cls, id int64 [S,MT] (id 0 = a free
     slot), missed int32 [S,MT], next_id int64 [S], live int32 [S].  max_tracks: taken from the row length when None.  Works on
     any device (tests read a host copy)."""
-    if state.dtype != torch.int32 or state.dim() != 2 or not state.is_contiguous():
-        raise ValueError(f'track_state_views: a contiguous int32 state [streams, words] expected, got {state.dtype} {tuple(state.shape)}')
-    S, words = state.shape
-    if max_tracks is None:
-        max_tracks = (words - _lib.TRACK_STATE_HEADER) // _lib.TRACK_SLOT_WORDS
-    mt = int(max_tracks)
-    if words != track_state_words(mt):
-        raise ValueError(f'track_state_views: {words} words per stream is not the state of max_tracks = {mt}')
-    o = _lib.TRACK_STATE_HEADER
+    mt = _row_slots(state, _lib.TRACK_STATE_HEADER, _lib.TRACK_SLOT_WORDS) if max_tracks is None else int(max_tracks)
+    _state_check(_TRACK_STATE, state, (mt,), 'track_state_views', views=True)
+    S, o = state.shape[0], _lib.TRACK_STATE_HEADER
     out = {'next_id': state[:, 0:2].view(torch.int64)[:, 0], 'live': state[:, 2]}
     out['cls'] = state[:, o:o + 2 * mt].view(torch.int64)
     out['id'] = state[:, o + 2 * mt:o + 4 * mt].view(torch.int64)
@@ -1762,7 +1816,7 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     if records.dim() != 3 or records.shape[0] != S or records.shape[1] < 1:
         raise ValueError(f'track_frames: records of shape [S*F, {words}] or [{S}, F, {words}] expected, got {tuple(records.shape)}')
     F = records.shape[1]
-    _check_track_state(tracker_state, mt, 'track_frames')
+    _state_check(_TRACK_STATE, tracker_state, (mt,), 'track_frames')
     require_gpu(records, 'track_frames')
     if records.device != tracker_state.device:
         raise ValueError(f'track_frames: records on {records.device}, state on {tracker_state.device}')
@@ -1778,15 +1832,10 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
         if (not isinstance(desc, torch.Tensor) or desc.dtype != torch.uint16 or desc.numel() != S * F * _lib.REC_TOPK * _lib.APPEAR_BINS or
                 tuple(desc.shape[-2:]) != (_lib.REC_TOPK, _lib.APPEAR_BINS) or desc.device != dev or not desc.is_contiguous()):
             raise ValueError(f'track_frames: desc must be a contiguous uint16 tensor [{S * F},{_lib.REC_TOPK},{_lib.APPEAR_BINS}] on {dev}')
-        _check_appear_state(astate, mt, 'track_frames')
+        _state_check(_APPEAR_STATE, astate, (mt,), 'track_frames')
         if astate.shape[0] != S or astate.device != dev:
             raise ValueError(f'track_frames: the appearance state must be [{S}, words] on {dev}')
-    if out is None:
-        out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
-    for k, (shape, dt) in shapes.items():
-        t = out[k]
-        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            raise ValueError(f'track_frames: out[{k!r}] must be a contiguous {dt} tensor {shape} on {dev}')
+    out = out_planes('track_frames', out, shapes, dev)
     if shift is not None:
         if (not isinstance(shift, torch.Tensor) or shift.dtype != torch.int32 or shift.numel() != S * F * 4 or shift.shape[-1] != 4 or
                 shift.device != dev or not shift.is_contiguous()):
@@ -1838,6 +1887,35 @@ def _zone_points(what, pts, n_lo, n_hi):
     return zone_quantise(a)
 
 
+def _zone_anchor(what, anchor):
+    """The C selector of the tested point of a box, 'center' or 'bottom'."""
+    if not isinstance(anchor, str) or anchor not in ZONE_ANCHORS:
+        raise ValueError(f'{what}: anchor {anchor!r} is not one of {sorted(ZONE_ANCHORS)}')
+    return ZONE_ANCHORS[anchor]
+
+
+def _set_classes(what, struct, classes):
+    """classes (None, or 1 .. 16 class indices) into the n_classes and classes fields of a ZoneSet or TrailSet."""
+    if classes is None:
+        return
+    cl = [int(c) for c in classes]
+    if not 1 <= len(cl) <= _lib.ZONE_MAX_CLASSES or any(c < 0 or c >= 1 << 31 for c in cl):
+        raise ValueError(f'{what}: classes is None or 1 .. {_lib.ZONE_MAX_CLASSES} class indices, got {classes!r}')
+    struct.n_classes = len(cl)
+    struct.classes[:len(cl)] = cl
+
+
+def _frame_hw(what, hw):
+    """A frame size (H, W) as two integers of 1 .. ZONE_MAX_FRAME each."""
+    try:
+        h, w = (int(v) for v in hw)
+    except (TypeError, ValueError):
+        raise ValueError(f'{what}: a frame size (H, W) expected, got {hw!r}') from None
+    if not (1 <= h <= _lib.ZONE_MAX_FRAME and 1 <= w <= _lib.ZONE_MAX_FRAME):
+        raise ValueError(f'{what}: a frame size (H, W) of 1 .. {_lib.ZONE_MAX_FRAME} each expected, got {hw!r}')
+    return h, w
+
+
 def zone_set(img_hw, polygons=(), lines=(), anchor='center', classes=None, coasting=False, heat=None):
     """The parameter struct of mydet_zones_frames (a _lib.ZoneSet; include/mydet.h has the rules).  img_hw: the frame size
     (H, W), each 1 .. 32768.  polygons: at most 16 sequences of 3 .. 16 points (x, y) in frame pixels; lines: at most 16 pairs
@@ -1846,21 +1924,15 @@ def zone_set(img_hw, polygons=(), lines=(), anchor='center', classes=None, coast
     coasting: also observe live tracks without a detection in the frame, at their predicted boxes.  heat: None, or (gh, gw),
     each 1 .. 1024.  ValueError for anything out of range, a polygon of zero area or a line of zero length after quantisation,
     non-finite coordinates, or neither polygons nor lines; touches no device."""
-    if not isinstance(anchor, str) or anchor not in ZONE_ANCHORS:
-        raise ValueError(f'zone_set: anchor {anchor!r} is not one of {sorted(ZONE_ANCHORS)}')
-    try:
-        h, w = (int(v) for v in img_hw)
-    except (TypeError, ValueError):
-        raise ValueError(f'zone_set: a frame size (H, W) expected, got {img_hw!r}') from None
-    if not (1 <= h <= _lib.ZONE_MAX_FRAME and 1 <= w <= _lib.ZONE_MAX_FRAME):
-        raise ValueError(f'zone_set: a frame size (H, W) of 1 .. {_lib.ZONE_MAX_FRAME} each expected, got {img_hw!r}')
+    anchor = _zone_anchor('zone_set', anchor)
+    h, w = _frame_hw('zone_set', img_hw)
     polygons, lines = list(polygons), list(lines)
     if not polygons and not lines:
         raise ValueError('zone_set: neither polygons nor lines given')
     if len(polygons) > _lib.ZONES_MAX or len(lines) > _lib.ZONES_MAX:
         raise ValueError(f'zone_set: at most {_lib.ZONES_MAX} polygons and {_lib.ZONES_MAX} lines, got {len(polygons)} and {len(lines)}')
     z = _lib.ZoneSet()
-    z.n_polygons, z.n_lines, z.anchor, z.coasting, z.img_h, z.img_w = len(polygons), len(lines), ZONE_ANCHORS[anchor], int(bool(coasting)), h, w
+    z.n_polygons, z.n_lines, z.anchor, z.coasting, z.img_h, z.img_w = len(polygons), len(lines), anchor, int(bool(coasting)), h, w
     for p, poly in enumerate(polygons):
         q = _zone_points(f'polygon {p}', poly, 3, _lib.ZONE_MAX_VERTICES).astype(np.int64)
         nxt = np.roll(q, -1, axis=0)
@@ -1874,12 +1946,7 @@ def zone_set(img_hw, polygons=(), lines=(), anchor='center', classes=None, coast
         if np.array_equal(q[0], q[1]):
             raise ValueError(f'zone_set: line {l} has no length at 1/16 pixel: {line!r}')
         z.line[l][:] = q.reshape(-1).tolist()
-    if classes is not None:
-        cl = [int(c) for c in classes]
-        if not 1 <= len(cl) <= _lib.ZONE_MAX_CLASSES or any(c < 0 or c >= 1 << 31 for c in cl):
-            raise ValueError(f'zone_set: classes is None or 1 .. {_lib.ZONE_MAX_CLASSES} class indices, got {classes!r}')
-        z.n_classes = len(cl)
-        z.classes[:len(cl)] = cl
+    _set_classes('zone_set', z, classes)
     if heat is not None:
         try:
             gh, gw = (int(v) for v in heat)
@@ -1893,37 +1960,20 @@ def zone_set(img_hw, polygons=(), lines=(), anchor='center', classes=None, coast
 
 def zones_state_words(max_tracks):
     """int32 words of one stream's zone state (include/mydet.h: mydet_zones_state_words); host arithmetic only."""
-    max_tracks = int(max_tracks)
-    if not 1 <= max_tracks <= _lib.TRACK_MAX_TRACKS:
-        raise ValueError(f'zones: 1 <= max_tracks <= {_lib.TRACK_MAX_TRACKS} expected, got {max_tracks}')
-    return (_lib.ZONES_STATE_HEADER + _lib.ZONES_SLOT_WORDS * max_tracks + 3) // 4 * 4
+    return (_lib.ZONES_STATE_HEADER + _lib.ZONES_SLOT_WORDS * _max_tracks('zones', max_tracks) + 3) // 4 * 4
+
+
+_ZONES_STATE = _StateFamily('zones', 'zones', zones_state_words, 'max_tracks = {}', 'mydet_zones_reset', _ints, True)
 
 
 def zones_state(streams, max_tracks, device):
     """A reset zone state: int32 [streams, zones_state_words(max_tracks)] (include/mydet.h has the layout)."""
-    words = zones_state_words(max_tracks)
-    streams = int(streams)
-    if streams < 1:
-        raise ValueError(f'zones: streams >= 1 expected, got {streams}')
-    state = torch.empty((streams, words), dtype=torch.int32, device=device)
-    return zones_reset_(state, max_tracks)
-
-
-def _check_zones_state(state, max_tracks, what):
-    words = zones_state_words(max_tracks)
-    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != words or not state.is_contiguous():
-        got = f'{state.dtype} {tuple(state.shape)}' if isinstance(state, torch.Tensor) else type(state).__name__
-        raise ValueError(f'{what}: a contiguous int32 state [streams, {words}] for max_tracks = {max_tracks} expected, got {got}')
-    require_gpu(state, what)
-    return words
+    return _state_new(_ZONES_STATE, streams, (max_tracks,), device)
 
 
 def zones_reset_(state, max_tracks):
     """Reset a zone state in place (mydet_zones_reset): nobody inside, every counter and the frame counter 0."""
-    _check_zones_state(state, max_tracks, 'zones_reset_')
-    code = _lib.lib().mydet_zones_reset(_ptr(state), state.shape[0], int(max_tracks), _stream())
-    _lib.check(code, 'mydet_zones_reset')
-    return state
+    return _state_reset(_ZONES_STATE, state, (max_tracks,))
 
 
 def zones_heat(streams, zone_set, device):
@@ -1938,15 +1988,9 @@ def zones_state_views(state, max_tracks=None):
     [S], zone_counts int32 [S,16,4] (entries, exits, lost, visits), line_counts int32 [S,16,2] (pos, neg), dwell_max int32
     [S,16], dwell_sum int64 [S,16], id int64 [S,MT] (0 = an empty slot), inside, sides, px, py int32 [S,MT], entered int32
     [S,16,MT].  max_tracks: taken from the row length when None.  Works on any device (tests read a host copy)."""
-    if state.dtype != torch.int32 or state.dim() != 2 or not state.is_contiguous():
-        raise ValueError(f'zones_state_views: a contiguous int32 state [streams, words] expected, got {state.dtype} {tuple(state.shape)}')
-    S, words = state.shape
-    if max_tracks is None:
-        max_tracks = (words - _lib.ZONES_STATE_HEADER) // _lib.ZONES_SLOT_WORDS
-    mt = int(max_tracks)
-    if words != zones_state_words(mt):
-        raise ValueError(f'zones_state_views: {words} words per stream is not the state of max_tracks = {mt}')
-    Z = _lib.ZONES_MAX
+    mt = _row_slots(state, _lib.ZONES_STATE_HEADER, _lib.ZONES_SLOT_WORDS) if max_tracks is None else int(max_tracks)
+    _state_check(_ZONES_STATE, state, (mt,), 'zones_state_views', views=True)
+    S, Z = state.shape[0], _lib.ZONES_MAX
     out = {'now': state[:, 0], 'zone_counts': state[:, 4:4 + 4 * Z].view(S, Z, 4), 'line_counts': state[:, 4 + 4 * Z:4 + 6 * Z].view(S, Z, 2),
            'dwell_max': state[:, 4 + 6 * Z:4 + 7 * Z], 'dwell_sum': state[:, 4 + 7 * Z:4 + 9 * Z].view(torch.int64)}
     o = _lib.ZONES_STATE_HEADER
@@ -1959,8 +2003,9 @@ def zones_state_views(state, max_tracks=None):
     return out
 
 
-def _track_planes(what, track_out):
-    """(S, F, MT, device) of the dict ops.track_frames returned, its box, id, cls, missed and count planes checked."""
+def _track_planes(what, track_out, fam, state, *more):
+    """(S, F, MT, device) of the dict ops.track_frames returned, its box, id, cls, missed and count planes checked, and with
+    them the state of family `fam` (`more`: what its row length takes after MT) that a launch behind the tracker's keeps."""
     box = track_out['box']
     if not isinstance(box, torch.Tensor) or box.dim() != 4 or box.shape[3] != 5:
         raise ValueError(f'{what}: track_out is the dict of ops.track_frames (box [S,F,MT,5], id, cls, missed, count)')
@@ -1968,10 +2013,11 @@ def _track_planes(what, track_out):
     dev = box.device
     shapes = {'box': ((S, F, mt, 5), torch.float32), 'id': ((S, F, mt), torch.int64), 'cls': ((S, F, mt), torch.int64),
               'missed': ((S, F, mt), torch.int32), 'count': ((S, F), torch.int32)}
-    for k, (shape, dt) in shapes.items():
-        t = track_out[k]
-        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            raise ValueError(f'{what}: track_out[{k!r}] must be a contiguous {dt} tensor {shape} on {dev}')
+    _check_planes(what, 'track_out', track_out, shapes, dev)
+    _state_check(fam, state, (mt,) + more, what)
+    if state.shape[0] != S or state.device != dev:
+        raise ValueError(f'{what}: a state of {S} streams on {dev} expected, got {state.shape[0]} on {state.device}')
+    require_gpu(box, what)
     return S, F, mt, dev
 
 
@@ -1984,12 +2030,7 @@ def zones_frames(track_out, state, zone_set, heat=None, out=None):
     (entries, exits, lost, visits; cumulative), line_counts [S,F,L,2] (pos, neg; cumulative).  out: such a dict to write into."""
     if not isinstance(zone_set, _lib.ZoneSet):
         raise TypeError(f'zones_frames: zone_set is a _lib.ZoneSet (ops.zone_set), got {type(zone_set).__name__}')
-    S, F, mt, dev = _track_planes('zones_frames', track_out)
-    box = track_out['box']
-    _check_zones_state(state, mt, 'zones_frames')
-    if state.shape[0] != S or state.device != dev:
-        raise ValueError(f'zones_frames: a state of {S} streams on {dev} expected, got {state.shape[0]} on {state.device}')
-    require_gpu(box, 'zones_frames')
+    S, F, mt, dev = _track_planes('zones_frames', track_out, _ZONES_STATE, state)
     if zone_set.heat_h > 0:
         want = (S, zone_set.heat_h, zone_set.heat_w)
         if not isinstance(heat, torch.Tensor) or tuple(heat.shape) != want or heat.dtype != torch.int32 or heat.device != dev or not heat.is_contiguous():
@@ -1997,16 +2038,12 @@ def zones_frames(track_out, state, zone_set, heat=None, out=None):
     elif heat is not None:
         raise ValueError('zones_frames: heat given, but the zone_set has no heat grid')
     Z, L = zone_set.n_polygons, zone_set.n_lines
-    oshapes = {'inside': (S, F, mt), 'crossed': (S, F, mt), 'dwell': (S, F, mt, Z), 'occupancy': (S, F, Z), 'zone_counts': (S, F, Z, 4),
-               'line_counts': (S, F, L, 2)}
-    if out is None:
-        out = {k: torch.empty(shape, dtype=torch.int32, device=dev) for k, shape in oshapes.items()}
-    for k, shape in oshapes.items():
-        t = out[k]
-        if tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
-            raise ValueError(f'zones_frames: out[{k!r}] must be a contiguous int32 tensor {shape} on {dev}')
+    i32 = torch.int32
+    out = out_planes('zones_frames', out, {'inside': ((S, F, mt), i32), 'crossed': ((S, F, mt), i32), 'dwell': ((S, F, mt, Z), i32),
+                                           'occupancy': ((S, F, Z), i32), 'zone_counts': ((S, F, Z, 4), i32),
+                                           'line_counts': ((S, F, L, 2), i32)}, dev)
     t0 = TIMER.start() if TIMER else None
-    code = _lib.lib().mydet_zones_frames(_ptr(box), _ptr(track_out['id']), _ptr(track_out['cls']), _ptr(track_out['missed']),
+    code = _lib.lib().mydet_zones_frames(_ptr(track_out['box']), _ptr(track_out['id']), _ptr(track_out['cls']), _ptr(track_out['missed']),
                                          _ptr(track_out['count']), S, F, mt, ctypes.byref(zone_set), _ptr(state), _ptr(heat),
                                          _ptr(out['inside']), _ptr(out['crossed']), _ptr(out['dwell']), _ptr(out['occupancy']),
                                          _ptr(out['zone_counts']), _ptr(out['line_counts']), _stream())
@@ -2052,12 +2089,7 @@ def motion_geometry(frame_hw, set):
     2R + 16 reduced pixels per side, too large (32768), or has more than 1024 blocks."""
     if not isinstance(set, _lib.MotionSet):
         raise TypeError(f'motion: set is a _lib.MotionSet (ops.motion_set), got {type(set).__name__}')
-    try:
-        H, W = (int(v) for v in frame_hw)
-    except (TypeError, ValueError):
-        raise ValueError(f'motion: a frame size (H, W) expected, got {frame_hw!r}') from None
-    if not (1 <= H <= _lib.ZONE_MAX_FRAME and 1 <= W <= _lib.ZONE_MAX_FRAME):
-        raise ValueError(f'motion: a frame size (H, W) of 1 .. {_lib.ZONE_MAX_FRAME} each expected, got {frame_hw!r}')
+    H, W = _frame_hw('motion', frame_hw)
     R = set.search
     k = set.reduce or next((c for c in (2, 4) if max(H, W) <= 512 * c), 8)
     hr, wr = H // k, W // k
@@ -2072,39 +2104,26 @@ def motion_geometry(frame_hw, set):
                 min_blocks=set.min_blocks or max(2, (nb + 7) // 8), state_words=words)
 
 
-def _check_motion_state(state, geo, what):
-    words = geo['state_words']
-    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != words or not state.is_contiguous():
-        got = f'{state.dtype} {tuple(state.shape)}' if isinstance(state, torch.Tensor) else type(state).__name__
-        raise ValueError(f"{what}: a contiguous int32 state [streams, {words}] for {geo['H']}x{geo['W']} frames expected, got {got}")
-    require_gpu(state, what)
+# the family's argument is the geometry of a frame size under a motion_set, so that a call works it out once
+_MOTION_STATE = _StateFamily('motion', 'motion', lambda geo: geo['state_words'], '{0[H]}x{0[W]} frames', 'mydet_motion_reset',
+                             lambda geo: (geo['H'], geo['W'], geo['k'], geo['R']), True)
 
 
 def motion_state(streams, frame_hw, set, device):
     """A reset estimator state: int32 [streams, words] for frames of frame_hw under `set` (include/mydet.h has the layout)."""
-    geo = motion_geometry(frame_hw, set)
-    streams = int(streams)
-    if streams < 1:
-        raise ValueError(f'motion: streams >= 1 expected, got {streams}')
-    state = torch.empty((streams, geo['state_words']), dtype=torch.int32, device=device)
-    return motion_reset_(state, frame_hw, set)
+    return _state_new(_MOTION_STATE, streams, (motion_geometry(frame_hw, set),), device)
 
 
 def motion_reset_(state, frame_hw, set):
     """Reset an estimator state in place (mydet_motion_reset): the next frame of every stream has no previous one."""
-    geo = motion_geometry(frame_hw, set)
-    _check_motion_state(state, geo, 'motion_reset_')
-    code = _lib.lib().mydet_motion_reset(_ptr(state), state.shape[0], geo['H'], geo['W'], geo['k'], geo['R'], _stream())
-    _lib.check(code, 'mydet_motion_reset')
-    return state
+    return _state_reset(_MOTION_STATE, state, (motion_geometry(frame_hw, set),))
 
 
 def motion_state_views(state, frame_hw, set):
     """Field views of an estimator state int32 [S, words], nothing copied: seen int32 [S], reduced uint8 [S,hr,wr] (the last
     frame's reduced luma), patches uint8 [S,nb,P,P].  Works on any device (tests read a host copy)."""
     geo = motion_geometry(frame_hw, set)
-    if state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != geo['state_words'] or not state.is_contiguous():
-        raise ValueError(f"motion_state_views: a contiguous int32 state [streams, {geo['state_words']}] expected, got {state.dtype} {tuple(state.shape)}")
+    _state_check(_MOTION_STATE, state, (geo,), 'motion_state_views', views=True)
     S, o = state.shape[0], _lib.MOTION_STATE_HEADER
     nred, npat = geo['hr'] * geo['wrp'] // 4, geo['nb'] * geo['P'] ** 2 // 4
     return {'seen': state[:, 0],
@@ -2126,19 +2145,13 @@ def motion_frames(image, state, set, frames_per_stream=None, layout=None, out=No
     img, yuv, B = _image(what, image, layout, 'bt601', False, False)
     H, W = (img.shape[1:3] if yuv is None else img[0].shape[1:3])
     geo = motion_geometry((H, W), set)
-    _check_motion_state(state, geo, what)
+    _state_check(_MOTION_STATE, state, (geo,), what)
     S = state.shape[0]
     if B % S or (frames_per_stream is not None and int(frames_per_stream) * S != B):
         raise ValueError(f'{what}: {B} frames are not F frames of each of {S} streams')
     F = B // S
     dev = _same_device(what, img, [state])
-    shapes = {'shift': (S, F, 4), 'blocks': (S, F, geo['nb'], 6)}
-    if out is None:
-        out = {k: torch.empty(shape, dtype=torch.int32, device=dev) for k, shape in shapes.items()}
-    for k, shape in shapes.items():
-        t = out[k]
-        if tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
-            raise ValueError(f'{what}: out[{k!r}] must be a contiguous int32 tensor {shape} on {dev}')
+    out = out_planes(what, out, {'shift': ((S, F, 4), torch.int32), 'blocks': ((S, F, geo['nb'], 6), torch.int32)}, dev)
     nbytes = _lib.lib().mydet_motion_workspace_bytes(B, geo['H'], geo['W'], geo['k'], geo['R'])
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     _launch_on_image(what, img, yuv, 'mydet_motion_frames_rgb_u8', 'mydet_motion_frames_yuv420', S, ctypes.byref(set), _ptr(state),
@@ -2967,68 +2980,40 @@ def trail_set(max_points, anchor='center', classes=None):
     or 'bottom' and classes None or 1 .. 16 class indices, as in zone_set.  A ValueError otherwise; touches no device."""
     if isinstance(max_points, bool) or not isinstance(max_points, (int, np.integer)) or not 2 <= max_points <= _lib.TRAIL_MAX_POINTS:
         raise ValueError(f'trail_set: an integer max_points in 2 .. {_lib.TRAIL_MAX_POINTS} expected, got {max_points!r}')
-    if not isinstance(anchor, str) or anchor not in ZONE_ANCHORS:
-        raise ValueError(f'trail_set: anchor {anchor!r} is not one of {sorted(ZONE_ANCHORS)}')
     t = _lib.TrailSet()
-    t.max_points, t.anchor = int(max_points), ZONE_ANCHORS[anchor]
-    if classes is not None:
-        cl = [int(c) for c in classes]
-        if not 1 <= len(cl) <= _lib.ZONE_MAX_CLASSES or any(c < 0 or c >= 1 << 31 for c in cl):
-            raise ValueError(f'trail_set: classes is None or 1 .. {_lib.ZONE_MAX_CLASSES} class indices, got {classes!r}')
-        t.n_classes = len(cl)
-        t.classes[:len(cl)] = cl
+    t.max_points, t.anchor = int(max_points), _zone_anchor('trail_set', anchor)
+    _set_classes('trail_set', t, classes)
     return t
 
 
 def trails_state_words(max_tracks, max_points):
     """int32 words of one stream's trail state (include/mydet.h: mydet_trails_state_words); host arithmetic only."""
-    max_tracks, max_points = int(max_tracks), int(max_points)
-    if not 1 <= max_tracks <= _lib.TRACK_MAX_TRACKS:
-        raise ValueError(f'trails: 1 <= max_tracks <= {_lib.TRACK_MAX_TRACKS} expected, got {max_tracks}')
+    max_tracks, max_points = _max_tracks('trails', max_tracks), int(max_points)
     if not 2 <= max_points <= _lib.TRAIL_MAX_POINTS:
         raise ValueError(f'trails: 2 <= max_points <= {_lib.TRAIL_MAX_POINTS} expected, got {max_points}')
     return (max_tracks * (4 + 2 * max_points) + 3) // 4 * 4
 
 
-def _check_trails_state(state, max_tracks, max_points, what):
-    words = trails_state_words(max_tracks, max_points)
-    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != words or not state.is_contiguous():
-        got = f'{state.dtype} {tuple(state.shape)}' if isinstance(state, torch.Tensor) else type(state).__name__
-        raise ValueError(f'{what}: a contiguous int32 state [streams, {words}] for max_tracks = {max_tracks}, max_points = {max_points} expected, '
-                         f'got {got}')
-    require_gpu(state, what)
-    return words
+_TRAILS_STATE = _StateFamily('trails', 'trails', trails_state_words, 'max_tracks = {}, max_points = {}', 'mydet_trails_reset', _ints, True)
 
 
 def trails_state(streams, max_tracks, max_points, device):
     """A reset trail state: int32 [streams, trails_state_words(max_tracks, max_points)] (include/mydet.h has the layout)."""
-    words = trails_state_words(max_tracks, max_points)
-    streams = int(streams)
-    if streams < 1:
-        raise ValueError(f'trails: streams >= 1 expected, got {streams}')
-    state = torch.empty((streams, words), dtype=torch.int32, device=device)
-    return trails_reset_(state, max_tracks, max_points)
+    return _state_new(_TRAILS_STATE, streams, (max_tracks, max_points), device)
 
 
 def trails_reset_(state, max_tracks, max_points):
     """Reset a trail state in place (mydet_trails_reset): every ring empty."""
-    _check_trails_state(state, max_tracks, max_points, 'trails_reset_')
-    code = _lib.lib().mydet_trails_reset(_ptr(state), state.shape[0], int(max_tracks), int(max_points), _stream())
-    _lib.check(code, 'mydet_trails_reset')
-    return state
+    return _state_reset(_TRAILS_STATE, state, (max_tracks, max_points))
 
 
 def trails_state_views(state, max_tracks, max_points):
     """Field views of a trail state int32 [S, words] (include/mydet.h: mydet_trails_frames), nothing copied: id int64 [S,MT]
     (0 = an empty slot), fill, head int32 [S,MT], ring int32 [S,MT,L,2].  Works on any device (tests read a host copy)."""
-    if state.dtype != torch.int32 or state.dim() != 2 or not state.is_contiguous():
-        raise ValueError(f'trails_state_views: a contiguous int32 state [streams, words] expected, got {state.dtype} {tuple(state.shape)}')
     mt, L = int(max_tracks), int(max_points)
-    S, words = state.shape
-    if words != trails_state_words(mt, L):
-        raise ValueError(f'trails_state_views: {words} words per stream is not the state of max_tracks = {mt}, max_points = {L}')
+    _state_check(_TRAILS_STATE, state, (mt, L), 'trails_state_views', views=True)
     return {'id': state[:, :2 * mt].view(torch.int64), 'fill': state[:, 2 * mt:3 * mt], 'head': state[:, 3 * mt:4 * mt],
-            'ring': state[:, 4 * mt:4 * mt + 2 * L * mt].view(S, mt, L, 2)}
+            'ring': state[:, 4 * mt:4 * mt + 2 * L * mt].view(state.shape[0], mt, L, 2)}
 
 
 def trails_frames(track_out, state, trail_set, out=None):
@@ -3039,19 +3024,10 @@ def trails_frames(track_out, state, trail_set, out=None):
     what = 'trails_frames'
     if not isinstance(trail_set, _lib.TrailSet):
         raise TypeError(f'{what}: trail_set is a _lib.TrailSet (ops.trail_set), got {type(trail_set).__name__}')
-    S, F, mt, dev = _track_planes(what, track_out)
     L = trail_set.max_points
-    _check_trails_state(state, mt, L, what)
-    if state.shape[0] != S or state.device != dev:
-        raise ValueError(f'{what}: a state of {S} streams on {dev} expected, got {state.shape[0]} on {state.device}')
-    require_gpu(track_out['box'], what)
-    oshapes = {'points': (S, F, mt, L, 2), 'len': (S, F, mt), 'bbox': (S, F, mt, 4)}
-    if out is None:
-        out = {k: torch.empty(shape, dtype=torch.int32, device=dev) for k, shape in oshapes.items()}
-    for k, shape in oshapes.items():
-        t = out[k]
-        if tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
-            raise ValueError(f'{what}: out[{k!r}] must be a contiguous int32 tensor {shape} on {dev}')
+    S, F, mt, dev = _track_planes(what, track_out, _TRAILS_STATE, state, L)
+    out = out_planes(what, out, {'points': ((S, F, mt, L, 2), torch.int32), 'len': ((S, F, mt), torch.int32),
+                                 'bbox': ((S, F, mt, 4), torch.int32)}, dev)
     t0 = TIMER.start() if TIMER else None
     code = _lib.lib().mydet_trails_frames(_ptr(track_out['box']), _ptr(track_out['id']), _ptr(track_out['cls']), _ptr(track_out['missed']),
                                           _ptr(track_out['count']), S, F, mt, ctypes.byref(trail_set), _ptr(state), _ptr(out['points']),
@@ -3577,37 +3553,27 @@ def appear_set(gate=0.3, reid=0.6, momentum=0.9, reach=2.0, update_thres=0.3):
 
 def appear_state_words(max_tracks):
     """int32 words of one stream's appearance state (mydet_track_appear_state_words); host arithmetic only."""
-    track_state_words(max_tracks)                                      # the range check
-    return ((1 + _lib.APPEAR_BINS) * int(max_tracks) + 3) // 4 * 4
+    return ((1 + _lib.APPEAR_BINS) * _max_tracks('tracker', max_tracks) + 3) // 4 * 4
 
 
-def _check_appear_state(state, max_tracks, what):
-    words = appear_state_words(max_tracks)
-    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != words or not state.is_contiguous():
-        got = f'{state.dtype} {tuple(state.shape)}' if isinstance(state, torch.Tensor) else type(state).__name__
-        raise ValueError(f'{what}: a contiguous int32 appearance state [streams, {words}] for max_tracks = {max_tracks} expected, got {got}')
-    return words
+# the one family whose state may live on the host: its reset is a fill, and nothing but the tracker launch reads it
+_APPEAR_STATE = _StateFamily('appear', 'appear_state', appear_state_words, 'the appearance templates of max_tracks = {}', None, None, False)
 
 
 def appear_state(streams, max_tracks, device):
     """A cleared appearance state: int32 zeros [streams, appear_state_words(max_tracks)] -- no slot has a template."""
-    words = appear_state_words(max_tracks)
-    streams = int(streams)
-    if streams < 1:
-        raise ValueError(f'appear_state: streams >= 1 expected, got {streams}')
-    return torch.zeros((streams, words), dtype=torch.int32, device=device)
+    return _state_new(_APPEAR_STATE, streams, (max_tracks,), device)
 
 
 def appear_reset_(state, max_tracks):
     """Clear an appearance state in place: every `has` flag and every template bin is 0 (the state's initial value)."""
-    _check_appear_state(state, max_tracks, 'appear_reset_')
-    return state.zero_()
+    return _state_reset(_APPEAR_STATE, state, (max_tracks,))
 
 
 def appear_state_views(state, max_tracks):
     """Field views of an appearance state int32 [S, words], nothing copied: has int32 [S,MT], tmpl int32 [S,128,MT] in units of
     1/256 sample (bin-major).  Works on any device."""
-    _check_appear_state(state, max_tracks, 'appear_state_views')
+    _state_check(_APPEAR_STATE, state, (max_tracks,), 'appear_state_views', views=True)
     mt = int(max_tracks)
     return {'has': state[:, :mt], 'tmpl': state[:, mt:mt + _lib.APPEAR_BINS * mt].view(state.shape[0], _lib.APPEAR_BINS, mt)}
 
