@@ -1601,6 +1601,87 @@ int mydet_track_frames_appear_f32(const int32_t *records, int64_t stream_stride_
                                   const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
                                   int32_t *out_sim, int32_t *out_how, void *stream);
 
+/* Key frames: the detector runs on every n-th frame only, and the boxes of a key frame are carried through the frames that follow
+ * by matching their pixels (csrc/carry.hip), so that the tracker still gets one record per frame.  Everything after one conversion
+ * of the box is integer arithmetic; tests/_carry_ref.py restates the rules and the kernels equal it with == on every output and
+ * on every word of the state.  The reference project has nothing like it (DeepStream's `interval` with a visual tracker is the
+ * deployed form of the idea).
+ *
+ * Frames: frame f of stream s is frame o = s*F + f of the B = S*F frames of the call.  `first` in [0, every) is the place of the
+ * call's frame 0 inside its interval: frame f is a KEY frame when (first + f) % every == 0.  A stream has K = the number of key
+ * frames among its F frames; key_records holds the detector's records of the key frames, stream-major: key k of stream s is row
+ * s*K + k, rows key_stride_words apart, each a record of MYDET_REC_WORDS (box_width 4) or MYDET_REC_ROT_WORDS (box_width 5) words.
+ * Luma L(y, x): that of the camera-motion estimator above, per source.  A coordinate outside the frame clamps to the edge.
+ * Every slot (the 512 rows of a record) of every stream is carried on its own.
+ *
+ * 1. Key frame.  The frame's row of out_records is its key record, every word copied.  With COUNT outside 1 .. 512 (0, the
+ *    bad-class marker) no slot is carried: every slot is EMPTY.  Otherwise slot j >= COUNT is EMPTY, and slot j < COUNT takes
+ *    v16 = (int) floorf(v * 16.0f + 0.5f), float32 with separate multiply and add, of v = cx, cy, w, h.  It is NOT CARRIABLE
+ *    when one of the four is not finite or |v| >= 2^26, or w16 <= 0 or h16 <= 0.  Else it is ALIVE with m = min(w16, h16),
+ *    side = 3 m / 4 (box_width 5: m / 2, which lies inside the box at any angle), the cell size s = clamp((side + 255) / 256, 1, 16)
+ *    pixels, X = cx16 >> 4, Y = cy16 >> 4 (arithmetic shifts), off = (0, 0), rel = (0, 0), and its template is taken from this
+ *    frame:   coarse  C(i, j) = (sum of L over the s x s pixels at (Y - 8 s + i s, X - 8 s + j s) + s*s/2) / (s*s),  i, j in 0 .. 15;
+ *             patch   P(i, j) = L(Y - 16 + i, X - 16 + j), i, j in 0 .. 31, for s >= 2 (zero bytes for s == 1).
+ *    The template stays for the whole interval.
+ * 2. In-between frame t, ALIVE slot.  (dx, dy) = the frame's shift when `shift` is given and its valid == 1, else (0, 0).
+ *    c = clamp(off + rel + (dx, dy), -65536, 65536) per axis.  Coarse search: for every (i, j) in [-R, R]^2, R = `search`, the SAD of
+ *    C against the 16 x 16 cell means of frame t, computed like C, whose grid starts at (Y - 8 s + c.y + i s, X - 8 s + c.x + j s).
+ *    The best candidate is the smallest (SAD, i*i + j*j, i, j), compared lexicographically (the estimator's order); smin = its
+ *    SAD, smax = the largest SAD.  smax - smin < min_texture: the slot is FLAT.  Else smin > 256 max_diff: it is LOST.  Else
+ *    n = c + (j s, i s), and for s >= 2 the refine search: for every (ey, ex) in [-s, s]^2 the SAD of P against L of frame t at
+ *    (Y - 16 + n.y + ey, X - 16 + n.x + ex); the best by (SAD, ey*ey + ex*ex, ey, ex); n = n + (ex, ey).  Then
+ *    rel = (n - off) - (dx, dy), off = n.  With (X + off.x, Y + off.y) outside [0, W) x [0, H) the slot has LEFT.
+ *    A FLAT, LOST or LEFT slot, like a NOT CARRIABLE one, stays what it is until the next key frame.
+ * 3. The row of an in-between frame: the ALIVE slots in key order, compacted.  cx = cx + (float) off.x, cy = cy + (float) off.y,
+ *    one float32 add each; w, h, angle, score and class are the key slot's; INDEX = the key slot; COUNT = their number; 3 zero
+ *    words; entries from COUNT on are zero.
+ * Out: out_how int32 [S*F][512]: 0 EMPTY, 1 in a key frame's row (slots below its COUNT in 1 .. 512), 2 carried, 3 FLAT, 4 LOST,
+ *   5 LEFT, 6 NOT CARRIABLE; 3 .. 6 are repeated in every in-between frame until the next key frame.  out_offset int32
+ *   [S*F][512][2] = off (x, y) where how == 2, else 0.  out_sad int32 [S*F][512][2] = (smin, smax) in the frame in which the slot was
+ *   searched (how 2, and 3 .. 5 in the frame they were decided), else 0.
+ * state: S * mydet_carry_state_words() int32 words, 16-byte aligned, caller-owned, persistent; mydet_carry_reset makes it all zero.
+ *   Per stream 512 slots of MYDET_CARRY_SLOT_WORDS words:  [0] status (0 EMPTY, 2 ALIVE, 3 .. 6)  [1] s  [2] cx16  [3] cy16
+ *   [4] off.x  [5] off.y  [6] rel.x  [7] rel.y  [8 .. 11] the key box (cx, cy, w, h) f32  [12] angle f32 (0 for box_width 4)  [13] score f32
+ *   [14, 15] class i64  [16 .. 79] C, 256 bytes  [80 .. 335] P, 1024 bytes.  Every word but [0] is zero unless the slot is ALIVE.
+ *   Two calls of F1 and F2 frames (first of the second = (first + F1) % every) leave exactly the outputs and the state of one call
+ *   of F1 + F2 frames.  A workgroup is the only reader and writer of its slot's state.
+ * ws: device scratch of S * 512 * 8 int32 words, stream-ordered (the key fields of the slots that a call carries in from the state).
+ * shift: NULL, or DEVICE int32 [S*F][4] = (dx, dy, valid, n_valid), out_shift of the estimator above.
+ * Frames are read in place: RGB packed pixels with any row and frame stride; 4:2:0 through mydet_yuv420_src, every layout.
+ * Not part of the rules: scale, rotation or deformation of a carried box, sub-pixel offsets, a template update within an interval.
+ * MYDET_E_BADARG, with nothing launched: B or S < 1, B no multiple of S, S > 65535; a null set; every outside 1 .. 16; search outside
+ *   4 .. 16; min_texture outside [0, 2^24); max_diff outside 0 .. 255; first outside [0, every); box_width not 4 or 5; a null or
+ *   misaligned pointer (state, out_records, key_records: 16 bytes; the others: 4; key_records may be NULL when K == 0, shift always);
+ *   key_stride_words below the record's words or no multiple of 4; H or W outside 1 .. 32768; the source errors of the pixel format. */
+#define MYDET_CARRY_SLOTS        512
+#define MYDET_CARRY_SLOT_HEADER  16
+#define MYDET_CARRY_SLOT_WORDS   336      /* header + 1280 template bytes */
+#define MYDET_CARRY_MAX_EVERY    16
+#define MYDET_CARRY_HOW_NONE     0
+#define MYDET_CARRY_HOW_KEY      1
+#define MYDET_CARRY_HOW_CARRIED  2
+#define MYDET_CARRY_HOW_FLAT     3
+#define MYDET_CARRY_HOW_LOST     4
+#define MYDET_CARRY_HOW_LEFT     5
+#define MYDET_CARRY_HOW_NOT      6
+typedef struct mydet_carry_set {
+    int every;                           /* a key frame every n-th frame, 1 .. 16 */
+    int search;                          /* R: the coarse search range in cells, 4 .. 16 */
+    int min_texture;                     /* the least SAD range over the candidates of a slot that is followed */
+    int max_diff;                        /* the largest mean absolute cell difference of a match, 0 .. 255 */
+    int reserved[4];
+} mydet_carry_set;
+int64_t mydet_carry_state_words(void);
+int mydet_carry_reset(int32_t *state, int S, void *stream);
+int mydet_carry_records_rgb_u8(const unsigned char *src, int B, int H, int W, int64_t src_img_bytes, int64_t src_row_bytes, int S,
+                               const mydet_carry_set *set, int first, const int32_t *key_records, int64_t key_stride_words,
+                               int box_width, int32_t *state, const int32_t *shift, int32_t *ws, int32_t *out_records,
+                               int32_t *out_how, int32_t *out_offset, int32_t *out_sad, void *stream);
+int mydet_carry_records_yuv420(const struct mydet_yuv420_src *src, int B, int H, int W, int S, const mydet_carry_set *set, int first,
+                               const int32_t *key_records, int64_t key_stride_words, int box_width, int32_t *state,
+                               const int32_t *shift, int32_t *ws, int32_t *out_records, int32_t *out_how, int32_t *out_offset,
+                               int32_t *out_sad, void *stream);
+
 /* Scoring detections against ground truth: COCO's bbox evaluation with useCats = 1, in three stream-ordered launches
  * (csrc/evalmatch.hip).  Replaces utils/evaluation/coco.py (coco_evaluate_bbox, myCOCOeval) and utils/evaluation/cepdof.py
  * (evaluate_json, CEPDOFeval) of the reference, which sit on pycocotools: its computeIoU, evaluateImg and accumulate.  The

@@ -101,6 +101,12 @@ SIGNATURES = {
     'mydet_motion_reset': [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr],
     'mydet_motion_frames_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
     'mydet_motion_frames_yuv420': [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
+    'mydet_carry_state_words': [],
+    'mydet_carry_reset': [c_ptr, c_int, c_ptr],
+    'mydet_carry_records_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_int, c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
+                                   c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_carry_records_yuv420': [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                   c_ptr, c_ptr],
     'mydet_zones_state_words': [c_int],
     'mydet_zones_reset': [c_ptr, c_int, c_int, c_ptr],
     'mydet_zones_frames': [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
@@ -164,7 +170,7 @@ SIGNATURES = {
 RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems',
                'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words', 'mydet_mot_scratch_bytes', 'mydet_zones_state_words',
                'mydet_redact_workspace_bytes', 'mydet_trails_state_words', 'mydet_motion_state_words', 'mydet_motion_workspace_bytes',
-               'mydet_track_appear_state_words'}
+               'mydet_track_appear_state_words', 'mydet_carry_state_words'}
 
 # detection record layout (MYDET_REC_* of include/mydet.h), in int32 words
 REC_TOPK = 512
@@ -198,6 +204,9 @@ ZONE_ANCHOR_CENTER, ZONE_ANCHOR_BOTTOM = 0, 1
 ZONES_STATE_HEADER, ZONES_SLOT_WORDS = 148, 22
 # camera motion (mydet_motion_frames_*): MYDET_MOTION_* of include/mydet.h
 MOTION_MIN_SEARCH, MOTION_MAX_SEARCH, MOTION_MAX_BLOCKS, MOTION_STATE_HEADER = 4, 16, 1024, 4
+# key frames (mydet_carry_records_*): MYDET_CARRY_* of include/mydet.h
+CARRY_SLOTS, CARRY_SLOT_HEADER, CARRY_SLOT_WORDS, CARRY_MAX_EVERY = 512, 16, 336, 16
+CARRY_HOW_NONE, CARRY_HOW_KEY, CARRY_HOW_CARRIED, CARRY_HOW_FLAT, CARRY_HOW_LOST, CARRY_HOW_LEFT, CARRY_HOW_NOT = range(7)
 # overlay renderer (mydet_draw_boxes_*): MYDET_DRAW_* of include/mydet.h
 DRAW_MAX_BOXES, DRAW_MAX_THICKNESS, DRAW_MAX_GLYPHS, DRAW_NAME_BYTES = 512, 64, 33, 16
 DRAW_COLOR_CLASS, DRAW_COLOR_ID, DRAW_COLOR_FIXED = 0, 1, 2
@@ -301,6 +310,11 @@ class TrackAppear(ctypes.Structure):
 class MotionSet(ctypes.Structure):
     """mydet_motion_set (include/mydet.h): the settings of the camera-motion estimator; 0 = the default of the frame size."""
     _fields_ = [('reduce', c_int), ('search', c_int), ('min_texture', c_int), ('min_blocks', c_int), ('reserved', c_int * 4)]
+
+
+class CarrySet(ctypes.Structure):
+    """mydet_carry_set (include/mydet.h): the settings of the key-frame carry."""
+    _fields_ = [('every', c_int), ('search', c_int), ('min_texture', c_int), ('max_diff', c_int), ('reserved', c_int * 4)]
 
 
 class ZoneSet(ctypes.Structure):

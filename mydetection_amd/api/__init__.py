@@ -8,13 +8,15 @@ truth, `TrackEvaluator`, which scores its tracks against ground-truth identities
 polygons and across lines on the device, and `Overlay`, which paints those zones, lines, counters and the tracks' trails into
 the annotated frames, and `CameraMotion`, which estimates the global image shift of every frame on the device and moves the
 tracker's predictions by it, and `Appearance`, which gives every detection a colour descriptor on the device and lets the
-tracker gate its matches and re-identify lost tracks by it."""
+tracker gate its matches and re-identify lost tracks by it, and `KeyFrames`, which runs the network on every n-th frame only and
+carries the boxes through the frames between by their pixels, on the device."""
 from .appearance import Appearance
 from .detection import Augment, Chips, Detector, Draw, Nms, Redact, Tiles
 from .evaluation import Evaluator, TrackEvaluator
+from .keyframes import KeyFrames
 from .motion import CameraMotion
 from .overlay import Overlay
 from .tracking import Tracker
 from .zones import Zones
 
-__all__ = ['Appearance', 'Augment', 'CameraMotion', 'Chips', 'Detector', 'Draw', 'Evaluator', 'Nms', 'Overlay', 'Redact', 'Tiles', 'TrackEvaluator', 'Tracker', 'Zones']
+__all__ = ['Appearance', 'Augment', 'CameraMotion', 'Chips', 'Detector', 'Draw', 'Evaluator', 'KeyFrames', 'Nms', 'Overlay', 'Redact', 'Tiles', 'TrackEvaluator', 'Tracker', 'Zones']

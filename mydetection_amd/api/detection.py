@@ -17,6 +17,7 @@ from ..models.general import name_to_model
 from ..utils import image_ops as imgUtils
 from ..utils.structures import ImageObjects
 from .appearance import Appearance
+from .keyframes import KeyFrames
 from .motion import CameraMotion
 from .overlay import Overlay
 from .zones import Zones
@@ -248,6 +249,14 @@ class _Frames:
         return (ops.crop_boxes_yuv420 if yuv else ops.crop_boxes)(image, boxes=boxes, counts=counts, **yuv, **chip_kwargs)
 
 
+def _frame_subset(t, idxs):
+    """Frames `idxs` (ascending, at least one) of a device tensor [B, ...]: a view when they are evenly spaced, else one gather."""
+    step = idxs[1] - idxs[0] if len(idxs) > 1 else 1
+    if all(b - a == step for a, b in zip(idxs, idxs[1:])):
+        return t[idxs[0]:idxs[-1] + 1:step]
+    return t.index_select(0, torch.tensor(idxs, device=t.device))
+
+
 class _RgbFrames(_Frames):
     """uint8 RGB frames [B,H,W,3]: the tensors `parts` of one size from Detector._frame_groups.  packed: the call goes on to
     draw into or read the frames, which takes packed pixels -- frames that are not are copied once, on the device."""
@@ -281,6 +290,11 @@ class _RgbFrames(_Frames):
 
     def image(self):
         return self.on_device(), {}
+
+    def select(self, idxs):
+        """The source of frames `idxs` (ascending) of this one, on the device: a strided view when they are evenly spaced, else
+        one gather of those frames."""
+        return _RgbFrames(self.det, list(range(len(idxs))), [_frame_subset(self.on_device(), idxs)])
 
     drawn = on_device
 
@@ -324,6 +338,14 @@ class _Yuv420Frames(_Frames):
 
     def image(self):
         return self.on_device(), self.yuv
+
+    def select(self, idxs):
+        """As _RgbFrames.select, of every plane."""
+        sub = object.__new__(_Yuv420Frames)
+        sub.det, sub.given, sub.yuv, sub.in_place, sub.surface = self.det, None, self.yuv, False, None
+        sub.n, sub.hw, sub.idxs = len(idxs), self.hw, list(range(len(idxs)))
+        sub.planes = tuple(_frame_subset(t, idxs) for t in self.on_device())
+        return sub
 
     def drawn(self):
         return self.on_device() if self.surface is None else self.surface
@@ -674,6 +696,26 @@ class Detector():
             return self._records_of_inputs(sources, call)
         return self._records_of_windows(self._one_source(sources, 'tiled'), call)
 
+    def _carried_records(self, src, call, keyframes, tracker, shift):
+        """[(frame indices, records)] of the B frames of one source with keyframes=: only the key frames of the call (host
+        arithmetic on the KeyFrames' counter) go through _source_records -- the forward pass, the post-process, the window merge,
+        the view fusion --, as a subset of the source; then ONE launch pair (ops.carry_records) on the whole original frames makes
+        the record of every frame: a key frame's is the detector's, copied, an in-between frame's the key boxes carried by their
+        pixels.  shift: the camera motion of the call's frames, or None.  No host synchronisation."""
+        B, S = src.n, tracker.streams
+        F = B // S
+        keys = [s * F + f for s in range(S) for f, k in enumerate(keyframes.key_mask(F)) if k]
+        key_rec = None
+        if keys:
+            (_, key_rec), = self._source_records([src.select(keys)], call)
+            hw = key_rec['img_hw'][0]
+        else:                                                        # what the records of these frames would report
+            geo = self._geometry(src.hw[0], src.hw[1], call.preprocessing, call.input_size)
+            hw = src.hw if call.tiles is not None or geo[3] is not None else geo[2]
+        rec = keyframes.run(*src.image(), key_rec, tracker, src.hw, F, 5 if self.model.bb_format == 'cxcywhd' else 4, shift)
+        rec['img_hw'] = [hw] * B
+        return [(list(range(B)), rec)]
+
     def _records_of_inputs(self, sources, call):
         """The untiled records: sources of one network input size are one batch, in input order (one fused launch per source
         builds its part: ops.frames_to_input / ops.yuv420_to_input), and yield one (indices, records)."""
@@ -789,13 +831,14 @@ class Detector():
         overlay = self._pop_overlay(kwargs, tracker, zones, draw)
         motion = self._pop_companion(kwargs, 'motion', tracker)
         appearance = self._pop_appearance(kwargs, tracker)
+        keyframes = self._pop_companion(kwargs, 'keyframes', tracker)
         sources = make_sources()
         used = draw is not None or chips is not None or redact is not None
         if tracker is not None:
             src = self._one_source(sources, 'tracked')
             tracker.check_call(src.n, src.hw, self.model.bb_format)
             for companion, args in ((zones, (src.hw, self.model.bb_format)), (overlay, (zones, src.hw)), (motion, (src.hw,)),
-                                    (appearance, (src.hw,))):
+                                    (appearance, (src.hw,)), (keyframes, (src.hw,))):
                 if companion is not None:
                     companion.check_call(tracker, *args)
         elif used:
@@ -807,10 +850,13 @@ class Detector():
             # and the views of augment= included) runs at the lower threshold; the tracker keeps the call's own as high_thres
             tracker.assoc(conf_thres)
             call = self._call_settings(dict(kwargs, conf_thres=min(conf_thres, tracker.low_thres)), whole=True)
-        records = self._source_records(sources, call)
+        if keyframes is None:
+            records = self._source_records(sources, call)
         if tracker is not None:
             # the camera motion of the whole original frames (whatever tiles= and augment= fed the network), ahead of the tracker
             shift = None if motion is None else motion.run(*src.image(), tracker, src.hw)['shift']
+            if keyframes is not None:                                # the network on the key frames, the carry on all of them
+                records = self._carried_records(src, call, keyframes, tracker, shift)
             # the descriptors come from the whole original frames too, at the call's final records: behind the motion launches
             found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres, zones, overlay, shift,
                                                  None if appearance is None else (appearance, src))
@@ -866,7 +912,18 @@ class Detector():
         (mydet_track_frames_appear_f32) keeps a template per track, offers an IoU match only when the histogram intersection
         reaches `gate`, and gives a detection that would start a track to the most similar lost track within `reach` instead
         when it reaches `reid`.  No host synchronisation is added; appearance.last has desc, sim and how.  Every frame method
-        that takes tracker= takes appearance=; without it every call is bit for bit what it was."""
+        that takes tracker= takes appearance=; without it every call is bit for bit what it was.
+        keyframes: None, or a mydetection_amd.api.KeyFrames (with tracker= only: ValueError otherwise) to run the network on every
+        n-th frame of a stream only.  Its counter says which frames of the call are key frames (host arithmetic, calls of any
+        length continue each other); only those go through the input launch, the forward pass and the post-process (tiles= and
+        augment= included), as a strided view or one gather of the frames.  One launch pair on the call's whole original frames
+        (include/mydet.h: mydet_carry_records_rgb_u8) then makes the record of every frame: a key frame's is the detector's,
+        an in-between frame's holds the key boxes moved to where their pixels are found -- block matching against a template
+        taken at the key frame, around the box's last step and the camera's shift (motion=) --, and a box whose pixels are
+        flat, gone or out of the frame is left out, so that its track coasts as on any miss.  The tracker, the zones, the
+        trails and everything that paints read those records as any others; no host synchronisation is added; keyframes.last has
+        how, offset and sad.  every=1 gives the objects of the call without keyframes=, bit for bit.  Every frame method that
+        takes tracker= takes keyframes=; without it every call is bit for bit what it was."""
         return self._detect(lambda: self._rgb_sources(frames), kwargs)
 
     @staticmethod
@@ -883,7 +940,8 @@ class Detector():
     _COMPANIONS = {'zones': (Zones, 'zones= counts tracks'),
                    'overlay': (Overlay, None),
                    'motion': (CameraMotion, 'motion= moves the predictions of a tracker'),
-                   'appearance': (Appearance, 'appearance= gates and re-identifies the tracks of a tracker')}
+                   'appearance': (Appearance, 'appearance= gates and re-identifies the tracks of a tracker'),
+                   'keyframes': (KeyFrames, 'keyframes= fills the frames between key frames for a tracker')}
 
     @staticmethod
     def _pop_companion(kwargs, key, tracker):
@@ -922,7 +980,7 @@ class Detector():
 
     @staticmethod
     def _no_tracker(kwargs, what):
-        if 'tracker' in kwargs or 'coasting' in kwargs or 'zones' in kwargs or 'motion' in kwargs or 'appearance' in kwargs:
+        if 'tracker' in kwargs or 'coasting' in kwargs or 'zones' in kwargs or 'motion' in kwargs or 'appearance' in kwargs or 'keyframes' in kwargs:
             raise TypeError(f'{what}: track ids in the json rows are not built; use the predict_frames form with tracker=')
 
     def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres, zones=None, overlay=None, shift=None, appearance=None):

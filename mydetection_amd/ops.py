@@ -2159,6 +2159,138 @@ def motion_frames(image, state, set, frames_per_stream=None, layout=None, out=No
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# Key frames (include/mydet.h: mydet_carry_records_rgb_u8, where the rules are; csrc/carry.hip)
+
+def carry_set(every=4, search=8, min_texture=1024, max_diff=24):
+    """The settings of the key-frame carry (a _lib.CarrySet; include/mydet.h has the rules).  every: a key frame every n-th
+    frame, 1 .. 16; search: the coarse search range, 4 .. 16 cells; min_texture: the least SAD range over a slot's candidates
+    that is followed (below it the slot is flat); max_diff: the largest mean absolute difference per cell of a match, 0 .. 255
+    (above it the slot is lost).  ValueError for anything out of range; touches no device."""
+    def whole(name, v, lo, hi, text):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f'carry_set: {name} is an integer, got {v!r}')
+        if not lo <= int(v) <= hi:
+            raise ValueError(f'carry_set: {name} of {text} expected, got {v!r}')
+        return int(v)
+    c = _lib.CarrySet()
+    c.every = whole('every', every, 1, _lib.CARRY_MAX_EVERY, f'1 .. {_lib.CARRY_MAX_EVERY} frames')
+    c.search = whole('search', search, _lib.MOTION_MIN_SEARCH, _lib.MOTION_MAX_SEARCH, f'{_lib.MOTION_MIN_SEARCH} .. {_lib.MOTION_MAX_SEARCH} cells')
+    c.min_texture = whole('min_texture', min_texture, 0, (1 << 24) - 1, '0 .. 2^24 - 1')
+    c.max_diff = whole('max_diff', max_diff, 0, 255, '0 .. 255')
+    return c
+
+
+def carry_state_words():
+    """int32 words of one stream's carry state: 512 slots of a 16-word header and 1280 template bytes."""
+    return _lib.CARRY_SLOTS * _lib.CARRY_SLOT_WORDS
+
+
+_CARRY_STATE = _StateFamily('carry', 'carry', carry_state_words, '512 slots', 'mydet_carry_reset', lambda: (), True)
+
+
+def carry_state(streams, device):
+    """A reset carry state: int32 zeros [streams, carry_state_words()] -- no slot is carried."""
+    return _state_new(_CARRY_STATE, streams, (), device)
+
+
+def carry_reset_(state):
+    """Reset a carry state in place (mydet_carry_reset): the frames before the next key frame carry nothing."""
+    return _state_reset(_CARRY_STATE, state, ())
+
+
+def carry_state_views(state):
+    """Field views of a carry state int32 [S, words], nothing copied: status, cell, cx16, cy16 int32 [S,512]; offset, rel int32
+    [S,512,2]; box float32 [S,512,4]; angle, score float32 [S,512]; cls int64 [S,512]; coarse uint8 [S,512,16,16]; patch uint8
+    [S,512,32,32].  Works on any device (tests read a host copy)."""
+    _state_check(_CARRY_STATE, state, (), 'carry_state_views', views=True)
+    S = state.shape[0]
+    slots = state.view(S, _lib.CARRY_SLOTS, _lib.CARRY_SLOT_WORDS)
+    h = _lib.CARRY_SLOT_HEADER
+    return {'status': slots[:, :, 0], 'cell': slots[:, :, 1], 'cx16': slots[:, :, 2], 'cy16': slots[:, :, 3],
+            'offset': slots[:, :, 4:6], 'rel': slots[:, :, 6:8], 'box': slots[:, :, 8:12].view(torch.float32),
+            'angle': slots[:, :, 12].view(torch.float32), 'score': slots[:, :, 13].view(torch.float32),
+            'cls': slots[:, :, 14:16].view(torch.int64)[:, :, 0],
+            'coarse': slots[:, :, h:h + 64].view(torch.uint8).view(S, _lib.CARRY_SLOTS, 16, 16),
+            'patch': slots[:, :, h + 64:h + 320].view(torch.uint8).view(S, _lib.CARRY_SLOTS, 32, 32)}
+
+
+def carry_first(key_mask, every):
+    """The place of a call's frame 0 inside its interval, from the call's key mask (a sequence of F truth values: frame f is a
+    key frame): `first` with key_mask[f] == ((first + f) % every == 0).  A ValueError for a mask no `first` gives."""
+    mask = [bool(k) for k in key_mask]
+    if not mask:
+        raise ValueError('carry_records: an empty key mask')
+    first = (every - mask.index(True)) % every if True in mask else 1 % every
+    if mask != [(first + f) % every == 0 for f in range(len(mask))]:
+        raise ValueError(f'carry_records: key mask {mask} is no run of frames with a key frame every {every}')
+    return first
+
+
+def carry_records(source, key_records, key_mask, state, set, frames_per_stream=None, layout=None, shift=None, out=None, records=None):
+    """One record per frame out of the records of the key frames (include/mydet.h: mydet_carry_records_rgb_u8, where the rules
+    are): a key frame's row is its key record, an in-between row the key boxes carried by their pixels.  source: what the
+    ops.draw_* functions take first, read only -- uint8 RGB frames [S*F,H,W,3] with packed pixels and any row and frame
+    strides (layout None), or the planes of `layout`; frame f of stream s is frame s*F + f.  key_records: the record dict
+    (record_views) or the int32 buffer [S*K, words] of the K key frames of every stream, stream-major, or None when the call
+    has no key frame.  key_mask: F truth values, frame f of every stream is a key frame (one every `set.every` frames).
+    state: carry_state(...), updated in place; its row count is S.  shift: None, or int32 [S,F,4], the 'shift' of motion_frames
+    for the same frames.  Returns the record dict of the [S*F, words] buffer with 'how' int32 [S,F,512], 'offset' and 'sad' int32
+    [S,F,512,2] beside it, all on the device; out: a dict with such 'how', 'offset' and 'sad' to write into; records: the int32
+    [S*F, words] buffer to write into.  width: 4, or 5 for rotated records, is the key records'; without any it is `records`'."""
+    what = 'carry_records'
+    if not isinstance(set, _lib.CarrySet):
+        raise TypeError(f'{what}: set is a _lib.CarrySet (ops.carry_set), got {type(set).__name__}')
+    img, yuv, B = _image(what, source, layout, 'bt601', False, False)
+    _state_check(_CARRY_STATE, state, (), what)
+    S = state.shape[0]
+    if B % S or (frames_per_stream is not None and int(frames_per_stream) * S != B):
+        raise ValueError(f'{what}: {B} frames are not F frames of each of {S} streams')
+    F = B // S
+    mask = list(key_mask)
+    if len(mask) != F:
+        raise ValueError(f'{what}: a key mask of {F} entries expected, got {len(mask)}')
+    first = carry_first(mask, set.every)
+    K = sum(bool(k) for k in mask)
+    key = key_records
+    if isinstance(key, dict):
+        key = _record_buffer(what, key)
+    if key is None:
+        if K:
+            raise ValueError(f'{what}: the call has {K} key frames per stream and no key records')
+        if records is None:
+            raise ValueError(f'{what}: without key records, `records` says the record width')
+        words = records.shape[-1]
+    else:
+        if not isinstance(key, torch.Tensor) or key.dtype != torch.int32 or key.dim() != 2 or key.shape[1] not in (_lib.REC_WORDS, _lib.REC_ROT_WORDS):
+            raise ValueError(f'{what}: int32 key records [S*K, {_lib.REC_WORDS} | {_lib.REC_ROT_WORDS}] expected')
+        if key.shape[0] != S * K:
+            raise ValueError(f'{what}: {S * K} key records ({S} streams x {K} key frames) expected, got {key.shape[0]}')
+        if K and (key.stride(1) != 1 or key.stride(0) % 4 or key.stride(0) < key.shape[1]):
+            key = key.contiguous()
+        words = key.shape[1]
+    dev = _same_device(what, img, [state, key, shift, records])
+    if shift is not None:
+        if not isinstance(shift, torch.Tensor) or shift.dtype != torch.int32 or tuple(shift.shape) != (S, F, 4) or not shift.is_contiguous():
+            raise ValueError(f'{what}: shift is a contiguous int32 tensor [{S}, {F}, 4] (motion_frames), got '
+                             f'{tuple(shift.shape) if isinstance(shift, torch.Tensor) else type(shift).__name__}')
+    if records is None:
+        records = torch.empty((B, words), dtype=torch.int32, device=dev)
+    if not isinstance(records, torch.Tensor) or records.dtype != torch.int32 or tuple(records.shape) != (B, words) or not records.is_contiguous() \
+            or words not in (_lib.REC_WORDS, _lib.REC_ROT_WORDS):
+        raise ValueError(f'{what}: records is a contiguous int32 tensor [{B}, {words}]')
+    planes = out_planes(what, out, {'how': ((S, F, _lib.CARRY_SLOTS), torch.int32), 'offset': ((S, F, _lib.CARRY_SLOTS, 2), torch.int32),
+                                    'sad': ((S, F, _lib.CARRY_SLOTS, 2), torch.int32)}, dev)
+    ws = torch.empty((S, _lib.CARRY_SLOTS, 8), dtype=torch.int32, device=dev)
+    _launch_on_image(what, img, yuv, 'mydet_carry_records_rgb_u8', 'mydet_carry_records_yuv420', S, ctypes.byref(set), first,
+                     _ptr(key) if K else None, key.stride(0) if K else 0, 4 if words == _lib.REC_WORDS else 5, _ptr(state),
+                     None if shift is None else _ptr(shift), _ptr(ws), _ptr(records), _ptr(planes['how']), _ptr(planes['offset']),
+                     _ptr(planes['sad']))
+    res = record_views(records)
+    res.update(how=planes['how'], offset=planes['offset'], sad=planes['sad'])
+    return res
+
+
 def bboxes_iou(a, b, xyxy=False):
     require_gpu(a, 'bboxes_iou')
     a, b = a.contiguous().float(), b.contiguous().float()
