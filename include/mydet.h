@@ -1578,7 +1578,8 @@ int mydet_crop_boxes_yuv420(const mydet_yuv420_src *src, int B, int H, int W,
  *   MYDET_E_BADARG: as mydet_track_frames_motion_f32, and a null or misaligned appear, desc, appear_state, out_sim or out_how;
  *   gate or reid outside 0..MYDET_APPEAR_SIM_MAX; alpha outside 1..256; reach negative or not finite; update_thres NaN.
  *   MYDET_E_UNSUPP: MYDET_TRACK_ASSIGN_OPTIMAL (the solver forms its costs on the fly and would recompute S inside its inner
- *   loop).  mydet_track_appear_state_words is 0 for a max_tracks the tracker refuses. */
+ *   loop: mydet_track_frames_appear_optimal_f32 below computes S ahead of the solve and fuses it into the cost).
+ *   mydet_track_appear_state_words is 0 for a max_tracks the tracker refuses. */
 #define MYDET_APPEAR_BINS    128
 #define MYDET_APPEAR_SAMPLES 512
 #define MYDET_APPEAR_SIM_MAX 131072      /* 256 * MYDET_APPEAR_SAMPLES */
@@ -1600,6 +1601,41 @@ int mydet_track_frames_appear_f32(const int32_t *records, int64_t stream_stride_
                                   int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
                                   const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
                                   int32_t *out_sim, int32_t *out_how, void *stream);
+
+/* Appearance in the optimal assignment (mydet_track_frames_appear_optimal_f32): mydet_track_frames_appear_f32 with
+ *   weight   0..256, the share of the appearance in the fused affinity below;
+ *   sim_ws   DEVICE int32, S * mydet_track_appear_ws_words(max_tracks) words (512 * max_tracks per stream), 16-byte aligned,
+ *            caller-owned; nothing is assumed about its content at the start.
+ * It takes assoc->assign == MYDET_TRACK_ASSIGN_OPTIMAL only.  Every rule of mydet_track_frames_appear_f32 holds word for word --
+ * predict with the camera shift, update, the template update at update_thres, retire, births, out_how, out_sim (S of the matched
+ * pair with the template as it was before the update), bad-class frames -- except the associate step, which is the optimal one
+ * of mydet_track_assoc: the same rows, columns, dummies, solver and tie rule, one band or two.  Only the cost of a real column
+ * changes.  With q = (int)floorf(iou * 65536.0f), S = S(j, d) with the template before this frame's update, and a = S >> 1
+ * (0..65536), for a pair (row i = detection d, column j), all in integers:
+ *   eligible   as in mydet_track_assoc (the track is live, not taken by an earlier stage, of the detection's class, passes the
+ *              stage-2 missed == 1 rule, iou > the stage's threshold), and it passes the gate: gate == 0, or has[j] == 0, or
+ *              S >= gate;
+ *   affinity   m = q when has[j] == 0, else m = ((256 - weight) * q + weight * a) >> 8;
+ *   cost       65536 - m when eligible, 131072 when not, 65536 on a dummy column.
+ * Re-identification (reid > 0) keeps its rule: the rank-order walk after the stages, the largest S wins, the lowest slot on a
+ * tie, how = 3.  It runs behind the solve exactly as it runs behind the walk.
+ * With weight == 0, gate == 0 and reid == 0 every tracker output and every word of the tracker state are those of
+ * mydet_track_frames_motion_f32 with the same optimal assoc.
+ * The workspace.  S is computed once per pair, by the whole workgroup, between predict and the solve; the solver's cost reads
+ *   one word of it.  After a launch, for each stream whose last frame is not a bad-class frame, with n that frame's detections
+ *   and MT = max_tracks: sim_ws[d * MT + j] == S(j, d), with the templates as they were before that frame's update, for every
+ *   NEEDED pair (d < n, j): track j is live after predict, has[j] == 1, track j has the class of d, iou > the threshold of d's
+ *   band, and for a low-band d missed == 1.  None of that depends on the solver's outcome.  Every other word may hold anything.
+ * MYDET_E_BADARG: everything mydet_track_frames_appear_f32 answers so; weight outside 0..256; a null or misaligned sim_ws.
+ * MYDET_E_UNSUPP: MYDET_TRACK_ASSIGN_GREEDY (the walk's key stays IoU-major), and max_tracks above MYDET_TRACK_MAX_TRACKS.
+ * Nothing is launched and no buffer is touched on either.  mydet_track_appear_ws_words is 0 for a max_tracks the tracker refuses. */
+int64_t mydet_track_appear_ws_words(int max_tracks);
+int mydet_track_frames_appear_optimal_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                          int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                          float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                          int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
+                                          const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
+                                          int32_t *out_sim, int32_t *out_how, int weight, int32_t *sim_ws, void *stream);
 
 /* Key frames: the detector runs on every n-th frame only, and the boxes of a key frame are carried through the frames that follow
  * by matching their pixels (csrc/carry.hip), so that the tracker still gets one record per frame.  Everything after one conversion

@@ -93,6 +93,9 @@ SIGNATURES = {
     'mydet_track_appear_state_words': [c_int],
     'mydet_track_frames_appear_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_track_appear_ws_words': [c_int],
+    'mydet_track_frames_appear_optimal_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                              c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr],
     'mydet_appear_boxes_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr],
     'mydet_appear_boxes_yuv420': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr],
     'mydet_motion_default_reduce': [c_int, c_int],
@@ -170,7 +173,7 @@ SIGNATURES = {
 RETURNS_I64 = {'mydet_wino_weights_floats', 'mydet_wino4_weights_floats', 'mydet_wino4_workspace_bytes', 'mydet_split_bf16_elems',
                'mydet_merge_tile_records_scratch_bytes', 'mydet_fuse_view_records_scratch_bytes', 'mydet_track_state_words', 'mydet_mot_scratch_bytes', 'mydet_zones_state_words',
                'mydet_redact_workspace_bytes', 'mydet_trails_state_words', 'mydet_motion_state_words', 'mydet_motion_workspace_bytes',
-               'mydet_track_appear_state_words', 'mydet_carry_state_words'}
+               'mydet_track_appear_state_words', 'mydet_carry_state_words', 'mydet_track_appear_ws_words'}
 
 # detection record layout (MYDET_REC_* of include/mydet.h), in int32 words
 REC_TOPK = 512

@@ -911,7 +911,10 @@ class Detector():
         central 0.75 of the box, a 4 x 4 x 4 colour histogram for its upper and one for its lower half --, and the tracker launch
         (mydet_track_frames_appear_f32) keeps a template per track, offers an IoU match only when the histogram intersection
         reaches `gate`, and gives a detection that would start a track to the most similar lost track within `reach` instead
-        when it reaches `reid`.  No host synchronisation is added; appearance.last has desc, sim and how.  Every frame method
+        when it reaches `reid`.  An Appearance(weight=...) runs with a tracker of assign='optimal' instead (a greedy one is the
+        ValueError then): each stage is one minimum-cost assignment on a fused IoU-and-similarity cost
+        (mydet_track_frames_appear_optimal_f32), the gate and the re-identification as before.
+        No host synchronisation is added; appearance.last has desc, sim and how.  Every frame method
         that takes tracker= takes appearance=; without it every call is bit for bit what it was.
         keyframes: None, or a mydetection_amd.api.KeyFrames (with tracker= only: ValueError otherwise) to run the network on every
         n-th frame of a stream only.  Its counter says which frames of the call are key frames (host arithmetic, calls of any
@@ -962,7 +965,8 @@ class Detector():
 
     @staticmethod
     def _pop_appearance(kwargs, tracker):
-        """As _pop_companion, and a ValueError with a tracker whose assignment is 'optimal'."""
+        """As _pop_companion, and a ValueError with a tracker whose assignment is not the one the object runs with: 'greedy'
+        without a weight, 'optimal' with one."""
         appearance = Detector._pop_companion(kwargs, 'appearance', tracker)
         if appearance is not None:
             appearance.check_tracker(tracker)
@@ -1000,11 +1004,12 @@ class Detector():
         width = 5 if 'angle' in rec else 4
         state = tracker.bind(frame_hw, width, rec['records'].device)
         params = tracker.params(frame_hw, tracker.resolve_match(self.model.bb_format), conf_thres)
-        assoc, appear = tracker.assoc(conf_thres), None
+        assoc, appear, fused = tracker.assoc(conf_thres), None, {}
         if appearance is not None:
             birth = max(params.new_thres, assoc.high_thres) if assoc is not None and assoc.bands else params.new_thres
             appear = appearance[0].run(*appearance[1].image(), rec, tracker, frame_hw, birth)
-        out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks, assoc=assoc, shift=shift, appear=appear)
+            fused = appearance[0].launch_args()
+        out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks, assoc=assoc, shift=shift, appear=appear, **fused)
         if appearance is not None:
             appearance[0].took(out)
         zout = None if zones is None else zones.run(out, tracker, frame_hw)

@@ -57,6 +57,10 @@ struct TrackAppearArgs : TrackArgs {
     int32_t *astate;                  // per stream: has [MT], then tmpl [128][MT] (bin-major: the lanes of a wave read adjacent words)
     int64_t astate_words;
     int32_t *osim, *ohow;
+#ifdef MYDET_TRACK_APPEAR_OPTIMAL                                     // mydet_track_frames_appear_optimal_f32 only
+    int32_t *sim_ws;                  // per stream: S(j, d) at sim_ws[d * MT + j], KMAX * MT words
+    int weight;                       // 0..256: the share of the appearance in the fused affinity
+#endif
 };
 template <bool APPEAR>
 using TrackKernelArgs = std::conditional_t<APPEAR, TrackAppearArgs, TrackArgs>;
@@ -70,6 +74,10 @@ struct AssocLds {
     int32_t tmissed[TMAX];            // missed after predict (>= 1), or -1 for a slot that is not live
     int32_t tmd[TMAX];                // the record slot a track took, or -1
     int32_t rowd[KMAX], rowp[KMAX];   // a stage's rows: record slot and rank
+};
+// The optimal assignment with an appearance publishes `has` too: the similarity phase and the cost read other tracks' flags
+struct AssocAppearLds : AssocLds {
+    int32_t thas[TMAX];
 };
 // An upper bound of track_kernel's static arrays (33 - 37 KiB).  The opt-in asks for the dynamic part plus this, so the request
 // covers the kernel's whole LDS whether the runtime holds the limit against the dynamic part alone or against the sum.
@@ -103,6 +111,24 @@ struct AssocCost {
         }
         if (!(iou > thr)) return ASSOC_INELIGIBLE;                 // a NaN (0/0) is never eligible
         return MOT_ONE - (int64_t)(int)floorf(iou * 65536.0f);
+    }
+};
+
+// The fused cost (include/mydet.h: mydet_track_frames_appear_optimal_f32): AssocCost's, then the gate and the affinity m from ONE
+// word of the workspace the similarity phase filled.  An eligible pair of AssocCost is MOT_ONE - q, so q comes back out of it.
+template <bool ROT>
+struct AssocAppearCost {
+    AssocCost<ROT> iou;
+    const int32_t *thas;              // has[j] before this frame's update
+    const int32_t *ws;                // the stream's S: ws[d * MT + j]
+    int gate, weight;
+    __device__ __forceinline__ int64_t operator()(int i, int j) const {
+        const int64_t c = iou(i, j);
+        if (j >= iou.MT || c == ASSOC_INELIGIBLE || !thas[j]) return c;
+        const int sv = ws[iou.A->rowd[i] * iou.MT + j];
+        if (gate > 0 && sv < gate) return ASSOC_INELIGIBLE;
+        const int q = (int)(MOT_ONE - c);
+        return MOT_ONE - (int64_t)(((256 - weight) * q + weight * (sv >> 1)) >> 8);
     }
 };
 
@@ -149,10 +175,88 @@ __device__ __forceinline__ int appear_sim(const int32_t *tm, int MT, const uint1
     return s;
 }
 
+// The similarity phase of the fused cost, on every wave of the workgroup between predict and the solve: S(j, d) of every needed
+// pair (include/mydet.h: the workspace of mydet_track_frames_appear_optimal_f32) into ws[d * MT + j].  A wave takes every
+// nwave-th detection and walks the track slots 64 at a time: the need test is lane-per-track with the IoU of the walk, operation
+// for operation, and a ballot picks the form of the sum.  Dense (>= APPEAR_DENSE lanes need their pair): lanes own tracks, every
+// lane sums its own column -- the 64 template words of a bin are adjacent, one load serves the wave.  Sparse: lanes own bins,
+// two each, for up to four pairs at a time, and a shuffle tree adds them: one round of loads per four pairs instead of a
+// chain of 128.  Both are the same integer sum.
+constexpr int APPEAR_DENSE = 16;
+template <bool ROT>
+__device__ __forceinline__ void appear_sim_phase(const float (*g)[KMAX], const float *sc, const int64_t *dcl, const AssocAppearLds &A, int n,
+                                                 int MT, const mydet_track_assoc &as, float match_thres, const int32_t *tmpl,
+                                                 const uint16_t *dframe, int32_t *ws, int lane, int wave, int nwave) {
+    for (int d0 = wave; d0 < n; d0 += nwave) {
+        const int d = __builtin_amdgcn_readfirstlane(d0);
+        float thr = match_thres;
+        bool second = false;
+        if (as.bands) {
+            const float s = sc[d];
+            if (!(s >= as.high_thres)) {
+                if (!(s >= as.low_thres && s < as.high_thres)) continue;      // in no band: no pair of it is needed
+                thr = as.low_match_thres;
+                second = true;
+            }
+        }
+        const uint16_t *dr = dframe + (int64_t)d * ABINS;
+        const int dlo = (int)dr[lane] << 8, dhi = (int)dr[lane + 64] << 8;
+        const int64_t dc = dcl[d];
+        for (int j0 = 0; j0 < MT; j0 += 64) {
+            const int j = j0 + lane;                                   // < blockDim.x: every thread published its slot
+            const int tmj = A.tmissed[j];
+            bool need = tmj >= 0 && A.thas[j] != 0 && A.tcls[j] == dc && (!second || tmj == 1);
+            if (need) {
+                float iou;
+                if constexpr (ROT) {
+                    const rotiou::Box bi{g[0][d], g[1][d], g[2][d], g[3][d], g[4][d], g[5][d], g[6][d]};
+                    const rotiou::Box bj{A.t[0][j], A.t[1][j], A.t[2][j], A.t[3][j], A.t[4][j], A.t[5][j], A.t[6][j]};
+                    iou = rotiou::rot_iou(bi, bj);
+                } else {
+                    const float xx1 = fmaxf(g[0][d], A.t[0][j]), yy1 = fmaxf(g[1][d], A.t[1][j]);
+                    const float xx2 = fminf(g[2][d], A.t[2][j]), yy2 = fminf(g[3][d], A.t[3][j]);
+                    const float ww = fmaxf(0.0f, xx2 - xx1), hh = fmaxf(0.0f, yy2 - yy1);
+                    const float inter = ww * hh;
+                    iou = inter / (g[4][d] + A.t[4][j] - inter);
+                }
+                need = iou > thr;                                      // a NaN (0/0) is never needed
+            }
+            unsigned long long bal = __ballot(need);
+            if (__popcll(bal) >= APPEAR_DENSE) {
+                if (need) ws[d * MT + j] = appear_sim(tmpl + j, MT, dr);
+                continue;
+            }
+            while (bal) {
+                int jj[4], v[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    jj[k] = bal ? j0 + __ffsll((long long)bal) - 1 : -1;
+                    bal &= bal - 1ull;                                 // 0 stays 0
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    v[k] = 0;
+                    if (jj[k] >= 0) v[k] = min(tmpl[lane * MT + jj[k]], dlo) + min(tmpl[(lane + 64) * MT + jj[k]], dhi);
+                }
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[k] += __shfl_xor(v[k], off, 64);
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (lane == k && jj[k] >= 0) ws[d * MT + jj[k]] = v[k];
+            }
+        }
+    }
+}
+
 template <int BW, bool ROT, int MODE, bool APPEAR>
 __global__ __launch_bounds__(TMAX) void track_kernel(const TrackKernelArgs<APPEAR> a) {
     static_assert(!ROT || BW == 5, "the rotated IoU needs the angle column");
-    static_assert(!APPEAR || MODE != ASSOC_OPTIMAL, "the appearance runs with the greedy walk only");
+#ifndef MYDET_TRACK_APPEAR_OPTIMAL
+    static_assert(!APPEAR || MODE != ASSOC_OPTIMAL, "the fused cost is the instance of track_appear_optimal.hip");
+#endif
     extern __shared__ __align__(16) unsigned char track_dyn[];     // AssocLds (ASSOC_OPTIMAL only)
     __shared__ float s_z[5][KMAX];                    // the frame's detections: cx, cy, w, h, angle (0 for BW = 4)
     __shared__ float s_g[ROT ? 7 : 5][KMAX];          // pair-test planes: x1, y1, x2, y2, area | the seven fields of rotiou::Box
@@ -201,6 +305,13 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackKernelArgs<APPEA
         int32_t *as = a.astate + (int64_t)s * a.astate_words;
         tm = as + MT + tid;
         if (slot_ok) has = as[tid];
+    }
+    // the fused cost: the stream's workspace and its whole template, which the similarity phase reads across the slots
+    [[maybe_unused]] int32_t *ws = nullptr;
+    [[maybe_unused]] const int32_t *tmpl = nullptr;
+    if constexpr (APPEAR && MODE == ASSOC_OPTIMAL) {
+        ws = a.sim_ws + (int64_t)s * KMAX * MT;
+        tmpl = a.astate + (int64_t)s * a.astate_words + MT;
     }
     const float one_minus_m = 1.0f - P.momentum;
 
@@ -303,6 +414,15 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackKernelArgs<APPEA
             if (any_live) {
                 A.t[0][tid] = t0; A.t[1][tid] = t1; A.t[2][tid] = t2; A.t[3][tid] = t3; A.t[4][tid] = t4; A.t[5][tid] = t5; A.t[6][tid] = t6;
                 A.tcls[tid] = cls; A.tmissed[tid] = live ? missed : -1; A.tmd[tid] = -1;
+                if constexpr (APPEAR) {
+                    // The phase reads template columns that other lanes and waves wrote in steps 4, 5 and 6 of the frame
+                    // before: the barrier at the top of the frame released those global stores at workgroup scope.  What it
+                    // stores into ws, wavefront 0 reads in the solve: the barrier below.
+                    AssocAppearLds &AA = *reinterpret_cast<AssocAppearLds *>(track_dyn);
+                    AA.thas[tid] = has;
+                    __syncthreads();
+                    appear_sim_phase<ROT>(s_g, s_sc, s_cl, AA, n, MT, a.as, P.match_thres, tmpl, dframe, ws, lane, wave, nwave);
+                }
                 __syncthreads();
                 if (wave == 0) {
                     const HungWaveSync wsync;
@@ -329,7 +449,13 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackKernelArgs<APPEA
                         }
                         wsync();
                         if (nr > 0) {
-                            const AssocCost<ROT> cost = {s_g, s_cl, &A, MT, stage == 1, stage == 1 ? a.as.low_match_thres : P.match_thres};
+                            const AssocCost<ROT> iou_cost = {s_g, s_cl, &A, MT, stage == 1, stage == 1 ? a.as.low_match_thres : P.match_thres};
+                            const auto cost = [&] {
+                                if constexpr (APPEAR)
+                                    return AssocAppearCost<ROT>{iou_cost, reinterpret_cast<AssocAppearLds *>(track_dyn)->thas, ws, a.ap.gate, a.weight};
+                                else
+                                    return iou_cost;
+                            }();
                             hung_solve(A.h, nr, MT + nr, cost, lane, wsync);
                             for (int j = lane; j < MT; j += 64) {  // a row on a real column; the costs first: they read tmd
                                 const int i = A.h.p[j];
@@ -346,6 +472,8 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackKernelArgs<APPEA
                 }
                 __syncthreads();
                 md = A.tmd[tid];
+                if constexpr (APPEAR)
+                    if (md >= 0) how = a.as.bands && !(s_sc[md] >= a.as.high_thres) ? 2 : 1;
             }
         } else if (any_live) {
             for (int p = 0; p < n; ++p) {
@@ -411,7 +539,9 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackKernelArgs<APPEA
                 for (int p0 = 0; p0 < n64; p0 += nthr) {
                     const int p = p0 + tid;
                     bool flag = p < n && s_dmatch[p] < 0 && s_sc[s_order[p]] >= P.new_thres;
-                    if constexpr (MODE != ASSOC_GREEDY) flag = flag && s_sc[s_order[p]] >= a.as.high_thres;
+                    if constexpr (MODE == ASSOC_OPTIMAL) {         // bands are a launch argument there
+                        if (a.as.bands) flag = flag && s_sc[s_order[p]] >= a.as.high_thres;
+                    } else if constexpr (MODE != ASSOC_GREEDY) flag = flag && s_sc[s_order[p]] >= a.as.high_thres;
                     const unsigned long long bits = __ballot(flag);
                     if (lane == 0 && p < KMAX) s_bmask[p >> 6] = bits;
                 }
@@ -448,7 +578,11 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackKernelArgs<APPEA
                 }
             }
             // S of the matched pair, before the template moves (0 for a track without an appearance: its template is zero)
-            if (md >= 0) simv = appear_sim(tm, MT, dframe + (int64_t)md * ABINS);
+            if constexpr (MODE == ASSOC_OPTIMAL) {                 // a pair the solve matched was needed: the phase has its S
+                if (md >= 0) simv = how == 3 ? appear_sim(tm, MT, dframe + (int64_t)md * ABINS) : has ? ws[md * MT + tid] : 0;
+            } else {
+                if (md >= 0) simv = appear_sim(tm, MT, dframe + (int64_t)md * ABINS);
+            }
         }
 
         // 4. update the matched tracks (KFTracklet.update)
@@ -592,8 +726,9 @@ __global__ __launch_bounds__(256) void track_reset_kernel(int32_t *state, int64_
 
 }  // namespace
 
-// This file is two translation units (the Makefile builds track_appear.hip, which is this file under MYDET_TRACK_APPEAR): the
-// instances and entry points without an appearance here, the ones with it there.  One unit would do for the language, but
+// This file is three translation units (the Makefile builds track_appear.hip, which is this file under MYDET_TRACK_APPEAR, and
+// track_appear_optimal.hip, which adds MYDET_TRACK_APPEAR_OPTIMAL): the instances and entry points without an appearance here,
+// the greedy ones with it in the second, the optimal assignment on the fused cost in the third.  One unit would do for the language, but
 // the compiler's inlining choices inside an instance depend on how many instances share its helpers, and the instances that
 // were here before the appearance must stay the code they were (profiles/appearance.md has both builds side by side).
 #ifndef MYDET_TRACK_APPEAR
@@ -620,8 +755,8 @@ int track_launch(const TrackKernelArgs<APPEAR> &a, dim3 grid, dim3 block, hipStr
     size_t dyn = 0;
     if constexpr (MODE == ASSOC_OPTIMAL) {
         static unsigned long long opted = 0ull;                    // one bit per device ordinal
-        dyn = sizeof(AssocLds);
-        const int st = mydet_lds_opt_in(opted, track_kernel<BW, ROT, MODE, APPEAR>, (int)sizeof(AssocLds) + ASSOC_STATIC_LDS);
+        dyn = APPEAR ? sizeof(AssocAppearLds) : sizeof(AssocLds);
+        const int st = mydet_lds_opt_in(opted, track_kernel<BW, ROT, MODE, APPEAR>, (int)dyn + ASSOC_STATIC_LDS);
         if (st) return st;
     }
     hipLaunchKernelGGL((track_kernel<BW, ROT, MODE, APPEAR>), grid, block, dyn, stream, a);
@@ -689,11 +824,31 @@ extern "C" int mydet_track_frames_motion_f32(const int32_t *records, int64_t str
 }
 
 #else
+#ifndef MYDET_TRACK_APPEAR_OPTIMAL
 extern "C" int64_t mydet_track_appear_state_words(int max_tracks) {
     if (max_tracks < 1 || max_tracks > MYDET_TRACK_MAX_TRACKS) return 0;
     return ((int64_t)(1 + MYDET_APPEAR_BINS) * max_tracks + 3) / 4 * 4;
 }
+#endif
 
+namespace {
+
+// The argument rules of the appearance that both of its entry points share, behind track_setup's; fills the rest of `a`
+int track_appear_setup(TrackAppearArgs &a, int max_tracks, const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
+                       int32_t *out_sim, int32_t *out_how) {
+    if (!appear || !desc || !appear_state || !out_sim || !out_how) return MYDET_E_BADARG;
+    if (((uintptr_t)desc & 15) || ((uintptr_t)appear_state & 15) || ((uintptr_t)out_sim & 3) || ((uintptr_t)out_how & 3)) return MYDET_E_BADARG;
+    if (appear->gate < 0 || appear->gate > MYDET_APPEAR_SIM_MAX || appear->reid < 0 || appear->reid > MYDET_APPEAR_SIM_MAX) return MYDET_E_BADARG;
+    if (appear->alpha < 1 || appear->alpha > 256) return MYDET_E_BADARG;
+    if (!track_finite(appear->reach) || appear->reach < 0.0f || appear->update_thres != appear->update_thres) return MYDET_E_BADARG;
+    a.ap = *appear; a.desc = desc; a.astate = appear_state; a.astate_words = mydet_track_appear_state_words(max_tracks);
+    a.osim = out_sim; a.ohow = out_how;
+    return 0;
+}
+
+}  // namespace
+
+#ifndef MYDET_TRACK_APPEAR_OPTIMAL
 extern "C" int mydet_track_frames_appear_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
                                              int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
                                              float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
@@ -704,18 +859,39 @@ extern "C" int mydet_track_frames_appear_f32(const int32_t *records, int64_t str
     const int code = track_setup(a, records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
                                  out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift);
     if (code) return code;
-    if (!appear || !desc || !appear_state || !out_sim || !out_how) return MYDET_E_BADARG;
-    if (((uintptr_t)desc & 15) || ((uintptr_t)appear_state & 15) || ((uintptr_t)out_sim & 3) || ((uintptr_t)out_how & 3)) return MYDET_E_BADARG;
-    if (appear->gate < 0 || appear->gate > MYDET_APPEAR_SIM_MAX || appear->reid < 0 || appear->reid > MYDET_APPEAR_SIM_MAX) return MYDET_E_BADARG;
-    if (appear->alpha < 1 || appear->alpha > 256) return MYDET_E_BADARG;
-    if (!track_finite(appear->reach) || appear->reach < 0.0f || appear->update_thres != appear->update_thres) return MYDET_E_BADARG;
-    if (assoc->assign != MYDET_TRACK_ASSIGN_GREEDY) return MYDET_E_UNSUPP;          // the solver forms its costs on the fly
-    a.ap = *appear; a.desc = desc; a.astate = appear_state; a.astate_words = mydet_track_appear_state_words(max_tracks);
-    a.osim = out_sim; a.ohow = out_how;
+    const int acode = track_appear_setup(a, max_tracks, appear, desc, appear_state, out_sim, out_how);
+    if (acode) return acode;
+    if (assoc->assign != MYDET_TRACK_ASSIGN_GREEDY) return MYDET_E_UNSUPP;          // mydet_track_frames_appear_optimal_f32 has the fused cost
     const dim3 grid((unsigned)S), block((unsigned)((max_tracks + 63) / 64 * 64));
     if (assoc->bands) return track_launch_mode<ASSOC_GREEDY_BANDS, true>(a, box_width, grid, block, (hipStream_t)stream);
     return track_launch_mode<ASSOC_GREEDY, true>(a, box_width, grid, block, (hipStream_t)stream);
 }
+#else
+extern "C" int64_t mydet_track_appear_ws_words(int max_tracks) {
+    if (max_tracks < 1 || max_tracks > MYDET_TRACK_MAX_TRACKS) return 0;
+    return (int64_t)MYDET_REC_TOPK * max_tracks;
+}
+
+extern "C" int mydet_track_frames_appear_optimal_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S,
+                                                     int F, int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                                     float *out_box, float *out_score, int64_t *out_class, int64_t *out_id,
+                                                     int32_t *out_missed, int32_t *out_count, int32_t *out_dropped,
+                                                     const mydet_track_assoc *assoc, const int32_t *shift, const mydet_track_appear *appear,
+                                                     const uint16_t *desc, int32_t *appear_state, int32_t *out_sim, int32_t *out_how,
+                                                     int weight, int32_t *sim_ws, void *stream) {
+    TrackAppearArgs a;
+    const int code = track_setup(a, records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
+                                 out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift);
+    if (code) return code;
+    const int acode = track_appear_setup(a, max_tracks, appear, desc, appear_state, out_sim, out_how);
+    if (acode) return acode;
+    if (weight < 0 || weight > 256 || !sim_ws || ((uintptr_t)sim_ws & 15)) return MYDET_E_BADARG;
+    if (assoc->assign != MYDET_TRACK_ASSIGN_OPTIMAL) return MYDET_E_UNSUPP;         // the walk's key stays IoU-major
+    a.weight = weight; a.sim_ws = sim_ws;
+    const dim3 grid((unsigned)S), block((unsigned)((max_tracks + 63) / 64 * 64));
+    return track_launch_mode<ASSOC_OPTIMAL, true>(a, box_width, grid, block, (hipStream_t)stream);
+}
+#endif
 
 #endif
 

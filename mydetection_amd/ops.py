@@ -1767,7 +1767,8 @@ def track_state_views(state, max_tracks=None):
     return out
 
 
-def track_frames(records, tracker_state, params, frames_per_stream=None, max_tracks=None, out=None, assoc=None, shift=None, appear=None):
+def track_frames(records, tracker_state, params, frames_per_stream=None, max_tracks=None, out=None, assoc=None, shift=None, appear=None,
+                 appear_weight=None, appear_ws=None):
     """Advance S streams by F frames each in ONE launch (include/mydet.h: mydet_track_frames_f32, where the rules are).
     records: the detection records in frame coordinates -- an int32 tensor [S*F, words] (frame f of stream s in row s*F + f) or
     [S, F, words] with any strides along S and F that are multiples of 4 words, or the record_views dict of a [S*F, words]
@@ -1783,7 +1784,11 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     frames, uint16 [S*F,512,128] or [S,F,512,128] (appear_records, or any 128 bins that sum to at most 512 per row), and the
     int32 [S, words] state of appear_state, updated in place: the gate, the re-identification and the templates of
     mydet_track_frames_appear_f32 (greedy assignment only: a ValueError with assign 'optimal', before any launch).  The dict
-    then also holds sim and how, int32 [S,F,MT]."""
+    then also holds sim and how, int32 [S,F,MT].  appear_weight: None, or with appear= an int in 0..256 -- the optimal assignment
+    on the fused IoU-and-appearance cost of mydet_track_frames_appear_optimal_f32: m = ((256 - weight) * q + weight * (S >> 1)) >> 8.
+    It takes an assoc with assign 'optimal' (a greedy one is a ValueError before any launch) and appear_ws, the int32
+    [S, appear_ws_words(max_tracks)] tensor of appear_workspace, which afterwards holds S of the last frame's needed pairs at
+    [s, d * max_tracks + j]."""
     if not isinstance(params, _lib.TrackParams):
         raise TypeError(f'track_frames: params is a _lib.TrackParams (ops.track_params), got {type(params).__name__}')
     if assoc is not None and not isinstance(assoc, _lib.TrackAssoc):
@@ -1804,8 +1809,19 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     if appear is not None:
         if not isinstance(appear, (tuple, list)) or len(appear) != 3 or not isinstance(appear[0], _lib.TrackAppear):
             raise TypeError('track_frames: appear is (ops.appear_set(...), desc, appear_state) or None')
-        if assoc is not None and assoc.assign != _lib.TRACK_ASSIGN_GREEDY:
+        if appear_weight is None and assoc is not None and assoc.assign != _lib.TRACK_ASSIGN_GREEDY:
             raise ValueError("track_frames: the appearance runs with assign 'greedy' only (the optimal assignment forms its costs on the fly)")
+    if appear_weight is None:
+        if appear_ws is not None:
+            raise ValueError('track_frames: appear_ws is the workspace of the fused cost and goes with appear_weight')
+    else:
+        if appear is None:
+            raise ValueError('track_frames: appear_weight weighs the appearance of appear=(ops.appear_set(...), desc, appear_state)')
+        if isinstance(appear_weight, bool) or not isinstance(appear_weight, (int, np.integer)) or not 0 <= int(appear_weight) <= 256:
+            raise ValueError(f'track_frames: appear_weight is None or an int in 0..256, got {appear_weight!r}')
+        if assoc is None or assoc.assign != _lib.TRACK_ASSIGN_OPTIMAL:
+            raise ValueError("track_frames: the fused IoU-and-appearance cost (appear_weight) runs with assign 'optimal' only "
+                             '(the greedy walk keeps its IoU-major key)')
     if params.match == _lib.TRACK_MATCH_ROTATED and width != 5:
         raise ValueError("track_frames: match 'rotated' needs 'cxcywhd' records (the rotated record with its angle plane)")
     if records.dim() == 2:
@@ -1835,6 +1851,8 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
         _state_check(_APPEAR_STATE, astate, (mt,), 'track_frames')
         if astate.shape[0] != S or astate.device != dev:
             raise ValueError(f'track_frames: the appearance state must be [{S}, words] on {dev}')
+        if appear_weight is not None:
+            _workspace_check(appear_ws, S, mt, dev, 'track_frames')
     out = out_planes('track_frames', out, shapes, dev)
     if shift is not None:
         if (not isinstance(shift, torch.Tensor) or shift.dtype != torch.int32 or shift.numel() != S * F * 4 or shift.shape[-1] != 4 or
@@ -1843,7 +1861,12 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     t0 = TIMER.start() if TIMER else None
     args = (_ptr(records), records.stride(0), records.stride(1), S, F, width, ctypes.byref(params), mt, _ptr(tracker_state), _ptr(out['box']),
             _ptr(out['score']), _ptr(out['cls']), _ptr(out['id']), _ptr(out['missed']), _ptr(out['count']), _ptr(out['dropped']))
-    if appear is not None:
+    if appear is not None and appear_weight is not None:
+        name = 'mydet_track_frames_appear_optimal_f32'
+        code = _lib.lib().mydet_track_frames_appear_optimal_f32(*args, ctypes.byref(assoc), None if shift is None else _ptr(shift),
+                                                                ctypes.byref(aset), _ptr(desc), _ptr(astate), _ptr(out['sim']),
+                                                                _ptr(out['how']), int(appear_weight), _ptr(appear_ws), _stream())
+    elif appear is not None:
         name = 'mydet_track_frames_appear_f32'
         code = _lib.lib().mydet_track_frames_appear_f32(*args, ctypes.byref(track_assoc() if assoc is None else assoc),
                                                         None if shift is None else _ptr(shift), ctypes.byref(aset), _ptr(desc), _ptr(astate),
@@ -3700,6 +3723,26 @@ def appear_state(streams, max_tracks, device):
 def appear_reset_(state, max_tracks):
     """Clear an appearance state in place: every `has` flag and every template bin is 0 (the state's initial value)."""
     return _state_reset(_APPEAR_STATE, state, (max_tracks,))
+
+
+def appear_ws_words(max_tracks):
+    """int32 words of one stream's similarity workspace (mydet_track_appear_ws_words): 512 * max_tracks; host arithmetic only."""
+    return _lib.REC_TOPK * _max_tracks('tracker', max_tracks)
+
+
+def appear_workspace(streams, max_tracks, device):
+    """The workspace of the fused cost (track_frames' appear_ws): int32 [streams, appear_ws_words(max_tracks)], not initialised
+    -- the launch assumes nothing about its content."""
+    words = appear_ws_words(max_tracks)
+    return torch.empty((check_streams('appear_workspace', streams), words), dtype=torch.int32, device=device)
+
+
+def _workspace_check(ws, S, mt, dev, what):
+    words = appear_ws_words(mt)
+    if (not isinstance(ws, torch.Tensor) or ws.dtype != torch.int32 or tuple(ws.shape) != (S, words) or ws.device != dev or
+            not ws.is_contiguous()):
+        got = f'{ws.dtype} {tuple(ws.shape)} on {ws.device}' if isinstance(ws, torch.Tensor) else type(ws).__name__
+        raise ValueError(f'{what}: appear_ws must be the contiguous int32 [{S}, {words}] tensor of ops.appear_workspace on {dev}, got {got}')
 
 
 def appear_state_views(state, max_tracks):
