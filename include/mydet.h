@@ -869,7 +869,8 @@ int mydet_trails_frames(const float *box, const int64_t *id, const int64_t *cls,
  *   keeps every read inside the frame.
  * Result: (dx, dy) = the component-wise lower median of the block vectors, in whole pixels: content at p in the previous frame
  *   is at p + d in this one; valid = 1; n_valid = the number of valid blocks.  The first frame of a stream after a reset is
- *   (0, 0, 0, 0).  Not part of the rules: sub-pixel precision, rotation or zoom, masking detections out, motion beyond R k.
+ *   (0, 0, 0, 0).  Not part of these rules: masking detections out, motion beyond R k; rotation, zoom and sub-pixel shifts are
+ *   the similarity model's (mydet_motion_warp_frames_rgb_u8 below).
  * Out: out_shift int32 [S*F][4] = (dx, dy, valid, n_valid); out_blocks (may be NULL) int32 [S*F][nb][6] = (cdx, cdy, smin, smax,
  *   fdx, fdy), the block vector in (fdx, fdy); fields are zero where they are undefined (everything in a stream's first frame
  *   after a reset; fdx, fdy of an invalid block and of a frame without enough valid blocks).
@@ -893,7 +894,9 @@ typedef struct mydet_motion_set {
     int reduce;                          /* k: 2 | 4 | 8, or 0 for the default of the frame size */
     int search;                          /* R, reduced pixels */
     int min_texture, min_blocks;         /* min_blocks 0: max(2, ceil(nb / 8)) */
-    int reserved[4];
+    int reserved[4];                     /* read by mydet_motion_warp_frames_* only: [0] the model (MYDET_MOTION_MODEL_SIMILARITY), [1] the
+                                            tolerance, [2] max_zoom, [3] max_rotation, Q16, 0 for the defaults; mydet_motion_frames_*
+                                            ignore them, as they always did */
 } mydet_motion_set;
 int mydet_motion_default_reduce(int H, int W);
 int64_t mydet_motion_state_words(int H, int W, int k, int R);
@@ -904,6 +907,62 @@ int mydet_motion_frames_rgb_u8(const unsigned char *src, int B, int H, int W, in
                                int32_t *out_blocks, void *stream);
 int mydet_motion_frames_yuv420(const struct mydet_yuv420_src *src, int B, int H, int W, int S, const mydet_motion_set *set, int32_t *state,
                                void *ws, int64_t ws_bytes, int32_t *out_shift, int32_t *out_blocks, void *stream);
+
+/* Camera motion with rotation and zoom: a four-parameter similarity per frame, fitted to the block vectors of the estimator
+ * above (csrc/motion.hip: motion_fit_kernel), for a camera that yaws, rolls, zooms, climbs or descends -- there the block
+ * vectors left and right of the centre disagree and their median says little.  Everything is an integer; tests/_warp_ref.py
+ * restates the rules and the kernels equal it with == on every output and on the state.
+ *
+ * The luma, the reduced luma, the blocks, the coarse stage, block validity, min_blocks, the state (layout, reset, the
+ * two-calls-equal-one-call rule), the workspace, the frame sources and the errors are those of mydet_motion_frames_rgb_u8; a state
+ * may pass between the two families.  Three things differ.
+ * Refine stage: the window of a valid block sits at the block's OWN coarse vector c = (cdx, cdy) instead of the median D: for
+ *   (ey, ex) in [-k, k]^2 the SAD at (py + c.y k + ey, px + c.x k + ex), the same tie rule, (fdx, fdy) = c k + e.  |c| <= R as
+ *   |D| <= R, so the reads stay inside the frame: rows py + c.y k - k .. py + c.y k + k + P lie in [3k, (hr - 3) k], as P <= 8k
+ *   and 16 nby <= hr - 2R; columns alike.
+ * Fit, over the n valid blocks in ascending block index i.  Block i = by nbx + bx has the lattice point u_i = (bx, by), the
+ *   centre p_i = ((R + 16 bx + 8) k, (R + 16 by + 8) k), the half-pixel offset q_i = 2 p_i - (W, H) from the frame centre
+ *   c = (W/2, H/2), and the vector d_i = (fdx, fdy).  The model is p -> p + t + (M - I)(p - c), M - I = [[a, -b], [b, a]]; a, b,
+ *   t = (tx, ty) are Q16.  Every division is a floor division; (M - I)(p_i - c) in Q16 is m_i = ((a q.x - b q.y) >> 1,
+ *   (b q.x + a q.y) >> 1).
+ *   Start: h = n / 2; pair i with j = i + (n - h) for i < h; with dp = p_j - p_i, dd = d_j - d_i the pair gives
+ *     a_ij = ((dp . dd) << 16) / |dp|^2 and b_ij = ((dp.x dd.y - dp.y dd.x) << 16) / |dp|^2 (|dp|^2 > 0: blocks are distinct).
+ *     a, b = the lower medians over the pairs; tx, ty = the lower medians over i of (d_i << 16) - m_i.  No pair (n < 2): invalid.
+ *     A block with a foreign motion spoils the pair it is in, so the start tolerates foreign blocks up to a quarter of the
+ *     valid ones (half of the pairs), not up to a half.
+ *   Two rounds: the inliers are the blocks with |(d_i << 16) - t - m_i| <= tolerance in both components; m = their number;
+ *     fewer than 3: invalid.  With the sums over the inliers Su = sum u, Sd = sum d, Sq = sum q:
+ *       den = 16 k (m sum |u|^2 - |Su|^2)            (0: invalid; three distinct blocks never give it)
+ *       a = ((m sum (u . d) - Su . Sd) << 16) / den,  b = ((m sum (u.x d.y - u.y d.x) - (Su.x Sd.y - Su.y Sd.x)) << 16) / den
+ *       tx = ((Sd.x << 17) - (a Sq.x - b Sq.y)) / (2 m),  ty = ((Sd.y << 17) - (b Sq.x + a Sq.y)) / (2 m)
+ *     -- the least squares on centred coordinates with numerators and denominator scaled by m^2 / (16 k), and the t that makes
+ *     the model exact at the inliers' centroid.  n_inliers and the inlier mask are those of the second round.
+ *   int64 holds every intermediate: with n <= 1024, |u| < 512, |d| <= 136, |q| <= 32768 and |a|, |b| < 2^21 (|dd| / |dp| <= 272 / 32)
+ *     the largest are the least-squares numerator, below 2^55, and den, below 2^47.
+ * Derived: s_q = isqrt((65536 + a)^2 + b^2) (the floor of the root); u = (b << 16) / (65536 + a); deg_q = Q16 degrees of atan(u / 2^16)
+ *   = sign(u) ((|u| p) >> 24) with u2 = (u u) >> 16, p = c1 - ((u2 (c3 - ((u2 (c5 - ((u2 c7) >> 16))) >> 16))) >> 16) and
+ *   c1, c3, c5, c7 = 961263669, 320421223, 192252734, 137323381 = round(180 / pi / (1, 3, 5, 7) 2^24): within 8 units (0.00013
+ *   degrees) of the real arctangent of u / 2^16 on |u| <= 2^14; the floor of u is worth up to 58 more (0.001 degrees in all).  Invalid: |s_q - 65536| > max_zoom; 65536 + a <= 0; |u| > 2^14;
+ *   |deg_q| > max_rotation; |tx| or |ty| >= 2^24 (256 pixels, beyond any block vector; below it the tracker's float32 takes t exactly).
+ * Settings, the reserved words of mydet_motion_set: [0] = MYDET_MOTION_MODEL_SIMILARITY; [1] = tolerance, Q16 pixels, 0 for 2.0, at
+ *   most 16.0; [2] = max_zoom, Q16, 0 for 1/8, at most 1/4; [3] = max_rotation, Q16 degrees, 0 for 7.0, at most 14.0.
+ * Out: out_warp int32 [S*F][8] = (a, b, tx, ty, s_q, deg_q, valid, n_inliers), all zero where the frame is invalid (wherever
+ *   mydet_motion_frames_rgb_u8 reports valid 0, and the invalid exits above); out_shift int32 [S*F][4] = ((tx + 32768) >> 16,
+ *   (ty + 32768) >> 16, valid, n_valid), (0, 0, 0, n_valid) where invalid: the motion of the frame centre in whole pixels, for every
+ *   reader of a shift; out_blocks (may be NULL) as above, with (fdx, fdy) = c k + e for every valid block of a frame with at least
+ *   min_blocks valid blocks -- also where the fit then leaves by an invalid exit: the block vectors were made and stay written --
+ *   and zero for an invalid block and a frame with fewer valid blocks; out_inliers (may be NULL) int32 [S*F][nb], 1 for an inlier of the
+ *   second round of a valid frame.  A pure whole-pixel shift of the whole frame gives a = b = 0, s_q = 65536, deg_q = 0, t = shift << 16.
+ * MYDET_E_BADARG: as mydet_motion_frames_rgb_u8, and reserved[0] not MYDET_MOTION_MODEL_SIMILARITY, a setting out of range, a null
+ *   or misaligned out_warp, a misaligned out_inliers. */
+#define MYDET_MOTION_MODEL_SHIFT       0
+#define MYDET_MOTION_MODEL_SIMILARITY  1
+int mydet_motion_warp_frames_rgb_u8(const unsigned char *src, int B, int H, int W, int64_t src_img_bytes, int64_t src_row_bytes, int S,
+                                    const mydet_motion_set *set, int32_t *state, void *ws, int64_t ws_bytes, int32_t *out_shift,
+                                    int32_t *out_warp, int32_t *out_blocks, int32_t *out_inliers, void *stream);
+int mydet_motion_warp_frames_yuv420(const struct mydet_yuv420_src *src, int B, int H, int W, int S, const mydet_motion_set *set,
+                                    int32_t *state, void *ws, int64_t ws_bytes, int32_t *out_shift, int32_t *out_warp, int32_t *out_blocks,
+                                    int32_t *out_inliers, void *stream);
 
 /* The tracker with camera motion: mydet_track_frames_assoc_f32 with one more argument, `shift` (DEVICE, int32 [S*F][4] = (dx, dy,
  * valid, n_valid): out_shift of the estimator above for the same S and F; 4-byte aligned).  mydet_track_frames_assoc_f32 and
@@ -917,6 +976,28 @@ int mydet_track_frames_motion_f32(const int32_t *records, int64_t stream_stride_
                                   float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
                                   int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
                                   void *stream);
+
+/* The tracker with the similarity model: mydet_track_frames_motion_f32 with `warp` (DEVICE, int32 [S*F][8] = (a, b, tx, ty, s_q,
+ * deg_q, valid, n_inliers): out_warp of mydet_motion_warp_frames_rgb_u8 for the same S and F; 4-byte aligned) in the place of shift.
+ * Rule, float32 in this order (-ffp-contract=off), in a frame whose valid == 1, for every live track inside `predict`, after
+ * x += v and where the shift applies:
+ *   fa = (float)a * 2^-16, fb, ftx, fty alike (exact below 2^24);  ux = x[0] - img_w * 0.5f,  uy = x[1] - img_h * 0.5f
+ *   x[0] = x[0] + ftx;  x[1] = x[1] + fty
+ *   unless a == 0 and b == 0:   x[0] = x[0] + (fa * ux - fb * uy);  x[1] = x[1] + (fb * ux + fa * uy);
+ *                               v[0] = v0 + (fa * v0 - fb * v1);    v[1] = v1 + (fb * v0 + fa * v1)     (v0, v1 the old v[0], v[1])
+ *   unless s_q == 65536:        fs = (float)s_q * 2^-16;  x[2], x[3], v[2], v[3] each times fs
+ *   box_width 5, unless deg_q == 0:   x[4] = x[4] + (float)deg_q * 2^-16, before the reduction to [0, 180)
+ * A positive b turns the x axis towards y, the direction in which a record's angle counts.  Covariances are untouched (a
+ * stated simplification).  The identity parts are skipped, so a row that is a pure whole-pixel shift (a = b = 0, s_q = 65536,
+ * deg_q = 0, t a multiple of 65536) gives the bits of mydet_track_frames_motion_f32 with that shift; warp = NULL gives the bits
+ * of mydet_track_frames_assoc_f32.  An invalid row and a bad-class frame leave the prediction, or the state, alone.
+ * mydet_track_frames_appear_warp_f32 and mydet_track_frames_appear_optimal_warp_f32 (declared with their shift siblings' argument
+ * lists, warp in the place of shift) are the same for the appearance entry points. */
+int mydet_track_frames_warp_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *warp,
+                                void *stream);
 
 /* Winograd F(4x4,3x3) form of the same 3x3 stride-1 pad-1 conv + BN + act (+ residual) as mydet_conv2d_wino_f32
  * (4x fewer multiplies than the direct form; used for the deep layers with chip-filling grids).  `u` = the
@@ -1601,6 +1682,13 @@ int mydet_track_frames_appear_f32(const int32_t *records, int64_t stream_stride_
                                   int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
                                   const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
                                   int32_t *out_sim, int32_t *out_how, void *stream);
+/* ... with the similarity model: `warp` of mydet_track_frames_warp_f32 in the place of shift, the same rule */
+int mydet_track_frames_appear_warp_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                       int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                       float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                       int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *warp,
+                                       const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
+                                       int32_t *out_sim, int32_t *out_how, void *stream);
 
 /* Appearance in the optimal assignment (mydet_track_frames_appear_optimal_f32): mydet_track_frames_appear_f32 with
  *   weight   0..256, the share of the appearance in the fused affinity below;
@@ -1636,6 +1724,14 @@ int mydet_track_frames_appear_optimal_f32(const int32_t *records, int64_t stream
                                           int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
                                           const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
                                           int32_t *out_sim, int32_t *out_how, int weight, int32_t *sim_ws, void *stream);
+/* ... with the similarity model: `warp` of mydet_track_frames_warp_f32 in the place of shift, the same rule */
+int mydet_track_frames_appear_optimal_warp_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S,
+                                               int F, int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                               float *out_box, float *out_score, int64_t *out_class, int64_t *out_id,
+                                               int32_t *out_missed, int32_t *out_count, int32_t *out_dropped,
+                                               const mydet_track_assoc *assoc, const int32_t *warp, const mydet_track_appear *appear,
+                                               const uint16_t *desc, int32_t *appear_state, int32_t *out_sim, int32_t *out_how,
+                                               int weight, int32_t *sim_ws, void *stream);
 
 /* Key frames: the detector runs on every n-th frame only, and the boxes of a key frame are carried through the frames that follow
  * by matching their pixels (csrc/carry.hip), so that the tracker still gets one record per frame.  Everything after one conversion

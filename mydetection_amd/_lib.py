@@ -90,12 +90,18 @@ SIGNATURES = {
                                      c_ptr, c_ptr],
     'mydet_track_frames_motion_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_ptr, c_ptr],
+    'mydet_track_frames_warp_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                    c_ptr, c_ptr, c_ptr],
     'mydet_track_appear_state_words': [c_int],
     'mydet_track_frames_appear_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
+    'mydet_track_frames_appear_warp_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                           c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
     'mydet_track_appear_ws_words': [c_int],
     'mydet_track_frames_appear_optimal_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                               c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr],
+    'mydet_track_frames_appear_optimal_warp_f32': [c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                                   c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr],
     'mydet_appear_boxes_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr],
     'mydet_appear_boxes_yuv420': [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr],
     'mydet_motion_default_reduce': [c_int, c_int],
@@ -104,6 +110,9 @@ SIGNATURES = {
     'mydet_motion_reset': [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr],
     'mydet_motion_frames_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
     'mydet_motion_frames_yuv420': [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
+    'mydet_motion_warp_frames_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
+                                        c_ptr],
+    'mydet_motion_warp_frames_yuv420': [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
     'mydet_carry_state_words': [],
     'mydet_carry_reset': [c_ptr, c_int, c_ptr],
     'mydet_carry_records_rgb_u8': [c_ptr, c_int, c_int, c_int, c_i64, c_i64, c_int, c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
@@ -207,6 +216,7 @@ ZONE_ANCHOR_CENTER, ZONE_ANCHOR_BOTTOM = 0, 1
 ZONES_STATE_HEADER, ZONES_SLOT_WORDS = 148, 22
 # camera motion (mydet_motion_frames_*): MYDET_MOTION_* of include/mydet.h
 MOTION_MIN_SEARCH, MOTION_MAX_SEARCH, MOTION_MAX_BLOCKS, MOTION_STATE_HEADER = 4, 16, 1024, 4
+MOTION_MODEL_SHIFT, MOTION_MODEL_SIMILARITY = 0, 1
 # key frames (mydet_carry_records_*): MYDET_CARRY_* of include/mydet.h
 CARRY_SLOTS, CARRY_SLOT_HEADER, CARRY_SLOT_WORDS, CARRY_MAX_EVERY = 512, 16, 336, 16
 CARRY_HOW_NONE, CARRY_HOW_KEY, CARRY_HOW_CARRIED, CARRY_HOW_FLAT, CARRY_HOW_LOST, CARRY_HOW_LEFT, CARRY_HOW_NOT = range(7)
@@ -311,7 +321,8 @@ class TrackAppear(ctypes.Structure):
 
 
 class MotionSet(ctypes.Structure):
-    """mydet_motion_set (include/mydet.h): the settings of the camera-motion estimator; 0 = the default of the frame size."""
+    """mydet_motion_set (include/mydet.h): the settings of the camera-motion estimator; 0 = the default of the frame size.
+    reserved: the similarity model's words (the model, then tolerance, max_zoom, max_rotation in Q16), all 0 for the shift."""
     _fields_ = [('reduce', c_int), ('search', c_int), ('min_texture', c_int), ('min_blocks', c_int), ('reserved', c_int * 4)]
 
 

@@ -858,7 +858,9 @@ class Detector():
             if keyframes is not None:                                # the network on the key frames, the carry on all of them
                 records = self._carried_records(src, call, keyframes, tracker, shift)
             # the descriptors come from the whole original frames too, at the call's final records: behind the motion launches
-            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres, zones, overlay, shift,
+            # (under the similarity model the tracker takes the model; the carry above keeps the centre's shift)
+            found = objs = self._tracked_objects(records, src.hw, tracker, coasting, conf_thres, zones, overlay,
+                                                 None if motion is None else motion.track_args(),
                                                  None if appearance is None else (appearance, src))
         elif used:
             records = list(records)
@@ -902,6 +904,9 @@ class Detector():
         Its launches run on the call's whole original frames before the tracker's (include/mydet.h: mydet_motion_frames_rgb_u8),
         give one integer shift (dx, dy) per frame against the frame before it, and the tracker moves every prediction by it
         before the association (mydet_track_frames_motion_f32); no host synchronisation is added, motion.last has the shifts.
+        A CameraMotion(model='similarity') fits shift, rotation and zoom (mydet_motion_warp_frames_rgb_u8): the tracker's launch
+        then takes motion.last['warp'] and moves, turns and scales every prediction (mydet_track_frames_warp_f32), while the
+        key-frame carry keeps reading motion.last['shift'], the motion of the frame centre.
         Zones, trails and the heat map stay in frame pixels and assume a fixed camera.  Every frame method that takes tracker=
         takes motion=; without it every call is bit for bit what it was.
         appearance: None, or a mydetection_amd.api.Appearance (with tracker= only, and only with its assign='greedy': ValueError
@@ -987,13 +992,13 @@ class Detector():
         if 'tracker' in kwargs or 'coasting' in kwargs or 'zones' in kwargs or 'motion' in kwargs or 'appearance' in kwargs or 'keyframes' in kwargs:
             raise TypeError(f'{what}: track ids in the json rows are not built; use the predict_frames form with tracker=')
 
-    def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres, zones=None, overlay=None, shift=None, appearance=None):
+    def _tracked_objects(self, records, frame_hw, tracker, coasting, conf_thres, zones=None, overlay=None, camera=None, appearance=None):
         """The tracked form of _objects_of_records: one eager tracker launch on the call's records (frame coordinates, one
         buffer), then per frame the ImageObjects of the tracks with missed == 0 (coasting: of every live track).  Two host
         synchronisations: the frame counts, and the indices of the selected slots.  zones: a Zones whose launch follows the
         tracker's at once (no synchronisation in between); the objects then carry zone_mask and line_events.  overlay: an
-        Overlay, whose trails launch follows them and which keeps the tracker's outputs for its paint launch.  shift: the
-        camera motion of the call's frames (CameraMotion.run), on the device.  appearance: (an Appearance, the call's frame
+        Overlay, whose trails launch follows them and which keeps the tracker's outputs for its paint launch.  camera: the
+        camera motion of the call's frames (CameraMotion.track_args: shift= or warp=), on the device.  appearance: (an Appearance, the call's frame
         source): its descriptor launch on these records runs right ahead of the tracker's."""
         from ..utils.structures import ImageObjects
         records = list(records)
@@ -1009,7 +1014,7 @@ class Detector():
             birth = max(params.new_thres, assoc.high_thres) if assoc is not None and assoc.bands else params.new_thres
             appear = appearance[0].run(*appearance[1].image(), rec, tracker, frame_hw, birth)
             fused = appearance[0].launch_args()
-        out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks, assoc=assoc, shift=shift, appear=appear, **fused)
+        out = ops.track_frames(rec, state, params, max_tracks=tracker.max_tracks, assoc=assoc, appear=appear, **(camera or {}), **fused)
         if appearance is not None:
             appearance[0].took(out)
         zout = None if zones is None else zones.run(out, tracker, frame_hw)

@@ -20,6 +20,12 @@
 //                             every reader of the old state has run (stream order), so no frame of the call sees a torn state.
 // Launches 3 and 5 are tiny; merging them into their producers would need a grid-wide "last workgroup" protocol for a few
 // microseconds (profiles/motion.md has the numbers).
+//
+// The similarity model (mydet_motion_warp_frames_*; tests/_warp_ref.py restates it) keeps launches 1 - 3, refines every block
+// around its OWN coarse vector (under rotation the block vectors differ by far more than k), and puts motion_fit_kernel, one
+// workgroup per frame, between the refine and the finish launch, which then only writes the state: medians by counting ranks
+// (the Q16 values have no small range for a histogram), two rounds of closed-form least squares on the block lattice, the zoom
+// and the angle from an integer square root and an integer arctangent polynomial.  profiles/motion_warp.md has the numbers.
 #include "common.h"
 #include "yuv_fetch.h"
 
@@ -32,6 +38,7 @@ constexpr int NPART = 4;                                             // a candid
 constexpr int BINS_MAX = 2 * (R_MAX * 8 + 8) + 1;                    // block vectors live in [-(R k + k), R k + k]
 constexpr int SAVE_GROUPS = 32;                                      // workgroups per stream that write the state
 constexpr int ST_HEADER = MYDET_MOTION_STATE_HEADER;
+constexpr int64_t MOTION_T_LIMIT = 1 << 24;                          // Q16: a fitted translation of 256 pixels or more is no result
 
 // Geometry of the rules for one frame size (include/mydet.h)
 struct Geo {
@@ -148,6 +155,9 @@ struct MotionArgs {
     unsigned char *red;                                              // workspace
     int32_t *info, *blocks;                                          // blocks: out_blocks, or the workspace's
     int32_t *oshift;
+    int model;                                                       // 0: the shift; 1: the similarity, with the fields below
+    int tol_q, zoom_q, rot_q;                                        // Q16: pixels, |s - 1|, degrees
+    int32_t *owarp, *oinl;                                           // oinl may be null
 };
 
 // 1. reduced luma: thread = four neighbouring reduced pixels of one row
@@ -338,7 +348,9 @@ __global__ __launch_bounds__(256) void motion_median_kernel(const MotionArgs a) 
 }
 
 // 4. refine stage: one workgroup per (block, frame), valid blocks of frames with a coarse result only
-template <int K, typename Src>
+// OWN (the similarity model): the window sits at the block's own coarse vector instead of the frame's median D.  |c| <= R as
+// |D| <= R, so the geometry argument is the same: rows py + c.y K - K .. + P + 2K lie in [3K, (hr - 3) K] (P <= 8K, 16 nby <= hr - 2R).
+template <int K, typename Src, bool OWN>
 __global__ __launch_bounds__(256) void motion_refine_kernel(const Src src, const MotionArgs a) {
     constexpr int P = 8 * K < 32 ? 8 * K : 32, BW = P / 4, WS = P + 2 * K, SIDE = 2 * K + 1, NCAND = SIDE * SIDE;
     constexpr int WP = (((WS + 3) >> 2) + 1) | 1;
@@ -352,7 +364,7 @@ __global__ __launch_bounds__(256) void motion_refine_kernel(const Src src, const
     const int32_t *info = a.info + (int64_t)o * 4;
     int32_t *ob = a.blocks + ((int64_t)o * g.nb + b) * 6;
     if (!info[2] || !block_valid(ob, a.min_texture)) return;         // workgroup-uniform; fields 4, 5 are zero already
-    const int Dx = info[0], Dy = info[1];
+    const int Dx = OWN ? ob[0] : info[0], Dy = OWN ? ob[1] : info[1];
     const int by = b / g.nbx, bx = b - by * g.nbx;
     const int py = (g.R + 16 * by + 8) * K - P / 2, px = (g.R + 16 * bx + 8) * K - P / 2;         // the patch origin
     unsigned char *tpl = reinterpret_cast<unsigned char *>(s_tpl), *win = reinterpret_cast<unsigned char *>(s_win);
@@ -385,13 +397,14 @@ __global__ __launch_bounds__(256) void motion_refine_kernel(const Src src, const
 }
 
 // 5. workgroups [0, S*F): the frame's result; then SAVE_GROUPS workgroups per stream write the state of its last frame
-template <int K, typename Src>
+// FIT (the similarity model): motion_fit_kernel has written the frames' results, only the state is written here
+template <int K, typename Src, bool FIT>
 __global__ __launch_bounds__(256) void motion_finish_kernel(const Src src, const MotionArgs a) {
     constexpr int P = 8 * K < 32 ? 8 * K : 32;
     __shared__ int s_hist[2 * BINS_MAX];
     __shared__ int s_out[3];
     const Geo &g = a.g;
-    const int tid = threadIdx.x, nframes = a.S * a.F;
+    const int tid = threadIdx.x, nframes = FIT ? 0 : a.S * a.F;
     if ((int)blockIdx.x < nframes) {
         const int o = blockIdx.x;
         const int32_t *info = a.info + (int64_t)o * 4;
@@ -425,6 +438,196 @@ __global__ __launch_bounds__(256) void motion_finish_kernel(const Src src, const
     if (part == 0 && tid < words - used) st[used + tid] = 0;        // the padding (< 4 words)
 }
 
+// ---- the similarity model (include/mydet.h: mydet_motion_warp_frames_rgb_u8) ----
+// Everything below is int64.  Bounds, with n <= 1024 blocks, lattice coordinates |u| < 512 (the block lattice: a block's centre
+// is (R + 8) k + 16 k u, so the 16 k between lattice steps divides out of the least squares), block vectors |d| <= 136 and
+// half-pixel offsets |q| <= 32768: a pair's numerator (dp . dd) << 16 < 2^41; the least-squares numerator
+// (m sum(u . d) - sum u . sum d) << 16 < 2^55 and its denominator 16 k (m sum |u|^2 - |sum u|^2) < 2^47; with |a|, |b| < 2^21 (a
+// pair's or a fit's |dd| / |dp| <= 272 / 32) the translation's numerator (sum d << 17) - (a sum qx - b sum qy) < 2^48.
+
+__device__ __forceinline__ int64_t floor_div(int64_t num, int64_t den) {                 // den > 0
+    const int64_t q = num / den;
+    return num - q * den < 0 ? q - 1 : q;
+}
+
+__device__ __forceinline__ int64_t isqrt_u64(uint64_t v) {
+    uint64_t r = 0, bit = 1ull << 62;
+    while (bit > v) bit >>= 2;
+    while (bit) {
+        if (v >= r + bit) { v -= r + bit; r = (r >> 1) + bit; }
+        else r >>= 1;
+        bit >>= 2;
+    }
+    return (int64_t)r;
+}
+
+// Q16 degrees of atan(u / 2^16), |u| <= 2^14: the odd polynomial of the header on |u|, constants round(180 / pi / (1, 3, 5, 7) 2^24)
+__device__ __forceinline__ int64_t atan_deg_q(int64_t u) {
+    const int64_t m = u < 0 ? -u : u, u2 = (m * m) >> 16;
+    int64_t p = 137323381;
+    p = 192252734 - ((u2 * p) >> 16);
+    p = 320421223 - ((u2 * p) >> 16);
+    p = 961263669 - ((u2 * p) >> 16);
+    const int64_t d = (m * p) >> 24;
+    return u < 0 ? -d : d;
+}
+
+// The lower median of val[0, n) (n >= 1) by counting: the element whose rank under (value, index) is (n - 1) / 2.  The values
+// are complete before the call (a barrier); on return every thread has the median and val may be written again.
+__device__ __forceinline__ int64_t rank_median(const int64_t *val, int n, int64_t *res) {
+    const int m = (n - 1) / 2;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int64_t vi = val[i];
+        int r = 0;
+        for (int j = 0; j < n; ++j) {
+            const int64_t vj = val[j];
+            r += (vj < vi || (vj == vi && j < i)) ? 1 : 0;
+        }
+        if (r == m) *res = vi;
+    }
+    __syncthreads();
+    return *res;
+}
+
+// One workgroup per frame: the fit over the frame's valid blocks -> out_warp, out_shift, the inlier mask.  Every branch around
+// a barrier is workgroup-uniform: its condition comes from LDS words every thread reads alike.
+__global__ __launch_bounds__(256) void motion_fit_kernel(const MotionArgs a) {
+    constexpr int NSUM = 10;
+    __shared__ int64_t s_va[NB_MAX], s_vb[NB_MAX];
+    __shared__ int s_blk[NB_MAX], s_dx[NB_MAX], s_dy[NB_MAX];
+    __shared__ int s_inl[NB_MAX];                                    // by block index
+    __shared__ int s_wcnt[NB_MAX / 64];
+    __shared__ int64_t s_res[4];
+    __shared__ unsigned long long s_sum[NSUM];
+    const Geo &g = a.g;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, o = blockIdx.x, nb = g.nb, k = g.k;
+    const int32_t *info = a.info + (int64_t)o * 4;
+    const int32_t *blk = a.blocks + (int64_t)o * nb * 6;
+    int32_t *os = a.oshift + (int64_t)o * 4, *ow = a.owarp + (int64_t)o * 8;
+    int32_t *oi = a.oinl ? a.oinl + (int64_t)o * nb : nullptr;
+    const int n_valid = info[3];
+    bool ok = info[2] != 0;                                          // workgroup-uniform, as every later change of it
+    int64_t ma = 0, mb = 0, tx = 0, ty = 0, s_q = 0, deg_q = 0;
+    int n = 0, m_in = 0;
+
+    for (int b = tid; b < nb; b += 256) s_inl[b] = 0;
+    if (ok) {
+        // the valid blocks in ascending block index
+        unsigned long long bal[NB_MAX / 256];
+#pragma unroll
+        for (int c = 0; c < NB_MAX / 256; ++c) {
+            const int b = c * 256 + tid;
+            bal[c] = __ballot(b < nb && block_valid(blk + (int64_t)b * 6, a.min_texture));
+            if (lane == 0) s_wcnt[c * 4 + wave] = __popcll(bal[c]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < NB_MAX / 256; ++c) {
+            const int b = c * 256 + tid;
+            int pos = 0;
+            for (int i = 0; i < c * 4 + wave; ++i) pos += s_wcnt[i];
+            if ((bal[c] >> lane) & 1ull) {
+                pos += __popcll(bal[c] & ((1ull << lane) - 1ull));
+                s_blk[pos] = b; s_dx[pos] = blk[(int64_t)b * 6 + 4]; s_dy[pos] = blk[(int64_t)b * 6 + 5];
+            }
+        }
+        for (int i = 0; i < NB_MAX / 64; ++i) n += s_wcnt[i];
+        __syncthreads();
+    }
+    const int h = n / 2;
+    ok = ok && h > 0;                                                // no pair
+    // block i: lattice (ux, uy), centre p, q = 2 p - (W, H)
+#define FIT_BLOCK(i)                                                                       \
+    const int uy = s_blk[i] / g.nbx, ux = s_blk[i] - uy * g.nbx;                           \
+    const int64_t qx = 2 * (int64_t)((g.R + 16 * ux + 8) * k) - g.W, qy = 2 * (int64_t)((g.R + 16 * uy + 8) * k) - g.H; \
+    const int64_t dx = s_dx[i], dy = s_dy[i]
+    if (ok) {
+        for (int i = tid; i < h; i += 256) {
+            const int j = i + (n - h);
+            const int uyi = s_blk[i] / g.nbx, uxi = s_blk[i] - uyi * g.nbx, uyj = s_blk[j] / g.nbx, uxj = s_blk[j] - uyj * g.nbx;
+            const int64_t ex = (int64_t)(16 * k) * (uxj - uxi), ey = (int64_t)(16 * k) * (uyj - uyi);
+            const int64_t fx = s_dx[j] - s_dx[i], fy = s_dy[j] - s_dy[i], den = ex * ex + ey * ey;      // > 0: distinct blocks
+            s_va[i] = floor_div((ex * fx + ey * fy) << 16, den);
+            s_vb[i] = floor_div((ex * fy - ey * fx) << 16, den);
+        }
+        __syncthreads();
+        ma = rank_median(s_va, h, &s_res[0]);
+        mb = rank_median(s_vb, h, &s_res[1]);
+        for (int i = tid; i < n; i += 256) {
+            FIT_BLOCK(i);
+            s_va[i] = (dx << 16) - ((ma * qx - mb * qy) >> 1);
+            s_vb[i] = (dy << 16) - ((mb * qx + ma * qy) >> 1);
+        }
+        __syncthreads();
+        tx = rank_median(s_va, n, &s_res[2]);
+        ty = rank_median(s_vb, n, &s_res[3]);
+    }
+    for (int round = 0; round < 2; ++round) {
+        if (!ok) break;
+        if (tid < NSUM) s_sum[tid] = 0ull;
+        __syncthreads();
+        int64_t acc[NSUM];
+#pragma unroll
+        for (int q = 0; q < NSUM; ++q) acc[q] = 0;
+        for (int i = tid; i < n; i += 256) {
+            FIT_BLOCK(i);
+            const int64_t rx = (dx << 16) - tx - ((ma * qx - mb * qy) >> 1), ry = (dy << 16) - ty - ((mb * qx + ma * qy) >> 1);
+            const bool in = (rx < 0 ? -rx : rx) <= a.tol_q && (ry < 0 ? -ry : ry) <= a.tol_q;
+            s_inl[s_blk[i]] = in ? 1 : 0;
+            if (in) {
+                acc[0] += 1; acc[1] += ux; acc[2] += uy; acc[3] += dx; acc[4] += dy;
+                acc[5] += (int64_t)ux * ux + (int64_t)uy * uy;
+                acc[6] += ux * dx + uy * dy;
+                acc[7] += ux * dy - uy * dx;
+                acc[8] += qx; acc[9] += qy;
+            }
+        }
+        if (acc[0]) {
+#pragma unroll
+            for (int q = 0; q < NSUM; ++q) atomicAdd(&s_sum[q], (unsigned long long)acc[q]);
+        }
+        __syncthreads();
+        const int64_t m = (int64_t)s_sum[0], sux = (int64_t)s_sum[1], suy = (int64_t)s_sum[2], sdx = (int64_t)s_sum[3], sdy = (int64_t)s_sum[4];
+        const int64_t suu = (int64_t)s_sum[5], sud = (int64_t)s_sum[6], sxd = (int64_t)s_sum[7], sqx = (int64_t)s_sum[8], sqy = (int64_t)s_sum[9];
+        __syncthreads();                                             // s_sum is read: the next round may clear it
+        const int64_t den = (int64_t)(16 * k) * (m * suu - (sux * sux + suy * suy));
+        if (m < 3 || den == 0) { ok = false; break; }
+        ma = floor_div((m * sud - (sux * sdx + suy * sdy)) << 16, den);
+        mb = floor_div((m * sxd - (sux * sdy - suy * sdx)) << 16, den);
+        tx = floor_div((sdx << 17) - (ma * sqx - mb * sqy), 2 * m);
+        ty = floor_div((sdy << 17) - (mb * sqx + ma * sqy), 2 * m);
+        m_in = (int)m;
+    }
+#undef FIT_BLOCK
+    if (ok) {                                                        // the derived integers and the caps
+        s_q = isqrt_u64((uint64_t)((65536 + ma) * (65536 + ma) + mb * mb));
+        const int64_t dz = s_q - 65536;
+        ok = (dz < 0 ? -dz : dz) <= a.zoom_q && 65536 + ma > 0;
+        ok = ok && (tx < 0 ? -tx : tx) < MOTION_T_LIMIT && (ty < 0 ? -ty : ty) < MOTION_T_LIMIT;
+        if (ok) {
+            const int64_t u = floor_div(mb << 16, 65536 + ma);
+            ok = (u < 0 ? -u : u) <= 16384;
+            if (ok) {
+                deg_q = atan_deg_q(u);
+                ok = (deg_q < 0 ? -deg_q : deg_q) <= a.rot_q;
+            }
+        }
+    }
+    __syncthreads();                                                 // s_inl is complete
+    if (tid < 8) {
+        const int64_t w[8] = {ma, mb, tx, ty, s_q, deg_q, 1, m_in};
+        int32_t v = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v = tid == q ? (int32_t)w[q] : v;
+        ow[tid] = ok ? v : 0;
+    }
+    if (tid == 0) {
+        os[0] = ok ? (int32_t)((tx + 32768) >> 16) : 0; os[1] = ok ? (int32_t)((ty + 32768) >> 16) : 0; os[2] = ok ? 1 : 0; os[3] = n_valid;
+    }
+    if (oi)
+        for (int b = tid; b < nb; b += 256) oi[b] = ok ? s_inl[b] : 0;
+}
+
 __global__ __launch_bounds__(256) void motion_reset_kernel(int32_t *state, int64_t words) {
     int32_t *st = state + (int64_t)blockIdx.y * words;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) st[i] = 0;
@@ -437,8 +640,14 @@ int motion_launch(const Src &src, const MotionArgs &a, hipStream_t stream) {
     hipLaunchKernelGGL((motion_reduce_kernel<K, Src>), dim3((unsigned)((g.hr * (g.wrp / 4) + 255) / 256), frames), dim3(256), 0, stream, src, a);
     hipLaunchKernelGGL(motion_coarse_kernel, dim3((unsigned)g.nb, frames), dim3(256), 0, stream, a);
     hipLaunchKernelGGL(motion_median_kernel, dim3(frames), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL((motion_refine_kernel<K, Src>), dim3((unsigned)g.nb, frames), dim3(256), 0, stream, src, a);
-    hipLaunchKernelGGL((motion_finish_kernel<K, Src>), dim3(frames + (unsigned)(a.S * SAVE_GROUPS)), dim3(256), 0, stream, src, a);
+    if (a.model) {
+        hipLaunchKernelGGL((motion_refine_kernel<K, Src, true>), dim3((unsigned)g.nb, frames), dim3(256), 0, stream, src, a);
+        hipLaunchKernelGGL(motion_fit_kernel, dim3(frames), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((motion_finish_kernel<K, Src, true>), dim3((unsigned)(a.S * SAVE_GROUPS)), dim3(256), 0, stream, src, a);
+        return mydet_launch_status();
+    }
+    hipLaunchKernelGGL((motion_refine_kernel<K, Src, false>), dim3((unsigned)g.nb, frames), dim3(256), 0, stream, src, a);
+    hipLaunchKernelGGL((motion_finish_kernel<K, Src, false>), dim3(frames + (unsigned)(a.S * SAVE_GROUPS)), dim3(256), 0, stream, src, a);
     return mydet_launch_status();
 }
 
@@ -451,7 +660,17 @@ int motion_launch_k(const Src &src, const MotionArgs &a, hipStream_t stream) {
 
 // The checks both entry points share; fills `a`
 int motion_args(MotionArgs &a, int B, int H, int W, int S, const mydet_motion_set *set, int32_t *state, void *ws, int64_t ws_bytes,
-                int32_t *out_shift, int32_t *out_blocks) {
+                int32_t *out_shift, int32_t *out_blocks, bool warp = false, int32_t *out_warp = nullptr, int32_t *out_inliers = nullptr) {
+    a.model = 0; a.tol_q = a.zoom_q = a.rot_q = 0; a.owarp = a.oinl = nullptr;
+    if (warp) {                                                      // the similarity model: the reserved words of the settings
+        if (!set || !out_warp || ((uintptr_t)out_warp & 3) || ((uintptr_t)out_inliers & 3)) return MYDET_E_BADARG;
+        const int *r = set->reserved;
+        if (r[0] != MYDET_MOTION_MODEL_SIMILARITY) return MYDET_E_BADARG;
+        if (r[1] < 0 || r[1] > 16 << 16 || r[2] < 0 || r[2] > 1 << 14 || r[3] < 0 || r[3] > 14 << 16) return MYDET_E_BADARG;
+        a.model = 1;
+        a.tol_q = r[1] ? r[1] : 2 << 16; a.zoom_q = r[2] ? r[2] : 1 << 13; a.rot_q = r[3] ? r[3] : 7 << 16;
+        a.owarp = out_warp; a.oinl = out_inliers;
+    }
     if (B <= 0 || S <= 0 || B % S || !set || !state || !ws || !out_shift) return MYDET_E_BADARG;
     if (((uintptr_t)state & 15) || ((uintptr_t)ws & 15) || ((uintptr_t)out_shift & 3) || ((uintptr_t)out_blocks & 3)) return MYDET_E_BADARG;
     if (H < 1 || W < 1) return MYDET_E_BADARG;
@@ -508,16 +727,29 @@ extern "C" int mydet_motion_frames_rgb_u8(const unsigned char *src, int B, int H
     return motion_launch_k(l, a, (hipStream_t)stream);
 }
 
-extern "C" int mydet_motion_frames_yuv420(const mydet_yuv420_src *src, int B, int H, int W, int S, const mydet_motion_set *set,
-                                          int32_t *state, void *ws, int64_t ws_bytes, int32_t *out_shift, int32_t *out_blocks,
-                                          void *stream) {
+extern "C" int mydet_motion_warp_frames_rgb_u8(const unsigned char *src, int B, int H, int W, int64_t img_bytes, int64_t row_bytes, int S,
+                                               const mydet_motion_set *set, int32_t *state, void *ws, int64_t ws_bytes, int32_t *out_shift,
+                                               int32_t *out_warp, int32_t *out_blocks, int32_t *out_inliers, void *stream) {
+    if (!src || img_bytes < 0 || W < 1 || row_bytes < 3 * (int64_t)W) return MYDET_E_BADARG;
+    MotionArgs a;
+    const int st = motion_args(a, B, H, W, S, set, state, ws, ws_bytes, out_shift, out_blocks, true, out_warp, out_inliers);
+    if (st) return st;
+    const int vec = a.g.k == 2 ? 8 : 16;
+    const RgbLuma l = {src, img_bytes, row_bytes, (((uintptr_t)src | (uintptr_t)img_bytes | (uintptr_t)row_bytes) & (uintptr_t)(vec - 1)) ? 0 : 1};
+    return motion_launch_k(l, a, (hipStream_t)stream);
+}
+
+// The 4:2:0 entry points: warp = false is mydet_motion_frames_yuv420
+static int motion_frames_yuv420(const mydet_yuv420_src *src, int B, int H, int W, int S, const mydet_motion_set *set, int32_t *state, void *ws,
+                                int64_t ws_bytes, int32_t *out_shift, int32_t *out_blocks, bool warp, int32_t *out_warp,
+                                int32_t *out_inliers, void *stream) {
     YuvSrc ys;
     int bps;
     bool planar;
     int st = yuv_source(ys, bps, planar, src, B, H, W);
     if (st) return st;
     MotionArgs a;
-    st = motion_args(a, B, H, W, S, set, state, ws, ws_bytes, out_shift, out_blocks);
+    st = motion_args(a, B, H, W, S, set, state, ws, ws_bytes, out_shift, out_blocks, warp, out_warp, out_inliers);
     if (st) return st;
 #define MOTION_CALL(BPS, PLANAR)                                                   \
     do {                                                                           \
@@ -527,4 +759,16 @@ extern "C" int mydet_motion_frames_yuv420(const mydet_yuv420_src *src, int B, in
     YUV_DISPATCH(bps, planar, MOTION_CALL);
 #undef MOTION_CALL
     return MYDET_E_BADARG;
+}
+
+extern "C" int mydet_motion_warp_frames_yuv420(const mydet_yuv420_src *src, int B, int H, int W, int S, const mydet_motion_set *set,
+                                               int32_t *state, void *ws, int64_t ws_bytes, int32_t *out_shift, int32_t *out_warp,
+                                               int32_t *out_blocks, int32_t *out_inliers, void *stream) {
+    return motion_frames_yuv420(src, B, H, W, S, set, state, ws, ws_bytes, out_shift, out_blocks, true, out_warp, out_inliers, stream);
+}
+
+extern "C" int mydet_motion_frames_yuv420(const mydet_yuv420_src *src, int B, int H, int W, int S, const mydet_motion_set *set,
+                                          int32_t *state, void *ws, int64_t ws_bytes, int32_t *out_shift, int32_t *out_blocks,
+                                          void *stream) {
+    return motion_frames_yuv420(src, B, H, W, S, set, state, ws, ws_bytes, out_shift, out_blocks, false, nullptr, nullptr, stream);
 }

@@ -49,6 +49,7 @@ struct TrackArgs {
     int32_t *omissed, *ocount, *odropped;
     mydet_track_assoc as;             // read by the instances with bands or the optimal assignment only
     const int32_t *shift;             // null, or the camera motion of frame o at shift + 4 o: (dx, dy, valid, n_valid)
+    const int32_t *warp;              // null, or its similarity model at warp + 8 o: (a, b, tx, ty, s_q, deg_q, valid, n_inliers); never with shift
 };
 // The arguments of the instances with an appearance (mydet_track_frames_appear_f32): the others keep TrackArgs as it was
 struct TrackAppearArgs : TrackArgs {
@@ -382,6 +383,30 @@ __global__ __launch_bounds__(TMAX) void track_kernel(const TrackKernelArgs<APPEA
             if (a.shift) {                                         // camera motion: the prediction moves with the image
                 const int32_t *sh = a.shift + o * 4;
                 if (sh[2] == 1) { x[0] = x[0] + (float)sh[0]; x[1] = x[1] + (float)sh[1]; }
+            } else if (a.warp) {                                   // the similarity model (include/mydet.h: mydet_track_frames_warp_f32)
+                const int32_t *wr = a.warp + o * 8;
+                if (wr[6] == 1) {
+                    // one rounded operation per line of the header; identity parts are skipped, so that a pure shift row
+                    // gives the bits of the branch above (-0.0 + 0.0 would not)
+                    constexpr float Q = 1.0f / 65536.0f;
+                    const float fa = (float)wr[0] * Q, fb = (float)wr[1] * Q, ftx = (float)wr[2] * Q, fty = (float)wr[3] * Q;
+                    const float ux = x[0] - P.img_w * 0.5f, uy = x[1] - P.img_h * 0.5f;
+                    x[0] = x[0] + ftx;
+                    x[1] = x[1] + fty;
+                    if (wr[0] != 0 || wr[1] != 0) {
+                        x[0] = x[0] + (fa * ux - fb * uy);
+                        x[1] = x[1] + (fb * ux + fa * uy);
+                        const float v0 = v[0], v1 = v[1];
+                        v[0] = v0 + (fa * v0 - fb * v1);
+                        v[1] = v1 + (fb * v0 + fa * v1);
+                    }
+                    if (wr[4] != 65536) {
+                        const float fs = (float)wr[4] * Q;
+                        x[2] = x[2] * fs; x[3] = x[3] * fs; v[2] = v[2] * fs; v[3] = v[3] * fs;
+                    }
+                    if constexpr (BW == 5)
+                        if (wr[5] != 0) x[4] = x[4] + (float)wr[5] * Q;
+                }
             }
             x[4] = mod180(x[4]);
             if (missed >= 1) score = P.momentum * score;
@@ -774,7 +799,7 @@ int track_launch_mode(const TrackKernelArgs<APPEAR> &a, int box_width, dim3 grid
 int track_setup(TrackArgs &a, const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F, int box_width,
                 const mydet_track_params *params, int max_tracks, int32_t *state, float *out_box, float *out_score, int64_t *out_class,
                 int64_t *out_id, int32_t *out_missed, int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc,
-                const int32_t *shift) {
+                const int32_t *shift, const int32_t *warp = nullptr) {
     if (S <= 0 || F <= 0 || max_tracks < 1) return MYDET_E_BADARG;
     if (box_width != 4 && box_width != 5) return MYDET_E_BADARG;
     if (!records || !params || !state || !out_box || !out_score || !out_class || !out_id || !out_missed || !out_count || !out_dropped)
@@ -792,7 +817,7 @@ int track_setup(TrackArgs &a, const int32_t *records, int64_t stream_stride_word
     if (((uintptr_t)records & 15) || ((uintptr_t)state & 15)) return MYDET_E_BADARG;
     if (stream_stride_words < 0 || frame_stride_words < 0 || (stream_stride_words & 3) || (frame_stride_words & 3)) return MYDET_E_BADARG;
     if (((uintptr_t)out_box & 3) || ((uintptr_t)out_score & 3) || ((uintptr_t)out_class & 7) || ((uintptr_t)out_id & 7) ||
-        ((uintptr_t)out_missed & 3) || ((uintptr_t)out_count & 3) || ((uintptr_t)out_dropped & 3) || ((uintptr_t)shift & 3))
+        ((uintptr_t)out_missed & 3) || ((uintptr_t)out_count & 3) || ((uintptr_t)out_dropped & 3) || ((uintptr_t)shift & 3) || ((uintptr_t)warp & 3))
         return MYDET_E_BADARG;
     if (max_tracks > MYDET_TRACK_MAX_TRACKS) return MYDET_E_UNSUPP;
     a.rec = records; a.stream_st = stream_stride_words; a.frame_st = frame_stride_words; a.F = F; a.MT = max_tracks;
@@ -802,25 +827,44 @@ int track_setup(TrackArgs &a, const int32_t *records, int64_t stream_stride_word
     a.odropped = out_dropped;
     a.as = *assoc;
     a.shift = shift;
+    a.warp = warp;
     return 0;
 }
 
 }  // namespace
 
 #ifndef MYDET_TRACK_APPEAR
-extern "C" int mydet_track_frames_motion_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
-                                             int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
-                                             float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
-                                             int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
-                                             void *stream) {
+// The entry points with a camera motion: at most one of shift and warp is not null
+static int track_frames_camera(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F, int box_width,
+                               const mydet_track_params *params, int max_tracks, int32_t *state, float *out_box, float *out_score,
+                               int64_t *out_class, int64_t *out_id, int32_t *out_missed, int32_t *out_count, int32_t *out_dropped,
+                               const mydet_track_assoc *assoc, const int32_t *shift, const int32_t *warp, void *stream) {
     TrackArgs a;
     const int code = track_setup(a, records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
-                                 out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift);
+                                 out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift, warp);
     if (code) return code;
     const dim3 grid((unsigned)S), block((unsigned)((max_tracks + 63) / 64 * 64));
     if (assoc->assign == MYDET_TRACK_ASSIGN_OPTIMAL) return track_launch_mode<ASSOC_OPTIMAL>(a, box_width, grid, block, (hipStream_t)stream);
     if (assoc->bands) return track_launch_mode<ASSOC_GREEDY_BANDS>(a, box_width, grid, block, (hipStream_t)stream);
     return track_launch_mode<ASSOC_GREEDY>(a, box_width, grid, block, (hipStream_t)stream);
+}
+
+extern "C" int mydet_track_frames_motion_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                             int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                             float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                             int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
+                                             void *stream) {
+    return track_frames_camera(records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box, out_score,
+                               out_class, out_id, out_missed, out_count, out_dropped, assoc, shift, nullptr, stream);
+}
+
+extern "C" int mydet_track_frames_warp_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                           int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                           float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                           int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *warp,
+                                           void *stream) {
+    return track_frames_camera(records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box, out_score,
+                               out_class, out_id, out_missed, out_count, out_dropped, assoc, nullptr, warp, stream);
 }
 
 #else
@@ -849,15 +893,15 @@ int track_appear_setup(TrackAppearArgs &a, int max_tracks, const mydet_track_app
 }  // namespace
 
 #ifndef MYDET_TRACK_APPEAR_OPTIMAL
-extern "C" int mydet_track_frames_appear_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
-                                             int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
-                                             float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
-                                             int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
-                                             const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
-                                             int32_t *out_sim, int32_t *out_how, void *stream) {
+static int track_frames_appear_camera(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                      int box_width, const mydet_track_params *params, int max_tracks, int32_t *state, float *out_box,
+                                      float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed, int32_t *out_count,
+                                      int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift, const int32_t *warp,
+                                      const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state, int32_t *out_sim,
+                                      int32_t *out_how, void *stream) {
     TrackAppearArgs a;
     const int code = track_setup(a, records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
-                                 out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift);
+                                 out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift, warp);
     if (code) return code;
     const int acode = track_appear_setup(a, max_tracks, appear, desc, appear_state, out_sim, out_how);
     if (acode) return acode;
@@ -866,10 +910,53 @@ extern "C" int mydet_track_frames_appear_f32(const int32_t *records, int64_t str
     if (assoc->bands) return track_launch_mode<ASSOC_GREEDY_BANDS, true>(a, box_width, grid, block, (hipStream_t)stream);
     return track_launch_mode<ASSOC_GREEDY, true>(a, box_width, grid, block, (hipStream_t)stream);
 }
+
+extern "C" int mydet_track_frames_appear_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                             int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                             float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                             int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
+                                             const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
+                                             int32_t *out_sim, int32_t *out_how, void *stream) {
+    return track_frames_appear_camera(records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
+                                      out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift, nullptr, appear, desc,
+                                      appear_state, out_sim, out_how, stream);
+}
+
+extern "C" int mydet_track_frames_appear_warp_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S,
+                                                  int F, int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                                  float *out_box, float *out_score, int64_t *out_class, int64_t *out_id,
+                                                  int32_t *out_missed, int32_t *out_count, int32_t *out_dropped,
+                                                  const mydet_track_assoc *assoc, const int32_t *warp, const mydet_track_appear *appear,
+                                                  const uint16_t *desc, int32_t *appear_state, int32_t *out_sim, int32_t *out_how,
+                                                  void *stream) {
+    return track_frames_appear_camera(records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
+                                      out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, nullptr, warp, appear, desc,
+                                      appear_state, out_sim, out_how, stream);
+}
 #else
 extern "C" int64_t mydet_track_appear_ws_words(int max_tracks) {
     if (max_tracks < 1 || max_tracks > MYDET_TRACK_MAX_TRACKS) return 0;
     return (int64_t)MYDET_REC_TOPK * max_tracks;
+}
+
+static int track_frames_appear_optimal_camera(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S, int F,
+                                              int box_width, const mydet_track_params *params, int max_tracks, int32_t *state,
+                                              float *out_box, float *out_score, int64_t *out_class, int64_t *out_id, int32_t *out_missed,
+                                              int32_t *out_count, int32_t *out_dropped, const mydet_track_assoc *assoc, const int32_t *shift,
+                                              const int32_t *warp, const mydet_track_appear *appear, const uint16_t *desc,
+                                              int32_t *appear_state, int32_t *out_sim, int32_t *out_how, int weight, int32_t *sim_ws,
+                                              void *stream) {
+    TrackAppearArgs a;
+    const int code = track_setup(a, records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
+                                 out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift, warp);
+    if (code) return code;
+    const int acode = track_appear_setup(a, max_tracks, appear, desc, appear_state, out_sim, out_how);
+    if (acode) return acode;
+    if (weight < 0 || weight > 256 || !sim_ws || ((uintptr_t)sim_ws & 15)) return MYDET_E_BADARG;
+    if (assoc->assign != MYDET_TRACK_ASSIGN_OPTIMAL) return MYDET_E_UNSUPP;         // the walk's key stays IoU-major
+    a.weight = weight; a.sim_ws = sim_ws;
+    const dim3 grid((unsigned)S), block((unsigned)((max_tracks + 63) / 64 * 64));
+    return track_launch_mode<ASSOC_OPTIMAL, true>(a, box_width, grid, block, (hipStream_t)stream);
 }
 
 extern "C" int mydet_track_frames_appear_optimal_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words, int S,
@@ -879,17 +966,21 @@ extern "C" int mydet_track_frames_appear_optimal_f32(const int32_t *records, int
                                                      const mydet_track_assoc *assoc, const int32_t *shift, const mydet_track_appear *appear,
                                                      const uint16_t *desc, int32_t *appear_state, int32_t *out_sim, int32_t *out_how,
                                                      int weight, int32_t *sim_ws, void *stream) {
-    TrackAppearArgs a;
-    const int code = track_setup(a, records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state, out_box,
-                                 out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift);
-    if (code) return code;
-    const int acode = track_appear_setup(a, max_tracks, appear, desc, appear_state, out_sim, out_how);
-    if (acode) return acode;
-    if (weight < 0 || weight > 256 || !sim_ws || ((uintptr_t)sim_ws & 15)) return MYDET_E_BADARG;
-    if (assoc->assign != MYDET_TRACK_ASSIGN_OPTIMAL) return MYDET_E_UNSUPP;         // the walk's key stays IoU-major
-    a.weight = weight; a.sim_ws = sim_ws;
-    const dim3 grid((unsigned)S), block((unsigned)((max_tracks + 63) / 64 * 64));
-    return track_launch_mode<ASSOC_OPTIMAL, true>(a, box_width, grid, block, (hipStream_t)stream);
+    return track_frames_appear_optimal_camera(records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state,
+                                              out_box, out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, shift, nullptr,
+                                              appear, desc, appear_state, out_sim, out_how, weight, sim_ws, stream);
+}
+
+extern "C" int mydet_track_frames_appear_optimal_warp_f32(const int32_t *records, int64_t stream_stride_words, int64_t frame_stride_words,
+                                                          int S, int F, int box_width, const mydet_track_params *params, int max_tracks,
+                                                          int32_t *state, float *out_box, float *out_score, int64_t *out_class,
+                                                          int64_t *out_id, int32_t *out_missed, int32_t *out_count, int32_t *out_dropped,
+                                                          const mydet_track_assoc *assoc, const int32_t *warp,
+                                                          const mydet_track_appear *appear, const uint16_t *desc, int32_t *appear_state,
+                                                          int32_t *out_sim, int32_t *out_how, int weight, int32_t *sim_ws, void *stream) {
+    return track_frames_appear_optimal_camera(records, stream_stride_words, frame_stride_words, S, F, box_width, params, max_tracks, state,
+                                              out_box, out_score, out_class, out_id, out_missed, out_count, out_dropped, assoc, nullptr, warp,
+                                              appear, desc, appear_state, out_sim, out_how, weight, sim_ws, stream);
 }
 #endif
 

@@ -1768,7 +1768,7 @@ def track_state_views(state, max_tracks=None):
 
 
 def track_frames(records, tracker_state, params, frames_per_stream=None, max_tracks=None, out=None, assoc=None, shift=None, appear=None,
-                 appear_weight=None, appear_ws=None):
+                 appear_weight=None, appear_ws=None, warp=None):
     """Advance S streams by F frames each in ONE launch (include/mydet.h: mydet_track_frames_f32, where the rules are).
     records: the detection records in frame coordinates -- an int32 tensor [S*F, words] (frame f of stream s in row s*F + f) or
     [S, F, words] with any strides along S and F that are multiples of 4 words, or the record_views dict of a [S*F, words]
@@ -1788,7 +1788,12 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
     on the fused IoU-and-appearance cost of mydet_track_frames_appear_optimal_f32: m = ((256 - weight) * q + weight * (S >> 1)) >> 8.
     It takes an assoc with assign 'optimal' (a greedy one is a ValueError before any launch) and appear_ws, the int32
     [S, appear_ws_words(max_tracks)] tensor of appear_workspace, which afterwards holds S of the last frame's needed pairs at
-    [s, d * max_tracks + j]."""
+    [s, d * max_tracks + j].  warp: None, or in the place of shift the similarity model of the same frames --
+    motion_frames(...)['warp'] of a set with model 'similarity', int32 [S,F,8] or [S*F,8] on the records' device: in a frame with
+    valid == 1 every prediction is moved, turned and scaled about the frame centre (mydet_track_frames_warp_f32 and its
+    appearance siblings).  Both shift and warp: a ValueError before any launch."""
+    if shift is not None and warp is not None:
+        raise ValueError('track_frames: shift and warp are two forms of one camera motion; pass one of them')
     if not isinstance(params, _lib.TrackParams):
         raise TypeError(f'track_frames: params is a _lib.TrackParams (ops.track_params), got {type(params).__name__}')
     if assoc is not None and not isinstance(assoc, _lib.TrackAssoc):
@@ -1858,10 +1863,27 @@ def track_frames(records, tracker_state, params, frames_per_stream=None, max_tra
         if (not isinstance(shift, torch.Tensor) or shift.dtype != torch.int32 or shift.numel() != S * F * 4 or shift.shape[-1] != 4 or
                 shift.device != dev or not shift.is_contiguous()):
             raise ValueError(f'track_frames: shift must be a contiguous int32 tensor [{S},{F},4] on {dev} (ops.motion_frames)')
+    if warp is not None:
+        if (not isinstance(warp, torch.Tensor) or warp.dtype != torch.int32 or warp.numel() != S * F * 8 or warp.shape[-1] != 8 or
+                warp.device != dev or not warp.is_contiguous()):
+            raise ValueError(f'track_frames: warp must be a contiguous int32 tensor [{S},{F},8] on {dev} (ops.motion_frames)')
     t0 = TIMER.start() if TIMER else None
     args = (_ptr(records), records.stride(0), records.stride(1), S, F, width, ctypes.byref(params), mt, _ptr(tracker_state), _ptr(out['box']),
             _ptr(out['score']), _ptr(out['cls']), _ptr(out['id']), _ptr(out['missed']), _ptr(out['count']), _ptr(out['dropped']))
-    if appear is not None and appear_weight is not None:
+    if warp is not None and appear is not None and appear_weight is not None:
+        name = 'mydet_track_frames_appear_optimal_warp_f32'
+        code = _lib.lib().mydet_track_frames_appear_optimal_warp_f32(*args, ctypes.byref(assoc), _ptr(warp), ctypes.byref(aset), _ptr(desc),
+                                                                     _ptr(astate), _ptr(out['sim']), _ptr(out['how']), int(appear_weight),
+                                                                     _ptr(appear_ws), _stream())
+    elif warp is not None and appear is not None:
+        name = 'mydet_track_frames_appear_warp_f32'
+        code = _lib.lib().mydet_track_frames_appear_warp_f32(*args, ctypes.byref(track_assoc() if assoc is None else assoc), _ptr(warp),
+                                                             ctypes.byref(aset), _ptr(desc), _ptr(astate), _ptr(out['sim']), _ptr(out['how']),
+                                                             _stream())
+    elif warp is not None:
+        name = 'mydet_track_frames_warp_f32'
+        code = _lib.lib().mydet_track_frames_warp_f32(*args, ctypes.byref(track_assoc() if assoc is None else assoc), _ptr(warp), _stream())
+    elif appear is not None and appear_weight is not None:
         name = 'mydet_track_frames_appear_optimal_f32'
         code = _lib.lib().mydet_track_frames_appear_optimal_f32(*args, ctypes.byref(assoc), None if shift is None else _ptr(shift),
                                                                 ctypes.byref(aset), _ptr(desc), _ptr(astate), _ptr(out['sim']),
@@ -2079,11 +2101,31 @@ def zones_frames(track_out, state, zone_set, heat=None, out=None):
 # ---------------------------------------------------------------------------------------------------------------------------
 # Camera motion (include/mydet.h: mydet_motion_frames_rgb_u8, where the rules are; csrc/motion.hip)
 
-def motion_set(reduce=None, search=8, min_texture=1024, min_blocks=None):
+MOTION_MODELS = {'shift': _lib.MOTION_MODEL_SHIFT, 'similarity': _lib.MOTION_MODEL_SIMILARITY}
+
+
+def motion_set(reduce=None, search=8, min_texture=1024, min_blocks=None, model='shift', max_zoom=None, max_rotation=None, tolerance=2.0):
     """The settings of the camera-motion estimator (a _lib.MotionSet; include/mydet.h has the rules).  reduce: None (by frame
     size: the smallest of 2, 4, 8 with max(H, W) <= 512 * reduce, else 8) or 2, 4, 8; search: 4 .. 16 reduced pixels;
     min_texture: the least SAD range of a block that counts; min_blocks: None (max(2, ceil(blocks / 8))) or the least number of
-    valid blocks of a frame.  ValueError for anything out of range; touches no device."""
+    valid blocks of a frame.  model: 'shift' (one integer shift per frame) or 'similarity' (shift, rotation and isotropic zoom,
+    mydet_motion_warp_frames_rgb_u8), whose fit takes max_zoom: None (1/8) or the largest |zoom - 1| of a valid frame, up to
+    1/4; max_rotation: None (7) or the largest rotation in degrees, up to 14; tolerance: the inlier distance in pixels, up to 16.
+    The three are stored as Q16 integers, round(v * 65536).  ValueError for anything out of range, and for a max_zoom, a
+    max_rotation or another tolerance with model 'shift'; touches no device."""
+    if model not in MOTION_MODELS:
+        raise ValueError(f"motion_set: model is 'shift' or 'similarity', got {model!r}")
+    def real(name, v, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 < float(v) <= hi:
+            raise ValueError(f'motion_set: 0 < {name} <= {hi} expected, got {v!r}')
+        q = int(round(float(v) * 65536))
+        if q < 1:
+            raise ValueError(f'motion_set: {name} of {v!r} is below 2^-16')
+        return q
+    fit = (real('tolerance', tolerance, 16.0), 0 if max_zoom is None else real('max_zoom', max_zoom, 0.25),
+           0 if max_rotation is None else real('max_rotation', max_rotation, 14.0))
+    if model == 'shift' and (max_zoom is not None or max_rotation is not None or fit[0] != 2 << 16):
+        raise ValueError("motion_set: max_zoom, max_rotation and tolerance belong to model='similarity'")
     def whole(name, v):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
             raise ValueError(f'motion_set: {name} is an integer, got {v!r}')
@@ -2103,6 +2145,9 @@ def motion_set(reduce=None, search=8, min_texture=1024, min_blocks=None):
         m.min_blocks = whole('min_blocks', min_blocks)
         if not 1 <= m.min_blocks <= _lib.MOTION_MAX_BLOCKS:
             raise ValueError(f'motion_set: min_blocks is None or 1 .. {_lib.MOTION_MAX_BLOCKS}, got {min_blocks!r}')
+    if model == 'similarity':                                        # the reserved words stay zero for the shift: today's struct
+        m.reserved[0] = _lib.MOTION_MODEL_SIMILARITY
+        m.reserved[1], m.reserved[2], m.reserved[3] = fit
     return m
 
 
@@ -2154,17 +2199,24 @@ def motion_state_views(state, frame_hw, set):
             'patches': state[:, o + nred:o + nred + npat].view(torch.uint8).view(S, geo['nb'], geo['P'], geo['P'])}
 
 
-def motion_frames(image, state, set, frames_per_stream=None, layout=None, out=None):
+def motion_frames(image, state, set, frames_per_stream=None, layout=None, out=None, inliers=False):
     """The camera motion of S streams x F frames (include/mydet.h: mydet_motion_frames_rgb_u8, where the rules are): per frame
     one integer shift against the frame before it, which for a stream's first frame is the last frame of the previous call
     (kept in `state`).  image: what the ops.draw_* functions take first, read only -- uint8 RGB frames [S*F,H,W,3] with
     packed pixels and any row and frame strides (layout None), or the planes of `layout` ('nv12', 'nv21', 'i420', 'yv12', 'p010',
     'i010') as in yuv420_to_rgb; frame f of stream s is frame s*F + f.  state: motion_state(...), updated in place; its row
     count is S.  frames_per_stream: F, checked against the batch when given.  Returns {'shift': int32 [S,F,4] (dx, dy, valid,
-    n_valid), 'blocks': int32 [S,F,nb,6] (cdx, cdy, smin, smax, fdx, fdy)} on the device; out: such a dict to write into."""
+    n_valid), 'blocks': int32 [S,F,nb,6] (cdx, cdy, smin, smax, fdx, fdy)} on the device; out: such a dict to write into.
+    With a set of model 'similarity' (mydet_motion_warp_frames_rgb_u8) the dict also holds 'warp': int32 [S,F,8] = (a, b, tx, ty,
+    s_q, deg_q, valid, n_inliers), the fitted model in Q16, which track_frames takes as warp=; 'shift' is then the motion of the
+    frame centre in whole pixels; inliers=True adds 'inliers': int32 [S,F,nb], the blocks the fit kept (a ValueError with
+    model 'shift', before any launch)."""
     what = 'motion_frames'
     if not isinstance(set, _lib.MotionSet):
         raise TypeError(f'{what}: set is a _lib.MotionSet (ops.motion_set), got {type(set).__name__}')
+    similarity = set.reserved[0] == _lib.MOTION_MODEL_SIMILARITY
+    if inliers and not similarity:
+        raise ValueError(f"{what}: inliers are the similarity model's (ops.motion_set(model='similarity'))")
     img, yuv, B = _image(what, image, layout, 'bt601', False, False)
     H, W = (img.shape[1:3] if yuv is None else img[0].shape[1:3])
     geo = motion_geometry((H, W), set)
@@ -2174,9 +2226,19 @@ def motion_frames(image, state, set, frames_per_stream=None, layout=None, out=No
         raise ValueError(f'{what}: {B} frames are not F frames of each of {S} streams')
     F = B // S
     dev = _same_device(what, img, [state])
-    out = out_planes(what, out, {'shift': ((S, F, 4), torch.int32), 'blocks': ((S, F, geo['nb'], 6), torch.int32)}, dev)
+    shapes = {'shift': ((S, F, 4), torch.int32), 'blocks': ((S, F, geo['nb'], 6), torch.int32)}
+    if similarity:
+        shapes['warp'] = ((S, F, 8), torch.int32)
+        if inliers:
+            shapes['inliers'] = ((S, F, geo['nb']), torch.int32)
+    out = out_planes(what, out, shapes, dev)
     nbytes = _lib.lib().mydet_motion_workspace_bytes(B, geo['H'], geo['W'], geo['k'], geo['R'])
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    if similarity:
+        _launch_on_image(what, img, yuv, 'mydet_motion_warp_frames_rgb_u8', 'mydet_motion_warp_frames_yuv420', S, ctypes.byref(set),
+                         _ptr(state), _ptr(ws), nbytes, _ptr(out['shift']), _ptr(out['warp']), _ptr(out['blocks']),
+                         _ptr(out['inliers']) if inliers else None)
+        return out
     _launch_on_image(what, img, yuv, 'mydet_motion_frames_rgb_u8', 'mydet_motion_frames_yuv420', S, ctypes.byref(set), _ptr(state),
                      _ptr(ws), nbytes, _ptr(out['shift']), _ptr(out['blocks']))
     return out
